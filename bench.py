@@ -1,20 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the Assign10 path-tracing pass on N MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[3], the one the metric is quoted on): scenes/cornell.xml packed by the
 reference host for 1920x1080, rays_per_pixel = 256 (16x16 lens grid), one progressive pass, depth 8 (eight
 bounces after the primary hit; the reference hard-codes five, A10 code.js:1829 -- `--bounces 5` measures that,
-and the default run reports it beside the headline in "depth5"), seeds s[id] = 1 + (mix32(id ^ 0x9E3779B9)
+and a --full run reports it beside the headline in "depth5"), seeds s[id] = 1 + (mix32(id ^ 0x9E3779B9)
 mod 2147483646) generated on the device.  One "step" is one such frame: initTrace .. 8 bounces .. copyToPixel,
 through mirt_render_first_pass: ONE fused launch that also resolves the pixels (round 4: no per-ray accumulator, 8 B per sample + 20 B per
-pixel of HBM traffic; --keep-acu: the accumulator written per ray as a progressive second pass would need it).  Beside the headline the
-default run reports the grid kernel (`grid_scene`: cornell_teapot3) and BASELINE configs 2 / 3 (`frames`), each with a roofline fraction and a
-bounded CPU baseline, and the same frame on the second numerics contract (`default_contract`: libmirt_default.so, in a child process) (--no-extras skips them).
+pixel of HBM traffic; --keep-acu: the accumulator written per ray as a progressive second pass would need it).
 Inputs (scene buffers, seeds) are resident in HBM before the timed region.
+
+A plain run sets up, warms up, times --steps steps and prints the line; `ms_per_step` is the wall time of one timed step.
+--dump-outputs DIR writes what the last timed step computed (the RGBA8 frame and the per-pixel radiance sums, as float32 .npy;
+a fixed, seeded sample of pixels at sizes beyond 64 MB) so that two builds can be compared output for output on identical inputs.
+--full adds what takes runs of its own beside the headline: a bounded CPU baseline and the reference's own kernels on the GPU
+(`cpu_baseline`, `reference_gpu_baseline`; --no-cpu skips them), the reference's depth (`depth5`; --no-depth5), and for cornell the
+grid kernel (`grid_scene`: cornell_teapot3) and BASELINE configs 2 / 3 (`frames`), each with a roofline fraction and a bounded CPU
+baseline, and the same frame on the second numerics contract (`default_contract`: libmirt_default.so, in a child process) (--no-extras skips these).
 
 N > 1: one process per GPU; the frame is cut into N contiguous row tiles (ray ids stay global, so the
 image is identical for every N); each step ends with the one real exchange of the path, an RCCL
@@ -61,6 +67,27 @@ def resolves_in_pass(rpp):
         return 256 % rpp == 0
     c = rpp // 256
     return rpp % 256 == 0 and c <= 32 and c & (c - 1) == 0
+
+
+def dump_outputs(out_dir, height, width, pixel, radiance=None, budget=64_000_000, sample=1 << 20):
+    """--dump-outputs: write the last timed step's outputs as float32 .npy files, so two builds can be compared output for output.
+    pixel: the RGBA8 frame (H*W*4 uint8); radiance: the per-pixel fp32 radiance sums (H*W*4 float32) or None.  A frame whose files
+    would exceed `budget` bytes is written as a fixed, seeded sample of `sample` pixels, the same ones in every run for a given size
+    (pixel_index.npy, float64)."""
+    npix = height * width
+    arrays = {"pixel": np.asarray(pixel, np.uint8).reshape(npix, 4).astype(np.float32)}
+    if radiance is not None:
+        arrays["radiance"] = np.asarray(radiance, np.float32).reshape(npix, 4)
+    if npix * 16 * len(arrays) <= budget:
+        arrays = {k: v.reshape(height, width, 4) for k, v in arrays.items()}
+    else:
+        idx = np.sort(np.random.default_rng(20150410).choice(npix, min(sample, npix), replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def csrc_sha256():
@@ -261,6 +288,11 @@ def main():
                     "frame without it -- the pass resolves its pixels itself, 8 B per sample + 20 B per pixel (SURVEY 8d)")
     ap.add_argument("--pmc-summary", default=None, help="pmc_summary.json of a rocprofv3 run of this command (profiles/run_profile.sh); default: the "
                     "newest one under profiles/ stamped with this source tree and workload.  Without one, `traffic` and `issue` are null")
+    ap.add_argument("--full", action="store_true", help="also measure what sits beside the headline, each in runs of its own: cpu_baseline and "
+                    "reference_gpu_baseline (--no-cpu skips them), depth5 (--no-depth5), grid_scene, frames and default_contract (--no-extras)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32): the RGBA8 frame and, on one GPU, the per-pixel fp32 radiance sums -- a fixed, seeded sample of pixels when "
+                    "the frame exceeds the size budget (pixel_index.npy then names them)")
     args = ap.parse_args()
     if args.rpp is None:
         args.rpp = 256 if args.scene == "cornell" else 16
@@ -362,6 +394,12 @@ def main():
     if use_dist:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt = float(dt_t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for its caller: the assembled RGBA8 frame and, on one GPU (rank 0 holds the whole frame), the radiance sums
+        pix = tiling.assemble(frame, sc.height, sc.width, world) if use_dist else tile[:sc.height * sc.width * 4]
+        rad = fr.radiance.read(np.float32) if world == 1 else None
+        names = dump_outputs(args.dump_outputs, sc.height, sc.width, pix.cpu().numpy(), rad)
+        log(f"dump-outputs: {', '.join(names)} -> {args.dump_outputs}")
 
     # N > 1: every rank's own kernel time and its gather's own event time (the all_gather includes waiting for the slowest rank), so that a
     # first run on N real GPUs is diagnosable from its one line: load imbalance shows in launch_ms, transport trouble in gather_ms
@@ -430,7 +468,7 @@ def main():
     }
     if per_rank:
         out["per_rank"] = per_rank
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(packed, log, args.bounces, sc.rpp)
         try:
             rg = reference_gpu_baseline(packed, log, args.bounces)
@@ -439,7 +477,7 @@ def main():
             rg = None
         if rg:
             out["reference_gpu_baseline"] = rg
-    if rank == 0 and world == 1 and args.bounces == 8 and not args.no_depth5 and fps_table:
+    if args.full and rank == 0 and world == 1 and args.bounces == 8 and not args.no_depth5 and fps_table:
         # the reference's own depth (five bounces), same frame, two untimed-warmup-free steps: reported beside the headline
         t5 = []
         for _ in range(2):
@@ -450,7 +488,7 @@ def main():
         out["depth5"] = {"launch_ms": round(float(np.mean(t5)), 3), "Msamples_per_s_kernel": round(fr.nrays / np.mean(t5) / 1e3, 1),
                          "flops_per_sample": fps_table[5], "frac": round(fps_table[5] * fr.nrays / (np.mean(t5) * 1e-3) / 1e12 / PEAK_VALU_TFLOPS, 4)}
     fr.release()
-    if rank == 0 and world == 1 and args.scene == "cornell" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and args.scene == "cornell" and not args.no_extras:
         # beside the headline: the grid kernel and BASELINE configs 2 / 3, each with its own roofline fraction and a bounded CPU baseline
         try:
             out["grid_scene"] = grid_scene_record(ctx, log, render, scene, not args.no_cpu)

@@ -23,6 +23,7 @@ OWN_SCENES = {"own_studio_48x36_r4": ("studio.xml", 48, 36, 4), "own_gems_48x36_
               "own_gems_64x48_r1": ("gems.xml", 64, 48, 1), "own_flat_32x24_r4": ("flat.xml", 32, 24, 4)}
 PAGE = os.path.join(ROOT, "tests", "scenes", "page")
 HOST = os.path.join(ROOT, "2015-raytracing_amd", "host")
+REFERENCE_DATA = os.path.join(GOLDEN, "reference_data.tar.gz")
 
 
 def pytest_configure(config):
@@ -33,6 +34,19 @@ def pytest_configure(config):
 def pkg():
     import __graft_entry__ as g
     return g.load_package()
+
+
+@pytest.fixture(scope="session")
+def ref_data(tmp_path_factory):
+    """The reference's data files (no code), stored with the fixtures and unpacked once per session: a10/scenes/*.xml and a10/tri/*.json
+    (Assign10's page), tri/*.json (the Assign04 / Assign07 meshes, the same files in both), mol/*.pdb (the Assign07 molecules the frame
+    fixtures use), and a10/ref_host_pack_96x64_r4.json: what the reference's own host code packs from each A10 scene at 96x64 x 4 rays
+    (oracle/gen/ref_host_dump.js <reference tree> <scene>.xml 96 64 4, one entry per scene)."""
+    import tarfile
+    d = tmp_path_factory.mktemp("reference_data")
+    with tarfile.open(REFERENCE_DATA) as t:
+        t.extractall(d)
+    return str(d)
 
 
 def load_fixture(name):

@@ -152,9 +152,8 @@ def test_restatement_reproduces_the_expectations_from_the_same_stream(name):
     check_against_expectation(name, res["reads"], res["buffers"]["acu"].tobytes(), res["buffers"]["seeds"].tobytes())
 
 
-@pytest.mark.skipif(not os.path.isdir(REFROOT), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", ["cornell_320x240_k2_p2", "cornell_teapot3_320x240_k1_p2", "threeLights_160x120_k3_p3"])
-def test_our_renderer_issues_the_same_launches_as_the_reference_host(name):
+def test_our_renderer_issues_the_same_launches_as_the_reference_host(name, ref_data):
     """host/renderer.js::GranularRenderer is our re-write of the sequence.  On the recorder, for the same scene file, it must issue the
     same launches in the same order as the reference's code.js did: kernel, dim, global, local, and for every launch the same scalar
     argument bytes and the same buffer sizes bound at launch time (buffer CONTENTS are compared by test_js_host.py)."""
@@ -173,7 +172,7 @@ def test_our_renderer_issues_the_same_launches_as_the_reference_host(name):
       g.release();
       console.log(JSON.stringify(rec.trace()));
     """
-    ours = json.loads(run_node("-e", js, HOST, f"{REFROOT}/Assign10-Path_Tracing/scenes/{scene}", str(w), str(h), str(k), str(passes)))
+    ours = json.loads(run_node("-e", js, HOST, os.path.join(ref_data, "a10", "scenes", scene), str(w), str(h), str(k), str(passes)))
     theirs, _ = CT.load_trace(CT.golden_prefix(name))
 
     def launches(t):

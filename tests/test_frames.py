@@ -17,8 +17,6 @@ from conftest import GOLDEN, HOST, PAGE, ROOT, bits
 CASES = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(GOLDEN, "frame_*.npz")))
 node = shutil.which("node")
 REF = "/root/reference"
-REF_TRI = {4: f"{REF}/Assign04-Triangle_Mesh/tri", 7: f"{REF}/Assign07-3D_uniform_grid_acceleration/tri"}
-REF_MOL = f"{REF}/Assign07-3D_uniform_grid_acceleration/mol"
 
 
 def fixture(name):
@@ -44,23 +42,20 @@ def test_a01_fixture_is_the_expected_sphere():
     assert (fx["pixel"][:, 3] == 255).all() and np.array_equal(fx["pixel"][:, 0], fx["pixel"][:, 1])
 
 
-def mesh_path(d, name):
+def mesh_path(d, name, ref_data=None):
+    """the job's input file: ours under tests/scenes/page, the reference's from the stored reference data (conftest.ref_data)"""
     if d["assign"] == 1:
         return "-"
     if "mol" in d:   # Assign07's molecule mode
-        p = os.path.join(PAGE, "mol", d["mol"]) if "own" in name else os.path.join(REF_MOL, d["mol"])
-        return p if os.path.exists(p) else None
-    p = os.path.join(PAGE, "tri", d["mesh"]) if "own" in name else os.path.join(REF_TRI[d["assign"]], d["mesh"])
-    return p if os.path.exists(p) else None
+        return os.path.join(PAGE, "mol", d["mol"]) if "own" in name else os.path.join(ref_data, "mol", d["mol"])
+    return os.path.join(PAGE, "tri", d["mesh"]) if "own" in name else os.path.join(ref_data, "tri", d["mesh"])
 
 
 @pytest.mark.skipif(node is None, reason="node is not installed")
 @pytest.mark.parametrize("name", CASES)
-def test_js_host_packs_frames_like_the_reference_host(name):
+def test_js_host_packs_frames_like_the_reference_host(name, ref_data):
     fx, d = fixture(name)
-    mp = mesh_path(d, name)
-    if mp is None:
-        pytest.skip("reference mesh not present (GPU box)")
+    mp = mesh_path(d, name, ref_data)
     r = subprocess.run([node, os.path.join(HOST, "cli.js"), "pack-frame", str(d["assign"]), mp, str(d["width"]), str(d["height"]),
                         str(d.get("n_slabs", 0))], capture_output=True)
     assert r.returncode == 0, r.stderr.decode()

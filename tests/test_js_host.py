@@ -68,15 +68,13 @@ def test_node_graph_replayed_passes(tmp_path):
     assert np.array_equal(bits(np.fromfile(out + ".radiance.f32", np.float32).reshape(-1, 4)), bits(A.radiance_sums(st.acu, 4)))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PAGE), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("scene", ["basic", "basic2", "cornell", "cornell_official", "cornell_teapot", "cornell_teapot2",
                                    "cornell_teapot3", "threeLights", "triangles", "twoLights"])
-def test_reference_scenes_load_unchanged(scene):
-    """scenes/*.xml and tri/*.json of the reference, read where they lie: our host and the reference's own host code
-    (run in a vm sandbox) must emit identical buffers."""
-    dump = os.path.join(os.path.dirname(HOST), "..", "oracle", "gen", "ref_host_dump.js")
-    want = json.loads(run_node(dump, "/root/reference", scene + ".xml", "96", "64", "4", cwd="/tmp"))
-    got = json.loads(run_node(os.path.join(HOST, "cli.js"), "pack", f"{REF_PAGE}/scenes/{scene}.xml", "96", "64", "4"))
+def test_reference_scenes_load_unchanged(scene, ref_data):
+    """scenes/*.xml and tri/*.json of the reference (the stored copies, conftest.ref_data): our host must emit the buffers the
+    reference's own host code (run in a vm sandbox by oracle/gen/ref_host_dump.js) emitted from them, as stored beside them."""
+    want = json.load(open(os.path.join(ref_data, "a10", "ref_host_pack_96x64_r4.json")))[scene]
+    got = json.loads(run_node(os.path.join(HOST, "cli.js"), "pack", os.path.join(ref_data, "a10", "scenes", scene + ".xml"), "96", "64", "4"))
     same_packed(want, got)
 
 
