@@ -22,7 +22,9 @@ SRC=("${HERE}/mirt_abi.cpp" "${HERE}/pt_kernels_granular.hip" "${HERE}/pt_kernel
 if [ -z "${MIRT_OUT:-}" ] && [ "${MIRT_SKIP_DEFAULT_CONTRACT:-0}" != 1 ]; then
     "${HIPCC}" "${FLAGS[@]/-fhip-fp32-correctly-rounded-divide-sqrt/-fno-hip-fp32-correctly-rounded-divide-sqrt}" -DPT_PLAIN_DIV=1 \
         -shared -o "${HERE}/../libmirt_default.so" "${SRC[@]}" "$@" &
+    default_pid=$!
 fi
 "${HIPCC}" "${FLAGS[@]}" -shared -o "${OUT}" "${SRC[@]}" "$@"
-wait
+# a bare `wait` returns 0 whatever the background build did: wait for that job by its pid, so set -e sees it fail
+if [ -n "${default_pid:-}" ]; then wait "${default_pid}"; fi
 echo "built ${OUT}"

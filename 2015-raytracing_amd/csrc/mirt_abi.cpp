@@ -903,7 +903,7 @@ int mirt_kernel_set_arg_buf(mirt_kernel* k, unsigned index, mirt_buf* buf) try {
 // sceneRender}, any number of {bouncePaths, closest-hit kernels, per-light block}, copyToPixel -- it runs the pass as ONE launch of
 // k_fusedPass (render_pass_impl) + the recorded copyToPixel.  Anything else (a different order, mixed buffers, a read / write / release /
 // other command in between) flushes the held enqueues one by one, unchanged.  See include/mirt.h for what the mode trades.
-static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh);
+static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes = 1, bool mark_start = true);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
 
 static bool same_f(const float* x, const float* y, int n) { return memcmp(x, y, (size_t)n * 4) == 0; }
@@ -1323,7 +1323,9 @@ static int fill_grid(mirt_ctx* ctx, const char* what, const mirt_grid* g, bool t
     return MIRT_OK;
 }
 
-static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh) {
+// passes > 1: that many progressive passes in one launch (mirt_render_passes), pass_index the first of them.  mark_start false: the profiling
+// interval goes on from the event an earlier pass of the same mirt_render_passes call recorded.
+static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes, bool mark_start) {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_pass: unknown context");
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: descriptor size mismatch");
     if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: empty image");
@@ -1356,6 +1358,9 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh) 
     A.row0 = d->row0; A.nrows = nrows; A.bounces = d->bounces;
     A.n_lights = d->n_lights;
     A.fresh = fresh ? 1u : 0u;
+    A.passes = passes;
+    // the frame after the last pass: 1 / (rpp * passes so far), A10 code.js:1412
+    const float res_m = (float)(1.0 / ((double)d->rays_per_pixel * ((double)d->pass_index + (double)(passes - 1u))));
     int rc;
     if (d->spheres && (rc = fill_grid(ctx, "spheres", d->spheres, false, true, &A.sets[A.n_sets++]))) return rc;
     if (d->triangles && (rc = fill_grid(ctx, "triangles", d->triangles, true, true, &A.sets[A.n_sets++]))) return rc;
@@ -1402,8 +1407,8 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh) 
         A.resolve = 1u;
         A.pixel = d->pixel ? d->pixel->ptr : nullptr;
         A.radiance = d->radiance ? d->radiance->ptr : nullptr;
-        A.res_m = (float)(1.0 / ((double)d->rays_per_pixel * (double)d->pass_index));  // A10 code.js:1412
-        if (ctx->res_m_override == ctx->res_m_override) A.res_m = ctx->res_m_override;   // (not a NaN: try_fuse_pass hands over the recorded copyToPixel's own factor)
+        A.res_m = res_m;
+        if (passes == 1u && ctx->res_m_override == ctx->res_m_override) A.res_m = ctx->res_m_override;   // (not a NaN: try_fuse_pass hands over the recorded copyToPixel's own factor)
         A.chunks = pt::fused_chunks(d->rays_per_pixel);
         if (A.chunks > 1u && !A.radiance) {   // a pixel of more than 256 rays: its sums travel from launch to launch through memory (FusedArgs::chunks)
             if ((rc = ensure_scratch(ctx, (size_t)npix * 16))) return rc;
@@ -1418,7 +1423,7 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh) 
         pt::launch_lensDraws(ctx->stream, A.seeds, ctx->scratch, d->width, d->height, d->width, d->height, d->row0, nrows);
         A.uv = ctx->scratch;
     }
-    if (ctx->profiling && !ctx->capturing) HIPCHK(ctx, hipEventRecord(ctx->pe[0], ctx->stream));
+    if (ctx->profiling && !ctx->capturing && mark_start) HIPCHK(ctx, hipEventRecord(ctx->pe[0], ctx->stream));
     bool optimistic = pt::fused_fast_available() && !ctx->force_exact;
     for (uint32_t i = 0; i < A.n_sets; ++i) optimistic = optimistic && A.sets[i].fast_ok != 0;
     if (optimistic) {
@@ -1463,8 +1468,8 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh) 
     }
     if (ctx->profiling && !ctx->capturing) HIPCHK(ctx, hipEventRecord(ctx->pe[1], ctx->stream));
     if (!resolve_in_pass && (d->pixel || d->radiance)) {
-        float m = (float)(1.0 / ((double)d->rays_per_pixel * (double)d->pass_index));  // A10 code.js:1412
-        if (ctx->res_m_override == ctx->res_m_override) m = ctx->res_m_override;
+        float m = res_m;
+        if (passes == 1u && ctx->res_m_override == ctx->res_m_override) m = ctx->res_m_override;
         pt::launch_copyToPixel(ctx->stream, d->pixel ? d->pixel->ptr : nullptr, A.acu, m, (uint32_t)npix, A.rpp, (uint32_t)npix,
                                d->radiance ? d->radiance->ptr : nullptr);
     }
@@ -1477,6 +1482,36 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh) 
 
 int mirt_render_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try { if (live_has(ctx)) FLUSH_PENDING(ctx); return render_pass_impl(ctx, d, false); } MIRT_CATCH("mirt_render_pass", return MIRT_E_DEVICE)
 int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try { if (live_has(ctx)) FLUSH_PENDING(ctx); return render_pass_impl(ctx, d, true); } MIRT_CATCH("mirt_render_first_pass", return MIRT_E_DEVICE)
+
+// n_passes progressive passes in one call: the same results as mirt_render_first_pass (MIRT_PASSES_FRESH) or mirt_render_pass at pass_index,
+// then mirt_render_pass at pass_index + 1 .. pass_index + n_passes - 1 -- one launch (per block of a pixel's rays) that runs every sample through
+// all of them (pt_kernels_fused.hip k_fusedPass MULTI).
+int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes, uint32_t flags) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_passes: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_render_passes");
+    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: descriptor size mismatch");
+    if (flags & ~MIRT_PASSES_FRESH) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: unknown flags 0x%x", flags);
+    if (n_passes < 1u || n_passes > MIRT_MAX_PASSES_PER_CALL)
+        return fail(ctx, MIRT_E_ARG, "mirt_render_passes: n_passes %u outside 1..%u (one launch lasts about n_passes single passes)", n_passes, MIRT_MAX_PASSES_PER_CALL);
+    if (d->pass_index > UINT32_MAX - (n_passes - 1u)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: pass_index %u + %u passes overflows", d->pass_index, n_passes);
+    const bool fresh = (flags & MIRT_PASSES_FRESH) != 0u;
+    // rays_per_pixel 1 couples the rows of a pass through seeds[col] (A10 code.cl:429): a lane cannot run its ray on alone, so the call queues
+    // n_passes ordinary passes -- and those need the accumulator between them
+    const bool single = d->rays_per_pixel == 1u;
+    if (!d->acu && !(fresh && !single && ctx->inpass_resolve && pt::fused_resolves(d->rays_per_pixel, d->pixel || d->radiance)))
+        return fail(ctx, MIRT_E_ARG, "mirt_render_passes: acu may only be NULL with MIRT_PASSES_FRESH, a pixel or radiance buffer and rays_per_pixel > 1 dividing 256 "
+                                     "or 256 times a power of two up to 32, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", fresh ? "fresh" : "NOT fresh",
+                    d->rays_per_pixel, d->pixel || d->radiance ? "" : ", no output buffer");
+    if (!single) return render_pass_impl(ctx, d, fresh, n_passes);
+    mirt_pass_desc p = *d;
+    for (uint32_t i = 0; i < n_passes; ++i) {
+        p.pass_index = d->pass_index + i;
+        const int rc = render_pass_impl(ctx, &p, fresh && i == 0u, 1u, i == 0u);
+        if (rc) return rc;
+    }
+    return MIRT_OK;
+} MIRT_CATCH("mirt_render_passes", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_fusion(mirt_ctx* ctx, int level) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_fusion: unknown context");

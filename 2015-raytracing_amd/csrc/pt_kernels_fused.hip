@@ -514,7 +514,30 @@ PT_DEV void resolve_block(const FusedArgs& A, const float* rows, uint64_t first,
 // WAVES != 0: an occupancy variant of the optimistic grid kernels.  PT_FUSED_WAVES_GRIDS waves per SIMD only exist while a block's LDS lets as
 // many blocks share a CU (26 880 B at six); a scene with bigger cell tables gets five blocks at best, and for it the 96-register build --
 // no scratch -- is the better kernel: launch_fused picks by the bytes it is about to ask for.
-template <bool FAST, int GRIDS, int WAVES = 0>
+// The kernel arguments through a pointer the compiler cannot see through, made anew by every trip of the MULTI kernel's pass loop.  As
+// loop-invariant loads, the arguments the path reads (camera, bounds, lights, sets ...) were hoisted out of the loop and kept alive across the
+// whole path: 15 -> 51 spilled SGPRs and 0 -> 10 spilled VGPRs in the headline kernel.  The pointer stays in the kernarg address space, so the
+// loads stay scalar.  (k_fusedPass's FusedArgs is its first argument: offset 0 of the kernarg segment.)
+PT_DEV const FusedArgs& opaque_args() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const FusedArgs*)p;
+}
+// MULTI: FusedArgs::passes progressive passes in one launch (mirt_render_passes).  Passes interact only through a ray's own seed and its own
+// accumulator, so each lane runs its sample through every pass in a row: the seed stays in a register, the accumulator in the park rows, and
+// both are written once at the end -- bit-identical to that many separate passes.  The unit of the optimistic / exact pair is the same as in
+// one pass (a sample, or with in-pass resolve a block): a sample that left the guard windows in ANY pass is handed over, and the exact kernel
+// re-runs all of its passes from the seed and accumulator it started with, which nothing of it has overwritten.
+// MULTI 1: the plain loop, every pass walks its path from the primary ray.  MULTI 2: PRIMARY-HIT REUSE -- for rays_per_pixel > 1 segment 0 is the
+// same in every pass (the lens grid is un-jittered and initTrace, the closest hit and lightRender draw nothing from the seed), so passes after the
+// first take its vertex (p, n, material) and the light lightRender added, if any, from eight LDS rows pass 0 left (kReuseWords) instead of tracing
+// the primary ray again.  (Its guard-window verdict is already in `defer`, which every pass ORs into.)
+constexpr int kReuseWords = 8;
+PT_DEV float* reuse_rows() {   // [word][lane]: p.xyz, n.xyz, material id, the light lightRender added (-1: none)
+    __shared__ __attribute__((aligned(16))) float reuse_mem[kReuseWords][256];
+    return &reuse_mem[0][threadIdx.x];
+}
+template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0>
 __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_GRIDS : (FAST ? PT_FUSED_WAVES_FAST : PT_FUSED_WAVES))) k_fusedPass(const FusedArgs A, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     const uint64_t n_local = (uint64_t)A.nrows * A.width * A.rpp;
     stage_block<FAST, GRIDS>(A);
@@ -567,7 +590,15 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
     park.put(0, acc.x); park.put(1, acc.y); park.put(2, acc.z); park.put(3, acc.w);
     park.put(4, 1.0f); park.put(5, 1.0f); park.put(6, 1.0f);
 #endif
-    Ray ray = primary_ray(A, lid);
+  for (uint32_t pass = 0;;) {   // (one trip unless MULTI)
+    const FusedArgs& P = MULTI ? opaque_args() : A;
+    if (MULTI && FAST) {   // the ray id from the thread index, as at the end of the path (see there): kept across the passes it cost spills
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        const uint64_t again = (uint64_t)wg_block(P) * 256u + t, n = (uint64_t)P.nrows * P.width * P.rpp;
+        lid = again < n ? (uint32_t)again : (uint32_t)(n - 1u);
+    }
+    Ray ray = primary_ray(P, lid);
     Poi poi;
     poi.p = mk3(0.0f, 0.0f, 0.0f);
     poi.n = mk3(0.0f, 0.0f, 0.0f);
@@ -576,7 +607,7 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
 
     // segment 0 is the primary ray; segments 1..bounces start with bouncePaths (code.js:1829-1846)
     pt_count(PC_WAVES);
-    for (uint32_t seg = 0; seg <= A.bounces; ++seg) {
+    for (uint32_t seg = 0; seg <= P.bounces; ++seg) {
         pt_count(PC_SEGMENTS);
         if (seg > 0) {
             if (poi.matId >= 0) {
@@ -591,11 +622,32 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
             }
         }
         if (PT_COUNT && !(ray.mint == ray.maxt)) pt_count(PC_SEG_LANES, true);
-        closest_all<FAST, GRIDS, Park>(A, ray, poi, park, defer);
+        bool reused = false;   // MULTI 2, a pass after the first: segment 0 as pass 0 left it (wave-uniform: every lane of the wave skips the walk)
+#if PT_PARK_LDS
+        if constexpr (MULTI == 2) {
+            float* const reuse = reuse_rows();
+            if (seg == 0 && pass != 0u) {
+                poi.p = mk3(reuse[0], reuse[256], reuse[512]);
+                poi.n = mk3(reuse[768], reuse[1024], reuse[1280]);
+                poi.matId = (int32_t)__float_as_uint(reuse[1536]);
+                const int32_t lit = (int32_t)__float_as_uint(reuse[1792]);
+                if (lit >= 0) {
+                    const f3 irr = norm3(ld3(P.lights[lit].light + 6));
+                    park.acc_add(irr.x, irr.y, irr.z);
+                }
+                if (PT_PARK_PN_FOR(GRIDS)) park.put_pn(poi);
+                reused = true;
+            } else if (seg == 0) {
+                reuse[1792] = __uint_as_float(0xFFFFFFFFu);   // pass 0: no light added (yet)
+            }
+        }
+#endif
+      if (MULTI != 2 || !reused) {
+        closest_all<FAST, GRIDS, Park>(P, ray, poi, park, defer);
         if (seg == 0) {
-            for (uint32_t l = 0; l < A.n_lights; ++l) {  // lightRender (code.cl:600-629), primary segment only
+            for (uint32_t l = 0; l < P.n_lights; ++l) {  // lightRender (code.cl:600-629), primary segment only
                 if (ray.mint == ray.maxt) continue;
-                const LightArgs& L = A.lights[l];
+                const LightArgs& L = P.lights[l];
                 f3 irr = norm3(ld3(L.light + 6));
                 if (!light_visible(ray, ld3(L.light), ld3(L.light + 3), L.light[9])) continue;
                 ray.mint = PT_INF;
@@ -603,13 +655,28 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
                 poi.matId = -1;
 #if PT_PARK_LDS
                 park.acc_add(irr.x, irr.y, irr.z);
+                if constexpr (MULTI == 2) reuse_rows()[1792] = __uint_as_float(l);
 #else
                 acc.x += irr.x; acc.y += irr.y; acc.z += irr.z; acc.w += 1.0f;
 #endif
             }
         }
-        direct_all<FAST, GRIDS, Park>(A, poi, seed, acc, park, defer);
+#if PT_PARK_LDS
+        if constexpr (MULTI == 2) if (seg == 0) {   // pass 0: keep segment 0 for the passes after it
+            float* const reuse = reuse_rows();
+            reuse[0] = poi.p.x; reuse[256] = poi.p.y; reuse[512] = poi.p.z;
+            reuse[768] = poi.n.x; reuse[1024] = poi.n.y; reuse[1280] = poi.n.z;
+            reuse[1536] = __uint_as_float((uint32_t)poi.matId);
+        }
+#endif
+      }
+        direct_all<FAST, GRIDS, Park>(P, poi, seed, acc, park, defer);
     }
+    if (!MULTI || ++pass == A.passes) break;
+#if PT_PARK_LDS
+    park.put(4, 1.0f); park.put(5, 1.0f); park.put(6, 1.0f);   // the next pass's path starts unattenuated; the accumulator goes on
+#endif
+  }
 
     if (FAST) {
         // the ray id again, from the thread index (one sample per thread in this kernel): re-deriving it here costs a few instructions,
@@ -670,6 +737,18 @@ __global__ void __launch_bounds__(256) k_deferCount(const uint32_t* mask, uint32
     for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
+// Several passes in one launch: primary-hit reuse (MULTI 2) where it pays, the plain loop (MULTI 1) elsewhere.  4 passes, device events, medians of
+// 5 alternating repetitions (profiles/multipass/multipass_ab.json): cornell 1080p x 256, depth 8 (single-cell sets) 96.66 ms per pass with reuse, 98.45 plain
+// (101.94 as ordinary passes); cornell_teapot3 1080p x 16, depth 5 (grid meshes) 24.52 with reuse (27.16 forced to 6 waves: its 8 LDS rows cost the
+// grid kernel a block per CU, and it spills 71 VGPRs) against 20.36 plain (19.89 ordinary).  So: reuse for scenes without grids only.
+// MIRT_MULTIPASS_REUSE=1 / 0 forces one or the other -- an A/B switch, read per launch so that one process can alternate them (profiles/multipass_bench.py).
+static bool multipass_reuse(bool grids) { const char* e = getenv("MIRT_MULTIPASS_REUSE"); return e && e[0] ? e[0] != '0' : !grids; }
+template <bool FAST, int GRIDS, int WAVES = 0>
+static void launch_pass(const dim3& grid, size_t lds, hipStream_t s, const FusedArgs& b, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
+    if (b.passes > 1u && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    else if (b.passes > 1u) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    else hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+}
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     const uint64_t n = redo_mask ? redo_words : (uint64_t)a.nrows * a.width * a.rpp;
     if (!n) return;
@@ -709,18 +788,21 @@ void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_
     if (fast) {
         // LDS is handed out in 1280-byte granules, 128 of them per CU: the blocks per CU this launch can have, and the waves per SIMD worth compiling for
         static const int force_waves = [] { const char* e = getenv("MIRT_GRID_WAVES"); return e ? atoi(e) : 0; }();   // A/B and test switch
-        const size_t fixed = sizeof(float) * ((size_t)PT_PARK_WORDS(1) * 256u + kLensTab);   // the grid kernels' static LDS: parked state, lens table
+        const size_t fixed = sizeof(float) * ((size_t)PT_PARK_WORDS(1) * 256u + kLensTab   // the grid kernels' static LDS: parked state, lens table
+                                              + (b.passes > 1u && multipass_reuse(grids) ? (size_t)kReuseWords * 256u : 0u));   // (and segment 0's rows: MULTI 2)
         const size_t want = grids && staged ? lds : lds2, granules = (want + fixed + 1279u) / 1280u;
+        // (several passes in one launch pick the same way: the 5-wave build, spill-free, is slower there too -- cornell_teapot3 1080p x 16, 4 passes,
+        // plain loop: 21.12 ms per pass against 20.29 at 6 waves with 39 spilled VGPRs, profiles/multipass/multipass_bench_{5,6}waves_grid.json)
         const bool five = force_waves ? force_waves == 5 : (granules ? 128u / granules : 8u) < (unsigned)PT_FUSED_WAVES_GRIDS;
-        if (grids && staged && five) hipLaunchKernelGGL((k_fusedPass<true, 1, 5>), grid, dim3(256), lds, s, b, defer_mask, (const uint32_t*)nullptr, 0u);
-        else if (grids && staged) hipLaunchKernelGGL((k_fusedPass<true, 1>), grid, dim3(256), lds, s, b, defer_mask, (const uint32_t*)nullptr, 0u);
-        else if (grids && five) hipLaunchKernelGGL((k_fusedPass<true, 2, 5>), grid, dim3(256), lds2, s, b, defer_mask, (const uint32_t*)nullptr, 0u);
-        else if (grids) hipLaunchKernelGGL((k_fusedPass<true, 2>), grid, dim3(256), lds2, s, b, defer_mask, (const uint32_t*)nullptr, 0u);
-        else hipLaunchKernelGGL((k_fusedPass<true, 0>), grid, dim3(256), lds_tri, s, b, defer_mask, (const uint32_t*)nullptr, 0u);
+        if (grids && staged && five) launch_pass<true, 1, 5>(grid, lds, s, b, defer_mask, nullptr, 0u);
+        else if (grids && staged) launch_pass<true, 1>(grid, lds, s, b, defer_mask, nullptr, 0u);
+        else if (grids && five) launch_pass<true, 2, 5>(grid, lds2, s, b, defer_mask, nullptr, 0u);
+        else if (grids) launch_pass<true, 2>(grid, lds2, s, b, defer_mask, nullptr, 0u);
+        else launch_pass<true, 0>(grid, lds_tri, s, b, defer_mask, nullptr, 0u);
     } else {
-        if (grids && staged) hipLaunchKernelGGL((k_fusedPass<false, 1>), grid, dim3(256), lds, s, b, (uint32_t*)nullptr, redo_mask, redo_words);
-        else if (grids) hipLaunchKernelGGL((k_fusedPass<false, 2>), grid, dim3(256), lds2, s, b, (uint32_t*)nullptr, redo_mask, redo_words);
-        else hipLaunchKernelGGL((k_fusedPass<false, 0>), grid, dim3(256), 0, s, b, (uint32_t*)nullptr, redo_mask, redo_words);
+        if (grids && staged) launch_pass<false, 1>(grid, lds, s, b, nullptr, redo_mask, redo_words);
+        else if (grids) launch_pass<false, 2>(grid, lds2, s, b, nullptr, redo_mask, redo_words);
+        else launch_pass<false, 0>(grid, 0, s, b, nullptr, redo_mask, redo_words);
     }
 }
 bool fused_fast_available() { return PT_EXACT_FAST_DIV != 0; }

@@ -104,6 +104,10 @@ struct FusedArgs {
     uint32_t chunks;         // 1, or rpp / 256
     uint32_t chunk;          // this launch's c
     uint32_t chunk_bits;     // redo mode: the bits of a 32-block mask word that are blocks of this launch (all ones when chunks == 1)
+    // Progressive passes in ONE launch (mirt_render_passes): every sample runs `passes` passes in a row, its seed and accumulator carried in the
+    // kernel, and is written once at the end; `fresh` applies to the first of them, `res_m` to the frame after the last.  > 1 picks the MULTI
+    // instantiations of k_fusedPass; 0 and 1 run the single-pass kernels, which never read it.
+    uint32_t passes;
 };
 // whether a pass with these arguments resolves inside the kernel: whole pixels per block (or whole blocks per pixel, see FusedArgs::chunks) and
 // somewhere to put the result.  A frame's first pass may then do without `acu`; a later pass reads and writes it as ever -- the block's LDS holds the

@@ -7,6 +7,7 @@
 // in one launch (queue.renderPass).  Both produce bit-identical frames.
 "use strict";
 let { webcl } = require("./webcl.js");
+const { MAX_PASSES_PER_CALL } = require("./webcl.js");
 const scene = require("./scene.js");
 // tests point the drivers at another implementation of the same object model (./webcl_record.js) to compare call streams
 function setWebCL(impl) { webcl = impl; }
@@ -270,20 +271,37 @@ class FusedRenderer {
     if (opt.seeds) this.q.enqueueWriteBuffer(this.seeds, false, 0, this.nrays * 4, opt.seeds.subarray(first, first + this.nrays), []);
     else this.q.seedFill(this.seeds, first, this.nrays, opt.seedBase || 0);
     // not zeroed: the first pass initialises it (firstPass below).  opt.keepAcu === false: a one-pass frame without the 16 bytes per ray -- the pass
-    // resolves its pixels itself (mirt_render_first_pass with acu == NULL: rays_per_pixel must divide 256 or be 256 times a power of two up to 32, and there is no second pass)
+    // resolves its pixels itself (mirt_render_first_pass with acu == NULL: rays_per_pixel must divide 256 or be 256 times a power of two up to 32, and there is no second
+    // pass) -- or, opt.passesInOneLaunch, a frame of every pass in one call (executePasses)
     this.acu = opt.keepAcu === false ? null : this.ctx.createBuffer(webcl.MEM_READ_WRITE, this.nrays * 16);
     this.pixel = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 4);
     this.radiance = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
     this.passes = 1;
   }
-  executeRender(bounces) {
+  passDesc(bounces) {
     const p = this.p, d = this.dev;
-    this.q.renderPass({ width: p.width, height: p.height, raysPerPixel: p.rays_per_pixel, row0: this.row0, nrows: this.nrows,
+    return { width: p.width, height: p.height, raysPerPixel: p.rays_per_pixel, row0: this.row0, nrows: this.nrows,
       bounces: bounces === undefined ? 5 : bounces, passIndex: this.passes, cam: p.cam, sceneBounds: p.bounds,
       focalLength: p.focal_length, lensRad: p.lens_rad, spheres: d.sph, triangles: d.tri, meshes: d.meshes, lights: p.lights,
       material: d.material, seeds: this.seeds, acu: this.acu, pixel: this.pixel, radiance: this.radiance,
-      firstPass: this.passes === 1 });   // preRender's initAcu (code.js:1078-1099) folded into the frame's first pass
+      firstPass: this.passes === 1 };   // preRender's initAcu (code.js:1078-1099) folded into the frame's first pass
+  }
+  executeRender(bounces) {
+    this.q.renderPass(this.passDesc(bounces));
     this.passes++;
+  }
+  // n passes in one call (mirt_render_passes): the frame after the last of them, as n executeRender calls would leave it.  Starting the frame
+  // it needs no accumulator where the passes resolve their own pixels (keepAcu false).  A call runs at most MAX_PASSES_PER_CALL passes: with the
+  // accumulator kept, more are split into calls of that many (the frame is the same); without it a frame cannot go on after its first call
+  executePasses(n, bounces) {
+    if (!this.acu && n > MAX_PASSES_PER_CALL)
+      throw new Error(`${n} passes in one launch without a per-ray accumulator: at most ${MAX_PASSES_PER_CALL} (MIRT_MAX_PASSES_PER_CALL); keep the accumulator to split them over calls`);
+    for (let left = n; left > 0; ) {
+      const k = Math.min(left, MAX_PASSES_PER_CALL);
+      this.q.renderPasses(this.passDesc(bounces), k);
+      this.passes += k;
+      left -= k;
+    }
   }
   readPixels() { const o = new Uint8ClampedArray(this.npix * 4); this.q.enqueueReadBuffer(this.pixel, false, 0, o.length, o, []); this.q.finish(); return o; }
   readRadiance() { const o = new Float32Array(this.npix * 4); this.q.enqueueReadBuffer(this.radiance, false, 0, o.byteLength, o, []); this.q.finish(); return o; }
@@ -317,7 +335,8 @@ function renderTiled(packed, nDevices, passes, opt) {
   const live = tiles.filter((t) => t);
   const q0 = live[0].q;
   q0.timerStart();
-  for (let p = 0; p < passes; p++) live.forEach((t) => t.executeRender(opt.bounces));
+  if (opt.passesInOneLaunch) live.forEach((t) => t.executePasses(passes, opt.bounces));   // one call per tile, then the gather
+  else for (let p = 0; p < passes; p++) live.forEach((t) => t.executeRender(opt.bounces));
   const npix = packed.width * packed.height;
   const root = group.contexts[0];
   const frame = root.createBuffer(webcl.MEM_READ_WRITE, npix * 4), rad = root.createBuffer(webcl.MEM_READ_WRITE, npix * 16);
@@ -368,9 +387,11 @@ function renderFile(file, width, height, rpp, passes, opt) {
     if (opt.sceneObject) opt.sceneObject.keepSoups = true;
     try { return renderTiled(packed, opt.gpus, passes, opt); } finally { if (ownCtx) ownCtx.release(); }
   }
+  if (opt.passesInOneLaunch && opt.granular) throw new Error("passes in one launch are the fused pass's (mirt_render_passes): not with the kernel-by-kernel host");
   const R = opt.granular ? new GranularRenderer(packed, opt) : new FusedRenderer(packed, opt);
   R.q.timerStart();
-  for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
+  if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces);
+  else for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
   const ms = R.q.timerStopMs();
   const res = { pixel: R.readPixels(), radiance: opt.granular ? radianceSums(R.readAcu(), rpp) : R.readRadiance(), ms: ms,
                 device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: R.ctx.fusedPasses ? R.ctx.fusedPasses() : 0 };

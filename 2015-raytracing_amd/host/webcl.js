@@ -49,6 +49,8 @@ function wrap(f) {  // native errors -> WebCL-style exceptions
   }
 }
 
+const MAX_PASSES_PER_CALL = 64;   // MIRT_MAX_PASSES_PER_CALL (include/mirt.h)
+
 const C = {
   // values follow the OpenCL 1.1 / WebCL 1.0 enumerants
   PLATFORM_PROFILE: 0x0900, PLATFORM_VERSION: 0x0901, PLATFORM_NAME: 0x0902, PLATFORM_VENDOR: 0x0903, PLATFORM_EXTENSIONS: 0x0904,
@@ -170,6 +172,13 @@ class WebCLCommandQueue {
       pixel: desc.pixel ? desc.pixel.h : undefined, radiance: desc.radiance ? desc.radiance.h : undefined,
     });
     wrap(() => native().renderPass(this.ctx.h, d));
+  }
+  // n passes from desc.passIndex on in one call (mirt_render_passes): the frame after the last of them; desc.firstPass starts the frame.
+  // At most MAX_PASSES_PER_CALL (checked here: the addon reads the count as a uint32, which would wrap)
+  renderPasses(desc, n) {
+    if (!Number.isInteger(n) || n < 1 || n > MAX_PASSES_PER_CALL)
+      throw new WebCLException("INVALID_VALUE", "renderPasses: the pass count is an integer in 1.." + MAX_PASSES_PER_CALL + " (MIRT_MAX_PASSES_PER_CALL), not " + n);
+    this.renderPass(Object.assign({}, desc, { nPasses: n }));
   }
   // ---- extension: the host's grid builders on the device (mirt_grid_build / mirt_grid_gather_*) ----
   // primsF64: a Float64Array (uploaded here) or a WebCLBuffer that already holds the fp64 soup (meshIngest) with `count` primitives
@@ -307,4 +316,4 @@ const webcl = Object.assign({
 }, C);
 
 // `window.WebCL` is only tested for existence by the reference (A10 code.js:468); `webcl` is the entry object.
-module.exports = { webcl, WebCL: C, WebCLException };
+module.exports = { webcl, WebCL: C, WebCLException, MAX_PASSES_PER_CALL };

@@ -58,6 +58,8 @@ class _PassDesc(C.Structure):
 
 _lib = None
 
+PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
+
 # name -> (restype, argtypes): every symbol include/mirt.h declares
 SYMBOLS = {
     "mirt_device_count": (C.c_int, []),
@@ -87,6 +89,7 @@ SYMBOLS = {
     "mirt_enqueue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "mirt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc)]),
     "mirt_render_first_pass": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc)]),
+    "mirt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_ctx_set_exact_only": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_set_fusion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -396,6 +399,11 @@ class Context:
         """fresh: the frame's first pass with initAcu folded in (mirt_render_first_pass): acu is not read."""
         f = lib().mirt_render_first_pass if fresh else lib().mirt_render_pass
         self._chk(f(self.h, C.byref(desc)))
+
+    def render_passes(self, desc, n_passes, fresh=False):
+        """n_passes progressive passes from desc.pass_index on in one call (mirt_render_passes); fresh: the first of them starts the frame
+        (MIRT_PASSES_FRESH: acu is not read, and may be None where the passes resolve their own pixels)."""
+        self._chk(lib().mirt_render_passes(self.h, C.byref(desc), int(n_passes), PASSES_FRESH if fresh else 0))
 
     def destroy(self):
         if self.h:

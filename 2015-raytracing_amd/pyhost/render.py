@@ -201,7 +201,7 @@ class FusedRenderer:
     def __init__(self, ctx, scene, seeds=None, seed_base=0, row0=0, nrows=None, want_radiance=True, keep_acu=True):
         """nrows None: the whole image from row0 = 0.  nrows == 0 is an EMPTY tile (more ranks than rows): it owns minimal buffers and
         its passes do nothing -- it is not the whole frame.
-        keep_acu False: no per-ray accumulator at all (16 B per ray never allocated); only a frame's first pass can then run, with
+        keep_acu False: no per-ray accumulator at all (16 B per ray never allocated); only a frame's first pass (or first execute_passes) can then run, with
         rays_per_pixel dividing 256, or 256 times a power of two up to 32 (1024, 4096): the pass resolves its pixels itself
         (mirt_render_first_pass with acu == NULL)."""
         self.ctx, self.s = ctx, scene
@@ -235,6 +235,17 @@ class FusedRenderer:
                                row0=self.row0, nrows=self.nrows)
         self.ctx.render_pass(d, fresh=fresh)
         self.passes += 1
+
+    def execute_passes(self, n, bounces=5, fresh=False):
+        """n progressive passes in one call (mirt_render_passes): the frame after the last of them, as n execute_render calls would leave it.
+        fresh: the first of them starts the frame; then keep_acu False is enough where the passes resolve their own pixels."""
+        if not self.nrays:
+            self.passes += n
+            return
+        d = self.dev.pass_desc(self.seeds, self.acu, self.pixel, self.radiance, pass_index=self.passes, bounces=bounces,
+                               row0=self.row0, nrows=self.nrows)
+        self.ctx.render_passes(d, n, fresh=fresh)
+        self.passes += n
 
     def release(self):
         for b in (self.seeds, self.acu, self.pixel, self.radiance):

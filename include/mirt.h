@@ -199,6 +199,22 @@ MIRT_API int mirt_render_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
  * reference's one chain of additions, cut at multiples of 256 and carried through memory at 16 B per pixel and launch instead of 16 B
  * per ray.  `acu` may be NULL there too; results are bit-identical. */
 MIRT_API int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
+/* Several progressive passes in ONE call (A10 code.js:1806-1853: executeRender, executeCopyToPixel, passes++ -- n_passes times).  Results equal,
+ * bit for bit in every buffer the caller passes (seeds, acu if given, pixel, radiance), this sequence:
+ *   mirt_render_first_pass (flags & MIRT_PASSES_FRESH) or mirt_render_pass, at desc->pass_index;
+ *   then mirt_render_pass at pass_index + 1 .. pass_index + n_passes - 1.
+ * Pixel and radiance are those of the last pass (tone factor 1 / (rays_per_pixel * (pass_index + n_passes - 1))).  Passes interact only through a
+ * ray's own seed and its own accumulator, so one launch runs every sample through all n_passes passes, the accumulator on chip, and writes the
+ * seeds (and `acu`) once: a multi-pass frame needs no per-ray accumulator and moves none between the passes.
+ * `acu` may be NULL exactly where a first pass may do without it: MIRT_PASSES_FRESH, a pixel or radiance buffer, rays_per_pixel dividing 256 or 256
+ * times a power of two up to 32 (and MIRT_INPASS_RESOLVE not 0) -- except rays_per_pixel 1, whose rows are coupled through seeds[col] (A10
+ * code.cl:429): the call then queues n_passes ordinary passes and needs `acu`.  NULL elsewhere is MIRT_E_ARG.  n_passes is 1..64 (one launch lasts
+ * about n_passes single passes); row tiles and global ray ids work as in mirt_render_pass.  mirt_pass_deferred counts the samples (blocks) handed
+ * to the exact kernel in the same unit as for one pass -- such a sample re-runs all of its passes; mirt_pass_timing covers the whole call.
+ * Not while capturing (MIRT_E_ARG). */
+#define MIRT_PASSES_FRESH 1u            /* the batch starts the frame: acu starts at zero and is not read */
+#define MIRT_MAX_PASSES_PER_CALL 64u
+MIRT_API int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* desc, uint32_t n_passes, uint32_t flags);
 /* Two ways to run the pass, identical results.  Default: the optimistic pair -- a kernel whose divisions are 3-operation
  * forms proven bit-exact inside a guard window (exhaustively, on the device: profiles/r1_divcheck_exhaustive.txt), plus the
  * exact kernel re-running the samples whose rays left the window (NaN rays, axis-parallel directions, ...); it needs every
