@@ -1388,29 +1388,31 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     A.material = d->material->ptr;
     A.nmat = (uint32_t)(d->material->bytes / 16);
     if ((rc = need(ctx, "seeds", d->seeds, nrays * 4))) return rc;
-    // copyToPixel inside the pass: a frame's first pass at a ray count that puts whole pixels into a block of 256 ray ids (pt_launch.hpp
-    // fused_resolves).  Then -- and only then -- `acu` is optional: without it nothing per ray but the seed touches memory.
-    const bool resolve_in_pass = ctx->inpass_resolve && pt::fused_resolves(d->rays_per_pixel, d->pixel || d->radiance) && (fresh || d->acu);
+    // copyToPixel inside the pass: a frame's first pass at a ray count that divides 256 or is above 256 (pt_launch.hpp fused_resolves: the segment
+    // plan).  Then -- and only then -- `acu` is optional: without it nothing per ray but the seed touches memory.  With `acu`, only at the counts
+    // of fused_resolves_with_acu; elsewhere the accumulator is written and the separate copyToPixel reads it back.
+    const bool want_out = d->pixel || d->radiance;
+    const bool resolve_in_pass = ctx->inpass_resolve && (d->acu ? pt::fused_resolves_with_acu(d->rays_per_pixel, want_out) : fresh && pt::fused_resolves(d->rays_per_pixel, want_out));
     ctx->last_pass_resolved = resolve_in_pass;
     if (!d->acu && !(resolve_in_pass && fresh))
         return fail(ctx, MIRT_E_ARG, "mirt_render_pass: acu may only be null for a frame's first pass (mirt_render_first_pass) with a pixel or radiance buffer and "
-                                     "rays_per_pixel dividing 256 or 256 times a power of two up to 32 (here: %s, %u rays per pixel%s)", fresh ? "first pass" : "NOT a first pass",
-                    d->rays_per_pixel, d->pixel || d->radiance ? "" : ", no output buffer");
+                                     "rays_per_pixel dividing 256 or above 256, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", fresh ? "first pass" : "NOT a first pass",
+                    d->rays_per_pixel, want_out ? "" : ", no output buffer");
     if (d->acu && (rc = need(ctx, "acu", d->acu, nrays * kAcuBytes))) return rc;
     A.seeds = (int32_t*)d->seeds->ptr;
     A.acu = d->acu ? d->acu->ptr : nullptr;
     if (d->pixel && (rc = need(ctx, "pixel", d->pixel, npix * 4))) return rc;
     if (d->radiance && (rc = need(ctx, "radiance", d->radiance, npix * 16))) return rc;
-    A.chunks = 1u;
-    A.chunk_bits = ~0u;
+    A.seg_off = 0u;
+    A.seg_len = A.rpp;   // one segment: the whole pass (FusedArgs::seg_off)
+    A.seg_pitch = 256u;
     if (resolve_in_pass) {
         A.resolve = 1u;
         A.pixel = d->pixel ? d->pixel->ptr : nullptr;
         A.radiance = d->radiance ? d->radiance->ptr : nullptr;
         A.res_m = res_m;
         if (passes == 1u && ctx->res_m_override == ctx->res_m_override) A.res_m = ctx->res_m_override;   // (not a NaN: try_fuse_pass hands over the recorded copyToPixel's own factor)
-        A.chunks = pt::fused_chunks(d->rays_per_pixel);
-        if (A.chunks > 1u && !A.radiance) {   // a pixel of more than 256 rays: its sums travel from launch to launch through memory (FusedArgs::chunks)
+        if (A.rpp > 256u && !A.radiance) {   // a pixel of more than 256 rays: its sums travel from launch to launch through memory (FusedArgs::seg_off)
             if ((rc = ensure_scratch(ctx, (size_t)npix * 16))) return rc;
             A.radiance = ctx->scratch;
         }
@@ -1426,11 +1428,24 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     if (ctx->profiling && !ctx->capturing && mark_start) HIPCHK(ctx, hipEventRecord(ctx->pe[0], ctx->stream));
     bool optimistic = pt::fused_fast_available() && !ctx->force_exact;
     for (uint32_t i = 0; i < A.n_sets; ++i) optimistic = optimistic && A.sets[i].fast_ok != 0;
+    // Resolving in the pass: one launch (or optimistic + redo pair) per segment of the plan, in ray order (pt_launch.hpp fused_segment); each goes
+    // on from the sums the one before left.  Every launch of the plan has its own region of the deferred-block mask, one bit per block.
+    const auto seg_words = [&](uint32_t len) { return (uint32_t)((((uint64_t)npix * len + 255) / 256 + 31) / 32); };
+    uint64_t resolve_words = 0;
+    if (resolve_in_pass)
+        for (uint32_t off = 0, len; off < A.rpp; off += len) { len = pt::fused_segment(A.rpp, off); resolve_words += seg_words(len); }
+    void* const pixel_out = A.pixel;
+    const auto set_segment = [&](uint32_t off) {
+        A.seg_off = off;
+        A.seg_len = pt::fused_segment(A.rpp, off);
+        A.seg_pitch = A.seg_len == 256u && A.rpp > 256u ? A.rpp : 256u;
+        A.pixel = off + A.seg_len == A.rpp ? pixel_out : nullptr;
+    };
     if (optimistic) {
         // optimistic kernel (exact cheap divisions inside their window) + exact kernel over the samples that left the window:
         // the second launch walks the first one's bit mask on the device, so the pair is queued without a host round trip
-        // one bit per sample -- or, resolving in the pass, per block of 256 ray ids (pt_kernels_fused.hip)
-        const uint32_t words = resolve_in_pass ? (uint32_t)(((nrays + 255) / 256 + 31) / 32) : (uint32_t)((nrays + 31) / 32);
+        // one bit per sample -- or, resolving in the pass, per block of 256 samples (pt_kernels_fused.hip)
+        const uint32_t words = (uint32_t)(resolve_in_pass ? resolve_words : (nrays + 31) / 32);
         const size_t need_bytes = 16 + (size_t)words * 4;
         if (ctx->defer_bytes < need_bytes) {
             NOT_WHILE_CAPTURING(ctx, "growing the deferred-sample mask");
@@ -1442,28 +1457,30 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
         if (ctx->capturing) ctx->cap_defer = true;
         uint32_t* mask = (uint32_t*)ctx->defer + 4;
         HIPCHK(ctx, hipMemsetAsync(ctx->defer, 0, need_bytes, ctx->stream));
-        // one pair of launches -- or, a pixel of more than 256 rays resolved in the pass, one pair per block of 256 rays of a pixel, in ray order: launch c
-        // goes on from the sums launch c - 1 and its redo left (FusedArgs::chunks).  The mask collects the deferred blocks of every launch.
-        void* const pixel_out = A.pixel;
-        for (uint32_t c = 0; c < A.chunks; ++c) {
-            A.chunk = c;
-            if (A.chunks > 1u) {   // every chunks-th bit from bit c on (chunks divides 32: a block's bit sits at its number modulo 32)
-                A.chunk_bits = 0u;
-                for (uint32_t b = c; b < 32u; b += A.chunks) A.chunk_bits |= 1u << b;
-            }
-            A.pixel = c + 1u == A.chunks ? pixel_out : nullptr;
+        // one pair of launches -- or, resolving in the pass, one pair per segment, each on its own region of the mask; the redo launch of a
+        // segment runs before the next segment's launches read the sums it leaves (stream order)
+        if (!resolve_in_pass) {
             pt::launch_fused(ctx->stream, A, true, mask, nullptr, 0);
             pt::launch_fused(ctx->stream, A, false, nullptr, mask, words);
+        } else {
+            uint32_t* region = mask;
+            for (uint32_t off = 0; off < A.rpp; off += A.seg_len) {
+                set_segment(off);
+                const uint32_t w = seg_words(A.seg_len);
+                pt::launch_fused(ctx->stream, A, true, region, nullptr, 0);
+                pt::launch_fused(ctx->stream, A, false, nullptr, region, w);
+                region += w;
+            }
         }
         ctx->defer_words = words;
         ctx->defer_unit = resolve_in_pass ? 256u : 1u;
     } else {
-        void* const pixel_out = A.pixel;
-        for (uint32_t c = 0; c < A.chunks; ++c) {
-            A.chunk = c;
-            A.pixel = c + 1u == A.chunks ? pixel_out : nullptr;
-            pt::launch_fused(ctx->stream, A, false, nullptr, nullptr, 0);
-        }
+        if (!resolve_in_pass) pt::launch_fused(ctx->stream, A, false, nullptr, nullptr, 0);
+        else
+            for (uint32_t off = 0; off < A.rpp; off += A.seg_len) {
+                set_segment(off);
+                pt::launch_fused(ctx->stream, A, false, nullptr, nullptr, 0);
+            }
         ctx->defer_words = 0;
     }
     if (ctx->profiling && !ctx->capturing) HIPCHK(ctx, hipEventRecord(ctx->pe[1], ctx->stream));
@@ -1501,7 +1518,7 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
     const bool single = d->rays_per_pixel == 1u;
     if (!d->acu && !(fresh && !single && ctx->inpass_resolve && pt::fused_resolves(d->rays_per_pixel, d->pixel || d->radiance)))
         return fail(ctx, MIRT_E_ARG, "mirt_render_passes: acu may only be NULL with MIRT_PASSES_FRESH, a pixel or radiance buffer and rays_per_pixel > 1 dividing 256 "
-                                     "or 256 times a power of two up to 32, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", fresh ? "fresh" : "NOT fresh",
+                                     "or above 256, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", fresh ? "fresh" : "NOT fresh",
                     d->rays_per_pixel, d->pixel || d->radiance ? "" : ", no output buffer");
     if (!single) return render_pass_impl(ctx, d, fresh, n_passes);
     mirt_pass_desc p = *d;

@@ -435,20 +435,29 @@ PT_DEV Ray primary_ray(const FusedArgs& A, uint32_t lid) {
     return ray;
 }
 
-// copyToPixel inside the pass (A10 code.cl:1366-1386) for the block that holds ray ids [first, first + 256): `rows` = the block's parked
-// accumulators, [channel][lane] (rows 0..3 of the park area), final for every lane (the caller's barrier).  rpp divides 256, so the block
-// holds 256 / rpp whole pixels; one lane per (pixel, channel) adds that pixel's rpp samples in the reference's order -- sequential in i,
-// from +0: the fp32 sum is order-dependent -- reading them four at a time (a channel's row is contiguous in LDS); the four lanes of a pixel
-// (one DPP quad) hand their sums to the first, which writes `radiance` (the sums) and `pixel` (the tone-scaled RGBA8, truncating).
+// copyToPixel inside the pass (A10 code.cl:1366-1386) for block `blk` of the launch: `rows` = the block's parked accumulators, [channel][lane]
+// (rows 0..3 of the park area), final for every lane (the caller's barrier).  The block holds the segments of 256 / seg_len whole pixels
+// (FusedArgs::seg_off), lane-contiguous; one lane per (pixel, channel) adds that pixel's seg_len samples in the reference's order -- sequential
+// in i, from +0 or from the sum the segments before it left: the fp32 sum is order-dependent -- reading them four at a time (a channel's row is
+// contiguous in LDS); the four lanes of a pixel (one DPP quad) hand their sums to the first, which writes `radiance` (the sums) and `pixel`
+// (the tone-scaled RGBA8, truncating).
 #ifndef PT_RESOLVE_PRIO
 #define PT_RESOLVE_PRIO 1
 #endif
-// The block of 256 consecutive ray ids a workgroup renders (outside the redo loop): its own number -- or, a pixel of more than 256 rays being resolved
-// in `chunks` launches, block `chunk` of pixel blockIdx.x (FusedArgs::chunks).  Scalar arithmetic on kernel arguments, re-derived where it is used.
-PT_DEV uint32_t wg_block(const FusedArgs& A) { return blockIdx.x * A.chunks + A.chunk; }
-PT_DEV void resolve_block(const FusedArgs& A, const float* rows, uint64_t first, uint64_t n_local) {
-    const uint32_t rpp = A.rpp, per = rpp < 256u ? rpp : 256u, ppb = 256u / per;   // per: the rays of ONE pixel this block holds (rpp > 256: FusedArgs::chunks)
-    const uint32_t pix0 = (uint32_t)(first / rpp), npix = (uint32_t)(n_local / rpp);
+// The ray id of lane t of block `blk` of this launch -- the one place it is derived (FusedArgs::seg_off): sample seg_off + t % seg_len of pixel
+// blk * (256 / seg_len) + t / seg_len.  SEG = false, a contiguous segment (seg_len == rpp, or 256, and every launch that does not resolve in the
+// pass): the block's first id, scalar arithmetic on kernel arguments, plus the lane.  In 64 bits: the caller checks it against the tile's ray
+// count (a lane past the last pixel -- its pixel >= the tile's -- rides along on the tile's last sample); a valid id fits 32 bits.
+template <bool SEG>
+PT_DEV uint64_t seg_ray(const FusedArgs& A, uint32_t blk, uint32_t t) {
+    if (!SEG) return (uint64_t)(blk * A.seg_pitch + A.seg_off) + t;
+    const uint32_t sh = (uint32_t)__builtin_ctz(A.seg_len);   // wave-uniform
+    const uint32_t pix = (blk << (8u - sh)) + (t >> sh);
+    return (uint64_t)pix * A.rpp + (A.seg_off + (t & (A.seg_len - 1u)));
+}
+PT_DEV void resolve_block(const FusedArgs& A, const float* rows, uint32_t blk, uint64_t n_local) {
+    const uint32_t rpp = A.rpp, per = A.seg_len, ppb = 256u / per;   // per: the rays of ONE pixel this block holds (FusedArgs::seg_len)
+    const uint32_t pix0 = blk * ppb, npix = (uint32_t)(n_local / rpp);
 #if PT_RESOLVE_PRIO
     // The sums are chains of dependent additions (256 long at 256 rays per pixel, on four lanes) at the very end of a block whose other waves
     // have left: until the chain ends the block's LDS and this wave's slot are held.  At the top priority the chain's instructions issue as they
@@ -459,10 +468,10 @@ PT_DEV void resolve_block(const FusedArgs& A, const float* rows, uint64_t first,
         const uint32_t j = q >> 2, c = q & 3u;
         const float* r = rows + c * 256u + j * per;
         float s = 0.0f;
-        // a later block of a pixel of more than 256 rays: the chain goes on from the sum over the blocks before it (FusedArgs::chunks)
-        if (A.chunk != 0u && pix0 + j < npix) s = ((const float*)A.radiance)[4u * (size_t)(pix0 + j) + c];
+        // a later segment of a pixel of more than 256 rays: the chain goes on from the sum over the segments before it (FusedArgs::seg_off)
+        if (A.seg_off != 0u && pix0 + j < npix) s = ((const float*)A.radiance)[4u * (size_t)(pix0 + j) + c];
         if (per >= 4u) {
-            const float4* r4 = (const float4*)r;   // 16-byte aligned: the rows are, and `per` is a multiple of 4
+            const float4* r4 = (const float4*)r;   // 16-byte aligned: the rows are, and `per` is a multiple of 4 (a power of two)
             for (uint32_t i = 0; i < per / 4u; ++i) { const float4 v = r4[i]; s += v.x; s += v.y; s += v.z; s += v.w; }
         } else {
             for (uint32_t i = 0; i < per; ++i) s += r[i];
@@ -537,7 +546,8 @@ PT_DEV float* reuse_rows() {   // [word][lane]: p.xyz, n.xyz, material id, the l
     __shared__ __attribute__((aligned(16))) float reuse_mem[kReuseWords][256];
     return &reuse_mem[0][threadIdx.x];
 }
-template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0>
+// SEG: the general form of the ray ids of a launch's segment (seg_ray); false for every contiguous one.
+template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0, bool SEG = false>
 __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_GRIDS : (FAST ? PT_FUSED_WAVES_FAST : PT_FUSED_WAVES))) k_fusedPass(const FusedArgs A, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     const uint64_t n_local = (uint64_t)A.nrows * A.width * A.rpp;
     stage_block<FAST, GRIDS>(A);
@@ -546,17 +556,17 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
     // GRIDS: the walk shares its triangle tests across the wave (pt_trace_coop.hpp), so every lane stays in to the end: a lane
     // without a sample of its own (past the end of the tile; no bit left in its redo word) rides along on the tile's last sample
     // and writes nothing.
-    // In-pass resolve (A.resolve): the unit of everything is the BLOCK of 256 consecutive ray ids -- the optimistic kernel hands a whole block
-    // over when one of its samples left the guard windows (a bit per block in `defer_mask`; nothing of the block is written), and the exact
-    // kernel's redo mode is one block per 32-block word of that mask, every thread one sample of each marked block in turn.  Every thread stays
-    // in to the block's barrier: a lane past the end of the tile rides along as in the grid kernels.
-    uint64_t base = (uint64_t)wg_block(A) * 256u + threadIdx.x;   // (every launch of this kernel uses 256-thread blocks: launch_fused)
+    // In-pass resolve (A.resolve): the unit of everything is the BLOCK of 256 samples (FusedArgs::seg_off) -- the optimistic kernel hands a whole
+    // block over when one of its samples left the guard windows (a bit per block of the launch in `defer_mask`, the launch's own region of the
+    // mask; nothing of the block is written), and the exact kernel's redo mode is one block per 32-block word of that region, every thread one
+    // sample of each marked block in turn.  Every thread stays in to the block's barrier: a lane past the end of the tile rides along as in the
+    // grid kernels.
+    uint64_t base = seg_ray<SEG>(A, blockIdx.x, threadIdx.x);   // (every launch of this kernel uses 256-thread blocks: launch_fused)
     uint32_t todo = 1u;
     uint32_t stride = 1u;
     if (!FAST && redo_mask) {
         if (A.resolve) {
-            todo = redo_mask[blockIdx.x] & A.chunk_bits;   // (the grid is one block per word; the bits of this launch's blocks: FusedArgs::chunks)
-            base = (uint64_t)blockIdx.x * (32u * 256u) + threadIdx.x;
+            todo = redo_mask[blockIdx.x];   // (the grid is one block per word)
             stride = 256u;
         } else {
             if (GRIDS) todo = base < redo_words ? redo_mask[base] : 0u;
@@ -571,8 +581,10 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
     bool valid = todo != 0u;
     if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) break; }
     else if (!valid) break;
-    // the id is checked in 64 bits (the last block of a tile of nearly 2^32 rays reaches past it) and kept in 32
-    const uint64_t lid64 = base + (valid ? (uint32_t)__builtin_ctz(todo) * stride : 0u);
+    // the id is checked in 64 bits (the last block of a tile of nearly 2^32 rays reaches past it) and kept in 32.  (Resolving, redo mode: lane
+    // threadIdx.x of the marked block of this trip -- wave-uniform todo.)
+    const uint64_t lid64 = stride == 256u ? seg_ray<SEG>(A, blockIdx.x * 32u + (valid ? (uint32_t)__builtin_ctz(todo) : 0u), threadIdx.x)
+                                          : base + (valid ? (uint32_t)__builtin_ctz(todo) * stride : 0u);
     uint32_t lid = (uint32_t)lid64;
     if (lid64 >= n_local) {
         if (!GRIDS && !A.resolve) return;
@@ -595,7 +607,7 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
     if (MULTI && FAST) {   // the ray id from the thread index, as at the end of the path (see there): kept across the passes it cost spills
         uint32_t t = threadIdx.x;
         asm volatile("" : "+v"(t));
-        const uint64_t again = (uint64_t)wg_block(P) * 256u + t, n = (uint64_t)P.nrows * P.width * P.rpp;
+        const uint64_t again = seg_ray<SEG>(P, blockIdx.x, t), n = (uint64_t)P.nrows * P.width * P.rpp;
         lid = again < n ? (uint32_t)again : (uint32_t)(n - 1u);
     }
     Ray ray = primary_ray(P, lid);
@@ -683,7 +695,7 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
         // keeping it (and the 64-bit addresses made from it) alive across the whole path cost spilled registers in every variant
         uint32_t t = threadIdx.x;
         asm volatile("" : "+v"(t));
-        const uint64_t again = (uint64_t)wg_block(A) * 256u + t;
+        const uint64_t again = seg_ray<SEG>(A, blockIdx.x, t);
         lid = (uint32_t)again;
         if (GRIDS || A.resolve) valid = again < n_local;   // (a lane past the end of the tile rode along on the tile's last sample)
     }
@@ -695,17 +707,16 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
         if (FAST && defer) pt_blk_defer[0] = 1u;
         __syncthreads();   // every lane's accumulator is final in LDS, and so is the flag
         if (FAST && pt_blk_defer[0] != 0u) {   // the whole block goes to the exact kernel: its seeds stay as they were, no pixel of it is written
-            if (threadIdx.x == 0u) atomicOr(&defer_mask[wg_block(A) >> 5], 1u << (wg_block(A) & 31u));
+            if (threadIdx.x == 0u) atomicOr(&defer_mask[blockIdx.x >> 5], 1u << (blockIdx.x & 31u));
             return;
         }
         if (valid) {
             A.seeds[lid] = seed;
             if (A.acu) ((float4*)A.acu)[lid] = make_float4(park_mem[0][threadIdx.x], park_mem[1][threadIdx.x], park_mem[2][threadIdx.x], park_mem[3][threadIdx.x]);
         }
-        // the block's first ray id: wave-uniform (blockIdx alone in the optimistic kernel; the marked block of this trip in the redo loop)
-        const uint64_t first = FAST || stride != 256u ? (uint64_t)wg_block(A) * 256u
-                                                      : (uint64_t)blockIdx.x * (32u * 256u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(todo)) * 256u;
-        resolve_block(A, &park_mem[0][0], first, n_local);
+        // the block of the launch: wave-uniform (blockIdx alone in the optimistic kernel; the marked block of this trip in the redo loop)
+        const uint32_t blk = FAST || stride != 256u ? blockIdx.x : blockIdx.x * 32u + (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(todo));
+        resolve_block(A, &park_mem[0][0], blk, n_local);
         if (FAST) return;
         __syncthreads();   // the redo loop's next block parks into the same rows
         continue;
@@ -743,11 +754,16 @@ __global__ void __launch_bounds__(256) k_deferCount(const uint32_t* mask, uint32
 // grid kernel a block per CU, and it spills 71 VGPRs) against 20.36 plain (19.89 ordinary).  So: reuse for scenes without grids only.
 // MIRT_MULTIPASS_REUSE=1 / 0 forces one or the other -- an A/B switch, read per launch so that one process can alternate them (profiles/multipass_bench.py).
 static bool multipass_reuse(bool grids) { const char* e = getenv("MIRT_MULTIPASS_REUSE"); return e && e[0] ? e[0] != '0' : !grids; }
+template <bool FAST, int GRIDS, int WAVES, bool SEG>
+static void launch_seg(const dim3& grid, size_t lds, hipStream_t s, const FusedArgs& b, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
+    if (b.passes > 1u && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    else if (b.passes > 1u) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    else hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 0, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+}
 template <bool FAST, int GRIDS, int WAVES = 0>
 static void launch_pass(const dim3& grid, size_t lds, hipStream_t s, const FusedArgs& b, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
-    if (b.passes > 1u && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
-    else if (b.passes > 1u) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
-    else hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    if (b.resolve && !fused_segment_contiguous(b.rpp, b.seg_len)) launch_seg<FAST, GRIDS, WAVES, true>(grid, lds, s, b, defer_mask, redo_mask, redo_words);
+    else launch_seg<FAST, GRIDS, WAVES, false>(grid, lds, s, b, defer_mask, redo_mask, redo_words);
 }
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     const uint64_t n = redo_mask ? redo_words : (uint64_t)a.nrows * a.width * a.rpp;
@@ -779,9 +795,10 @@ void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_
         }
 
     }
-    // redo mode: one thread per 32-sample word of the mask, or (in-pass resolve: the mask is per block) one block per 32-block word
-    // (resolving a pixel of more than 256 rays: one workgroup per pixel and launch, FusedArgs::chunks -- n is a multiple of 256 * chunks then)
-    const dim3 grid(redo_mask && a.resolve ? (unsigned)redo_words : (unsigned)((n + 255) / 256 / (a.chunks ? a.chunks : 1u)));
+    // redo mode: one thread per 32-sample word of the mask, or (in-pass resolve: the mask is per block) one block per 32-block word.  Otherwise a
+    // block per 256 samples of the launch's segment: 256 / seg_len pixels each (FusedArgs::seg_off; without in-pass resolve seg_len is rpp)
+    const dim3 grid(redo_mask && a.resolve ? (unsigned)redo_words
+                  : a.resolve ? (unsigned)(((uint64_t)a.nrows * a.width * a.seg_len + 255) / 256) : (unsigned)((n + 255) / 256));
     // dynamic LDS: the waves' exchange areas, then the staged tables (what the scene needs, not the 16 KB cap: occupancy), then the staged triangles
     const size_t lds_tri = tri_words ? (size_t)(tri_base4 - tri_base + tri_words) * 4u : 0u;
     const size_t lds2 = (size_t)kCoopWordsPerBlock * 4u + lds_tri, lds = (size_t)kCoopWordsPerBlock * 4u + (staged ? (size_t)used * 4u : 0u) + lds_tri;

@@ -89,36 +89,53 @@ struct FusedArgs {
     void* acu;               // float4[nrows*width*rpp], accumulated into
     const void* uv;          // rpp == 1: float2[nrows*width] lens draws from launch_lensDraws
     uint32_t fresh;          // 1: the accumulator starts at zero and is not read (initAcu folded into the pass, mirt_render_first_pass)
-    // copyToPixel INSIDE the pass (A10 code.cl:1366-1386; `resolve` != 0): a block of 256 consecutive ray ids holds whole pixels (rpp divides 256) and the
-    // pass is a frame's first, so every accumulator of a pixel is final in the block's LDS when its last sample ends: the block sums them in the
-    // reference's order and writes `pixel` (RGBA8) and / or `radiance` (the un-scaled sums); `acu` may then be null -- nothing per ray but the seed
+    // copyToPixel INSIDE the pass (A10 code.cl:1366-1386; `resolve` != 0): a block of 256 lanes holds whole SEGMENTS of pixels (seg_off, seg_len below)
+    // and the pass is a frame's first, so every accumulator of a segment is final in the block's LDS when its last sample ends: the block sums them in
+    // the reference's order and writes `pixel` (RGBA8) and / or `radiance` (the un-scaled sums); `acu` may then be null -- nothing per ray but the seed
     // touches memory: 8 B per sample + 20 B per pixel.  launch_fused decides (fused_resolves()).
     void* pixel;             // uchar4[nrows*width] or null
     void* radiance;          // float4[nrows*width] or null
     float res_m;             // 1 / (rpp * passes), A10 code.js:1412
     uint32_t resolve;
-    // A pixel of MORE than 256 rays (rpp = 256 * chunks; chunks a power of two <= 32: 1024 rays are 4) resolves in `chunks` launches: launch c renders the
-    // c-th block of 256 ray ids of EVERY pixel (workgroup b: block b * chunks + c) and continues the pixel's chain of additions from what `radiance`
-    // holds -- the sums over the blocks before it, written by launches 0 .. c-1 -- so the reference's one chain (A10 code.cl:1377-1380) is cut at
-    // multiples of 256 and carried through memory, 16 B per pixel and launch instead of 16 B per ray.  `pixel` is given to the last launch only.
-    uint32_t chunks;         // 1, or rpp / 256
-    uint32_t chunk;          // this launch's c
-    uint32_t chunk_bits;     // redo mode: the bits of a 32-block mask word that are blocks of this launch (all ones when chunks == 1)
+    // The launch's SEGMENT (fused_segment): samples [seg_off, seg_off + seg_len) of EVERY pixel of the tile, seg_len a power of two <= 256.  A block
+    // holds 256 / seg_len pixels' segments: lane t of block b is sample seg_off + t % seg_len of pixel b * (256 / seg_len) + t / seg_len (k_fusedPass
+    // seg_ray).  A pixel of more than 256 rays resolves in several launches, in ray order, each continuing the pixel's chain of additions from what
+    // `radiance` holds -- the sums over the segments before it -- so the reference's one chain (A10 code.cl:1377-1380) is cut at segment boundaries
+    // and carried through memory, 16 B per pixel and launch instead of 16 B per ray.  `pixel` is given to the last launch only.
+    uint32_t seg_off;        // 0 unless resolving a pixel of more than 256 rays
+    uint32_t seg_len;        // rpp when the pass is one segment (rpp <= 256, or not resolving in the pass)
+    uint32_t seg_pitch;      // a CONTIGUOUS segment (seg_len == rpp, or 256): the ray ids from one block's first to the next's -- 256, or rpp when a
+                             // block is 256 samples of one pixel (then block b's first ray is b * rpp + seg_off)
     // Progressive passes in ONE launch (mirt_render_passes): every sample runs `passes` passes in a row, its seed and accumulator carried in the
     // kernel, and is written once at the end; `fresh` applies to the first of them, `res_m` to the frame after the last.  > 1 picks the MULTI
     // instantiations of k_fusedPass; 0 and 1 run the single-pass kernels, which never read it.
     uint32_t passes;
 };
-// whether a pass with these arguments resolves inside the kernel: whole pixels per block (or whole blocks per pixel, see FusedArgs::chunks) and
-// somewhere to put the result.  A frame's first pass may then do without `acu`; a later pass reads and writes it as ever -- the block's LDS holds the
-// accumulators as the pass leaves them, which is what the separate copyToPixel would read back.
-inline uint32_t fused_chunks(uint32_t rpp) { return rpp > 256u ? rpp / 256u : 1u; }
+// Whether a pass with these arguments can resolve inside the kernel: rpp divides 256 (whole pixels per block), or rpp > 256 -- any count: the
+// segment plan below covers it -- and somewhere to put the result.  A frame's first pass may then do without `acu`.
 inline bool fused_resolves(uint32_t rpp, bool want_out) {
     if (!want_out || rpp == 0u) return false;
-    if (rpp <= 256u) return 256u % rpp == 0u;
+    return rpp > 256u || 256u % rpp == 0u;
+}
+// Whether a pass that KEEPS `acu` resolves in the kernel too: only at the counts that resolved in the pass before the segment plan -- rpp divides
+// 256, or is 256 times a power of two up to 32.  At the other counts above 256 such a pass writes `acu` and runs the separate copyToPixel: resolving
+// there beside a kept accumulator was not measured against it.  The block's LDS holds the accumulators as the pass leaves them, which is what copyToPixel would read back.
+inline bool fused_resolves_with_acu(uint32_t rpp, bool want_out) {
+    if (!fused_resolves(rpp, want_out)) return false;
+    if (rpp <= 256u) return true;
     const uint32_t c = rpp / 256u;
     return rpp % 256u == 0u && c <= 32u && (c & (c - 1u)) == 0u;
 }
+// The segment plan: a pixel's rays [0, rpp) cut in ray order into power-of-two segments of at most 256 -- floor(rpp / 256) of 256, then one per
+// set bit of rpp % 256, largest first (289: 256, 32, 1).  The length of the segment that starts at sample `off` is the largest power of two that
+// is at most 256 and at most the rays left.  rpp <= 256 (dividing 256): one segment, the whole pixel.
+inline uint32_t fused_segment(uint32_t rpp, uint32_t off) {
+    if (rpp <= 256u) return rpp;
+    const uint32_t left = rpp - off;
+    return left >= 256u ? 256u : 1u << (31 - __builtin_clz(left));
+}
+// the contiguous form of a segment's ray ids (FusedArgs::seg_pitch) applies: the segment is the whole pixel, or 256 of its rays
+inline bool fused_segment_contiguous(uint32_t rpp, uint32_t len) { return len == rpp || len == 256u; }
 // fast: the optimistic kernel (writes deferred samples' bits into defer_mask); !fast: the exact kernel over `list` (or everything)
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words);
 bool fused_fast_available();   // compiled with PT_EXACT_FAST_DIV

@@ -38,7 +38,8 @@ if (cmd === "pack") {
   if (rest.length < 6) usage();
   const renderer = require("./renderer.js");
   const opt = { granular: rest.includes("--granular"), graph: rest.includes("--graph"), fusion: rest.includes("--fusion"), deviceGrid: rest.includes("--device-grid"), bounces: 5, seeds: null,
-                keepAcu: !rest.includes("--no-acu"),   // --no-acu: a frame without the 16 bytes per ray: the pass resolves its own pixels (mirt.h) -- one pass, or
+                keepAcu: !rest.includes("--no-acu"),   // --no-acu: a frame without the 16 bytes per ray: the pass resolves its own pixels (mirt.h; raysPerPixel
+                                                        // dividing 256 or above 256) -- one pass, or
                 passesInOneLaunch: rest.includes("--passes-in-one-launch") };   // all of them in one call (mirt_render_passes; with --gpus, one per tile):
                                                                                  // at most 64 without the accumulator, calls of 64 with it
   let i;

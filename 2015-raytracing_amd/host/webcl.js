@@ -173,7 +173,8 @@ class WebCLCommandQueue {
     });
     wrap(() => native().renderPass(this.ctx.h, d));
   }
-  // n passes from desc.passIndex on in one call (mirt_render_passes): the frame after the last of them; desc.firstPass starts the frame.
+  // n passes from desc.passIndex on in one call (mirt_render_passes): the frame after the last of them; desc.firstPass starts the frame, and then
+  // desc.acu may be null where the passes resolve their own pixels (rays_per_pixel > 1 dividing 256, or above 256: mirt.h).
   // At most MAX_PASSES_PER_CALL (checked here: the addon reads the count as a uint32, which would wrap)
   renderPasses(desc, n) {
     if (!Number.isInteger(n) || n < 1 || n > MAX_PASSES_PER_CALL)

@@ -193,11 +193,14 @@ MIRT_API int mirt_render_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
  * A LATER pass (mirt_render_pass) with a pixel or radiance buffer resolves inside the pass under the same condition -- `acu` is then read and
  * written as ever, and the separate copyToPixel's second read of it is saved; the runtime's command-stream fusion (mirt_ctx_set_fusion) folds the
  * host's recorded copyToPixel into the pass the same way, with the factor the host passed.
- * MORE than 256 rays per pixel, 256 times a power of two up to 32 (the squares among them: 1024 = BASELINE config 5's 32 x 32 lens grid,
- * and 4096): a pixel spans 4 (16) blocks, so the pass is queued as 4 (16) launches, launch c rendering the c-th block of every pixel and
- * going on from the sums launch c - 1 left in `radiance` (or in the context's scratch buffer when the caller passes none): the
- * reference's one chain of additions, cut at multiples of 256 and carried through memory at 16 B per pixel and launch instead of 16 B
- * per ray.  `acu` may be NULL there too; results are bit-identical. */
+ * MORE than 256 rays per pixel, any count (17 x 17 = 289, BASELINE config 5's 32 x 32 = 1024, ...): the pixel's rays are cut, in ray order,
+ * into power-of-two segments of at most 256 -- floor(rays_per_pixel / 256) of 256, then one per set bit of the rest, largest first (289: 256,
+ * 32, 1) -- and the pass is queued as one launch per segment, each rendering that segment of every pixel (a block holds 256 / length pixels'
+ * segments) and going on from the sums the launch before it left in `radiance` (or in the context's scratch buffer when the caller passes
+ * none): the reference's one chain of additions, cut at segment boundaries and carried through memory at 16 B per pixel and launch instead of
+ * 16 B per ray.  A first pass may leave `acu` NULL at every such count; results are bit-identical.  With `acu` given, a pass resolves inside
+ * the kernel only at 256 times a power of two up to 32 (1024, 4096); at the other counts above 256 it writes `acu` and runs the separate
+ * copyToPixel. */
 MIRT_API int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
 /* Several progressive passes in ONE call (A10 code.js:1806-1853: executeRender, executeCopyToPixel, passes++ -- n_passes times).  Results equal,
  * bit for bit in every buffer the caller passes (seeds, acu if given, pixel, radiance), this sequence:
@@ -206,8 +209,8 @@ MIRT_API int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
  * Pixel and radiance are those of the last pass (tone factor 1 / (rays_per_pixel * (pass_index + n_passes - 1))).  Passes interact only through a
  * ray's own seed and its own accumulator, so one launch runs every sample through all n_passes passes, the accumulator on chip, and writes the
  * seeds (and `acu`) once: a multi-pass frame needs no per-ray accumulator and moves none between the passes.
- * `acu` may be NULL exactly where a first pass may do without it: MIRT_PASSES_FRESH, a pixel or radiance buffer, rays_per_pixel dividing 256 or 256
- * times a power of two up to 32 (and MIRT_INPASS_RESOLVE not 0) -- except rays_per_pixel 1, whose rows are coupled through seeds[col] (A10
+ * `acu` may be NULL exactly where a first pass may do without it: MIRT_PASSES_FRESH, a pixel or radiance buffer, rays_per_pixel dividing 256 or
+ * above 256 (and MIRT_INPASS_RESOLVE not 0) -- except rays_per_pixel 1, whose rows are coupled through seeds[col] (A10
  * code.cl:429): the call then queues n_passes ordinary passes and needs `acu`.  NULL elsewhere is MIRT_E_ARG.  n_passes is 1..64 (one launch lasts
  * about n_passes single passes); row tiles and global ray ids work as in mirt_render_pass.  mirt_pass_deferred counts the samples (blocks) handed
  * to the exact kernel in the same unit as for one pass -- such a sample re-runs all of its passes; mirt_pass_timing covers the whole call.
