@@ -290,6 +290,22 @@ uint32_t exit_is_far_face(const float* b8, uint32_t n) {
     }
     return exact ? 1u : 0u;
 }
+// n == 1, the optimistic kernel's cell exit (pt_trace.hpp cell1_exit): per axis the forward plane x_up = lo + 1*((hi-lo)/1), formed as above, into
+// up[k]; bit k of the result is set where x_up == hi.  `ok` is cleared unless every x_up is zero or within [2^-30, 2^20] (the bounds' window,
+// GridArgs::fast_ok) and every backward plane lo + 0*((hi-lo)/1) equals lo (the kernel takes the box's far quotient for d < 0).
+uint32_t exit_planes(const float* b8, float up[3], bool& ok) {
+    uint32_t far = 0;
+    for (int k = 0; k < 3; ++k) {
+        volatile float lo = b8[k], hi = b8[4 + k];
+        volatile float delta = (hi - lo) / 1.0f;
+        volatile float u = lo + 1.0f * delta, dn = lo + 0.0f * delta;
+        up[k] = u;
+        if (u == hi) far |= 1u << k;
+        const float a = std::fabs(u);
+        if (!(a == 0.0f || (a >= 9.3132257e-10f && a <= 1048576.0f)) || !(dn == lo)) ok = false;
+    }
+    return far;
+}
 
 // (re)builds the prepared-triangle copy of a position buffer when its contents changed
 int ensure_prepared(mirt_ctx* ctx, mirt_buf* pb, uint32_t count) {
@@ -1306,10 +1322,16 @@ static int fill_grid(mirt_ctx* ctx, const char* what, const mirt_grid* g, bool t
     for (int k = 0; k < 3; ++k)
         if (!(g->bounds[k] <= g->bounds[4 + k])) o->fast_ok = 0;
     if (tri && !g->prims->prep_sane) o->fast_ok = 0;
+    o->exit_far_axes = 7u;
+    o->exit_up[0] = g->bounds[4]; o->exit_up[1] = g->bounds[5]; o->exit_up[2] = g->bounds[6];
+    if (g->n_slabs == 1u) {
+        bool planes_ok = true;
+        o->exit_far_axes = exit_planes(g->bounds, o->exit_up, planes_ok);
+        if (!planes_ok) o->fast_ok = 0;
+    }
     // the walk's wave-uniform quotients, once, in the arithmetic the kernel would use: fp32, correctly rounded
     o->walk_ok = 1;
     o->nslots = g->cell_offsets->off_last;   // validated by check_grid above
-    o->first_zero = g->cell_offsets->off_first == 0u;
     for (int k = 0; k < 3; ++k) {
         const float span = g->bounds[4 + k] - g->bounds[k];
         const float delta = span / (float)g->n_slabs;
@@ -1802,7 +1824,7 @@ int mirt_debug_divcheck(mirt_ctx* ctx, int mode, uint64_t seed, uint64_t count, 
     FLUSH_PENDING(ctx);
     int rc = need(ctx, "mirt_debug_divcheck out", out16, 16 * 8);
     if (rc) return rc;
-    if (mode < 0 || mode > 5) return fail(ctx, MIRT_E_ARG, "mirt_debug_divcheck: mode is 0..5");
+    if (mode < 0 || mode > 6) return fail(ctx, MIRT_E_ARG, "mirt_debug_divcheck: mode is 0..6");
     if (mode == 4 && (seed > (1u << 23) || count > (1u << 23) - seed)) return fail(ctx, MIRT_E_ARG, "mirt_debug_divcheck: mode 4 walks denominators [seed, seed+count) within 2^23 mantissas");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipMemsetAsync(out16->ptr, 0, 16 * 8, ctx->stream));

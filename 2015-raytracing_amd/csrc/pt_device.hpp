@@ -104,6 +104,23 @@ PT_DEV float lcg_float(int32_t s) { return cl_fabs((float)s * 4.6566128730773925
 PT_DEV float get_rand(int32_t& seed) { seed = lcg_next(seed); return lcg_float(seed); }
 
 // ---- camera: A10 code.cl:108-119, 143-197 ------------------------------------------
+// concentric's quotient num / den (code.cl:158, 163), num and den being fl(2x - 1) and fl(2y - 1) in either order, |num| <= |den| up to one
+// rounding (`top` compares the rounded squares).  For a finite x, fl(2x - 1) is zero or at least 2^-24 in magnitude (below 1/2 in magnitude, x
+// is in (1/4, 3/4) and 2x - 1 is exact -- Sterbenz -- and a multiple of 2^-24), and a zero is +0 (an exact 1 - 1 rounds to +0).  The callers'
+// x and y are draws in [0, 1] (get_rand: |s| * 2^-31, the lens grid's coordinates, launch_lensDraws): den is zero or within [2^-24, 1], num
+// zero or at most |den| -- inside div_exact3's window (pt_numerics.hpp).  For a +0 numerator its two refinement steps keep the sign of n * r,
+// which is the sign the division gives, so the select that hands over a -0 is not needed (div_exact3_anyzero).  A den outside [2^-24, 2^40]
+// -- zero: a = b = 0, the reference's 0 / 0, a NaN; or whatever a caller might pass beyond [0, 1] -- takes the compiler's division, on a branch
+// no lane of the hot loop takes in practice.  mirt_debug_divcheck mode 6 checks this against the division on the device.
+PT_DEV float concentric_quotient(float num, float den) {
+#if PT_EXACT_FAST_DIV && !PT_PLAIN_DIV
+    float q = div_exact3_anyzero(num, den, rcp_refined(den));
+    if (__builtin_expect(!((int)(__builtin_fabsf(den) >= 0x1p-24f) & (int)(__builtin_fabsf(den) <= 0x1p+40f)), 0)) q = num / den;
+    return q;
+#else
+    return num / den;
+#endif
+}
 PT_DEV void concentric(float inx, float iny, float& ox, float& oy) {
     if (inx == 0.0f && iny == 0.0f) { ox = inx; oy = iny; return; }
     float a = cl_fma(2.0f, inx, -1.0f);        // code.cl:152-153, contracted
@@ -111,8 +128,9 @@ PT_DEV void concentric(float inx, float iny, float& ox, float& oy) {
     const bool top = (a * a) > (b * b);
     float radius = top ? (1.0f * a) : (1.0f * b);
     const float num = top ? b : a, den = top ? a : b;
-    float q = num / den;   // code.cl:158, 163: b / a or a / b -- one division on the selected operands (written as a select of two
-                           // quotients the compiler evaluates both: eleven instructions per call for nothing)
+    // b / a or a / b -- one division on the selected operands (written as a select of two quotients the compiler evaluates both: eleven
+    // instructions per call for nothing)
+    const float q = concentric_quotient(num, den);
     float phi = top ? (PT_PI_4 * q) : cl_fma(-PT_PI_4, q, PT_PI_2);   // code.cl:164: c - a*b contracts to fma(-a, b, c)
     float s, c;
     cl_sincos(phi, s, c);

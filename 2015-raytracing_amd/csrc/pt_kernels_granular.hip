@@ -223,6 +223,7 @@ PT_DEV GridArgs mk_set(const float4* prims, const uint32_t* off, const Box8& b, 
     S.n = n; S.mesh_matid = 0; S.kind = 0; S.fast_ok = 0; S.lds_off = kNoLds; S.exit_is_far_face = exit_far;
     for (int i = 0; i < 3; ++i) { S.delta[i] = 0.0f; S.rdelta[i] = 0.0f; }   // the optimistic kernel's (these kernels divide for themselves)
     S.walk_ok = 0; S.nslots = 0;
+    S.exit_far_axes = 0; S.exit_up[0] = S.exit_up[1] = S.exit_up[2] = 0.0f;   // (the optimistic kernel's as well)
     return S;
 }
 template <int KIND>
@@ -537,6 +538,48 @@ __global__ void __launch_bounds__(256) k_divCheck(int mode, uint64_t seed, uint6
             }
         }
         if (m3) atomicAdd(&out[3], m3);
+        return;
+    }
+    if (mode == 6) {
+        // the fused pass's cheaper quotients over the operand domains their comments state, against the compiler's correctly rounded division:
+        //   out[1] concentric_quotient (pt_device.hpp) on the operands concentric forms from x, y = |s| * 2^-31 (get_rand's draws for random s), an
+        //          eighth of each exactly 1/2 (zero numerators, and a = b = 0: the 0 / 0) -- bit for bit, a NaN equal to a NaN; out[4] / out[5] the
+        //          (num, den) bits of a mismatch
+        //   out[2] the cell exit's div_exact3_anyzero(x_up - o, d, rcp_refined(d)) (pt_trace.hpp cell1_exit): x_up and o zero (one in sixteen) or
+        //          within [2^-30, 2^20], |d| within [2^-40, 2^40], all signs -- equal as values (the sign of a zero is free there); out[6] / out[7]
+        //          the (num, d) bits of a mismatch
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+            uint64_t h = (i + seed) * 0x9E3779B97F4A7C15ull;
+            h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32; h *= 0x94D049BB133111EBull; h ^= h >> 29;
+            uint64_t g = h * 0xD6E8FEB86659FD93ull;
+            g ^= g >> 32; g *= 0xD6E8FEB86659FD93ull; g ^= g >> 32;
+            float x = lcg_float((int32_t)(uint32_t)h), y = lcg_float((int32_t)(uint32_t)(h >> 32));
+            if ((g & 7u) == 0u) x = 0.5f;
+            if (((g >> 3) & 7u) == 0u) y = 0.5f;
+            const float a = cl_fma(2.0f, x, -1.0f), b = cl_fma(2.0f, y, -1.0f);
+            const bool top = (a * a) > (b * b);
+            const float num = top ? b : a, den = top ? a : b;
+            const float got = concentric_quotient(num, den), want = num / den;
+            if (!(__float_as_uint(got) == __float_as_uint(want) || (got != got && want != want))) {
+                ++m1;
+                out[4] = __float_as_uint(num); out[5] = __float_as_uint(den);
+            }
+            auto pick = [](uint64_t v, uint32_t e0, uint32_t span, bool zero) {   // sign, exponent in [e0, e0 + span), mantissa: from v
+                if (zero) return __uint_as_float((uint32_t)(v >> 63) << 31);
+                return __uint_as_float(((uint32_t)(v >> 63) << 31) | ((e0 + (uint32_t)((v >> 23) % span)) << 23) | ((uint32_t)v & 0x7FFFFFu));
+            };
+            const float up = pick(g, 127u - 30u, 50u, ((g >> 6) & 15u) == 0u);
+            const float o = pick(g >> 7 ^ h, 127u - 30u, 50u, ((g >> 10) & 15u) == 0u);
+            const float d = pick(h >> 5 ^ g << 7, 127u - 40u, 80u, false);
+            const float n = up - o;
+            const float qe = div_exact3_anyzero(n, d, rcp_refined(d)), we = n / d;
+            if (!(qe == we)) {
+                ++m2;
+                out[6] = __float_as_uint(n); out[7] = __float_as_uint(d);
+            }
+        }
+        if (m1) atomicAdd(&out[1], m1);
+        if (m2) atomicAdd(&out[2], m2);
         return;
     }
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {

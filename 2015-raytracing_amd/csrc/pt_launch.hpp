@@ -61,8 +61,10 @@ struct GridArgs {            // one cell-sorted primitive set, device pointers
                              // 4) of the set's `nslots` prepared records staged in LDS for the per-lane candidate loops, or kNoLds
     float delta[3], rdelta[3]; // n > 1, optimistic kernel: the cell width per axis (hi - lo) / n and its reciprocal, both correctly rounded --
     uint32_t nslots;         // off[n^3], the number of (cell, primitive) slots, when the host knows it (0: the walk reads it from the table)
-    uint32_t first_zero;     // off[0] == 0 (host-checked): a single-cell set's list is slots [0, nslots)
-    uint32_t walk_ok;        // what every lane would compute for itself from wave-uniform inputs (pt_trace.hpp axis_setup_t).  walk_ok: the
+    uint32_t exit_far_axes;  // n == 1, optimistic kernel: bit k set where the cell's forward exit plane x_up = lo + 1*((hi-lo)/1) (A10 code.cl:699-707)
+                             // equals hi, so a ray with d_k >= 0 leaves the cell where it leaves the box (pt_trace.hpp cell1_exit)
+    float exit_up[3];        // ... and x_up itself per axis, for the axes whose bit is clear (the backward plane lo + 0*((hi-lo)/1) is lo: host-checked)
+    uint32_t walk_ok;      // what every lane would compute for itself from wave-uniform inputs (pt_trace.hpp axis_setup_t).  walk_ok: the
                              // widths and spans sit inside the windows in which the kernel's 3-operation divisions are exact; a lane that
                              // walks a set without it hands its sample to the exact kernel
     uint32_t exit_is_far_face; // n == 1 only: lo + 1*((hi-lo)/1) == hi and lo + 0*((hi-lo)/1) == lo hold bitwise on all three

@@ -378,10 +378,32 @@ PT_DEV Box set_box_of(const GridArgs& S) {
 }
 // The t at which a ray leaves the single cell of an n == 1 set: axis_setup with n == 1 -- slab = 0, the cell exit is the far face as the
 // reference computes it, lo + (0 + (d>=0)) * ((hi-lo)/1)   (A10 code.cl:699-707)
-PT_DEV float cell1_exit(const Ray& ray, const BoxHit& bh, const GridArgs& S) {
+// FAST (the optimistic kernel, not under PT_PLAIN_DIV), per axis, from what the host worked out once per set (GridArgs::exit_far_axes / exit_up):
+//   * d < 0: the plane lo + 0*((hi-lo)/1) is lo (host-checked; a zero lo may come back as a zero of the other sign), so the quotient is the box's
+//     far slab quotient (lo - o) / d, which inter_aabb_t already formed: tf = the larger of the two slab quotients = the lo one when d < 0;
+//   * d >= 0 on an axis whose x_up = lo + 1*((hi-lo)/1) is hi (bit k): likewise the box's (hi - o) / d;
+//   * d >= 0 on the other axes (cornell.xml's sphere set misses hi by one ulp on all three): (x_up - o) / d through the ray's refined
+//     reciprocal (RayRcp), three operations where the correctly rounded division takes about eleven.  Exact: the ray window (ray_guard: o
+//     zero or in [2^-30, 2^20], |d| in [2^-40, 2^40]) and the set's (GridArgs::fast_ok: x_up zero or in [2^-30, 2^20], like the bounds)
+//     make the numerator the difference of two floats that are zero or multiples of 2^-53 of at most 2^20 -- zero or within [2^-53, 2^21],
+//     inside div_exact3's window, as the slab numerators are.  A zero numerator may give a zero of either sign: the exit is only compared
+//     (cmin <= t <= cmax, and min(cmax, maxt) in the plane window), as the slab quotients of slab1_fast without SIGNED_ZERO.
+// The exact kernel and the default contract keep the reference's divisions.
+template <bool FAST>
+PT_DEV float cell1_exit(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const GridArgs& S) {
     float tn[3];
     if (S.exit_is_far_face) {  // host-verified: the cell's exit planes ARE the box's far planes (see mirt_abi.cpp)
         tn[0] = bh.tfx; tn[1] = bh.tfy; tn[2] = bh.tfz;
+#if !PT_PLAIN_DIV
+    } else if (FAST) {
+        const float tf[3] = {bh.tfx, bh.tfy, bh.tfz}, up[3] = {S.exit_up[0], S.exit_up[1], S.exit_up[2]};
+        const float oo[3] = {ray.o.x, ray.o.y, ray.o.z}, dd[3] = {ray.d.x, ray.d.y, ray.d.z}, rc[3] = {rr.x, rr.y, rr.z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float q = div_exact3_anyzero(up[k] - oo[k], dd[k], rc[k]);
+            tn[k] = (((S.exit_far_axes >> k) & 1u) != 0u || !(dd[k] >= 0.0f)) ? tf[k] : q;
+        }
+#endif
     } else {
         const float lo[3] = {S.bound[0], S.bound[1], S.bound[2]}, hi[3] = {S.bound[4], S.bound[5], S.bound[6]};
         const float oo[3] = {ray.o.x, ray.o.y, ray.o.z}, dd[3] = {ray.d.x, ray.d.y, ray.d.z};
@@ -409,7 +431,7 @@ PT_DEV float cell1_exit(const Ray& ray, const BoxHit& bh, const GridArgs& S) {
 // distinct triangles are conflict-free).  In a closed room 5-7 of cornell.xml's 12 triangles survive the sweep.  Same predicates, same
 // arithmetic, same order within a lane (ties on t go to the lower index exactly as in the reference's loop).
 template <int KIND, bool ANY, int RULE = TRI_A10, bool FAST = false, bool FLAG_ONLY = false, bool LANES = false>
-PT_DEV Hit trace_cell1(const Ray& ray, const BoxHit& bh, const GridArgs& S) {
+PT_DEV Hit trace_cell1(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const GridArgs& S) {   // rr: ray_rcp<FAST>(ray), the caller's
     Hit ch;
     ch.idx = UINT32_MAX;
     ch.t = ray.maxt;
@@ -418,7 +440,7 @@ PT_DEV Hit trace_cell1(const Ray& ray, const BoxHit& bh, const GridArgs& S) {
     SphereRay sr;
     if (KIND == SPHERES) sr = sphere_ray<FAST>(ray.d);
     const float cmin = bh.tmin;
-    const float cmax = cell1_exit(ray, bh, S);
+    const float cmax = cell1_exit<FAST>(ray, rr, bh, S);
     const uint32_t begin = __builtin_amdgcn_readfirstlane(ldc_u32(S.off, 0));
     const uint32_t end = __builtin_amdgcn_readfirstlane(ldc_u32(S.off, 1));
     bool done = false;
@@ -663,7 +685,7 @@ PT_DEV Hit trace_dda(const Ray& ray, const BoxHit& bh, const GridArgs& S, bool& 
 
 template <int KIND, bool ANY, int RULE = TRI_A10, bool FAST = false>
 PT_DEV Hit trace_set(const Ray& ray, const BoxHit& bh, const GridArgs& S, bool& defer) {
-    if (S.n == 1u) return trace_cell1<KIND, ANY, RULE, FAST>(ray, bh, S);
+    if (S.n == 1u) return trace_cell1<KIND, ANY, RULE, FAST>(ray, ray_rcp<FAST>(ray), bh, S);
     return trace_dda<KIND, ANY, RULE, FAST>(ray, bh, S, defer);
 }
 

@@ -322,7 +322,8 @@ MIRT_API int mirt_debug_prepared(mirt_ctx* ctx, mirt_buf* positions, uint32_t co
  * rounded division over `count` generated (n, d) pairs; `out16` receives 16 uint64 (see k_divCheck).
  * mode 0/1/2: random pairs inside the windows; 3: all 2^32 denominators of the reciprocal; 4: every numerator mantissa
  * against the `count` denominator mantissas starting at `seed` (2^23 launches' worth covers all 2^46 pairs); 5: the 9-operation
- * correctly rounded sqrt over all 2^32 bit patterns (out[1] mismatches of cl_sqrt, out[2] / out[3] of the bare core / outside denormals) */
+ * correctly rounded sqrt over all 2^32 bit patterns (out[1] mismatches of cl_sqrt, out[2] / out[3] of the bare core / outside denormals);
+ * 6: the fused pass's concentric-map quotient (out[1]) and single-cell exit quotient (out[2]) over `count` operand pairs of their domains */
 MIRT_API int mirt_debug_divcheck(mirt_ctx* ctx, int mode, uint64_t seed, uint64_t count, mirt_buf* out16);
 
 /* ---- launch-bound sequences as HIP graphs ------------------------------------------------------
