@@ -299,7 +299,8 @@ bool read_grid(napi_env env, napi_value o, mirt_grid* g) {
 }
 // renderPass(ctx, {width,height,raysPerPixel,row0,nrows,bounces,passIndex,cam,sceneBounds,focalLength,lensRad,
 //                  spheres?,triangles?,meshes[],lights[{shadow,scene,light}],material,seeds,acu,pixel?,radiance?})
-// desc.nPasses: that many passes in one call (mirt_render_passes; desc.firstPass -> MIRT_PASSES_FRESH; webcl.js checks the count's range)
+// desc.nPasses: that many passes in one call (mirt_render_passes; desc.firstPass -> MIRT_PASSES_FRESH, desc.everyPass -> MIRT_PASSES_EVERY_FRAME: pixel /
+// radiance hold nPasses frames; webcl.js checks the count's range and the frame buffers' sizes)
 napi_value RenderPass(napi_env env, napi_callback_info info) {
     ARGS(2);
     void* c;
@@ -353,9 +354,12 @@ napi_value RenderPass(napi_env env, napi_callback_info info) {
     p.radiance = prop_buf(env, d, "radiance");
     bool first = false;   // desc.firstPass: initAcu folded into the pass (mirt_render_first_pass)
     { napi_value v; bool has = false; if (napi_has_named_property(env, d, "firstPass", &has) == napi_ok && has && napi_get_named_property(env, d, "firstPass", &v) == napi_ok) napi_get_value_bool(env, v, &first); }
+    bool every = false;
+    { napi_value v; bool has = false; if (napi_has_named_property(env, d, "everyPass", &has) == napi_ok && has && napi_get_named_property(env, d, "everyPass", &v) == napi_ok) napi_get_value_bool(env, v, &every); }
     uint32_t n_passes = 0;
     int rc;
-    if (prop_u32(env, d, "nPasses", &n_passes)) rc = mirt_render_passes((mirt_ctx*)c, &p, n_passes, first ? MIRT_PASSES_FRESH : 0u);
+    if (prop_u32(env, d, "nPasses", &n_passes))
+        rc = mirt_render_passes((mirt_ctx*)c, &p, n_passes, (first ? MIRT_PASSES_FRESH : 0u) | (every ? MIRT_PASSES_EVERY_FRAME : 0u));
     else rc = first ? mirt_render_first_pass((mirt_ctx*)c, &p) : mirt_render_pass((mirt_ctx*)c, &p);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);

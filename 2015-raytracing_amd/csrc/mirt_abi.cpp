@@ -919,7 +919,7 @@ int mirt_kernel_set_arg_buf(mirt_kernel* k, unsigned index, mirt_buf* buf) try {
 // sceneRender}, any number of {bouncePaths, closest-hit kernels, per-light block}, copyToPixel -- it runs the pass as ONE launch of
 // k_fusedPass (render_pass_impl) + the recorded copyToPixel.  Anything else (a different order, mixed buffers, a read / write / release /
 // other command in between) flushes the held enqueues one by one, unchanged.  See include/mirt.h for what the mode trades.
-static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes = 1, bool mark_start = true);
+static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes = 1, bool mark_start = true, uint32_t frame = 0, bool every = false);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
 
 static bool same_f(const float* x, const float* y, int n) { return memcmp(x, y, (size_t)n * 4) == 0; }
@@ -1346,8 +1346,9 @@ static int fill_grid(mirt_ctx* ctx, const char* what, const mirt_grid* g, bool t
 }
 
 // passes > 1: that many progressive passes in one launch (mirt_render_passes), pass_index the first of them.  mark_start false: the profiling
-// interval goes on from the event an earlier pass of the same mirt_render_passes call recorded.
-static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes, bool mark_start) {
+// interval goes on from the event an earlier pass of the same mirt_render_passes call recorded.  MIRT_PASSES_EVERY_FRAME: `every` -- the launch resolves
+// in the kernel and writes all `passes` frames (pt_launch.hpp FusedArgs::every) -- or `frame`: an ordinary pass writes frame slot `frame` of pixel / radiance.
+static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes, bool mark_start, uint32_t frame, bool every) {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_pass: unknown context");
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: descriptor size mismatch");
     if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: empty image");
@@ -1423,18 +1424,35 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     if (d->acu && (rc = need(ctx, "acu", d->acu, nrays * kAcuBytes))) return rc;
     A.seeds = (int32_t*)d->seeds->ptr;
     A.acu = d->acu ? d->acu->ptr : nullptr;
-    if (d->pixel && (rc = need(ctx, "pixel", d->pixel, npix * 4))) return rc;
-    if (d->radiance && (rc = need(ctx, "radiance", d->radiance, npix * 16))) return rc;
+    const uint64_t frames = every ? passes : (uint64_t)frame + 1u;   // frames the pixel / radiance buffers hold, back to back
+    if (d->pixel && (rc = need(ctx, "pixel", d->pixel, npix * 4 * frames))) return rc;
+    if (d->radiance && (rc = need(ctx, "radiance", d->radiance, npix * 16 * frames))) return rc;
+    void* const pixel_ptr = d->pixel ? (char*)d->pixel->ptr + (size_t)frame * npix * 4 : nullptr;
+    void* const radiance_ptr = d->radiance ? (char*)d->radiance->ptr + (size_t)frame * npix * 16 : nullptr;
+    if (every && !resolve_in_pass) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: a frame after every pass in one launch needs a pass that resolves in the kernel");
+    void* carry[2] = {nullptr, nullptr};   // every frame, more than 256 rays per pixel: the segments' sums, alternated (below)
     A.seg_off = 0u;
     A.seg_len = A.rpp;   // one segment: the whole pass (FusedArgs::seg_off)
     A.seg_pitch = 256u;
     if (resolve_in_pass) {
         A.resolve = 1u;
-        A.pixel = d->pixel ? d->pixel->ptr : nullptr;
-        A.radiance = d->radiance ? d->radiance->ptr : nullptr;
+        A.pixel = pixel_ptr;
+        A.radiance = radiance_ptr;
         A.res_m = res_m;
         if (passes == 1u && ctx->res_m_override == ctx->res_m_override) A.res_m = ctx->res_m_override;   // (not a NaN: try_fuse_pass hands over the recorded copyToPixel's own factor)
-        if (A.rpp > 256u && !A.radiance) {   // a pixel of more than 256 rays: its sums travel from launch to launch through memory (FusedArgs::seg_off)
+        if (every) {
+            A.every = 1u;
+            A.pass_index = d->pass_index;
+            // A pixel of more than 256 rays: segment i of every pass goes on from the sums segment i - 1 left for that pass.  An optimistic block may write
+            // pass p's sums and defer in a later pass, and the redo launch must read what the optimistic one read: so the sums alternate between two arrays
+            // of `passes` frames (FusedArgs::carry), segment i writing carry[(nseg - 1 - i) & 1] -- the last one carry[0], the caller's radiance or scratch.
+            if (A.rpp > 256u) {
+                const size_t fb = (size_t)passes * npix * 16;
+                if ((rc = ensure_scratch(ctx, A.radiance ? fb : 2 * fb))) return rc;
+                carry[0] = A.radiance ? A.radiance : ctx->scratch;
+                carry[1] = (char*)ctx->scratch + (A.radiance ? 0 : fb);
+            }
+        } else if (A.rpp > 256u && !A.radiance) {   // a pixel of more than 256 rays: its sums travel from launch to launch through memory (FusedArgs::seg_off)
             if ((rc = ensure_scratch(ctx, (size_t)npix * 16))) return rc;
             A.radiance = ctx->scratch;
         }
@@ -1454,14 +1472,20 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     // on from the sums the one before left.  Every launch of the plan has its own region of the deferred-block mask, one bit per block.
     const auto seg_words = [&](uint32_t len) { return (uint32_t)((((uint64_t)npix * len + 255) / 256 + 31) / 32); };
     uint64_t resolve_words = 0;
+    uint32_t nseg = 0, seg_i = 0;
     if (resolve_in_pass)
-        for (uint32_t off = 0, len; off < A.rpp; off += len) { len = pt::fused_segment(A.rpp, off); resolve_words += seg_words(len); }
+        for (uint32_t off = 0, len; off < A.rpp; off += len) { len = pt::fused_segment(A.rpp, off); resolve_words += seg_words(len); ++nseg; }
     void* const pixel_out = A.pixel;
     const auto set_segment = [&](uint32_t off) {
         A.seg_off = off;
         A.seg_len = pt::fused_segment(A.rpp, off);
         A.seg_pitch = A.seg_len == 256u && A.rpp > 256u ? A.rpp : 256u;
         A.pixel = off + A.seg_len == A.rpp ? pixel_out : nullptr;
+        if (carry[0]) {   // (every frame, the segment plan: see above)
+            A.radiance = carry[(nseg - 1u - seg_i) & 1u];
+            A.carry = carry[(nseg - seg_i) & 1u];
+            ++seg_i;
+        }
     };
     if (optimistic) {
         // optimistic kernel (exact cheap divisions inside their window) + exact kernel over the samples that left the window:
@@ -1509,8 +1533,7 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     if (!resolve_in_pass && (d->pixel || d->radiance)) {
         float m = res_m;
         if (passes == 1u && ctx->res_m_override == ctx->res_m_override) m = ctx->res_m_override;
-        pt::launch_copyToPixel(ctx->stream, d->pixel ? d->pixel->ptr : nullptr, A.acu, m, (uint32_t)npix, A.rpp, (uint32_t)npix,
-                               d->radiance ? d->radiance->ptr : nullptr);
+        pt::launch_copyToPixel(ctx->stream, pixel_ptr, A.acu, m, (uint32_t)npix, A.rpp, (uint32_t)npix, radiance_ptr);
     }
     if (ctx->profiling && !ctx->capturing) { HIPCHK(ctx, hipEventRecord(ctx->pe[2], ctx->stream)); ctx->pe_valid = true; }
     HIPCHK(ctx, hipGetLastError());
@@ -1530,7 +1553,7 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
     FLUSH_PENDING(ctx);
     NOT_WHILE_CAPTURING(ctx, "mirt_render_passes");
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: descriptor size mismatch");
-    if (flags & ~MIRT_PASSES_FRESH) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: unknown flags 0x%x", flags);
+    if (flags & ~(MIRT_PASSES_FRESH | MIRT_PASSES_EVERY_FRAME)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: unknown flags 0x%x", flags);
     if (n_passes < 1u || n_passes > MIRT_MAX_PASSES_PER_CALL)
         return fail(ctx, MIRT_E_ARG, "mirt_render_passes: n_passes %u outside 1..%u (one launch lasts about n_passes single passes)", n_passes, MIRT_MAX_PASSES_PER_CALL);
     if (d->pass_index > UINT32_MAX - (n_passes - 1u)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: pass_index %u + %u passes overflows", d->pass_index, n_passes);
@@ -1542,11 +1565,27 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
         return fail(ctx, MIRT_E_ARG, "mirt_render_passes: acu may only be NULL with MIRT_PASSES_FRESH, a pixel or radiance buffer and rays_per_pixel > 1 dividing 256 "
                                      "or above 256, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", fresh ? "fresh" : "NOT fresh",
                     d->rays_per_pixel, d->pixel || d->radiance ? "" : ", no output buffer");
-    if (!single) return render_pass_impl(ctx, d, fresh, n_passes);
+    // MIRT_PASSES_EVERY_FRAME: pixel / radiance hold n_passes frames; both are checked before anything runs
+    const bool every = (flags & MIRT_PASSES_EVERY_FRAME) != 0u;
+    if (every) {
+        if (!d->pixel && !d->radiance) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: MIRT_PASSES_EVERY_FRAME needs a pixel or radiance buffer for the frames");
+        const uint64_t npix = (uint64_t)(d->nrows ? d->nrows : d->height) * d->width;
+        if (d->pixel && live_has(d->pixel) && (uint64_t)d->pixel->bytes < npix * 4 * n_passes)
+            return fail(ctx, MIRT_E_ARG, "mirt_render_passes: pixel holds %zu bytes, %u frames of %llu pixels need %llu", d->pixel->bytes, n_passes,
+                        (unsigned long long)npix, (unsigned long long)(npix * 4 * n_passes));
+        if (d->radiance && live_has(d->radiance) && (uint64_t)d->radiance->bytes < npix * 16 * n_passes)
+            return fail(ctx, MIRT_E_ARG, "mirt_render_passes: radiance holds %zu bytes, %u frames of %llu pixels need %llu", d->radiance->bytes, n_passes,
+                        (unsigned long long)npix, (unsigned long long)(npix * 16 * n_passes));
+    }
+    if (!single && !every) return render_pass_impl(ctx, d, fresh, n_passes);
+    // every frame from one launch where the passes resolve in the kernel (render_pass_impl's resolve_in_pass with a frame buffer)
+    const bool in_kernel = ctx->inpass_resolve && (d->acu ? pt::fused_resolves_with_acu(d->rays_per_pixel, true) : fresh && pt::fused_resolves(d->rays_per_pixel, true));
+    if (every && !single && n_passes > 1u && in_kernel) return render_pass_impl(ctx, d, fresh, n_passes, true, 0u, true);
+    // elsewhere ordinary passes, each writing its own frame slot when every frame is asked for
     mirt_pass_desc p = *d;
     for (uint32_t i = 0; i < n_passes; ++i) {
         p.pass_index = d->pass_index + i;
-        const int rc = render_pass_impl(ctx, &p, fresh && i == 0u, 1u, i == 0u);
+        const int rc = render_pass_impl(ctx, &p, fresh && i == 0u, 1u, i == 0u, every ? i : 0u);
         if (rc) return rc;
     }
     return MIRT_OK;

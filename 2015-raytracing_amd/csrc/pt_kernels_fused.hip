@@ -491,6 +491,53 @@ PT_DEV void resolve_block(const FusedArgs& A, const float* rows, uint32_t blk, u
     }
 }
 
+// resolve_block with its inputs spelled out, for a launch that writes a frame after every pass (FusedArgs::every): the chain goes on from `carry` and
+// writes `radiance` / `pixel` (either may be null) with the tone factor `res_m`.  (A copy, not a generalisation: the single-frame kernels keep
+// resolve_block's instructions -- routed through this function the compiler schedules their resolve differently.)
+PT_DEV void resolve_rows(const FusedArgs& A, const float* rows, uint32_t blk, uint64_t n_local, const float* carry, void* radiance, void* pixel, float res_m) {
+    const uint32_t rpp = A.rpp, per = A.seg_len, ppb = 256u / per;   // per: the rays of ONE pixel this block holds (FusedArgs::seg_len)
+    const uint32_t pix0 = blk * ppb, npix = (uint32_t)(n_local / rpp);
+#if PT_RESOLVE_PRIO
+    // The sums are chains of dependent additions (256 long at 256 rays per pixel, on four lanes) at the very end of a block whose other waves
+    // have left: until the chain ends the block's LDS and this wave's slot are held.  At the top priority the chain's instructions issue as they
+    // become ready instead of waiting their turn among the SIMD's other waves.
+    __builtin_amdgcn_s_setprio(3);
+#endif
+    for (uint32_t q = threadIdx.x; q < 4u * ppb; q += 256u) {   // whole quads: 4 ppb is a multiple of 4, and so is every q - threadIdx.x
+        const uint32_t j = q >> 2, c = q & 3u;
+        const float* r = rows + c * 256u + j * per;
+        float s = 0.0f;
+        // a later segment of a pixel of more than 256 rays: the chain goes on from the sum over the segments before it (FusedArgs::seg_off)
+        if (A.seg_off != 0u && pix0 + j < npix) s = carry[4u * (size_t)(pix0 + j) + c];
+        if (per >= 4u) {
+            const float4* r4 = (const float4*)r;   // 16-byte aligned: the rows are, and `per` is a multiple of 4 (a power of two)
+            for (uint32_t i = 0; i < per / 4u; ++i) { const float4 v = r4[i]; s += v.x; s += v.y; s += v.z; s += v.w; }
+        } else {
+            for (uint32_t i = 0; i < per; ++i) s += r[i];
+        }
+        const int si = (int)__float_as_uint(s);
+        const float x = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0x00, 0xf, 0xf, true));   // quad_perm [0,0,0,0]
+        const float y = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0x55, 0xf, 0xf, true));   // [1,1,1,1]
+        const float z = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0xaa, 0xf, 0xf, true));   // [2,2,2,2]
+        const float w = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0xff, 0xf, 0xf, true));   // [3,3,3,3]
+        if (c != 0u || pix0 + j >= npix) continue;
+        if (radiance) ((float4*)radiance)[pix0 + j] = make_float4(x, y, z, w);
+        if (pixel) {
+            const float sc = 255.0f * res_m;
+            const float cx = cl_clamp((x * sc) * 1.8f, 0.0f, 255.0f), cy = cl_clamp((y * sc) * 1.8f, 0.0f, 255.0f), cz = cl_clamp((z * sc) * 1.8f, 0.0f, 255.0f);
+            ((uchar4*)pixel)[pix0 + j] = make_uchar4((unsigned char)f2u(cx), (unsigned char)f2u(cy), (unsigned char)f2u(cz), 255);
+        }
+    }
+}
+// Frame p of the launch's `passes` (pixel, radiance and carry hold that many frames of nrows * width pixels).  Its factor is render_pass_impl's res_m for
+// pass pass_index + p, the same double operations: the sum of two integers below 2^32 is exact, and so the product and quotient round as the host's.
+PT_DEV void resolve_frame(const FusedArgs& A, const float* rows, uint32_t blk, uint64_t n_local, uint32_t p) {
+    const size_t at = (size_t)p * A.nrows * A.width;
+    const float m = (float)(1.0 / ((double)A.rpp * ((double)A.pass_index + (double)p)));
+    resolve_rows(A, rows, blk, n_local, A.carry ? (const float*)A.carry + 4u * at : nullptr, A.radiance ? (void*)((float4*)A.radiance + at) : nullptr,
+                 A.pixel ? (void*)((uchar4*)A.pixel + at) : nullptr, m);
+}
+
 #ifndef PT_FUSED_WAVES
 #define PT_FUSED_WAVES 6   // waves per SIMD the register allocator must leave room for (A/B without SLP packing: 5 -> 182.8 ms, 6 -> 178.3, 7 -> 181.0, 8 -> 192.1)
 #endif
@@ -547,8 +594,10 @@ PT_DEV float* reuse_rows() {   // [word][lane]: p.xyz, n.xyz, material id, the l
     return &reuse_mem[0][threadIdx.x];
 }
 // SEG: the general form of the ray ids of a launch's segment (seg_ray); false for every contiguous one.
-template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0, bool SEG = false>
+// EVERY: a frame after every pass (FusedArgs::every): instantiated for resolving launches of several passes only.
+template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0, bool SEG = false, bool EVERY = false>
 __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_GRIDS : (FAST ? PT_FUSED_WAVES_FAST : PT_FUSED_WAVES))) k_fusedPass(const FusedArgs A, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
+    static_assert(!EVERY || (MULTI != 0 && PT_PARK_LDS), "a frame after every pass resolves from the park rows of the multi-pass loop");
     const uint64_t n_local = (uint64_t)A.nrows * A.width * A.rpp;
     stage_block<FAST, GRIDS>(A);
     // Exact kernel in redo mode (`redo_mask`: the bits the optimistic kernel set): one thread per 32-sample word, a loop over its
@@ -684,6 +733,26 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
       }
         direct_all<FAST, GRIDS, Park>(P, poi, seed, acc, park, defer);
     }
+#if PT_PARK_LDS
+    if constexpr (EVERY) if (pass + 1u < A.passes) {
+        // The frame after this pass, from the park rows as they stand.  The first barrier makes every lane's accumulator final in LDS, and the block's
+        // verdict with it: an optimistic block that has deferred leaves now (the exact kernel re-runs it whole from the seeds and accumulators it
+        // started with, every frame included) and saves its remaining passes.  Lanes past the end of the tile ride along and the redo loop is
+        // block-uniform, so every thread reaches both barriers.  The second keeps the next pass's light out of the rows until the sums have read them.
+        if (FAST && defer) pt_blk_defer[0] = 1u;
+        __syncthreads();
+        if (FAST && pt_blk_defer[0] != 0u) {
+            if (threadIdx.x == 0u) atomicOr(&defer_mask[blockIdx.x >> 5], 1u << (blockIdx.x & 31u));
+            return;
+        }
+        const uint32_t blk = FAST || stride != 256u ? blockIdx.x : blockIdx.x * 32u + (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(todo));
+        resolve_frame(P, &park_mem[0][0], blk, n_local, pass);
+#if PT_RESOLVE_PRIO
+        __builtin_amdgcn_s_setprio(0);   // (resolve_rows raised it for its chain; the next pass's path runs at the usual priority)
+#endif
+        __syncthreads();
+    }
+#endif
     if (!MULTI || ++pass == A.passes) break;
 #if PT_PARK_LDS
     park.put(4, 1.0f); park.put(5, 1.0f); park.put(6, 1.0f);   // the next pass's path starts unattenuated; the accumulator goes on
@@ -716,7 +785,8 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
         }
         // the block of the launch: wave-uniform (blockIdx alone in the optimistic kernel; the marked block of this trip in the redo loop)
         const uint32_t blk = FAST || stride != 256u ? blockIdx.x : blockIdx.x * 32u + (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(todo));
-        resolve_block(A, &park_mem[0][0], blk, n_local);
+        if constexpr (EVERY) resolve_frame(A, &park_mem[0][0], blk, n_local, A.passes - 1u);
+        else resolve_block(A, &park_mem[0][0], blk, n_local);
         if (FAST) return;
         __syncthreads();   // the redo loop's next block parks into the same rows
         continue;
@@ -756,7 +826,10 @@ __global__ void __launch_bounds__(256) k_deferCount(const uint32_t* mask, uint32
 static bool multipass_reuse(bool grids) { const char* e = getenv("MIRT_MULTIPASS_REUSE"); return e && e[0] ? e[0] != '0' : !grids; }
 template <bool FAST, int GRIDS, int WAVES, bool SEG>
 static void launch_seg(const dim3& grid, size_t lds, hipStream_t s, const FusedArgs& b, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
-    if (b.passes > 1u && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    const bool every = b.every != 0u && b.resolve != 0u && b.passes > 1u;   // a frame after every pass (FusedArgs::every)
+    if (every && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2, SEG, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    else if (every) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1, SEG, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    else if (b.passes > 1u && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
     else if (b.passes > 1u) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
     else hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 0, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
 }

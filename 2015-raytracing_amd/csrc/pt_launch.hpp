@@ -112,6 +112,14 @@ struct FusedArgs {
     // kernel, and is written once at the end; `fresh` applies to the first of them, `res_m` to the frame after the last.  > 1 picks the MULTI
     // instantiations of k_fusedPass; 0 and 1 run the single-pass kernels, which never read it.
     uint32_t passes;
+    // A frame after EVERY pass of such a launch (mirt_render_passes with MIRT_PASSES_EVERY_FRAME; `every` != 0 in resolving launches with passes > 1
+    // only): `pixel` and `radiance` then hold `passes` frames of nrows * width pixels back to back, frame p the one after pass p, tone-scaled by
+    // 1 / (rpp * (pass_index + p)) -- worked out in the kernel in double, as the host works out res_m.  A later segment of a pixel of more than 256
+    // rays goes on from `carry` (`passes` frames of the sums the segments before it left) instead of from `radiance`: the optimistic and the redo
+    // launch of a segment read the same carry, which neither of them writes.
+    uint32_t every;
+    uint32_t pass_index;     // the 1-based index of the launch's first pass
+    const void* carry;       // float4[passes * nrows * width]; read only by a launch with seg_off != 0
 };
 // Whether a pass with these arguments can resolve inside the kernel: rpp divides 256 (whole pixels per block), or rpp > 256 -- any count: the
 // segment plan below covers it -- and somewhere to put the result.  A frame's first pass may then do without `acu`.

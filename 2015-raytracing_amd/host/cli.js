@@ -1,7 +1,7 @@
 #!/usr/bin/env node
 // host/cli.js -- command-line front end of the JavaScript host.
 //   node cli.js pack   <scene.xml> <width> <height> <raysPerPixel>                 -> packed kernel inputs as JSON (stdout)
-//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]]
+//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]]
 //                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|-> <width> <height> <nSlabs|0> <out.rgba>  -> RGBA8 frame of that job
@@ -40,8 +40,9 @@ if (cmd === "pack") {
   const opt = { granular: rest.includes("--granular"), graph: rest.includes("--graph"), fusion: rest.includes("--fusion"), deviceGrid: rest.includes("--device-grid"), bounces: 5, seeds: null,
                 keepAcu: !rest.includes("--no-acu"),   // --no-acu: a frame without the 16 bytes per ray: the pass resolves its own pixels (mirt.h; raysPerPixel
                                                         // dividing 256 or above 256) -- one pass, or
-                passesInOneLaunch: rest.includes("--passes-in-one-launch") };   // all of them in one call (mirt_render_passes; with --gpus, one per tile):
-                                                                                 // at most 64 without the accumulator, calls of 64 with it
+                passesInOneLaunch: rest.includes("--passes-in-one-launch"),   // all of them in one call (mirt_render_passes; with --gpus, one per tile):
+                                                                               // at most 64 without the accumulator, calls of 64 with it
+                everyPass: rest.includes("--every-pass") };   // ... and the frame after every pass k = 1..passes: <stem>.pass<k><ext> (+ .radiance.f32)
   let i;
   if ((i = rest.indexOf("--bounces")) >= 0) opt.bounces = +rest[i + 1];
   if ((i = rest.indexOf("--gpus")) >= 0) { opt.gpus = +rest[i + 1]; opt.forceRccl = rest.includes("--force-rccl"); }   // row tiles over N devices + gather
@@ -50,6 +51,14 @@ if (cmd === "pack") {
   const res = renderer.renderFile(file, w, h, rpp, passes, opt);
   writeFrame(out, res.pixel, w, h);
   fs.writeFileSync(out + ".radiance.f32", Buffer.from(res.radiance.buffer, res.radiance.byteOffset, res.radiance.byteLength));
+  if (res.frames) {
+    const ext = path.extname(out), stem = out.slice(0, out.length - ext.length), n = w * h * 4;
+    for (let k = 1; k <= res.frames.n; k++) {
+      const f = `${stem}.pass${k}${ext}`, rad = res.frames.radiance.subarray((k - 1) * n, k * n);
+      writeFrame(f, res.frames.pixel.subarray((k - 1) * n, k * n), w, h);
+      fs.writeFileSync(f + ".radiance.f32", Buffer.from(rad.buffer, rad.byteOffset, rad.byteLength));
+    }
+  }
   process.stderr.write(`rendered ${file} ${w}x${h} rpp ${rpp}, ${passes} pass(es), ${opt.granular ? (opt.fusion ? "kernel-by-kernel, passes fused by the runtime" : "kernel-by-kernel") : "fused"}: ${res.ms.toFixed(2)} ms on ${res.device}; passes the runtime fused from enqueues: ${res.fusedPasses}\n`);
   if (res.routes) process.stderr.write(`gather routes per tile: ${res.routes.join(" ")}; peer access root<-tile: ${res.peerAccess.join(" ")}\n`);
 } else if (cmd === "pack-frame" || cmd === "frame") {

@@ -293,16 +293,36 @@ class FusedRenderer {
   // n passes in one call (mirt_render_passes): the frame after the last of them, as n executeRender calls would leave it.  Starting the frame
   // it needs no accumulator where the passes resolve their own pixels (keepAcu false).  A call runs at most MAX_PASSES_PER_CALL passes: with the
   // accumulator kept, more are split into calls of that many (the frame is the same); without it a frame cannot go on after its first call
-  executePasses(n, bounces) {
+  // opt.everyPass: the frame after every pass too (MIRT_PASSES_EVERY_FRAME), into frame buffers of each call's k passes, read back after the call:
+  // readFrames() returns them all.  this.pixel / this.radiance then hold the last frame, as without it.
+  executePasses(n, bounces, opt) {
+    const every = !!(opt && opt.everyPass);
     if (!this.acu && n > MAX_PASSES_PER_CALL)
       throw new Error(`${n} passes in one launch without a per-ray accumulator: at most ${MAX_PASSES_PER_CALL} (MIRT_MAX_PASSES_PER_CALL); keep the accumulator to split them over calls`);
+    if (every) this.frames = { n: 0, pixel: new Uint8ClampedArray(n * this.npix * 4), radiance: new Float32Array(n * this.npix * 4) };
     for (let left = n; left > 0; ) {
       const k = Math.min(left, MAX_PASSES_PER_CALL);
-      this.q.renderPasses(this.passDesc(bounces), k);
+      if (!every) this.q.renderPasses(this.passDesc(bounces), k);
+      else {
+        const fp = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, k * this.npix * 4), fr = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, k * this.npix * 16);
+        try {
+          this.q.renderPasses(Object.assign(this.passDesc(bounces), { pixel: fp, radiance: fr, everyPass: true }), k);
+          const f = this.frames, px = f.pixel.subarray(f.n * this.npix * 4, (f.n + k) * this.npix * 4), rd = f.radiance.subarray(f.n * this.npix * 4, (f.n + k) * this.npix * 4);
+          this.q.enqueueReadBuffer(fp, true, 0, px.byteLength, px, []);
+          this.q.enqueueReadBuffer(fr, true, 0, rd.byteLength, rd, []);
+          this.q.finish();
+          f.n += k;
+          const last = (f.n - 1) * this.npix * 4;   // the renderer's own buffers hold the last frame
+          this.q.enqueueWriteBuffer(this.pixel, true, 0, this.npix * 4, f.pixel.subarray(last, last + this.npix * 4), []);
+          this.q.enqueueWriteBuffer(this.radiance, true, 0, this.npix * 16, f.radiance.subarray(last, last + this.npix * 4), []);
+        } finally { fp.release(); fr.release(); }
+      }
       this.passes += k;
       left -= k;
     }
   }
+  // the frames of the last executePasses(n, bounces, {everyPass: true}): { n, pixel: n RGBA8 frames, radiance: n float4 frames }, back to back
+  readFrames() { return this.frames; }
   readPixels() { const o = new Uint8ClampedArray(this.npix * 4); this.q.enqueueReadBuffer(this.pixel, false, 0, o.length, o, []); this.q.finish(); return o; }
   readRadiance() { const o = new Float32Array(this.npix * 4); this.q.enqueueReadBuffer(this.radiance, false, 0, o.byteLength, o, []); this.q.finish(); return o; }
   readAcu() { const a = new Float32Array(this.nrays * 4); this.q.enqueueReadBuffer(this.acu, false, 0, a.byteLength, a, []); this.q.finish(); return a; }
@@ -382,19 +402,22 @@ function renderFile(file, width, height, rpp, passes, opt) {
     packed = scene.packScene(sc, width, height, rpp, 1, true);
     opt = Object.assign({}, opt, { sceneObject: sc, ctx: ownCtx });
   } else packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, rpp);
-  if (opt.gpus) {
+  if (opt.everyPass && opt.gpus > 1) throw new Error("--every-pass is not available with --gpus N > 1: the gather would interleave the tiles' frames");
+  if (opt.gpus && !(opt.everyPass && opt.gpus === 1)) {
     // N contexts, one per device: each builds its own copy of the scene (the loader's soups stay on ownCtx until every tile is built)
     if (opt.sceneObject) opt.sceneObject.keepSoups = true;
     try { return renderTiled(packed, opt.gpus, passes, opt); } finally { if (ownCtx) ownCtx.release(); }
   }
+  if (opt.everyPass && !opt.passesInOneLaunch) throw new Error("--every-pass writes the frames of passes in one launch: give --passes-in-one-launch too");
   if (opt.passesInOneLaunch && opt.granular) throw new Error("passes in one launch are the fused pass's (mirt_render_passes): not with the kernel-by-kernel host");
   const R = opt.granular ? new GranularRenderer(packed, opt) : new FusedRenderer(packed, opt);
   R.q.timerStart();
-  if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces);
+  if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces, { everyPass: opt.everyPass });
   else for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
   const ms = R.q.timerStopMs();
   const res = { pixel: R.readPixels(), radiance: opt.granular ? radianceSums(R.readAcu(), rpp) : R.readRadiance(), ms: ms,
                 device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: R.ctx.fusedPasses ? R.ctx.fusedPasses() : 0 };
+  if (opt.everyPass) res.frames = R.readFrames();
   R.release();
   if (ownCtx) ownCtx.release();
   return res;

@@ -176,9 +176,17 @@ class WebCLCommandQueue {
   // n passes from desc.passIndex on in one call (mirt_render_passes): the frame after the last of them; desc.firstPass starts the frame, and then
   // desc.acu may be null where the passes resolve their own pixels (rays_per_pixel > 1 dividing 256, or above 256: mirt.h).
   // At most MAX_PASSES_PER_CALL (checked here: the addon reads the count as a uint32, which would wrap)
+  // desc.everyPass: the frame after every pass too (MIRT_PASSES_EVERY_FRAME): desc.pixel / desc.radiance hold n frames back to back (checked here)
   renderPasses(desc, n) {
     if (!Number.isInteger(n) || n < 1 || n > MAX_PASSES_PER_CALL)
       throw new WebCLException("INVALID_VALUE", "renderPasses: the pass count is an integer in 1.." + MAX_PASSES_PER_CALL + " (MIRT_MAX_PASSES_PER_CALL), not " + n);
+    if (desc.everyPass) {
+      const npix = (desc.nrows || desc.height) * desc.width;
+      if (!desc.pixel && !desc.radiance) throw new WebCLException("INVALID_VALUE", "renderPasses: everyPass needs a pixel or radiance buffer for the frames");
+      for (const [name, b, per] of [["pixel", desc.pixel, 4], ["radiance", desc.radiance, 16]])
+        if (b && b.byteLength < n * npix * per)
+          throw new WebCLException("INVALID_BUFFER_SIZE", `renderPasses: ${name} holds ${b.byteLength} bytes, ${n} frames of ${npix} pixels need ${n * npix * per}`);
+    }
     this.renderPass(Object.assign({}, desc, { nPasses: n }));
   }
   // ---- extension: the host's grid builders on the device (mirt_grid_build / mirt_grid_gather_*) ----

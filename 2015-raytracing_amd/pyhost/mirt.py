@@ -59,6 +59,7 @@ class _PassDesc(C.Structure):
 _lib = None
 
 PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
+PASSES_EVERY_FRAME = 2   # MIRT_PASSES_EVERY_FRAME (include/mirt.h)
 
 # name -> (restype, argtypes): every symbol include/mirt.h declares
 SYMBOLS = {
@@ -400,10 +401,12 @@ class Context:
         f = lib().mirt_render_first_pass if fresh else lib().mirt_render_pass
         self._chk(f(self.h, C.byref(desc)))
 
-    def render_passes(self, desc, n_passes, fresh=False):
+    def render_passes(self, desc, n_passes, fresh=False, every_frame=False):
         """n_passes progressive passes from desc.pass_index on in one call (mirt_render_passes); fresh: the first of them starts the frame
-        (MIRT_PASSES_FRESH: acu is not read, and may be None where the passes resolve their own pixels)."""
-        self._chk(lib().mirt_render_passes(self.h, C.byref(desc), int(n_passes), PASSES_FRESH if fresh else 0))
+        (MIRT_PASSES_FRESH: acu is not read, and may be None where the passes resolve their own pixels).  every_frame: desc.pixel / desc.radiance
+        hold n_passes frames back to back, the frame after each pass (MIRT_PASSES_EVERY_FRAME)."""
+        flags = (PASSES_FRESH if fresh else 0) | (PASSES_EVERY_FRAME if every_frame else 0)
+        self._chk(lib().mirt_render_passes(self.h, C.byref(desc), int(n_passes), flags))
 
     def destroy(self):
         if self.h:

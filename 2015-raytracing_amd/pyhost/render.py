@@ -236,19 +236,43 @@ class FusedRenderer:
         self.ctx.render_pass(d, fresh=fresh)
         self.passes += 1
 
-    def execute_passes(self, n, bounces=5, fresh=False):
+    def execute_passes(self, n, bounces=5, fresh=False, every_frame=False):
         """n progressive passes in one call (mirt_render_passes): the frame after the last of them, as n execute_render calls would leave it.
-        fresh: the first of them starts the frame; then keep_acu False is enough where the passes resolve their own pixels."""
+        fresh: the first of them starts the frame; then keep_acu False is enough where the passes resolve their own pixels.
+        every_frame: the frame after EVERY pass as well (MIRT_PASSES_EVERY_FRAME), into n-frame buffers this renderer owns; returns them as
+        (n, npix, 4) uint8 pixels and float32 radiance sums (None without want_radiance).  self.pixel / self.radiance hold the last frame."""
         if not self.nrays:
             self.passes += n
-            return
-        d = self.dev.pass_desc(self.seeds, self.acu, self.pixel, self.radiance, pass_index=self.passes, bounces=bounces,
-                               row0=self.row0, nrows=self.nrows)
-        self.ctx.render_passes(d, n, fresh=fresh)
+            return (np.zeros((n, 0, 4), np.uint8), None if self.radiance is None else np.zeros((n, 0, 4), np.float32)) if every_frame else None
+        pixel, radiance = self.pixel, self.radiance
+        if every_frame:
+            pixel = self._frames("_frame_pixel", n * self.npix * 4)
+            radiance = None if self.radiance is None else self._frames("_frame_radiance", n * self.npix * 16)
+        d = self.dev.pass_desc(self.seeds, self.acu, pixel, radiance, pass_index=self.passes, bounces=bounces, row0=self.row0, nrows=self.nrows)
+        self.ctx.render_passes(d, n, fresh=fresh, every_frame=every_frame)
         self.passes += n
+        if not every_frame:
+            return None
+        pix = pixel.read(np.uint8, count=n * self.npix * 4).reshape(n, self.npix, 4)
+        self.pixel.write(pix[-1])
+        rad = None
+        if radiance is not None:
+            rad = radiance.read(np.float32, count=n * self.npix * 4).reshape(n, self.npix, 4)
+            self.radiance.write(rad[-1])
+        return pix, rad
+
+    def _frames(self, name, nbytes):
+        """a frame buffer of at least nbytes, kept for the next call"""
+        b = getattr(self, name, None)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.release()
+            b = self.ctx.buffer(nbytes)
+            setattr(self, name, b)
+        return b
 
     def release(self):
-        for b in (self.seeds, self.acu, self.pixel, self.radiance):
+        for b in (self.seeds, self.acu, self.pixel, self.radiance, getattr(self, "_frame_pixel", None), getattr(self, "_frame_radiance", None)):
             if b:
                 b.release()
         self.dev.release()

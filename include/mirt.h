@@ -206,7 +206,7 @@ MIRT_API int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
  * bit for bit in every buffer the caller passes (seeds, acu if given, pixel, radiance), this sequence:
  *   mirt_render_first_pass (flags & MIRT_PASSES_FRESH) or mirt_render_pass, at desc->pass_index;
  *   then mirt_render_pass at pass_index + 1 .. pass_index + n_passes - 1.
- * Pixel and radiance are those of the last pass (tone factor 1 / (rays_per_pixel * (pass_index + n_passes - 1))).  Passes interact only through a
+ * Pixel and radiance are those of the last pass (MIRT_PASSES_EVERY_FRAME: of every pass, below) (tone factor 1 / (rays_per_pixel * (pass_index + n_passes - 1))).  Passes interact only through a
  * ray's own seed and its own accumulator, so one launch runs every sample through all n_passes passes, the accumulator on chip, and writes the
  * seeds (and `acu`) once: a multi-pass frame needs no per-ray accumulator and moves none between the passes.
  * `acu` may be NULL exactly where a first pass may do without it: MIRT_PASSES_FRESH, a pixel or radiance buffer, rays_per_pixel dividing 256 or
@@ -216,6 +216,15 @@ MIRT_API int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
  * to the exact kernel in the same unit as for one pass -- such a sample re-runs all of its passes; mirt_pass_timing covers the whole call.
  * Not while capturing (MIRT_E_ARG). */
 #define MIRT_PASSES_FRESH 1u            /* the batch starts the frame: acu starts at zero and is not read */
+/* A frame after EVERY pass (A10 code.js:1806-1854 shows one after each executeRender): `pixel` then holds n_passes RGBA8 frames back to back, frame p at
+ * byte p * npix * 4, and `radiance` n_passes float4 frames, frame p at byte p * npix * 16 (npix: the tile's pixels).  Either may be NULL, not both.  Frame p
+ * equals, bit for bit, pixel / radiance after the (p+1)-th call of the ordinary sequence above, tone factor 1 / (rays_per_pixel * (pass_index + p));
+ * seeds and acu end as without the flag.  Where the passes resolve in the kernel (see mirt_render_first_pass: rays_per_pixel > 1 dividing 256 or above
+ * 256, fresh and acu-free, or with acu at the counts that resolve beside it) every frame comes from the same launch(es), the sums of a pixel of more than
+ * 256 rays alternating between two carry arrays of n_passes frames (the caller's radiance and context scratch); elsewhere the call queues n_passes
+ * ordinary passes, each writing its frame slot.  A buffer smaller than n_passes frames is MIRT_E_ARG and nothing runs.  A library without the flag
+ * answers it with MIRT_E_ARG (unknown flags): that is how a host detects it. */
+#define MIRT_PASSES_EVERY_FRAME 2u
 #define MIRT_MAX_PASSES_PER_CALL 64u
 MIRT_API int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* desc, uint32_t n_passes, uint32_t flags);
 /* Two ways to run the pass, identical results.  Default: the optimistic pair -- a kernel whose divisions are 3-operation
