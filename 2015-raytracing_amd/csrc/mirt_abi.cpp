@@ -919,7 +919,18 @@ int mirt_kernel_set_arg_buf(mirt_kernel* k, unsigned index, mirt_buf* buf) try {
 // sceneRender}, any number of {bouncePaths, closest-hit kernels, per-light block}, copyToPixel -- it runs the pass as ONE launch of
 // k_fusedPass (render_pass_impl) + the recorded copyToPixel.  Anything else (a different order, mixed buffers, a read / write / release /
 // other command in between) flushes the held enqueues one by one, unchanged.  See include/mirt.h for what the mode trades.
-static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes = 1, bool mark_start = true, uint32_t frame = 0, bool every = false);
+// How render_pass_impl runs a pass.  passes > 1: that many progressive passes in one launch (mirt_render_passes), pass_index the first of them.
+// mark_start false: the profiling interval goes on from the event an earlier pass of the same mirt_render_passes call recorded.
+// MIRT_PASSES_EVERY_FRAME: `every` -- the launch resolves in the kernel and writes all `passes` frames (pt_launch.hpp FusedArgs::every) -- or
+// `frame`: an ordinary pass writes frame slot `frame` of pixel / radiance.
+struct PassOpts {
+    bool fresh = false;
+    uint32_t passes = 1;
+    bool mark_start = true;
+    uint32_t frame = 0;
+    bool every = false;
+};
+static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
 
 static bool same_f(const float* x, const float* y, int n) { return memcmp(x, y, (size_t)n * 4) == 0; }
@@ -1046,7 +1057,7 @@ static int try_fuse_pass(mirt_ctx* ctx, std::vector<mirt_ctx::Pending>& P) {
     // its factor as the host passed it; where it cannot, render_pass_impl queues the separate kernel behind the pass, with that factor
     d.pixel = PB(i, 0);
     ctx->res_m_override = PF(i, 2);
-    int rc = render_pass_impl(ctx, &d, false);
+    int rc = render_pass_impl(ctx, &d, PassOpts{});
     ctx->res_m_override = NAN;
     if (rc && rc != MIRT_E_DEVICE) return 1;   // refused before anything was launched (a size, a grid that fails validation ...): run the stream as issued,
     if (rc) return rc;                          // whose own checks then report it against the kernel that trips it
@@ -1345,10 +1356,22 @@ static int fill_grid(mirt_ctx* ctx, const char* what, const mirt_grid* g, bool t
     return MIRT_OK;
 }
 
-// passes > 1: that many progressive passes in one launch (mirt_render_passes), pass_index the first of them.  mark_start false: the profiling
-// interval goes on from the event an earlier pass of the same mirt_render_passes call recorded.  MIRT_PASSES_EVERY_FRAME: `every` -- the launch resolves
-// in the kernel and writes all `passes` frames (pt_launch.hpp FusedArgs::every) -- or `frame`: an ordinary pass writes frame slot `frame` of pixel / radiance.
-static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, uint32_t passes, bool mark_start, uint32_t frame, bool every) {
+// what the plan of a pass is asked for (pt_pass_plan.hpp), from the descriptor as the caller gave it
+static pt::PassRequest pass_request(const mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o) {
+    pt::PassRequest r;
+    r.rpp = d->rays_per_pixel;
+    r.npix = (uint64_t)(d->nrows ? d->nrows : d->height) * d->width;
+    r.passes = o.passes;
+    r.fresh = o.fresh;
+    r.has_acu = d->acu != nullptr;
+    r.has_pixel = d->pixel != nullptr;
+    r.has_radiance = d->radiance != nullptr;
+    r.every = o.every;
+    r.inpass_resolve = ctx->inpass_resolve;
+    return r;
+}
+
+static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o) {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_pass: unknown context");
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: descriptor size mismatch");
     if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: empty image");
@@ -1380,10 +1403,11 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     A.width = d->width; A.height = d->height; A.rpp = d->rays_per_pixel;
     A.row0 = d->row0; A.nrows = nrows; A.bounces = d->bounces;
     A.n_lights = d->n_lights;
-    A.fresh = fresh ? 1u : 0u;
-    A.passes = passes;
-    // the frame after the last pass: 1 / (rpp * passes so far), A10 code.js:1412
-    const float res_m = (float)(1.0 / ((double)d->rays_per_pixel * ((double)d->pass_index + (double)(passes - 1u))));
+    A.fresh = o.fresh ? 1u : 0u;
+    A.passes = o.passes;
+    // the frame after the last pass: 1 / (rpp * passes so far), A10 code.js:1412 -- or the recorded copyToPixel's own factor, which try_fuse_pass hands over (not a NaN)
+    const float res_m = o.passes == 1u && ctx->res_m_override == ctx->res_m_override ? ctx->res_m_override
+                                                                                     : (float)(1.0 / ((double)d->rays_per_pixel * ((double)d->pass_index + (double)(o.passes - 1u))));
     int rc;
     if (d->spheres && (rc = fill_grid(ctx, "spheres", d->spheres, false, true, &A.sets[A.n_sets++]))) return rc;
     if (d->triangles && (rc = fill_grid(ctx, "triangles", d->triangles, true, true, &A.sets[A.n_sets++]))) return rc;
@@ -1411,88 +1435,53 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     A.material = d->material->ptr;
     A.nmat = (uint32_t)(d->material->bytes / 16);
     if ((rc = need(ctx, "seeds", d->seeds, nrays * 4))) return rc;
-    // copyToPixel inside the pass: a frame's first pass at a ray count that divides 256 or is above 256 (pt_launch.hpp fused_resolves: the segment
-    // plan).  Then -- and only then -- `acu` is optional: without it nothing per ray but the seed touches memory.  With `acu`, only at the counts
-    // of fused_resolves_with_acu; elsewhere the accumulator is written and the separate copyToPixel reads it back.
+    // what is launched, worked out once (pt_pass_plan.hpp): whether the pass resolves its own pixels -- then, and only then, `acu` is optional --
+    // its segments, the mask and the scratch buffer
+    const pt::PassPlan plan = pt::pass_plan(pass_request(ctx, d, o));
     const bool want_out = d->pixel || d->radiance;
-    const bool resolve_in_pass = ctx->inpass_resolve && (d->acu ? pt::fused_resolves_with_acu(d->rays_per_pixel, want_out) : fresh && pt::fused_resolves(d->rays_per_pixel, want_out));
-    ctx->last_pass_resolved = resolve_in_pass;
-    if (!d->acu && !(resolve_in_pass && fresh))
+    ctx->last_pass_resolved = plan.resolves;
+    if (!plan.null_acu_ok)
         return fail(ctx, MIRT_E_ARG, "mirt_render_pass: acu may only be null for a frame's first pass (mirt_render_first_pass) with a pixel or radiance buffer and "
-                                     "rays_per_pixel dividing 256 or above 256, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", fresh ? "first pass" : "NOT a first pass",
+                                     "rays_per_pixel dividing 256 or above 256, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", o.fresh ? "first pass" : "NOT a first pass",
                     d->rays_per_pixel, want_out ? "" : ", no output buffer");
     if (d->acu && (rc = need(ctx, "acu", d->acu, nrays * kAcuBytes))) return rc;
     A.seeds = (int32_t*)d->seeds->ptr;
     A.acu = d->acu ? d->acu->ptr : nullptr;
-    const uint64_t frames = every ? passes : (uint64_t)frame + 1u;   // frames the pixel / radiance buffers hold, back to back
+    const uint64_t frames = o.every ? o.passes : (uint64_t)o.frame + 1u;   // frames the pixel / radiance buffers hold, back to back
     if (d->pixel && (rc = need(ctx, "pixel", d->pixel, npix * 4 * frames))) return rc;
     if (d->radiance && (rc = need(ctx, "radiance", d->radiance, npix * 16 * frames))) return rc;
-    void* const pixel_ptr = d->pixel ? (char*)d->pixel->ptr + (size_t)frame * npix * 4 : nullptr;
-    void* const radiance_ptr = d->radiance ? (char*)d->radiance->ptr + (size_t)frame * npix * 16 : nullptr;
-    if (every && !resolve_in_pass) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: a frame after every pass in one launch needs a pass that resolves in the kernel");
-    void* carry[2] = {nullptr, nullptr};   // every frame, more than 256 rays per pixel: the segments' sums, alternated (below)
-    A.seg_off = 0u;
-    A.seg_len = A.rpp;   // one segment: the whole pass (FusedArgs::seg_off)
-    A.seg_pitch = 256u;
-    if (resolve_in_pass) {
+    void* const pixel_ptr = d->pixel ? (char*)d->pixel->ptr + (size_t)o.frame * npix * 4 : nullptr;
+    void* const radiance_ptr = d->radiance ? (char*)d->radiance->ptr + (size_t)o.frame * npix * 16 : nullptr;
+    if (o.every && !plan.resolves) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: a frame after every pass in one launch needs a pass that resolves in the kernel");
+    // the column streams live in seeds[0..width): only the tile that owns row 0 holds them
+    if (A.rpp == 1 && d->row0 != 0) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: rays_per_pixel == 1 couples rows through seeds[col] (A10 code.cl:429); render it as one tile");
+    if (plan.scratch_bytes && (rc = ensure_scratch(ctx, (size_t)plan.scratch_bytes))) return rc;
+    char* const scratch = (char*)ctx->scratch;
+    if (plan.resolves) {
         A.resolve = 1u;
-        A.pixel = pixel_ptr;
-        A.radiance = radiance_ptr;
+        // a pixel of more than 256 rays: its sums travel from launch to launch through memory (FusedArgs::seg_off)
+        A.radiance = plan.sums.bytes ? scratch + plan.sums.off : radiance_ptr;
         A.res_m = res_m;
-        if (passes == 1u && ctx->res_m_override == ctx->res_m_override) A.res_m = ctx->res_m_override;   // (not a NaN: try_fuse_pass hands over the recorded copyToPixel's own factor)
-        if (every) {
+        if (o.every) {
             A.every = 1u;
             A.pass_index = d->pass_index;
-            // A pixel of more than 256 rays: segment i of every pass goes on from the sums segment i - 1 left for that pass.  An optimistic block may write
-            // pass p's sums and defer in a later pass, and the redo launch must read what the optimistic one read: so the sums alternate between two arrays
-            // of `passes` frames (FusedArgs::carry), segment i writing carry[(nseg - 1 - i) & 1] -- the last one carry[0], the caller's radiance or scratch.
-            if (A.rpp > 256u) {
-                const size_t fb = (size_t)passes * npix * 16;
-                if ((rc = ensure_scratch(ctx, A.radiance ? fb : 2 * fb))) return rc;
-                carry[0] = A.radiance ? A.radiance : ctx->scratch;
-                carry[1] = (char*)ctx->scratch + (A.radiance ? 0 : fb);
-            }
-        } else if (A.rpp > 256u && !A.radiance) {   // a pixel of more than 256 rays: its sums travel from launch to launch through memory (FusedArgs::seg_off)
-            if ((rc = ensure_scratch(ctx, (size_t)npix * 16))) return rc;
-            A.radiance = ctx->scratch;
         }
     }
-
-    if (A.rpp == 1) {
-        // the column streams live in seeds[0..width): only the tile that owns row 0 holds them
-        if (d->row0 != 0) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: rays_per_pixel == 1 couples rows through seeds[col] (A10 code.cl:429); render it as one tile");
-        if ((rc = ensure_scratch(ctx, (size_t)npix * 8))) return rc;
-        pt::launch_lensDraws(ctx->stream, A.seeds, ctx->scratch, d->width, d->height, d->width, d->height, d->row0, nrows);
-        A.uv = ctx->scratch;
+    // every frame, more than 256 rays per pixel: the two arrays the segments' sums alternate between (FusedArgs::carry, pt_pass_plan.hpp pass_segment)
+    void* const carry[2] = {plan.carry[0].bytes ? scratch + plan.carry[0].off : radiance_ptr, scratch + plan.carry[1].off};
+    if (plan.lens.bytes) {
+        A.uv = scratch + plan.lens.off;
+        pt::launch_lensDraws(ctx->stream, A.seeds, scratch + plan.lens.off, d->width, d->height, d->width, d->height, d->row0, nrows);
     }
-    if (ctx->profiling && !ctx->capturing && mark_start) HIPCHK(ctx, hipEventRecord(ctx->pe[0], ctx->stream));
+    if (ctx->profiling && !ctx->capturing && o.mark_start) HIPCHK(ctx, hipEventRecord(ctx->pe[0], ctx->stream));
     bool optimistic = pt::fused_fast_available() && !ctx->force_exact;
     for (uint32_t i = 0; i < A.n_sets; ++i) optimistic = optimistic && A.sets[i].fast_ok != 0;
-    // Resolving in the pass: one launch (or optimistic + redo pair) per segment of the plan, in ray order (pt_launch.hpp fused_segment); each goes
-    // on from the sums the one before left.  Every launch of the plan has its own region of the deferred-block mask, one bit per block.
-    const auto seg_words = [&](uint32_t len) { return (uint32_t)((((uint64_t)npix * len + 255) / 256 + 31) / 32); };
-    uint64_t resolve_words = 0;
-    uint32_t nseg = 0, seg_i = 0;
-    if (resolve_in_pass)
-        for (uint32_t off = 0, len; off < A.rpp; off += len) { len = pt::fused_segment(A.rpp, off); resolve_words += seg_words(len); ++nseg; }
-    void* const pixel_out = A.pixel;
-    const auto set_segment = [&](uint32_t off) {
-        A.seg_off = off;
-        A.seg_len = pt::fused_segment(A.rpp, off);
-        A.seg_pitch = A.seg_len == 256u && A.rpp > 256u ? A.rpp : 256u;
-        A.pixel = off + A.seg_len == A.rpp ? pixel_out : nullptr;
-        if (carry[0]) {   // (every frame, the segment plan: see above)
-            A.radiance = carry[(nseg - 1u - seg_i) & 1u];
-            A.carry = carry[(nseg - seg_i) & 1u];
-            ++seg_i;
-        }
-    };
+    uint32_t* mask = nullptr;
     if (optimistic) {
         // optimistic kernel (exact cheap divisions inside their window) + exact kernel over the samples that left the window:
         // the second launch walks the first one's bit mask on the device, so the pair is queued without a host round trip
         // one bit per sample -- or, resolving in the pass, per block of 256 samples (pt_kernels_fused.hip)
-        const uint32_t words = (uint32_t)(resolve_in_pass ? resolve_words : (nrays + 31) / 32);
-        const size_t need_bytes = 16 + (size_t)words * 4;
+        const size_t need_bytes = 16 + (size_t)plan.mask_words * 4;
         if (ctx->defer_bytes < need_bytes) {
             NOT_WHILE_CAPTURING(ctx, "growing the deferred-sample mask");
             if (ctx->defer) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->defer)); ctx->defer = nullptr; ctx->defer_bytes = 0; }
@@ -1501,40 +1490,32 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
             ctx->defer_bytes = need_bytes;
         }
         if (ctx->capturing) ctx->cap_defer = true;
-        uint32_t* mask = (uint32_t*)ctx->defer + 4;
+        mask = (uint32_t*)ctx->defer + 4;
         HIPCHK(ctx, hipMemsetAsync(ctx->defer, 0, need_bytes, ctx->stream));
-        // one pair of launches -- or, resolving in the pass, one pair per segment, each on its own region of the mask; the redo launch of a
-        // segment runs before the next segment's launches read the sums it leaves (stream order)
-        if (!resolve_in_pass) {
-            pt::launch_fused(ctx->stream, A, true, mask, nullptr, 0);
-            pt::launch_fused(ctx->stream, A, false, nullptr, mask, words);
-        } else {
-            uint32_t* region = mask;
-            for (uint32_t off = 0; off < A.rpp; off += A.seg_len) {
-                set_segment(off);
-                const uint32_t w = seg_words(A.seg_len);
-                pt::launch_fused(ctx->stream, A, true, region, nullptr, 0);
-                pt::launch_fused(ctx->stream, A, false, nullptr, region, w);
-                region += w;
-            }
+    }
+    // One launch -- optimistic: one pair of launches -- per segment of the plan, in ray order, each on its own region of the mask; the redo launch of
+    // a segment runs before the next segment's launches read the sums it leaves (stream order).  A pass that does not resolve is one segment.
+    for (uint32_t i = 0; i < plan.n_segments; ++i) {
+        const pt::PassSegment seg = pt::pass_segment(plan, i);
+        A.seg_off = seg.off;
+        A.seg_len = seg.len;
+        A.seg_pitch = seg.pitch;
+        A.pixel = seg.writes_pixel ? pixel_ptr : nullptr;
+        if (plan.carries) {
+            A.radiance = carry[seg.carry_write];
+            A.carry = carry[seg.carry_read];
         }
-        ctx->defer_words = words;
-        ctx->defer_unit = resolve_in_pass ? 256u : 1u;
-    } else {
-        if (!resolve_in_pass) pt::launch_fused(ctx->stream, A, false, nullptr, nullptr, 0);
-        else
-            for (uint32_t off = 0; off < A.rpp; off += A.seg_len) {
-                set_segment(off);
-                pt::launch_fused(ctx->stream, A, false, nullptr, nullptr, 0);
-            }
-        ctx->defer_words = 0;
+        if (optimistic) {
+            pt::launch_fused(ctx->stream, A, true, mask + seg.mask_first, nullptr, 0);
+            pt::launch_fused(ctx->stream, A, false, nullptr, mask + seg.mask_first, seg.mask_words);
+        } else {
+            pt::launch_fused(ctx->stream, A, false, nullptr, nullptr, 0);
+        }
     }
+    ctx->defer_words = optimistic ? plan.mask_words : 0u;
+    if (optimistic) ctx->defer_unit = plan.mask_unit;
     if (ctx->profiling && !ctx->capturing) HIPCHK(ctx, hipEventRecord(ctx->pe[1], ctx->stream));
-    if (!resolve_in_pass && (d->pixel || d->radiance)) {
-        float m = res_m;
-        if (passes == 1u && ctx->res_m_override == ctx->res_m_override) m = ctx->res_m_override;
-        pt::launch_copyToPixel(ctx->stream, pixel_ptr, A.acu, m, (uint32_t)npix, A.rpp, (uint32_t)npix, radiance_ptr);
-    }
+    if (!plan.resolves && want_out) pt::launch_copyToPixel(ctx->stream, pixel_ptr, A.acu, res_m, (uint32_t)npix, A.rpp, (uint32_t)npix, radiance_ptr);
     if (ctx->profiling && !ctx->capturing) { HIPCHK(ctx, hipEventRecord(ctx->pe[2], ctx->stream)); ctx->pe_valid = true; }
     HIPCHK(ctx, hipGetLastError());
     d->seeds->version++;
@@ -1542,8 +1523,13 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, bool fresh, 
     return MIRT_OK;
 }
 
-int mirt_render_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try { if (live_has(ctx)) FLUSH_PENDING(ctx); return render_pass_impl(ctx, d, false); } MIRT_CATCH("mirt_render_pass", return MIRT_E_DEVICE)
-int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try { if (live_has(ctx)) FLUSH_PENDING(ctx); return render_pass_impl(ctx, d, true); } MIRT_CATCH("mirt_render_first_pass", return MIRT_E_DEVICE)
+int mirt_render_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try { if (live_has(ctx)) FLUSH_PENDING(ctx); return render_pass_impl(ctx, d, PassOpts{}); } MIRT_CATCH("mirt_render_pass", return MIRT_E_DEVICE)
+int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try {
+    if (live_has(ctx)) FLUSH_PENDING(ctx);
+    PassOpts o;
+    o.fresh = true;
+    return render_pass_impl(ctx, d, o);
+} MIRT_CATCH("mirt_render_first_pass", return MIRT_E_DEVICE)
 
 // n_passes progressive passes in one call: the same results as mirt_render_first_pass (MIRT_PASSES_FRESH) or mirt_render_pass at pass_index,
 // then mirt_render_pass at pass_index + 1 .. pass_index + n_passes - 1 -- one launch (per block of a pixel's rays) that runs every sample through
@@ -1557,19 +1543,19 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
     if (n_passes < 1u || n_passes > MIRT_MAX_PASSES_PER_CALL)
         return fail(ctx, MIRT_E_ARG, "mirt_render_passes: n_passes %u outside 1..%u (one launch lasts about n_passes single passes)", n_passes, MIRT_MAX_PASSES_PER_CALL);
     if (d->pass_index > UINT32_MAX - (n_passes - 1u)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: pass_index %u + %u passes overflows", d->pass_index, n_passes);
-    const bool fresh = (flags & MIRT_PASSES_FRESH) != 0u;
-    // rays_per_pixel 1 couples the rows of a pass through seeds[col] (A10 code.cl:429): a lane cannot run its ray on alone, so the call queues
-    // n_passes ordinary passes -- and those need the accumulator between them
-    const bool single = d->rays_per_pixel == 1u;
-    if (!d->acu && !(fresh && !single && ctx->inpass_resolve && pt::fused_resolves(d->rays_per_pixel, d->pixel || d->radiance)))
+    PassOpts o;
+    o.fresh = (flags & MIRT_PASSES_FRESH) != 0u;
+    o.passes = n_passes;
+    o.every = (flags & MIRT_PASSES_EVERY_FRAME) != 0u;
+    const pt::PassPlan plan = pt::pass_plan(pass_request(ctx, d, o));   // (of the call as asked for: its null-acu verdict and its route)
+    if (!plan.null_acu_ok_passes)
         return fail(ctx, MIRT_E_ARG, "mirt_render_passes: acu may only be NULL with MIRT_PASSES_FRESH, a pixel or radiance buffer and rays_per_pixel > 1 dividing 256 "
-                                     "or above 256, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", fresh ? "fresh" : "NOT fresh",
+                                     "or above 256, unless MIRT_INPASS_RESOLVE=0 (here: %s, %u rays per pixel%s)", o.fresh ? "fresh" : "NOT fresh",
                     d->rays_per_pixel, d->pixel || d->radiance ? "" : ", no output buffer");
     // MIRT_PASSES_EVERY_FRAME: pixel / radiance hold n_passes frames; both are checked before anything runs
-    const bool every = (flags & MIRT_PASSES_EVERY_FRAME) != 0u;
-    if (every) {
+    if (o.every) {
         if (!d->pixel && !d->radiance) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: MIRT_PASSES_EVERY_FRAME needs a pixel or radiance buffer for the frames");
-        const uint64_t npix = (uint64_t)(d->nrows ? d->nrows : d->height) * d->width;
+        const uint64_t npix = plan.npix;
         if (d->pixel && live_has(d->pixel) && (uint64_t)d->pixel->bytes < npix * 4 * n_passes)
             return fail(ctx, MIRT_E_ARG, "mirt_render_passes: pixel holds %zu bytes, %u frames of %llu pixels need %llu", d->pixel->bytes, n_passes,
                         (unsigned long long)npix, (unsigned long long)(npix * 4 * n_passes));
@@ -1577,15 +1563,17 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
             return fail(ctx, MIRT_E_ARG, "mirt_render_passes: radiance holds %zu bytes, %u frames of %llu pixels need %llu", d->radiance->bytes, n_passes,
                         (unsigned long long)npix, (unsigned long long)(npix * 16 * n_passes));
     }
-    if (!single && !every) return render_pass_impl(ctx, d, fresh, n_passes);
-    // every frame from one launch where the passes resolve in the kernel (render_pass_impl's resolve_in_pass with a frame buffer)
-    const bool in_kernel = ctx->inpass_resolve && (d->acu ? pt::fused_resolves_with_acu(d->rays_per_pixel, true) : fresh && pt::fused_resolves(d->rays_per_pixel, true));
-    if (every && !single && n_passes > 1u && in_kernel) return render_pass_impl(ctx, d, fresh, n_passes, true, 0u, true);
+    // one launch: the frame after the last pass, or -- where the passes resolve in the kernel -- every pass's frame
+    if (plan.route != pt::ROUTE_ORDINARY_PASSES) return render_pass_impl(ctx, d, o);
     // elsewhere ordinary passes, each writing its own frame slot when every frame is asked for
     mirt_pass_desc p = *d;
     for (uint32_t i = 0; i < n_passes; ++i) {
         p.pass_index = d->pass_index + i;
-        const int rc = render_pass_impl(ctx, &p, fresh && i == 0u, 1u, i == 0u, every ? i : 0u);
+        PassOpts one;
+        one.fresh = o.fresh && i == 0u;
+        one.mark_start = i == 0u;
+        one.frame = o.every ? i : 0u;
+        const int rc = render_pass_impl(ctx, &p, one);
         if (rc) return rc;
     }
     return MIRT_OK;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pt_pass_plan.hpp"   // fused_resolves, fused_segment and the launch plan of a fused pass (host-only)
+
 namespace pt {
 
 enum { KIND_SPHERES = 0, KIND_TRIANGLES = 1 };
@@ -94,12 +96,12 @@ struct FusedArgs {
     // copyToPixel INSIDE the pass (A10 code.cl:1366-1386; `resolve` != 0): a block of 256 lanes holds whole SEGMENTS of pixels (seg_off, seg_len below)
     // and the pass is a frame's first, so every accumulator of a segment is final in the block's LDS when its last sample ends: the block sums them in
     // the reference's order and writes `pixel` (RGBA8) and / or `radiance` (the un-scaled sums); `acu` may then be null -- nothing per ray but the seed
-    // touches memory: 8 B per sample + 20 B per pixel.  launch_fused decides (fused_resolves()).
+    // touches memory: 8 B per sample + 20 B per pixel.  The pass's plan decides (pt_pass_plan.hpp pass_plan: `resolves`).
     void* pixel;             // uchar4[nrows*width] or null
     void* radiance;          // float4[nrows*width] or null
     float res_m;             // 1 / (rpp * passes), A10 code.js:1412
     uint32_t resolve;
-    // The launch's SEGMENT (fused_segment): samples [seg_off, seg_off + seg_len) of EVERY pixel of the tile, seg_len a power of two <= 256.  A block
+    // The launch's SEGMENT (pt_pass_plan.hpp pass_segment, fused_segment): samples [seg_off, seg_off + seg_len) of EVERY pixel of the tile, seg_len a power of two <= 256.  A block
     // holds 256 / seg_len pixels' segments: lane t of block b is sample seg_off + t % seg_len of pixel b * (256 / seg_len) + t / seg_len (k_fusedPass
     // seg_ray).  A pixel of more than 256 rays resolves in several launches, in ray order, each continuing the pixel's chain of additions from what
     // `radiance` holds -- the sums over the segments before it -- so the reference's one chain (A10 code.cl:1377-1380) is cut at segment boundaries
@@ -121,31 +123,6 @@ struct FusedArgs {
     uint32_t pass_index;     // the 1-based index of the launch's first pass
     const void* carry;       // float4[passes * nrows * width]; read only by a launch with seg_off != 0
 };
-// Whether a pass with these arguments can resolve inside the kernel: rpp divides 256 (whole pixels per block), or rpp > 256 -- any count: the
-// segment plan below covers it -- and somewhere to put the result.  A frame's first pass may then do without `acu`.
-inline bool fused_resolves(uint32_t rpp, bool want_out) {
-    if (!want_out || rpp == 0u) return false;
-    return rpp > 256u || 256u % rpp == 0u;
-}
-// Whether a pass that KEEPS `acu` resolves in the kernel too: only at the counts that resolved in the pass before the segment plan -- rpp divides
-// 256, or is 256 times a power of two up to 32.  At the other counts above 256 such a pass writes `acu` and runs the separate copyToPixel: resolving
-// there beside a kept accumulator was not measured against it.  The block's LDS holds the accumulators as the pass leaves them, which is what copyToPixel would read back.
-inline bool fused_resolves_with_acu(uint32_t rpp, bool want_out) {
-    if (!fused_resolves(rpp, want_out)) return false;
-    if (rpp <= 256u) return true;
-    const uint32_t c = rpp / 256u;
-    return rpp % 256u == 0u && c <= 32u && (c & (c - 1u)) == 0u;
-}
-// The segment plan: a pixel's rays [0, rpp) cut in ray order into power-of-two segments of at most 256 -- floor(rpp / 256) of 256, then one per
-// set bit of rpp % 256, largest first (289: 256, 32, 1).  The length of the segment that starts at sample `off` is the largest power of two that
-// is at most 256 and at most the rays left.  rpp <= 256 (dividing 256): one segment, the whole pixel.
-inline uint32_t fused_segment(uint32_t rpp, uint32_t off) {
-    if (rpp <= 256u) return rpp;
-    const uint32_t left = rpp - off;
-    return left >= 256u ? 256u : 1u << (31 - __builtin_clz(left));
-}
-// the contiguous form of a segment's ray ids (FusedArgs::seg_pitch) applies: the segment is the whole pixel, or 256 of its rays
-inline bool fused_segment_contiguous(uint32_t rpp, uint32_t len) { return len == rpp || len == 256u; }
 // fast: the optimistic kernel (writes deferred samples' bits into defer_mask); !fast: the exact kernel over `list` (or everything)
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words);
 bool fused_fast_available();   // compiled with PT_EXACT_FAST_DIV
