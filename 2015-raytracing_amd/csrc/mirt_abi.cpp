@@ -7,6 +7,7 @@
 // not become an out-of-bounds access on the GPU.
 #include "../../include/mirt.h"
 #include "pt_launch.hpp"
+#include "pt_stream_match.hpp"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -52,21 +53,8 @@ bool live_is(const void* p, HandleKind k) {
 struct mirt_graph;
 struct mirt_group;
 
-struct mirt_buf;
-enum ArgType { A_BUF, A_U32, A_F32, A_F16, A_AABB };
-enum KernelId {
-    K_sizeofRay, K_sizeofPoi, K_initAcu, K_initTrace, K_sphereTrace, K_triangleTrace, K_meshTrace, K_lightRender,
-    K_initShadowTrace, K_sphereShadowTrace, K_triangleShadowTrace, K_sceneRender, K_bouncePaths, K_copyToPixel,
-    K_a01_raytrace, K_a04_sizeofRay, K_a04_initTrace, K_a04_meshTrace, K_a07_sizeofRay, K_a07_initTrace, K_a07_meshTrace, K_a07_molTrace, K_COUNT
-};
-
-struct KernelSpec { const char* name; KernelId id; std::vector<ArgType> args; };
-
-struct KArg {
-    bool set = false;
-    mirt_buf* buf = nullptr;
-    union { uint32_t u; float f; float v[16]; } val;
-};
+// the kernel table and the stream recogniser: pt_stream_match.hpp (a kernel's named argument indices stay in their namespace: pt::sphereTrace::pois)
+using pt::ArgType; using pt::A_BUF; using pt::KernelId; using pt::KernelSpec; using pt::KArg; using pt::Enqueue; using pt::kKernels; using pt::arg_size; using pt::f2u_host;
 
 struct mirt_ctx {
     int device = -1;
@@ -96,8 +84,7 @@ struct mirt_ctx {
     mirt_group* group = nullptr;  // set when the context belongs to a device group (mirt_group_create)
     // command-stream fusion (mirt_ctx_set_fusion): enqueues of the Assign10 pass kernels held back until the pass is complete
     int fusion = 0;
-    struct Pending { const KernelSpec* spec; std::vector<KArg> args; unsigned dim; size_t g[3]; };
-    std::vector<Pending> pending;
+    std::vector<Enqueue> pending;
     uint64_t fused_passes = 0;    // passes executed as ONE fused launch because their enqueue stream matched executeRender's
     // what a recording has touched so far (mirt_graph pins): device allocations a replay will read or write
     uint64_t scratch_gen = 1, defer_gen = 1;   // bumped whenever the allocation is replaced
@@ -141,38 +128,6 @@ struct mirt_buf {
     bool prep_sane = false;   // every plane-normal component is 0 or in [2^-40, 2^40]
 };
 
-static const std::vector<KernelSpec>& kernel_table() {
-    // argument lists: A10 code.cl:440-1386 as bound by A10 code.js
-    static const std::vector<KernelSpec> t = {
-        {"sizeofRay", K_sizeofRay, {A_BUF}},
-        {"sizeofPoi", K_sizeofPoi, {A_BUF}},
-        {"initAcu", K_initAcu, {A_BUF, A_U32}},
-        {"initTrace", K_initTrace, {A_BUF, A_BUF, A_BUF, A_AABB, A_F16, A_F32, A_F32, A_U32}},
-        {"sphereTrace", K_sphereTrace, {A_U32, A_BUF, A_BUF, A_BUF, A_BUF, A_BUF, A_AABB, A_U32}},
-        {"triangleTrace", K_triangleTrace, {A_U32, A_BUF, A_BUF, A_BUF, A_BUF, A_BUF, A_BUF, A_AABB, A_U32}},
-        {"meshTrace", K_meshTrace, {A_U32, A_BUF, A_BUF, A_BUF, A_BUF, A_BUF, A_U32, A_AABB, A_U32}},
-        {"lightRender", K_lightRender, {A_BUF, A_BUF, A_BUF, A_F16, A_U32}},
-        {"initShadowTrace", K_initShadowTrace, {A_BUF, A_BUF, A_U32, A_F16, A_BUF}},
-        {"sphereShadowTrace", K_sphereShadowTrace, {A_U32, A_BUF, A_BUF, A_BUF, A_AABB, A_U32}},
-        {"triangleShadowTrace", K_triangleShadowTrace, {A_U32, A_BUF, A_BUF, A_BUF, A_AABB, A_U32}},
-        {"sceneRender", K_sceneRender, {A_BUF, A_BUF, A_BUF, A_BUF, A_F16, A_U32}},
-        {"bouncePaths", K_bouncePaths, {A_BUF, A_BUF, A_BUF, A_U32}},
-        {"copyToPixel", K_copyToPixel, {A_BUF, A_BUF, A_F32, A_U32, A_U32}},
-        // earlier assignments, selected with a dialect prefix (their kernel names collide with A10's):
-        // A01 code.cl:116; A04 code.cl:200-315; A07 code.cl:307-626
-        {"A01:raytrace", K_a01_raytrace, {A_BUF, A_F16}},
-        {"A04:sizeofRay", K_a04_sizeofRay, {A_BUF}},
-        {"A04:initTrace", K_a04_initTrace, {A_BUF, A_F16, A_BUF}},
-        {"A04:meshTrace", K_a04_meshTrace, {A_BUF, A_F16, A_BUF, A_U32, A_BUF, A_BUF, A_BUF, A_BUF}},
-        {"A07:sizeofRay", K_a07_sizeofRay, {A_BUF}},
-        {"A07:initTrace", K_a07_initTrace, {A_BUF, A_F16, A_BUF, A_AABB}},
-        {"A07:meshTrace", K_a07_meshTrace, {A_BUF, A_F16, A_BUF, A_U32, A_BUF, A_BUF, A_BUF, A_BUF, A_AABB, A_U32, A_BUF}},
-        // molTrace(pixels, fcam, rays, s_size, s_atoms, s_mindex, m_color, bound, n_slabs, slab_size)   A07 code.cl:337-344
-        {"A07:molTrace", K_a07_molTrace, {A_BUF, A_F16, A_BUF, A_U32, A_BUF, A_BUF, A_BUF, A_AABB, A_U32, A_BUF}},
-    };
-    return t;
-}
-
 struct mirt_kernel {
     mirt_ctx* ctx = nullptr;
     const KernelSpec* spec = nullptr;
@@ -202,22 +157,6 @@ int fail(mirt_ctx* ctx, int code, const char* fmt, ...) {
         hipError_t _e = (expr);                                                                    \
         if (_e != hipSuccess) return fail((ctx), MIRT_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
-
-size_t arg_size(ArgType t) {
-    switch (t) {
-        case A_U32: case A_F32: return 4;
-        case A_F16: return 64;
-        case A_AABB: return 32;
-        default: return 0;
-    }
-}
-
-uint32_t f2u_host(float f) {
-    if (!(f == f)) return 0u;
-    if (f >= 4294967296.0f) return UINT32_MAX;
-    if (f <= 0.0f) return 0u;
-    return (uint32_t)f;
-}
 
 // operations that wait on the stream or move host memory cannot be part of a recording
 #define NOT_WHILE_CAPTURING(ctx, what) \
@@ -853,7 +792,7 @@ int mirt_program_check(mirt_ctx* ctx, const char* source, char* missing, size_t 
     int n_missing = 0;
     for (const auto& name : ks) {
         bool found = false;
-        for (const auto& k : kernel_table()) if (prefix + name == k.name) found = true;
+        for (const auto& k : kKernels) if (prefix + name == k.name) found = true;
         if (!found) { if (n_missing++) miss += ","; miss += name; }
     }
     if (missing && cap) snprintf(missing, cap, "%s", miss.c_str());
@@ -864,7 +803,7 @@ int mirt_kernel_get(mirt_ctx* ctx, const char* name, mirt_kernel** out) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_kernel_get: unknown context");
     if (!name || !out) return fail(ctx, MIRT_E_ARG, "mirt_kernel_get: null argument");
     *out = nullptr;
-    for (const auto& s : kernel_table()) {
+    for (const auto& s : kKernels) {
         if (strcmp(name, s.name) == 0) {
             mirt_kernel* k = new mirt_kernel();
             k->ctx = ctx; k->spec = &s; k->args.resize(s.args.size());
@@ -933,147 +872,42 @@ struct PassOpts {
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
 
-static bool same_f(const float* x, const float* y, int n) { return memcmp(x, y, (size_t)n * 4) == 0; }
-
-// MIRT_OK: the held stream was a whole pass and has been executed fused.  1: not a pass (nothing executed).  < 0: error.
-static int try_fuse_pass(mirt_ctx* ctx, std::vector<mirt_ctx::Pending>& P) {
-    size_t i = 0;
-    auto id = [&](size_t k) { return k < P.size() ? P[k].spec->id : K_COUNT; };
-#define PB(k, j) (P[k].args[j].buf)
-#define PU(k, j) (P[k].args[j].val.u)
-#define PF(k, j) (P[k].args[j].val.f)
-#define PV(k, j) (P[k].args[j].val.v)
-    if (id(0) != K_initTrace || P[0].dim != 2) return 1;
-    mirt_buf *seeds = PB(0, 0), *rays = PB(0, 1), *pois = PB(0, 2);
-    const uint32_t rpp = PU(0, 7);
-    const uint32_t cols = f2u_host(PV(0, 4)[14]), rows = f2u_host(PV(0, 4)[15]);
-    if (!rpp || !cols || !rows || P[0].g[0] < cols || P[0].g[1] < rows) return 1;
-    const uint64_t total64 = (uint64_t)cols * rows * rpp;
-    if (total64 > 0xFFFFFFFFull) return 1;
-    const uint32_t total = (uint32_t)total64;
-    i = 1;
-    struct SetRef { int kind; mirt_buf *prims, *normals, *matid, *off; float bounds[8]; uint32_t n, mesh_matid; };
-    auto closest_group = [&](std::vector<SetRef>& out) -> bool {
-        for (;; ++i) {
-            const KernelId k = id(i);
-            if (k != K_sphereTrace && k != K_triangleTrace && k != K_meshTrace) return true;
-            if (PU(i, 0) != total || PB(i, 1) != pois || PB(i, 2) != rays || P[i].g[0] < total) return false;
-            SetRef r;
-            memset(&r, 0, sizeof r);
-            if (k == K_sphereTrace) { r.kind = 0; r.prims = PB(i, 3); r.matid = PB(i, 4); r.off = PB(i, 5); memcpy(r.bounds, PV(i, 6), 32); r.n = PU(i, 7); }
-            else if (k == K_triangleTrace) { r.kind = 1; r.prims = PB(i, 3); r.normals = PB(i, 4); r.matid = PB(i, 5); r.off = PB(i, 6); memcpy(r.bounds, PV(i, 7), 32); r.n = PU(i, 8); }
-            else { r.kind = 2; r.prims = PB(i, 3); r.normals = PB(i, 4); r.off = PB(i, 5); r.mesh_matid = PU(i, 6); memcpy(r.bounds, PV(i, 7), 32); r.n = PU(i, 8); }
-            out.push_back(r);
-        }
-    };
-    std::vector<SetRef> sets;
-    if (!closest_group(sets)) return 1;
-    // upload order the fused pass assumes: at most one sphere set, then at most one loose-triangle set, then the meshes
-    {
-        size_t k = 0;
-        if (k < sets.size() && sets[k].kind == 0) ++k;
-        if (k < sets.size() && sets[k].kind == 1) ++k;
-        for (; k < sets.size(); ++k) if (sets[k].kind != 2) return 1;
-        if (sets.size() > 2u + MIRT_MAX_MESHES) return 1;
-    }
-    struct LightRef { float light[16], shadow[16], scene[16]; };
-    std::vector<LightRef> lights;
-    mirt_buf *acu = nullptr, *shadow = nullptr, *material = nullptr;
-    for (; id(i) == K_lightRender; ++i) {
-        if (PB(i, 0) != pois || PB(i, 1) != rays || PU(i, 4) != total || P[i].g[0] < total) return 1;
-        if (acu && PB(i, 2) != acu) return 1;
-        acu = PB(i, 2);
-        LightRef L;
-        memset(&L, 0, sizeof L);
-        memcpy(L.light, PV(i, 3), 64);
-        lights.push_back(L);
-    }
-    if (lights.size() > MIRT_MAX_LIGHTS) return 1;
-    auto direct_block = [&](bool first) -> bool {
-        for (size_t l = 0; l < lights.size(); ++l) {
-            if (id(i) != K_initShadowTrace || PB(i, 1) != pois || PU(i, 2) != total || PB(i, 4) != seeds || P[i].g[0] < total) return false;
-            if (shadow && PB(i, 0) != shadow) return false;
-            shadow = PB(i, 0);
-            if (first) memcpy(lights[l].shadow, PV(i, 3), 64); else if (!same_f(lights[l].shadow, PV(i, 3), 16)) return false;
-            ++i;
-            for (const SetRef& r : sets) {   // one any-hit kernel per set, same order, same geometry
-                const KernelId want = r.kind == 0 ? K_sphereShadowTrace : K_triangleShadowTrace;
-                if (id(i) != want || PU(i, 0) != total || PB(i, 1) != shadow || PB(i, 2) != r.prims || PB(i, 3) != r.off ||
-                    !same_f(PV(i, 4), r.bounds, 8) || PU(i, 5) != r.n || P[i].g[0] < total) return false;
-                ++i;
-            }
-            if (id(i) != K_sceneRender || PB(i, 0) != acu || PB(i, 1) != pois || PB(i, 2) != shadow || PU(i, 5) != total || P[i].g[0] < total) return false;
-            if (material && PB(i, 3) != material) return false;
-            material = PB(i, 3);
-            if (first) memcpy(lights[l].scene, PV(i, 4), 64); else if (!same_f(lights[l].scene, PV(i, 4), 16)) return false;
-            ++i;
-        }
-        return true;
-    };
-    if (lights.empty() || !direct_block(true)) return 1;     // a scene without lights has no sceneRender to take acu / material from: not fused
-    uint32_t bounces = 0;
-    while (id(i) == K_bouncePaths) {
-        if (PB(i, 0) != pois || PB(i, 1) != rays || PB(i, 2) != seeds || PU(i, 3) != total || P[i].g[0] < total) return 1;
-        ++i;
-        std::vector<SetRef> again;
-        if (!closest_group(again) || again.size() != sets.size()) return 1;
-        for (size_t k = 0; k < sets.size(); ++k)
-            if (again[k].kind != sets[k].kind || again[k].prims != sets[k].prims || again[k].normals != sets[k].normals || again[k].matid != sets[k].matid ||
-                again[k].off != sets[k].off || again[k].n != sets[k].n || again[k].mesh_matid != sets[k].mesh_matid || !same_f(again[k].bounds, sets[k].bounds, 8)) return 1;
-        if (!direct_block(false)) return 1;
-        ++bounces;
-    }
-    if (id(i) != K_copyToPixel || i + 1 != P.size()) return 1;
-    if (PB(i, 1) != acu || PU(i, 3) != cols * rows || PU(i, 4) != rpp || P[i].g[0] < cols * rows) return 1;
-    {   // the fused pass takes k x k rays per pixel only (see render_pass_impl)
-        const uint32_t k = (uint32_t)std::sqrt((double)rpp);
-        const uint32_t kk = (k + 1) * (k + 1) == rpp ? k + 1 : k;
-        if (kk * kk != rpp) return 1;
-    }
+// MIRT_OK: the held stream was a whole pass (match_pass, pt_stream_match.hpp) and has been executed fused.  1: not a pass (nothing executed).  < 0: error.
+static int try_fuse_pass(mirt_ctx* ctx, const std::vector<Enqueue>& P) {
+    pt::PassMatch m;
+    if (!pt::match_pass(P, &m)) return 1;
     // ---- it is a pass: one fused launch + the recorded copyToPixel
     mirt_pass_desc d;
     memset(&d, 0, sizeof d);
     d.struct_size = sizeof d;
-    d.width = cols; d.height = rows; d.rays_per_pixel = rpp; d.bounces = bounces; d.pass_index = 1;
-    memcpy(d.cam, PV(0, 4), 64);
-    memcpy(d.scene_bounds, PV(0, 3), 32);
-    d.focal_length = PF(0, 5); d.lens_rad = PF(0, 6);
-    std::vector<mirt_grid> grids(sets.size());
-    std::vector<mirt_light> ls(lights.size());
-    for (size_t k = 0; k < sets.size(); ++k) {
-        grids[k].prims = sets[k].prims; grids[k].normals = sets[k].normals; grids[k].matid = sets[k].matid; grids[k].cell_offsets = sets[k].off;
-        memcpy(grids[k].bounds, sets[k].bounds, 32);
-        grids[k].n_slabs = sets[k].n; grids[k].mesh_matid = sets[k].mesh_matid;
-    }
+    d.width = m.width; d.height = m.height; d.rays_per_pixel = m.rpp; d.bounces = m.bounces; d.pass_index = 1;
+    memcpy(d.cam, m.cam, 64);
+    memcpy(d.scene_bounds, m.scene_bounds, 32);
+    d.focal_length = m.focal_length; d.lens_rad = m.lens_rad;
     size_t k = 0;
-    if (k < sets.size() && sets[k].kind == 0) d.spheres = &grids[k++];
-    if (k < sets.size() && sets[k].kind == 1) d.triangles = &grids[k++];
-    d.meshes = k < sets.size() ? &grids[k] : nullptr;
-    d.n_meshes = (uint32_t)(sets.size() - k);
-    for (size_t l = 0; l < lights.size(); ++l) { memcpy(ls[l].light, lights[l].light, 64); memcpy(ls[l].shadow, lights[l].shadow, 64); memcpy(ls[l].scene, lights[l].scene, 64); }
-    d.lights = ls.data(); d.n_lights = (uint32_t)ls.size();
-    d.material = material; d.seeds = seeds; d.acu = acu;
+    if (m.spheres) d.spheres = &m.sets[k++];
+    if (m.triangles) d.triangles = &m.sets[k++];
+    d.meshes = k < m.sets.size() ? &m.sets[k] : nullptr;
+    d.n_meshes = (uint32_t)(m.sets.size() - k);
+    d.lights = m.lights.data(); d.n_lights = (uint32_t)m.lights.size();
+    d.material = m.material; d.seeds = m.seeds; d.acu = m.acu;
     // the recorded copyToPixel goes into the pass where the pass can resolve its own pixels (whole pixels per block of 256 ray ids): its pixel buffer and
     // its factor as the host passed it; where it cannot, render_pass_impl queues the separate kernel behind the pass, with that factor
-    d.pixel = PB(i, 0);
-    ctx->res_m_override = PF(i, 2);
+    d.pixel = m.pixel;
+    ctx->res_m_override = m.tone;
     int rc = render_pass_impl(ctx, &d, PassOpts{});
     ctx->res_m_override = NAN;
     if (rc && rc != MIRT_E_DEVICE) return 1;   // refused before anything was launched (a size, a grid that fails validation ...): run the stream as issued,
     if (rc) return rc;                          // whose own checks then report it against the kernel that trips it
-    PB(i, 0)->version++;   // (written by the pass itself, or by the copyToPixel render_pass_impl queued behind it with the recorded factor)
+    m.pixel->version++;   // (written by the pass itself, or by the copyToPixel render_pass_impl queued behind it with the recorded factor)
     ctx->fused_passes++;
     return MIRT_OK;
-#undef PB
-#undef PU
-#undef PF
-#undef PV
 }
 
 // run whatever is held back: as one fused pass when it is one, else enqueue by enqueue, unchanged
 static int flush_pending(mirt_ctx* ctx) {
     if (ctx->pending.empty()) return MIRT_OK;
-    std::vector<mirt_ctx::Pending> P;
+    std::vector<Enqueue> P;
     P.swap(ctx->pending);
     for (auto& p : P)
         for (size_t j = 0; j < p.args.size(); ++j)
@@ -1086,7 +920,7 @@ static int flush_pending(mirt_ctx* ctx) {
     return MIRT_OK;
 }
 
-static bool is_pass_kernel(KernelId k) { return k >= K_initTrace && k <= K_copyToPixel; }
+static bool is_pass_kernel(KernelId k) { return k >= pt::K_initTrace && k <= pt::K_copyToPixel; }
 
 int mirt_enqueue(mirt_ctx* ctx, mirt_kernel* k, unsigned dim, const size_t* global, const size_t* local) try {
     (void)local;  // no kernel uses local memory or barriers: the work-group shape is ours to choose
@@ -1102,13 +936,13 @@ int mirt_enqueue(mirt_ctx* ctx, mirt_kernel* k, unsigned dim, const size_t* glob
     for (unsigned d = 0; d < dim; ++d)
         if (global[d] > 0xFFFFFFFFull) return fail(ctx, MIRT_E_ARG, "%s: global size exceeds 2^32", S.name);
     if (ctx->fusion >= 2 && !ctx->capturing && is_pass_kernel(S.id)) {
-        if (S.id == K_initTrace) FLUSH_PENDING(ctx);                 // a new pass begins: whatever was held is not one
-        if (S.id == K_initTrace || !ctx->pending.empty()) {
-            mirt_ctx::Pending p;
+        if (S.id == pt::K_initTrace) FLUSH_PENDING(ctx);                 // a new pass begins: whatever was held is not one
+        if (S.id == pt::K_initTrace || !ctx->pending.empty()) {
+            Enqueue p;
             p.spec = &S; p.args = k->args; p.dim = dim;
             for (unsigned d = 0; d < 3; ++d) p.g[d] = d < dim ? global[d] : 1;
             ctx->pending.push_back(std::move(p));
-            if (S.id == K_copyToPixel) return flush_pending(ctx);    // the pass is complete: run it now
+            if (S.id == pt::K_copyToPixel) return flush_pending(ctx);    // the pass is complete: run it now
             return MIRT_OK;
         }
     }
@@ -1121,181 +955,198 @@ static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& 
     hipStream_t st = ctx->stream;
     const uint32_t g0 = (uint32_t)global[0];
     int rc;
-#define BUF(i) (a[i].buf)
-#define U(i) (a[i].val.u)
-#define F(i) (a[i].val.f)
-#define V(i) (a[i].val.v)
+    auto A = [&](auto j) { return pt::arg(a, j); };   // the argument by its name: a buffer handle, a scalar, or the floats of a float16 / AABB
     switch (S.id) {
-        case K_sizeofRay:
-        case K_sizeofPoi:
-            if ((rc = need(ctx, S.name, BUF(0), 4))) return rc;
-            pt::launch_sizeof(st, S.id == K_sizeofRay, (uint32_t*)BUF(0)->ptr);
-            break;
-        case K_initAcu: {
-            uint32_t cnt = std::min(g0, U(1));
-            if ((rc = need(ctx, S.name, BUF(0), (uint64_t)cnt * kAcuBytes))) return rc;
-            pt::launch_initAcu(st, BUF(0)->ptr, U(1), g0);
-            BUF(0)->version++;
+        case pt::K_sizeofRay:
+        case pt::K_sizeofPoi: {
+            namespace K = pt::sizeofRay;
+            if ((rc = need(ctx, S.name, A(K::size), 4))) return rc;
+            pt::launch_sizeof(st, S.id == pt::K_sizeofRay, (uint32_t*)A(K::size)->ptr);
             break;
         }
-        case K_initTrace: {
+        case pt::K_initAcu: {
+            namespace K = pt::initAcu;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, S.name, A(K::acu), (uint64_t)cnt * kAcuBytes))) return rc;
+            pt::launch_initAcu(st, A(K::acu)->ptr, A(K::total), g0);
+            A(K::acu)->version++;
+            break;
+        }
+        case pt::K_initTrace: {
+            namespace K = pt::initTrace;
             if (dim != 2) return fail(ctx, MIRT_E_ARG, "initTrace is a 2-D NDRange (A10 code.js:1330)");
             const uint32_t g1 = (uint32_t)global[1];
-            const uint32_t cols = f2u_host(V(4)[14]), rows = f2u_host(V(4)[15]);
-            const uint32_t rpp = U(7);
+            const uint32_t cols = f2u_host(A(K::fcam)[14]), rows = f2u_host(A(K::fcam)[15]);
+            const uint32_t rpp = A(K::rays_per_pixel);
             const uint32_t wc = std::min(g0, cols), wr = std::min(g1, rows);
             if (wc && wr) {
                 if (rpp == 0) return fail(ctx, MIRT_E_ARG, "initTrace: rays_per_pixel is 0");
-                uint64_t rays = ((uint64_t)cols * (wr - 1) + wc) * rpp;  // one past the last ray touched
-                if ((rc = need(ctx, "initTrace rays", BUF(1), rays * kRayBytes))) return rc;
-                if ((rc = need(ctx, "initTrace pois", BUF(2), rays * kPoiBytes))) return rc;
+                uint64_t nrays = ((uint64_t)cols * (wr - 1) + wc) * rpp;  // one past the last ray touched
+                if ((rc = need(ctx, "initTrace rays", A(K::rays), nrays * kRayBytes))) return rc;
+                if ((rc = need(ctx, "initTrace pois", A(K::pois), nrays * kPoiBytes))) return rc;
                 if (rpp == 1) {
-                    if ((rc = need(ctx, "initTrace seeds", BUF(0), (uint64_t)wc * 4))) return rc;
+                    if ((rc = need(ctx, "initTrace seeds", A(K::seeds), (uint64_t)wc * 4))) return rc;
                     if ((rc = ensure_scratch(ctx, (size_t)cols * rows * 8))) return rc;
-                    pt::launch_lensDraws(st, BUF(0)->ptr, ctx->scratch, cols, rows, g0, g1, 0, rows);
+                    pt::launch_lensDraws(st, A(K::seeds)->ptr, ctx->scratch, cols, rows, g0, g1, 0, rows);
                 }
-                pt::launch_initTrace(st, BUF(1)->ptr, BUF(2)->ptr, ctx->scratch, V(3), V(4), F(5), F(6), rpp, g0, g1);
+                pt::launch_initTrace(st, A(K::rays)->ptr, A(K::pois)->ptr, ctx->scratch, A(K::bound), A(K::fcam), A(K::focal_length), A(K::lens_rad), rpp, g0, g1);
             }
             break;
         }
-        case K_sphereTrace: {
-            uint32_t cnt = std::min(g0, U(0));
-            if ((rc = need(ctx, "sphereTrace pois", BUF(1), (uint64_t)cnt * kPoiBytes))) return rc;
-            if ((rc = need(ctx, "sphereTrace rays", BUF(2), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = check_grid(ctx, "sphereTrace grid", BUF(5), U(7), BUF(3), 16, nullptr, BUF(4)))) return rc;
-            pt::launch_closest(st, pt::KIND_SPHERES, U(0), BUF(1)->ptr, BUF(2)->ptr, BUF(3)->ptr, nullptr, BUF(4)->ptr, 0, BUF(5)->ptr, V(6), U(7), exit_is_far_face(V(6), U(7)), g0);
+        case pt::K_sphereTrace: {
+            namespace K = pt::sphereTrace;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "sphereTrace pois", A(K::pois), (uint64_t)cnt * kPoiBytes))) return rc;
+            if ((rc = need(ctx, "sphereTrace rays", A(K::rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = check_grid(ctx, "sphereTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 16, nullptr, A(K::matid)))) return rc;
+            pt::launch_closest(st, pt::KIND_SPHERES, A(K::total), A(K::pois)->ptr, A(K::rays)->ptr, A(K::prims)->ptr, nullptr, A(K::matid)->ptr, 0, A(K::off)->ptr, A(K::bounds), A(K::n_slabs),
+                               exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
-        case K_triangleTrace: {
-            uint32_t cnt = std::min(g0, U(0));
-            if ((rc = need(ctx, "triangleTrace pois", BUF(1), (uint64_t)cnt * kPoiBytes))) return rc;
-            if ((rc = need(ctx, "triangleTrace rays", BUF(2), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = check_grid(ctx, "triangleTrace grid", BUF(6), U(8), BUF(3), 48, BUF(4), BUF(5)))) return rc;
-            if ((rc = ensure_prepared(ctx, BUF(3), BUF(6)->off_last))) return rc;
-            pt::launch_closest(st, pt::KIND_TRIANGLES, U(0), BUF(1)->ptr, BUF(2)->ptr, BUF(3)->prep, BUF(4)->ptr, BUF(5)->ptr, 0, BUF(6)->ptr, V(7), U(8), exit_is_far_face(V(7), U(8)), g0);
+        case pt::K_triangleTrace: {
+            namespace K = pt::triangleTrace;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "triangleTrace pois", A(K::pois), (uint64_t)cnt * kPoiBytes))) return rc;
+            if ((rc = need(ctx, "triangleTrace rays", A(K::rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = check_grid(ctx, "triangleTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 48, A(K::normals), A(K::matid)))) return rc;
+            if ((rc = ensure_prepared(ctx, A(K::prims), A(K::off)->off_last))) return rc;
+            pt::launch_closest(st, pt::KIND_TRIANGLES, A(K::total), A(K::pois)->ptr, A(K::rays)->ptr, A(K::prims)->prep, A(K::normals)->ptr, A(K::matid)->ptr, 0, A(K::off)->ptr, A(K::bounds), A(K::n_slabs),
+                               exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
-        case K_meshTrace: {
-            uint32_t cnt = std::min(g0, U(0));
-            if ((rc = need(ctx, "meshTrace pois", BUF(1), (uint64_t)cnt * kPoiBytes))) return rc;
-            if ((rc = need(ctx, "meshTrace rays", BUF(2), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = check_grid(ctx, "meshTrace grid", BUF(5), U(8), BUF(3), 48, BUF(4), nullptr))) return rc;
-            if ((rc = ensure_prepared(ctx, BUF(3), BUF(5)->off_last))) return rc;
-            pt::launch_closest(st, pt::KIND_TRIANGLES, U(0), BUF(1)->ptr, BUF(2)->ptr, BUF(3)->prep, BUF(4)->ptr, nullptr, U(6), BUF(5)->ptr, V(7), U(8), exit_is_far_face(V(7), U(8)), g0);
+        case pt::K_meshTrace: {
+            namespace K = pt::meshTrace;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "meshTrace pois", A(K::pois), (uint64_t)cnt * kPoiBytes))) return rc;
+            if ((rc = need(ctx, "meshTrace rays", A(K::rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = check_grid(ctx, "meshTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 48, A(K::normals), nullptr))) return rc;
+            if ((rc = ensure_prepared(ctx, A(K::prims), A(K::off)->off_last))) return rc;
+            pt::launch_closest(st, pt::KIND_TRIANGLES, A(K::total), A(K::pois)->ptr, A(K::rays)->ptr, A(K::prims)->prep, A(K::normals)->ptr, nullptr, A(K::matid), A(K::off)->ptr, A(K::bounds), A(K::n_slabs),
+                               exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
-        case K_lightRender: {
-            uint32_t cnt = std::min(g0, U(4));
-            if ((rc = need(ctx, "lightRender pois", BUF(0), (uint64_t)cnt * kPoiBytes))) return rc;
-            if ((rc = need(ctx, "lightRender rays", BUF(1), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = need(ctx, "lightRender acu", BUF(2), (uint64_t)cnt * kAcuBytes))) return rc;
-            pt::launch_lightRender(st, BUF(0)->ptr, BUF(1)->ptr, BUF(2)->ptr, V(3), U(4), g0);
+        case pt::K_lightRender: {
+            namespace K = pt::lightRender;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "lightRender pois", A(K::pois), (uint64_t)cnt * kPoiBytes))) return rc;
+            if ((rc = need(ctx, "lightRender rays", A(K::rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = need(ctx, "lightRender acu", A(K::acu), (uint64_t)cnt * kAcuBytes))) return rc;
+            pt::launch_lightRender(st, A(K::pois)->ptr, A(K::rays)->ptr, A(K::acu)->ptr, A(K::light_info), A(K::total), g0);
             break;
         }
-        case K_initShadowTrace: {
-            uint32_t cnt = std::min(g0, U(2));
-            if ((rc = need(ctx, "initShadowTrace shadow", BUF(0), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = need(ctx, "initShadowTrace pois", BUF(1), (uint64_t)cnt * kPoiBytes))) return rc;
-            if ((rc = need(ctx, "initShadowTrace seeds", BUF(4), (uint64_t)cnt * 4))) return rc;
-            pt::launch_initShadowTrace(st, BUF(0)->ptr, BUF(1)->ptr, U(2), V(3), BUF(4)->ptr, g0);
+        case pt::K_initShadowTrace: {
+            namespace K = pt::initShadowTrace;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "initShadowTrace shadow", A(K::shadow_rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = need(ctx, "initShadowTrace pois", A(K::pois), (uint64_t)cnt * kPoiBytes))) return rc;
+            if ((rc = need(ctx, "initShadowTrace seeds", A(K::seeds), (uint64_t)cnt * 4))) return rc;
+            pt::launch_initShadowTrace(st, A(K::shadow_rays)->ptr, A(K::pois)->ptr, A(K::total), A(K::light_info), A(K::seeds)->ptr, g0);
             break;
         }
-        case K_sphereShadowTrace: {
-            uint32_t cnt = std::min(g0, U(0));
-            if ((rc = need(ctx, "sphereShadowTrace shadow", BUF(1), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = check_grid(ctx, "sphereShadowTrace grid", BUF(3), U(5), BUF(2), 16, nullptr, nullptr))) return rc;
-            pt::launch_anyhit(st, pt::KIND_SPHERES, U(0), BUF(1)->ptr, BUF(2)->ptr, BUF(3)->ptr, V(4), U(5), exit_is_far_face(V(4), U(5)), g0);
+        case pt::K_sphereShadowTrace: {
+            namespace K = pt::shadowTrace;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "sphereShadowTrace shadow", A(K::shadow_rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = check_grid(ctx, "sphereShadowTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 16, nullptr, nullptr))) return rc;
+            pt::launch_anyhit(st, pt::KIND_SPHERES, A(K::total), A(K::shadow_rays)->ptr, A(K::prims)->ptr, A(K::off)->ptr, A(K::bounds), A(K::n_slabs), exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
-        case K_triangleShadowTrace: {
-            uint32_t cnt = std::min(g0, U(0));
-            if ((rc = need(ctx, "triangleShadowTrace shadow", BUF(1), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = check_grid(ctx, "triangleShadowTrace grid", BUF(3), U(5), BUF(2), 48, nullptr, nullptr))) return rc;
-            if ((rc = ensure_prepared(ctx, BUF(2), BUF(3)->off_last))) return rc;
-            pt::launch_anyhit(st, pt::KIND_TRIANGLES, U(0), BUF(1)->ptr, BUF(2)->prep, BUF(3)->ptr, V(4), U(5), exit_is_far_face(V(4), U(5)), g0);
+        case pt::K_triangleShadowTrace: {
+            namespace K = pt::shadowTrace;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "triangleShadowTrace shadow", A(K::shadow_rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = check_grid(ctx, "triangleShadowTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 48, nullptr, nullptr))) return rc;
+            if ((rc = ensure_prepared(ctx, A(K::prims), A(K::off)->off_last))) return rc;
+            pt::launch_anyhit(st, pt::KIND_TRIANGLES, A(K::total), A(K::shadow_rays)->ptr, A(K::prims)->prep, A(K::off)->ptr, A(K::bounds), A(K::n_slabs), exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
-        case K_sceneRender: {
-            uint32_t cnt = std::min(g0, U(5));
-            if ((rc = need(ctx, "sceneRender acu", BUF(0), (uint64_t)cnt * kAcuBytes))) return rc;
-            if ((rc = need(ctx, "sceneRender pois", BUF(1), (uint64_t)cnt * kPoiBytes))) return rc;
-            if ((rc = need(ctx, "sceneRender shadow", BUF(2), (uint64_t)cnt * kRayBytes))) return rc;
-            pt::launch_sceneRender(st, BUF(0)->ptr, BUF(1)->ptr, BUF(2)->ptr, BUF(3)->ptr, (uint32_t)(BUF(3)->bytes / 16), V(4), U(5), g0);
+        case pt::K_sceneRender: {
+            namespace K = pt::sceneRender;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "sceneRender acu", A(K::acu), (uint64_t)cnt * kAcuBytes))) return rc;
+            if ((rc = need(ctx, "sceneRender pois", A(K::pois), (uint64_t)cnt * kPoiBytes))) return rc;
+            if ((rc = need(ctx, "sceneRender shadow", A(K::shadow_rays), (uint64_t)cnt * kRayBytes))) return rc;
+            pt::launch_sceneRender(st, A(K::acu)->ptr, A(K::pois)->ptr, A(K::shadow_rays)->ptr, A(K::material)->ptr, (uint32_t)(A(K::material)->bytes / 16), A(K::light_info), A(K::total), g0);
             break;
         }
-        case K_bouncePaths: {
-            uint32_t cnt = std::min(g0, U(3));
-            if ((rc = need(ctx, "bouncePaths pois", BUF(0), (uint64_t)cnt * kPoiBytes))) return rc;
-            if ((rc = need(ctx, "bouncePaths rays", BUF(1), (uint64_t)cnt * kRayBytes))) return rc;
-            if ((rc = need(ctx, "bouncePaths seeds", BUF(2), (uint64_t)cnt * 4))) return rc;
-            pt::launch_bouncePaths(st, BUF(0)->ptr, BUF(1)->ptr, BUF(2)->ptr, U(3), g0);
+        case pt::K_bouncePaths: {
+            namespace K = pt::bouncePaths;
+            uint32_t cnt = std::min(g0, A(K::total));
+            if ((rc = need(ctx, "bouncePaths pois", A(K::pois), (uint64_t)cnt * kPoiBytes))) return rc;
+            if ((rc = need(ctx, "bouncePaths rays", A(K::rays), (uint64_t)cnt * kRayBytes))) return rc;
+            if ((rc = need(ctx, "bouncePaths seeds", A(K::seeds), (uint64_t)cnt * 4))) return rc;
+            pt::launch_bouncePaths(st, A(K::pois)->ptr, A(K::rays)->ptr, A(K::seeds)->ptr, A(K::total), g0);
             break;
         }
-        case K_copyToPixel: {
-            uint32_t cnt = std::min(g0, U(3));
-            if ((rc = need(ctx, "copyToPixel pixel", BUF(0), (uint64_t)cnt * 4))) return rc;
-            if ((rc = need(ctx, "copyToPixel acu", BUF(1), (uint64_t)cnt * U(4) * kAcuBytes))) return rc;
-            pt::launch_copyToPixel(st, BUF(0)->ptr, BUF(1)->ptr, F(2), U(3), U(4), g0, nullptr);
+        case pt::K_copyToPixel: {
+            namespace K = pt::copyToPixel;
+            uint32_t cnt = std::min(g0, A(K::pixels));
+            if ((rc = need(ctx, "copyToPixel pixel", A(K::pixel), (uint64_t)cnt * 4))) return rc;
+            if ((rc = need(ctx, "copyToPixel acu", A(K::acu), (uint64_t)cnt * A(K::rays_per_pixel) * kAcuBytes))) return rc;
+            pt::launch_copyToPixel(st, A(K::pixel)->ptr, A(K::acu)->ptr, A(K::m), A(K::pixels), A(K::rays_per_pixel), g0, nullptr);
             break;
         }
-        case K_a04_sizeofRay:
-        case K_a07_sizeofRay:
-            if ((rc = need(ctx, S.name, BUF(0), 4))) return rc;
-            pt::launch_sizeof(st, true, (uint32_t*)BUF(0)->ptr);
+        case pt::K_a04_sizeofRay:
+        case pt::K_a07_sizeofRay: {
+            namespace K = pt::sizeofRay;
+            if ((rc = need(ctx, S.name, A(K::size), 4))) return rc;
+            pt::launch_sizeof(st, true, (uint32_t*)A(K::size)->ptr);
             break;
-        case K_a01_raytrace: {
+        }
+        case pt::K_a01_raytrace: {
+            namespace K = pt::frame;
             if (dim != 2) return fail(ctx, MIRT_E_ARG, "raytrace is a 2-D NDRange (A01 code.js:241)");
             const uint32_t g1 = (uint32_t)global[1];
-            const uint32_t rows = f2u_host(V(1)[14]), cols = f2u_host(V(1)[15]);   // A01 packs rows, cols (code.js:50)
+            const uint32_t rows = f2u_host(A(K::fcam)[14]), cols = f2u_host(A(K::fcam)[15]);   // A01 packs rows, cols (code.js:50)
             const uint32_t wc = std::min(g0, cols), wr = std::min(g1, rows);
             if (wc && wr) {
-                if ((rc = need(ctx, "raytrace pixels", BUF(0), ((uint64_t)cols * (wr - 1) + wc) * 4))) return rc;
-                pt::launch_a01_raytrace(st, BUF(0)->ptr, V(1), g0, g1);
+                if ((rc = need(ctx, "raytrace pixels", A(K::pixels), ((uint64_t)cols * (wr - 1) + wc) * 4))) return rc;
+                pt::launch_a01_raytrace(st, A(K::pixels)->ptr, A(K::fcam), g0, g1);
             }
             break;
         }
-        case K_a04_initTrace:
-        case K_a07_initTrace:
-        case K_a04_meshTrace:
-        case K_a07_meshTrace:
-        case K_a07_molTrace: {
+        case pt::K_a04_initTrace:
+        case pt::K_a07_initTrace:
+        case pt::K_a04_meshTrace:
+        case pt::K_a07_meshTrace:
+        case pt::K_a07_molTrace: {
+            namespace K = pt::frame;
             if (dim != 2) return fail(ctx, MIRT_E_ARG, "%s is a 2-D NDRange", S.name);
             const uint32_t g1 = (uint32_t)global[1];
-            const uint32_t cols = f2u_host(V(1)[14]), rows = f2u_host(V(1)[15]);
+            const uint32_t cols = f2u_host(A(K::fcam)[14]), rows = f2u_host(A(K::fcam)[15]);
             const uint32_t wc = std::min(g0, cols), wr = std::min(g1, rows);
             if (!wc || !wr) break;
             const uint64_t npx = (uint64_t)cols * (wr - 1) + wc;
-            if ((rc = need(ctx, "pixels", BUF(0), npx * 4))) return rc;
-            if ((rc = need(ctx, "rays", BUF(2), npx * kRayBytes))) return rc;
-            if (S.id == K_a04_initTrace) pt::launch_frame_initTrace(st, false, BUF(0)->ptr, V(1), BUF(2)->ptr, nullptr, g0, g1);
-            else if (S.id == K_a07_initTrace) pt::launch_frame_initTrace(st, true, BUF(0)->ptr, V(1), BUF(2)->ptr, V(3), g0, g1);
-            else if (S.id == K_a04_meshTrace) {
-                const uint32_t T = U(3);
-                if ((rc = need(ctx, "meshTrace t_pos", BUF(4), (uint64_t)T * 48))) return rc;
-                if ((rc = need(ctx, "meshTrace t_normal", BUF(5), (uint64_t)T * 48))) return rc;
-                if ((rc = need(ctx, "meshTrace t_mindex", BUF(6), (uint64_t)T * 4))) return rc;
-                if ((rc = need(ctx, "meshTrace m_color", BUF(7), 16))) return rc;
-                if ((rc = ensure_prepared(ctx, BUF(4), T))) return rc;
-                pt::launch_a04_meshTrace(st, BUF(0)->ptr, V(1), BUF(2)->ptr, T, BUF(4)->prep, BUF(5)->ptr, BUF(6)->ptr, BUF(7)->ptr,
-                                         (uint32_t)(BUF(7)->bytes / 16), g0, g1);
-            } else if (S.id == K_a07_molTrace) {
-                // s_mindex / m_color (args 5, 6) are bound by the reference host but never read by the kernel (code.cl:459-460)
-                if ((rc = check_grid(ctx, "molTrace grid", BUF(9), U(8), BUF(4), 16, nullptr, nullptr))) return rc;
-                pt::launch_a07_molTrace(st, BUF(0)->ptr, V(1), BUF(2)->ptr, BUF(4)->ptr, V(7), U(8), BUF(9)->ptr, g0, g1);
+            if ((rc = need(ctx, "pixels", A(K::pixels), npx * 4))) return rc;
+            if ((rc = need(ctx, "rays", A(K::rays), npx * kRayBytes))) return rc;
+            if (S.id == pt::K_a04_initTrace) pt::launch_frame_initTrace(st, false, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, nullptr, g0, g1);
+            else if (S.id == pt::K_a07_initTrace) pt::launch_frame_initTrace(st, true, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, A(pt::a07_initTrace::bound), g0, g1);
+            else if (S.id == pt::K_a04_meshTrace) {
+                namespace M = pt::a04_meshTrace;
+                const uint32_t T = A(M::t_size);
+                if ((rc = need(ctx, "meshTrace t_pos", A(M::t_pos), (uint64_t)T * 48))) return rc;
+                if ((rc = need(ctx, "meshTrace t_normal", A(M::t_normal), (uint64_t)T * 48))) return rc;
+                if ((rc = need(ctx, "meshTrace t_mindex", A(M::t_mindex), (uint64_t)T * 4))) return rc;
+                if ((rc = need(ctx, "meshTrace m_color", A(M::m_color), 16))) return rc;
+                if ((rc = ensure_prepared(ctx, A(M::t_pos), T))) return rc;
+                pt::launch_a04_meshTrace(st, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, T, A(M::t_pos)->prep, A(M::t_normal)->ptr, A(M::t_mindex)->ptr, A(M::m_color)->ptr,
+                                         (uint32_t)(A(M::m_color)->bytes / 16), g0, g1);
+            } else if (S.id == pt::K_a07_molTrace) {
+                namespace M = pt::a07_molTrace;
+                // s_mindex / m_color are bound by the reference host but never read by the kernel (code.cl:459-460)
+                if ((rc = check_grid(ctx, "molTrace grid", A(M::slab_size), A(M::n_slabs), A(M::s_atoms), 16, nullptr, nullptr))) return rc;
+                pt::launch_a07_molTrace(st, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, A(M::s_atoms)->ptr, A(M::bound), A(M::n_slabs), A(M::slab_size)->ptr, g0, g1);
             } else {
-                if ((rc = check_grid(ctx, "meshTrace grid", BUF(10), U(9), BUF(4), 48, BUF(5), nullptr))) return rc;
-                if ((rc = ensure_prepared(ctx, BUF(4), BUF(10)->off_last))) return rc;
-                pt::launch_a07_meshTrace(st, BUF(0)->ptr, V(1), BUF(2)->ptr, BUF(4)->prep, BUF(5)->ptr, V(8), U(9), BUF(10)->ptr, BUF(10)->off_last, g0, g1);
+                namespace M = pt::a07_meshTrace;
+                if ((rc = check_grid(ctx, "meshTrace grid", A(M::slab_size), A(M::n_slabs), A(M::t_pos), 48, A(M::t_normal), nullptr))) return rc;
+                if ((rc = ensure_prepared(ctx, A(M::t_pos), A(M::slab_size)->off_last))) return rc;
+                pt::launch_a07_meshTrace(st, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, A(M::t_pos)->prep, A(M::t_normal)->ptr, A(M::bound), A(M::n_slabs), A(M::slab_size)->ptr, A(M::slab_size)->off_last, g0, g1);
             }
             break;
         }
         default:
             return fail(ctx, MIRT_E_NAME, "kernel not implemented");
     }
-#undef BUF
-#undef U
-#undef F
-#undef V
     HIPCHK(ctx, hipGetLastError());
     return MIRT_OK;
 }
