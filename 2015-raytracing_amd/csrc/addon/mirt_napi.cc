@@ -365,6 +365,49 @@ napi_value RenderPass(napi_env env, napi_callback_info info) {
     return undef(env);
 }
 
+// renderFrame(ctx, {assign,width,height,cam,bounds?,nSlabs?, tSize?,tPos?,tNormal?,tMindex?,tMcolor?,tSlabSize?, sSize?,sAtoms?,sMindex?,sMcolor?,sSlabSize?,
+//                   pixel, rays?}): a whole Assign04 / Assign07 frame in one launch (mirt_render_frame)
+napi_value RenderFrame(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "renderFrame(ctx, desc)");
+    napi_value d = argv[1];
+    mirt_frame_desc f;
+    memset(&f, 0, sizeof f);
+    f.struct_size = sizeof f;
+    if (!prop_u32(env, d, "assign", &f.assign) || !prop_u32(env, d, "width", &f.width) || !prop_u32(env, d, "height", &f.height) || !prop_floats(env, d, "cam", f.cam, 16))
+        return throw_type(env, "renderFrame: assign, width, height, cam (16 floats)");
+    prop_floats(env, d, "bounds", f.bounds, 8);
+    prop_u32(env, d, "nSlabs", &f.n_slabs);
+    prop_u32(env, d, "tSize", &f.t_size);
+    prop_u32(env, d, "sSize", &f.s_size);
+    f.t_pos = prop_buf(env, d, "tPos"); f.t_normal = prop_buf(env, d, "tNormal"); f.t_mindex = prop_buf(env, d, "tMindex"); f.t_mcolor = prop_buf(env, d, "tMcolor");
+    f.t_slab_size = prop_buf(env, d, "tSlabSize");
+    f.s_atoms = prop_buf(env, d, "sAtoms"); f.s_mindex = prop_buf(env, d, "sMindex"); f.s_mcolor = prop_buf(env, d, "sMcolor"); f.s_slab_size = prop_buf(env, d, "sSlabSize");
+    f.pixel = prop_buf(env, d, "pixel");
+    f.rays = prop_buf(env, d, "rays");
+    int rc = mirt_render_frame((mirt_ctx*)c, &f);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value CtxSetFrameFusion(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c; uint32_t on;
+    if (!get_ext(env, argv[0], &c) || !get_u32(env, argv[1], &on)) return throw_type(env, "ctxSetFrameFusion(ctx, on)");
+    int rc = mirt_ctx_set_frame_fusion((mirt_ctx*)c, (int)on);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value CtxFusedFrames(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "ctxFusedFrames(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_ctx_fused_frames((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
+}
+
 napi_value SeedFill(napi_env env, napi_callback_info info) {
     ARGS(5);
     void *c, *b; double first, count; uint32_t base;
@@ -610,7 +653,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

@@ -86,6 +86,9 @@ struct mirt_ctx {
     int fusion = 0;
     std::vector<Enqueue> pending;
     uint64_t fused_passes = 0;    // passes executed as ONE fused launch because their enqueue stream matched executeRender's
+    // the same for the frame dialects (mirt_ctx_set_frame_fusion): an A04 / A07 initTrace and the enqueues behind it are held in `pending` too
+    bool frame_fusion = false;
+    uint64_t fused_frames = 0;
     // what a recording has touched so far (mirt_graph pins): device allocations a replay will read or write
     uint64_t scratch_gen = 1, defer_gen = 1;   // bumped whenever the allocation is replaced
     struct Pin { mirt_buf* buf; uint64_t uid; uint64_t prep_gen; uint64_t version; bool content; };
@@ -355,6 +358,7 @@ static int create_ctx(int device, mirt_ctx** out) {
     c->stream = c->own_stream;
     if (const char* f = getenv("MIRT_INPASS_RESOLVE")) c->inpass_resolve = atoi(f) != 0;   // A/B and test switch
     if (const char* f = getenv("MIRT_FUSION")) c->fusion = atoi(f) >= 2 ? 2 : 0;   // same as mirt_ctx_set_fusion: for hosts that cannot be edited at all
+    if (const char* f = getenv("MIRT_FRAME_FUSION")) c->frame_fusion = atoi(f) != 0;   // same as mirt_ctx_set_frame_fusion
     (void)hipEventCreate(&c->ev0);
     (void)hipEventCreate(&c->ev1);
     for (auto& e : c->pe) (void)hipEventCreate(&e);
@@ -646,6 +650,7 @@ int mirt_finish(mirt_ctx* ctx) try {
     NOT_WHILE_CAPTURING(ctx, "mirt_finish");
     // inside a held pass (the reference calls finish() after every sceneRender, A10 code.js:1406) nothing is observable until a read, which
     // flushes -- unless the pass works on memory the caller can reach behind the ABI (mirt_buf_wrap): then finish() means finish
+    if (!ctx->pending.empty() && pt::is_frame_init(ctx->pending[0].spec->id)) FLUSH_PENDING(ctx);   // a held frame runs at finish (the pages read the pixels next)
     if (ctx->fusion >= 2 && !ctx->pending.empty()) {
         bool wrapped = false;
         for (const auto& p : ctx->pending)
@@ -871,6 +876,31 @@ struct PassOpts {
 };
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
+static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d);
+
+// The frame dialects' counterpart of try_fuse_pass.  MIRT_OK: the held stream was a frame (match_frame, pt_stream_match.hpp) and ran as one launch; the
+// ray buffer is not written.  1: not a frame, or refused before anything was launched (nothing executed).  < 0: error.
+static int try_fuse_frame(mirt_ctx* ctx, const std::vector<Enqueue>& P) {
+    pt::FrameMatch m;
+    if (!pt::match_frame(P, &m)) return 1;
+    mirt_frame_desc d;
+    memset(&d, 0, sizeof d);
+    d.struct_size = sizeof d;
+    d.assign = m.assign; d.width = m.width; d.height = m.height;
+    memcpy(d.cam, m.cam, 64);
+    memcpy(d.bounds, m.bounds, 32);
+    d.n_slabs = m.n_slabs;
+    if (m.mesh) { d.t_size = m.t_size; d.t_pos = m.t_pos; d.t_normal = m.t_normal; d.t_mindex = m.t_mindex; d.t_mcolor = m.t_mcolor; d.t_slab_size = m.t_slab_size; }
+    if (m.mol) { d.s_size = m.s_size; d.s_atoms = m.s_atoms; d.s_mindex = m.s_mindex; d.s_mcolor = m.s_mcolor; d.s_slab_size = m.s_slab_size; }
+    d.pixel = m.pixels;
+    // the kernels check the ray buffer's extent too: a stream whose rays are too small fails enqueue by enqueue, as issued
+    if (!live_has(m.rays) || (uint64_t)m.rays->bytes < (uint64_t)m.width * m.height * kRayBytes) return 1;
+    const int rc = render_frame_impl(ctx, &d);
+    if (rc && rc != MIRT_E_DEVICE) return 1;
+    if (rc) return rc;
+    ctx->fused_frames++;
+    return MIRT_OK;
+}
 
 // MIRT_OK: the held stream was a whole pass (match_pass, pt_stream_match.hpp) and has been executed fused.  1: not a pass (nothing executed).  < 0: error.
 static int try_fuse_pass(mirt_ctx* ctx, const std::vector<Enqueue>& P) {
@@ -913,7 +943,7 @@ static int flush_pending(mirt_ctx* ctx) {
         for (size_t j = 0; j < p.args.size(); ++j)
             if (p.spec->args[j] == A_BUF && (!live_has(p.args[j].buf) || p.args[j].buf->ctx != ctx))
                 return fail(ctx, MIRT_E_HANDLE, "%s: a buffer of a held-back enqueue was released", p.spec->name);
-    int rc = try_fuse_pass(ctx, P);
+    int rc = pt::is_frame_init(P[0].spec->id) ? try_fuse_frame(ctx, P) : try_fuse_pass(ctx, P);
     if (rc <= 0) return rc;
     for (auto& p : P)
         if ((rc = launch_kernel(ctx, *p.spec, p.args, p.dim, p.g))) return rc;
@@ -935,6 +965,21 @@ int mirt_enqueue(mirt_ctx* ctx, mirt_kernel* k, unsigned dim, const size_t* glob
     }
     for (unsigned d = 0; d < dim; ++d)
         if (global[d] > 0xFFFFFFFFull) return fail(ctx, MIRT_E_ARG, "%s: global size exceeds 2^32", S.name);
+    if (ctx->frame_fusion && !ctx->capturing) {
+        // From an A04 / A07 initTrace on EVERY enqueue is held, whatever its kernel: the recogniser judges the stream as the host issued it, so a
+        // frame with anything else inside it (a second initTrace, a kernel of another dialect, stages out of order) runs enqueue by enqueue, whole
+        const bool held = !ctx->pending.empty() && pt::is_frame_init(ctx->pending[0].spec->id);
+        if (held || pt::is_frame_init(S.id)) {
+            if (!held) FLUSH_PENDING(ctx);                               // (a held Assign10 pass)
+            Enqueue p;
+            p.spec = &S; p.args = k->args; p.dim = dim;
+            for (unsigned d = 0; d < 3; ++d) p.g[d] = d < dim ? global[d] : 1;
+            ctx->pending.push_back(std::move(p));
+            if (ctx->pending.size() > 3) return flush_pending(ctx);     // longer than any frame: it is not one, run it now
+            return MIRT_OK;
+        }
+    }
+    if (!ctx->pending.empty() && pt::is_frame_init(ctx->pending[0].spec->id)) FLUSH_PENDING(ctx);   // anything else ends a held frame
     if (ctx->fusion >= 2 && !ctx->capturing && is_pass_kernel(S.id)) {
         if (S.id == pt::K_initTrace) FLUSH_PENDING(ctx);                 // a new pass begins: whatever was held is not one
         if (S.id == pt::K_initTrace || !ctx->pending.empty()) {
@@ -1444,6 +1489,77 @@ int mirt_ctx_fused_passes(mirt_ctx* ctx, uint64_t* count) try {
     *count = ctx->fused_passes;
     return MIRT_OK;
 } MIRT_CATCH("mirt_ctx_fused_passes", return MIRT_E_DEVICE)
+
+int mirt_ctx_set_frame_fusion(mirt_ctx* ctx, int on) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_frame_fusion: unknown context");
+    FLUSH_PENDING(ctx);
+    ctx->frame_fusion = on != 0;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_ctx_set_frame_fusion", return MIRT_E_DEVICE)
+
+int mirt_ctx_fused_frames(mirt_ctx* ctx, uint64_t* count) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_fused_frames: unknown context");
+    if (!count) return fail(ctx, MIRT_E_ARG, "mirt_ctx_fused_frames: null output");
+    *count = ctx->fused_frames;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_ctx_fused_frames", return MIRT_E_DEVICE)
+
+// A whole Assign04 / Assign07 frame in one launch (pt_kernels_frame.hip k_frame_fused).  Every check launch_kernel makes for initTrace and the trace
+// kernels over the full image is made here, all of them before anything is prepared or launched.
+static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d) {
+    if (!d || d->struct_size != sizeof(mirt_frame_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: descriptor size mismatch");
+    if (d->assign != 4 && d->assign != 7) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: assign %u (4 and 7 are frames of two launches; Assign01 is one launch already, Assign10 is mirt_render_pass)", d->assign);
+    const bool mesh = d->t_pos != nullptr, mol = d->s_atoms != nullptr;
+    if (!mesh && !mol) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: no stage asked for (neither t_pos nor s_atoms)");
+    if (d->assign == 4 && mol) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: Assign04's molecule kernel is not built (its molecule mode is Assign07's)");
+    if (!d->width || !d->height) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: empty image");
+    const uint32_t cols = f2u_host(d->cam[14]), rows = f2u_host(d->cam[15]);
+    if (cols != d->width || rows != d->height) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: camera says %ux%u, descriptor %ux%u", cols, rows, d->width, d->height);
+    if (!d->pixel) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: null pixel buffer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t npx = (uint64_t)cols * rows;
+    int rc;
+    if ((rc = need(ctx, "mirt_render_frame pixel", d->pixel, npx * 4))) return rc;
+    if (d->rays && (rc = need(ctx, "mirt_render_frame rays", d->rays, npx * kRayBytes))) return rc;
+    pt::FrameArgs A;
+    memset(&A, 0, sizeof A);
+    memcpy(A.cam, d->cam, 64);
+    A.assign = d->assign; A.gx = cols; A.gy = rows;
+    if (d->assign == 4) {
+        const uint32_t T = d->t_size;
+        if (!d->t_normal || !d->t_mindex || !d->t_mcolor) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: the Assign04 mesh needs t_normal, t_mindex and t_mcolor");
+        if ((rc = need(ctx, "mirt_render_frame t_pos", d->t_pos, (uint64_t)T * 48))) return rc;
+        if ((rc = need(ctx, "mirt_render_frame t_normal", d->t_normal, (uint64_t)T * 48))) return rc;
+        if ((rc = need(ctx, "mirt_render_frame t_mindex", d->t_mindex, (uint64_t)T * 4))) return rc;
+        if ((rc = need(ctx, "mirt_render_frame t_mcolor", d->t_mcolor, 16))) return rc;
+        if ((rc = ensure_prepared(ctx, d->t_pos, T))) return rc;
+        A.t_size = T; A.prep = d->t_pos->prep; A.normals = d->t_normal->ptr; A.mindex = d->t_mindex->ptr; A.mcolor = d->t_mcolor->ptr;
+        A.ncolors = (uint32_t)(d->t_mcolor->bytes / 16);
+    } else {
+        memcpy(A.bound, d->bounds, 32);
+        A.n_slabs = d->n_slabs; A.mesh = mesh; A.mol = mol;
+        if (mol && !d->s_slab_size) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: the molecule needs s_slab_size");
+        if (mesh && (!d->t_normal || !d->t_slab_size)) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: the Assign07 mesh needs t_normal and t_slab_size");
+        if (mol && (rc = check_grid(ctx, "mirt_render_frame molecule grid", d->s_slab_size, d->n_slabs, d->s_atoms, 16, nullptr, nullptr))) return rc;
+        if (mesh && (rc = check_grid(ctx, "mirt_render_frame mesh grid", d->t_slab_size, d->n_slabs, d->t_pos, 48, d->t_normal, nullptr))) return rc;
+        if (mesh && (rc = ensure_prepared(ctx, d->t_pos, d->t_slab_size->off_last))) return rc;
+        if (mol) { A.atoms = d->s_atoms->ptr; A.mol_slab_size = d->s_slab_size->ptr; }
+        if (mesh) { A.prep = d->t_pos->prep; A.normals = d->t_normal->ptr; A.slab_size = d->t_slab_size->ptr; A.n_slots = d->t_slab_size->off_last; }
+    }
+    A.pixels = d->pixel->ptr;
+    A.rays = d->rays ? d->rays->ptr : nullptr;
+    pt::launch_frame_fused(ctx->stream, A);
+    HIPCHK(ctx, hipGetLastError());
+    d->pixel->version++;
+    if (d->rays) d->rays->version++;
+    return MIRT_OK;
+}
+
+int mirt_render_frame(mirt_ctx* ctx, const mirt_frame_desc* d) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_frame: unknown context");
+    FLUSH_PENDING(ctx);
+    return render_frame_impl(ctx, d);
+} MIRT_CATCH("mirt_render_frame", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_exact_only(mirt_ctx* ctx, int on) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_exact_only: unknown context");

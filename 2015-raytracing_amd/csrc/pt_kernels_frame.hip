@@ -292,6 +292,155 @@ __global__ void __launch_bounds__(256) k_a07_molTrace(uchar4* pixels, F16 cam16,
     pixels[pix] = make_uchar4(f2u8((float)((hx % 2) + 1) * k), f2u8((float)((hy % 2) + 1) * k), f2u8((float)((hz % 2) + 1) * k), 255);
 }
 
+// ---- the whole Assign04 / Assign07 frame in one launch (mirt_render_frame) ---------------------------------------------------------------
+// initTrace + the trace kernel(s) above on one thread per pixel, the ray in registers: no 48-byte ray goes out to memory and comes back between two
+// launches.  A stage below is its kernel's body on a ray it is handed instead of one it loads: every early return of the kernel is a return that
+// leaves the colour as it was (black, or what the stage before left -- what initTrace's and molTrace's stores leave in `pixels` today), the store of
+// rays[pix].maxt is an assignment to ray.maxt.  The kernel stores the pixel once, and the finished ray once when a ray buffer is given (RAYS): the
+// same 40 bytes the launches leave there.  Which stages run is the template parameter STAGES; the walks have no run-time switch.
+enum FrameStage : uint32_t { FS_A04 = 1u, FS_MESH = 2u, FS_MOL = 4u };
+
+PT_DEV uchar4 parity_colour(int hx, int hy, int hz, float shade) {   // A07 code.cl:463-469, 616-622
+    const float k = shade * 127.0f;
+    return make_uchar4(f2u8((float)((hx % 2) + 1) * k), f2u8((float)((hy % 2) + 1) * k), f2u8((float)((hz % 2) + 1) * k), 255);
+}
+
+// k_a04_meshTrace on `ray`
+PT_DEV void frame_stage_a04(const Cam& cam, Ray& ray, uint32_t t_size, const float4* prep, const float4* normals, const uint32_t* mindex,
+                            const float4* mcolor, uint32_t ncolors, uchar4& colour) {
+    float champ_t = PT_INF, cb = 0.0f, cg = 0.0f;
+    uint32_t champ_i = t_size;
+    const float4* __restrict__ p = prep;
+    const float4* __restrict__ groups = prep + 3u * (size_t)t_size;
+    const float dd = ray.d.x * ray.d.x + ray.d.y * ray.d.y + ray.d.z * ray.d.z;
+    for (uint32_t i = 0; i < t_size; ++i, p += 3) {
+        if ((i % kTriGroup) == 0u && i + kTriGroup <= t_size && __builtin_amdgcn_ballot_w64(!group_missed(ray, dd, groups[i / kTriGroup])) == 0ull) {
+            i += kTriGroup - 1u;
+            p += 3u * (kTriGroup - 1u);
+            continue;
+        }
+        const float4 A = p[0], B = p[1], C = p[2];
+        const f3 p0 = mk3(A.x, A.y, A.z), e1 = mk3(B.x, B.y, B.z), e2 = mk3(C.x, C.y, C.z), n = mk3(A.w, B.w, C.w);
+        const float div = dot3(n, ray.d);
+        bool in = !(div <= 0);
+        if (__builtin_amdgcn_ballot_w64(in) == 0ull) continue;
+        const float idiv = rcp_exact(div, !in);
+        const f3 s = sub3(ray.o, p0);
+        const float beta = dot3(cross3(s, ray.d), e2) * idiv;
+        in = in & !(beta < 0.0f) & !(beta > 1.0f);
+        if (__builtin_amdgcn_ballot_w64(in) == 0ull) continue;
+        const float gamma = dot3(cross3(s, e1), ray.d) * idiv;
+        const float gb = gamma + beta;
+        in = in & !(gamma < 0.0f) & !(gamma > 1.0f) & !(gb < 0.0f) & !(gb > 1.0f);
+        if (__builtin_amdgcn_ballot_w64(in) == 0ull) continue;
+        const float t = dot3(cross3(s, e2), e1) * -idiv;
+        in = in & (t > ray.mint) & (t < ray.maxt);
+        if (in && t < champ_t) { champ_t = t; champ_i = i; cb = beta; cg = gamma; }
+    }
+    if (champ_i >= t_size) return;
+    ray.maxt = champ_t;
+    const f3 n = interp_normal(normals, champ_i, cb, cg);
+    const float shade = cl_clamp(dot3(cam.W, n), 0.0f, 1.0f);
+    const uint32_t m = mindex[champ_i];
+    if (m >= ncolors) return;
+    const float4 mc = mcolor[m];
+    colour = make_uchar4(f2u8((mc.x * 255.0f) * shade), f2u8((mc.y * 255.0f) * shade), f2u8((mc.z * 255.0f) * shade), 255);
+}
+
+// The grid walk of k_a07_meshTrace (MOL false: triangles, GROUPS as there) and of k_a07_molTrace (MOL true: atoms) on `ray`: phase A closes and
+// opens cells until the lane holds a primitive, phase B tests it.  prims: the prepared records (+ group spheres at record group_slots) | the atoms.
+template <bool MOL, bool GROUPS>
+PT_DEV void frame_stage_grid(const Cam& cam, Ray& ray, const Box& bound, const float4* prims, const float4* normals, uint32_t n_slabs,
+                             const uint32_t* slab_size, uint32_t group_slots, uchar4& colour) {
+    if (ray.mint == ray.maxt) return;
+    const BoxHit bh = inter_aabb(ray, bound);
+    if (!bh.v) return;
+    Axis ax = axis_setup(ray.o.x, ray.d.x, bh.tmin, bound.lo.x, bound.hi.x, n_slabs);
+    Axis ay = axis_setup(ray.o.y, ray.d.y, bh.tmin, bound.lo.y, bound.hi.y, n_slabs);
+    Axis az = axis_setup(ray.o.z, ray.d.z, bh.tmin, bound.lo.z, bound.hi.z, n_slabs);
+    SphereRay sr = {0.0f, 0.0f};
+    if (MOL) sr = sphere_ray<false>(ray.d);
+    float champ_t = ray.maxt, cb = 0.0f, cg = 0.0f;
+    uint32_t champ_i = UINT32_MAX;
+    int hx = 0, hy = 0, hz = 0;
+    const uint32_t zs = n_slabs * n_slabs, ys = n_slabs;
+    float t = bh.tmin, cmin = t, cmax = cl_min(cl_min(ax.tnext, ay.tnext), az.tnext);
+    uint32_t cell = __umul24((uint32_t)az.slab, zs) + __umul24((uint32_t)ay.slab, ys) + (uint32_t)ax.slab;
+    uint32_t i = slab_size[cell], end = slab_size[cell + 1];
+    const float dd = !MOL && GROUPS ? ray.d.x * ray.d.x + ray.d.y * ray.d.y + ray.d.z * ray.d.z : 0.0f;
+    for (;;) {
+        bool alive = true;
+        while (i == end) {
+            if (champ_i != UINT32_MAX) { alive = false; break; }
+            t = cmax;
+            if (t == ax.tnext) {
+                ax.tnext += ax.dt;
+                ax.slab += ax.dslab;
+                if (t >= bh.tmax || ax.slab == ax.limit) { alive = false; break; }
+            } else if (t == ay.tnext) {
+                ay.tnext += ay.dt;
+                ay.slab += ay.dslab;
+                if (t >= bh.tmax || ay.slab == ay.limit) { alive = false; break; }
+            } else {
+                az.tnext += az.dt;
+                az.slab += az.dslab;
+                if (t >= bh.tmax || az.slab == az.limit) { alive = false; break; }
+            }
+            cmin = t;
+            cmax = cl_min(cl_min(ax.tnext, ay.tnext), az.tnext);
+            cell = __umul24((uint32_t)az.slab, zs) + __umul24((uint32_t)ay.slab, ys) + (uint32_t)ax.slab;
+            i = slab_size[cell];
+            end = slab_size[cell + 1];
+        }
+        if (!alive) break;
+        if (!MOL && GROUPS) {
+            const bool whole = ((i % kTriGroup) == 0u) & (end - i >= kTriGroup);
+            if (__builtin_amdgcn_ballot_w64(!whole) == 0ull &&
+                __builtin_amdgcn_ballot_w64(!group_missed(ray, dd, (prims + 3u * (size_t)group_slots)[i / kTriGroup])) == 0ull) {
+                i += kTriGroup;
+                continue;
+            }
+        }
+        float ti, b = 0.0f, g = 0.0f;
+        bool hit;
+        if (MOL) {
+            hit = sph_test(ray.o, ray.d, sr, cmin, cmax, prims[i], ti);
+        } else {
+            const float4* __restrict__ p = prims + 3u * (size_t)i;
+            hit = tri_test_staged<TRI_A07>(true, ray.o, ray.d, cmin, cmax, p[0], p[1], p[2], ti, b, g);
+        }
+        if (hit && ti < champ_t) { champ_t = ti; champ_i = i; cb = b; cg = g; hx = ax.slab; hy = ay.slab; hz = az.slab; }
+        ++i;
+    }
+    if (champ_i == UINT32_MAX) return;
+    ray.maxt = champ_t;
+    f3 n;
+    if (MOL) n = norm3(sub3(fma3(champ_t, ray.d, ray.o), ld3(prims[champ_i])));   // A07 code.cl:455-457
+    else n = interp_normal(normals, champ_i, cb, cg);
+    colour = parity_colour(hx, hy, hz, cl_clamp(dot3(cam.W, n), 0.0f, 1.0f));
+}
+
+template <uint32_t STAGES, bool GROUPS, bool RAYS>
+__global__ void __launch_bounds__(256) k_frame_fused(FrameArgs a) {
+    const Cam cam = mk_cam(*reinterpret_cast<const F16*>(a.cam));
+    const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t row = blockIdx.y * blockDim.y + threadIdx.y;
+    if (col >= a.gx || row >= a.gy || col >= cam.cols || row >= cam.rows) return;
+    const size_t pix = (size_t)cam.cols * row + col;
+    Ray ray = pinhole_ray(cam, (float)col, (float)row);
+    const Box bound = mk_box(*reinterpret_cast<const Box8*>(a.bound));
+    if (!(STAGES & FS_A04)) clip_to(ray, bound);   // A07 code.cl:321-328
+    uchar4 colour = make_uchar4(0, 0, 0, 255);
+    if (STAGES & FS_A04)
+        frame_stage_a04(cam, ray, a.t_size, (const float4*)a.prep, (const float4*)a.normals, (const uint32_t*)a.mindex, (const float4*)a.mcolor, a.ncolors, colour);
+    // computeBoth (A07 code.js:629-661): the molecule, then the mesh from the maxt the molecule left
+    if (STAGES & FS_MOL) frame_stage_grid<true, false>(cam, ray, bound, (const float4*)a.atoms, nullptr, a.n_slabs, (const uint32_t*)a.mol_slab_size, 0u, colour);
+    if (STAGES & FS_MESH)
+        frame_stage_grid<false, GROUPS>(cam, ray, bound, (const float4*)a.prep, (const float4*)a.normals, a.n_slabs, (const uint32_t*)a.slab_size, a.group_slots, colour);
+    if (RAYS) store_ray48(&((RayAoS*)a.rays)[pix], ray);
+    ((uchar4*)a.pixels)[pix] = colour;
+}
+
 static F16 mk16f(const float* f) { F16 r; for (int i = 0; i < 16; ++i) r.v[i] = f[i]; return r; }
 static Box8 mk8f(const float* f) { Box8 r; for (int i = 0; i < 8; ++i) r.v[i] = f ? f[i] : 0.0f; return r; }
 static dim3 grid2(uint32_t gx, uint32_t gy) { return dim3((gx + 31) / 32, (gy + 7) / 8); }
@@ -330,6 +479,23 @@ void launch_a07_molTrace(hipStream_t s, void* pixels, const float* cam, void* ra
     if (!gx || !gy) return;
     hipLaunchKernelGGL(k_a07_molTrace, grid2(gx, gy), dim3(32, 8), 0, s, (uchar4*)pixels, mk16f(cam), (RayAoS*)rays, (const float4*)atoms, mk8f(bound),
                        n_slabs, (const uint32_t*)slab_size, gx, gy);
+}
+
+template <uint32_t STAGES, bool GROUPS>
+static void launch_frame_fused_t(hipStream_t s, const FrameArgs& a) {
+    if (a.rays) hipLaunchKernelGGL((k_frame_fused<STAGES, GROUPS, true>), grid2(a.gx, a.gy), dim3(32, 8), 0, s, a);
+    else hipLaunchKernelGGL((k_frame_fused<STAGES, GROUPS, false>), grid2(a.gx, a.gy), dim3(32, 8), 0, s, a);
+}
+void launch_frame_fused(hipStream_t s, FrameArgs a) {
+    if (!a.gx || !a.gy) return;
+    if (a.assign == 4) { launch_frame_fused_t<FS_A04, false>(s, a); return; }
+    // the same rule as launch_a07_meshTrace: group spheres where cells are long on average
+    const uint64_t cells = (uint64_t)a.n_slabs * a.n_slabs * a.n_slabs;
+    a.group_slots = a.mesh && (uint64_t)a.n_slots >= cells * 4u * kTriGroup ? a.n_slots : 0u;
+    const bool mesh = a.mesh != 0u, mol = a.mol != 0u;
+    if (mesh && mol) { if (a.group_slots) launch_frame_fused_t<FS_MOL | FS_MESH, true>(s, a); else launch_frame_fused_t<FS_MOL | FS_MESH, false>(s, a); }
+    else if (mesh) { if (a.group_slots) launch_frame_fused_t<FS_MESH, true>(s, a); else launch_frame_fused_t<FS_MESH, false>(s, a); }
+    else if (mol) launch_frame_fused_t<FS_MOL, false>(s, a);
 }
 
 }  // namespace pt

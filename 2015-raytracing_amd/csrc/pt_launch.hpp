@@ -166,4 +166,30 @@ void launch_a07_meshTrace(hipStream_t s, void* pixels, const float* cam, void* r
 void launch_a07_molTrace(hipStream_t s, void* pixels, const float* cam, void* rays, const void* atoms, const float* bound, uint32_t n_slabs,
                          const void* slab_size, uint32_t gx, uint32_t gy);
 
+// the whole frame in one launch (k_frame_fused): initTrace and the trace stage(s) on one thread per pixel, the ray in registers.  assign 4: the brute
+// force over `prep`; assign 7: the molecule stage when `atoms` is set, then the mesh stage when `prep` is, the mesh starting from the maxt the molecule
+// left (A07 code.js:629-661 computeBoth).  rays null: nothing per ray touches memory.  The caller has checked every extent (mirt_abi.cpp render_frame_impl).
+struct FrameArgs {
+    float cam[16];
+    float bound[8];          // assign 7: the one box of initTrace's clip and of both grids
+    void* pixels;            // uchar4 per pixel
+    void* rays;              // 48 B per pixel, or null
+    uint32_t assign;
+    uint32_t mesh, mol;      // assign 7: which stages run
+    uint32_t gx, gy;         // the NDRange; pixels outside it or outside cam.cols x cam.rows stay untouched
+    uint32_t t_size;         // assign 4
+    const void* prep;        // prepared records (launch_prepTriangles) of the t_size triangles | of the n_slots grid slots
+    const void* normals;
+    const void* mindex;      // assign 4
+    const void* mcolor;
+    uint32_t ncolors;
+    uint32_t n_slabs;        // assign 7, both grids
+    const void* slab_size;   // the mesh's cell table
+    uint32_t n_slots;
+    uint32_t group_slots;    // (launch_frame_fused sets it)
+    const void* atoms;       // float4 {c, r*r} per slot
+    const void* mol_slab_size;
+};
+void launch_frame_fused(hipStream_t s, FrameArgs a);
+
 }  // namespace pt

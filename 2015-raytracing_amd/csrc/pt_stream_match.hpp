@@ -312,4 +312,66 @@ inline bool match_pass(const std::vector<Enqueue>& P, PassMatch* m) {
     return true;
 }
 
+// ---- the frame dialects (Assign04 / Assign07): is a held stream exactly one frame as the pages issue it -- compute (A07 code.js:571-600: initTrace,
+// molTrace), computeTri (A04 code.js:553-577, A07 code.js:603-628: initTrace, meshTrace) or computeBoth (A07 code.js:629-661: initTrace, molTrace,
+// meshTrace) -- over one pixel buffer, one ray buffer, one camera block, one box and one NDRange that covers the image?  The fused frame
+// (mirt_render_frame) writes pixels only, so a wrong "yes" loses a ray buffer somebody reads or renders over the wrong box: everything is compared.
+struct FrameMatch {
+    uint32_t assign = 0, width = 0, height = 0;
+    float cam[16], bounds[8];                       // bounds: Assign07 only (zero for Assign04)
+    mirt_buf *pixels = nullptr, *rays = nullptr;
+    bool mesh = false, mol = false;
+    uint32_t t_size = 0, s_size = 0, n_slabs = 0;   // n_slabs: of both grids
+    mirt_buf *t_pos = nullptr, *t_normal = nullptr, *t_mindex = nullptr, *t_mcolor = nullptr, *t_slab_size = nullptr;
+    mirt_buf *s_atoms = nullptr, *s_mindex = nullptr, *s_mcolor = nullptr, *s_slab_size = nullptr;
+};
+
+inline bool is_frame_init(KernelId k) { return k == K_a04_initTrace || k == K_a07_initTrace; }
+inline bool is_frame_trace(KernelId k) { return k == K_a04_meshTrace || k == K_a07_meshTrace || k == K_a07_molTrace; }
+
+inline bool match_frame(const std::vector<Enqueue>& P, FrameMatch* m) {
+    if (P.size() < 2 || P.size() > 3 || !is_frame_init(P[0].spec->id) || P[0].dim != 2) return false;
+    const bool a07 = P[0].spec->id == K_a07_initTrace;
+    const std::vector<KArg>& a0 = P[0].args;
+    mirt_buf *pixels = arg(a0, frame::pixels), *rays = arg(a0, frame::rays);
+    const float* cam = arg(a0, frame::fcam);
+    const uint32_t cols = f2u_host(cam[14]), rows = f2u_host(cam[15]);
+    if (!cols || !rows || P[0].g[0] < cols || P[0].g[1] < rows) return false;
+    FrameMatch r;
+    memset(r.bounds, 0, sizeof r.bounds);
+    if (a07) memcpy(r.bounds, arg(a0, a07_initTrace::bound), 32);
+    for (size_t i = 1; i < P.size(); ++i) {
+        const Enqueue& e = P[i];
+        const std::vector<KArg>& a = e.args;
+        // every stage over the same pixels, camera block and rays, with the global size of the initTrace
+        if (!is_frame_trace(e.spec->id) || e.dim != 2 || e.g[0] != P[0].g[0] || e.g[1] != P[0].g[1]) return false;
+        if (arg(a, frame::pixels) != pixels || arg(a, frame::rays) != rays || memcmp(arg(a, frame::fcam), cam, 64) != 0) return false;
+        if (e.spec->id == K_a04_meshTrace) {
+            namespace M = a04_meshTrace;
+            if (a07 || r.mesh) return false;
+            r.mesh = true; r.t_size = arg(a, M::t_size);
+            r.t_pos = arg(a, M::t_pos); r.t_normal = arg(a, M::t_normal); r.t_mindex = arg(a, M::t_mindex); r.t_mcolor = arg(a, M::m_color);
+        } else if (e.spec->id == K_a07_molTrace) {
+            namespace M = a07_molTrace;
+            if (!a07 || r.mol || r.mesh) return false;                      // the molecule comes first, once
+            if (memcmp(arg(a, M::bound), r.bounds, 32) != 0) return false;
+            r.mol = true; r.s_size = arg(a, M::s_size); r.n_slabs = arg(a, M::n_slabs);
+            r.s_atoms = arg(a, M::s_atoms); r.s_mindex = arg(a, M::s_mindex); r.s_mcolor = arg(a, M::m_color); r.s_slab_size = arg(a, M::slab_size);
+        } else {
+            namespace M = a07_meshTrace;
+            if (!a07 || r.mesh) return false;
+            if (memcmp(arg(a, M::bound), r.bounds, 32) != 0) return false;
+            if (r.mol && arg(a, M::n_slabs) != r.n_slabs) return false;    // computeBoth bins both models with the page's one n_slabs
+            r.mesh = true; r.t_size = arg(a, M::t_size); r.n_slabs = arg(a, M::n_slabs);
+            r.t_pos = arg(a, M::t_pos); r.t_normal = arg(a, M::t_normal); r.t_mindex = arg(a, M::t_mindex); r.t_mcolor = arg(a, M::m_color);
+            r.t_slab_size = arg(a, M::slab_size);
+        }
+    }
+    r.assign = a07 ? 7u : 4u; r.width = cols; r.height = rows;
+    memcpy(r.cam, cam, 64);
+    r.pixels = pixels; r.rays = rays;
+    *m = r;
+    return true;
+}
+
 }  // namespace pt

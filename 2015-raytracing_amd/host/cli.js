@@ -4,7 +4,7 @@
 //   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]]
 //                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
-//   node cli.js frame      <1|4|7> <mesh.json|-> <width> <height> <nSlabs|0> <out.rgba>  -> RGBA8 frame of that job
+//   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
 //   node cli.js devices                                                             -> what webcl.getPlatforms()/getDevices() report
 "use strict";
@@ -64,11 +64,19 @@ if (cmd === "pack") {
 } else if (cmd === "pack-frame" || cmd === "frame") {
   if (rest.length < 4) usage();
   const frame = require("./frame.js");
-  const assign = +rest[0], text = rest[1] === "-" ? null : fs.readFileSync(rest[1], "utf8").replace(/^\ufeff/, "");
-  const model = text === null ? null : /\.pdb$/i.test(rest[1]) ? { pdb: text } : JSON.parse(text);   // .pdb: Assign07's molecule mode
-  const p = frame.packFrame(assign, model, +rest[2], +rest[3], +rest[4] || 2);
-  if (cmd === "pack-frame") process.stdout.write(JSON.stringify(scene.packedToJSON(p)));
-  else writeFrame(rest[5], frame.renderFrame(p), +rest[2], +rest[3]);
+  const oneLaunch = rest.includes("--one-launch");
+  const a = rest.filter((x) => x !== "--one-launch");
+  const read = (f) => fs.readFileSync(f, "utf8").replace(/^\ufeff/, "");
+  const assign = +a[0], text = a[1] === "-" ? null : read(a[1]);
+  let model = text === null ? null : /\.pdb$/i.test(a[1]) ? { pdb: text } : JSON.parse(text);   // .pdb: Assign07's molecule mode
+  if (assign === 7 && model && !model.pdb && /\.pdb$/i.test(a[2] || "")) { model = { mesh: model, pdb: read(a[2]) }; a.splice(2, 1); }   // both models
+  const p = frame.packFrame(assign, model, +a[2], +a[3], +a[4] || 2);
+  if (cmd === "pack-frame") { const j = scene.packedToJSON(p); if (p.mol) j.mol = scene.packedToJSON(p.mol); process.stdout.write(JSON.stringify(j)); }
+  else {
+    const px = frame.renderFrame(p, { oneLaunch: oneLaunch });
+    writeFrame(a[5], px, +a[2], +a[3]);
+    process.stderr.write(`frame ${assign} ${+a[2]}x${+a[3]}: ${oneLaunch ? "one launch" : "kernel by kernel"}; frames the runtime fused from enqueues: ${px.fusedFrames}\n`);
+  }
 } else if (cmd === "ingest") {
   if (rest.length < 2) usage();
   const model = JSON.parse(fs.readFileSync(rest[0], "utf8").replace(/^\ufeff/, ""));

@@ -24,8 +24,21 @@ function packFrame(assign, model, width, height, nSlabs) {
     const f = cam.toFloat32Array(); f[14] = height; f[15] = width;
     return { assign: 1, width: width, height: height, cam: f };
   }
+  // Both models, { mesh: <parsed mesh.json>, pdb: <file text> }: computeBoth's merged bound and camera (A07 code.js:642-650), and BOTH packings binned in
+  // that one bound with the page's one n_slabs (the page bins and bounds each model in its own box, :475, 533): the mesh job's fields, the molecule's
+  // under `mol`.  One box is what lets the frame run as one launch with one grid walk set-up (mirt_render_frame).
+  if (assign === 7 && model && model.mesh && typeof model.pdb === "string") {
+    const md = scene.parseMeshJSON(model.mesh), mol = parsePDB(model.pdb);
+    const both = new scene.Bounds();
+    both.merge(mol.bounds); both.merge(md.bounds);
+    const p = packFrame(7, Object.assign({}, model.mesh, { boundsOverride: both }), width, height, nSlabs);
+    const m = packMol(Object.assign({}, mol, { bounds: both }), new scene.Camera(), width, height, nSlabs);
+    p.mol = { s_size: m.s_size, atoms: m.atoms, mindex: m.mindex, mcolor: m.mcolor, slab_size: m.slab_size };
+    return p;
+  }
   if (assign === 7 && model && typeof model.pdb === "string") return packMol(parsePDB(model.pdb), cam, width, height, nSlabs);   // { pdb: <file text> }
   const md = scene.parseMeshJSON(model);
+  if (model.boundsOverride) md.bounds = model.boundsOverride;
   cam.defaultInit(); cam.set(md.bounds, width, height);
   const p = { assign: assign, width: width, height: height, cam: cam.toFloat32Array(), bounds: scene.bounds2AABB(md.bounds),
               t_size: md.nTriangles, mcolor: new Float32Array(md.materials) };
@@ -87,13 +100,21 @@ function renderFrame(p, opt) {
   if (!devs.length) throw new Error("no MI355X visible: this host has no CPU path");
   const device = devs[opt.device || 0];
   const ctx = webcl.createContext(device), q = ctx.createCommandQueue();
+  if (opt.frameFusion !== undefined) ctx.setFrameFusion(opt.frameFusion);
   const prog = ctx.createProgram(MANIFEST[p.assign]);
   prog.build();
   const w = p.width, h = p.height, res = [];
   const buf = (flags, a) => { const b = ctx.createBuffer(flags, Math.max(a.byteLength || a, 16)); res.push(b); if (a.byteLength) q.enqueueWriteBuffer(b, false, 0, a.byteLength, a, []); return b; };
   const pixels = buf(webcl.MEM_WRITE_ONLY, w * h * 4);
   const gws = [ceilTo(w, 8), ceilTo(h, 8)], lws = [8, 8];   // getLocalWS(2, 64)
-  if (p.assign === 1) {
+  if (opt.oneLaunch && p.assign !== 1) {   // the whole frame in one launch, no ray buffer (queue.renderFrame)
+    const RO = webcl.MEM_READ_ONLY, d = { assign: p.assign, width: w, height: h, cam: p.cam, bounds: p.bounds, nSlabs: p.n_slabs || 0, pixel: pixels };
+    const mol = p.atoms ? p : p.mol;
+    if (mol) Object.assign(d, { sSize: mol.s_size, sAtoms: buf(RO, mol.atoms), sMindex: buf(RO, mol.mindex), sMcolor: buf(RO, mol.mcolor), sSlabSize: buf(RO, mol.slab_size) });
+    if (p.pos) Object.assign(d, { tSize: p.t_size, tPos: buf(RO, p.pos), tNormal: buf(RO, p.normal), tMindex: buf(RO, p.mindex), tMcolor: buf(RO, p.mcolor) });
+    if (p.pos && p.assign === 7) d.tSlabSize = buf(RO, p.slab_size);
+    q.renderFrame(d);
+  } else if (p.assign === 1) {
     const k = prog.createKernel("raytrace"); res.push(k);
     k.setArg(0, pixels); k.setArg(1, p.cam);
     q.enqueueNDRangeKernel(k, 2, null, gws, lws);
@@ -102,6 +123,13 @@ function renderFrame(p, opt) {
     sk.setArg(0, sb); q.enqueueNDRangeKernel(sk, 1, null, [1], [1]); q.enqueueReadBuffer(sb, false, 0, 4, so, []); q.finish(); sb.release(); sk.release();
     const rays = buf(webcl.MEM_READ_WRITE, w * h * so[0]);
     const it = prog.createKernel("initTrace"), mt = prog.createKernel(p.atoms ? "molTrace" : "meshTrace"); res.push(it, mt);
+    let mo = null;   // both models: the molecule's kernel, ahead of the mesh's (A07 code.js:659-661)
+    if (p.mol) {
+      const RO = webcl.MEM_READ_ONLY, m = p.mol;
+      mo = prog.createKernel("molTrace"); res.push(mo);
+      [pixels, p.cam, rays, new Uint32Array([m.s_size]), buf(RO, m.atoms), buf(RO, m.mindex), buf(RO, m.mcolor), p.bounds, new Uint32Array([p.n_slabs]),
+       buf(RO, m.slab_size)].forEach((v, i) => mo.setArg(i, v));
+    }
     it.setArg(0, pixels); it.setArg(1, p.cam); it.setArg(2, rays);
     if (p.assign === 7) it.setArg(3, p.bounds);
     const RO = webcl.MEM_READ_ONLY;
@@ -111,11 +139,13 @@ function renderFrame(p, opt) {
     } else [pixels, p.cam, rays, new Uint32Array([p.t_size]), buf(RO, p.pos), buf(RO, p.normal), buf(RO, p.mindex), buf(RO, p.mcolor)].forEach((v, i) => mt.setArg(i, v));
     if (p.assign === 7 && !p.atoms) { mt.setArg(8, p.bounds); mt.setArg(9, new Uint32Array([p.n_slabs])); mt.setArg(10, buf(RO, p.slab_size)); }
     q.enqueueNDRangeKernel(it, 2, null, gws, lws);
+    if (mo) q.enqueueNDRangeKernel(mo, 2, null, gws, lws);
     q.enqueueNDRangeKernel(mt, 2, null, gws, lws);
   }
   const out = new Uint8ClampedArray(w * h * 4);
   q.enqueueReadBuffer(pixels, false, 0, out.length, out, []);
   q.finish();
+  out.fusedFrames = ctx.fusedFrames();   // frames the runtime ran as one launch from the enqueues above (ctx.setFrameFusion / MIRT_FRAME_FUSION=1)
   res.forEach((r) => r.release());
   prog.release(); q.release(); ctx.release();
   return out;

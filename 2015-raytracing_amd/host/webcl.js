@@ -173,6 +173,14 @@ class WebCLCommandQueue {
     });
     wrap(() => native().renderPass(this.ctx.h, d));
   }
+  // ---- extension: a whole Assign04 / Assign07 frame in one launch (mirt_render_frame): initTrace and the trace kernel(s) on one thread per pixel,
+  // no ray buffer unless desc.rays is given.  desc: {assign, width, height, cam, bounds, nSlabs, pixel, rays?} plus the mesh {tSize, tPos, tNormal,
+  // tMindex, tMcolor, tSlabSize} and / or the molecule {sSize, sAtoms, sMindex, sMcolor, sSlabSize} as WebCLBuffers; both: molecule, then mesh (computeBoth)
+  renderFrame(desc) {
+    const d = Object.assign({}, desc);
+    for (const k of ["tPos", "tNormal", "tMindex", "tMcolor", "tSlabSize", "sAtoms", "sMindex", "sMcolor", "sSlabSize", "pixel", "rays"]) d[k] = desc[k] ? desc[k].h : undefined;
+    wrap(() => native().renderFrame(this.ctx.h, d));
+  }
   // n passes from desc.passIndex on in one call (mirt_render_passes): the frame after the last of them; desc.firstPass starts the frame, and then
   // desc.acu may be null where the passes resolve their own pixels (rays_per_pixel > 1 dividing 256, or above 256: mirt.h).
   // At most MAX_PASSES_PER_CALL (checked here: the addon reads the count as a uint32, which would wrap)
@@ -289,6 +297,10 @@ class WebCLContext {
   // (mirt_ctx_create) stays at 0 unless asked.
   setFusion(level) { wrap(() => native().ctxSetFusion(this.h, level)); }
   fusedPasses() { return wrap(() => native().ctxFusedPasses(this.h)); }
+  // extension (mirt_ctx_set_frame_fusion): the Assign04 / Assign07 pages' frame stream -- initTrace, then molTrace and / or meshTrace -- runs as one
+  // launch and the Ray buffer is not written.  Off unless asked for here or with MIRT_FRAME_FUSION=1 in the environment.
+  setFrameFusion(on) { wrap(() => native().ctxSetFrameFusion(this.h, on ? 1 : 0)); }
+  fusedFrames() { return wrap(() => native().ctxFusedFrames(this.h)); }
   release() { if (this.h && !this.grouped) wrap(() => native().ctxDestroy(this.h)); this.h = null; }
 }
 

@@ -56,6 +56,15 @@ class _PassDesc(C.Structure):
                 ("material", C.c_void_p), ("seeds", C.c_void_p), ("acu", C.c_void_p), ("pixel", C.c_void_p), ("radiance", C.c_void_p)]
 
 
+class _FrameDesc(C.Structure):   # mirt_frame_desc
+    _fields_ = [("struct_size", C.c_uint32), ("assign", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("cam", C.c_float * 16), ("bounds", C.c_float * 8), ("t_size", C.c_uint32), ("s_size", C.c_uint32),
+                ("t_pos", C.c_void_p), ("t_normal", C.c_void_p), ("t_mindex", C.c_void_p), ("t_mcolor", C.c_void_p),
+                ("s_atoms", C.c_void_p), ("s_mindex", C.c_void_p), ("s_mcolor", C.c_void_p),
+                ("n_slabs", C.c_uint32), ("reserved", C.c_uint32),
+                ("t_slab_size", C.c_void_p), ("s_slab_size", C.c_void_p), ("pixel", C.c_void_p), ("rays", C.c_void_p)]
+
+
 _lib = None
 
 PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
@@ -95,6 +104,9 @@ SYMBOLS = {
     "mirt_ctx_set_exact_only": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_set_fusion": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_fused_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_render_frame": (C.c_int, [C.c_void_p, C.POINTER(_FrameDesc)]),
+    "mirt_ctx_set_frame_fusion": (C.c_int, [C.c_void_p, C.c_int]),
+    "mirt_ctx_fused_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_seed_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32]),
     "mirt_zero": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mirt_timer_start": (C.c_int, [C.c_void_p]),
@@ -298,6 +310,34 @@ class Context:
         n = C.c_uint64()
         self._chk(lib().mirt_ctx_fused_passes(self.h, C.byref(n)))
         return n.value
+
+    def set_frame_fusion(self, on=True):
+        """command-stream fusion of the Assign04 / Assign07 frame stream (include/mirt.h): initTrace + molTrace / meshTrace run as one launch"""
+        self._chk(lib().mirt_ctx_set_frame_fusion(self.h, 1 if on else 0))
+
+    def fused_frames(self):
+        n = C.c_uint64()
+        self._chk(lib().mirt_ctx_fused_frames(self.h, C.byref(n)))
+        return n.value
+
+    def render_frame(self, assign, width, height, cam, pixel, bounds=None, n_slabs=0, mesh=None, mol=None, rays=None):
+        """mirt_render_frame: a whole Assign04 / Assign07 frame in one launch.  mesh: dict(t_size, pos, normal, mindex, mcolor[, slab_size]) of
+        Buffers, mol: dict(s_size, atoms, mindex, mcolor, slab_size); both: the molecule, then the mesh.  rays: optional 48-byte-per-pixel Buffer."""
+        d = _FrameDesc()
+        d.struct_size, d.assign, d.width, d.height, d.n_slabs = C.sizeof(_FrameDesc), int(assign), int(width), int(height), int(n_slabs)
+        d.cam = _f(cam, 16)
+        if bounds is not None:
+            d.bounds = _f(bounds, 8)
+        h = lambda b: b.h if b is not None else None   # noqa: E731
+        if mesh:
+            d.t_size = int(mesh.get("t_size", 0))
+            d.t_pos, d.t_normal, d.t_mindex, d.t_mcolor = h(mesh.get("pos")), h(mesh.get("normal")), h(mesh.get("mindex")), h(mesh.get("mcolor"))
+            d.t_slab_size = h(mesh.get("slab_size"))
+        if mol:
+            d.s_size = int(mol.get("s_size", 0))
+            d.s_atoms, d.s_mindex, d.s_mcolor, d.s_slab_size = h(mol.get("atoms")), h(mol.get("mindex")), h(mol.get("mcolor")), h(mol.get("slab_size"))
+        d.pixel, d.rays = h(pixel), h(rays)
+        self._chk(lib().mirt_render_frame(self.h, C.byref(d)))
 
     def set_profiling(self, on=True):
         self._chk(lib().mirt_ctx_set_profiling(self.h, 1 if on else 0))

@@ -285,6 +285,11 @@ class FramePacked:
         self.assign, self.width, self.height = int(d["assign"]), int(d["width"]), int(d["height"])
         self.cam = np.asarray(d["cam"], np.float32)
         self.mol = "atoms" in d       # A07 molecule mode: parsePDB + splitMolData + molTrace (A07 code.js:569-600)
+        self.both = None              # both models (`cli.js pack-frame 7 <mesh.json> <mol.pdb>`): the mesh job's fields, the molecule's packing under "mol"
+        if isinstance(d.get("mol"), dict):
+            m = d["mol"]
+            self.both = dict(s_size=int(m["s_size"]), atoms=np.asarray(m["atoms"], np.float32), mindex=np.asarray(m["mindex"], np.uint32),
+                             mcolor=np.asarray(m["mcolor"], np.float32), slab_size=np.asarray(m["slab_size"], np.uint32))
         if self.mol:
             self.bounds = np.asarray(d["bounds"], np.float32)
             self.s_size = int(d["s_size"])
@@ -353,6 +358,97 @@ def render_frame(ctx, p, timing=None):
     finally:
         for b in keep:
             b.release()
+
+
+def render_frame_stream(ctx, p, rays_fill=None):
+    """render_frame's enqueue stream for every Assign04 / Assign07 job, the both-models one included -- initTrace, molTrace (a molecule, or
+    p.both), meshTrace (a mesh) -- with nothing between the enqueues, as the pages issue a frame (A07 code.js:659-661).  rays_fill: a byte the ray
+    buffer is filled with first.  Returns (pixels [H*W,4] uint8, rays bytes)."""
+    pre = {4: "A04:", 7: "A07:"}[p.assign]
+    w, h = p.width, p.height
+    l = get_local_ws(2, 64)
+    gws = [-(-w // l[0]) * l[0], -(-h // l[1]) * l[1]]
+    keep, ks = [], []
+    up = lambda a: keep.append(ctx.buffer_from(a)) or keep[-1]
+    try:
+        pixels = ctx.buffer(w * h * 4, mirt.MEM_WRITE_ONLY)
+        keep.append(pixels)
+        rays = ctx.buffer(w * h * RAY_BYTES)
+        keep.append(rays)
+        if rays_fill is not None:
+            rays.write(np.full(w * h * RAY_BYTES, rays_fill, np.uint8))
+        it = ctx.kernel(pre + "initTrace").set_args(pixels, p.cam, rays)
+        ks.append(it)
+        if p.assign == 7:
+            it.set_arg(3, p.bounds)
+        stages = []
+        mol = dict(s_size=p.s_size, atoms=p.atoms, mindex=p.mindex, mcolor=p.mcolor, slab_size=p.slab_size) if p.mol else p.both
+        if mol:
+            stages.append(ctx.kernel(pre + "molTrace").set_args(pixels, p.cam, rays, _u32(mol["s_size"]), up(mol["atoms"]), up(mol["mindex"]), up(mol["mcolor"]),
+                                                                 p.bounds, _u32(p.n_slabs), up(mol["slab_size"])))
+        if not p.mol:
+            mt = ctx.kernel(pre + "meshTrace").set_args(pixels, p.cam, rays, _u32(p.t_size), up(p.pos), up(p.normal), up(p.mindex), up(p.mcolor))
+            if p.assign == 7:
+                mt.set_arg(8, p.bounds).set_arg(9, _u32(p.n_slabs)).set_arg(10, up(p.slab_size))
+            stages.append(mt)
+        ks += stages
+        it.enqueue(gws, l)
+        for k in stages:
+            k.enqueue(gws, l)
+        ctx.finish()
+        return pixels.read(np.uint8).reshape(-1, 4), rays.read(np.uint8)
+    finally:
+        for k in ks:
+            k.release()
+        for b in keep:
+            b.release()
+
+
+class FrameOneLaunch:
+    """An Assign04 / Assign07 frame job uploaded once, rendered by mirt_render_frame: one launch per frame, no ray buffer unless keep_rays."""
+
+    def __init__(self, ctx, p, keep_rays=False):
+        self.ctx, self.p, self.bufs = ctx, p, []
+        up = lambda a: self.bufs.append(ctx.buffer_from(a)) or self.bufs[-1]
+        self.pixels = ctx.buffer(p.width * p.height * 4, mirt.MEM_WRITE_ONLY)
+        self.rays = ctx.buffer(p.width * p.height * RAY_BYTES) if keep_rays else None
+        self.bufs += [b for b in (self.pixels, self.rays) if b]
+        self.mesh = self.mol = None
+        mol = dict(s_size=p.s_size, atoms=p.atoms, mindex=p.mindex, mcolor=p.mcolor, slab_size=p.slab_size) if p.mol else p.both
+        if mol:
+            self.mol = dict(s_size=mol["s_size"], atoms=up(mol["atoms"]), mindex=up(mol["mindex"]), mcolor=up(mol["mcolor"]), slab_size=up(mol["slab_size"]))
+        if not p.mol:
+            self.mesh = dict(t_size=p.t_size, pos=up(p.pos), normal=up(p.normal), mindex=up(p.mindex), mcolor=up(p.mcolor))
+            if p.assign == 7:
+                self.mesh["slab_size"] = up(p.slab_size)
+
+    def render(self):
+        p = self.p
+        self.ctx.render_frame(p.assign, p.width, p.height, p.cam, self.pixels, bounds=getattr(p, "bounds", None), n_slabs=getattr(p, "n_slabs", 0),
+                              mesh=self.mesh, mol=self.mol, rays=self.rays)
+
+    def release(self):
+        for b in self.bufs:
+            b.release()
+        self.bufs = []
+
+
+def render_frame_one_launch(ctx, p, keep_rays=False, timing=None):
+    """The frame of render_frame (Assign04 / Assign07, the both-models job included) through mirt_render_frame: initTrace and the trace kernel(s) in
+    one launch.  Returns (pixels [H*W,4] uint8, rays bytes or None); keep_rays: the kernel also stores every finished ray.
+    timing: a dict that receives "frame_ms", the HIP-event time of the one launch."""
+    f = FrameOneLaunch(ctx, p, keep_rays)
+    try:
+        if timing is None:
+            f.render()
+        else:
+            ctx.finish()
+            ctx.timer_start()
+            f.render()
+            timing["frame_ms"] = ctx.timer_stop_ms()
+        return f.pixels.read(np.uint8).reshape(-1, 4), (f.rays.read(np.uint8) if keep_rays else None)
+    finally:
+        f.release()
 
 
 def frame_resized(d, w, h):

@@ -264,6 +264,54 @@ MIRT_API int mirt_ctx_set_exact_only(mirt_ctx* ctx, int on);
 MIRT_API int mirt_ctx_set_fusion(mirt_ctx* ctx, int level);
 MIRT_API int mirt_ctx_fused_passes(mirt_ctx* ctx, uint64_t* count);
 
+/* ---- extension: a whole Assign04 / Assign07 frame in one launch ------------------------------------
+ * One call == compute() / computeTri() / computeBoth() of those pages minus the read-back (A04 code.js:553-577, A07 code.js:571-661): initTrace and
+ * the trace kernel(s) on one thread per pixel, the primary ray in registers.  Kernel by kernel a frame is two or three launches with a 48-byte ray per
+ * pixel written and read back between them; here nothing per ray touches memory unless `rays` is given.  `pixel` ends bit-identical to enqueueing the
+ * kernels one by one: the colour where a stage hits, (0, 0, 0, 255) elsewhere.
+ * Stages.  assign 4: the brute-force mesh (t_pos .. t_mcolor, t_size triangles).  assign 7: the molecule (s_atoms, s_slab_size) and / or the mesh
+ * (t_pos, t_normal, t_slab_size; A07's kernels bind t_mindex / t_mcolor / s_mindex / s_mcolor but never read them: they may be NULL), both in grids of
+ * n_slabs cells per axis over `bounds`; with both set the mesh is traced after the molecule, from the maxt the molecule left, as computeBoth's
+ * second kernel does (the page gives each model's kernel the model's own box; here both grids span the one `bounds`).  A stage is asked for by its first buffer (t_pos, s_atoms) being non-NULL.
+ * `rays`, optional: the finished ray per pixel (o, d, mint, final maxt: the 40 bytes of the 48 the kernels write), as the launches leave it.
+ * Checks are those of mirt_enqueue on the same kernels: MIRT_E_RANGE for a buffer smaller than the launch touches (pixel, rays, a cell table shorter
+ * than n_slabs^3 + 1, primitive arrays shorter than the table says), MIRT_E_DATA for a table that fails validation; MIRT_E_ARG for assign other than
+ * 4 or 7, a molecule with assign 4, no stage, or a camera block whose image size is not width x height.  Nothing is written when a check fails.
+ * Inside mirt_capture_begin / mirt_capture_end under the rule of mirt_render_pass: run it once before recording it. */
+typedef struct mirt_frame_desc {
+    uint32_t struct_size;           /* sizeof(mirt_frame_desc)                                      */
+    uint32_t assign;                /* 4 or 7                                                       */
+    uint32_t width, height;
+    float cam[16];                  /* Camera.toFloat32Array (A04 code.js / A07 code.js:73-81)      */
+    float bounds[8];                /* assign 7: (min,1,max,1) of the model(s); ignored for 4       */
+    uint32_t t_size;                /* mesh: triangles (assign 4), informative for assign 7         */
+    uint32_t s_size;                /* molecule: atoms, informative                                 */
+    mirt_buf *t_pos, *t_normal, *t_mindex, *t_mcolor;   /* mesh, or t_pos NULL                      */
+    mirt_buf *s_atoms, *s_mindex, *s_mcolor;            /* molecule, or s_atoms NULL                */
+    uint32_t n_slabs;               /* assign 7: cells per axis of both grids                       */
+    uint32_t reserved;
+    mirt_buf* t_slab_size;          /* assign 7 mesh: uint[n_slabs^3 + 1]                           */
+    mirt_buf* s_slab_size;          /* assign 7 molecule: uint[n_slabs^3 + 1]                       */
+    mirt_buf* pixel;                /* uchar4 per pixel                                             */
+    mirt_buf* rays;                 /* optional: 48 bytes per pixel                                 */
+} mirt_frame_desc;
+MIRT_API int mirt_render_frame(mirt_ctx* ctx, const mirt_frame_desc* desc);
+
+/* Command-stream fusion of the frame dialects: the Assign04 / Assign07 pages' own enqueue stream at the one-launch frame's speed, with no change to
+ * the host.  A separate switch from mirt_ctx_set_fusion (whose levels keep their meaning), off by default; MIRT_FRAME_FUSION=1 in the environment
+ * turns it on for every new context.  With it on an "A04:" / "A07:" initTrace enqueue is held back, and so are the enqueues that follow it (at most three);
+ * when the held stream IS a frame as the pages issue it -- initTrace then meshTrace (computeTri), initTrace then molTrace (compute), or initTrace,
+ * molTrace, meshTrace (computeBoth), every stage over the same pixels, camera block, rays and box, with the initTrace's global size, which covers the
+ * image -- it runs as ONE launch of mirt_render_frame.  Anything else is launched enqueue by enqueue, in order, exactly as with the switch off.  The
+ * held stream runs at the first command that would flush a held Assign10 pass (see mirt_ctx_set_fusion: buffer read / write / release, another
+ * enqueue that does not continue the frame, capture, timers, destroy ...) and also at mirt_finish.
+ *   - pixels after the frame are bit-identical to the switch being off; the Ray buffer is NOT written by a fused frame -- it keeps its previous
+ *     contents.  The pages never read it (they cannot: they do not know its layout beyond sizeof).
+ *   - errors of a held enqueue are reported by the call that flushes it, as for a held pass.
+ * mirt_ctx_fused_frames: how many frames of this context ran fused. */
+MIRT_API int mirt_ctx_set_frame_fusion(mirt_ctx* ctx, int on);
+MIRT_API int mirt_ctx_fused_frames(mirt_ctx* ctx, uint64_t* count);
+
 /* seeds[i] = 1 + (mix32((first_ray + i) ^ 0x9E3779B9 ^ seed_base) mod 2147483646): the
  * reproducible stand-in for the host's Math.random() seeding (A10 code.js:1140-1146). */
 MIRT_API int mirt_seed_fill(mirt_ctx* ctx, mirt_buf* seeds, uint64_t first_ray, uint64_t count, uint32_t seed_base);
