@@ -301,11 +301,11 @@ bool read_grid(napi_env env, napi_value o, mirt_grid* g) {
 //                  spheres?,triangles?,meshes[],lights[{shadow,scene,light}],material,seeds,acu,pixel?,radiance?})
 // desc.nPasses: that many passes in one call (mirt_render_passes; desc.firstPass -> MIRT_PASSES_FRESH, desc.everyPass -> MIRT_PASSES_EVERY_FRAME: pixel /
 // radiance hold nPasses frames; webcl.js checks the count's range and the frame buffers' sizes)
-napi_value RenderPass(napi_env env, napi_callback_info info) {
-    ARGS(2);
+// renderGuides(ctx, desc, normalHits, albedoDepth): the same descriptor (seeds, acu, pixel, radiance, lights are not needed), two float4-per-pixel
+// buffers of the tile, either may be null (mirt_render_guides)
+static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, bool guides, napi_value nhv, napi_value adv) {
     void* c;
-    if (!get_ext(env, argv[0], &c)) return throw_type(env, "renderPass(ctx, desc)");
-    napi_value d = argv[1];
+    if (!get_ext(env, ctxv, &c)) return throw_type(env, guides ? "renderGuides(ctx, desc, normalHits, albedoDepth)" : "renderPass(ctx, desc)");
     mirt_pass_desc p;
     memset(&p, 0, sizeof p);
     p.struct_size = sizeof p;
@@ -352,6 +352,14 @@ napi_value RenderPass(napi_env env, napi_callback_info info) {
     p.acu = prop_buf(env, d, "acu");
     p.pixel = prop_buf(env, d, "pixel");
     p.radiance = prop_buf(env, d, "radiance");
+    if (guides) {
+        void *nh = nullptr, *ad = nullptr;
+        get_ext(env, nhv, &nh);
+        get_ext(env, adv, &ad);
+        const int rc = mirt_render_guides((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad);
+        if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+        return undef(env);
+    }
     bool first = false;   // desc.firstPass: initAcu folded into the pass (mirt_render_first_pass)
     { napi_value v; bool has = false; if (napi_has_named_property(env, d, "firstPass", &has) == napi_ok && has && napi_get_named_property(env, d, "firstPass", &v) == napi_ok) napi_get_value_bool(env, v, &first); }
     bool every = false;
@@ -363,6 +371,14 @@ napi_value RenderPass(napi_env env, napi_callback_info info) {
     else rc = first ? mirt_render_first_pass((mirt_ctx*)c, &p) : mirt_render_pass((mirt_ctx*)c, &p);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);
+}
+napi_value RenderPass(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    return render_call(env, argv[0], argv[1], false, nullptr, nullptr);
+}
+napi_value RenderGuides(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    return render_call(env, argv[0], argv[1], true, argv[2], argv[3]);
 }
 
 // renderFrame(ctx, {assign,width,height,cam,bounds?,nSlabs?, tSize?,tPos?,tNormal?,tMindex?,tMcolor?,tSlabSize?, sSize?,sAtoms?,sMindex?,sMcolor?,sSlabSize?,
@@ -653,7 +669,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

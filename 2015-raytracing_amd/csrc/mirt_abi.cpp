@@ -68,6 +68,8 @@ struct mirt_ctx {
     size_t defer_bytes = 0;
     uint32_t defer_words = 0;     // mask words the last mirt_render_pass used (0: it ran the exact kernel only)
     uint32_t defer_unit = 1;      // samples per mask bit: 1, or 256 when that pass resolved its pixels itself (a bit per block)
+    void* guide_mask = nullptr;   // mirt_render_guides, optimistic pair: a bit per pixel of the tile (its own allocation: the pass's mask and what
+    size_t guide_mask_bytes = 0;  // mirt_pass_deferred reports of it stay as the last pass left them)
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     float res_m_override = NAN;        // try_fuse_pass -> render_pass_impl: the tone factor of the recorded copyToPixel, as the host passed it
@@ -378,6 +380,7 @@ static int destroy_ctx(mirt_ctx* ctx) {
     while (!ctx->bufs.empty()) free_buf(*ctx->bufs.begin(), true);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->defer) (void)hipFree(ctx->defer);
+    if (ctx->guide_mask) (void)hipFree(ctx->guide_mask);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1267,43 +1270,38 @@ static pt::PassRequest pass_request(const mirt_ctx* ctx, const mirt_pass_desc* d
     return r;
 }
 
-static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o) {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_pass: unknown context");
-    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: descriptor size mismatch");
-    if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: empty image");
+// What mirt_render_pass and mirt_render_guides check and fill alike, in this order: the descriptor, the k x k ray count, the tile, then the camera,
+// bounds, primitive sets (validated and prepared: fill_grid) and material of `A`.  guides: the lights and pass_index are not looked at.
+static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bool guides, pt::FusedArgs& A) {
+    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
+    if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "%s: empty image", fn);
     {   // the host only ever makes k x k rays per pixel (A10 code.js:540); initTrace's k x k loops leave the tail of any other count
         // unwritten (code.cl:479-512), i.e. those rays would be whatever the buffer held -- there is nothing to reproduce
         const uint32_t k = (uint32_t)std::sqrt((double)d->rays_per_pixel);
         const uint32_t kk = (k + 1) * (k + 1) == d->rays_per_pixel ? k + 1 : k;
         if (kk * kk != d->rays_per_pixel)
-            return fail(ctx, MIRT_E_ARG, "mirt_render_pass: rays_per_pixel %u is not a square (the lens grid is k x k, A10 code.js:540)", d->rays_per_pixel);
+            return fail(ctx, MIRT_E_ARG, "%s: rays_per_pixel %u is not a square (the lens grid is k x k, A10 code.js:540)", fn, d->rays_per_pixel);
     }
-    if (d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: %u lights > %d (enqueue the kernels one by one instead)", d->n_lights, MIRT_MAX_LIGHTS);
-    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: %u meshes > %d (enqueue the kernels one by one instead)", d->n_meshes, MIRT_MAX_MESHES);
-    if ((d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: null light/mesh array");
-    if (!d->pass_index) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: pass_index is 1-based");
+    if (!guides && d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
+    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
+    if ((!guides && d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
+    if (!guides && !d->pass_index) return fail(ctx, MIRT_E_ARG, "%s: pass_index is 1-based", fn);
     const uint32_t cols = f2u_host(d->cam[14]), rows = f2u_host(d->cam[15]);
-    if (cols != d->width || rows != d->height) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: camera says %ux%u, descriptor %ux%u", cols, rows, d->width, d->height);
+    if (cols != d->width || rows != d->height) return fail(ctx, MIRT_E_ARG, "%s: camera says %ux%u, descriptor %ux%u", fn, cols, rows, d->width, d->height);
     const uint32_t nrows = d->nrows ? d->nrows : d->height;
-    if (d->row0 >= d->height || nrows > d->height - d->row0) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: row tile [%u,+%u) outside the image", d->row0, nrows);
+    if (d->row0 >= d->height || nrows > d->height - d->row0) return fail(ctx, MIRT_E_ARG, "%s: row tile [%u,+%u) outside the image", fn, d->row0, nrows);
     const uint64_t npix = (uint64_t)nrows * d->width;
     const uint64_t nrays = npix * d->rays_per_pixel;
-    if (nrays > 0xFFFFFF00ull) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: %llu rays in one tile (the kernels index a tile's rays with 32 bits); split the rows over more launches", (unsigned long long)nrays);
+    if (nrays > 0xFFFFFF00ull) return fail(ctx, MIRT_E_ARG, "%s: %llu rays in one tile (the kernels index a tile's rays with 32 bits); split the rows over more launches", fn, (unsigned long long)nrays);
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
-    pt::FusedArgs A;
     memset(&A, 0, sizeof A);
     memcpy(A.cam, d->cam, sizeof A.cam);
     memcpy(A.bound, d->scene_bounds, sizeof A.bound);
     A.focal_length = d->focal_length; A.lens_rad = d->lens_rad;
     A.width = d->width; A.height = d->height; A.rpp = d->rays_per_pixel;
     A.row0 = d->row0; A.nrows = nrows; A.bounces = d->bounces;
-    A.n_lights = d->n_lights;
-    A.fresh = o.fresh ? 1u : 0u;
-    A.passes = o.passes;
-    // the frame after the last pass: 1 / (rpp * passes so far), A10 code.js:1412 -- or the recorded copyToPixel's own factor, which try_fuse_pass hands over (not a NaN)
-    const float res_m = o.passes == 1u && ctx->res_m_override == ctx->res_m_override ? ctx->res_m_override
-                                                                                     : (float)(1.0 / ((double)d->rays_per_pixel * ((double)d->pass_index + (double)(o.passes - 1u))));
+    A.n_lights = guides ? 0u : d->n_lights;
     int rc;
     if (d->spheres && (rc = fill_grid(ctx, "spheres", d->spheres, false, true, &A.sets[A.n_sets++]))) return rc;
     if (d->triangles && (rc = fill_grid(ctx, "triangles", d->triangles, true, true, &A.sets[A.n_sets++]))) return rc;
@@ -1319,10 +1317,10 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
         for (uint32_t i = 0; i < ng; ++i)
             for (uint32_t j = i + 1; j < ng; ++j)
                 if (gs[i]->prims == gs[j]->prims && gs[i]->cell_offsets->off_last != gs[j]->cell_offsets->off_last)
-                    return fail(ctx, MIRT_E_ARG, "mirt_render_pass: two triangle sets share a position buffer but hold %u and %u slots (one prepared copy per buffer: "
-                                                 "give each set its own buffer)", gs[i]->cell_offsets->off_last, gs[j]->cell_offsets->off_last);
+                    return fail(ctx, MIRT_E_ARG, "%s: two triangle sets share a position buffer but hold %u and %u slots (one prepared copy per buffer: "
+                                                 "give each set its own buffer)", fn, gs[i]->cell_offsets->off_last, gs[j]->cell_offsets->off_last);
     }
-    for (uint32_t l = 0; l < d->n_lights; ++l) {
+    for (uint32_t l = 0; l < A.n_lights; ++l) {
         memcpy(A.lights[l].shadow, d->lights[l].shadow, 64);
         memcpy(A.lights[l].scene, d->lights[l].scene, 64);
         memcpy(A.lights[l].light, d->lights[l].light, 64);
@@ -1330,6 +1328,22 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
     if ((rc = need(ctx, "material", d->material, 16))) return rc;
     A.material = d->material->ptr;
     A.nmat = (uint32_t)(d->material->bytes / 16);
+    return MIRT_OK;
+}
+
+static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o) {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_pass: unknown context");
+    pt::FusedArgs A;
+    int rc;
+    if ((rc = pass_setup(ctx, "mirt_render_pass", d, false, A))) return rc;
+    const uint32_t nrows = A.nrows;
+    const uint64_t npix = (uint64_t)nrows * d->width;
+    const uint64_t nrays = npix * d->rays_per_pixel;
+    A.fresh = o.fresh ? 1u : 0u;
+    A.passes = o.passes;
+    // the frame after the last pass: 1 / (rpp * passes so far), A10 code.js:1412 -- or the recorded copyToPixel's own factor, which try_fuse_pass hands over (not a NaN)
+    const float res_m = o.passes == 1u && ctx->res_m_override == ctx->res_m_override ? ctx->res_m_override
+                                                                                     : (float)(1.0 / ((double)d->rays_per_pixel * ((double)d->pass_index + (double)(o.passes - 1u))));
     if ((rc = need(ctx, "seeds", d->seeds, nrays * 4))) return rc;
     // what is launched, worked out once (pt_pass_plan.hpp): whether the pass resolves its own pixels -- then, and only then, `acu` is optional --
     // its segments, the mask and the scratch buffer
@@ -1474,6 +1488,45 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
     }
     return MIRT_OK;
 } MIRT_CATCH("mirt_render_passes", return MIRT_E_DEVICE)
+
+// First-hit guide buffers of the tile (pt_kernels_guides.hip): the descriptor's geometry through the checks of mirt_render_pass, then one launch
+// -- or the optimistic / exact pair -- of one lane per pixel.  Nothing but the two outputs is written.
+int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_guides: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_render_guides");
+    if (!normal_hits && !albedo_depth) return fail(ctx, MIRT_E_ARG, "mirt_render_guides: normal_hits and albedo_depth are both NULL (either may be, not both)");
+    if (d && d->struct_size == sizeof(mirt_pass_desc) && d->rays_per_pixel == 1u)
+        return fail(ctx, MIRT_E_ARG, "mirt_render_guides: rays_per_pixel == 1 draws its lens sample from seeds[col] (A10 code.cl:429), so its guides would change "
+                                     "with the seeds and from pass to pass; the guides are defined for the un-jittered k x k lens grid, rays_per_pixel >= 4");
+    pt::FusedArgs A;
+    int rc;
+    if ((rc = pass_setup(ctx, "mirt_render_guides", d, true, A))) return rc;
+    const uint64_t npix = (uint64_t)A.nrows * A.width;
+    if (normal_hits && (rc = need(ctx, "normal_hits", normal_hits, npix * 16))) return rc;
+    if (albedo_depth && (rc = need(ctx, "albedo_depth", albedo_depth, npix * 16))) return rc;
+    void* const nh = normal_hits ? normal_hits->ptr : nullptr;
+    void* const ad = albedo_depth ? albedo_depth->ptr : nullptr;
+    bool optimistic = pt::fused_fast_available() && !ctx->force_exact;
+    for (uint32_t i = 0; i < A.n_sets; ++i) optimistic = optimistic && A.sets[i].fast_ok != 0;
+    if (optimistic) {
+        const size_t need_bytes = (size_t)((npix + 31u) / 32u) * 4u;
+        if (ctx->guide_mask_bytes < need_bytes) {
+            if (ctx->guide_mask) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->guide_mask)); ctx->guide_mask = nullptr; ctx->guide_mask_bytes = 0; }
+            HIPCHK(ctx, hipMalloc(&ctx->guide_mask, need_bytes));
+            ctx->guide_mask_bytes = need_bytes;
+        }
+        HIPCHK(ctx, hipMemsetAsync(ctx->guide_mask, 0, need_bytes, ctx->stream));
+        pt::launch_guides(ctx->stream, A, true, nh, ad, (uint32_t*)ctx->guide_mask, nullptr);
+        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, (const uint32_t*)ctx->guide_mask);
+    } else {
+        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, nullptr);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (normal_hits) normal_hits->version++;
+    if (albedo_depth) albedo_depth->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_render_guides", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_fusion(mirt_ctx* ctx, int level) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_fusion: unknown context");

@@ -24,23 +24,11 @@
 // Moeller-Trumbore (A10 code.cl:252-256), computed once with the same fp32 operations, so
 // every value that reaches a ray-dependent operation has the bits it has in the reference.
 #include <stdlib.h>
-#include "pt_trace_coop.hpp"
+#include "pt_closest.hpp"
 
 #ifndef PT_SKIP_DARK_SHADOWS
 #define PT_SKIP_DARK_SHADOWS 1   // grid kernels: a shadow ray whose vertex the light cannot light is not traced (direct_all)
 #endif
-#ifndef PT_AABB_UNSIGNED_ZERO
-#define PT_AABB_UNSIGNED_ZERO 1   // single-cell sets only (their tmin / tmax / exits are compare-only): see slab1_fast
-#endif
-
-#ifndef PT_LANE_LISTS
-#define PT_LANE_LISTS 1          // optimistic kernel: single-cell triangle sets through per-lane candidate lists (pt_trace.hpp trace_cell1, LANES)
-#endif
-#ifndef PT_LANE_LISTS_GRIDS
-#define PT_LANE_LISTS_GRIDS 1    // ... in the grid kernels as well (cornell_teapot3 35.8 -> 33.4 ms, cornell_teapot 24.0 -> 22.7, own_gems 12.4 -> 12.8)
-#endif
-#define PT_LANE_LISTS_FOR(FAST, GRIDS) ((FAST) && PT_LANE_LISTS && ((GRIDS) == 0 || PT_LANE_LISTS_GRIDS))
-
 namespace pt {
 
 // prepared triangle: 3 x float4 = {p0.xyz, n.x} {e1.xyz, n.y} {e2.xyz, n.z}
@@ -165,22 +153,6 @@ __global__ void __launch_bounds__(64) k_planeList(const float4* prep, uint32_t c
     }
 }
 
-// Cold per-ray state parked in LDS instead of registers: the accumulator (touched once per shading event) and the
-// path attenuation (once per shade).  Seven dwords per lane = 7 KB per 256-thread block, [word][lane] so a wave's
-// access is one conflict-free row.  It buys the register allocator seven VGPRs on a kernel that is held at
-// 6 waves/SIMD by an 80-register budget.
-#ifndef PT_PARK_LDS
-#define PT_PARK_LDS 1
-#endif
-#ifndef PT_PARK_PN
-#define PT_PARK_PN 0   // A/B: parking p and n as well is slower (199.9 vs 196.2 ms): the reloads sit on the critical path
-#endif
-#ifndef PT_PARK_PN_GRIDS
-#define PT_PARK_PN_GRIDS 1   // the same for the grid kernels only: their walks hold far more state (38 -> 22 spilled VGPRs; cornell_teapot3 859 -> 880
-                             // Msamples/s, own_gems 2399 -> 2541)
-#endif
-#define PT_PARK_PN_FOR(GRIDS) (PT_PARK_PN || (PT_PARK_PN_GRIDS && (GRIDS) != 0))
-#define PT_PARK_WORDS(GRIDS) (PT_PARK_PN_FOR(GRIDS) ? 13 : 7)
 // STRIDE: words between the rows of one lane's record ([word][lane] rows of 256 lanes in k_fusedPass).  ATTE_LDS: the attenuation is
 // parked too (else it stays in registers and the p / n rows move up).
 template <int STRIDE, bool ATTE_LDS>
@@ -197,61 +169,6 @@ struct ParkT {
     PT_DEV void get_pn(Poi& q) const { q.p = mk3(get(kP), get(kP + 1), get(kP + 2)); q.n = mk3(get(kN), get(kN + 1), get(kN + 2)); }
 };
 typedef ParkT<256, true> Park;
-
-PT_DEV Box set_box(const GridArgs& S) { return set_box_of(S); }
-
-
-// closest hit over every set in upload order, z-buffered through ray.maxt
-// (A10 code.cl:675-800, 802-935, 937-1070; order A10 code.js:1809-1813)
-template <bool FAST, int GRIDS, class PARK>
-PT_DEV void closest_all(const FusedArgs& A, Ray& ray, Poi& poi, const PARK& park, bool& defer) {
-    if (FAST && !(ray.mint == ray.maxt)) defer = defer || !ray_guard(ray);   // a dead ray divides nothing
-    const RayRcp rr = ray_rcp<FAST>(ray);
-    for (uint32_t s = 0; s < A.n_sets; ++s) {
-        const GridArgs& S = A.sets[s];
-        const bool live = !(ray.mint == ray.maxt);
-        Hit ch;
-        ch.idx = UINT32_MAX;
-        if (!GRIDS || S.n == 1u) {
-            if (live) {
-                pt_count(PC_BOX_TESTS); pt_count(PC_BOX_LANES, true);
-                const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(ray, rr, set_box(S));
-                if (bh.v) ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, false, TRI_A10, FAST>(ray, rr, bh, S) : trace_cell1<TRIANGLES, false, TRI_A10, FAST, false, PT_LANE_LISTS_FOR(FAST, GRIDS)>(ray, rr, bh, S);
-            }
-        } else if (S.kind == KIND_TRIANGLES) {   // every lane of the wave enters: the tests of the walk are shared (pt_trace_coop.hpp)
-            BoxHit bh = {};
-            if (live) bh = inter_aabb_t<FAST, true>(ray, rr, set_box(S));
-            ch = trace_dda_coop<COOP_CLOSEST, FAST, GRIDS == 1>(live && bh.v, ray, rr, bh, S, defer);
-        } else if (live) {
-            const BoxHit bh = inter_aabb_t<FAST, true>(ray, rr, set_box(S));
-            if (bh.v) ch = trace_dda<SPHERES, false, TRI_A10, FAST, GRIDS == 1>(ray, bh, S, defer);
-        }
-        if (ch.idx == UINT32_MAX) continue;
-        ray.maxt = ch.t;
-        poi.p = fma3(ch.t, ray.d, ray.o);   // getPoint, code.cl:87
-        if (S.kind == KIND_SPHERES) {
-            poi.n = norm3(sub3(poi.p, ld3(((const float4*)S.prims)[ch.idx])));
-            poi.matId = (int32_t)((const uint32_t*)S.matid)[ch.idx];
-        } else {
-            float w = 1.0f - ch.beta - ch.gamma;  // code.cl:409-411
-            if (PT_LANE_LISTS_FOR(FAST, GRIDS) && S.n == 1u && S.lds_off != kNoLds) {
-                // a set staged for the candidate loops carries its vertex normals and material ids in LDS too: three ds_read_b128 and a
-                // ds_read_b32 instead of four dependent global loads between the hit and the bounce
-                const uint32_t base = S.lds_off + 12u * S.nslots;
-                const float4* nn = (const float4*)&pt_lds_dyn[base + __umul24(ch.idx, 12u)];
-                poi.n = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
-                poi.matId = (int32_t)pt_lds_dyn[base + 12u * S.nslots + ch.idx];
-            } else {
-                const float4* nn = (const float4*)S.normals + 3u * (size_t)ch.idx;
-                poi.n = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
-                poi.matId = (int32_t)(S.matid ? ((const uint32_t*)S.matid)[ch.idx] : S.mesh_matid);
-            }
-        }
-#if PT_PARK_LDS
-        if (PT_PARK_PN_FOR(GRIDS)) park.put_pn(poi);
-#endif
-    }
-}
 
 // per light: shadow ray, any-hit over every set, shade (A10 code.js:1817-1826; code.cl:631-673,
 // 1073-1321, 1323-1364)
@@ -334,105 +251,6 @@ PT_DEV void direct_all(const FusedArgs& A, Poi& poi, int32_t& seed, float4& acc,
         acc.x += c.x; acc.y += c.y; acc.z += c.z; acc.w += 1.0f;
 #endif
     }
-}
-
-// Block prologue of the fused kernels.  GRIDS: the cell-offset tables of the grid sets (uint[n^3 + 1] each) are copied into LDS once
-// per block, before any thread leaves: launch_fused gave every set that fits a slot (GridArgs::lds_off).  The primitives of a grid stay
-// in memory.  PT_LANE_LISTS: likewise the prepared records of the single-cell triangle sets launch_fused gave a slot (the candidate
-// loops fetch them per lane by ds_read_b128).
-// The k x k lens grid's coordinates (code.cl:482-509): coord = delta / 2 and then `+= delta` per step -- sample (i, j) of every pixel needs
-// the i-th and the j-th partial sum of that chain.  One thread walks the chain once per block and leaves the k values in LDS (as
-// every lane walking it to its own i and j it cost up to 2 (k - 1) dependent additions per sample: 30 of them at 256 rays per pixel, 62 at
-// 1024).  k > kLensTab: the lanes walk.
-constexpr uint32_t kLensTab = 64;
-static_assert(kLensTab % 4u == 0u, "the static LDS ahead of pt_lds_dyn stays a multiple of 16 bytes");
-__shared__ float pt_lens_tab[kLensTab];
-__shared__ uint32_t pt_blk_defer[4];   // in-pass resolve: "a sample of this block left the guard windows" (word 0; four words keep what follows 16-byte aligned)
-// (the ray count is laundered through an SGPR: as a common subexpression of the block prologue and of every sample's set-up, the float made from it
-// stayed alive in a VGPR between the two -- the one register the 64-register build had to spill)
-PT_DEV uint32_t lens_side(const FusedArgs& A) {
-    uint32_t rpp = A.rpp;
-    asm volatile("" : "+s"(rpp));
-    return f2u_uniform(cl_sqrt((float)rpp));
-}
-
-template <bool FAST, int GRIDS>
-PT_DEV void stage_block(const FusedArgs& A) {
-    if (threadIdx.x == 0u) pt_blk_defer[0] = 0u;
-    if (A.rpp > 1u && threadIdx.x == 0u) {
-        const uint32_t side = lens_side(A);
-        if (side <= kLensTab) {
-            const float delta = 1.0f / (float)side;
-            float c = delta / 2.0f;
-            for (uint32_t k = 0; k < side; ++k) { pt_lens_tab[k] = c; c += delta; }
-        }
-    }
-    if (!(GRIDS == 1 || PT_LANE_LISTS_FOR(FAST, GRIDS))) __syncthreads();
-    if (GRIDS == 1 || PT_LANE_LISTS_FOR(FAST, GRIDS)) {
-        for (uint32_t s = 0; s < A.n_sets; ++s) {
-            const GridArgs& S = A.sets[s];
-            if (S.lds_off == kNoLds) continue;
-            if (S.n == 1u) {
-                if (!PT_LANE_LISTS_FOR(FAST, GRIDS)) continue;
-                // [records 12 words each][vertex normals 12 words each][material ids, one word each: a mesh's single id repeated]
-                const uint32_t words = S.nslots * 12u;
-                const uint32_t* src = (const uint32_t*)S.prims;
-                const uint32_t* nrm = (const uint32_t*)S.normals;
-                const uint32_t* mid = (const uint32_t*)S.matid;
-                for (uint32_t k = threadIdx.x; k < words; k += 256u) { pt_lds_dyn[S.lds_off + k] = src[k]; pt_lds_dyn[S.lds_off + words + k] = nrm[k]; }
-                for (uint32_t k = threadIdx.x; k < S.nslots; k += 256u) pt_lds_dyn[S.lds_off + 2u * words + k] = mid ? mid[k] : S.mesh_matid;
-            } else if (GRIDS == 1) {
-                const uint32_t words = S.n * S.n * S.n + 1u;
-                const uint32_t* src = (const uint32_t*)S.off;
-                for (uint32_t k = threadIdx.x; k < words; k += 256u) pt_lds_dyn[S.lds_off + k] = src[k];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// initTrace (code.cl:458-543) for one ray id of the tile: thin-lens ray through its pixel, clipped to the scene box
-// (tile-local ray ids fit 32 bits: mirt_render_pass refuses a tile of more than 2^32 - 256 rays)
-PT_DEV Ray primary_ray(const FusedArgs& A, uint32_t lid) {
-    // (the host makes rays_per_pixel k x k; when k is a power of two -- 1, 4, 16, 64, 256, 1024 -- the pixel and the sample are a shift and a mask)
-    const bool pow2 = (A.rpp & (A.rpp - 1u)) == 0u;   // wave-uniform
-    const uint32_t lpix = pow2 ? lid >> (uint32_t)__builtin_ctz(A.rpp) : lid / A.rpp;
-    const uint32_t smp = pow2 ? lid & (A.rpp - 1u) : lid - lpix * A.rpp;
-    const uint32_t lrow = lpix / A.width;
-    const uint32_t col = lpix - lrow * A.width;
-    const uint32_t row = A.row0 + lrow;
-    Cam cam;
-    cam.eye = ld3(A.cam); cam.U = ld3(A.cam + 3); cam.V = ld3(A.cam + 6); cam.W = ld3(A.cam + 9);
-    cam.width = A.cam[12]; cam.height = A.cam[13];
-    cam.cols = f2u_uniform(A.cam[14]); cam.rows = f2u_uniform(A.cam[15]);
-    Box bound;
-    bound.lo = mk3(A.bound[0], A.bound[1], A.bound[2]);
-    bound.hi = mk3(A.bound[4], A.bound[5], A.bound[6]);
-    const f3 fp = focal_point(cam, (float)col, (float)row, A.focal_length);
-    float cx, cy;
-    if (A.rpp > 1) {
-        // un-jittered k x k lens grid; coordinates accumulate by repeated addition in the
-        // reference (coord += delta), so they are rebuilt the same way
-        const uint32_t side = lens_side(A);
-        const uint32_t i = smp / side, j = smp - i * side;
-        if (side <= kLensTab) {   // the chain's partial sums, left in LDS by stage_block
-            cy = pt_lens_tab[i];
-            cx = pt_lens_tab[j];
-        } else {
-            const float delta = 1.0f / (float)side;
-            cy = delta / 2.0f;
-            for (uint32_t k = 0; k < i; ++k) cy += delta;
-            cx = delta / 2.0f;
-            for (uint32_t k = 0; k < j; ++k) cx += delta;
-        }
-    } else {
-        float2 c = ((const float2*)A.uv)[lpix];
-        cx = c.x;
-        cy = c.y;
-    }
-    Ray ray = thin_lens_ray(cam, fp, A.lens_rad, cx, cy);
-    clip_to(ray, bound);
-    return ray;
 }
 
 // copyToPixel inside the pass (A10 code.cl:1366-1386) for block `blk` of the launch: `rows` = the block's parked accumulators, [channel][lane]
@@ -558,9 +376,6 @@ PT_DEV void resolve_frame(const FusedArgs& A, const float* rows, uint32_t blk, u
 // 64 packed rays, three wait at a barrier).  It cuts VALU instructions 4x on those walks and was 30 % SLOWER (cornell_teapot3
 // 1080p x16: 72.2 -> 93.8 ms): the waiting waves keep their registers, so each SIMD is left with too few runnable waves.
 // What pays instead is sharing the TESTS inside each wave, no barrier, no idle wave: pt_trace_coop.hpp (65.4 -> 40.2 ms).
-#ifndef PT_STAGE_TABLES
-#define PT_STAGE_TABLES 1
-#endif
 #ifndef PT_FUSED_WAVES_GRIDS
 #define PT_FUSED_WAVES_GRIDS 6   // the grid walk is latency-bound: it wants waves.  Round 3, cornell_teapot3 1080p x 16: 4 waves per SIMD 38.2 ms, 5 (96 VGPRs, no
                                 // scratch) 31.6, 6 (80 VGPRs, 18 spilled around the walks, 64 B of scratch) 29.3 -- 6 needs a block's LDS within 26 880 B (six
@@ -841,40 +656,14 @@ static void launch_pass(const dim3& grid, size_t lds, hipStream_t s, const Fused
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     const uint64_t n = redo_mask ? redo_words : (uint64_t)a.nrows * a.width * a.rpp;
     if (!n) return;
-    bool grids = false;
-    for (uint32_t i = 0; i < a.n_sets; ++i) grids = grids || a.sets[i].n != 1u;
-    FusedArgs b = a;   // LDS slots for the cell-offset tables: all of them or none (the walk's table reads are compiled for one address space)
-    uint64_t used = 0;
-    for (uint32_t i = 0; i < b.n_sets; ++i) {
-        b.sets[i].lds_off = kNoLds;
-        if (b.sets[i].n > 1u) { b.sets[i].lds_off = kCoopWordsPerBlock + (uint32_t)(used < kLdsOffWords ? used : kLdsOffWords); used += (uint64_t)b.sets[i].n * b.sets[i].n * b.sets[i].n + 1u; }
-    }
-    const bool staged = PT_STAGE_TABLES && used <= kLdsOffWords;
-    if (grids && !staged)
-        for (uint32_t i = 0; i < b.n_sets; ++i) b.sets[i].lds_off = kNoLds;
-    // ... then the prepared records of the single-cell triangle sets, for the candidate loops of the optimistic kernel: all that fit
-    // kLdsTriMax records, in upload order (a set without a slot runs the wave-uniform loop)
-    uint32_t tri_words = 0;
-    const uint32_t tri_base = grids ? kCoopWordsPerBlock + (staged ? (uint32_t)used : 0u) : 0u;   // multiples of 4 words: kCoopWordsPerBlock is, `used` is rounded up below
-    const uint32_t tri_base4 = (tri_base + 3u) & ~3u;
-    if (fast && PT_LANE_LISTS_FOR(true, grids ? 1 : 0)) {
-        uint32_t tris = 0;
-        for (uint32_t i = 0; i < b.n_sets; ++i) {
-            GridArgs& S = b.sets[i];
-            if (S.n != 1u || S.kind != KIND_TRIANGLES || !S.pnorm || S.nslots == 0u || tris + S.nslots > kLdsTriMax) continue;
-            S.lds_off = tri_base4 + tri_words;
-            tri_words += S.nslots * 28u;   // records, vertex normals, material ids (stage_block), rounded up to whole float4s
-            tris += S.nslots;
-        }
-
-    }
+    FusedArgs b = a;
+    const FusedLds slots = fused_lds_slots(b, fast);   // pt_closest.hpp
+    const bool grids = slots.grids, staged = slots.staged;
+    const size_t lds_tri = slots.lds_tri, lds2 = slots.lds2, lds = slots.lds;
     // redo mode: one thread per 32-sample word of the mask, or (in-pass resolve: the mask is per block) one block per 32-block word.  Otherwise a
     // block per 256 samples of the launch's segment: 256 / seg_len pixels each (FusedArgs::seg_off; without in-pass resolve seg_len is rpp)
     const dim3 grid(redo_mask && a.resolve ? (unsigned)redo_words
                   : a.resolve ? (unsigned)(((uint64_t)a.nrows * a.width * a.seg_len + 255) / 256) : (unsigned)((n + 255) / 256));
-    // dynamic LDS: the waves' exchange areas, then the staged tables (what the scene needs, not the 16 KB cap: occupancy), then the staged triangles
-    const size_t lds_tri = tri_words ? (size_t)(tri_base4 - tri_base + tri_words) * 4u : 0u;
-    const size_t lds2 = (size_t)kCoopWordsPerBlock * 4u + lds_tri, lds = (size_t)kCoopWordsPerBlock * 4u + (staged ? (size_t)used * 4u : 0u) + lds_tri;
     if (fast) {
         // LDS is handed out in 1280-byte granules, 128 of them per CU: the blocks per CU this launch can have, and the waves per SIMD worth compiling for
         static const int force_waves = [] { const char* e = getenv("MIRT_GRID_WAVES"); return e ? atoi(e) : 0; }();   // A/B and test switch

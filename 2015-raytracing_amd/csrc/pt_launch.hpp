@@ -127,6 +127,10 @@ struct FusedArgs {
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words);
 bool fused_fast_available();   // compiled with PT_EXACT_FAST_DIV
 void launch_deferCount(hipStream_t s, const uint32_t* mask, uint32_t words, uint32_t* count);
+// First-hit guide buffers (pt_kernels_guides.hip): float4 per pixel of the tile, normal_hits = (sum of the hit samples' normals, hits),
+// albedo_depth = (sum of their material colours, sum of their Ray.maxt).  One lane per pixel; the optimistic / exact pair as in launch_fused, the
+// mask one bit per pixel: (nrows * width + 31) / 32 words.  Reads the camera, bounds, sets and material of `a`; either output may be null.
+void launch_guides(hipStream_t s, const FusedArgs& a, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask, const uint32_t* redo_mask);
 // {p0,e1,e2,n} records from the host's 3 x float4 position buffer (see pt_kernels_fused.hip); `out` holds count records of 48 B,
 // behind them ceil(count / kTriGroup) float4 {centre, R'^2}: the bounding spheres of groups of consecutive records, and behind those, for
 // count <= kLdsTriMax, the candidate sweep's plane list (GridArgs::pnorm)

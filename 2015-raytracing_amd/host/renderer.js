@@ -321,13 +321,28 @@ class FusedRenderer {
       left -= k;
     }
   }
+  // first-hit guide buffers of this renderer's tile (queue.renderGuides), kept on the device for a gather: normalHits, albedoDepth, float4 per pixel
+  renderGuides() {
+    if (!this.normalHits) {
+      this.normalHits = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
+      this.albedoDepth = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
+    }
+    this.q.renderGuides(this.passDesc(), this.normalHits, this.albedoDepth);
+  }
+  readGuides() {
+    const n = new Float32Array(this.npix * 4), a = new Float32Array(this.npix * 4);
+    this.q.enqueueReadBuffer(this.normalHits, false, 0, n.byteLength, n, []);
+    this.q.enqueueReadBuffer(this.albedoDepth, false, 0, a.byteLength, a, []);
+    this.q.finish();
+    return { normalHits: n, albedoDepth: a };
+  }
   // the frames of the last executePasses(n, bounces, {everyPass: true}): { n, pixel: n RGBA8 frames, radiance: n float4 frames }, back to back
   readFrames() { return this.frames; }
   readPixels() { const o = new Uint8ClampedArray(this.npix * 4); this.q.enqueueReadBuffer(this.pixel, false, 0, o.length, o, []); this.q.finish(); return o; }
   readRadiance() { const o = new Float32Array(this.npix * 4); this.q.enqueueReadBuffer(this.radiance, false, 0, o.byteLength, o, []); this.q.finish(); return o; }
   readAcu() { const a = new Float32Array(this.nrays * 4); this.q.enqueueReadBuffer(this.acu, false, 0, a.byteLength, a, []); this.q.finish(); return a; }
   release() {
-    [this.seeds, this.acu, this.pixel, this.radiance].forEach((b) => b && b.release());
+    [this.seeds, this.acu, this.pixel, this.radiance, this.normalHits, this.albedoDepth].forEach((b) => b && b.release());
     this.dev.bufs.forEach((b) => b.release());
     this.q.release();
     if (this.ownCtx) this.ctx.release();
@@ -357,12 +372,19 @@ function renderTiled(packed, nDevices, passes, opt) {
   q0.timerStart();
   if (opt.passesInOneLaunch) live.forEach((t) => t.executePasses(passes, opt.bounces));   // one call per tile, then the gather
   else for (let p = 0; p < passes; p++) live.forEach((t) => t.executeRender(opt.bounces));
+  if (opt.guides) live.forEach((t) => t.renderGuides());   // every device its tile's guides, gathered like radiance
   const npix = packed.width * packed.height;
   const root = group.contexts[0];
   const frame = root.createBuffer(webcl.MEM_READ_WRITE, npix * 4), rad = root.createBuffer(webcl.MEM_READ_WRITE, npix * 16);
-  const dummy = tiles.map((t, i) => t || { pixel: group.contexts[i].createBuffer(webcl.MEM_READ_WRITE, 16), radiance: group.contexts[i].createBuffer(webcl.MEM_READ_WRITE, 16), npix: 0 });
+  const mk16 = (i) => group.contexts[i].createBuffer(webcl.MEM_READ_WRITE, 16);
+  const dummy = tiles.map((t, i) => t || { pixel: mk16(i), radiance: mk16(i), normalHits: opt.guides ? mk16(i) : null, albedoDepth: opt.guides ? mk16(i) : null, npix: 0 });
   group.gather(dummy.map((t) => t.pixel), dummy.map((t) => t.npix * 4), frame, 0, opt.forceRccl);
   group.gather(dummy.map((t) => t.radiance), dummy.map((t) => t.npix * 16), rad, 0, opt.forceRccl);
+  const gnh = opt.guides ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 16) : null, gad = opt.guides ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 16) : null;
+  if (opt.guides) {
+    group.gather(dummy.map((t) => t.normalHits), dummy.map((t) => t.npix * 16), gnh, 0, opt.forceRccl);
+    group.gather(dummy.map((t) => t.albedoDepth), dummy.map((t) => t.npix * 16), gad, 0, opt.forceRccl);
+  }
   group.finish();
   const ms = q0.timerStopMs();
   // what the gather did: the route of every tile and whether each context reads the root's device directly (mirt.h MIRT_ROUTE_*)
@@ -371,7 +393,14 @@ function renderTiled(packed, nDevices, passes, opt) {
   q0.enqueueReadBuffer(frame, true, 0, pixel.length, pixel, []);
   q0.enqueueReadBuffer(rad, true, 0, radiance.byteLength, radiance, []);
   q0.finish();
-  const res = { pixel: pixel, radiance: radiance, ms: ms, device: live.length + " x " + live[0].device.getInfo(webcl.DEVICE_NAME), tiles: tiles.map((t) => (t ? [t.row0, t.nrows] : [0, 0])), routes: routes, peerAccess: peers };
+  let guides;
+  if (opt.guides) {
+    guides = { normalHits: new Float32Array(npix * 4), albedoDepth: new Float32Array(npix * 4) };
+    q0.enqueueReadBuffer(gnh, true, 0, npix * 16, guides.normalHits, []);
+    q0.enqueueReadBuffer(gad, true, 0, npix * 16, guides.albedoDepth, []);
+    q0.finish();
+  }
+  const res = { pixel: pixel, radiance: radiance, guides: guides, ms: ms, device: live.length + " x " + live[0].device.getInfo(webcl.DEVICE_NAME), tiles: tiles.map((t) => (t ? [t.row0, t.nrows] : [0, 0])), routes: routes, peerAccess: peers };
   live.forEach((t) => t.release());
   group.release();
   return res;
@@ -409,6 +438,7 @@ function renderFile(file, width, height, rpp, passes, opt) {
     try { return renderTiled(packed, opt.gpus, passes, opt); } finally { if (ownCtx) ownCtx.release(); }
   }
   if (opt.everyPass && !opt.passesInOneLaunch) throw new Error("--every-pass writes the frames of passes in one launch: give --passes-in-one-launch too");
+  if (opt.guides && opt.granular) throw new Error("--guides are the fused host's (mirt_render_guides): not with the kernel-by-kernel host");
   if (opt.passesInOneLaunch && opt.granular) throw new Error("passes in one launch are the fused pass's (mirt_render_passes): not with the kernel-by-kernel host");
   const R = opt.granular ? new GranularRenderer(packed, opt) : new FusedRenderer(packed, opt);
   R.q.timerStart();
@@ -418,6 +448,7 @@ function renderFile(file, width, height, rpp, passes, opt) {
   const res = { pixel: R.readPixels(), radiance: opt.granular ? radianceSums(R.readAcu(), rpp) : R.readRadiance(), ms: ms,
                 device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: R.ctx.fusedPasses ? R.ctx.fusedPasses() : 0 };
   if (opt.everyPass) res.frames = R.readFrames();
+  if (opt.guides) { R.renderGuides(); res.guides = R.readGuides(); }
   R.release();
   if (ownCtx) ownCtx.release();
   return res;

@@ -12,7 +12,8 @@
 //   ctx.createBuffer(flags, bytes)                                     :1083, 1117-1118, ...
 //   queue.enqueueWriteBuffer / enqueueReadBuffer / enqueueNDRangeKernel / finish  :1095-1096, 1153, 1532-1533
 //   release() on everything                                            :1539-1552
-// plus extensions: queue.renderPass(desc), the whole executeRender() in one fused launch; webcl.createDeviceGroup(devices), N contexts
+// plus extensions: queue.renderPass(desc), the whole executeRender() in one fused launch; queue.renderGuides(desc, normalHits, albedoDepth), the
+// first-hit guide buffers of the same descriptor; webcl.createDeviceGroup(devices), N contexts
 // in this one process with group.gather() to assemble row tiles on one device (RCCL); queue.gridBuild*, capture / launchGraph.
 //
 // There is no OpenCL compiler behind createProgram(): the kernels are built-in HIP code, looked
@@ -163,15 +164,25 @@ class WebCLCommandQueue {
   captureEnd() { return { h: wrap(() => native().captureEnd(this.ctx.h)), release() { native().graphRelease(this.h); } }; }
   launchGraph(g) { wrap(() => native().graphLaunch(this.ctx.h, g.h)); }
   // ---- extension: one fused launch for the whole pass (mirt_render_pass) -------------------
-  renderPass(desc) {
+  _passDesc(desc) {
     const g = (s) => s && { prims: s.prims.h, normals: s.normals ? s.normals.h : undefined, matid: s.matid ? s.matid.h : undefined,
                             cellOffsets: s.cellOffsets.h, bounds: s.bounds, nSlabs: s.nSlabs, meshMatId: s.meshMatId || 0 };
-    const d = Object.assign({}, desc, {
+    return Object.assign({}, desc, {
       spheres: g(desc.spheres), triangles: g(desc.triangles), meshes: (desc.meshes || []).map(g),
-      material: desc.material.h, seeds: desc.seeds.h, acu: desc.acu ? desc.acu.h : undefined,   // no acu: a first pass that resolves its pixels itself (mirt.h)
+      material: desc.material.h, seeds: desc.seeds ? desc.seeds.h : undefined, acu: desc.acu ? desc.acu.h : undefined,   // no acu: a first pass that resolves its pixels itself (mirt.h)
       pixel: desc.pixel ? desc.pixel.h : undefined, radiance: desc.radiance ? desc.radiance.h : undefined,
     });
+  }
+  renderPass(desc) {
+    const d = this._passDesc(desc);
     wrap(() => native().renderPass(this.ctx.h, d));
+  }
+  // ---- extension: first-hit guide buffers of desc's row tile (mirt_render_guides): float4 per pixel, normalHits = (sum of the hit samples' normals,
+  // hits), albedoDepth = (sum of their material colours, sum of their hit distances).  Either may be null, not both; desc's seeds, acu, pixel,
+  // radiance and lights are not needed and nothing but the two buffers is written
+  renderGuides(desc, normalHits, albedoDepth) {
+    const d = this._passDesc(desc);
+    wrap(() => native().renderGuides(this.ctx.h, d, normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
   }
   // ---- extension: a whole Assign04 / Assign07 frame in one launch (mirt_render_frame): initTrace and the trace kernel(s) on one thread per pixel,
   // no ray buffer unless desc.rays is given.  desc: {assign, width, height, cam, bounds, nSlabs, pixel, rays?} plus the mesh {tSize, tPos, tNormal,

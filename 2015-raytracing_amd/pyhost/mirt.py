@@ -100,6 +100,7 @@ SYMBOLS = {
     "mirt_render_pass": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc)]),
     "mirt_render_first_pass": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc)]),
     "mirt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32]),
+    "mirt_render_guides": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_ctx_set_exact_only": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_set_fusion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -448,6 +449,11 @@ class Context:
         flags = (PASSES_FRESH if fresh else 0) | (PASSES_EVERY_FRAME if every_frame else 0)
         self._chk(lib().mirt_render_passes(self.h, C.byref(desc), int(n_passes), flags))
 
+    def render_guides(self, desc, normal_hits=None, albedo_depth=None):
+        """First-hit guide buffers of desc's row tile (mirt_render_guides): float4 per pixel, (sum of the hit samples' normals, hits) and
+        (sum of their material colours, sum of their hit distances).  Either buffer may be None, not both; desc.seeds / acu are not touched."""
+        self._chk(lib().mirt_render_guides(self.h, C.byref(desc), normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
     def destroy(self):
         if self.h:
             lib().mirt_ctx_destroy(self.h)
@@ -518,7 +524,7 @@ class DeviceScene:
         d.lights = C.cast(larr, C.POINTER(_Light))
         d.n_lights = len(s.lights)
         d.material = self.material.h
-        d.seeds, d.acu = seeds.h, (acu.h if acu else None)   # acu None: a frame's first pass that resolves its pixels itself (include/mirt.h)
+        d.seeds, d.acu = (seeds.h if seeds else None), (acu.h if acu else None)   # acu None: a frame's first pass that resolves its pixels itself (include/mirt.h)
         d.pixel = pixel.h if pixel else None
         d.radiance = radiance.h if radiance else None
         d._keep = keep

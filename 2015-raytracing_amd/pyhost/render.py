@@ -261,6 +261,23 @@ class FusedRenderer:
             self.radiance.write(rad[-1])
         return pix, rad
 
+    def guides(self, rows=None):
+        """First-hit guide buffers (mirt_render_guides) of this renderer's tile, or of rows = (row0, nrows) of the image: two float32 arrays
+        [pixels, 4], normal_hits = (sum of the hit samples' normals, hits) and albedo_depth = (sum of their material colours, sum of their hit
+        distances).  Seeds, accumulator and frame are not touched."""
+        row0, nrows = (self.row0, self.nrows) if rows is None else rows
+        npix = nrows * self.s.width
+        if not npix:
+            return np.zeros((0, 4), np.float32), np.zeros((0, 4), np.float32)
+        nh, ad = self.ctx.buffer(npix * 16), self.ctx.buffer(npix * 16)
+        try:
+            d = self.dev.pass_desc(None, None, row0=row0, nrows=nrows)
+            self.ctx.render_guides(d, nh, ad)
+            return nh.read(np.float32).reshape(-1, 4), ad.read(np.float32).reshape(-1, 4)
+        finally:
+            nh.release()
+            ad.release()
+
     def _frames(self, name, nbytes):
         """a frame buffer of at least nbytes, kept for the next call"""
         b = getattr(self, name, None)

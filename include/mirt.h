@@ -227,6 +227,23 @@ MIRT_API int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* desc);
 #define MIRT_PASSES_EVERY_FRAME 2u
 #define MIRT_MAX_PASSES_PER_CALL 64u
 MIRT_API int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* desc, uint32_t n_passes, uint32_t flags);
+/* First-hit GUIDE BUFFERS of the row tile, for a denoiser or a-trous filter behind a few-rays-per-pixel frame.  Per tile-local pixel, over its
+ * rays pixel * rays_per_pixel + i in sample order i = 0 .. rays_per_pixel - 1 (copyToPixel's order, A10 code.cl:1377-1380), each ray as initTrace
+ * and the closest-hit stage (sphereTrace, triangleTrace, every meshTrace in upload order) leave it, before lightRender and any shading:
+ *   normal_hits [pixel] = float4(sum Poi.normal.x, sum .y, sum .z, number of hit samples)
+ *   albedo_depth[pixel] = float4(sum material[matId].x, sum .y, sum .z, sum Ray.maxt)
+ * sequential fp32 sums from +0 over the HIT samples only, un-normalised like `radiance`; a pixel without a hit is all +0 in both.  A sample is a
+ * hit when the stage leaves a live vertex -- Poi.matId >= 0, the reference's own test (initTrace resets it to -1, code.cl:538-541; sceneRender
+ * shades iff matId >= 0, code.cl:1336); an id past the material table is not a hit and reads nothing.  The guides describe SURFACES: an emitter in
+ * front of the surface (lightRender) is not considered.  Poi.normal and Ray.maxt are the bits the kernel-by-kernel path stores.
+ * Reads of the descriptor: the image size, rays_per_pixel, row0 / nrows, cam, scene_bounds, focal_length, lens_rad, the primitive sets and
+ * material.  Ignored, and free to be NULL or 0: seeds, acu, pixel, radiance, the lights, bounces, pass_index.  Either output may be NULL, not both
+ * (MIRT_E_ARG).  Checks as in mirt_render_pass (descriptor size, tile inside the image, k x k rays: MIRT_E_ARG; cell tables: MIRT_E_DATA; a
+ * buffer too small: MIRT_E_RANGE); when one fails nothing is written.  Nothing but the two outputs is ever written: the k x k lens grid draws
+ * nothing from the seeds, so the guides are the same for every pass of a frame.  rays_per_pixel == 1 draws its lens sample from seeds[col]
+ * (code.cl:429) and is refused (MIRT_E_ARG).  Ray ids are global: a tile's guides equal the same rows of the whole frame's.  Not while capturing
+ * (MIRT_E_ARG).  MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
+MIRT_API int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* desc, mirt_buf* normal_hits, mirt_buf* albedo_depth);
 /* Two ways to run the pass, identical results.  Default: the optimistic pair -- a kernel whose divisions are 3-operation
  * forms proven bit-exact inside a guard window (exhaustively, on the device: profiles/r1_divcheck_exhaustive.txt), plus the
  * exact kernel re-running the samples whose rays left the window (NaN rays, axis-parallel directions, ...); it needs every
