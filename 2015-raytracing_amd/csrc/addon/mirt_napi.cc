@@ -381,6 +381,34 @@ napi_value RenderGuides(napi_env env, napi_callback_info info) {
     return render_call(env, argv[0], argv[1], true, argv[2], argv[3]);
 }
 
+// filterAtrous(ctx, {width,height,iterations,flags,normalPowerLog2,tone,sigmaDepth,sigmaColour, radiance,normalHits,albedoDepth, filtered?,pixel?}):
+// the a-trous filter of a frame on the device (mirt_filter_atrous); a number left out is 0, a buffer left out NULL -- the library checks them all
+napi_value FilterAtrous(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "filterAtrous(ctx, desc)");
+    napi_value d = argv[1];
+    mirt_filter_desc f;
+    memset(&f, 0, sizeof f);
+    f.struct_size = sizeof f;
+    prop_u32(env, d, "width", &f.width);
+    prop_u32(env, d, "height", &f.height);
+    prop_u32(env, d, "iterations", &f.iterations);
+    prop_u32(env, d, "flags", &f.flags);
+    prop_u32(env, d, "normalPowerLog2", &f.normal_power_log2);
+    prop_f32(env, d, "tone", &f.tone);
+    prop_f32(env, d, "sigmaDepth", &f.sigma_depth);
+    prop_f32(env, d, "sigmaColour", &f.sigma_colour);
+    f.radiance = prop_buf(env, d, "radiance");
+    f.normal_hits = prop_buf(env, d, "normalHits");
+    f.albedo_depth = prop_buf(env, d, "albedoDepth");
+    f.filtered = prop_buf(env, d, "filtered");
+    f.pixel = prop_buf(env, d, "pixel");
+    const int rc = mirt_filter_atrous((mirt_ctx*)c, &f);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+
 // renderFrame(ctx, {assign,width,height,cam,bounds?,nSlabs?, tSize?,tPos?,tNormal?,tMindex?,tMcolor?,tSlabSize?, sSize?,sAtoms?,sMindex?,sMcolor?,sSlabSize?,
 //                   pixel, rays?}): a whole Assign04 / Assign07 frame in one launch (mirt_render_frame)
 napi_value RenderFrame(napi_env env, napi_callback_info info) {
@@ -669,7 +697,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"filterAtrous", FilterAtrous}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

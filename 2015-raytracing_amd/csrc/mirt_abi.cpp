@@ -1528,6 +1528,77 @@ int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_
     return MIRT_OK;
 } MIRT_CATCH("mirt_render_guides", return MIRT_E_DEVICE)
 
+// The a-trous filter (pt_kernels_filter.hip; defined in include/mirt.h): every check first, then the prepare launch and one launch per iteration,
+// the last of which writes the outputs.  The two working images and the prepared guide are three float4 arrays of the context's scratch buffer,
+// asked for ONCE (growing the buffer frees the old one: pt_pass_plan.hpp).
+int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* d) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_filter_atrous: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_filter_atrous");
+    if (!d || d->struct_size != sizeof(mirt_filter_desc)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: descriptor size mismatch");
+    if (!d->width || !d->height) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: empty image");
+    if (d->width > 65535u || d->height > 65535u) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: %ux%u is more than 65535 pixels a side", d->width, d->height);
+    if (d->iterations > MIRT_FILTER_MAX_ITERATIONS) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: %u iterations > %u", d->iterations, MIRT_FILTER_MAX_ITERATIONS);
+    if (d->normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2)
+        return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: normal_power_log2 %u > %u", d->normal_power_log2, MIRT_FILTER_MAX_NORMAL_POWER_LOG2);
+    if (!(std::isfinite(d->tone) && d->tone > 0.0f)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: tone %g is not a finite positive factor", (double)d->tone);
+    const uint32_t both = MIRT_FILTER_DIRECT | MIRT_FILTER_TILED;
+    if ((d->flags & ~(MIRT_FILTER_DEMODULATE | both)) || (d->flags & both) == both) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: unknown flags 0x%x (or both structures forced)", d->flags);
+    if (!d->filtered && !d->pixel) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: filtered and pixel are both NULL (either may be, not both)");
+    const uint64_t npix = (uint64_t)d->width * d->height;
+    int rc;
+    if ((rc = need(ctx, "mirt_filter_atrous radiance", d->radiance, npix * 16))) return rc;
+    if ((rc = need(ctx, "mirt_filter_atrous normal_hits", d->normal_hits, npix * 16))) return rc;
+    if ((rc = need(ctx, "mirt_filter_atrous albedo_depth", d->albedo_depth, npix * 16))) return rc;
+    if (d->filtered && (rc = need(ctx, "mirt_filter_atrous filtered", d->filtered, npix * 16))) return rc;
+    if (d->pixel && (rc = need(ctx, "mirt_filter_atrous pixel", d->pixel, npix * 4))) return rc;
+    {   // an output is read by nobody and no input is written: the same handle, or (wrapped memory) the same bytes, twice is refused
+        const mirt_buf* const in[3] = {d->radiance, d->normal_hits, d->albedo_depth};
+        const mirt_buf* const out[2] = {d->filtered, d->pixel};
+        const uint64_t out_bytes[2] = {npix * 16, npix * 4};
+        auto overlap = [](const mirt_buf* a, uint64_t na, const mirt_buf* b, uint64_t nb) {
+            return a == b || ((const char*)a->ptr < (const char*)b->ptr + nb && (const char*)b->ptr < (const char*)a->ptr + na);
+        };
+        for (int o = 0; o < 2; ++o) {
+            if (!out[o]) continue;
+            for (int i = 0; i < 3; ++i)
+                if (overlap(out[o], out_bytes[o], in[i], npix * 16)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: an output aliases an input");
+        }
+        if (out[0] && out[1] && overlap(out[0], out_bytes[0], out[1], out_bytes[1])) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: filtered aliases pixel");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::FilterArgs A;
+    memset(&A, 0, sizeof A);
+    A.width = d->width; A.height = d->height;
+    A.demodulate = (d->flags & MIRT_FILTER_DEMODULATE) ? 1u : 0u;
+    A.npow = d->normal_power_log2;
+    A.depth_on = std::isfinite(d->sigma_depth) && d->sigma_depth > 0.0f;
+    A.colour_on = std::isfinite(d->sigma_colour) && d->sigma_colour > 0.0f;
+    A.tone = d->tone; A.sigma_depth = d->sigma_depth;
+    A.radiance = d->radiance->ptr; A.normal_hits = d->normal_hits->ptr; A.albedo_depth = d->albedo_depth->ptr;
+    A.filtered = d->filtered ? d->filtered->ptr : nullptr;
+    A.pixel = d->pixel ? d->pixel->ptr : nullptr;
+    if (d->iterations) {
+        const size_t plane = (size_t)npix * 16;
+        if ((rc = ensure_scratch(ctx, 3 * plane))) return rc;
+        char* const scratch = (char*)ctx->scratch;
+        A.work[0] = scratch; A.work[1] = scratch + plane; A.guide = scratch + 2 * plane;
+    }
+    pt::launch_filterPrepare(ctx->stream, A, d->iterations == 0u);
+    for (uint32_t i = 0; i < d->iterations; ++i) {
+        // inv_i = 1 / (k_i * k_i), k_i = sigma_colour * 2^-i: three IEEE fp32 operations of the host, each rounded on its own
+        volatile float k = d->sigma_colour * std::ldexp(1.0f, -(int)i);
+        volatile float kk = k * k;
+        volatile float inv = 1.0f / kk;
+        const bool tiled = (d->flags & both) ? (d->flags & MIRT_FILTER_TILED) != 0u : (pt::kFilterTiledSteps >> i & 1u) != 0u;
+        pt::launch_filterStep(ctx->stream, A, i & 1u, i, A.colour_on ? inv : 0.0f, i + 1u == d->iterations, tiled);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (d->filtered) d->filtered->version++;
+    if (d->pixel) d->pixel->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_filter_atrous", return MIRT_E_DEVICE)
+
 int mirt_ctx_set_fusion(mirt_ctx* ctx, int level) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_fusion: unknown context");
     if (level != 0 && level != 2) return fail(ctx, MIRT_E_ARG, "mirt_ctx_set_fusion: level is 0 (every enqueue launches) or 2 (whole passes are fused)");

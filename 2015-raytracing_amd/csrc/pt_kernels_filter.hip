@@ -1,0 +1,211 @@
+// pt_kernels_filter.hip -- the edge-avoiding a-trous filter behind a few-rays-per-pixel frame (mirt_filter_atrous), guided by the first-hit
+// guide buffers of pt_kernels_guides.hip.  The definition -- every operation, in order -- is the comment of mirt_filter_atrous in include/mirt.h;
+// tests/filter_common.py restates it in numpy and the kernels equal that restatement bit for bit, in both libraries.
+//
+// Numerics.  One fp32 operation at a time, rounded on its own: every translation unit builds with -ffp-contract=off, and nothing here is an fma.
+// The reference has no filter, so there is ONE contract for libmirt.so and libmirt_default.so: a plain `/` would be AMD's 2.5-ulp sequence in the
+// default-contract build, so every quotient is div_cr() below -- the operands widened to fp64, divided there (fp64 division is correctly rounded
+// in both builds) and rounded back: 53 >= 2 * 24 + 2 bits make the double rounding harmless, the result IS the correctly rounded fp32 quotient.
+// Four quotients per pixel and iteration beside 24 taps: their cost does not matter.  No exp, pow or sqrt: the edge terms are hats and repeated
+// squaring.
+//
+// Working set (the context's scratch buffer, FilterArgs::work / guide): two float4 images (I.x, I.y, I.z, live ? 1 : 0) that the iterations
+// alternate between, and the prepared guide (n^.x, n^.y, n^.z, z).  A tap is 32 B: its colour and, when it is live, its guide.
+//
+// Two structures of an iteration, the same filter_pixel() behind both (DESIGN.md section 5 has the comparison, profiles/filter/timing.json the numbers):
+//   k_filterDirect  one thread per pixel, blocks of 64 x 4 pixels; a wave is 64 neighbours of one row, so each of its 24 tap reads is one
+//                   contiguous 1 KB row segment served by L1 / L2 whatever the step is.
+//   k_filterTiled   for step s the pixels with equal (x mod s, y mod s) form an image of their own whose 5 x 5 neighbours are the taps: a block
+//                   stages a 20 x 20 tile of that lattice in LDS (colour + guide, 12.8 KB) and filters its inner 16 x 16.  Coalesced at s = 1,
+//                   strided loads beyond.
+// Measured at 1080p (MI355X): the tiles win at steps 1 and 2 (0.053 / 0.072 ms against 0.096 / 0.093), direct reads at 4, 8 and 16 (0.098 / 0.093 /
+// 0.086 ms against 0.106 / 0.189 / 0.130): kFilterTiledSteps in pt_launch.hpp.
+#include "pt_launch.hpp"
+#include "pt_numerics.hpp"
+
+namespace pt {
+
+PT_DEV float div_cr(float n, float d) { return (float)((double)n / (double)d); }
+
+// what the prepare step and the last step both need of a pixel: r = 1 / hits, a = A * r
+PT_DEV void filter_albedo(const FilterArgs& A, uint32_t p, float hits, float& ax, float& ay, float& az) {
+    const float4 ad = ((const float4*)A.albedo_depth)[p];
+    const float r = div_cr(1.0f, hits);
+    ax = ad.x * r; ay = ad.y * r; az = ad.z * r;
+}
+
+// out = I_n (times the albedo where the image was demodulated) -> filtered, pixel (k_copyToPixel's tone map, pt_kernels_granular.hip)
+PT_DEV void filter_finish(const FilterArgs& A, uint32_t p, float ox, float oy, float oz, bool live) {
+    if (A.demodulate && live) {
+        float ax, ay, az;
+        filter_albedo(A, p, ((const float4*)A.normal_hits)[p].w, ax, ay, az);
+        if (ax > 0.0f) ox = ox * ax;
+        if (ay > 0.0f) oy = oy * ay;
+        if (az > 0.0f) oz = oz * az;
+    }
+    if (A.filtered) ((float4*)A.filtered)[p] = make_float4(ox, oy, oz, ((const float4*)A.radiance)[p].w);
+    if (A.pixel) {
+        const float sc = 255.0f * A.tone;
+        const float x = cl_clamp((ox * sc) * 1.8f, 0.0f, 255.0f);
+        const float y = cl_clamp((oy * sc) * 1.8f, 0.0f, 255.0f);
+        const float z = cl_clamp((oz * sc) * 1.8f, 0.0f, 255.0f);
+        ((uchar4*)A.pixel)[p] = make_uchar4((unsigned char)f2u(x), (unsigned char)f2u(y), (unsigned char)f2u(z), 255);
+    }
+}
+
+// I_0 and the prepared guide of every pixel.  LAST (iterations == 0): the outputs, straight from I_0.
+template <bool LAST>
+__global__ void __launch_bounds__(256) k_filterPrepare(const FilterArgs A) {
+    const uint32_t npix = A.width * A.height;
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= npix) return;
+    const float4 R = ((const float4*)A.radiance)[p];
+    const float4 nh = ((const float4*)A.normal_hits)[p];
+    const bool live = nh.w > 0.0f;
+    float ix = R.x, iy = R.y, iz = R.z;
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (live) {
+        const float4 ad = ((const float4*)A.albedo_depth)[p];
+        const float r = div_cr(1.0f, nh.w);
+        g = make_float4(nh.x * r, nh.y * r, nh.z * r, ad.w * r);
+        if (A.demodulate) {
+            const float ax = ad.x * r, ay = ad.y * r, az = ad.z * r;
+            if (ax > 0.0f) ix = div_cr(R.x, ax);
+            if (ay > 0.0f) iy = div_cr(R.y, ay);
+            if (az > 0.0f) iz = div_cr(R.z, az);
+        }
+    }
+    if (LAST) { filter_finish(A, p, ix, iy, iz, live); return; }
+    ((float4*)A.work[0])[p] = make_float4(ix, iy, iz, live ? 1.0f : 0.0f);
+    ((float4*)A.guide)[p] = g;
+}
+
+// One iteration of one live centre pixel.  tap(dx, dy, c, g): the colour of the tap into c, false when it is outside the image or not live,
+// else its guide into g.  Returns I_{i+1}(p).
+template <class Tap>
+PT_DEV float4 filter_pixel(const FilterArgs& A, float inv_colour, const float4 cp, const float4 gp, const Tap& tap) {
+    const float h[3] = {0.375f, 0.25f, 0.0625f};
+    float izp = 0.0f;
+    if (A.depth_on) izp = div_cr(1.0f, A.sigma_depth * gp.w);
+    float sumw = 0.140625f;
+    float sx = cp.x * 0.140625f, sy = cp.y * 0.140625f, sz = cp.z * 0.140625f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            if (dx == 0 && dy == 0) continue;
+            float4 cq, gq;
+            if (!tap(dx, dy, cq, gq)) continue;
+            const float k = h[dy < 0 ? -dy : dy] * h[dx < 0 ? -dx : dx];
+            float wn = cl_max(0.0f, (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z);
+            for (uint32_t j = 0; j < A.npow; ++j) wn = wn * wn;
+            float w = k * wn;
+            if (A.depth_on) w = w * cl_max(0.0f, 1.0f - cl_fabs(gp.w - gq.w) * izp);
+            if (A.colour_on) {
+                const float ex = (cp.x - cq.x) * A.tone, ey = (cp.y - cq.y) * A.tone, ez = (cp.z - cq.z) * A.tone;
+                const float c = (ex * ex + ey * ey) + ez * ez;
+                w = w * cl_max(0.0f, 1.0f - c * inv_colour);
+            }
+            if (w > 0.0f) {
+                sumw += w;
+                sx += cq.x * w; sy += cq.y * w; sz += cq.z * w;
+            }
+        }
+    }
+    return make_float4(div_cr(sx, sumw), div_cr(sy, sumw), div_cr(sz, sumw), 1.0f);
+}
+
+template <bool LAST>
+PT_DEV void filter_store(const FilterArgs& A, uint32_t dst, uint32_t p, const float4 v) {
+    if (LAST) filter_finish(A, p, v.x, v.y, v.z, v.w != 0.0f);
+    else ((float4*)A.work[dst])[p] = v;
+}
+
+// (a) direct reads
+template <bool LAST>
+__global__ void __launch_bounds__(256) k_filterDirect(const FilterArgs A, uint32_t src, int step, float inv_colour) {
+    const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
+    const int W = (int)A.width, H = (int)A.height;
+    if (x >= W || y >= H) return;
+    const float4* const col = (const float4*)A.work[src];
+    const float4* const gd = (const float4*)A.guide;
+    const uint32_t p = (uint32_t)y * A.width + (uint32_t)x;
+    float4 v = col[p];
+    if (v.w != 0.0f) {
+        v = filter_pixel(A, inv_colour, v, gd[p], [&](int dx, int dy, float4& c, float4& g) {
+            const int qx = x + dx * step, qy = y + dy * step;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) return false;
+            const uint32_t q = (uint32_t)qy * A.width + (uint32_t)qx;
+            c = col[q];
+            g = gd[q];   // read whether the tap is live or not: both loads of a tap are then in flight together
+            return c.w != 0.0f;
+        });
+    }
+    filter_store<LAST>(A, src ^ 1u, p, v);
+}
+
+// (b) decimated LDS tiles.  blockIdx.x = tile column * step + (x mod step), blockIdx.y likewise.
+// kTilePitch: float4 between rows of the LDS tile.  The dense tile (20: 12.8 KB); rows 32 float4 apart (20 KB) measured the same at every step
+// (profiles/filter/timing_pitch32.json against timing.json)
+constexpr int kTileIn = 16, kTileHalo = 2, kTileSide = kTileIn + 2 * kTileHalo, kTilePitch = kTileSide;
+template <bool LAST>
+__global__ void __launch_bounds__(256) k_filterTiled(const FilterArgs A, uint32_t src, int step, float inv_colour) {
+    __shared__ float4 s_col[kTileSide * kTilePitch];
+    __shared__ float4 s_gd[kTileSide * kTilePitch];
+    const int W = (int)A.width, H = (int)A.height;
+    const int cx = (int)blockIdx.x % step, cy = (int)blockIdx.y % step;
+    const int lx0 = ((int)blockIdx.x / step) * kTileIn - kTileHalo, ly0 = ((int)blockIdx.y / step) * kTileIn - kTileHalo;   // lattice coordinates of the tile's corner
+    const float4* const col = (const float4*)A.work[src];
+    const float4* const gd = (const float4*)A.guide;
+    for (int i = (int)threadIdx.x; i < kTileSide * kTileSide; i += 256) {
+        const int ty = i / kTileSide, tx = i % kTileSide;
+        const int lx = lx0 + tx, ly = ly0 + ty;
+        const int qx = lx * step + cx, qy = ly * step + cy;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), g = c;   // outside the image: not live
+        if (lx >= 0 && ly >= 0 && qx < W && qy < H) {
+            const uint32_t q = (uint32_t)qy * A.width + (uint32_t)qx;
+            c = col[q];
+            g = gd[q];
+        }
+        s_col[ty * kTilePitch + tx] = c;
+        s_gd[ty * kTilePitch + tx] = g;
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x & 15u) + kTileHalo, ty = (int)(threadIdx.x >> 4) + kTileHalo;
+    const int x = (lx0 + tx) * step + cx, y = (ly0 + ty) * step + cy;
+    if (x >= W || y >= H) return;
+    const uint32_t p = (uint32_t)y * A.width + (uint32_t)x;
+    const int at = ty * kTilePitch + tx;
+    float4 v = s_col[at];
+    if (v.w != 0.0f) {
+        v = filter_pixel(A, inv_colour, v, s_gd[at], [&](int dx, int dy, float4& c, float4& g) {
+            c = s_col[at + dy * kTilePitch + dx];
+            if (c.w == 0.0f) return false;
+            g = s_gd[at + dy * kTilePitch + dx];
+            return true;
+        });
+    }
+    filter_store<LAST>(A, src ^ 1u, p, v);
+}
+
+void launch_filterPrepare(hipStream_t s, const FilterArgs& a, bool last) {
+    const dim3 grid((unsigned)(((uint64_t)a.width * a.height + 255u) / 256u));
+    if (last) hipLaunchKernelGGL(k_filterPrepare<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_filterPrepare<false>, grid, dim3(256), 0, s, a);
+}
+
+void launch_filterStep(hipStream_t s, const FilterArgs& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled) {
+    const int step = 1 << step_log2;
+    if (tiled) {
+        const uint32_t lw = (a.width + (uint32_t)step - 1u) / (uint32_t)step, lh = (a.height + (uint32_t)step - 1u) / (uint32_t)step;
+        const dim3 grid((lw + kTileIn - 1u) / kTileIn * (uint32_t)step, (lh + kTileIn - 1u) / kTileIn * (uint32_t)step);
+        if (last) hipLaunchKernelGGL(k_filterTiled<true>, grid, dim3(256), 0, s, a, src, step, inv_colour);
+        else hipLaunchKernelGGL(k_filterTiled<false>, grid, dim3(256), 0, s, a, src, step, inv_colour);
+    } else {
+        const dim3 grid((a.width + 63u) / 64u, (a.height + 3u) / 4u);
+        if (last) hipLaunchKernelGGL(k_filterDirect<true>, grid, dim3(256), 0, s, a, src, step, inv_colour);
+        else hipLaunchKernelGGL(k_filterDirect<false>, grid, dim3(256), 0, s, a, src, step, inv_colour);
+    }
+}
+
+}  // namespace pt

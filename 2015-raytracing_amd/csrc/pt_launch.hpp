@@ -131,6 +131,30 @@ void launch_deferCount(hipStream_t s, const uint32_t* mask, uint32_t words, uint
 // albedo_depth = (sum of their material colours, sum of their Ray.maxt).  One lane per pixel; the optimistic / exact pair as in launch_fused, the
 // mask one bit per pixel: (nrows * width + 31) / 32 words.  Reads the camera, bounds, sets and material of `a`; either output may be null.
 void launch_guides(hipStream_t s, const FusedArgs& a, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask, const uint32_t* redo_mask);
+// Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
+// every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
+struct FilterArgs {
+    uint32_t width, height;
+    uint32_t demodulate;         // MIRT_FILTER_DEMODULATE
+    uint32_t npow;               // normal_power_log2: the normal term is squared that many times
+    uint32_t depth_on, colour_on;
+    float tone, sigma_depth;
+    const void* radiance;        // float4 per pixel
+    const void* normal_hits;
+    const void* albedo_depth;
+    void* filtered;              // float4 per pixel, or null
+    void* pixel;                 // uchar4 per pixel, or null
+    void* work[2];               // (I.xyz, live ? 1 : 0): iteration i reads work[i & 1] and writes the other
+    void* guide;                 // (n^.xyz, z), zero where the pixel is not live
+};
+// I_0 into work[0] and the prepared guide; last (no iteration follows): the outputs instead
+void launch_filterPrepare(hipStream_t s, const FilterArgs& a, bool last);
+// iteration step_log2 (step 2^step_log2) from work[src] into work[src ^ 1], or -- last -- into the outputs.  inv_colour: 1 / (k_i * k_i), IEEE fp32,
+// from the host.  tiled: the decimated LDS tiles, else one thread per pixel reading its taps directly; the bits are the same.
+void launch_filterStep(hipStream_t s, const FilterArgs& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled);
+// which structure an iteration of step 2^step_log2 runs as unless the caller forces one: bit step_log2 set = tiled.  Measured at 1080p
+// (profiles/filter/timing.json, step_direct_ms against step_tiled_ms): the LDS tiles win at steps 1 and 2, direct reads at 4, 8 and 16.
+constexpr uint32_t kFilterTiledSteps = 0x03u;
 // {p0,e1,e2,n} records from the host's 3 x float4 position buffer (see pt_kernels_fused.hip); `out` holds count records of 48 B,
 // behind them ceil(count / kTriGroup) float4 {centre, R'^2}: the bounding spheres of groups of consecutive records, and behind those, for
 // count <= kLdsTriMax, the candidate sweep's plane list (GridArgs::pnorm)

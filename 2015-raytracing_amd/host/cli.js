@@ -1,8 +1,8 @@
 #!/usr/bin/env node
 // host/cli.js -- command-line front end of the JavaScript host.
 //   node cli.js pack   <scene.xml> <width> <height> <raysPerPixel>                 -> packed kernel inputs as JSON (stdout)
-//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]] [--guides PREFIX]
-//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows)
+//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]] [--guides PREFIX] [--denoise [iterations]]
+//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
@@ -47,10 +47,15 @@ if (cmd === "pack") {
   if ((i = rest.indexOf("--bounces")) >= 0) opt.bounces = +rest[i + 1];
   if ((i = rest.indexOf("--gpus")) >= 0) { opt.gpus = +rest[i + 1]; opt.forceRccl = rest.includes("--force-rccl"); }   // row tiles over N devices + gather
   if ((i = rest.indexOf("--guides")) >= 0) { if (!rest[i + 1]) usage(); opt.guides = rest[i + 1]; }   // first-hit guide buffers beside the frame (mirt_render_guides)
+  if ((i = rest.indexOf("--denoise")) >= 0) {   // the frame filtered on the device (mirt_filter_atrous); implies the guides; with --gpus N: gathered, then filtered on the root
+    opt.denoise = {};
+    if (/^\d+$/.test(rest[i + 1] || "")) opt.denoise.iterations = +rest[i + 1];
+  }
   if ((i = rest.indexOf("--seeds")) >= 0) { const b = fs.readFileSync(rest[i + 1]); opt.seeds = new Int32Array(b.buffer, b.byteOffset, b.length / 4); }
   const [file, w, h, rpp, passes, out] = [rest[0], +rest[1], +rest[2], +rest[3], +rest[4], rest[5]];
   const res = renderer.renderFile(file, w, h, rpp, passes, opt);
-  writeFrame(out, res.pixel, w, h);
+  writeFrame(out, res.denoised ? res.denoised.pixel : res.pixel, w, h);
+  if (res.denoised) fs.writeFileSync(out + ".filtered.f32", Buffer.from(res.denoised.filtered.buffer, res.denoised.filtered.byteOffset, res.denoised.filtered.byteLength));
   fs.writeFileSync(out + ".radiance.f32", Buffer.from(res.radiance.buffer, res.radiance.byteOffset, res.radiance.byteLength));
   if (res.guides) {
     for (const [name, a] of [["normal_hits", res.guides.normalHits], ["albedo_depth", res.guides.albedoDepth]])

@@ -336,13 +336,32 @@ class FusedRenderer {
     this.q.finish();
     return { normalHits: n, albedoDepth: a };
   }
+  // the a-trous-filtered frame of this renderer's current radiance (queue.filterFrame, guided by renderGuides()'s buffers), all on the device; f: any
+  // of iterations, normalPowerLog2, sigmaDepth, sigmaColour, demodulate, structure.  A row tile would be filtered alone: renderTiled gathers first
+  // and filters the whole frame on the root (filterGathered)
+  denoise(f, haveGuides) {   // haveGuides: renderGuides() has already run for this frame
+    if (!haveGuides) this.renderGuides();
+    if (!this.filtered) {
+      this.filtered = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
+      this.filteredPixel = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 4);
+    }
+    this.q.filterFrame(Object.assign({}, f, { width: this.p.width, height: this.nrows, tone: 1 / (this.p.rays_per_pixel * (this.passes - 1)),
+      radiance: this.radiance, normalHits: this.normalHits, albedoDepth: this.albedoDepth, filtered: this.filtered, pixel: this.filteredPixel }));
+  }
+  readDenoised() {
+    const px = new Uint8ClampedArray(this.npix * 4), f = new Float32Array(this.npix * 4);
+    this.q.enqueueReadBuffer(this.filteredPixel, false, 0, px.length, px, []);
+    this.q.enqueueReadBuffer(this.filtered, false, 0, f.byteLength, f, []);
+    this.q.finish();
+    return { pixel: px, filtered: f };
+  }
   // the frames of the last executePasses(n, bounces, {everyPass: true}): { n, pixel: n RGBA8 frames, radiance: n float4 frames }, back to back
   readFrames() { return this.frames; }
   readPixels() { const o = new Uint8ClampedArray(this.npix * 4); this.q.enqueueReadBuffer(this.pixel, false, 0, o.length, o, []); this.q.finish(); return o; }
   readRadiance() { const o = new Float32Array(this.npix * 4); this.q.enqueueReadBuffer(this.radiance, false, 0, o.byteLength, o, []); this.q.finish(); return o; }
   readAcu() { const a = new Float32Array(this.nrays * 4); this.q.enqueueReadBuffer(this.acu, false, 0, a.byteLength, a, []); this.q.finish(); return a; }
   release() {
-    [this.seeds, this.acu, this.pixel, this.radiance, this.normalHits, this.albedoDepth].forEach((b) => b && b.release());
+    [this.seeds, this.acu, this.pixel, this.radiance, this.normalHits, this.albedoDepth, this.filtered, this.filteredPixel].forEach((b) => b && b.release());
     this.dev.bufs.forEach((b) => b.release());
     this.q.release();
     if (this.ownCtx) this.ctx.release();
@@ -372,18 +391,26 @@ function renderTiled(packed, nDevices, passes, opt) {
   q0.timerStart();
   if (opt.passesInOneLaunch) live.forEach((t) => t.executePasses(passes, opt.bounces));   // one call per tile, then the gather
   else for (let p = 0; p < passes; p++) live.forEach((t) => t.executeRender(opt.bounces));
-  if (opt.guides) live.forEach((t) => t.renderGuides());   // every device its tile's guides, gathered like radiance
+  const wantGuides = !!(opt.guides || opt.denoise);   // --denoise implies the guides: the filter runs on the root, on the gathered frame
+  if (wantGuides) live.forEach((t) => t.renderGuides());   // every device its tile's guides, gathered like radiance
   const npix = packed.width * packed.height;
   const root = group.contexts[0];
   const frame = root.createBuffer(webcl.MEM_READ_WRITE, npix * 4), rad = root.createBuffer(webcl.MEM_READ_WRITE, npix * 16);
   const mk16 = (i) => group.contexts[i].createBuffer(webcl.MEM_READ_WRITE, 16);
-  const dummy = tiles.map((t, i) => t || { pixel: mk16(i), radiance: mk16(i), normalHits: opt.guides ? mk16(i) : null, albedoDepth: opt.guides ? mk16(i) : null, npix: 0 });
+  const dummy = tiles.map((t, i) => t || { pixel: mk16(i), radiance: mk16(i), normalHits: wantGuides ? mk16(i) : null, albedoDepth: wantGuides ? mk16(i) : null, npix: 0 });
   group.gather(dummy.map((t) => t.pixel), dummy.map((t) => t.npix * 4), frame, 0, opt.forceRccl);
   group.gather(dummy.map((t) => t.radiance), dummy.map((t) => t.npix * 16), rad, 0, opt.forceRccl);
-  const gnh = opt.guides ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 16) : null, gad = opt.guides ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 16) : null;
-  if (opt.guides) {
+  const gnh = wantGuides ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 16) : null, gad = wantGuides ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 16) : null;
+  if (wantGuides) {
     group.gather(dummy.map((t) => t.normalHits), dummy.map((t) => t.npix * 16), gnh, 0, opt.forceRccl);
     group.gather(dummy.map((t) => t.albedoDepth), dummy.map((t) => t.npix * 16), gad, 0, opt.forceRccl);
+  }
+  // the filter has no tiles: it runs once, on the root, over the gathered radiance and guides (filtering the tiles separately would differ near their borders)
+  const fil = opt.denoise ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 16) : null, filPix = opt.denoise ? root.createBuffer(webcl.MEM_READ_WRITE, npix * 4) : null;
+  if (opt.denoise) {
+    group.finish();
+    q0.filterFrame(Object.assign({}, opt.denoise, { width: packed.width, height: packed.height, tone: 1 / (packed.rays_per_pixel * passes),
+      radiance: rad, normalHits: gnh, albedoDepth: gad, filtered: fil, pixel: filPix }));
   }
   group.finish();
   const ms = q0.timerStopMs();
@@ -400,7 +427,14 @@ function renderTiled(packed, nDevices, passes, opt) {
     q0.enqueueReadBuffer(gad, true, 0, npix * 16, guides.albedoDepth, []);
     q0.finish();
   }
-  const res = { pixel: pixel, radiance: radiance, guides: guides, ms: ms, device: live.length + " x " + live[0].device.getInfo(webcl.DEVICE_NAME), tiles: tiles.map((t) => (t ? [t.row0, t.nrows] : [0, 0])), routes: routes, peerAccess: peers };
+  let denoised;
+  if (opt.denoise) {
+    denoised = { pixel: new Uint8ClampedArray(npix * 4), filtered: new Float32Array(npix * 4) };
+    q0.enqueueReadBuffer(filPix, true, 0, npix * 4, denoised.pixel, []);
+    q0.enqueueReadBuffer(fil, true, 0, npix * 16, denoised.filtered, []);
+    q0.finish();
+  }
+  const res = { pixel: pixel, radiance: radiance, guides: guides, denoised: denoised, ms: ms, device: live.length + " x " + live[0].device.getInfo(webcl.DEVICE_NAME), tiles: tiles.map((t) => (t ? [t.row0, t.nrows] : [0, 0])), routes: routes, peerAccess: peers };
   live.forEach((t) => t.release());
   group.release();
   return res;
@@ -438,7 +472,7 @@ function renderFile(file, width, height, rpp, passes, opt) {
     try { return renderTiled(packed, opt.gpus, passes, opt); } finally { if (ownCtx) ownCtx.release(); }
   }
   if (opt.everyPass && !opt.passesInOneLaunch) throw new Error("--every-pass writes the frames of passes in one launch: give --passes-in-one-launch too");
-  if (opt.guides && opt.granular) throw new Error("--guides are the fused host's (mirt_render_guides): not with the kernel-by-kernel host");
+  if ((opt.guides || opt.denoise) && opt.granular) throw new Error("--guides and --denoise are the fused host's (mirt_render_guides, mirt_filter_atrous): not with the kernel-by-kernel host");
   if (opt.passesInOneLaunch && opt.granular) throw new Error("passes in one launch are the fused pass's (mirt_render_passes): not with the kernel-by-kernel host");
   const R = opt.granular ? new GranularRenderer(packed, opt) : new FusedRenderer(packed, opt);
   R.q.timerStart();
@@ -449,6 +483,7 @@ function renderFile(file, width, height, rpp, passes, opt) {
                 device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: R.ctx.fusedPasses ? R.ctx.fusedPasses() : 0 };
   if (opt.everyPass) res.frames = R.readFrames();
   if (opt.guides) { R.renderGuides(); res.guides = R.readGuides(); }
+  if (opt.denoise) { R.denoise(opt.denoise, !!opt.guides); res.denoised = R.readDenoised(); }
   R.release();
   if (ownCtx) ownCtx.release();
   return res;

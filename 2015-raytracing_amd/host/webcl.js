@@ -13,7 +13,7 @@
 //   queue.enqueueWriteBuffer / enqueueReadBuffer / enqueueNDRangeKernel / finish  :1095-1096, 1153, 1532-1533
 //   release() on everything                                            :1539-1552
 // plus extensions: queue.renderPass(desc), the whole executeRender() in one fused launch; queue.renderGuides(desc, normalHits, albedoDepth), the
-// first-hit guide buffers of the same descriptor; webcl.createDeviceGroup(devices), N contexts
+// first-hit guide buffers of the same descriptor; queue.filterFrame(desc), the a-trous filter those guides drive; webcl.createDeviceGroup(devices), N contexts
 // in this one process with group.gather() to assemble row tiles on one device (RCCL); queue.gridBuild*, capture / launchGraph.
 //
 // There is no OpenCL compiler behind createProgram(): the kernels are built-in HIP code, looked
@@ -51,6 +51,9 @@ function wrap(f) {  // native errors -> WebCL-style exceptions
 }
 
 const MAX_PASSES_PER_CALL = 64;   // MIRT_MAX_PASSES_PER_CALL (include/mirt.h)
+
+// MIRT_FILTER_DEFAULT_* (include/mirt.h): the shipped parameters of queue.filterFrame
+const FILTER_DEFAULTS = { iterations: 3, normalPowerLog2: 5, sigmaDepth: 0.1, sigmaColour: 1.0, demodulate: true };
 
 const C = {
   // values follow the OpenCL 1.1 / WebCL 1.0 enumerants
@@ -183,6 +186,20 @@ class WebCLCommandQueue {
   renderGuides(desc, normalHits, albedoDepth) {
     const d = this._passDesc(desc);
     wrap(() => native().renderGuides(this.ctx.h, d, normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
+  }
+  // ---- extension: the edge-avoiding a-trous filter of a frame on the device (mirt_filter_atrous; include/mirt.h has the definition).  desc:
+  // {width, height, tone: 1 / (raysPerPixel * passes), radiance, normalHits, albedoDepth, filtered?, pixel?} plus any of iterations,
+  // normalPowerLog2, sigmaDepth, sigmaColour, demodulate (webcl.FILTER_DEFAULTS where left out) and structure ("direct" | "tiled": one kernel
+  // structure for every step, for measurement).  radiance as a pass writes it, the guides as renderGuides writes them; filtered: float4 per pixel,
+  // un-scaled like radiance; pixel: RGBA8.  Either output may be left out, not both.  The frame is filtered whole: gather row tiles first.
+  filterFrame(desc) {
+    const v = Object.assign({}, FILTER_DEFAULTS);
+    for (const k of Object.keys(FILTER_DEFAULTS)) if (desc[k] !== undefined && desc[k] !== null) v[k] = desc[k];
+    const h = (b) => (b ? b.h : undefined);
+    const d = { width: desc.width, height: desc.height, iterations: v.iterations, normalPowerLog2: v.normalPowerLog2, sigmaDepth: v.sigmaDepth,
+                sigmaColour: v.sigmaColour, tone: Math.fround(desc.tone), flags: (v.demodulate ? 1 : 0) | ({ direct: 2, tiled: 4 }[desc.structure] || 0),
+                radiance: h(desc.radiance), normalHits: h(desc.normalHits), albedoDepth: h(desc.albedoDepth), filtered: h(desc.filtered), pixel: h(desc.pixel) };
+    wrap(() => native().filterAtrous(this.ctx.h, d));
   }
   // ---- extension: a whole Assign04 / Assign07 frame in one launch (mirt_render_frame): initTrace and the trace kernel(s) on one thread per pixel,
   // no ray buffer unless desc.rays is given.  desc: {assign, width, height, cam, bounds, nSlabs, pixel, rays?} plus the mesh {tSize, tPos, tNormal,
@@ -345,6 +362,7 @@ const webcl = Object.assign({
     return c;
   },
   createDeviceGroup(devices) { return new WebCLDeviceGroup(devices); },
+  FILTER_DEFAULTS,
 }, C);
 
 // `window.WebCL` is only tested for existence by the reference (A10 code.js:468); `webcl` is the entry object.

@@ -65,10 +65,20 @@ class _FrameDesc(C.Structure):   # mirt_frame_desc
                 ("t_slab_size", C.c_void_p), ("s_slab_size", C.c_void_p), ("pixel", C.c_void_p), ("rays", C.c_void_p)]
 
 
+class _FilterDesc(C.Structure):   # mirt_filter_desc
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("normal_power_log2", C.c_uint32), ("tone", C.c_float), ("sigma_depth", C.c_float), ("sigma_colour", C.c_float),
+                ("radiance", C.c_void_p), ("normal_hits", C.c_void_p), ("albedo_depth", C.c_void_p), ("filtered", C.c_void_p), ("pixel", C.c_void_p)]
+
+
 _lib = None
 
 PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
 PASSES_EVERY_FRAME = 2   # MIRT_PASSES_EVERY_FRAME (include/mirt.h)
+
+FILTER_DEMODULATE, FILTER_DIRECT, FILTER_TILED = 1, 2, 4   # MIRT_FILTER_* (include/mirt.h)
+# MIRT_FILTER_DEFAULT_*: the shipped parameters of the a-trous filter (with FILTER_DEMODULATE)
+FILTER_DEFAULTS = {"iterations": 3, "normal_power_log2": 5, "sigma_depth": 0.1, "sigma_colour": 1.0, "demodulate": True}
 
 # name -> (restype, argtypes): every symbol include/mirt.h declares
 SYMBOLS = {
@@ -101,6 +111,7 @@ SYMBOLS = {
     "mirt_render_first_pass": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc)]),
     "mirt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32]),
     "mirt_render_guides": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
+    "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_ctx_set_exact_only": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_set_fusion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -453,6 +464,26 @@ class Context:
         """First-hit guide buffers of desc's row tile (mirt_render_guides): float4 per pixel, (sum of the hit samples' normals, hits) and
         (sum of their material colours, sum of their hit distances).  Either buffer may be None, not both; desc.seeds / acu are not touched."""
         self._chk(lib().mirt_render_guides(self.h, C.byref(desc), normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
+    def filter_atrous(self, width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,
+                      normal_power_log2=None, sigma_depth=None, sigma_colour=None, demodulate=None, structure=None):
+        """The edge-avoiding a-trous filter (mirt_filter_atrous, defined in include/mirt.h) of a width x height frame on the device: radiance as a
+        pass writes it, the guides as render_guides writes them, tone = 1 / (rays_per_pixel * passes).  Writes `filtered` (float4 per pixel,
+        un-scaled like radiance) and / or `pixel` (RGBA8).  Parameters left None are FILTER_DEFAULTS; structure: None (the measured choice per
+        step), "direct" or "tiled"."""
+        v = dict(FILTER_DEFAULTS)
+        for k, x in (("iterations", iterations), ("normal_power_log2", normal_power_log2), ("sigma_depth", sigma_depth), ("sigma_colour", sigma_colour),
+                     ("demodulate", demodulate)):
+            if x is not None:
+                v[k] = x
+        d = _FilterDesc()
+        d.struct_size = C.sizeof(_FilterDesc)
+        d.width, d.height, d.iterations, d.normal_power_log2 = int(width), int(height), int(v["iterations"]), int(v["normal_power_log2"])
+        d.flags = (FILTER_DEMODULATE if v["demodulate"] else 0) | {None: 0, "direct": FILTER_DIRECT, "tiled": FILTER_TILED}[structure]
+        d.tone, d.sigma_depth, d.sigma_colour = float(tone), float(v["sigma_depth"]), float(v["sigma_colour"])
+        d.radiance, d.normal_hits, d.albedo_depth = (b.h if b else None for b in (radiance, normal_hits, albedo_depth))
+        d.filtered, d.pixel = (filtered.h if filtered else None), (pixel.h if pixel else None)
+        self._chk(lib().mirt_filter_atrous(self.h, C.byref(d)))
 
     def destroy(self):
         if self.h:

@@ -278,6 +278,27 @@ class FusedRenderer:
             nh.release()
             ad.release()
 
+    def denoised(self, **params):
+        """The a-trous-filtered frame (mirt_filter_atrous) of this renderer's current radiance: the guides of its tile (mirt_render_guides, as
+        guides() renders them), then the filter, all on the device.  tone is 1 / (rays_per_pixel * passes rendered so far).  params:
+        iterations, normal_power_log2, sigma_depth, sigma_colour, demodulate, structure (mirt.FILTER_DEFAULTS where left out).  Returns
+        (pixel [pixels, 4] uint8, filtered [pixels, 4] float32, un-scaled like radiance).  A renderer of a row tile filters its tile alone: a
+        tiled frame is gathered first and filtered whole (include/mirt.h)."""
+        if self.radiance is None or self.passes < 2:
+            raise mirt.MirtError(-1, "FusedRenderer.denoised: needs want_radiance and at least one rendered pass")
+        if not self.npix:
+            return np.zeros((0, 4), np.uint8), np.zeros((0, 4), np.float32)
+        nh, ad = self.ctx.buffer(self.npix * 16), self.ctx.buffer(self.npix * 16)
+        out, pix = self.ctx.buffer(self.npix * 16), self.ctx.buffer(self.npix * 4)
+        try:
+            self.ctx.render_guides(self.dev.pass_desc(None, None, row0=self.row0, nrows=self.nrows), nh, ad)
+            tone = np.float32(1.0 / (self.s.rpp * (self.passes - 1)))
+            self.ctx.filter_atrous(self.s.width, self.nrows, tone, self.radiance, nh, ad, filtered=out, pixel=pix, **params)
+            return pix.read(np.uint8).reshape(-1, 4), out.read(np.float32).reshape(-1, 4)
+        finally:
+            for b in (nh, ad, out, pix):
+                b.release()
+
     def _frames(self, name, nbytes):
         """a frame buffer of at least nbytes, kept for the next call"""
         b = getattr(self, name, None)

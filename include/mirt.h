@@ -244,6 +244,70 @@ MIRT_API int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* desc, uint3
  * (code.cl:429) and is refused (MIRT_E_ARG).  Ray ids are global: a tile's guides equal the same rows of the whole frame's.  Not while capturing
  * (MIRT_E_ARG).  MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
 MIRT_API int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* desc, mirt_buf* normal_hits, mirt_buf* albedo_depth);
+/* Edge-avoiding A-TROUS FILTER of a few-rays-per-pixel frame, guided by the first-hit guide buffers: `radiance` as a pass writes it (un-scaled
+ * sums), `normal_hits` and `albedo_depth` as mirt_render_guides writes them, all float4 per pixel of a width x height image -- a whole frame, or a
+ * gathered one.  Everything stays on the device; the working images live in the context's scratch buffer.
+ *
+ * DEFINITION.  Every operation below is ONE fp32 operation rounded on its own, in the order written; nothing is a fused multiply-add; every `/`
+ * is the correctly rounded fp32 quotient; max(a, b) is v_max_f32 (a NaN loses).  R = radiance, (N, hits) = normal_hits, (A, D) = albedo_depth.
+ *   Per pixel p:   p is LIVE iff hits > 0.  For a live p: r = 1 / hits, n^ = N * r, z = D * r, a = A * r.
+ *                  I_0 = R.xyz.  With MIRT_FILTER_DEMODULATE, for a live p and per channel c: I_0.c = R.c / a.c where a.c > 0; elsewhere the
+ *                  channel is left alone and a.c counts as 1 on the way back.
+ *   A pixel that is not live (background) keeps I_0 through every iteration and is never a tap.
+ *   Iteration i = 0 .. iterations - 1, step s = 2^i, live p:
+ *     the centre first:  sumw = 0.140625, sumc = I_i(p) * 0.140625   (the B3 spline h = (1/16, 1/4, 3/8, 1/4, 1/16): exactly h[0]^2; no edge
+ *                        term is evaluated for the centre)
+ *     the other 24 taps q = p + s * (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner; a tap outside [0, width) x [0, height) or not live is
+ *     skipped; otherwise
+ *       k  = h[|dy|] * h[|dx|]
+ *       dn = max(0, (n^p.x * n^q.x + n^p.y * n^q.y) + n^p.z * n^q.z);  wn = dn squared normal_power_log2 times
+ *       wz = max(0, 1 - |zp - zq| * izp),  izp = 1 / (sigma_depth * zp) once per centre pixel;          wz = 1 when the term is off
+ *       e  = (I_i(p) - I_i(q)) * tone per channel,  c = (e.x * e.x + e.y * e.y) + e.z * e.z,
+ *       wc = max(0, 1 - c * inv_i),  inv_i = 1 / (k_i * k_i), k_i = sigma_colour * 2^-i (on the host, IEEE fp32);   wc = 1 when the term is off
+ *       w  = ((k * wn) * wz) * wc
+ *       only when w > 0 (false for a NaN):  sumw += w,  sumc += I_i(q) * w per channel
+ *     I_{i+1}(p) = sumc / sumw per channel.
+ *   End: out = I_n, per channel times a.c where the pixel was demodulated by it.  filtered = (out.xyz, R.w).  pixel = copyToPixel's own tone map
+ *   (A10 code.cl:1381-1385): clamp((out * (255 * tone)) * 1.8, 0, 255) converted like the pass's (truncate, NaN -> 0), alpha 255.
+ * A term is OFF when its sigma is <= 0, NaN or infinite.  `tone` is the float m copyToPixel takes, 1 / (rays_per_pixel * passes).
+ * What follows: with iterations == 0 and no DEMODULATE, filtered == radiance bit for bit and pixel == the pixel buffer the pass itself wrote;
+ * with the colour term on, a NaN or infinite pixel stays where it is and does not spread (its c is not a number below 1, so it is nobody's tap and has none);
+ * background pixels come out as they went in.  libmirt.so and libmirt_default.so give the same bits: the reference has no filter, there is one
+ * contract (csrc/pt_kernels_filter.hip says how the quotients are formed).
+ * The filter has NO TILES and no halo exchange: rows near a tile border need the neighbour's rows, so filtering row tiles separately gives a
+ * different picture within 2 * (2^iterations - 1) rows of a border.  With N devices, gather radiance and both guides to one context and filter there.
+ * Checks, nothing is written when one fails.  MIRT_E_ARG: struct_size, width or height 0 or above 65535, iterations > MIRT_FILTER_MAX_ITERATIONS,
+ * normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2, tone not finite or <= 0, unknown flags or both structure flags, both outputs NULL, an
+ * output that is (or overlaps) an input or the other output, a call while capturing.  MIRT_E_RANGE: a buffer smaller than width * height elements.
+ * MIRT_E_HANDLE: a bad context or buffer.  The call observes device state: a held command stream (mirt_ctx_set_fusion, frame fusion) is flushed first.
+ * MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
+#define MIRT_FILTER_DEMODULATE 1u       /* filter radiance / albedo and multiply the albedo back: texture and colour borders stay sharp   */
+/* An iteration runs as one of two kernels with identical results -- one thread per pixel reading its taps through the caches, or LDS tiles of
+ * the step's sub-lattice -- chosen per step size from measurements.  These force one for every step: for measurement. */
+#define MIRT_FILTER_DIRECT 2u
+#define MIRT_FILTER_TILED 4u
+#define MIRT_FILTER_MAX_ITERATIONS 5u
+#define MIRT_FILTER_MAX_NORMAL_POWER_LOG2 7u
+/* the parameters the hosts ship as defaults (Python Context.filter_atrous, Node queue.filterFrame, cli.js --denoise), with MIRT_FILTER_DEMODULATE */
+#define MIRT_FILTER_DEFAULT_ITERATIONS 3u
+#define MIRT_FILTER_DEFAULT_NORMAL_POWER_LOG2 5u
+#define MIRT_FILTER_DEFAULT_SIGMA_DEPTH 0.1f
+#define MIRT_FILTER_DEFAULT_SIGMA_COLOUR 1.0f
+typedef struct mirt_filter_desc {
+    uint32_t struct_size;           /* sizeof(mirt_filter_desc)                                    */
+    uint32_t width, height;         /* of the buffers the caller holds                             */
+    uint32_t iterations;            /* 0 .. 5; iteration i uses step 2^i                           */
+    uint32_t flags;                 /* MIRT_FILTER_*                                               */
+    uint32_t normal_power_log2;     /* 0 .. 7                                                      */
+    float tone;                     /* 1 / (rays_per_pixel * passes)                               */
+    float sigma_depth, sigma_colour;/* <= 0, NaN or inf: that term is off                          */
+    mirt_buf* radiance;             /* in:  float4 per pixel                                       */
+    mirt_buf* normal_hits;          /* in:  float4 per pixel                                       */
+    mirt_buf* albedo_depth;         /* in:  float4 per pixel                                       */
+    mirt_buf* filtered;             /* out: float4 per pixel, un-scaled like radiance; may be NULL */
+    mirt_buf* pixel;                /* out: uchar4 per pixel; may be NULL (not both)               */
+} mirt_filter_desc;
+MIRT_API int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* desc);
 /* Two ways to run the pass, identical results.  Default: the optimistic pair -- a kernel whose divisions are 3-operation
  * forms proven bit-exact inside a guard window (exhaustively, on the device: profiles/r1_divcheck_exhaustive.txt), plus the
  * exact kernel re-running the samples whose rays left the window (NaN rays, axis-parallel directions, ...); it needs every
