@@ -49,6 +49,11 @@ class Frame:
         self.assign, self.width, self.height = int(d["assign"]), int(d["width"]), int(d["height"])
         self.cam = np.asarray(d["cam"], np.float32)
         self.mol = "atoms" in d                                   # A07 molecule mode (parsePDB + splitMolData + molTrace)
+        self.both = None                                          # both models: the mesh job's fields, the molecule's packing under "mol"
+        if isinstance(d.get("mol"), dict):
+            m = d["mol"]
+            self.both = dict(s_size=int(m["s_size"]), atoms=np.asarray(m["atoms"], np.float32), mindex=np.asarray(m["mindex"], np.uint32),
+                             mcolor=np.asarray(m["mcolor"], np.float32), slab_size=np.asarray(m["slab_size"], np.uint32))
         if self.mol:
             self.bounds = np.asarray(d["bounds"], np.float32)
             self.s_size = int(d["s_size"])
@@ -93,6 +98,28 @@ def run_frame(kind, fr):
         f(_p(pixels), cp, _p(rays), bp, gx, gy)
         f = getattr(lib, pre + "meshTrace"); f.argtypes = [vp, fp, vp, u, vp, vp, vp, vp, fp, u, vp, sz, sz]; f.restype = None
         f(_p(pixels), cp, _p(rays), fr.t_size, _p(fr.pos), _p(fr.normal), _p(fr.mindex), _p(fr.mcolor), bp, fr.n_slabs, _p(fr.slab_size), gx, gy)
+    return pixels, rays
+
+
+def run_frame_both(kind, fr):
+    """The both-models frame of Assign07 (computeBoth, A07 code.js:629-661): initTrace, molTrace, meshTrace in that order on the same pixels and
+    rays.  fr: a mesh job that carries the molecule's packing under "mol" (Frame.both).  Returns (pixels uint8 [H*W,4], rays structured [H*W])."""
+    assert fr.assign == 7 and fr.both is not None and not fr.mol
+    lib, pre = _lib(kind, 7)
+    w, h = fr.width, fr.height
+    gx, gy = A._ceil(w, 8), A._ceil(h, 8)
+    pixels = np.zeros((w * h, 4), np.uint8)
+    rays = np.zeros(w * h, A.RAY_DT)
+    cp, _c = _f(fr.cam)
+    bp, _b = _f(fr.bounds)
+    m = fr.both
+    sz, vp, fp, u = C.c_size_t, C.c_void_p, C.POINTER(C.c_float), C.c_uint
+    f = getattr(lib, pre + "initTrace"); f.argtypes = [vp, fp, vp, fp, sz, sz]; f.restype = None
+    f(_p(pixels), cp, _p(rays), bp, gx, gy)
+    f = getattr(lib, pre + "molTrace"); f.argtypes = [vp, fp, vp, u, vp, vp, vp, fp, u, vp, sz, sz]; f.restype = None
+    f(_p(pixels), cp, _p(rays), m["s_size"], _p(m["atoms"]), _p(m["mindex"]), _p(m["mcolor"]), bp, fr.n_slabs, _p(m["slab_size"]), gx, gy)
+    f = getattr(lib, pre + "meshTrace"); f.argtypes = [vp, fp, vp, u, vp, vp, vp, vp, fp, u, vp, sz, sz]; f.restype = None
+    f(_p(pixels), cp, _p(rays), fr.t_size, _p(fr.pos), _p(fr.normal), _p(fr.mindex), _p(fr.mcolor), bp, fr.n_slabs, _p(fr.slab_size), gx, gy)
     return pixels, rays
 
 
