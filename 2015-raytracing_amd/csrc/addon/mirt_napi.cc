@@ -409,6 +409,36 @@ napi_value FilterAtrous(napi_env env, napi_callback_info info) {
     return undef(env);
 }
 
+// upsampleGuided(ctx, {width,height,factor,flags,normalPowerLog2,tone,sigmaDepth, radianceLo,normalHitsLo,albedoDepthLo, normalHits,albedoDepth,
+// upsampled?,pixel?}): guide-driven upsampling of a frame shaded at 1/factor resolution (mirt_upsample_guided); a number left out is 0, a buffer
+// left out NULL -- the library checks them all
+napi_value UpsampleGuided(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "upsampleGuided(ctx, desc)");
+    napi_value d = argv[1];
+    mirt_upsample_desc u;
+    memset(&u, 0, sizeof u);
+    u.struct_size = sizeof u;
+    prop_u32(env, d, "width", &u.width);
+    prop_u32(env, d, "height", &u.height);
+    prop_u32(env, d, "factor", &u.factor);
+    prop_u32(env, d, "flags", &u.flags);
+    prop_u32(env, d, "normalPowerLog2", &u.normal_power_log2);
+    prop_f32(env, d, "tone", &u.tone);
+    prop_f32(env, d, "sigmaDepth", &u.sigma_depth);
+    u.radiance_lo = prop_buf(env, d, "radianceLo");
+    u.normal_hits_lo = prop_buf(env, d, "normalHitsLo");
+    u.albedo_depth_lo = prop_buf(env, d, "albedoDepthLo");
+    u.normal_hits = prop_buf(env, d, "normalHits");
+    u.albedo_depth = prop_buf(env, d, "albedoDepth");
+    u.upsampled = prop_buf(env, d, "upsampled");
+    u.pixel = prop_buf(env, d, "pixel");
+    const int rc = mirt_upsample_guided((mirt_ctx*)c, &u);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+
 // renderFrame(ctx, {assign,width,height,cam,bounds?,nSlabs?, tSize?,tPos?,tNormal?,tMindex?,tMcolor?,tSlabSize?, sSize?,sAtoms?,sMindex?,sMcolor?,sSlabSize?,
 //                   pixel, rays?}): a whole Assign04 / Assign07 frame in one launch (mirt_render_frame)
 napi_value RenderFrame(napi_env env, napi_callback_info info) {
@@ -697,7 +727,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"filterAtrous", FilterAtrous}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

@@ -8,6 +8,7 @@
 #include "../../include/mirt.h"
 #include "pt_launch.hpp"
 #include "pt_stream_match.hpp"
+#include "pt_upsample_taps.hpp"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -1598,6 +1599,67 @@ int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* d) try {
     if (d->pixel) d->pixel->version++;
     return MIRT_OK;
 } MIRT_CATCH("mirt_filter_atrous", return MIRT_E_DEVICE)
+
+// Guide-driven upsampling (pt_kernels_upsample.hip; defined in include/mirt.h): every check first, then one launch.  No working memory.
+int mirt_upsample_guided(mirt_ctx* ctx, const mirt_upsample_desc* d) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_upsample_guided: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_upsample_guided");
+    if (!d || d->struct_size != sizeof(mirt_upsample_desc)) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: descriptor size mismatch");
+    if (!d->width || !d->height) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: empty image");
+    if (d->width > 65535u || d->height > 65535u) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: %ux%u is more than 65535 pixels a side", d->width, d->height);
+    if (!pt::upsample_factor_ok(d->factor))
+        return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: factor %u is outside %u .. %u", d->factor, MIRT_UPSAMPLE_MIN_FACTOR, MIRT_UPSAMPLE_MAX_FACTOR);
+    const uint32_t wl = pt::upsample_low_extent(d->width, d->factor), hl = pt::upsample_low_extent(d->height, d->factor);
+    if (!wl || !hl)
+        return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: %ux%u is not a multiple of factor %u (the two images would not show the same frustum)", d->width, d->height, d->factor);
+    if (d->normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2)
+        return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: normal_power_log2 %u > %u", d->normal_power_log2, MIRT_FILTER_MAX_NORMAL_POWER_LOG2);
+    if (!(std::isfinite(d->tone) && d->tone > 0.0f)) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: tone %g is not a finite positive factor", (double)d->tone);
+    if (d->flags & ~MIRT_UPSAMPLE_DEMODULATE) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: unknown flags 0x%x", d->flags);
+    if (!d->upsampled && !d->pixel) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: upsampled and pixel are both NULL (either may be, not both)");
+    const uint64_t npix = (uint64_t)d->width * d->height, nlo = (uint64_t)wl * hl;
+    int rc;
+    if ((rc = need(ctx, "mirt_upsample_guided radiance_lo", d->radiance_lo, nlo * 16))) return rc;
+    if ((rc = need(ctx, "mirt_upsample_guided normal_hits_lo", d->normal_hits_lo, nlo * 16))) return rc;
+    if ((rc = need(ctx, "mirt_upsample_guided albedo_depth_lo", d->albedo_depth_lo, nlo * 16))) return rc;
+    if ((rc = need(ctx, "mirt_upsample_guided normal_hits", d->normal_hits, npix * 16))) return rc;
+    if ((rc = need(ctx, "mirt_upsample_guided albedo_depth", d->albedo_depth, npix * 16))) return rc;
+    if (d->upsampled && (rc = need(ctx, "mirt_upsample_guided upsampled", d->upsampled, npix * 16))) return rc;
+    if (d->pixel && (rc = need(ctx, "mirt_upsample_guided pixel", d->pixel, npix * 4))) return rc;
+    {   // an output is read by nobody and no input is written: the same handle, or (wrapped memory) the same bytes, twice is refused
+        const mirt_buf* const in[5] = {d->radiance_lo, d->normal_hits_lo, d->albedo_depth_lo, d->normal_hits, d->albedo_depth};
+        const uint64_t in_bytes[5] = {nlo * 16, nlo * 16, nlo * 16, npix * 16, npix * 16};
+        const mirt_buf* const out[2] = {d->upsampled, d->pixel};
+        const uint64_t out_bytes[2] = {npix * 16, npix * 4};
+        auto overlap = [](const mirt_buf* a, uint64_t na, const mirt_buf* b, uint64_t nb) {
+            return a == b || ((const char*)a->ptr < (const char*)b->ptr + nb && (const char*)b->ptr < (const char*)a->ptr + na);
+        };
+        for (int o = 0; o < 2; ++o) {
+            if (!out[o]) continue;
+            for (int i = 0; i < 5; ++i)
+                if (overlap(out[o], out_bytes[o], in[i], in_bytes[i])) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: an output aliases an input");
+        }
+        if (out[0] && out[1] && overlap(out[0], out_bytes[0], out[1], out_bytes[1])) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: upsampled aliases pixel");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::UpsampleArgs A;
+    memset(&A, 0, sizeof A);
+    A.width = d->width; A.height = d->height; A.factor = d->factor;
+    A.demodulate = (d->flags & MIRT_UPSAMPLE_DEMODULATE) ? 1u : 0u;
+    A.npow = d->normal_power_log2;
+    A.depth_on = std::isfinite(d->sigma_depth) && d->sigma_depth > 0.0f;
+    A.tone = d->tone; A.sigma_depth = d->sigma_depth;
+    A.radiance_lo = d->radiance_lo->ptr; A.normal_hits_lo = d->normal_hits_lo->ptr; A.albedo_depth_lo = d->albedo_depth_lo->ptr;
+    A.normal_hits = d->normal_hits->ptr; A.albedo_depth = d->albedo_depth->ptr;
+    A.upsampled = d->upsampled ? d->upsampled->ptr : nullptr;
+    A.pixel = d->pixel ? d->pixel->ptr : nullptr;
+    pt::launch_upsample(ctx->stream, A);
+    HIPCHK(ctx, hipGetLastError());
+    if (d->upsampled) d->upsampled->version++;
+    if (d->pixel) d->pixel->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_upsample_guided", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_fusion(mirt_ctx* ctx, int level) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_fusion: unknown context");

@@ -155,6 +155,25 @@ void launch_filterStep(hipStream_t s, const FilterArgs& a, uint32_t src, uint32_
 // which structure an iteration of step 2^step_log2 runs as unless the caller forces one: bit step_log2 set = tiled.  Measured at 1080p
 // (profiles/filter/timing.json, step_direct_ms against step_tiled_ms): the LDS tiles win at steps 1 and 2, direct reads at 4, 8 and 16.
 constexpr uint32_t kFilterTiledSteps = 0x03u;
+// Guide-driven upsampling (pt_kernels_upsample.hip; the definition is mirt_upsample_guided's comment in include/mirt.h): a frame shaded at
+// (width / factor) x (height / factor) rebuilt at width x height from the guides of both resolutions.  The caller has checked every extent: the
+// three low inputs hold (width / factor) * (height / factor) float4, the high guides and outputs width * height elements, factor divides both sizes.
+struct UpsampleArgs {
+    uint32_t width, height;      // HIGH resolution
+    uint32_t factor;             // 2 .. 4
+    uint32_t demodulate;         // MIRT_UPSAMPLE_DEMODULATE
+    uint32_t npow;               // normal_power_log2
+    uint32_t depth_on;
+    float tone, sigma_depth;
+    const void* radiance_lo;     // float4 per low pixel
+    const void* normal_hits_lo;
+    const void* albedo_depth_lo;
+    const void* normal_hits;     // float4 per high pixel
+    const void* albedo_depth;
+    void* upsampled;             // float4 per high pixel, or null
+    void* pixel;                 // uchar4 per high pixel, or null
+};
+void launch_upsample(hipStream_t s, const UpsampleArgs& a);
 // {p0,e1,e2,n} records from the host's 3 x float4 position buffer (see pt_kernels_fused.hip); `out` holds count records of 48 B,
 // behind them ceil(count / kTriGroup) float4 {centre, R'^2}: the bounding spheres of groups of consecutive records, and behind those, for
 // count <= kLdsTriMax, the candidate sweep's plane list (GridArgs::pnorm)

@@ -1,8 +1,8 @@
 #!/usr/bin/env node
 // host/cli.js -- command-line front end of the JavaScript host.
 //   node cli.js pack   <scene.xml> <width> <height> <raysPerPixel>                 -> packed kernel inputs as JSON (stdout)
-//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]] [--guides PREFIX] [--denoise [iterations]]
-//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums
+//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]] [--guides PREFIX] [--denoise [iterations]] [--upscale F]
+//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
@@ -53,6 +53,28 @@ if (cmd === "pack") {
   }
   if ((i = rest.indexOf("--seeds")) >= 0) { const b = fs.readFileSync(rest[i + 1]); opt.seeds = new Int32Array(b.buffer, b.byteOffset, b.length / 4); }
   const [file, w, h, rpp, passes, out] = [rest[0], +rest[1], +rest[2], +rest[3], +rest[4], rest[5]];
+  let upscale = 0;
+  if ((i = rest.indexOf("--upscale")) >= 0) {   // shade at 1/F resolution, output at full (mirt_upsample_guided); one context: the upsampler has no tiles
+    if (!/^\d+$/.test(rest[i + 1] || "")) usage();
+    upscale = +rest[i + 1];
+    if (opt.gpus) { process.stderr.write("--upscale is not available with --gpus N: the upsampler, like the filter, wants whole frames on one context, and gathering the low frame and both pairs of guides is not built\n"); process.exit(2); }
+  }
+  if (upscale) {
+    const res = renderer.renderUpscaled(file, w, h, rpp, passes, upscale, opt);
+    const dump = (f, a) => fs.writeFileSync(f, Buffer.from(a.buffer, a.byteOffset, a.byteLength));
+    writeFrame(out, res.pixel, w, h);
+    dump(out + ".upsampled.f32", res.upsampled);
+    dump(out + ".radiance.f32", res.radiance);
+    if (res.denoised) dump(out + ".filtered.f32", res.denoised.filtered);
+    if (opt.guides) {
+      dump(`${opt.guides}.normal_hits.f32`, res.guides.normalHits);
+      dump(`${opt.guides}.albedo_depth.f32`, res.guides.albedoDepth);
+      dump(`${opt.guides}.normal_hits_lo.f32`, res.guidesLo.normalHits);
+      dump(`${opt.guides}.albedo_depth_lo.f32`, res.guidesLo.albedoDepth);
+    }
+    process.stderr.write(`rendered ${file} ${res.lowWidth}x${res.lowHeight} rpp ${rpp}, ${passes} pass(es)${opt.denoise ? ", filtered" : ""}, upsampled x${upscale} to ${w}x${h}: ${res.ms.toFixed(2)} ms on ${res.device}\n`);
+    process.exit(0);
+  }
   const res = renderer.renderFile(file, w, h, rpp, passes, opt);
   writeFrame(out, res.denoised ? res.denoised.pixel : res.pixel, w, h);
   if (res.denoised) fs.writeFileSync(out + ".filtered.f32", Buffer.from(res.denoised.filtered.buffer, res.denoised.filtered.byteOffset, res.denoised.filtered.byteLength));

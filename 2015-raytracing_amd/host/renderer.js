@@ -489,4 +489,46 @@ function renderFile(file, width, height, rpp, passes, opt) {
   return res;
 }
 
-module.exports = { GranularRenderer, FusedRenderer, renderFile, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };
+// Shade at 1/factor resolution, output at full (queue.upsampleFrame, mirt_upsample_guided).  width x height is the OUTPUT size, rpp the rays per
+// LOW pixel.  The scene file is loaded twice -- at (width / factor) x (height / factor), which the fused renderer traces, and at width x height for
+// the camera pack of the full-resolution guides: the camera's window is given in scene space, so both cover the same frustum.  On the device, in
+// order: the passes, the low guides, opt.denoise: the a-trous filter of the low frame, the guides at the output size, the upsampler.  One context
+// and whole frames: the upsampler, like the filter, has no tiles.
+function renderUpscaled(file, width, height, rpp, passes, factor, opt) {
+  opt = opt || {};
+  if (opt.gpus) throw new Error("--upscale is not available with --gpus N: the upsampler, like the filter, wants whole frames on one context, and gathering the low frame and both pairs of guides is not built");
+  if (opt.granular || opt.everyPass || opt.deviceGrid) throw new Error("--upscale drives the fused host on host-built grids: not with --granular, --every-pass or --device-grid");
+  if (!(factor >= 2 && factor <= 4) || factor !== Math.floor(factor)) throw new Error(`--upscale ${factor}: the factor is 2, 3 or 4`);
+  if (width % factor || height % factor) throw new Error(`--upscale ${factor}: ${width}x${height} is not a multiple of the factor (the two images would not show the same frustum)`);
+  const wl = width / factor, hl = height / factor;
+  const lo = scene.packScene(scene.loadSceneFile(file, wl, hl), wl, hl, rpp);
+  const hi = scene.packScene(scene.loadSceneFile(file, width, height), width, height, rpp);
+  const R = new FusedRenderer(lo, opt);
+  const npix = width * height;
+  const mk = (bytes) => R.ctx.createBuffer(webcl.MEM_READ_WRITE, bytes);
+  const nh = mk(npix * 16), ad = mk(npix * 16), up = mk(npix * 16), px = mk(npix * 4);
+  try {
+    R.q.timerStart();
+    if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces);
+    else for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
+    R.renderGuides();
+    if (opt.denoise) R.denoise(opt.denoise, true);
+    R.q.renderGuides(Object.assign(R.passDesc(), { width: width, height: height, row0: 0, nrows: height, cam: hi.cam }), nh, ad);
+    R.q.upsampleFrame(Object.assign({}, opt.upsample, { width: width, height: height, factor: factor, tone: 1 / (rpp * (R.passes - 1)),
+      radianceLo: opt.denoise ? R.filtered : R.radiance, normalHitsLo: R.normalHits, albedoDepthLo: R.albedoDepth, normalHits: nh, albedoDepth: ad,
+      upsampled: up, pixel: px }));
+    const ms = R.q.timerStopMs();
+    const read = (b, a) => { R.q.enqueueReadBuffer(b, true, 0, a.byteLength, a, []); return a; };
+    const res = { pixel: read(px, new Uint8ClampedArray(npix * 4)), upsampled: read(up, new Float32Array(npix * 4)), radiance: R.readRadiance(), ms: ms,
+                  guides: { normalHits: read(nh, new Float32Array(npix * 4)), albedoDepth: read(ad, new Float32Array(npix * 4)) }, guidesLo: R.readGuides(),
+                  device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: 0, lowWidth: wl, lowHeight: hl };
+    if (opt.denoise) res.denoised = R.readDenoised();
+    R.q.finish();
+    return res;
+  } finally {
+    [nh, ad, up, px].forEach((b) => b.release());
+    R.release();
+  }
+}
+
+module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };

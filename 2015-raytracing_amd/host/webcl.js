@@ -13,7 +13,8 @@
 //   queue.enqueueWriteBuffer / enqueueReadBuffer / enqueueNDRangeKernel / finish  :1095-1096, 1153, 1532-1533
 //   release() on everything                                            :1539-1552
 // plus extensions: queue.renderPass(desc), the whole executeRender() in one fused launch; queue.renderGuides(desc, normalHits, albedoDepth), the
-// first-hit guide buffers of the same descriptor; queue.filterFrame(desc), the a-trous filter those guides drive; webcl.createDeviceGroup(devices), N contexts
+// first-hit guide buffers of the same descriptor; queue.filterFrame(desc), the a-trous filter those guides drive; queue.upsampleFrame(desc), a frame
+// shaded at 1/f resolution rebuilt at full resolution from the guides of both; webcl.createDeviceGroup(devices), N contexts
 // in this one process with group.gather() to assemble row tiles on one device (RCCL); queue.gridBuild*, capture / launchGraph.
 //
 // There is no OpenCL compiler behind createProgram(): the kernels are built-in HIP code, looked
@@ -54,6 +55,8 @@ const MAX_PASSES_PER_CALL = 64;   // MIRT_MAX_PASSES_PER_CALL (include/mirt.h)
 
 // MIRT_FILTER_DEFAULT_* (include/mirt.h): the shipped parameters of queue.filterFrame
 const FILTER_DEFAULTS = { iterations: 3, normalPowerLog2: 5, sigmaDepth: 0.1, sigmaColour: 1.0, demodulate: true };
+// MIRT_UPSAMPLE_DEFAULT_* (include/mirt.h): the shipped parameters of queue.upsampleFrame
+const UPSAMPLE_DEFAULTS = { normalPowerLog2: 5, sigmaDepth: 0.1, demodulate: true };
 
 const C = {
   // values follow the OpenCL 1.1 / WebCL 1.0 enumerants
@@ -200,6 +203,21 @@ class WebCLCommandQueue {
                 sigmaColour: v.sigmaColour, tone: Math.fround(desc.tone), flags: (v.demodulate ? 1 : 0) | ({ direct: 2, tiled: 4 }[desc.structure] || 0),
                 radiance: h(desc.radiance), normalHits: h(desc.normalHits), albedoDepth: h(desc.albedoDepth), filtered: h(desc.filtered), pixel: h(desc.pixel) };
     wrap(() => native().filterAtrous(this.ctx.h, d));
+  }
+  // ---- extension: guide-driven upsampling of a frame shaded at 1/factor resolution (mirt_upsample_guided; include/mirt.h has the definition).
+  // desc: {width, height (the OUTPUT size, multiples of factor), factor: 2..4, tone: the low frame's 1 / (raysPerPixel * passes), radianceLo (a pass's
+  // radiance or filterFrame's filtered), normalHitsLo, albedoDepthLo (renderGuides at the low size), normalHits, albedoDepth (renderGuides at the
+  // output size), upsampled?, pixel?} plus any of normalPowerLog2, sigmaDepth, demodulate (webcl.UPSAMPLE_DEFAULTS where left out).  upsampled:
+  // float4 per output pixel, un-scaled like radiance; pixel: RGBA8.  Either output may be left out, not both.  Whole frames: gather row tiles first.
+  upsampleFrame(desc) {
+    const v = Object.assign({}, UPSAMPLE_DEFAULTS);
+    for (const k of Object.keys(UPSAMPLE_DEFAULTS)) if (desc[k] !== undefined && desc[k] !== null) v[k] = desc[k];
+    const h = (b) => (b ? b.h : undefined);
+    const d = { width: desc.width, height: desc.height, factor: desc.factor, normalPowerLog2: v.normalPowerLog2, sigmaDepth: v.sigmaDepth,
+                tone: Math.fround(desc.tone), flags: v.demodulate ? 1 : 0, radianceLo: h(desc.radianceLo), normalHitsLo: h(desc.normalHitsLo),
+                albedoDepthLo: h(desc.albedoDepthLo), normalHits: h(desc.normalHits), albedoDepth: h(desc.albedoDepth), upsampled: h(desc.upsampled),
+                pixel: h(desc.pixel) };
+    wrap(() => native().upsampleGuided(this.ctx.h, d));
   }
   // ---- extension: a whole Assign04 / Assign07 frame in one launch (mirt_render_frame): initTrace and the trace kernel(s) on one thread per pixel,
   // no ray buffer unless desc.rays is given.  desc: {assign, width, height, cam, bounds, nSlabs, pixel, rays?} plus the mesh {tSize, tPos, tNormal,
@@ -363,6 +381,7 @@ const webcl = Object.assign({
   },
   createDeviceGroup(devices) { return new WebCLDeviceGroup(devices); },
   FILTER_DEFAULTS,
+  UPSAMPLE_DEFAULTS,
 }, C);
 
 // `window.WebCL` is only tested for existence by the reference (A10 code.js:468); `webcl` is the entry object.

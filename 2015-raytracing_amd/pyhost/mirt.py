@@ -71,6 +71,13 @@ class _FilterDesc(C.Structure):   # mirt_filter_desc
                 ("radiance", C.c_void_p), ("normal_hits", C.c_void_p), ("albedo_depth", C.c_void_p), ("filtered", C.c_void_p), ("pixel", C.c_void_p)]
 
 
+class _UpsampleDesc(C.Structure):   # mirt_upsample_desc
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("factor", C.c_uint32), ("flags", C.c_uint32),
+                ("normal_power_log2", C.c_uint32), ("tone", C.c_float), ("sigma_depth", C.c_float),
+                ("radiance_lo", C.c_void_p), ("normal_hits_lo", C.c_void_p), ("albedo_depth_lo", C.c_void_p),
+                ("normal_hits", C.c_void_p), ("albedo_depth", C.c_void_p), ("upsampled", C.c_void_p), ("pixel", C.c_void_p)]
+
+
 _lib = None
 
 PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
@@ -79,6 +86,10 @@ PASSES_EVERY_FRAME = 2   # MIRT_PASSES_EVERY_FRAME (include/mirt.h)
 FILTER_DEMODULATE, FILTER_DIRECT, FILTER_TILED = 1, 2, 4   # MIRT_FILTER_* (include/mirt.h)
 # MIRT_FILTER_DEFAULT_*: the shipped parameters of the a-trous filter (with FILTER_DEMODULATE)
 FILTER_DEFAULTS = {"iterations": 3, "normal_power_log2": 5, "sigma_depth": 0.1, "sigma_colour": 1.0, "demodulate": True}
+
+UPSAMPLE_DEMODULATE = 1   # MIRT_UPSAMPLE_DEMODULATE (include/mirt.h)
+# MIRT_UPSAMPLE_DEFAULT_*: the shipped parameters of the guide-driven upsampler (with UPSAMPLE_DEMODULATE)
+UPSAMPLE_DEFAULTS = {"normal_power_log2": 5, "sigma_depth": 0.1, "demodulate": True}
 
 # name -> (restype, argtypes): every symbol include/mirt.h declares
 SYMBOLS = {
@@ -112,6 +123,7 @@ SYMBOLS = {
     "mirt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32]),
     "mirt_render_guides": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
+    "mirt_upsample_guided": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc)]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_ctx_set_exact_only": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_set_fusion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -484,6 +496,26 @@ class Context:
         d.radiance, d.normal_hits, d.albedo_depth = (b.h if b else None for b in (radiance, normal_hits, albedo_depth))
         d.filtered, d.pixel = (filtered.h if filtered else None), (pixel.h if pixel else None)
         self._chk(lib().mirt_filter_atrous(self.h, C.byref(d)))
+
+    def upsample_guided(self, width, height, factor, tone, radiance_lo, normal_hits_lo, albedo_depth_lo, normal_hits, albedo_depth,
+                        upsampled=None, pixel=None, normal_power_log2=None, sigma_depth=None, demodulate=None):
+        """Guide-driven upsampling (mirt_upsample_guided, defined in include/mirt.h) on the device: the radiance of a (width / factor) x
+        (height / factor) frame -- as a pass or filter_atrous wrote it, tone = that frame's 1 / (rays_per_pixel * passes) -- rebuilt at
+        width x height from the guides of both resolutions (render_guides at each size).  Writes `upsampled` (float4 per high pixel, un-scaled
+        like radiance) and / or `pixel` (RGBA8).  Parameters left None are UPSAMPLE_DEFAULTS."""
+        v = dict(UPSAMPLE_DEFAULTS)
+        for k, x in (("normal_power_log2", normal_power_log2), ("sigma_depth", sigma_depth), ("demodulate", demodulate)):
+            if x is not None:
+                v[k] = x
+        d = _UpsampleDesc()
+        d.struct_size = C.sizeof(_UpsampleDesc)
+        d.width, d.height, d.factor, d.normal_power_log2 = int(width), int(height), int(factor), int(v["normal_power_log2"])
+        d.flags = UPSAMPLE_DEMODULATE if v["demodulate"] else 0
+        d.tone, d.sigma_depth = float(tone), float(v["sigma_depth"])
+        d.radiance_lo, d.normal_hits_lo, d.albedo_depth_lo = (b.h if b else None for b in (radiance_lo, normal_hits_lo, albedo_depth_lo))
+        d.normal_hits, d.albedo_depth = (b.h if b else None for b in (normal_hits, albedo_depth))
+        d.upsampled, d.pixel = (upsampled.h if upsampled else None), (pixel.h if pixel else None)
+        self._chk(lib().mirt_upsample_guided(self.h, C.byref(d)))
 
     def destroy(self):
         if self.h:

@@ -316,6 +316,60 @@ class FusedRenderer:
         self.dev.release()
 
 
+class UpscaledRenderer:
+    """Shade at 1/factor resolution, output at full (mirt_upsample_guided): `scene` (a pyhost.scene.PackedScene) names the OUTPUT size W x H and
+    the rays per LOW pixel.  A FusedRenderer traces the same camera at (W / factor) x (H / factor) -- the camera's window is given in scene space,
+    so the frustum is the same -- and render() runs, all on the device: the passes, the low guides, optionally the a-trous filter of the low
+    frame, the guides at W x H, the upsampler.  The buffers of the last render() stay on the device for a caller that wants to read them:
+    lo.radiance, filtered (None without denoise), nh_lo / ad_lo, nh / ad, upsampled, pixel.  Whole frames only: no row tiles."""
+
+    def __init__(self, ctx, scene, factor, seeds=None, seed_base=0):
+        factor = int(factor)
+        if factor < 2 or factor > 4 or scene.width % factor or scene.height % factor:
+            raise mirt.MirtError(-1, f"UpscaledRenderer: {scene.width}x{scene.height} is not a multiple of a factor {factor} in 2 .. 4")
+        self.ctx, self.s, self.factor = ctx, scene, factor
+        self.wl, self.hl = scene.width // factor, scene.height // factor
+        self.lo = FusedRenderer(ctx, scene.resized(self.wl, self.hl, scene.rpp), seeds=seeds, seed_base=seed_base)
+        nlo, n = self.wl * self.hl, scene.width * scene.height
+        self.nh_lo, self.ad_lo, self.filtered = ctx.buffer(nlo * 16), ctx.buffer(nlo * 16), None
+        self.nh, self.ad = ctx.buffer(n * 16), ctx.buffer(n * 16)
+        self.upsampled, self.pixel = ctx.buffer(n * 16), ctx.buffer(n * 4)
+        self.tone = None
+
+    def guides_desc(self):
+        """the low renderer's scene on the device, seen through the camera pack of the output size: what mirt_render_guides reads"""
+        d = self.lo.dev.pass_desc(None, None)
+        d.width, d.height = self.s.width, self.s.height
+        d.cam = mirt._f(self.s.cam, 16)
+        return d
+
+    def render(self, passes=1, bounces=5, denoise=True, filter_params=None, **params):
+        """-> (pixel [W * H, 4] uint8, upsampled [W * H, 4] float32, un-scaled like radiance).  passes: progressive passes of the low frame, added
+        to those already rendered; denoise: filter the low frame first (filter_params: mirt.FILTER_DEFAULTS where left out); params:
+        normal_power_log2, sigma_depth, demodulate of the upsampler (mirt.UPSAMPLE_DEFAULTS where left out)."""
+        ctx, lo = self.ctx, self.lo
+        for _ in range(int(passes)):
+            lo.execute_render(bounces, fresh=(lo.passes == 1))
+        self.tone = np.float32(1.0 / (lo.s.rpp * (lo.passes - 1)))
+        ctx.render_guides(lo.dev.pass_desc(None, None), self.nh_lo, self.ad_lo)
+        radiance = lo.radiance
+        if denoise:
+            if self.filtered is None:
+                self.filtered = ctx.buffer(self.wl * self.hl * 16)
+            ctx.filter_atrous(self.wl, self.hl, self.tone, lo.radiance, self.nh_lo, self.ad_lo, filtered=self.filtered, **(filter_params or {}))
+            radiance = self.filtered
+        ctx.render_guides(self.guides_desc(), self.nh, self.ad)
+        ctx.upsample_guided(self.s.width, self.s.height, self.factor, self.tone, radiance, self.nh_lo, self.ad_lo, self.nh, self.ad,
+                            upsampled=self.upsampled, pixel=self.pixel, **params)
+        return self.pixel.read(np.uint8).reshape(-1, 4), self.upsampled.read(np.float32).reshape(-1, 4)
+
+    def release(self):
+        for b in (self.nh_lo, self.ad_lo, self.filtered, self.nh, self.ad, self.upsampled, self.pixel):
+            if b:
+                b.release()
+        self.lo.release()
+
+
 class FramePacked:
     """Packed inputs of an Assign01 / 04 / 07 frame job (what `node host/cli.js pack-frame` emits)."""
 

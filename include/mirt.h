@@ -308,6 +308,70 @@ typedef struct mirt_filter_desc {
     mirt_buf* pixel;                /* out: uchar4 per pixel; may be NULL (not both)               */
 } mirt_filter_desc;
 MIRT_API int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* desc);
+/* GUIDE-DRIVEN UPSAMPLING: shade at 1/f resolution, output at full.  The radiance of a wl x hl frame, wl = width / factor, hl = height / factor
+ * (`radiance_lo`: what a pass wrote as `radiance` or mirt_filter_atrous as `filtered`, un-scaled sums), is rebuilt at width x height by a
+ * joint-bilateral interpolation of its four nearest low pixels, weighted by the first-hit guides of BOTH resolutions (mirt_render_guides at
+ * wl x hl and at width x height) and re-modulated with the full-resolution albedo, so that geometric and material borders land on full-resolution
+ * pixels.  The camera's window is given in scene space (A10 code.cl:93-98), so the same camera at wl x hl covers the same frustum and low pixel
+ * (X, Y) covers the factor x factor high pixels under it: the sizes must be exact multiples of factor.  The two guide pairs may come from
+ * different ray counts: each is normalised by its own hit count.  `tone` is the low frame's 1 / (rays_per_pixel * passes).
+ *
+ * DEFINITION, in the conventions of mirt_filter_atrous: every operation below is ONE fp32 operation rounded on its own, in the order written;
+ * nothing is a fused multiply-add; every `/` is the correctly rounded fp32 quotient; max(a, b) is v_max_f32 (a NaN loses).  f = factor.
+ *   Per low pixel q:   R_lo = radiance_lo, (N_lo, hits_lo) = normal_hits_lo, (A_lo, D_lo) = albedo_depth_lo.  q is LIVE iff hits_lo > 0; then
+ *                      r = 1 / hits_lo, n^q = N_lo * r, zq = D_lo * r, aq = A_lo * r.  Tap value per channel c: J(q).c = R_lo.c / aq.c where q is
+ *                      live, MIRT_UPSAMPLE_DEMODULATE is set and aq.c > 0; otherwise J(q).c = R_lo.c.
+ *   Per high pixel p = (x, y):   p is LIVE iff hits > 0; then n^p, zp, ap likewise from normal_hits / albedo_depth, and
+ *                      izp = 1 / (sigma_depth * zp).  The depth term is OFF when sigma_depth is <= 0, NaN or infinite.
+ *   Tap geometry, in integers, per axis (csrc/pt_upsample_taps.hpp):  e = 2x + 1 - f;  X0 = floor(e / 2f) (floor: -1 at the left edge);
+ *                      m = e - 2f * X0 in [0, 2f);  tx = (float)m / (float)(2f);  bx[0] = 1 - tx, bx[1] = tx.  The same for y.
+ *   Live p: the taps q = (X0 + i, Y0 + j), j = 0, 1 outer, i = 0, 1 inner; a tap outside the low image or not live is skipped; otherwise
+ *       b  = by[j] * bx[i]
+ *       dn = max(0, (n^p.x * n^q.x + n^p.y * n^q.y) + n^p.z * n^q.z);  wn = dn squared normal_power_log2 times
+ *       wz = max(0, 1 - |zp - zq| * izp);          wz = 1 when the term is off
+ *       w  = (b * wn) * wz
+ *       only when w > 0 (false for a NaN):  sumw += w,  sumc += J(q) * w per channel; both sums start at +0.
+ *   Background p (not live): the same four taps, but only taps that are NOT live count; w = b (counted only when w > 0), tap value R_lo.xyz.
+ *   When sumw > 0:  I = sumc / sumw per channel.
+ *   FALLBACK, for either kind of p, when sumw > 0 is false (a surface the low frame does not have, weights that are all 0 or NaN):
+ *       Q0 = (x div f, y div f);  I = J(Q0) when p and Q0 are both live; otherwise I = R_lo(Q0).xyz and nothing is multiplied back.
+ *   End: for a live p that did not take the raw fallback, per channel: out.c = I.c * ap.c where the flag is set and ap.c > 0; otherwise
+ *   out.c = I.c.  upsampled = (out.xyz, R_lo(Q0).w).  pixel = copyToPixel's own tone map of out, exactly as mirt_filter_atrous's.
+ * What follows, and what does not.  Inside the low image the b of the four taps are those of plain bilinear interpolation between low pixel
+ * centres, clamped at the border (an outside tap is dropped and the division by sumw renormalises).  There is NO colour term here, so a NaN or
+ * infinite low pixel is NOT contained the way the filter contains one: it reaches every high pixel that counts it as a tap (up to (2f)^2 of them),
+ * with the depth term on or off; only `w > 0` keeps a NaN WEIGHT out.  libmirt.so and libmirt_default.so give the same bits: the reference has
+ * no upsampler, there is one contract (csrc/pt_kernels_upsample.hip).
+ * NOT built: row tiles (like the filter, the call wants whole frames: with N devices gather all five inputs to one context first), a footprint
+ * wider than 2 x 2 taps, a colour term, an LDS-tiled structure, sizes that factor does not divide.
+ * Checks, nothing is written when one fails.  MIRT_E_ARG: struct_size, width or height 0 or above 65535, factor outside 2 .. 4, a size that is not
+ * a multiple of factor, normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2, tone not finite or <= 0, unknown flags, both outputs NULL, an
+ * output that is (or overlaps) an input or the other output, a call while capturing.  MIRT_E_RANGE: a buffer smaller than its image.
+ * MIRT_E_HANDLE: a bad context or buffer.  A held command stream (mirt_ctx_set_fusion, frame fusion) is flushed first.
+ * MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
+#define MIRT_UPSAMPLE_DEMODULATE 1u     /* interpolate radiance / albedo of the low frame and multiply the full-resolution albedo back */
+#define MIRT_UPSAMPLE_MIN_FACTOR 2u
+#define MIRT_UPSAMPLE_MAX_FACTOR 4u
+/* the parameters the hosts ship as defaults (Python Context.upsample_guided, Node queue.upsampleFrame, cli.js --upscale), with MIRT_UPSAMPLE_DEMODULATE */
+#define MIRT_UPSAMPLE_DEFAULT_NORMAL_POWER_LOG2 5u
+#define MIRT_UPSAMPLE_DEFAULT_SIGMA_DEPTH 0.1f
+typedef struct mirt_upsample_desc {
+    uint32_t struct_size;           /* sizeof(mirt_upsample_desc)                                          */
+    uint32_t width, height;         /* the HIGH resolution: of normal_hits, albedo_depth and the outputs   */
+    uint32_t factor;                /* 2 .. 4; the low images are (width / factor) x (height / factor)     */
+    uint32_t flags;                 /* MIRT_UPSAMPLE_*                                                     */
+    uint32_t normal_power_log2;     /* 0 .. 7                                                              */
+    float tone;                     /* the low frame's 1 / (rays_per_pixel * passes)                       */
+    float sigma_depth;              /* <= 0, NaN or inf: the depth term is off                             */
+    mirt_buf* radiance_lo;          /* in:  float4 per low pixel                                           */
+    mirt_buf* normal_hits_lo;       /* in:  float4 per low pixel                                           */
+    mirt_buf* albedo_depth_lo;      /* in:  float4 per low pixel                                           */
+    mirt_buf* normal_hits;          /* in:  float4 per high pixel                                          */
+    mirt_buf* albedo_depth;         /* in:  float4 per high pixel                                          */
+    mirt_buf* upsampled;            /* out: float4 per high pixel, un-scaled like radiance; may be NULL    */
+    mirt_buf* pixel;                /* out: uchar4 per high pixel; may be NULL (not both)                  */
+} mirt_upsample_desc;
+MIRT_API int mirt_upsample_guided(mirt_ctx* ctx, const mirt_upsample_desc* desc);
 /* Two ways to run the pass, identical results.  Default: the optimistic pair -- a kernel whose divisions are 3-operation
  * forms proven bit-exact inside a guard window (exhaustively, on the device: profiles/r1_divcheck_exhaustive.txt), plus the
  * exact kernel re-running the samples whose rays left the window (NaN rays, axis-parallel directions, ...); it needs every
