@@ -7,6 +7,7 @@
 // not become an out-of-bounds access on the GPU.
 #include "../../include/mirt.h"
 #include "pt_launch.hpp"
+#include "pt_post_check.hpp"
 #include "pt_stream_match.hpp"
 #include "pt_upsample_taps.hpp"
 
@@ -1529,52 +1530,77 @@ int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_
     return MIRT_OK;
 } MIRT_CATCH("mirt_render_guides", return MIRT_E_DEVICE)
 
+// ---- the post-process stage: mirt_filter_atrous and mirt_upsample_guided.  The argument rules they share are pt_post_check.hpp's (host-only,
+// CPU-tested); here are those rules' messages, `fn` being the entry point's name, and the shared epilogue.
+static_assert(pt::kPostMaxNormalPowerLog2 == MIRT_FILTER_MAX_NORMAL_POWER_LOG2, "pt_post_check.hpp restates the header's limit");
+struct PostBuf { const char* label; mirt_buf* buf; uint64_t bytes; };   // an image of the call: need()'s label, its buffer, the bytes it takes; buf == nullptr: an output not asked for
+
+static int post_check_extent(mirt_ctx* ctx, const char* fn, uint32_t w, uint32_t h) {
+    const pt::PostExtent e = pt::post_extent(w, h);
+    if (e == pt::POST_EXTENT_EMPTY) return fail(ctx, MIRT_E_ARG, "%s: empty image", fn);
+    if (e == pt::POST_EXTENT_TOO_LARGE) return fail(ctx, MIRT_E_ARG, "%s: %ux%u is more than 65535 pixels a side", fn, w, h);
+    return MIRT_OK;
+}
+static int post_check_terms(mirt_ctx* ctx, const char* fn, uint32_t npow, float tone) {
+    if (!pt::post_normal_power_ok(npow)) return fail(ctx, MIRT_E_ARG, "%s: normal_power_log2 %u > %u", fn, npow, MIRT_FILTER_MAX_NORMAL_POWER_LOG2);
+    if (!pt::post_finite_positive(tone)) return fail(ctx, MIRT_E_ARG, "%s: tone %g is not a finite positive factor", fn, (double)tone);
+    return MIRT_OK;
+}
+// b: the N - 2 inputs, then the two outputs, `first` (the first one's name) and pixel.  One of the outputs is given; every buffer given is live,
+// this context's and large enough; an output is read by nobody and no input is written: the same handle, or (wrapped memory) the same bytes,
+// twice is refused.  Nothing is formatted or allocated unless a check fails: a caller that times the call times this too.
+extern "C++" {
+template <size_t N>
+int post_check_buffers(mirt_ctx* ctx, const char* fn, const char* first, const PostBuf (&b)[N]) {
+    if (!b[N - 2].buf && !b[N - 1].buf) return fail(ctx, MIRT_E_ARG, "%s: %s and pixel are both NULL (either may be, not both)", fn, first);
+    pt::PostRange r[N];
+    for (size_t i = 0; i < N; ++i) {
+        r[i] = {0, b[i].bytes, i < N - 2 || b[i].buf != nullptr};
+        if (!r[i].present) continue;
+        if (int rc = need(ctx, b[i].label, b[i].buf, b[i].bytes)) return rc;
+        r[i].addr = (uint64_t)(uintptr_t)b[i].buf->ptr;
+    }
+    const pt::PostAlias alias = pt::post_alias(r, N - 2, r + N - 2, 2);
+    if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: an output aliases an input", fn);
+    if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: %s aliases pixel", fn, first);
+    return MIRT_OK;
+}
+}  // extern "C++"
+// after the launches: their error, and the outputs given have new contents
+static int post_finish(mirt_ctx* ctx, const PostBuf* out) {
+    HIPCHK(ctx, hipGetLastError());
+    for (int o = 0; o < 2; ++o)
+        if (out[o].buf) out[o].buf->version++;
+    return MIRT_OK;
+}
+
 // The a-trous filter (pt_kernels_filter.hip; defined in include/mirt.h): every check first, then the prepare launch and one launch per iteration,
 // the last of which writes the outputs.  The two working images and the prepared guide are three float4 arrays of the context's scratch buffer,
 // asked for ONCE (growing the buffer frees the old one: pt_pass_plan.hpp).
 int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* d) try {
+    static const char fn[] = "mirt_filter_atrous";
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_filter_atrous: unknown context");
     FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_filter_atrous");
+    NOT_WHILE_CAPTURING(ctx, fn);
     if (!d || d->struct_size != sizeof(mirt_filter_desc)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: descriptor size mismatch");
-    if (!d->width || !d->height) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: empty image");
-    if (d->width > 65535u || d->height > 65535u) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: %ux%u is more than 65535 pixels a side", d->width, d->height);
+    int rc;
+    if ((rc = post_check_extent(ctx, fn, d->width, d->height))) return rc;
     if (d->iterations > MIRT_FILTER_MAX_ITERATIONS) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: %u iterations > %u", d->iterations, MIRT_FILTER_MAX_ITERATIONS);
-    if (d->normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2)
-        return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: normal_power_log2 %u > %u", d->normal_power_log2, MIRT_FILTER_MAX_NORMAL_POWER_LOG2);
-    if (!(std::isfinite(d->tone) && d->tone > 0.0f)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: tone %g is not a finite positive factor", (double)d->tone);
+    if ((rc = post_check_terms(ctx, fn, d->normal_power_log2, d->tone))) return rc;
     const uint32_t both = MIRT_FILTER_DIRECT | MIRT_FILTER_TILED;
     if ((d->flags & ~(MIRT_FILTER_DEMODULATE | both)) || (d->flags & both) == both) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: unknown flags 0x%x (or both structures forced)", d->flags);
-    if (!d->filtered && !d->pixel) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: filtered and pixel are both NULL (either may be, not both)");
     const uint64_t npix = (uint64_t)d->width * d->height;
-    int rc;
-    if ((rc = need(ctx, "mirt_filter_atrous radiance", d->radiance, npix * 16))) return rc;
-    if ((rc = need(ctx, "mirt_filter_atrous normal_hits", d->normal_hits, npix * 16))) return rc;
-    if ((rc = need(ctx, "mirt_filter_atrous albedo_depth", d->albedo_depth, npix * 16))) return rc;
-    if (d->filtered && (rc = need(ctx, "mirt_filter_atrous filtered", d->filtered, npix * 16))) return rc;
-    if (d->pixel && (rc = need(ctx, "mirt_filter_atrous pixel", d->pixel, npix * 4))) return rc;
-    {   // an output is read by nobody and no input is written: the same handle, or (wrapped memory) the same bytes, twice is refused
-        const mirt_buf* const in[3] = {d->radiance, d->normal_hits, d->albedo_depth};
-        const mirt_buf* const out[2] = {d->filtered, d->pixel};
-        const uint64_t out_bytes[2] = {npix * 16, npix * 4};
-        auto overlap = [](const mirt_buf* a, uint64_t na, const mirt_buf* b, uint64_t nb) {
-            return a == b || ((const char*)a->ptr < (const char*)b->ptr + nb && (const char*)b->ptr < (const char*)a->ptr + na);
-        };
-        for (int o = 0; o < 2; ++o) {
-            if (!out[o]) continue;
-            for (int i = 0; i < 3; ++i)
-                if (overlap(out[o], out_bytes[o], in[i], npix * 16)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: an output aliases an input");
-        }
-        if (out[0] && out[1] && overlap(out[0], out_bytes[0], out[1], out_bytes[1])) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: filtered aliases pixel");
-    }
+    const PostBuf b[5] = {{"mirt_filter_atrous radiance", d->radiance, npix * 16}, {"mirt_filter_atrous normal_hits", d->normal_hits, npix * 16}, {"mirt_filter_atrous albedo_depth", d->albedo_depth, npix * 16},
+                          {"mirt_filter_atrous filtered", d->filtered, npix * 16}, {"mirt_filter_atrous pixel", d->pixel, npix * 4}};
+    if ((rc = post_check_buffers(ctx, fn, "filtered", b))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::FilterArgs A;
     memset(&A, 0, sizeof A);
     A.width = d->width; A.height = d->height;
     A.demodulate = (d->flags & MIRT_FILTER_DEMODULATE) ? 1u : 0u;
     A.npow = d->normal_power_log2;
-    A.depth_on = std::isfinite(d->sigma_depth) && d->sigma_depth > 0.0f;
-    A.colour_on = std::isfinite(d->sigma_colour) && d->sigma_colour > 0.0f;
+    A.depth_on = pt::post_finite_positive(d->sigma_depth);
+    A.colour_on = pt::post_finite_positive(d->sigma_colour);
     A.tone = d->tone; A.sigma_depth = d->sigma_depth;
     A.radiance = d->radiance->ptr; A.normal_hits = d->normal_hits->ptr; A.albedo_depth = d->albedo_depth->ptr;
     A.filtered = d->filtered ? d->filtered->ptr : nullptr;
@@ -1594,71 +1620,44 @@ int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* d) try {
         const bool tiled = (d->flags & both) ? (d->flags & MIRT_FILTER_TILED) != 0u : (pt::kFilterTiledSteps >> i & 1u) != 0u;
         pt::launch_filterStep(ctx->stream, A, i & 1u, i, A.colour_on ? inv : 0.0f, i + 1u == d->iterations, tiled);
     }
-    HIPCHK(ctx, hipGetLastError());
-    if (d->filtered) d->filtered->version++;
-    if (d->pixel) d->pixel->version++;
-    return MIRT_OK;
+    return post_finish(ctx, b + 3);
 } MIRT_CATCH("mirt_filter_atrous", return MIRT_E_DEVICE)
 
 // Guide-driven upsampling (pt_kernels_upsample.hip; defined in include/mirt.h): every check first, then one launch.  No working memory.
 int mirt_upsample_guided(mirt_ctx* ctx, const mirt_upsample_desc* d) try {
+    static const char fn[] = "mirt_upsample_guided";
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_upsample_guided: unknown context");
     FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_upsample_guided");
+    NOT_WHILE_CAPTURING(ctx, fn);
     if (!d || d->struct_size != sizeof(mirt_upsample_desc)) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: descriptor size mismatch");
-    if (!d->width || !d->height) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: empty image");
-    if (d->width > 65535u || d->height > 65535u) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: %ux%u is more than 65535 pixels a side", d->width, d->height);
+    int rc;
+    if ((rc = post_check_extent(ctx, fn, d->width, d->height))) return rc;
     if (!pt::upsample_factor_ok(d->factor))
         return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: factor %u is outside %u .. %u", d->factor, MIRT_UPSAMPLE_MIN_FACTOR, MIRT_UPSAMPLE_MAX_FACTOR);
     const uint32_t wl = pt::upsample_low_extent(d->width, d->factor), hl = pt::upsample_low_extent(d->height, d->factor);
     if (!wl || !hl)
         return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: %ux%u is not a multiple of factor %u (the two images would not show the same frustum)", d->width, d->height, d->factor);
-    if (d->normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2)
-        return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: normal_power_log2 %u > %u", d->normal_power_log2, MIRT_FILTER_MAX_NORMAL_POWER_LOG2);
-    if (!(std::isfinite(d->tone) && d->tone > 0.0f)) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: tone %g is not a finite positive factor", (double)d->tone);
+    if ((rc = post_check_terms(ctx, fn, d->normal_power_log2, d->tone))) return rc;
     if (d->flags & ~MIRT_UPSAMPLE_DEMODULATE) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: unknown flags 0x%x", d->flags);
-    if (!d->upsampled && !d->pixel) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: upsampled and pixel are both NULL (either may be, not both)");
     const uint64_t npix = (uint64_t)d->width * d->height, nlo = (uint64_t)wl * hl;
-    int rc;
-    if ((rc = need(ctx, "mirt_upsample_guided radiance_lo", d->radiance_lo, nlo * 16))) return rc;
-    if ((rc = need(ctx, "mirt_upsample_guided normal_hits_lo", d->normal_hits_lo, nlo * 16))) return rc;
-    if ((rc = need(ctx, "mirt_upsample_guided albedo_depth_lo", d->albedo_depth_lo, nlo * 16))) return rc;
-    if ((rc = need(ctx, "mirt_upsample_guided normal_hits", d->normal_hits, npix * 16))) return rc;
-    if ((rc = need(ctx, "mirt_upsample_guided albedo_depth", d->albedo_depth, npix * 16))) return rc;
-    if (d->upsampled && (rc = need(ctx, "mirt_upsample_guided upsampled", d->upsampled, npix * 16))) return rc;
-    if (d->pixel && (rc = need(ctx, "mirt_upsample_guided pixel", d->pixel, npix * 4))) return rc;
-    {   // an output is read by nobody and no input is written: the same handle, or (wrapped memory) the same bytes, twice is refused
-        const mirt_buf* const in[5] = {d->radiance_lo, d->normal_hits_lo, d->albedo_depth_lo, d->normal_hits, d->albedo_depth};
-        const uint64_t in_bytes[5] = {nlo * 16, nlo * 16, nlo * 16, npix * 16, npix * 16};
-        const mirt_buf* const out[2] = {d->upsampled, d->pixel};
-        const uint64_t out_bytes[2] = {npix * 16, npix * 4};
-        auto overlap = [](const mirt_buf* a, uint64_t na, const mirt_buf* b, uint64_t nb) {
-            return a == b || ((const char*)a->ptr < (const char*)b->ptr + nb && (const char*)b->ptr < (const char*)a->ptr + na);
-        };
-        for (int o = 0; o < 2; ++o) {
-            if (!out[o]) continue;
-            for (int i = 0; i < 5; ++i)
-                if (overlap(out[o], out_bytes[o], in[i], in_bytes[i])) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: an output aliases an input");
-        }
-        if (out[0] && out[1] && overlap(out[0], out_bytes[0], out[1], out_bytes[1])) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: upsampled aliases pixel");
-    }
+    const PostBuf b[7] = {{"mirt_upsample_guided radiance_lo", d->radiance_lo, nlo * 16}, {"mirt_upsample_guided normal_hits_lo", d->normal_hits_lo, nlo * 16}, {"mirt_upsample_guided albedo_depth_lo", d->albedo_depth_lo, nlo * 16},
+                          {"mirt_upsample_guided normal_hits", d->normal_hits, npix * 16}, {"mirt_upsample_guided albedo_depth", d->albedo_depth, npix * 16},
+                          {"mirt_upsample_guided upsampled", d->upsampled, npix * 16}, {"mirt_upsample_guided pixel", d->pixel, npix * 4}};
+    if ((rc = post_check_buffers(ctx, fn, "upsampled", b))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::UpsampleArgs A;
     memset(&A, 0, sizeof A);
     A.width = d->width; A.height = d->height; A.factor = d->factor;
     A.demodulate = (d->flags & MIRT_UPSAMPLE_DEMODULATE) ? 1u : 0u;
     A.npow = d->normal_power_log2;
-    A.depth_on = std::isfinite(d->sigma_depth) && d->sigma_depth > 0.0f;
+    A.depth_on = pt::post_finite_positive(d->sigma_depth);
     A.tone = d->tone; A.sigma_depth = d->sigma_depth;
     A.radiance_lo = d->radiance_lo->ptr; A.normal_hits_lo = d->normal_hits_lo->ptr; A.albedo_depth_lo = d->albedo_depth_lo->ptr;
     A.normal_hits = d->normal_hits->ptr; A.albedo_depth = d->albedo_depth->ptr;
     A.upsampled = d->upsampled ? d->upsampled->ptr : nullptr;
     A.pixel = d->pixel ? d->pixel->ptr : nullptr;
     pt::launch_upsample(ctx->stream, A);
-    HIPCHK(ctx, hipGetLastError());
-    if (d->upsampled) d->upsampled->version++;
-    if (d->pixel) d->pixel->version++;
-    return MIRT_OK;
+    return post_finish(ctx, b + 5);
 } MIRT_CATCH("mirt_upsample_guided", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_fusion(mirt_ctx* ctx, int level) try {

@@ -2,12 +2,8 @@
 // guide buffers of pt_kernels_guides.hip.  The definition -- every operation, in order -- is the comment of mirt_filter_atrous in include/mirt.h;
 // tests/filter_common.py restates it in numpy and the kernels equal that restatement bit for bit, in both libraries.
 //
-// Numerics.  One fp32 operation at a time, rounded on its own: every translation unit builds with -ffp-contract=off, and nothing here is an fma.
-// The reference has no filter, so there is ONE contract for libmirt.so and libmirt_default.so: a plain `/` would be AMD's 2.5-ulp sequence in the
-// default-contract build, so every quotient is div_cr() below -- the operands widened to fp64, divided there (fp64 division is correctly rounded
-// in both builds) and rounded back: 53 >= 2 * 24 + 2 bits make the double rounding harmless, the result IS the correctly rounded fp32 quotient.
-// Four quotients per pixel and iteration beside 24 taps: their cost does not matter.  No exp, pow or sqrt: the edge terms are hats and repeated
-// squaring.
+// Numerics: pt_post.hpp, which also holds the arithmetic this file shares with the upsampler (pt_kernels_upsample.hip) -- div_cr(), the guide
+// normalisation, demodulation and its inverse, the normal and depth terms, the tone map and the final store.  The colour term is the filter's own.
 //
 // Working set (the context's scratch buffer, FilterArgs::work / guide): two float4 images (I.x, I.y, I.z, live ? 1 : 0) that the iterations
 // alternate between, and the prepared guide (n^.x, n^.y, n^.z, z).  A tap is 32 B: its colour and, when it is live, its guide.
@@ -21,36 +17,17 @@
 // Measured at 1080p (MI355X): the tiles win at steps 1 and 2 (0.053 / 0.072 ms against 0.096 / 0.093), direct reads at 4, 8 and 16 (0.098 / 0.093 /
 // 0.086 ms against 0.106 / 0.189 / 0.130): kFilterTiledSteps in pt_launch.hpp.
 #include "pt_launch.hpp"
-#include "pt_numerics.hpp"
+#include "pt_post.hpp"
 
 namespace pt {
 
-PT_DEV float div_cr(float n, float d) { return (float)((double)n / (double)d); }
-
-// what the prepare step and the last step both need of a pixel: r = 1 / hits, a = A * r
-PT_DEV void filter_albedo(const FilterArgs& A, uint32_t p, float hits, float& ax, float& ay, float& az) {
-    const float4 ad = ((const float4*)A.albedo_depth)[p];
-    const float r = div_cr(1.0f, hits);
-    ax = ad.x * r; ay = ad.y * r; az = ad.z * r;
-}
-
-// out = I_n (times the albedo where the image was demodulated) -> filtered, pixel (k_copyToPixel's tone map, pt_kernels_granular.hip)
+// out = I_n (times the albedo where the image was demodulated) -> filtered, pixel
 PT_DEV void filter_finish(const FilterArgs& A, uint32_t p, float ox, float oy, float oz, bool live) {
     if (A.demodulate && live) {
-        float ax, ay, az;
-        filter_albedo(A, p, ((const float4*)A.normal_hits)[p].w, ax, ay, az);
-        if (ax > 0.0f) ox = ox * ax;
-        if (ay > 0.0f) oy = oy * ay;
-        if (az > 0.0f) oz = oz * az;
+        const float r = post_inv_hits(((const float4*)A.normal_hits)[p].w);
+        post_modulate(ox, oy, oz, post_albedo(((const float4*)A.albedo_depth)[p], r));
     }
-    if (A.filtered) ((float4*)A.filtered)[p] = make_float4(ox, oy, oz, ((const float4*)A.radiance)[p].w);
-    if (A.pixel) {
-        const float sc = 255.0f * A.tone;
-        const float x = cl_clamp((ox * sc) * 1.8f, 0.0f, 255.0f);
-        const float y = cl_clamp((oy * sc) * 1.8f, 0.0f, 255.0f);
-        const float z = cl_clamp((oz * sc) * 1.8f, 0.0f, 255.0f);
-        ((uchar4*)A.pixel)[p] = make_uchar4((unsigned char)f2u(x), (unsigned char)f2u(y), (unsigned char)f2u(z), 255);
-    }
+    post_store(A.filtered, A.pixel, p, ox, oy, oz, ((const float4*)A.radiance)[p].w, A.tone);
 }
 
 // I_0 and the prepared guide of every pixel.  LAST (iterations == 0): the outputs, straight from I_0.
@@ -66,14 +43,9 @@ __global__ void __launch_bounds__(256) k_filterPrepare(const FilterArgs A) {
     float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (live) {
         const float4 ad = ((const float4*)A.albedo_depth)[p];
-        const float r = div_cr(1.0f, nh.w);
-        g = make_float4(nh.x * r, nh.y * r, nh.z * r, ad.w * r);
-        if (A.demodulate) {
-            const float ax = ad.x * r, ay = ad.y * r, az = ad.z * r;
-            if (ax > 0.0f) ix = div_cr(R.x, ax);
-            if (ay > 0.0f) iy = div_cr(R.y, ay);
-            if (az > 0.0f) iz = div_cr(R.z, az);
-        }
+        const float r = post_inv_hits(nh.w);
+        g = post_guide(nh, ad, r);
+        if (A.demodulate) post_demodulate(ix, iy, iz, post_albedo(ad, r));
     }
     if (LAST) { filter_finish(A, p, ix, iy, iz, live); return; }
     ((float4*)A.work[0])[p] = make_float4(ix, iy, iz, live ? 1.0f : 0.0f);
@@ -86,7 +58,7 @@ template <class Tap>
 PT_DEV float4 filter_pixel(const FilterArgs& A, float inv_colour, const float4 cp, const float4 gp, const Tap& tap) {
     const float h[3] = {0.375f, 0.25f, 0.0625f};
     float izp = 0.0f;
-    if (A.depth_on) izp = div_cr(1.0f, A.sigma_depth * gp.w);
+    if (A.depth_on) izp = post_inv_depth(A.sigma_depth, gp.w);
     float sumw = 0.140625f;
     float sx = cp.x * 0.140625f, sy = cp.y * 0.140625f, sz = cp.z * 0.140625f;
 #pragma unroll
@@ -97,10 +69,8 @@ PT_DEV float4 filter_pixel(const FilterArgs& A, float inv_colour, const float4 c
             float4 cq, gq;
             if (!tap(dx, dy, cq, gq)) continue;
             const float k = h[dy < 0 ? -dy : dy] * h[dx < 0 ? -dx : dx];
-            float wn = cl_max(0.0f, (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z);
-            for (uint32_t j = 0; j < A.npow; ++j) wn = wn * wn;
-            float w = k * wn;
-            if (A.depth_on) w = w * cl_max(0.0f, 1.0f - cl_fabs(gp.w - gq.w) * izp);
+            float w = k * post_normal_weight(gp, gq, A.npow);
+            if (A.depth_on) w = w * post_depth_hat(gp.w, gq.w, izp);
             if (A.colour_on) {
                 const float ex = (cp.x - cq.x) * A.tone, ey = (cp.y - cq.y) * A.tone, ez = (cp.z - cq.z) * A.tone;
                 const float c = (ex * ex + ey * ey) + ez * ez;

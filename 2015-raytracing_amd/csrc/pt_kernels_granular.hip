@@ -401,11 +401,7 @@ __global__ void __launch_bounds__(64) k_copyToPixel(uchar4* pixel, const float4*
     }
     if (id >= lim) return;
     if (radiance) radiance[id] = c;
-    float sc = 255.0f * m;
-    c.x = cl_clamp((c.x * sc) * 1.8f, 0.0f, 255.0f);
-    c.y = cl_clamp((c.y * sc) * 1.8f, 0.0f, 255.0f);
-    c.z = cl_clamp((c.z * sc) * 1.8f, 0.0f, 255.0f);
-    if (pixel) pixel[id] = make_uchar4((unsigned char)f2u(c.x), (unsigned char)f2u(c.y), (unsigned char)f2u(c.z), 255);
+    if (pixel) pixel[id] = tone_rgba8(c.x, c.y, c.z, m);
 }
 
 // rpp <= 4 (the page's default is 1: progressive passes): a pixel's samples span at most one 64-byte sector, so the work-item
@@ -423,11 +419,7 @@ __global__ void __launch_bounds__(256) k_copyToPixelSmall(uchar4* pixel, const f
         c.x += v.x; c.y += v.y; c.z += v.z; c.w += v.w;
     }
     if (radiance) radiance[id] = c;
-    float sc = 255.0f * m;
-    c.x = cl_clamp((c.x * sc) * 1.8f, 0.0f, 255.0f);
-    c.y = cl_clamp((c.y * sc) * 1.8f, 0.0f, 255.0f);
-    c.z = cl_clamp((c.z * sc) * 1.8f, 0.0f, 255.0f);
-    if (pixel) pixel[id] = make_uchar4((unsigned char)f2u(c.x), (unsigned char)f2u(c.y), (unsigned char)f2u(c.z), 255);
+    if (pixel) pixel[id] = tone_rgba8(c.x, c.y, c.z, m);
 }
 
 // splitmix32-style seed fill: s[id] = 1 + (mix(id ^ 0x9E3779B9 ^ base) mod 2147483646), ids global

@@ -102,6 +102,15 @@ PT_DEV uint32_t f2u_uniform(float f) {
     if (f <= 0.0f) return 0u;
     return (uint32_t)f;
 }
+// The reference's tone map (copyToPixel, code.cl:1366-1386): a radiance sum times (255 * tone) times 1.8, clamped to 0 .. 255 and truncated; NaN -> 0.
+// The separate resolve kernels, the a-trous filter and the upsampler all end in it.  (k_fusedPass keeps its own two copies: pt_kernels_fused.hip.)
+PT_DEV uchar4 tone_rgba8(float x, float y, float z, float tone) {
+    const float sc = 255.0f * tone;
+    x = cl_clamp((x * sc) * 1.8f, 0.0f, 255.0f);
+    y = cl_clamp((y * sc) * 1.8f, 0.0f, 255.0f);
+    z = cl_clamp((z * sc) * 1.8f, 0.0f, 255.0f);
+    return make_uchar4((unsigned char)f2u(x), (unsigned char)f2u(y), (unsigned char)f2u(z), 255);
+}
 
 // ---- exact division, cheaper ------------------------------------------------------------------------
 // hipcc expands a correctly rounded x/y into v_div_scale x2, v_rcp, 2 fma (reciprocal refinement), mul, 4 fma

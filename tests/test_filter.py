@@ -248,6 +248,7 @@ def test_refusals_write_nothing_and_leave_the_context_working(ctx, syn, syn_filt
     n = SYN_W * SYN_H
     fill_out, fill_pix = np.full(n * 4, 7.5, np.float32), np.full(n * 4, 0x5A, np.uint8)
     small16, small4 = ctx.buffer(n * 16 - 1), ctx.buffer(n * 4 - 1)
+    carved, wrapped = ctx.buffer(2 * n * 16), []
 
     def call(ctx_h=None, **over):
         d = mirt._FilterDesc()
@@ -283,6 +284,11 @@ def test_refusals_write_nothing_and_leave_the_context_working(ctx, syn, syn_filt
         refused(E_ARG, filtered=f.rad, pixel=None)      # aliasing: an output that is an input
         refused(E_ARG, filtered=f.nh)
         refused(E_ARG, filtered=None, pixel=f.ad)
+        for owner in (f.rad, f.out):                    # ... or wrapped memory that shares SOME bytes: a pixel image 16 bytes inside radiance, inside filtered
+            view = ctx.wrap(owner.device_ptr + 16, n * 4)
+            wrapped.append(view)
+            refused(E_ARG, pixel=view)
+        assert f.rad.read(np.float32).tobytes() == np.ascontiguousarray(syn[0], np.float32).tobytes(), "radiance was written"
         refused(E_RANGE, radiance=small16)
         refused(E_RANGE, normal_hits=small16)
         refused(E_RANGE, albedo_depth=small16)
@@ -301,6 +307,14 @@ def test_refusals_write_nothing_and_leave_the_context_working(ctx, syn, syn_filt
         finally:
             ctx.graph_release(ctx.capture_end())
         assert f.out.read(np.float32).tobytes() == fill_out.tobytes() and f.pix.read(np.uint8).tobytes() == fill_pix.tobytes(), "written inside a recording"
+        # touching is not aliasing: filtered ends exactly where radiance begins, both carved from one allocation
+        out_view, rad_view = ctx.wrap(carved.device_ptr, n * 16), ctx.wrap(carved.device_ptr + n * 16, n * 16)
+        wrapped += [out_view, rad_view]
+        rad_view.write(np.ascontiguousarray(syn[0], np.float32))
+        f.pix.write(fill_pix)
+        assert call(radiance=rad_view, filtered=out_view) == 0, ctx.last_error()
+        check("filtered ends where radiance begins", (out_view.read(np.float32).reshape(-1, 4), f.pix.read(np.uint8).reshape(-1, 4)),
+              atrous(*syn, SYN_W, SYN_H, np.float32(0.25), iterations=2, normal_power_log2=3, sigma_depth=0.1, sigma_colour=2.0, demodulate=True))
         # the context works afterwards: the filter, and a pass
         p = dict(DEFAULTS, iterations=2, normal_power_log2=3)
         check("after the refusals", f.run(SYN_TONE, **p), atrous(*syn, SYN_W, SYN_H, SYN_TONE, **p))
@@ -310,8 +324,8 @@ def test_refusals_write_nothing_and_leave_the_context_working(ctx, syn, syn_filt
         finally:
             r.release()
     finally:
-        small16.release()
-        small4.release()
+        for b in wrapped + [carved, small16, small4]:
+            b.release()
 
 
 def test_a_held_enqueue_stream_is_flushed_before_the_filter_reads_radiance(pkg):

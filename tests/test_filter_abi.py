@@ -89,11 +89,22 @@ def test_both_libraries_export_it(pkg, lib):
 def test_the_kernel_file_is_built_like_the_other_translation_units():
     sh = open(os.path.join(PKG, "csrc", "build.sh")).read()
     assert "pt_kernels_filter.hip" in re.search(r"^SRC=\((.*)\)$", sh, re.M).group(1)
-    src = open(os.path.join(PKG, "csrc", "pt_kernels_filter.hip")).read()
-    code = re.sub(r"//.*", "", src)
-    assert not re.search(r"\b(expf?|powf?|sqrtf?|fmaf?)\s*\(", code), "no exp, pow, sqrt or fma in the filter"
-    # one contract for both builds: every quotient goes through div_cr, the only `/` on floats in the file
-    assert len(re.findall(r"\(double\)\s*n\s*/\s*\(double\)\s*d", code)) == 1
+    code = {name: re.sub(r"//.*", "", open(os.path.join(PKG, "csrc", name)).read()) for name in ("pt_kernels_filter.hip", "pt_kernels_upsample.hip", "pt_post.hpp")}
+    for name, text in code.items():
+        assert not re.search(r"\b(expf?|powf?|sqrtf?|fmaf?)\s*\(", text), f"no exp, pow, sqrt or fma in {name}"
+    # one contract for both builds: every quotient goes through div_cr, the only `/` on floats -- defined once, in the shared header
+    assert len(re.findall(r"\(double\)\s*n\s*/\s*\(double\)\s*d", code["pt_post.hpp"])) == 1
+    assert code["pt_post.hpp"].count("/") == 1
+    # ... so what the kernel files divide are the integers of the grid and tile arithmetic: a `/` there has an unsigned literal or one of these
+    # integer names on its right, and no floating-point literal or cast on its left
+    # (a whitelist by NAME: a float variable called `f` or `step` would slip through, and a new integer divisor has to be added here)
+    integer = r"\d+u\b|(?:\(uint32_t\))?(?:step|kTileSide|kTileIn|f)\b"
+    for name in ("pt_kernels_filter.hip", "pt_kernels_upsample.hip"):
+        assert "(double)" not in code[name] and not re.search(r"\bdiv_cr\s*\([^()]*\)\s*\{", code[name]), f"{name} defines a quotient of its own"
+        for m in re.finditer(r"/", code[name]):
+            left, right = code[name][:m.start()].rstrip(), code[name][m.end():].lstrip()
+            assert re.match(integer, right), f"{name}: `/` applied to {right[:30]!r}"
+            assert not re.search(r"(\d\.\d*f?|\df|\(float\)\s*\w+)$", left), f"{name}: {left[-30:]!r} is divided"
 
 
 def test_the_addon_and_the_javascript_host_export_it():

@@ -36,6 +36,7 @@ def test_refusals_write_nothing_and_leave_the_context_working(ctx):
     out, pix = ctx.buffer(n * 16), ctx.buffer(n * 4)
     fill_out, fill_pix = np.full(n * 4, 7.5, np.float32), np.full(n * 4, 0x5A, np.uint8)
     small_lo, small_hi, small_pix = ctx.buffer(nlo * 16 - 1), ctx.buffer(n * 16 - 1), ctx.buffer(n * 4 - 1)
+    carved, wrapped = ctx.buffer(n * 16 + nlo * 16), []
 
     def call(ctx_h=None, **over):
         d = mirt._UpsampleDesc()
@@ -79,6 +80,11 @@ def test_refusals_write_nothing_and_leave_the_context_working(ctx):
             refused(E_ARG, upsampled=ins[k], pixel=None)
         refused(E_ARG, upsampled=None, pixel=ins["albedo_depth"])
         refused(E_ARG, upsampled=out, pixel=out)      # ... or the other output
+        for owner in (ins["normal_hits"], out):       # ... or wrapped memory that shares SOME bytes: a pixel image 16 bytes inside an input, inside upsampled
+            view = ctx.wrap(owner.device_ptr + 16, n * 4)
+            wrapped.append(view)
+            refused(E_ARG, pixel=view)
+        assert ins["normal_hits"].read(np.float32, n * 4).tobytes() == np.ascontiguousarray(inputs[3], np.float32).tobytes(), "normal_hits was written"
         for k in names[:3]:
             refused(E_RANGE, **{k: small_lo})
         for k in names[3:]:
@@ -99,14 +105,25 @@ def test_refusals_write_nothing_and_leave_the_context_working(ctx):
         finally:
             ctx.graph_release(ctx.capture_end())
         untouched("inside a recording")
-        # the context works afterwards
-        assert call() == 0, ctx.last_error()
         want = upsample(*inputs, W, H, F, SYN_TONE, **DEFAULTS)
+        # touching is not aliasing: upsampled ends exactly where radiance_lo begins, both carved from one allocation
+        out_view, lo_view = ctx.wrap(carved.device_ptr, n * 16), ctx.wrap(carved.device_ptr + n * 16, nlo * 16)
+        wrapped += [out_view, lo_view]
+        lo_view.write(np.ascontiguousarray(inputs[0], np.float32))
+        pix.write(fill_pix)
+        assert call(radiance_lo=lo_view, upsampled=out_view) == 0, ctx.last_error()
+        for tag, got, w in (("upsampled", out_view.read(np.float32).reshape(-1, 4), want[0]), ("pixel", pix.read(np.uint8).reshape(-1, 4), want[1])):
+            d = difference(f"upsampled ends where radiance_lo begins, {tag}", got, w)
+            assert d is None, d
+        # the context works afterwards
+        out.write(fill_out)
+        pix.write(fill_pix)
+        assert call() == 0, ctx.last_error()
         for tag, got, w in (("upsampled", out.read(np.float32).reshape(-1, 4), want[0]), ("pixel", pix.read(np.uint8).reshape(-1, 4), want[1])):
             d = difference(f"after the refusals, {tag}", got, w)
             assert d is None, d
     finally:
-        for b in list(ins.values()) + [out, pix, small_lo, small_hi, small_pix]:
+        for b in wrapped + list(ins.values()) + [out, pix, carved, small_lo, small_hi, small_pix]:
             b.release()
 
 
