@@ -8,6 +8,7 @@
 #include "../../include/mirt.h"
 #include "pt_launch.hpp"
 #include "pt_post_check.hpp"
+#include "pt_set_guard.hpp"
 #include "pt_stream_match.hpp"
 #include "pt_upsample_taps.hpp"
 
@@ -222,36 +223,6 @@ int check_grid(mirt_ctx* ctx, const char* what, mirt_buf* off, uint32_t n, const
 }
 
 int ensure_scratch(mirt_ctx* ctx, size_t bytes);
-
-// n == 1 only.  A10 code.cl:699-707: x_next = pmin + (0 + (d>=0)) * ((pmax-pmin)/1).  When that reproduces pmax / pmin bit for
-// bit on all three axes, the single cell's exit t is the very quotient interAABB already formed for the far slab plane.
-uint32_t exit_is_far_face(const float* b8, uint32_t n) {
-    if (n != 1) return 0;
-    bool exact = true;
-    for (int k = 0; k < 3; ++k) {
-        volatile float lo = b8[k], hi = b8[4 + k];
-        volatile float delta = (hi - lo) / 1.0f;
-        volatile float up = lo + 1.0f * delta, dn = lo + 0.0f * delta;
-        exact = exact && (up == hi) && (dn == lo) && (up == up);
-    }
-    return exact ? 1u : 0u;
-}
-// n == 1, the optimistic kernel's cell exit (pt_trace.hpp cell1_exit): per axis the forward plane x_up = lo + 1*((hi-lo)/1), formed as above, into
-// up[k]; bit k of the result is set where x_up == hi.  `ok` is cleared unless every x_up is zero or within [2^-30, 2^20] (the bounds' window,
-// GridArgs::fast_ok) and every backward plane lo + 0*((hi-lo)/1) equals lo (the kernel takes the box's far quotient for d < 0).
-uint32_t exit_planes(const float* b8, float up[3], bool& ok) {
-    uint32_t far = 0;
-    for (int k = 0; k < 3; ++k) {
-        volatile float lo = b8[k], hi = b8[4 + k];
-        volatile float delta = (hi - lo) / 1.0f;
-        volatile float u = lo + 1.0f * delta, dn = lo + 0.0f * delta;
-        up[k] = u;
-        if (u == hi) far |= 1u << k;
-        const float a = std::fabs(u);
-        if (!(a == 0.0f || (a >= 9.3132257e-10f && a <= 1048576.0f)) || !(dn == lo)) ok = false;
-    }
-    return far;
-}
 
 // (re)builds the prepared-triangle copy of a position buffer when its contents changed
 int ensure_prepared(mirt_ctx* ctx, mirt_buf* pb, uint32_t count) {
@@ -1050,7 +1021,7 @@ static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& 
             if ((rc = need(ctx, "sphereTrace rays", A(K::rays), (uint64_t)cnt * kRayBytes))) return rc;
             if ((rc = check_grid(ctx, "sphereTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 16, nullptr, A(K::matid)))) return rc;
             pt::launch_closest(st, pt::KIND_SPHERES, A(K::total), A(K::pois)->ptr, A(K::rays)->ptr, A(K::prims)->ptr, nullptr, A(K::matid)->ptr, 0, A(K::off)->ptr, A(K::bounds), A(K::n_slabs),
-                               exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
+                               pt::set_exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
         case pt::K_triangleTrace: {
@@ -1061,7 +1032,7 @@ static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& 
             if ((rc = check_grid(ctx, "triangleTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 48, A(K::normals), A(K::matid)))) return rc;
             if ((rc = ensure_prepared(ctx, A(K::prims), A(K::off)->off_last))) return rc;
             pt::launch_closest(st, pt::KIND_TRIANGLES, A(K::total), A(K::pois)->ptr, A(K::rays)->ptr, A(K::prims)->prep, A(K::normals)->ptr, A(K::matid)->ptr, 0, A(K::off)->ptr, A(K::bounds), A(K::n_slabs),
-                               exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
+                               pt::set_exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
         case pt::K_meshTrace: {
@@ -1072,7 +1043,7 @@ static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& 
             if ((rc = check_grid(ctx, "meshTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 48, A(K::normals), nullptr))) return rc;
             if ((rc = ensure_prepared(ctx, A(K::prims), A(K::off)->off_last))) return rc;
             pt::launch_closest(st, pt::KIND_TRIANGLES, A(K::total), A(K::pois)->ptr, A(K::rays)->ptr, A(K::prims)->prep, A(K::normals)->ptr, nullptr, A(K::matid), A(K::off)->ptr, A(K::bounds), A(K::n_slabs),
-                               exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
+                               pt::set_exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
         case pt::K_lightRender: {
@@ -1098,7 +1069,7 @@ static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& 
             uint32_t cnt = std::min(g0, A(K::total));
             if ((rc = need(ctx, "sphereShadowTrace shadow", A(K::shadow_rays), (uint64_t)cnt * kRayBytes))) return rc;
             if ((rc = check_grid(ctx, "sphereShadowTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 16, nullptr, nullptr))) return rc;
-            pt::launch_anyhit(st, pt::KIND_SPHERES, A(K::total), A(K::shadow_rays)->ptr, A(K::prims)->ptr, A(K::off)->ptr, A(K::bounds), A(K::n_slabs), exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
+            pt::launch_anyhit(st, pt::KIND_SPHERES, A(K::total), A(K::shadow_rays)->ptr, A(K::prims)->ptr, A(K::off)->ptr, A(K::bounds), A(K::n_slabs), pt::set_exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
         case pt::K_triangleShadowTrace: {
@@ -1107,7 +1078,7 @@ static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& 
             if ((rc = need(ctx, "triangleShadowTrace shadow", A(K::shadow_rays), (uint64_t)cnt * kRayBytes))) return rc;
             if ((rc = check_grid(ctx, "triangleShadowTrace grid", A(K::off), A(K::n_slabs), A(K::prims), 48, nullptr, nullptr))) return rc;
             if ((rc = ensure_prepared(ctx, A(K::prims), A(K::off)->off_last))) return rc;
-            pt::launch_anyhit(st, pt::KIND_TRIANGLES, A(K::total), A(K::shadow_rays)->ptr, A(K::prims)->prep, A(K::off)->ptr, A(K::bounds), A(K::n_slabs), exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
+            pt::launch_anyhit(st, pt::KIND_TRIANGLES, A(K::total), A(K::shadow_rays)->ptr, A(K::prims)->prep, A(K::off)->ptr, A(K::bounds), A(K::n_slabs), pt::set_exit_is_far_face(A(K::bounds), A(K::n_slabs)), g0);
             break;
         }
         case pt::K_sceneRender: {
@@ -1222,38 +1193,16 @@ static int fill_grid(mirt_ctx* ctx, const char* what, const mirt_grid* g, bool t
     memcpy(o->bound, g->bounds, sizeof o->bound);
     o->n = g->n_slabs;
     o->mesh_matid = g->mesh_matid;
-    o->exit_is_far_face = exit_is_far_face(g->bounds, g->n_slabs);
-    o->fast_ok = 1;
-    for (int k = 0; k < 8; ++k) {
-        if ((k & 3) == 3) continue;
-        const float a = std::fabs(g->bounds[k]);
-        if (!(a == 0.0f || (a >= 9.3132257e-10f && a <= 1048576.0f))) o->fast_ok = 0;
-    }
-    // the optimistic kernel's box test takes min / max of the two plane quotients as near / far: that needs lo <= hi on every axis
-    // (an inverted box is a miss in the reference; here it goes to the exact kernel)
-    for (int k = 0; k < 3; ++k)
-        if (!(g->bounds[k] <= g->bounds[4 + k])) o->fast_ok = 0;
-    if (tri && !g->prims->prep_sane) o->fast_ok = 0;
-    o->exit_far_axes = 7u;
-    o->exit_up[0] = g->bounds[4]; o->exit_up[1] = g->bounds[5]; o->exit_up[2] = g->bounds[6];
-    if (g->n_slabs == 1u) {
-        bool planes_ok = true;
-        o->exit_far_axes = exit_planes(g->bounds, o->exit_up, planes_ok);
-        if (!planes_ok) o->fast_ok = 0;
-    }
-    // the walk's wave-uniform quotients, once, in the arithmetic the kernel would use: fp32, correctly rounded
-    o->walk_ok = 1;
     o->nslots = g->cell_offsets->off_last;   // validated by check_grid above
-    for (int k = 0; k < 3; ++k) {
-        const float span = g->bounds[4 + k] - g->bounds[k];
-        const float delta = span / (float)g->n_slabs;
-        o->delta[k] = delta;
-        o->rdelta[k] = 1.0f / delta;
-        const float as = std::fabs(span), ad = std::fabs(delta);
-        const bool span_in = span == 0.0f || (as >= 8.6736174e-19f && as <= 1.1529215e18f);   // 0 | 2^-60 .. 2^60 (pt_trace.hpp num_window)
-        const bool delta_in = ad >= 9.094947e-13f && ad <= 1.0995116e12f;                      // 2^-40 .. 2^40       (den_window)
-        if (!(span_in && delta_in)) o->walk_ok = 0;
-    }
+    // the geometry-side guard of the optimistic kernel and the walk's wave-uniform quotients (pt_set_guard.hpp)
+    const pt::SetGuard v = pt::set_guard(g->bounds, g->n_slabs, !tri || g->prims->prep_sane);
+    o->fast_ok = v.fast_ok;
+    o->walk_ok = v.walk_ok;
+    o->exit_is_far_face = v.exit_is_far_face;
+    o->exit_far_axes = v.exit_far_axes;
+    memcpy(o->exit_up, v.exit_up, sizeof o->exit_up);
+    memcpy(o->delta, v.delta, sizeof o->delta);
+    memcpy(o->rdelta, v.rdelta, sizeof o->rdelta);
     return MIRT_OK;
 }
 
@@ -1386,8 +1335,7 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
         pt::launch_lensDraws(ctx->stream, A.seeds, scratch + plan.lens.off, d->width, d->height, d->width, d->height, d->row0, nrows);
     }
     if (ctx->profiling && !ctx->capturing && o.mark_start) HIPCHK(ctx, hipEventRecord(ctx->pe[0], ctx->stream));
-    bool optimistic = pt::fused_fast_available() && !ctx->force_exact;
-    for (uint32_t i = 0; i < A.n_sets; ++i) optimistic = optimistic && A.sets[i].fast_ok != 0;
+    const bool optimistic = pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A);
     uint32_t* mask = nullptr;
     if (optimistic) {
         // optimistic kernel (exact cheap divisions inside their window) + exact kernel over the samples that left the window:
@@ -1509,8 +1457,7 @@ int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_
     if (albedo_depth && (rc = need(ctx, "albedo_depth", albedo_depth, npix * 16))) return rc;
     void* const nh = normal_hits ? normal_hits->ptr : nullptr;
     void* const ad = albedo_depth ? albedo_depth->ptr : nullptr;
-    bool optimistic = pt::fused_fast_available() && !ctx->force_exact;
-    for (uint32_t i = 0; i < A.n_sets; ++i) optimistic = optimistic && A.sets[i].fast_ok != 0;
+    const bool optimistic = pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A);
     if (optimistic) {
         const size_t need_bytes = (size_t)((npix + 31u) / 32u) * 4u;
         if (ctx->guide_mask_bytes < need_bytes) {

@@ -44,10 +44,10 @@ __global__ void __launch_bounds__(256) k_prepTriangles(const float4* pos, float4
     out[3u * i] = make_float4(p0.x, p0.y, p0.z, n.x);
     out[3u * i + 1] = make_float4(e1.x, e1.y, e1.z, n.y);
     out[3u * i + 2] = make_float4(e2.x, e2.y, e2.z, n.z);
-    auto bad = [](float v) { const float a = __builtin_fabsf(v); return !(v == 0.0f || (a >= 9.094947e-13f && a <= 1.0995116e12f)); };
+    auto bad = [](float v) { const float a = __builtin_fabsf(v); return !(v == 0.0f || (a >= kDenLo && a <= kDenHi)); };   // pt_windows.hpp
     // ... and every vertex / edge component within 2^21 in magnitude (NaN fails): the bounds of the set are the caller's word, the
     // finiteness arguments of the optimistic kernel (pt_trace.hpp) are about the triangles themselves
-    auto big = [](float v) { return !(__builtin_fabsf(v) <= 2097152.0f); };
+    auto big = [](float v) { return !(__builtin_fabsf(v) <= kTriMax); };
     if (bad(n.x) || bad(n.y) || bad(n.z) || big(p0.x) || big(p0.y) || big(p0.z) || big(e1.x) || big(e1.y) || big(e1.z) || big(e2.x) || big(e2.y) || big(e2.z))
         atomicOr(insane, 1u);
     // One bounding sphere per group of kTriGroup consecutive records, behind the records: {centre, R'^2} with R' the radius inflated by

@@ -57,7 +57,9 @@ struct GridArgs {            // one cell-sorted primitive set, device pointers
     uint32_t mesh_matid;
     uint32_t kind;           // KIND_SPHERES | KIND_TRIANGLES
     uint32_t fast_ok;        // geometry-side guard of the exact 3-operation divisions (pt_trace.hpp ray_recip): every bound is 0 or
-                             // in [2^-30, 2^20]; for triangles every plane-normal component is 0 or in [2^-40, 2^40]
+                             // in [2^-30, 2^20]; for triangles every plane-normal component is 0 or in [2^-40, 2^40].  The host's verdict:
+                             // this field and delta, rdelta, exit_far_axes, exit_up, walk_ok, exit_is_far_face below are pt_set_guard.hpp's
+                             // SetGuard, copied (mirt_abi.cpp fill_grid)
     uint32_t lds_off;        // fused pass (launch_fused assigns it).  n > 1: dword index of this set's cell-offset table inside the block's
                              // LDS copy, or kNoLds when the tables of the scene do not fit.  n == 1, triangles: dword index (a multiple of
                              // 4) of the set's `nslots` prepared records staged in LDS for the per-lane candidate loops, or kNoLds
@@ -70,7 +72,7 @@ struct GridArgs {            // one cell-sorted primitive set, device pointers
                              // widths and spans sit inside the windows in which the kernel's 3-operation divisions are exact; a lane that
                              // walks a set without it hands its sample to the exact kernel
     uint32_t exit_is_far_face; // n == 1 only: lo + 1*((hi-lo)/1) == hi and lo + 0*((hi-lo)/1) == lo hold bitwise on all three
-                             // axes (checked on the host), so the single cell's exit t equals the AABB slab's far t
+                             // axes (checked on the host: pt_set_guard.hpp set_exit_is_far_face), so the single cell's exit t equals the AABB slab's far t
 };
 struct LightArgs {           // the three float16 packings of one light (A10 code.js:323-352)
     float shadow[16];        // pos, T, B, radius
@@ -123,6 +125,8 @@ struct FusedArgs {
     uint32_t pass_index;     // the 1-based index of the launch's first pass
     const void* carry;       // float4[passes * nrows * width]; read only by a launch with seg_off != 0
 };
+// the optimistic kernel may run the launch: every set passed its geometry-side guard (pt_set_guard.hpp)
+inline bool all_sets_fast_ok(const FusedArgs& a) { for (uint32_t i = 0; i < a.n_sets; ++i) if (!a.sets[i].fast_ok) return false; return true; }
 // fast: the optimistic kernel (writes deferred samples' bits into defer_mask); !fast: the exact kernel over `list` (or everything)
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words);
 bool fused_fast_available();   // compiled with PT_EXACT_FAST_DIV

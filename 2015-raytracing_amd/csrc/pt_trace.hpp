@@ -7,6 +7,7 @@
 #pragma once
 #include "pt_device.hpp"
 #include "pt_launch.hpp"
+#include "pt_windows.hpp"
 
 #ifndef PT_UNROLL_UNIFORM
 #define PT_UNROLL_UNIFORM 1   // primitives per trip of the wave-uniform loops
@@ -176,7 +177,7 @@ PT_DEV bool tri_test_staged(bool active, f3 o, f3 d, float cmin, float cmax, con
 }
 
 // Ray-side guard of the exact cheap divisions (pt_numerics.hpp "exact division, cheaper"): |d_k| in [2^-40, 2^40] and o_k zero or
-// in [2^-30, 2^20].  With the geometry-side guard (GridArgs::fast_ok, checked on the host: bounds zero or in [2^-30, 2^20],
+// in [2^-30, 2^20] (the numbers: pt_windows.hpp).  With the geometry-side guard (GridArgs::fast_ok, checked on the host, pt_set_guard.hpp: bounds zero or in [2^-30, 2^20],
 // triangle-plane normals zero or in [2^-40, 2^40] per component) it gives
 //   * every slab numerator lo-o / hi-o is zero or in [2^-53, 2^21]           -> div_exact3 == the true quotient
 //   * every determinant n.d is zero or in [2^-103, 2^82] (sums of products that are zero or >= 2^-80 cancel to zero or to a
@@ -193,10 +194,10 @@ PT_DEV bool ray_guard(const Ray& r) {
     const uint32_t dx = ab(r.d.x), dy = ab(r.d.y), dz = ab(r.d.z), ox = ab(r.o.x), oy = ab(r.o.y), oz = ab(r.o.z);
     const uint32_t dlo = umin3(dx, dy, dz), dhi = umax3(dx, dy, dz);
     const uint32_t olo = umin3(ox - 1u, oy - 1u, oz - 1u), ohi = umax3(ox, oy, oz);
-    return ((int)(dlo >= 0x2B800000u) & (int)(dhi <= 0x53800000u) & (int)(olo >= 0x30800000u - 1u) & (int)(ohi <= 0x49800000u)) != 0;   // 2^-40, 2^40, 2^-30, 2^20
+    return ((int)(dlo >= kDenLoBits) & (int)(dhi <= kDenHiBits) & (int)(olo >= kPosLoBits - 1u) & (int)(ohi <= kPosHiBits)) != 0;   // 2^-40, 2^40, 2^-30, 2^20 (pt_windows.hpp)
 #else
-    auto dwin = [](float d) { return __builtin_fabsf(d) >= 9.094947e-13f && __builtin_fabsf(d) <= 1.0995116e12f; };          // 2^-40 .. 2^40
-    auto owin = [](float o) { return o == 0.0f || (__builtin_fabsf(o) >= 9.3132257e-10f && __builtin_fabsf(o) <= 1048576.0f); };  // 0 | 2^-30 .. 2^20
+    auto dwin = [](float d) { return __builtin_fabsf(d) >= kDenLo && __builtin_fabsf(d) <= kDenHi; };          // 2^-40 .. 2^40
+    auto owin = [](float o) { return o == 0.0f || (__builtin_fabsf(o) >= kPosLo && __builtin_fabsf(o) <= kPosHi); };  // 0 | 2^-30 .. 2^20
     return dwin(r.d.x) && dwin(r.d.y) && dwin(r.d.z) && owin(r.o.x) && owin(r.o.y) && owin(r.o.z);
 #endif
 }
@@ -324,8 +325,8 @@ PT_DEV bool sph_test(f3 o, f3 d, const SphereRay& sr, float cmin, float cmax, co
 // axis_setup (pt_device.hpp) with the optimistic kernel's divisions: every quotient is div_exact3 on a refined reciprocal.  The
 // denominators are the ray direction (ray_guard), the slab count and the slab width; numerators and the slab width are checked
 // here, per lane, and a lane outside the windows marks its sample for the exact kernel.
-PT_DEV bool num_window(float v) { const float a = __builtin_fabsf(v); return ((int)(v == 0.0f) | ((int)(a >= 8.6736174e-19f) & (int)(a <= 1.1529215e18f))) != 0; }   // 0 | 2^-60 .. 2^60
-PT_DEV bool den_window(float v) { const float a = __builtin_fabsf(v); return a >= 9.094947e-13f && a <= 1.0995116e12f; }                    // 2^-40 .. 2^40
+PT_DEV bool num_window(float v) { const float a = __builtin_fabsf(v); return ((int)(v == 0.0f) | ((int)(a >= kNumLo) & (int)(a <= kNumHi))) != 0; }   // 0 | 2^-60 .. 2^60
+PT_DEV bool den_window(float v) { const float a = __builtin_fabsf(v); return a >= kDenLo && a <= kDenHi; }                    // 2^-40 .. 2^40
 // The slab width delta = (hi - lo) / n and 1 / delta depend on the set alone: the host computes them once (GridArgs::delta / rdelta,
 // correctly rounded, which is what div_exact3 / rcp_refined give inside their windows; GridArgs::walk_ok says the windows hold).
 template <bool FAST>
@@ -392,7 +393,7 @@ PT_DEV Box set_box_of(const GridArgs& S) {
 template <bool FAST>
 PT_DEV float cell1_exit(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const GridArgs& S) {
     float tn[3];
-    if (S.exit_is_far_face) {  // host-verified: the cell's exit planes ARE the box's far planes (see mirt_abi.cpp)
+    if (S.exit_is_far_face) {  // host-verified: the cell's exit planes ARE the box's far planes (pt_set_guard.hpp set_exit_is_far_face)
         tn[0] = bh.tfx; tn[1] = bh.tfy; tn[2] = bh.tfz;
 #if !PT_PLAIN_DIV
     } else if (FAST) {
