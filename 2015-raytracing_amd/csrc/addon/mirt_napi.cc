@@ -157,6 +157,15 @@ napi_value CtxFusedPasses(napi_env env, napi_callback_info info) {
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return mk_num(env, (double)n);
 }
+napi_value CtxGuidedPasses(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "ctxGuidedPasses(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_ctx_guided_passes((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
+}
 napi_value BufCreate(napi_env env, napi_callback_info info) {
     ARGS(3);
     void* c; double bytes; uint32_t flags;
@@ -303,9 +312,13 @@ bool read_grid(napi_env env, napi_value o, mirt_grid* g) {
 // radiance hold nPasses frames; webcl.js checks the count's range and the frame buffers' sizes)
 // renderGuides(ctx, desc, normalHits, albedoDepth): the same descriptor (seeds, acu, pixel, radiance, lights are not needed), two float4-per-pixel
 // buffers of the tile, either may be null (mirt_render_guides)
-static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, bool guides, napi_value nhv, napi_value adv) {
+// renderFirstPassGuided(ctx, desc, normalHits, albedoDepth): the frame's first pass of the descriptor and its guides in one call
+// (mirt_render_first_pass_guided)
+enum RenderCall { CALL_PASS, CALL_GUIDES, CALL_FIRST_PASS_GUIDED };
+static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, RenderCall call, napi_value nhv, napi_value adv) {
+    const bool guides = call != CALL_PASS;
     void* c;
-    if (!get_ext(env, ctxv, &c)) return throw_type(env, guides ? "renderGuides(ctx, desc, normalHits, albedoDepth)" : "renderPass(ctx, desc)");
+    if (!get_ext(env, ctxv, &c)) return throw_type(env, call == CALL_GUIDES ? "renderGuides(ctx, desc, normalHits, albedoDepth)" : call == CALL_FIRST_PASS_GUIDED ? "renderFirstPassGuided(ctx, desc, normalHits, albedoDepth)" : "renderPass(ctx, desc)");
     mirt_pass_desc p;
     memset(&p, 0, sizeof p);
     p.struct_size = sizeof p;
@@ -356,7 +369,8 @@ static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, bool 
         void *nh = nullptr, *ad = nullptr;
         get_ext(env, nhv, &nh);
         get_ext(env, adv, &ad);
-        const int rc = mirt_render_guides((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad);
+        const int rc = call == CALL_GUIDES ? mirt_render_guides((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad)
+                                           : mirt_render_first_pass_guided((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad);
         if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
         return undef(env);
     }
@@ -374,11 +388,15 @@ static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, bool 
 }
 napi_value RenderPass(napi_env env, napi_callback_info info) {
     ARGS(2);
-    return render_call(env, argv[0], argv[1], false, nullptr, nullptr);
+    return render_call(env, argv[0], argv[1], CALL_PASS, nullptr, nullptr);
 }
 napi_value RenderGuides(napi_env env, napi_callback_info info) {
     ARGS(4);
-    return render_call(env, argv[0], argv[1], true, argv[2], argv[3]);
+    return render_call(env, argv[0], argv[1], CALL_GUIDES, argv[2], argv[3]);
+}
+napi_value RenderFirstPassGuided(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    return render_call(env, argv[0], argv[1], CALL_FIRST_PASS_GUIDED, argv[2], argv[3]);
 }
 
 // filterAtrous(ctx, {width,height,iterations,flags,normalPowerLog2,tone,sigmaDepth,sigmaColour, radiance,normalHits,albedoDepth, filtered?,pixel?}):
@@ -723,11 +741,11 @@ napi_value GatherRoute(napi_env env, napi_callback_info info) {
 napi_value Init(napi_env env, napi_value exports) {
     struct { const char* name; napi_callback fn; } fns[] = {
         {"deviceCount", DeviceCount}, {"deviceName", DeviceName}, {"version", Version},
-        {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"finish", Finish}, {"ctxSetFusion", CtxSetFusion}, {"ctxFusedPasses", CtxFusedPasses},
+        {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"finish", Finish}, {"ctxSetFusion", CtxSetFusion}, {"ctxFusedPasses", CtxFusedPasses}, {"ctxGuidedPasses", CtxGuidedPasses},
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

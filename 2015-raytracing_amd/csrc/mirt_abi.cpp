@@ -91,6 +91,7 @@ struct mirt_ctx {
     int fusion = 0;
     std::vector<Enqueue> pending;
     uint64_t fused_passes = 0;    // passes executed as ONE fused launch because their enqueue stream matched executeRender's
+    uint64_t guided_passes = 0;   // mirt_render_first_pass_guided calls whose pass wrote the guides itself (the one-launch route)
     // the same for the frame dialects (mirt_ctx_set_frame_fusion): an A04 / A07 initTrace and the enqueues behind it are held in `pending` too
     bool frame_fusion = false;
     uint64_t fused_frames = 0;
@@ -849,6 +850,8 @@ struct PassOpts {
     bool mark_start = true;
     uint32_t frame = 0;
     bool every = false;
+    mirt_buf* guide_nh = nullptr;   // mirt_render_first_pass_guided: the first-hit guides of the tile are written too (either may be null)
+    mirt_buf* guide_ad = nullptr;
 };
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
@@ -1282,6 +1285,47 @@ static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bo
     return MIRT_OK;
 }
 
+// The guide launches of an already validated tile: the optimistic / exact pair of one lane per pixel, or the exact kernel alone.
+static int queue_guides(mirt_ctx* ctx, const pt::FusedArgs& A, void* nh, void* ad) {
+    const uint64_t npix = (uint64_t)A.nrows * A.width;
+    const bool optimistic = pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A);
+    if (optimistic) {
+        const size_t need_bytes = (size_t)((npix + 31u) / 32u) * 4u;
+        if (ctx->guide_mask_bytes < need_bytes) {
+            if (ctx->guide_mask) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->guide_mask)); ctx->guide_mask = nullptr; ctx->guide_mask_bytes = 0; }
+            HIPCHK(ctx, hipMalloc(&ctx->guide_mask, need_bytes));
+            ctx->guide_mask_bytes = need_bytes;
+        }
+        HIPCHK(ctx, hipMemsetAsync(ctx->guide_mask, 0, need_bytes, ctx->stream));
+        pt::launch_guides(ctx->stream, A, true, nh, ad, (uint32_t*)ctx->guide_mask, nullptr);
+        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, (const uint32_t*)ctx->guide_mask);
+    } else {
+        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, nullptr);
+    }
+    return MIRT_OK;
+}
+
+// mirt_render_first_pass_guided's own buffer rules, after the pass's: each guide given holds the tile's pixels x 16 B (MIRT_E_RANGE), and its bytes
+// meet those of no buffer of the descriptor nor the other guide's (MIRT_E_ARG) -- the pass and the guides are written by the same launches.
+static int guided_check_buffers(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* nh, mirt_buf* ad, uint64_t npix) {
+    int rc;
+    if (nh && (rc = need(ctx, "mirt_render_first_pass_guided normal_hits", nh, npix * 16))) return rc;
+    if (ad && (rc = need(ctx, "mirt_render_first_pass_guided albedo_depth", ad, npix * 16))) return rc;
+    std::vector<pt::PostRange> in;
+    const auto add = [&in](const mirt_buf* b) { if (b && live_has(b)) in.push_back({(uint64_t)(uintptr_t)b->ptr, (uint64_t)b->bytes, true}); };
+    const auto add_grid = [&add](const mirt_grid* g) { if (g) { add(g->prims); add(g->normals); add(g->matid); add(g->cell_offsets); } };
+    add(d->seeds); add(d->acu); add(d->pixel); add(d->radiance); add(d->material);
+    add_grid(d->spheres); add_grid(d->triangles);
+    for (uint32_t m = 0; m < d->n_meshes; ++m) add_grid(&d->meshes[m]);
+    const pt::PostRange out[2] = {{nh ? (uint64_t)(uintptr_t)nh->ptr : 0u, npix * 16, nh != nullptr}, {ad ? (uint64_t)(uintptr_t)ad->ptr : 0u, npix * 16, ad != nullptr}};
+    const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 2);
+    if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: a guide buffer aliases a buffer of the descriptor");
+    if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: normal_hits aliases albedo_depth");
+    return MIRT_OK;
+}
+// MIRT_GUIDED_PASS=0: mirt_render_first_pass_guided always queues the pass and then the guide launches -- an A/B and test switch, read per call
+static bool guided_pass_enabled() { const char* e = getenv("MIRT_GUIDED_PASS"); return !(e && e[0] == '0'); }
+
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o) {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_pass: unknown context");
     pt::FusedArgs A;
@@ -1316,6 +1360,13 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
     if (o.every && !plan.resolves) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: a frame after every pass in one launch needs a pass that resolves in the kernel");
     // the column streams live in seeds[0..width): only the tile that owns row 0 holds them
     if (A.rpp == 1 && d->row0 != 0) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: rays_per_pixel == 1 couples rows through seeds[col] (A10 code.cl:429); render it as one tile");
+    // the guides beside the pass (mirt_render_first_pass_guided): the last of the checks -- nothing has been queued yet -- and the route
+    const bool guided = o.guide_nh || o.guide_ad;
+    if (guided && (rc = guided_check_buffers(ctx, d, o.guide_nh, o.guide_ad, npix))) return rc;
+    void* const guide_nh = o.guide_nh ? o.guide_nh->ptr : nullptr;
+    void* const guide_ad = o.guide_ad ? o.guide_ad->ptr : nullptr;
+    const bool guides_in_pass = guided && pt::fused_guides_in_pass(plan, o.passes) && guided_pass_enabled();
+    if (guides_in_pass) { A.guide_nh = guide_nh; A.guide_ad = guide_ad; }
     if (plan.scratch_bytes && (rc = ensure_scratch(ctx, (size_t)plan.scratch_bytes))) return rc;
     char* const scratch = (char*)ctx->scratch;
     if (plan.resolves) {
@@ -1377,9 +1428,13 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
     if (ctx->profiling && !ctx->capturing) HIPCHK(ctx, hipEventRecord(ctx->pe[1], ctx->stream));
     if (!plan.resolves && want_out) pt::launch_copyToPixel(ctx->stream, pixel_ptr, A.acu, res_m, (uint32_t)npix, A.rpp, (uint32_t)npix, radiance_ptr);
     if (ctx->profiling && !ctx->capturing) { HIPCHK(ctx, hipEventRecord(ctx->pe[2], ctx->stream)); ctx->pe_valid = true; }
+    if (guides_in_pass) ctx->guided_passes++;
+    else if (guided && (rc = queue_guides(ctx, A, guide_nh, guide_ad))) return rc;   // everywhere else: exactly what mirt_render_guides queues
     HIPCHK(ctx, hipGetLastError());
     d->seeds->version++;
     if (d->acu) d->acu->version++;
+    if (o.guide_nh) o.guide_nh->version++;
+    if (o.guide_ad) o.guide_ad->version++;
     return MIRT_OK;
 }
 
@@ -1390,6 +1445,22 @@ int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try {
     o.fresh = true;
     return render_pass_impl(ctx, d, o);
 } MIRT_CATCH("mirt_render_first_pass", return MIRT_E_DEVICE)
+// mirt_render_first_pass + mirt_render_guides in one call: the checks of both before anything is queued, then -- where the plan allows
+// (pt_pass_plan.hpp fused_guides_in_pass) -- the pass's own launches write the guides (k_fusedPass GUIDES), elsewhere the guide launches follow.
+int mirt_render_first_pass_guided(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_first_pass_guided: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_render_first_pass_guided");
+    if (!normal_hits && !albedo_depth) return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: normal_hits and albedo_depth are both NULL (either may be, not both)");
+    if (d && d->struct_size == sizeof(mirt_pass_desc) && d->rays_per_pixel == 1u)
+        return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: rays_per_pixel == 1 draws its lens sample from seeds[col] (A10 code.cl:429); the guides are defined "
+                                     "for the un-jittered k x k lens grid, rays_per_pixel >= 4 (mirt_render_guides)");
+    PassOpts o;
+    o.fresh = true;
+    o.guide_nh = normal_hits;
+    o.guide_ad = albedo_depth;
+    return render_pass_impl(ctx, d, o);
+} MIRT_CATCH("mirt_render_first_pass_guided", return MIRT_E_DEVICE)
 
 // n_passes progressive passes in one call: the same results as mirt_render_first_pass (MIRT_PASSES_FRESH) or mirt_render_pass at pass_index,
 // then mirt_render_pass at pass_index + 1 .. pass_index + n_passes - 1 -- one launch (per block of a pixel's rays) that runs every sample through
@@ -1455,22 +1526,7 @@ int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_
     const uint64_t npix = (uint64_t)A.nrows * A.width;
     if (normal_hits && (rc = need(ctx, "normal_hits", normal_hits, npix * 16))) return rc;
     if (albedo_depth && (rc = need(ctx, "albedo_depth", albedo_depth, npix * 16))) return rc;
-    void* const nh = normal_hits ? normal_hits->ptr : nullptr;
-    void* const ad = albedo_depth ? albedo_depth->ptr : nullptr;
-    const bool optimistic = pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A);
-    if (optimistic) {
-        const size_t need_bytes = (size_t)((npix + 31u) / 32u) * 4u;
-        if (ctx->guide_mask_bytes < need_bytes) {
-            if (ctx->guide_mask) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->guide_mask)); ctx->guide_mask = nullptr; ctx->guide_mask_bytes = 0; }
-            HIPCHK(ctx, hipMalloc(&ctx->guide_mask, need_bytes));
-            ctx->guide_mask_bytes = need_bytes;
-        }
-        HIPCHK(ctx, hipMemsetAsync(ctx->guide_mask, 0, need_bytes, ctx->stream));
-        pt::launch_guides(ctx->stream, A, true, nh, ad, (uint32_t*)ctx->guide_mask, nullptr);
-        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, (const uint32_t*)ctx->guide_mask);
-    } else {
-        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, nullptr);
-    }
+    if ((rc = queue_guides(ctx, A, normal_hits ? normal_hits->ptr : nullptr, albedo_depth ? albedo_depth->ptr : nullptr))) return rc;
     HIPCHK(ctx, hipGetLastError());
     if (normal_hits) normal_hits->version++;
     if (albedo_depth) albedo_depth->version++;
@@ -1621,6 +1677,12 @@ int mirt_ctx_fused_passes(mirt_ctx* ctx, uint64_t* count) try {
     *count = ctx->fused_passes;
     return MIRT_OK;
 } MIRT_CATCH("mirt_ctx_fused_passes", return MIRT_E_DEVICE)
+int mirt_ctx_guided_passes(mirt_ctx* ctx, uint64_t* count) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_guided_passes: unknown context");
+    if (!count) return fail(ctx, MIRT_E_ARG, "mirt_ctx_guided_passes: null output");
+    *count = ctx->guided_passes;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_ctx_guided_passes", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_frame_fusion(mirt_ctx* ctx, int on) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_frame_fusion: unknown context");

@@ -408,11 +408,46 @@ PT_DEV float* reuse_rows() {   // [word][lane]: p.xyz, n.xyz, material id, the l
     __shared__ __attribute__((aligned(16))) float reuse_mem[kReuseWords][256];
     return &reuse_mem[0][threadIdx.x];
 }
+// The first-hit guides of the block's pixels (FusedArgs::guide_nh, guide_ad; defined in pt_kernels_guides.hip), from the registers of the pass
+// right after segment 0's closest_all -- the point k_guides takes them at, reached here by the same functions on the same ray ids, so the values
+// are k_guides's bit for bit.  The block resolves its pixels (rpp 4, 16 or 64, one contiguous segment): a pixel's samples are the rpp consecutive
+// lanes [t & ~(rpp - 1), +rpp) of ONE wave, in sample order.  Every lane walks its pixel's lanes in that order by ds_bpermute and adds what each
+// holds -- a lane that is not a hit (a dead vertex, an id past the material table, a lane past the end of the tile riding along) holds +0 in all
+// eight, and adding +0 leaves a sum that started at +0 unchanged bit for bit (such a sum is never -0), so the result is the sequential fp32 sum
+// over the HIT samples only.  The pixel's first lane stores.  One output after the other: four values and four sums are live at a time.  No LDS
+// of its own and no barrier: every lane of the wave is here (a resolving block keeps its lanes to the end) and rpp is wave-uniform.
+PT_DEV float lane_get(uint32_t lane4, float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)lane4, (int)__float_as_uint(v))); }   // v of lane lane4 / 4
+PT_DEV void guides_emit(const FusedArgs& A, const Ray& ray, const Poi& poi, bool valid, uint32_t blk) {
+    const uint32_t rpp = A.rpp, t = threadIdx.x;
+    const bool hit = valid && poi.matId >= 0 && (uint32_t)poi.matId < A.nmat;
+    const uint32_t first = (t & 63u) & ~(rpp - 1u);
+    const uint32_t pix = blk * (256u / rpp) + t / rpp;   // tile-local
+    const bool store = (t & (rpp - 1u)) == 0u && pix < A.nrows * A.width;
+    if (A.guide_nh) {
+        const float v0 = hit ? poi.n.x : 0.0f, v1 = hit ? poi.n.y : 0.0f, v2 = hit ? poi.n.z : 0.0f, v3 = hit ? 1.0f : 0.0f;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+        for (uint32_t i = 0, at = first << 2; i < rpp; ++i, at += 4u) { s0 += lane_get(at, v0); s1 += lane_get(at, v1); s2 += lane_get(at, v2); s3 += lane_get(at, v3); }
+        if (store) ((float4*)A.guide_nh)[pix] = make_float4(s0, s1, s2, s3);
+    }
+    if (A.guide_ad) {
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (hit) c = ((const float4*)A.material)[poi.matId];
+        const float v0 = c.x, v1 = c.y, v2 = c.z, v3 = hit ? ray.maxt : 0.0f;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+        for (uint32_t i = 0, at = first << 2; i < rpp; ++i, at += 4u) { s0 += lane_get(at, v0); s1 += lane_get(at, v1); s2 += lane_get(at, v2); s3 += lane_get(at, v3); }
+        if (store) ((float4*)A.guide_ad)[pix] = make_float4(s0, s1, s2, s3);
+    }
+}
 // SEG: the general form of the ray ids of a launch's segment (seg_ray); false for every contiguous one.
 // EVERY: a frame after every pass (FusedArgs::every): instantiated for resolving launches of several passes only.
-template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0, bool SEG = false, bool EVERY = false>
+// GUIDES: the pass writes the first-hit guides of its pixels too (guides_emit): instantiated for one resolving pass of one contiguous segment only
+// (MULTI 0, SEG and EVERY false).  The optimistic kernel learns its block's verdict only at the end of the path and does not carry eight sums that
+// far: it writes the guides at segment 0 whatever the verdict.  A block that defers afterwards is re-run whole by the exact kernel's redo mode,
+// which writes the same pixels' guides again, later on the same stream: those are the final ones.
+template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0, bool SEG = false, bool EVERY = false, bool GUIDES = false>
 __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_GRIDS : (FAST ? PT_FUSED_WAVES_FAST : PT_FUSED_WAVES))) k_fusedPass(const FusedArgs A, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     static_assert(!EVERY || (MULTI != 0 && PT_PARK_LDS), "a frame after every pass resolves from the park rows of the multi-pass loop");
+    static_assert(!GUIDES || (MULTI == 0 && !SEG && !EVERY), "the guides are taken from one resolving pass of one contiguous segment");
     const uint64_t n_local = (uint64_t)A.nrows * A.width * A.rpp;
     stage_block<FAST, GRIDS>(A);
     // Exact kernel in redo mode (`redo_mask`: the bits the optimistic kernel set): one thread per 32-sample word, a loop over its
@@ -520,6 +555,10 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
 #endif
       if (MULTI != 2 || !reused) {
         closest_all<FAST, GRIDS, Park>(P, ray, poi, park, defer);
+        if constexpr (GUIDES) if (seg == 0) {   // the block of the launch as at the resolve below: blockIdx alone, or the marked block of this trip
+            const uint32_t blk = FAST || stride != 256u ? blockIdx.x : blockIdx.x * 32u + (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(todo));
+            guides_emit(A, ray, poi, valid, blk);
+        }
         if (seg == 0) {
             for (uint32_t l = 0; l < P.n_lights; ++l) {  // lightRender (code.cl:600-629), primary segment only
                 if (ray.mint == ray.maxt) continue;
@@ -646,6 +685,7 @@ static void launch_seg(const dim3& grid, size_t lds, hipStream_t s, const FusedA
     else if (every) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1, SEG, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
     else if (b.passes > 1u && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
     else if (b.passes > 1u) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+    else if (!SEG && (b.guide_nh || b.guide_ad)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 0, false, false, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
     else hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 0, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
 }
 template <bool FAST, int GRIDS, int WAVES = 0>

@@ -124,6 +124,11 @@ struct FusedArgs {
     uint32_t every;
     uint32_t pass_index;     // the 1-based index of the launch's first pass
     const void* carry;       // float4[passes * nrows * width]; read only by a launch with seg_off != 0
+    // The first-hit guides written BY the pass (mirt_render_first_pass_guided, the one-launch route: pt_pass_plan.hpp fused_guides_in_pass): float4
+    // per pixel of the tile each, as launch_guides writes them; either may be null.  Both null: the pass's ordinary kernels.  One given picks the
+    // GUIDES instantiations of k_fusedPass, which exist for one resolving pass of one contiguous segment only -- the caller keeps to the route rule.
+    void* guide_nh;          // normal_hits
+    void* guide_ad;          // albedo_depth
 };
 // the optimistic kernel may run the launch: every set passed its geometry-side guard (pt_set_guard.hpp)
 inline bool all_sets_fast_ok(const FusedArgs& a) { for (uint32_t i = 0; i < a.n_sets; ++i) if (!a.sets[i].fast_ok) return false; return true; }

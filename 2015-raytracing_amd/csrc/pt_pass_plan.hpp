@@ -144,4 +144,12 @@ inline PassPlan pass_plan(const PassRequest& r) {
     return p;
 }
 
+// Whether mirt_render_first_pass_guided writes the first-hit guides from the pass's own launch (k_fusedPass GUIDES) instead of queueing
+// launch_guides behind it: the pass resolves its pixels in the kernel, as one segment and one pass, at 4, 16 or 64 rays per pixel -- a pixel's
+// samples are then rays_per_pixel consecutive lanes of ONE wave, which the kernel sums by lane shuffles.  Not at 256 rays (a pixel spans four
+// waves), not at a count that does not divide 256 or is above it, not beside a separate copyToPixel, not for several passes in one launch.
+inline bool fused_guides_in_pass(const PassPlan& p, uint32_t passes) {
+    return p.resolves && p.n_segments == 1u && passes == 1u && (p.rpp == 4u || p.rpp == 16u || p.rpp == 64u);
+}
+
 }  // namespace pt

@@ -73,6 +73,7 @@ if (cmd === "pack") {
       dump(`${opt.guides}.albedo_depth_lo.f32`, res.guidesLo.albedoDepth);
     }
     process.stderr.write(`rendered ${file} ${res.lowWidth}x${res.lowHeight} rpp ${rpp}, ${passes} pass(es)${opt.denoise ? ", filtered" : ""}, upsampled x${upscale} to ${w}x${h}: ${res.ms.toFixed(2)} ms on ${res.device}\n`);
+    process.stderr.write(`first passes that wrote their guides: ${res.guidedPasses || 0}\n`);
     process.exit(0);
   }
   const res = renderer.renderFile(file, w, h, rpp, passes, opt);
@@ -92,6 +93,7 @@ if (cmd === "pack") {
     }
   }
   process.stderr.write(`rendered ${file} ${w}x${h} rpp ${rpp}, ${passes} pass(es), ${opt.granular ? (opt.fusion ? "kernel-by-kernel, passes fused by the runtime" : "kernel-by-kernel") : "fused"}: ${res.ms.toFixed(2)} ms on ${res.device}; passes the runtime fused from enqueues: ${res.fusedPasses}\n`);
+  process.stderr.write(`first passes that wrote their guides: ${res.guidedPasses || 0}\n`);   // mirt_render_first_pass_guided's one-launch route (ctx.guidedPasses())
   if (res.routes) process.stderr.write(`gather routes per tile: ${res.routes.join(" ")}; peer access root<-tile: ${res.peerAccess.join(" ")}\n`);
 } else if (cmd === "pack-frame" || cmd === "frame") {
   if (rest.length < 4) usage();

@@ -329,6 +329,16 @@ class FusedRenderer {
     }
     this.q.renderGuides(this.passDesc(), this.normalHits, this.albedoDepth);
   }
+  // the frame's first pass and its guides in one call (queue.renderFirstPassGuided): executeRender() and renderGuides() at once
+  canRenderGuided() { return this.passes === 1 && typeof this.q.hasFirstPassGuided === "function" && this.q.hasFirstPassGuided(); }
+  executeRenderGuided(bounces) {
+    if (!this.normalHits) {
+      this.normalHits = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
+      this.albedoDepth = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
+    }
+    this.q.renderFirstPassGuided(this.passDesc(bounces), this.normalHits, this.albedoDepth);
+    this.passes++;
+  }
   readGuides() {
     const n = new Float32Array(this.npix * 4), a = new Float32Array(this.npix * 4);
     this.q.enqueueReadBuffer(this.normalHits, false, 0, n.byteLength, n, []);
@@ -475,15 +485,19 @@ function renderFile(file, width, height, rpp, passes, opt) {
   if ((opt.guides || opt.denoise) && opt.granular) throw new Error("--guides and --denoise are the fused host's (mirt_render_guides, mirt_filter_atrous): not with the kernel-by-kernel host");
   if (opt.passesInOneLaunch && opt.granular) throw new Error("passes in one launch are the fused pass's (mirt_render_passes): not with the kernel-by-kernel host");
   const R = opt.granular ? new GranularRenderer(packed, opt) : new FusedRenderer(packed, opt);
+  // one pass and its guides wanted: the pass writes them too (mirt_render_first_pass_guided), the files are the same bit for bit
+  const guided = !!(opt.guides || opt.denoise) && passes === 1 && !opt.passesInOneLaunch && R.canRenderGuided();
   R.q.timerStart();
-  if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces, { everyPass: opt.everyPass });
+  if (guided) R.executeRenderGuided(opt.bounces);
+  else if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces, { everyPass: opt.everyPass });
   else for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
   const ms = R.q.timerStopMs();
   const res = { pixel: R.readPixels(), radiance: opt.granular ? radianceSums(R.readAcu(), rpp) : R.readRadiance(), ms: ms,
-                device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: R.ctx.fusedPasses ? R.ctx.fusedPasses() : 0 };
+                device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: R.ctx.fusedPasses ? R.ctx.fusedPasses() : 0,
+                guidedPasses: R.ctx.guidedPasses ? R.ctx.guidedPasses() : 0 };
   if (opt.everyPass) res.frames = R.readFrames();
-  if (opt.guides) { R.renderGuides(); res.guides = R.readGuides(); }
-  if (opt.denoise) { R.denoise(opt.denoise, !!opt.guides); res.denoised = R.readDenoised(); }
+  if (opt.guides) { if (!guided) R.renderGuides(); res.guides = R.readGuides(); }
+  if (opt.denoise) { R.denoise(opt.denoise, guided || !!opt.guides); res.denoised = R.readDenoised(); }
   R.release();
   if (ownCtx) ownCtx.release();
   return res;
@@ -509,9 +523,11 @@ function renderUpscaled(file, width, height, rpp, passes, factor, opt) {
   const nh = mk(npix * 16), ad = mk(npix * 16), up = mk(npix * 16), px = mk(npix * 4);
   try {
     R.q.timerStart();
-    if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces);
+    const guided = passes === 1 && !opt.passesInOneLaunch && R.canRenderGuided();   // the low frame's one pass writes the low guides too
+    if (guided) R.executeRenderGuided(opt.bounces);
+    else if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces);
     else for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
-    R.renderGuides();
+    if (!guided) R.renderGuides();
     if (opt.denoise) R.denoise(opt.denoise, true);
     R.q.renderGuides(Object.assign(R.passDesc(), { width: width, height: height, row0: 0, nrows: height, cam: hi.cam }), nh, ad);
     R.q.upsampleFrame(Object.assign({}, opt.upsample, { width: width, height: height, factor: factor, tone: 1 / (rpp * (R.passes - 1)),
@@ -521,7 +537,7 @@ function renderUpscaled(file, width, height, rpp, passes, factor, opt) {
     const read = (b, a) => { R.q.enqueueReadBuffer(b, true, 0, a.byteLength, a, []); return a; };
     const res = { pixel: read(px, new Uint8ClampedArray(npix * 4)), upsampled: read(up, new Float32Array(npix * 4)), radiance: R.readRadiance(), ms: ms,
                   guides: { normalHits: read(nh, new Float32Array(npix * 4)), albedoDepth: read(ad, new Float32Array(npix * 4)) }, guidesLo: R.readGuides(),
-                  device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: 0, lowWidth: wl, lowHeight: hl };
+                  device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: 0, guidedPasses: R.ctx.guidedPasses ? R.ctx.guidedPasses() : 0, lowWidth: wl, lowHeight: hl };
     if (opt.denoise) res.denoised = R.readDenoised();
     R.q.finish();
     return res;

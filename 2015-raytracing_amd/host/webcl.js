@@ -190,6 +190,15 @@ class WebCLCommandQueue {
     const d = this._passDesc(desc);
     wrap(() => native().renderGuides(this.ctx.h, d, normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
   }
+  // ---- extension: a frame's first pass and its guide buffers in one call (mirt_render_first_pass_guided): every buffer ends as after
+  // renderPass(desc with firstPass) followed by renderGuides(desc, normalHits, albedoDepth) -- where the pass resolves its pixels at 4, 16 or 64 rays
+  // per pixel the pass's own launch writes the guides (ctx.guidedPasses() counts those calls), elsewhere the guide launches follow it.
+  // hasFirstPassGuided(): the loaded library has the entry point
+  hasFirstPassGuided() { return typeof native().renderFirstPassGuided === "function"; }
+  renderFirstPassGuided(desc, normalHits, albedoDepth) {
+    const d = this._passDesc(desc);
+    wrap(() => native().renderFirstPassGuided(this.ctx.h, d, normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
+  }
   // ---- extension: the edge-avoiding a-trous filter of a frame on the device (mirt_filter_atrous; include/mirt.h has the definition).  desc:
   // {width, height, tone: 1 / (raysPerPixel * passes), radiance, normalHits, albedoDepth, filtered?, pixel?} plus any of iterations,
   // normalPowerLog2, sigmaDepth, sigmaColour, demodulate (webcl.FILTER_DEFAULTS where left out) and structure ("direct" | "tiled": one kernel
@@ -343,6 +352,8 @@ class WebCLContext {
   // (mirt_ctx_create) stays at 0 unless asked.
   setFusion(level) { wrap(() => native().ctxSetFusion(this.h, level)); }
   fusedPasses() { return wrap(() => native().ctxFusedPasses(this.h)); }
+  // mirt_ctx_guided_passes: renderFirstPassGuided calls whose pass wrote the guides itself
+  guidedPasses() { return typeof native().ctxGuidedPasses === "function" ? wrap(() => native().ctxGuidedPasses(this.h)) : 0; }
   // extension (mirt_ctx_set_frame_fusion): the Assign04 / Assign07 pages' frame stream -- initTrace, then molTrace and / or meshTrace -- runs as one
   // launch and the Ray buffer is not written.  Off unless asked for here or with MIRT_FRAME_FUSION=1 in the environment.
   setFrameFusion(on) { wrap(() => native().ctxSetFrameFusion(this.h, on ? 1 : 0)); }

@@ -122,6 +122,8 @@ SYMBOLS = {
     "mirt_render_first_pass": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc)]),
     "mirt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32]),
     "mirt_render_guides": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
+    "mirt_render_first_pass_guided": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
+    "mirt_ctx_guided_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
     "mirt_upsample_guided": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc)]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -476,6 +478,17 @@ class Context:
         """First-hit guide buffers of desc's row tile (mirt_render_guides): float4 per pixel, (sum of the hit samples' normals, hits) and
         (sum of their material colours, sum of their hit distances).  Either buffer may be None, not both; desc.seeds / acu are not touched."""
         self._chk(lib().mirt_render_guides(self.h, C.byref(desc), normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
+    def render_first_pass_guided(self, desc, normal_hits=None, albedo_depth=None):
+        """A frame's first pass and its guide buffers in one call (mirt_render_first_pass_guided): every buffer ends as after
+        render_pass(desc, fresh=True) followed by render_guides(desc, normal_hits, albedo_depth).  Either guide may be None, not both."""
+        self._chk(lib().mirt_render_first_pass_guided(self.h, C.byref(desc), normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
+    def guided_passes(self):
+        """how many render_first_pass_guided calls of this context wrote the guides from the pass's own launch (mirt_ctx_guided_passes)"""
+        n = C.c_uint64()
+        self._chk(lib().mirt_ctx_guided_passes(self.h, C.byref(n)))
+        return n.value
 
     def filter_atrous(self, width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,
                       normal_power_log2=None, sigma_depth=None, sigma_colour=None, demodulate=None, structure=None):

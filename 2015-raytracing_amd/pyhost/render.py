@@ -299,6 +299,38 @@ class FusedRenderer:
             for b in (nh, ad, out, pix):
                 b.release()
 
+    def execute_render_guided(self, bounces=5):
+        """The frame's first pass and its first-hit guides in one call (mirt_render_first_pass_guided): execute_render(fresh=True) and guides()
+        at once, into guide buffers this renderer then owns -- self.normal_hits, self.albedo_depth, float4 per pixel of the tile, on the
+        device until release().  Returns them as two float32 arrays [pixels, 4]."""
+        if self.passes != 1:
+            raise mirt.MirtError(-1, "FusedRenderer.execute_render_guided: the frame's first pass only")
+        if not self.nrays:
+            self.passes += 1
+            return np.zeros((0, 4), np.float32), np.zeros((0, 4), np.float32)
+        self.normal_hits, self.albedo_depth = self._frames("normal_hits", self.npix * 16), self._frames("albedo_depth", self.npix * 16)
+        d = self.dev.pass_desc(self.seeds, self.acu, self.pixel, self.radiance, pass_index=1, bounces=bounces, row0=self.row0, nrows=self.nrows)
+        self.ctx.render_first_pass_guided(d, self.normal_hits, self.albedo_depth)
+        self.passes += 1
+        return (self.normal_hits.read(np.float32, count=4 * self.npix).reshape(-1, 4), self.albedo_depth.read(np.float32, count=4 * self.npix).reshape(-1, 4))
+
+    def denoised_first_pass(self, bounces=5, **params):
+        """execute_render_guided, then the a-trous filter of that one-pass frame (mirt_filter_atrous) guided by the buffers it wrote: what
+        execute_render(fresh=True) and denoised() give, without the second trace of the primary rays.  params and the result as denoised()."""
+        if self.radiance is None:
+            raise mirt.MirtError(-1, "FusedRenderer.denoised_first_pass: needs want_radiance")
+        self.execute_render_guided(bounces)
+        if not self.npix:
+            return np.zeros((0, 4), np.uint8), np.zeros((0, 4), np.float32)
+        out, pix = self.ctx.buffer(self.npix * 16), self.ctx.buffer(self.npix * 4)
+        try:
+            tone = np.float32(1.0 / self.s.rpp)
+            self.ctx.filter_atrous(self.s.width, self.nrows, tone, self.radiance, self.normal_hits, self.albedo_depth, filtered=out, pixel=pix, **params)
+            return pix.read(np.uint8).reshape(-1, 4), out.read(np.float32).reshape(-1, 4)
+        finally:
+            out.release()
+            pix.release()
+
     def _frames(self, name, nbytes):
         """a frame buffer of at least nbytes, kept for the next call"""
         b = getattr(self, name, None)
@@ -310,7 +342,8 @@ class FusedRenderer:
         return b
 
     def release(self):
-        for b in (self.seeds, self.acu, self.pixel, self.radiance, getattr(self, "_frame_pixel", None), getattr(self, "_frame_radiance", None)):
+        for b in (self.seeds, self.acu, self.pixel, self.radiance, getattr(self, "_frame_pixel", None), getattr(self, "_frame_radiance", None),
+                  getattr(self, "normal_hits", None), getattr(self, "albedo_depth", None)):
             if b:
                 b.release()
         self.dev.release()
@@ -348,10 +381,15 @@ class UpscaledRenderer:
         to those already rendered; denoise: filter the low frame first (filter_params: mirt.FILTER_DEFAULTS where left out); params:
         normal_power_log2, sigma_depth, demodulate of the upsampler (mirt.UPSAMPLE_DEFAULTS where left out)."""
         ctx, lo = self.ctx, self.lo
-        for _ in range(int(passes)):
-            lo.execute_render(bounces, fresh=(lo.passes == 1))
-        self.tone = np.float32(1.0 / (lo.s.rpp * (lo.passes - 1)))
-        ctx.render_guides(lo.dev.pass_desc(None, None), self.nh_lo, self.ad_lo)
+        if int(passes) == 1 and lo.passes == 1:   # exactly the frame's first pass: it writes the low guides itself (mirt_render_first_pass_guided)
+            ctx.render_first_pass_guided(lo.dev.pass_desc(lo.seeds, lo.acu, lo.pixel, lo.radiance, pass_index=1, bounces=bounces), self.nh_lo, self.ad_lo)
+            lo.passes += 1
+            self.tone = np.float32(1.0 / lo.s.rpp)
+        else:
+            for _ in range(int(passes)):
+                lo.execute_render(bounces, fresh=(lo.passes == 1))
+            self.tone = np.float32(1.0 / (lo.s.rpp * (lo.passes - 1)))
+            ctx.render_guides(lo.dev.pass_desc(None, None), self.nh_lo, self.ad_lo)
         radiance = lo.radiance
         if denoise:
             if self.filtered is None:

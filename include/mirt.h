@@ -244,6 +244,29 @@ MIRT_API int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* desc, uint3
  * (code.cl:429) and is refused (MIRT_E_ARG).  Ray ids are global: a tile's guides equal the same rows of the whole frame's.  Not while capturing
  * (MIRT_E_ARG).  MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
 MIRT_API int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* desc, mirt_buf* normal_hits, mirt_buf* albedo_depth);
+/* A frame's FIRST PASS AND ITS GUIDES in one call.  Every buffer the caller passes -- seeds, acu if given, pixel, radiance, normal_hits,
+ * albedo_depth -- ends bit for bit as after mirt_render_first_pass(ctx, desc) followed by mirt_render_guides(ctx, desc, normal_hits,
+ * albedo_depth): the guides are the values the pass itself holds right after its primary rays' closest-hit stage, before lightRender, and
+ * mirt_render_guides re-creates every primary ray and repeats that search only to arrive at them.  `desc` is the pass's descriptor, unchanged.
+ * Checks: those of both calls, all before anything is queued -- when one fails nothing is written at all, neither the guides nor the pass's
+ * buffers.  Either guide output may be NULL, not both (MIRT_E_ARG); rays_per_pixel == 1 is MIRT_E_ARG (the guides' own rule); a guide buffer
+ * smaller than the tile's pixels x 16 B is MIRT_E_RANGE; a guide buffer whose bytes are, or overlap, those of any buffer of the descriptor or
+ * of the other guide is MIRT_E_ARG; not while capturing (MIRT_E_ARG).  A held command stream (mirt_ctx_set_fusion) is flushed first.
+ * ROUTE.  The call works at every k x k count above 1; which launches it queues is the library's matter.  ONE LAUNCH (per kernel of the
+ * optimistic / exact pair): where the pass resolves its pixels in the kernel (see mirt_render_first_pass) as one segment with rays_per_pixel
+ * 4, 16 or 64, a pixel's samples are rays_per_pixel consecutive lanes of one wave, and the pass's kernel adds their eight values in sample
+ * order and writes the guides itself.  EVERYWHERE ELSE -- 256 rays (a pixel spans four waves), counts that do not divide 256 or are above it,
+ * MIRT_INPASS_RESOLVE=0, acu given with neither pixel nor radiance -- the call queues the pass and then the guide launches exactly as the two
+ * calls would.  MIRT_GUIDED_PASS=0 in the environment forces that everywhere (an A/B switch).  mirt_ctx_guided_passes: how many calls of this
+ * context took the one-launch route.  What the call does not do: several passes in one launch (mirt_render_passes has no guided form), a
+ * one-launch route at 256 rays per pixel, guides from a later pass (mirt_render_pass) -- they are the same for every pass of a frame, so
+ * the first pass is where they are taken.
+ * The optimistic kernel writes a block's guides before it knows whether the block stays inside the guard windows; a block that does not is
+ * re-run whole by the exact kernel, which writes the same pixels' guides again, later on the same stream.  The outputs are therefore final
+ * when the call's launches have completed (stream order, mirt_finish), like every other output of the pass -- not before.
+ * MIRT_ABI_VERSION is unchanged: a host detects the two entry points by their symbols. */
+MIRT_API int mirt_render_first_pass_guided(mirt_ctx* ctx, const mirt_pass_desc* desc, mirt_buf* normal_hits, mirt_buf* albedo_depth);
+MIRT_API int mirt_ctx_guided_passes(mirt_ctx* ctx, uint64_t* count);
 /* Edge-avoiding A-TROUS FILTER of a few-rays-per-pixel frame, guided by the first-hit guide buffers: `radiance` as a pass writes it (un-scaled
  * sums), `normal_hits` and `albedo_depth` as mirt_render_guides writes them, all float4 per pixel of a width x height image -- a whole frame, or a
  * gathered one.  Everything stays on the device; the working images live in the context's scratch buffer.

@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""tests/pass_guided_child.py -- run by tests/test_pass_guided.py in a process of its own, for what a process fixes when it starts:
+  default : MIRT_CONTRACT=default, so that pyhost loads libmirt_default.so -- mirt_render_first_pass_guided of the library built for the reference's
+            own build options against that library's two calls: cornell 7 x 5 x 16 (the last block partial) and own_flat, whose blocks defer;
+  waves5  : MIRT_GRID_WAVES=5 (read once per process) -- the 5-wave build of the optimistic grid kernels, cornell_teapot3 24 x 16 x 4 and x 16.
+Prints one JSON object per case; exits non-zero on the first difference, naming it."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as graft  # noqa: E402
+from pass_guided_common import compare, packed  # noqa: E402
+
+CASES = {"default": [("cornell_32x24_r4", 7, 5, 16, False), ("own_flat_32x24_r4", 32, 24, 4, True)],
+         "waves5": [("cornell_teapot3_32x24_r4", 24, 16, 4, False), ("cornell_teapot3_32x24_r4", 24, 16, 16, False)]}
+
+
+def main(mode):
+    graft.load_package()
+    from raytracing_amd.pyhost import mirt
+    if mode == "default":
+        assert os.path.basename(mirt.LIB_PATH) == "libmirt_default.so", mirt.LIB_PATH
+    else:
+        assert os.environ.get("MIRT_GRID_WAVES") == "5"
+    ctx = mirt.Context(0)
+    try:
+        for name, w, h, rpp, defers in CASES[mode]:
+            for exact_only in (False, True):
+                ctx.set_exact_only(exact_only)
+                diff, routed, deferred, _ = compare(ctx, packed(name, w, h, rpp), f"{name} {w}x{h} x{rpp} exact_only={exact_only}")
+                if not diff and routed != 1:
+                    diff = f"{name}: the call did not take the one-launch route"
+                if not diff and defers and not exact_only and deferred == 0:
+                    diff = f"{name} no longer defers: the exact kernel's rewrite of a deferred block's guides is not exercised"
+                print(json.dumps({"scene": name, "rpp": rpp, "exact_only": exact_only, "ok": not diff, "deferred": int(deferred), "difference": diff}), flush=True)
+                if diff:
+                    return 1
+    finally:
+        ctx.set_exact_only(False)
+        ctx.destroy()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1]))
