@@ -974,6 +974,30 @@ int mirt_enqueue(mirt_ctx* ctx, mirt_kernel* k, unsigned dim, const size_t* glob
     return launch_kernel(ctx, S, k->args, dim, global);
 } MIRT_CATCH("mirt_enqueue", return MIRT_E_DEVICE)
 
+// The buffer rules of the Assign04 / Assign07 trace stages, for launch_kernel's frame kernels and for render_frame_impl: each checks the stage's buffers
+// (`who`: the kernel or the entry point the message names), prepares the triangles the stage reads, and fills the stage's fields of the launch's arguments.
+static int frame_a04_mesh(mirt_ctx* ctx, const std::string& who, uint32_t T, mirt_buf* t_pos, const mirt_buf* t_normal, const mirt_buf* t_mindex, const mirt_buf* m_color, pt::FrameArgs& A) {
+    if (int rc = need(ctx, (who + " t_pos").c_str(), t_pos, (uint64_t)T * 48)) return rc;
+    if (int rc = need(ctx, (who + " t_normal").c_str(), t_normal, (uint64_t)T * 48)) return rc;
+    if (int rc = need(ctx, (who + " t_mindex").c_str(), t_mindex, (uint64_t)T * 4)) return rc;
+    if (int rc = need(ctx, (who + " m_color").c_str(), m_color, 16)) return rc;
+    if (int rc = ensure_prepared(ctx, t_pos, T)) return rc;
+    A.t_size = T; A.prep = t_pos->prep; A.normals = t_normal->ptr; A.mindex = t_mindex->ptr; A.mcolor = m_color->ptr; A.ncolors = (uint32_t)(m_color->bytes / 16);
+    return MIRT_OK;
+}
+static int frame_a07_mesh(mirt_ctx* ctx, const std::string& who, const float* bound, uint32_t n_slabs, mirt_buf* slab_size, mirt_buf* t_pos, const mirt_buf* t_normal, pt::FrameArgs& A) {
+    if (int rc = check_grid(ctx, (who + " mesh grid").c_str(), slab_size, n_slabs, t_pos, 48, t_normal, nullptr)) return rc;
+    if (int rc = ensure_prepared(ctx, t_pos, slab_size->off_last)) return rc;
+    memcpy(A.bound, bound, 32); A.n_slabs = n_slabs; A.prep = t_pos->prep; A.normals = t_normal->ptr; A.slab_size = slab_size->ptr; A.n_slots = slab_size->off_last;
+    return MIRT_OK;
+}
+// s_mindex / m_color are bound by the reference host but never read by the kernel (A07 code.cl:459-460)
+static int frame_a07_mol(mirt_ctx* ctx, const std::string& who, const float* bound, uint32_t n_slabs, mirt_buf* slab_size, const mirt_buf* s_atoms, pt::FrameArgs& A) {
+    if (int rc = check_grid(ctx, (who + " molecule grid").c_str(), slab_size, n_slabs, s_atoms, 16, nullptr, nullptr)) return rc;
+    memcpy(A.bound, bound, 32); A.n_slabs = n_slabs; A.atoms = s_atoms->ptr; A.mol_slab_size = slab_size->ptr;
+    return MIRT_OK;
+}
+
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -1145,26 +1169,15 @@ static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& 
             if ((rc = need(ctx, "rays", A(K::rays), npx * kRayBytes))) return rc;
             if (S.id == pt::K_a04_initTrace) pt::launch_frame_initTrace(st, false, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, nullptr, g0, g1);
             else if (S.id == pt::K_a07_initTrace) pt::launch_frame_initTrace(st, true, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, A(pt::a07_initTrace::bound), g0, g1);
-            else if (S.id == pt::K_a04_meshTrace) {
-                namespace M = pt::a04_meshTrace;
-                const uint32_t T = A(M::t_size);
-                if ((rc = need(ctx, "meshTrace t_pos", A(M::t_pos), (uint64_t)T * 48))) return rc;
-                if ((rc = need(ctx, "meshTrace t_normal", A(M::t_normal), (uint64_t)T * 48))) return rc;
-                if ((rc = need(ctx, "meshTrace t_mindex", A(M::t_mindex), (uint64_t)T * 4))) return rc;
-                if ((rc = need(ctx, "meshTrace m_color", A(M::m_color), 16))) return rc;
-                if ((rc = ensure_prepared(ctx, A(M::t_pos), T))) return rc;
-                pt::launch_a04_meshTrace(st, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, T, A(M::t_pos)->prep, A(M::t_normal)->ptr, A(M::t_mindex)->ptr, A(M::m_color)->ptr,
-                                         (uint32_t)(A(M::m_color)->bytes / 16), g0, g1);
-            } else if (S.id == pt::K_a07_molTrace) {
-                namespace M = pt::a07_molTrace;
-                // s_mindex / m_color are bound by the reference host but never read by the kernel (code.cl:459-460)
-                if ((rc = check_grid(ctx, "molTrace grid", A(M::slab_size), A(M::n_slabs), A(M::s_atoms), 16, nullptr, nullptr))) return rc;
-                pt::launch_a07_molTrace(st, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, A(M::s_atoms)->ptr, A(M::bound), A(M::n_slabs), A(M::slab_size)->ptr, g0, g1);
-            } else {
-                namespace M = pt::a07_meshTrace;
-                if ((rc = check_grid(ctx, "meshTrace grid", A(M::slab_size), A(M::n_slabs), A(M::t_pos), 48, A(M::t_normal), nullptr))) return rc;
-                if ((rc = ensure_prepared(ctx, A(M::t_pos), A(M::slab_size)->off_last))) return rc;
-                pt::launch_a07_meshTrace(st, A(K::pixels)->ptr, A(K::fcam), A(K::rays)->ptr, A(M::t_pos)->prep, A(M::t_normal)->ptr, A(M::bound), A(M::n_slabs), A(M::slab_size)->ptr, A(M::slab_size)->off_last, g0, g1);
+            else {
+                namespace M4 = pt::a04_meshTrace; namespace MM = pt::a07_molTrace; namespace MT = pt::a07_meshTrace;
+                pt::FrameArgs F = {};
+                memcpy(F.cam, A(K::fcam), 64); F.pixels = A(K::pixels)->ptr; F.rays = A(K::rays)->ptr; F.gx = g0; F.gy = g1;
+                if (S.id == pt::K_a04_meshTrace) rc = frame_a04_mesh(ctx, S.name, A(M4::t_size), A(M4::t_pos), A(M4::t_normal), A(M4::t_mindex), A(M4::m_color), F);
+                else if (S.id == pt::K_a07_molTrace) rc = frame_a07_mol(ctx, S.name, A(MM::bound), A(MM::n_slabs), A(MM::slab_size), A(MM::s_atoms), F);
+                else rc = frame_a07_mesh(ctx, S.name, A(MT::bound), A(MT::n_slabs), A(MT::slab_size), A(MT::t_pos), A(MT::t_normal), F);
+                if (rc) return rc;
+                pt::launch_frame_stage(st, F, S.id == pt::K_a04_meshTrace ? pt::FS_A04 : S.id == pt::K_a07_molTrace ? pt::FS_MOL : pt::FS_MESH);
             }
             break;
         }
@@ -1715,30 +1728,17 @@ static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d) {
     int rc;
     if ((rc = need(ctx, "mirt_render_frame pixel", d->pixel, npx * 4))) return rc;
     if (d->rays && (rc = need(ctx, "mirt_render_frame rays", d->rays, npx * kRayBytes))) return rc;
-    pt::FrameArgs A;
-    memset(&A, 0, sizeof A);
+    pt::FrameArgs A = {};
     memcpy(A.cam, d->cam, 64);
-    A.assign = d->assign; A.gx = cols; A.gy = rows;
+    A.assign = d->assign; A.mesh = mesh; A.mol = mol; A.gx = cols; A.gy = rows;
     if (d->assign == 4) {
-        const uint32_t T = d->t_size;
         if (!d->t_normal || !d->t_mindex || !d->t_mcolor) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: the Assign04 mesh needs t_normal, t_mindex and t_mcolor");
-        if ((rc = need(ctx, "mirt_render_frame t_pos", d->t_pos, (uint64_t)T * 48))) return rc;
-        if ((rc = need(ctx, "mirt_render_frame t_normal", d->t_normal, (uint64_t)T * 48))) return rc;
-        if ((rc = need(ctx, "mirt_render_frame t_mindex", d->t_mindex, (uint64_t)T * 4))) return rc;
-        if ((rc = need(ctx, "mirt_render_frame t_mcolor", d->t_mcolor, 16))) return rc;
-        if ((rc = ensure_prepared(ctx, d->t_pos, T))) return rc;
-        A.t_size = T; A.prep = d->t_pos->prep; A.normals = d->t_normal->ptr; A.mindex = d->t_mindex->ptr; A.mcolor = d->t_mcolor->ptr;
-        A.ncolors = (uint32_t)(d->t_mcolor->bytes / 16);
+        if ((rc = frame_a04_mesh(ctx, "mirt_render_frame", d->t_size, d->t_pos, d->t_normal, d->t_mindex, d->t_mcolor, A))) return rc;
     } else {
-        memcpy(A.bound, d->bounds, 32);
-        A.n_slabs = d->n_slabs; A.mesh = mesh; A.mol = mol;
         if (mol && !d->s_slab_size) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: the molecule needs s_slab_size");
         if (mesh && (!d->t_normal || !d->t_slab_size)) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: the Assign07 mesh needs t_normal and t_slab_size");
-        if (mol && (rc = check_grid(ctx, "mirt_render_frame molecule grid", d->s_slab_size, d->n_slabs, d->s_atoms, 16, nullptr, nullptr))) return rc;
-        if (mesh && (rc = check_grid(ctx, "mirt_render_frame mesh grid", d->t_slab_size, d->n_slabs, d->t_pos, 48, d->t_normal, nullptr))) return rc;
-        if (mesh && (rc = ensure_prepared(ctx, d->t_pos, d->t_slab_size->off_last))) return rc;
-        if (mol) { A.atoms = d->s_atoms->ptr; A.mol_slab_size = d->s_slab_size->ptr; }
-        if (mesh) { A.prep = d->t_pos->prep; A.normals = d->t_normal->ptr; A.slab_size = d->t_slab_size->ptr; A.n_slots = d->t_slab_size->off_last; }
+        if (mol && (rc = frame_a07_mol(ctx, "mirt_render_frame", d->bounds, d->n_slabs, d->s_slab_size, d->s_atoms, A))) return rc;
+        if (mesh && (rc = frame_a07_mesh(ctx, "mirt_render_frame", d->bounds, d->n_slabs, d->t_slab_size, d->t_pos, d->t_normal, A))) return rc;
     }
     A.pixels = d->pixel->ptr;
     A.rays = d->rays ? d->rays->ptr : nullptr;

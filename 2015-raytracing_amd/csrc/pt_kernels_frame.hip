@@ -89,10 +89,9 @@ __global__ void __launch_bounds__(256) k_frame_initTrace(uchar4* pixels, F16 cam
     pixels[(size_t)cam.cols * row + col] = make_uchar4(0, 0, 0, 255);
 }
 
-PT_DEV f3 interp_normal(const float4* normals, uint32_t i, float beta, float gamma) {
-    const float4* nn = normals + 3u * (size_t)i;
-    float w = 1.0f - beta - gamma;
-    return norm3(fma3(gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(beta, ld3(nn[1])))));
+PT_DEV uchar4 parity_colour(int hx, int hy, int hz, float shade) {   // A07 code.cl:463-469, 616-622
+    const float k = shade * 127.0f;
+    return make_uchar4(f2u8((float)((hx % 2) + 1) * k), f2u8((float)((hy % 2) + 1) * k), f2u8((float)((hz % 2) + 1) * k), 255);
 }
 
 // ---- Assign04 meshTrace: every pixel against every triangle, wave-uniform loop --------------------
@@ -141,7 +140,7 @@ __global__ void __launch_bounds__(256) k_a04_meshTrace(uchar4* pixels, F16 cam16
     }
     if (champ_i >= t_size) return;
     rays[pix].maxt = champ_t;
-    f3 n = interp_normal(normals, champ_i, cb, cg);
+    f3 n = interp_normal(normals + 3u * (size_t)champ_i, cb, cg);
     float shade = cl_clamp(dot3(cam.W, n), 0.0f, 1.0f);
     uint32_t m = mindex[champ_i];
     if (m >= ncolors) return;  // foreign-memory guard (the reference would read out of bounds)
@@ -222,91 +221,21 @@ __global__ void __launch_bounds__(256) k_a07_meshTrace(uchar4* pixels, F16 cam16
     }
     if (champ_i == UINT32_MAX) return;
     rays[pix].maxt = champ_t;
-    f3 n = interp_normal(normals, champ_i, cb, cg);
+    f3 n = interp_normal(normals + 3u * (size_t)champ_i, cb, cg);
     float shade = cl_clamp(dot3(cam.W, n), 0.0f, 1.0f);
-    float k = shade * 127.0f;                              // A07 code.cl:616-622
-    pixels[pix] = make_uchar4(f2u8((float)((hx % 2) + 1) * k), f2u8((float)((hy % 2) + 1) * k), f2u8((float)((hz % 2) + 1) * k), 255);
+    pixels[pix] = parity_colour(hx, hy, hz, shade);
 }
 
-// ---- Assign07 molTrace (code.cl:337-473): the same grid walk over atoms {c, r*r}; colour = parity of the hit cell x fake shade.
-// The hit record keeps the CELL of the champion (champ_slab, code.cl:402, 425-429): the walk ends once any cell produced one.
-__global__ void __launch_bounds__(256) k_a07_molTrace(uchar4* pixels, F16 cam16, RayAoS* rays, const float4* atoms, Box8 bound8, uint32_t n_slabs,
-                                                       const uint32_t* slab_size, uint32_t gx, uint32_t gy) {
-    const Cam cam = mk_cam(cam16);
-    uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t row = blockIdx.y * blockDim.y + threadIdx.y;
-    if (col >= gx || row >= gy || col >= cam.cols || row >= cam.rows) return;
-    const size_t pix = (size_t)cam.cols * row + col;
-    Ray ray = load_ray48(&rays[pix]);
-    if (ray.mint == ray.maxt) return;
-    const Box bound = mk_box(bound8);
-    BoxHit bh = inter_aabb(ray, bound);
-    if (!bh.v) return;
-    Axis ax = axis_setup(ray.o.x, ray.d.x, bh.tmin, bound.lo.x, bound.hi.x, n_slabs);
-    Axis ay = axis_setup(ray.o.y, ray.d.y, bh.tmin, bound.lo.y, bound.hi.y, n_slabs);
-    Axis az = axis_setup(ray.o.z, ray.d.z, bh.tmin, bound.lo.z, bound.hi.z, n_slabs);
-    const SphereRay sr = sphere_ray<false>(ray.d);
-    float champ_t = ray.maxt;
-    uint32_t champ_i = UINT32_MAX;
-    int hx = 0, hy = 0, hz = 0;
-    const uint32_t zs = n_slabs * n_slabs, ys = n_slabs;
-    // phase A / phase B as in trace_dda (pt_trace.hpp): close and open cells until every live lane holds an atom, then one test each
-    float t = bh.tmin, cmin = t, cmax = cl_min(cl_min(ax.tnext, ay.tnext), az.tnext);
-    uint32_t cell = __umul24((uint32_t)az.slab, zs) + __umul24((uint32_t)ay.slab, ys) + (uint32_t)ax.slab;
-    uint32_t i = slab_size[cell], end = slab_size[cell + 1];
-    for (;;) {
-        bool alive = true;
-        while (i == end) {
-            if (champ_i != UINT32_MAX) { alive = false; break; }
-            t = cmax;
-            if (t == ax.tnext) {
-                ax.tnext += ax.dt;
-                ax.slab += ax.dslab;
-                if (t >= bh.tmax || ax.slab == ax.limit) { alive = false; break; }
-            } else if (t == ay.tnext) {
-                ay.tnext += ay.dt;
-                ay.slab += ay.dslab;
-                if (t >= bh.tmax || ay.slab == ay.limit) { alive = false; break; }
-            } else {
-                az.tnext += az.dt;
-                az.slab += az.dslab;
-                if (t >= bh.tmax || az.slab == az.limit) { alive = false; break; }
-            }
-            cmin = t;
-            cmax = cl_min(cl_min(ax.tnext, ay.tnext), az.tnext);
-            cell = __umul24((uint32_t)az.slab, zs) + __umul24((uint32_t)ay.slab, ys) + (uint32_t)ax.slab;
-            i = slab_size[cell];
-            end = slab_size[cell + 1];
-        }
-        if (!alive) break;
-        float ti;
-        const bool hit = sph_test(ray.o, ray.d, sr, cmin, cmax, atoms[i], ti);
-        if (hit && ti < champ_t) { champ_t = ti; champ_i = i; hx = ax.slab; hy = ay.slab; hz = az.slab; }
-        ++i;
-    }
-    if (champ_i == UINT32_MAX) return;
-    rays[pix].maxt = champ_t;
-    const f3 ip = fma3(champ_t, ray.d, ray.o);
-    const float shade = cl_clamp(dot3(cam.W, norm3(sub3(ip, ld3(atoms[champ_i])))), 0.0f, 1.0f);   // code.cl:455-457
-    const float k = shade * 127.0f;                                                                // code.cl:463-469
-    pixels[pix] = make_uchar4(f2u8((float)((hx % 2) + 1) * k), f2u8((float)((hy % 2) + 1) * k), f2u8((float)((hz % 2) + 1) * k), 255);
-}
-
-// ---- the whole Assign04 / Assign07 frame in one launch (mirt_render_frame) ---------------------------------------------------------------
-// initTrace + the trace kernel(s) above on one thread per pixel, the ray in registers: no 48-byte ray goes out to memory and comes back between two
-// launches.  A stage below is its kernel's body on a ray it is handed instead of one it loads: every early return of the kernel is a return that
-// leaves the colour as it was (black, or what the stage before left -- what initTrace's and molTrace's stores leave in `pixels` today), the store of
-// rays[pix].maxt is an assignment to ray.maxt.  The kernel stores the pixel once, and the finished ray once when a ray buffer is given (RAYS): the
-// same 40 bytes the launches leave there.  Which stages run is the template parameter STAGES; the walks have no run-time switch.
-enum FrameStage : uint32_t { FS_A04 = 1u, FS_MESH = 2u, FS_MOL = 4u };
-
-PT_DEV uchar4 parity_colour(int hx, int hy, int hz, float shade) {   // A07 code.cl:463-469, 616-622
-    const float k = shade * 127.0f;
-    return make_uchar4(f2u8((float)((hx % 2) + 1) * k), f2u8((float)((hy % 2) + 1) * k), f2u8((float)((hz % 2) + 1) * k), 255);
-}
+// ---- the trace stages on a ray in registers ------------------------------------------------------------------------------------------------
+// A stage is a trace kernel's work on a ray it is handed instead of one it loads.  A hit sets ray.maxt and returns true; a miss -- mint == maxt, a
+// ray outside the box, no champion -- returns false and changes nothing.  A hit that shades sets `colour`, alpha 255; a miss, and an Assign04 hit
+// whose mindex names no colour, leave it as it was (black, or what the stage before left).  The one-launch kernel (k_frame_fused) runs its stages
+// in a row; k_a07_molTrace is the molecule stage between a load and two stores.  The two mesh kernels above keep a text of their own -- the same
+// loop and the same walk, line for line: as wrappers of these stages they compile to a few instructions more and measured 2 - 4 % slower on
+// parliament (profiles/frame_stages/README.md).
 
 // k_a04_meshTrace on `ray`
-PT_DEV void frame_stage_a04(const Cam& cam, Ray& ray, uint32_t t_size, const float4* prep, const float4* normals, const uint32_t* mindex,
+PT_DEV bool frame_stage_a04(const Cam& cam, Ray& ray, uint32_t t_size, const float4* prep, const float4* normals, const uint32_t* mindex,
                             const float4* mcolor, uint32_t ncolors, uchar4& colour) {
     float champ_t = PT_INF, cb = 0.0f, cg = 0.0f;
     uint32_t champ_i = t_size;
@@ -337,24 +266,27 @@ PT_DEV void frame_stage_a04(const Cam& cam, Ray& ray, uint32_t t_size, const flo
         in = in & (t > ray.mint) & (t < ray.maxt);
         if (in && t < champ_t) { champ_t = t; champ_i = i; cb = beta; cg = gamma; }
     }
-    if (champ_i >= t_size) return;
+    if (champ_i >= t_size) return false;
     ray.maxt = champ_t;
-    const f3 n = interp_normal(normals, champ_i, cb, cg);
+    const f3 n = interp_normal(normals + 3u * (size_t)champ_i, cb, cg);
     const float shade = cl_clamp(dot3(cam.W, n), 0.0f, 1.0f);
     const uint32_t m = mindex[champ_i];
-    if (m >= ncolors) return;
+    if (m >= ncolors) return true;   // a hit that leaves the colour alone
     const float4 mc = mcolor[m];
     colour = make_uchar4(f2u8((mc.x * 255.0f) * shade), f2u8((mc.y * 255.0f) * shade), f2u8((mc.z * 255.0f) * shade), 255);
+    return true;
 }
 
-// The grid walk of k_a07_meshTrace (MOL false: triangles, GROUPS as there) and of k_a07_molTrace (MOL true: atoms) on `ray`: phase A closes and
-// opens cells until the lane holds a primitive, phase B tests it.  prims: the prepared records (+ group spheres at record group_slots) | the atoms.
+// The grid walk of k_a07_meshTrace (MOL false: triangles, GROUPS as there) and of Assign07's molTrace (MOL true: atoms {c, r*r}; A07
+// code.cl:337-473) on `ray`: phase A closes and opens cells until the lane holds a primitive, phase B tests it.  The hit record keeps the CELL of the
+// champion (champ_slab, code.cl:402, 425-429): the walk ends once any cell produced one.  prims: the prepared records (+ group spheres at record
+// group_slots) | the atoms.
 template <bool MOL, bool GROUPS>
-PT_DEV void frame_stage_grid(const Cam& cam, Ray& ray, const Box& bound, const float4* prims, const float4* normals, uint32_t n_slabs,
+PT_DEV bool frame_stage_grid(const Cam& cam, Ray& ray, const Box& bound, const float4* prims, const float4* normals, uint32_t n_slabs,
                              const uint32_t* slab_size, uint32_t group_slots, uchar4& colour) {
-    if (ray.mint == ray.maxt) return;
+    if (ray.mint == ray.maxt) return false;
     const BoxHit bh = inter_aabb(ray, bound);
-    if (!bh.v) return;
+    if (!bh.v) return false;
     Axis ax = axis_setup(ray.o.x, ray.d.x, bh.tmin, bound.lo.x, bound.hi.x, n_slabs);
     Axis ay = axis_setup(ray.o.y, ray.d.y, bh.tmin, bound.lo.y, bound.hi.y, n_slabs);
     Axis az = axis_setup(ray.o.z, ray.d.z, bh.tmin, bound.lo.z, bound.hi.z, n_slabs);
@@ -412,14 +344,36 @@ PT_DEV void frame_stage_grid(const Cam& cam, Ray& ray, const Box& bound, const f
         if (hit && ti < champ_t) { champ_t = ti; champ_i = i; cb = b; cg = g; hx = ax.slab; hy = ay.slab; hz = az.slab; }
         ++i;
     }
-    if (champ_i == UINT32_MAX) return;
+    if (champ_i == UINT32_MAX) return false;
     ray.maxt = champ_t;
     f3 n;
     if (MOL) n = norm3(sub3(fma3(champ_t, ray.d, ray.o), ld3(prims[champ_i])));   // A07 code.cl:455-457
-    else n = interp_normal(normals, champ_i, cb, cg);
+    else n = interp_normal(normals + 3u * (size_t)champ_i, cb, cg);
     colour = parity_colour(hx, hy, hz, cl_clamp(dot3(cam.W, n), 0.0f, 1.0f));
+    return true;
 }
 
+// ---- Assign07 molTrace: the molecule stage on the ray initTrace left.  A hit stores the ray's new maxt (those 4 bytes, not the ray) and the
+// pixel; a miss stores nothing, so the pixel keeps what initTrace wrote.
+__global__ void __launch_bounds__(256) k_a07_molTrace(uchar4* pixels, F16 cam16, RayAoS* rays, const float4* atoms, Box8 bound8, uint32_t n_slabs,
+                                                       const uint32_t* slab_size, uint32_t gx, uint32_t gy) {
+    const Cam cam = mk_cam(cam16);
+    uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t row = blockIdx.y * blockDim.y + threadIdx.y;
+    if (col >= gx || row >= gy || col >= cam.cols || row >= cam.rows) return;
+    const size_t pix = (size_t)cam.cols * row + col;
+    Ray ray = load_ray48(&rays[pix]);
+    uchar4 colour;
+    if (!frame_stage_grid<true, false>(cam, ray, mk_box(bound8), atoms, nullptr, n_slabs, slab_size, 0u, colour)) return;
+    rays[pix].maxt = ray.maxt;
+    pixels[pix] = colour;
+}
+
+// ---- the whole Assign04 / Assign07 frame in one launch (mirt_render_frame) ---------------------------------------------------------------
+// initTrace + the stage(s) on one thread per pixel, the ray in registers: no 48-byte ray goes out to memory and comes back between two launches.
+// The colour starts as initTrace's black and every stage that shades overwrites it, as the launches' pixel stores do in `pixels`.  The kernel
+// stores the pixel once, and the finished ray once when a ray buffer is given (RAYS): the same 40 bytes the launches leave there.  Which stages
+// run is the template parameter STAGES (FrameStage bits, pt_launch.hpp); the walks have no run-time switch.
 template <uint32_t STAGES, bool GROUPS, bool RAYS>
 __global__ void __launch_bounds__(256) k_frame_fused(FrameArgs a) {
     const Cam cam = mk_cam(*reinterpret_cast<const F16*>(a.cam));
@@ -454,31 +408,31 @@ void launch_frame_initTrace(hipStream_t s, bool clip, void* pixels, const float*
     if (clip) hipLaunchKernelGGL(k_frame_initTrace<true>, grid2(gx, gy), dim3(32, 8), 0, s, (uchar4*)pixels, mk16f(cam), (RayAoS*)rays, mk8f(bound), gx, gy);
     else hipLaunchKernelGGL(k_frame_initTrace<false>, grid2(gx, gy), dim3(32, 8), 0, s, (uchar4*)pixels, mk16f(cam), (RayAoS*)rays, mk8f(nullptr), gx, gy);
 }
-void launch_a04_meshTrace(hipStream_t s, void* pixels, const float* cam, void* rays, uint32_t t_size, const void* prep, const void* normals,
-                          const void* mindex, const void* mcolor, uint32_t ncolors, uint32_t gx, uint32_t gy) {
-    if (!gx || !gy) return;
-    hipLaunchKernelGGL(k_a04_meshTrace, grid2(gx, gy), dim3(32, 8), 0, s, (uchar4*)pixels, mk16f(cam), (RayAoS*)rays, t_size, (const float4*)prep,
-                       (const float4*)normals, (const uint32_t*)mindex, (const float4*)mcolor, ncolors, gx, gy);
-}
-void launch_a07_meshTrace(hipStream_t s, void* pixels, const float* cam, void* rays, const void* prep, const void* normals, const float* bound,
-                          uint32_t n_slabs, const void* slab_size, uint32_t n_slots, uint32_t gx, uint32_t gy) {
-    if (!gx || !gy) return;
-    // the group spheres behind the n_slots records are consulted only where cells are long on average (coarse grids)
+// the group spheres behind a grid's n_slots prepared records are consulted only where cells are long on average (coarse grids): where they
+// start, in records, or 0 for the plain loop
+static uint32_t frame_group_slots(uint32_t n_slabs, uint32_t n_slots) {
     const uint64_t cells = (uint64_t)n_slabs * n_slabs * n_slabs;
-    const uint32_t group_slots = (uint64_t)n_slots >= cells * 4u * kTriGroup ? n_slots : 0u;
-    if (group_slots)
-        hipLaunchKernelGGL(k_a07_meshTrace<true>, grid2(gx, gy), dim3(32, 8), 0, s, (uchar4*)pixels, mk16f(cam), (RayAoS*)rays, (const float4*)prep,
-                           (const float4*)normals, mk8f(bound), n_slabs, (const uint32_t*)slab_size, group_slots, gx, gy);
-    else
-        hipLaunchKernelGGL(k_a07_meshTrace<false>, grid2(gx, gy), dim3(32, 8), 0, s, (uchar4*)pixels, mk16f(cam), (RayAoS*)rays, (const float4*)prep,
-                           (const float4*)normals, mk8f(bound), n_slabs, (const uint32_t*)slab_size, 0u, gx, gy);
+    return (uint64_t)n_slots >= cells * 4u * kTriGroup ? n_slots : 0u;
 }
-
-void launch_a07_molTrace(hipStream_t s, void* pixels, const float* cam, void* rays, const void* atoms, const float* bound, uint32_t n_slabs,
-                         const void* slab_size, uint32_t gx, uint32_t gy) {
-    if (!gx || !gy) return;
-    hipLaunchKernelGGL(k_a07_molTrace, grid2(gx, gy), dim3(32, 8), 0, s, (uchar4*)pixels, mk16f(cam), (RayAoS*)rays, (const float4*)atoms, mk8f(bound),
-                       n_slabs, (const uint32_t*)slab_size, gx, gy);
+void launch_frame_stage(hipStream_t s, const FrameArgs& a, FrameStage stage) {
+    if (!a.gx || !a.gy) return;
+    const dim3 grid = grid2(a.gx, a.gy), block(32, 8);
+    uchar4* pixels = (uchar4*)a.pixels;
+    RayAoS* rays = (RayAoS*)a.rays;
+    const float4 *prep = (const float4*)a.prep, *normals = (const float4*)a.normals;
+    const uint32_t group_slots = stage == FS_MESH ? frame_group_slots(a.n_slabs, a.n_slots) : 0u;
+    if (stage == FS_A04)
+        hipLaunchKernelGGL(k_a04_meshTrace, grid, block, 0, s, pixels, mk16f(a.cam), rays, a.t_size, prep, normals, (const uint32_t*)a.mindex,
+                           (const float4*)a.mcolor, a.ncolors, a.gx, a.gy);
+    else if (stage == FS_MOL)
+        hipLaunchKernelGGL(k_a07_molTrace, grid, block, 0, s, pixels, mk16f(a.cam), rays, (const float4*)a.atoms, mk8f(a.bound), a.n_slabs,
+                           (const uint32_t*)a.mol_slab_size, a.gx, a.gy);
+    else if (group_slots)
+        hipLaunchKernelGGL(k_a07_meshTrace<true>, grid, block, 0, s, pixels, mk16f(a.cam), rays, prep, normals, mk8f(a.bound), a.n_slabs,
+                           (const uint32_t*)a.slab_size, group_slots, a.gx, a.gy);
+    else
+        hipLaunchKernelGGL(k_a07_meshTrace<false>, grid, block, 0, s, pixels, mk16f(a.cam), rays, prep, normals, mk8f(a.bound), a.n_slabs,
+                           (const uint32_t*)a.slab_size, 0u, a.gx, a.gy);
 }
 
 template <uint32_t STAGES, bool GROUPS>
@@ -489,9 +443,7 @@ static void launch_frame_fused_t(hipStream_t s, const FrameArgs& a) {
 void launch_frame_fused(hipStream_t s, FrameArgs a) {
     if (!a.gx || !a.gy) return;
     if (a.assign == 4) { launch_frame_fused_t<FS_A04, false>(s, a); return; }
-    // the same rule as launch_a07_meshTrace: group spheres where cells are long on average
-    const uint64_t cells = (uint64_t)a.n_slabs * a.n_slabs * a.n_slabs;
-    a.group_slots = a.mesh && (uint64_t)a.n_slots >= cells * 4u * kTriGroup ? a.n_slots : 0u;
+    a.group_slots = a.mesh ? frame_group_slots(a.n_slabs, a.n_slots) : 0u;
     const bool mesh = a.mesh != 0u, mol = a.mol != 0u;
     if (mesh && mol) { if (a.group_slots) launch_frame_fused_t<FS_MOL | FS_MESH, true>(s, a); else launch_frame_fused_t<FS_MOL | FS_MESH, false>(s, a); }
     else if (mesh) { if (a.group_slots) launch_frame_fused_t<FS_MESH, true>(s, a); else launch_frame_fused_t<FS_MESH, false>(s, a); }

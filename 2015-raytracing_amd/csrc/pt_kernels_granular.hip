@@ -246,9 +246,7 @@ __global__ void __launch_bounds__(256) k_closest(uint32_t total, PoiAoS* pois, R
     if (KIND == SPHERES) {
         nrm = norm3(sub3(p, ld3(prims[ch.idx])));
     } else {
-        const float4* nn = normals + 3u * (size_t)ch.idx;
-        float w = 1.0f - ch.beta - ch.gamma;                         // code.cl:409-411
-        nrm = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
+        nrm = interp_normal(normals + 3u * (size_t)ch.idx, ch.beta, ch.gamma);
     }
     PoiAoS* pp = &pois[id];
     float4* q = reinterpret_cast<float4*>(pp);
@@ -309,9 +307,7 @@ __global__ void __launch_bounds__(256) k_closestMesh(uint32_t total, PoiAoS* poi
     if (!want || ch.idx == UINT32_MAX) return;
     rays[id].maxt = ch.t;
     const f3 p = fma3(ch.t, ray.d, ray.o);   // getPoint, code.cl:87
-    const float4* nn = normals + 3u * (size_t)ch.idx;
-    const float w = 1.0f - ch.beta - ch.gamma;                         // code.cl:409-411
-    const f3 nrm = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
+    const f3 nrm = interp_normal(normals + 3u * (size_t)ch.idx, ch.beta, ch.gamma);
     PoiAoS* pp = &pois[id];
     float4* q = reinterpret_cast<float4*>(pp);
     q[0] = make_float4(p.x, p.y, p.z, 0.0f);

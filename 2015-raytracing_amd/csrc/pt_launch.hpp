@@ -214,27 +214,20 @@ void launch_gatherU32(hipStream_t s, const uint32_t* order, uint32_t total, cons
 // ---- single-frame kernels of Assign01 / 04 / 07 (pt_kernels_frame.hip) -----------------------------
 void launch_a01_raytrace(hipStream_t s, void* pixels, const float* cam, uint32_t gx, uint32_t gy);
 void launch_frame_initTrace(hipStream_t s, bool clip, void* pixels, const float* cam, void* rays, const float* bound, uint32_t gx, uint32_t gy);
-void launch_a04_meshTrace(hipStream_t s, void* pixels, const float* cam, void* rays, uint32_t t_size, const void* prep, const void* normals,
-                          const void* mindex, const void* mcolor, uint32_t ncolors, uint32_t gx, uint32_t gy);
-// prep: the prepared records of the n_slots grid slots followed by one bounding sphere per kTriGroup records (launch_prepTriangles)
-void launch_a07_meshTrace(hipStream_t s, void* pixels, const float* cam, void* rays, const void* prep, const void* normals, const float* bound,
-                          uint32_t n_slabs, const void* slab_size, uint32_t n_slots, uint32_t gx, uint32_t gy);
-void launch_a07_molTrace(hipStream_t s, void* pixels, const float* cam, void* rays, const void* atoms, const float* bound, uint32_t n_slabs,
-                         const void* slab_size, uint32_t gx, uint32_t gy);
 
-// the whole frame in one launch (k_frame_fused): initTrace and the trace stage(s) on one thread per pixel, the ray in registers.  assign 4: the brute
-// force over `prep`; assign 7: the molecule stage when `atoms` is set, then the mesh stage when `prep` is, the mesh starting from the maxt the molecule
-// left (A07 code.js:629-661 computeBoth).  rays null: nothing per ray touches memory.  The caller has checked every extent (mirt_abi.cpp render_frame_impl).
+// What the Assign04 / Assign07 trace stages read, for both frame paths.  The caller has checked every extent (mirt_abi.cpp frame_a04_mesh,
+// frame_a07_mesh, frame_a07_mol, which also fill the stages' fields).
 struct FrameArgs {
     float cam[16];
     float bound[8];          // assign 7: the one box of initTrace's clip and of both grids
     void* pixels;            // uchar4 per pixel
-    void* rays;              // 48 B per pixel, or null
-    uint32_t assign;
-    uint32_t mesh, mol;      // assign 7: which stages run
+    void* rays;              // 48 B per pixel; launch_frame_fused: or null
+    uint32_t assign;         // launch_frame_fused: 4 or 7
+    uint32_t mesh, mol;      // launch_frame_fused, assign 7: which stages run
     uint32_t gx, gy;         // the NDRange; pixels outside it or outside cam.cols x cam.rows stay untouched
     uint32_t t_size;         // assign 4
-    const void* prep;        // prepared records (launch_prepTriangles) of the t_size triangles | of the n_slots grid slots
+    const void* prep;        // prepared records (launch_prepTriangles) of the t_size triangles | of the n_slots grid slots, behind them one
+                             // bounding sphere per kTriGroup records
     const void* normals;
     const void* mindex;      // assign 4
     const void* mcolor;
@@ -246,6 +239,12 @@ struct FrameArgs {
     const void* atoms;       // float4 {c, r*r} per slot
     const void* mol_slab_size;
 };
+// the whole frame in one launch (k_frame_fused): initTrace and the trace stage(s) on one thread per pixel, the ray in registers.  assign 4: the brute
+// force; assign 7: the molecule stage when `mol` is set, then the mesh stage when `mesh` is, the mesh starting from the maxt the molecule left
+// (A07 code.js:629-661 computeBoth).  rays null: nothing per ray touches memory.
 void launch_frame_fused(hipStream_t s, FrameArgs a);
+// one stage as a launch of its own (k_a04_meshTrace, k_a07_meshTrace, k_a07_molTrace) over the rays initTrace or the stage before left in a.rays
+enum FrameStage : uint32_t { FS_A04 = 1u, FS_MESH = 2u, FS_MOL = 4u };
+void launch_frame_stage(hipStream_t s, const FrameArgs& a, FrameStage stage);
 
 }  // namespace pt

@@ -42,6 +42,13 @@ __device__ __forceinline__ void pt_count(int, bool = false, unsigned long long =
 
 struct Hit { uint32_t idx; float t, beta, gamma; };
 
+// the shading normal at barycentrics (beta, gamma) of the triangle whose three vertex normals are nn[0..2] (A10 code.cl:409-411).  closest_all
+// (pt_closest.hpp) spells the same expression out twice: through this function the compiler schedules k_fusedPass and k_guides differently
+PT_DEV f3 interp_normal(const float4* nn, float beta, float gamma) {
+    const float w = 1.0f - beta - gamma;
+    return norm3(fma3(gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(beta, ld3(nn[1])))));
+}
+
 // Geometry the kernels only read, fetched in wave-uniform loops: through the CONSTANT address space, so the loads stay scalar
 // (s_load_dwordx4 / x16 into SGPRs) wherever the address is uniform.  Through a plain global pointer the back end may only use a scalar
 // load when nothing in the kernel can have stored to memory before it: a kernel that writes results inside its main loop (the
