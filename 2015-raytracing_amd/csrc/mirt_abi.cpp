@@ -1847,10 +1847,10 @@ int mirt_debug_numerics(mirt_ctx* ctx, int op, mirt_buf* a, mirt_buf* b, mirt_bu
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_debug_numerics: unknown context");
     FLUSH_PENDING(ctx);
     int rc;
-    if (!((op >= 0 && op <= 14) || (op >= 20 && op <= 27))) return fail(ctx, MIRT_E_ARG, "mirt_debug_numerics: op %d outside 0..14, 20..27", op);
+    if (!((op >= 0 && op <= 14) || (op >= 20 && op <= 28))) return fail(ctx, MIRT_E_ARG, "mirt_debug_numerics: op %d outside 0..14, 20..28", op);
     const bool vec = op >= 20 && op != 25;
     const uint64_t in_w = vec ? 3 : 1, out_w = (op == 21 || op == 24) ? 3 : op == 27 ? 4 : 1;
-    const bool two = op == 0 || (op >= 6 && op <= 12) || op == 20 || op == 21 || op == 23 || op == 25;
+    const bool two = op == 0 || (op >= 6 && op <= 12) || op == 20 || op == 21 || op == 23 || op == 25 || op == 28;
     if ((rc = need(ctx, "mirt_debug_numerics a", a, (uint64_t)n * 4 * in_w))) return rc;
     if (two && !b) return fail(ctx, MIRT_E_ARG, "mirt_debug_numerics: op %d needs two inputs", op);
     if (b && (rc = need(ctx, "mirt_debug_numerics b", b, (uint64_t)n * 4 * (two ? in_w : 1)))) return rc;

@@ -467,6 +467,15 @@ __global__ void __launch_bounds__(256) k_numerics(int op, const float* a, const 
             out[4 * i] = cl_fma(p, q, c); out[4 * i + 1] = cl_fma(p, q, -c); out[4 * i + 2] = cl_fma(-p, q, c); out[4 * i + 3] = cl_fma(p, q, c * p);
             return;
         }
+        case 28: {   // the optimistic kernel's ray-side guard: a = origin, b = direction; 1.0 accepted, 0.0 refused (tests/test_ray_guard.py)
+            Ray ray;
+            ray.o = ld3(a + 3 * i);
+            ray.d = ld3(b + 3 * i);
+            ray.mint = 0.0f;
+            ray.maxt = PT_INF;
+            r = ray_guard(ray) ? 1.0f : 0.0f;
+            break;
+        }
         default: break;
     }
     out[i] = r;

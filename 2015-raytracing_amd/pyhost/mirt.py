@@ -381,7 +381,8 @@ class Context:
         return n, miss.value.decode()
 
     def debug_numerics(self, op, a, b=None):
-        """op 0..14: one float per element; 20..27 except 25: float3 arguments as three consecutive floats (include/mirt.h)"""
+        """op 0..14: one float per element; 20..28 except 25: float3 arguments as three consecutive floats (include/mirt.h).
+        Op 28 (ray_guard) takes the origins as a and the directions as b, three floats each per ray, and returns one float per ray."""
         a = np.ascontiguousarray(a, np.float32)
         vec = op >= 20 and op != 25
         n = a.size // 3 if vec else a.size
