@@ -458,7 +458,8 @@ napi_value UpsampleGuided(napi_env env, napi_callback_info info) {
 }
 
 // renderFrame(ctx, {assign,width,height,cam,bounds?,nSlabs?, tSize?,tPos?,tNormal?,tMindex?,tMcolor?,tSlabSize?, sSize?,sAtoms?,sMindex?,sMcolor?,sSlabSize?,
-//                   pixel, rays?}): a whole Assign04 / Assign07 frame in one launch (mirt_render_frame)
+//                   pixel, rays?, aa?}): a whole Assign04 / Assign07 frame in one launch (mirt_render_frame); aa, when given: aa x aa samples a pixel, averaged
+//                   in that launch (mirt_render_frame_aa)
 napi_value RenderFrame(napi_env env, napi_callback_info info) {
     ARGS(2);
     void* c;
@@ -478,7 +479,9 @@ napi_value RenderFrame(napi_env env, napi_callback_info info) {
     f.s_atoms = prop_buf(env, d, "sAtoms"); f.s_mindex = prop_buf(env, d, "sMindex"); f.s_mcolor = prop_buf(env, d, "sMcolor"); f.s_slab_size = prop_buf(env, d, "sSlabSize");
     f.pixel = prop_buf(env, d, "pixel");
     f.rays = prop_buf(env, d, "rays");
-    int rc = mirt_render_frame((mirt_ctx*)c, &f);
+    uint32_t aa = 1;
+    const bool has_aa = prop_u32(env, d, "aa", &aa);
+    int rc = has_aa ? mirt_render_frame_aa((mirt_ctx*)c, &f, aa) : mirt_render_frame((mirt_ctx*)c, &f);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);
 }

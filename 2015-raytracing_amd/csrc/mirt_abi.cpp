@@ -855,7 +855,7 @@ struct PassOpts {
 };
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
-static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d);
+static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d, uint32_t aa = 1u);
 
 // The frame dialects' counterpart of try_fuse_pass.  MIRT_OK: the held stream was a frame (match_frame, pt_stream_match.hpp) and ran as one launch; the
 // ray buffer is not written.  1: not a frame, or refused before anything was launched (nothing executed).  < 0: error.
@@ -1712,8 +1712,10 @@ int mirt_ctx_fused_frames(mirt_ctx* ctx, uint64_t* count) try {
 } MIRT_CATCH("mirt_ctx_fused_frames", return MIRT_E_DEVICE)
 
 // A whole Assign04 / Assign07 frame in one launch (pt_kernels_frame.hip k_frame_fused).  Every check launch_kernel makes for initTrace and the trace
-// kernels over the full image is made here, all of them before anything is prepared or launched.
-static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d) {
+// kernels over the full image is made here, all of them before anything is prepared or launched.  aa > 1: mirt_render_frame_aa's frame, the same
+// checks on the same descriptor (the caller has checked aa itself and that there is no ray buffer), then the FINE frame's arguments -- the camera block
+// with aa times the columns and rows -- to the kernel that averages aa x aa of its samples into each of the descriptor's width x height pixels.
+static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d, uint32_t aa) {
     if (!d || d->struct_size != sizeof(mirt_frame_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: descriptor size mismatch");
     if (d->assign != 4 && d->assign != 7) return fail(ctx, MIRT_E_ARG, "mirt_render_frame: assign %u (4 and 7 are frames of two launches; Assign01 is one launch already, Assign10 is mirt_render_pass)", d->assign);
     const bool mesh = d->t_pos != nullptr, mol = d->s_atoms != nullptr;
@@ -1742,7 +1744,13 @@ static int render_frame_impl(mirt_ctx* ctx, const mirt_frame_desc* d) {
     }
     A.pixels = d->pixel->ptr;
     A.rays = d->rays ? d->rays->ptr : nullptr;
-    pt::launch_frame_fused(ctx->stream, A);
+    if (aa > 1u) {
+        A.gx = aa * cols; A.gy = aa * rows;   // at most 65535 each: exact as floats
+        A.cam[14] = (float)A.gx; A.cam[15] = (float)A.gy;
+        pt::launch_frame_aa(ctx->stream, A, aa, cols, rows);
+    } else {
+        pt::launch_frame_fused(ctx->stream, A);
+    }
     HIPCHK(ctx, hipGetLastError());
     d->pixel->version++;
     if (d->rays) d->rays->version++;
@@ -1754,6 +1762,18 @@ int mirt_render_frame(mirt_ctx* ctx, const mirt_frame_desc* d) try {
     FLUSH_PENDING(ctx);
     return render_frame_impl(ctx, d);
 } MIRT_CATCH("mirt_render_frame", return MIRT_E_DEVICE)
+
+int mirt_render_frame_aa(mirt_ctx* ctx, const mirt_frame_desc* d, uint32_t aa) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_frame_aa: unknown context");
+    FLUSH_PENDING(ctx);
+    if (aa < 1u || aa > 4u) return fail(ctx, MIRT_E_ARG, "mirt_render_frame_aa: aa %u (1 to 4 samples per axis)", aa);
+    if (aa > 1u && d && d->struct_size == sizeof(mirt_frame_desc)) {
+        if (d->rays) return fail(ctx, MIRT_E_ARG, "mirt_render_frame_aa: a ray buffer with aa %u (a pixel has no one ray)", aa);
+        if ((uint64_t)aa * d->width > 65535u || (uint64_t)aa * d->height > 65535u)
+            return fail(ctx, MIRT_E_ARG, "mirt_render_frame_aa: %ux%u at aa %u is a fine frame beyond 65535 samples per axis", d->width, d->height, aa);
+    }
+    return render_frame_impl(ctx, d, aa);
+} MIRT_CATCH("mirt_render_frame_aa", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_exact_only(mirt_ctx* ctx, int on) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_exact_only: unknown context");

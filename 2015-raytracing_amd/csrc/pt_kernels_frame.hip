@@ -395,6 +395,84 @@ __global__ void __launch_bounds__(256) k_frame_fused(FrameArgs a) {
     ((uchar4*)a.pixels)[pix] = colour;
 }
 
+// ---- the anti-aliased frame: AA x AA samples a pixel in one launch (mirt_render_frame_aa) ---------------------------------------------------
+// FrameArgs is the FINE frame's: a.cam says AA*ow x AA*oh, so pinhole_ray puts sample (AA*x + i, AA*y + j) exactly where k_frame_fused puts that
+// pixel of the fine frame, and the stages below are k_frame_fused's, in its order.  An output pixel is the integer box average of its AA*AA
+// samples' bytes, (S + AA*AA/2) / (AA*AA) per channel, alpha 255 (include/mirt.h); a.pixels is ow x oh.
+// One lane per SAMPLE (k_frame_aa_lanes): a pixel's samples sit in adjacent lanes of one wave, the wave covers a compact fine tile, the sums cross
+// lanes (DPP for AA 2 and 4, ds_bpermute for 3) and the pixel's first lane stores.  The other structure that gives these bits -- one thread per OUTPUT
+// pixel looping over its samples -- fills the device with 1 / (AA*AA) of the waves and measured 3.5 to 17 times slower
+// (profiles/frame_aa/README.md, where it is kept as a patch).
+template <uint32_t STAGES, bool GROUPS>
+PT_DEV uchar4 frame_sample(const FrameArgs& a, const Cam& cam, const Box& bound, uint32_t col, uint32_t row) {
+    Ray ray = pinhole_ray(cam, (float)col, (float)row);
+    if (!(STAGES & FS_A04)) clip_to(ray, bound);
+    uchar4 colour = make_uchar4(0, 0, 0, 255);
+    if (STAGES & FS_A04)
+        frame_stage_a04(cam, ray, a.t_size, (const float4*)a.prep, (const float4*)a.normals, (const uint32_t*)a.mindex, (const float4*)a.mcolor, a.ncolors, colour);
+    if (STAGES & FS_MOL) frame_stage_grid<true, false>(cam, ray, bound, (const float4*)a.atoms, nullptr, a.n_slabs, (const uint32_t*)a.mol_slab_size, 0u, colour);
+    if (STAGES & FS_MESH)
+        frame_stage_grid<false, GROUPS>(cam, ray, bound, (const float4*)a.prep, (const float4*)a.normals, a.n_slabs, (const uint32_t*)a.slab_size, a.group_slots, colour);
+    return colour;
+}
+// the sums of R and B ride in the halves of one register (16 * 255 < 65536), G in another
+template <uint32_t AA>
+PT_DEV uchar4 aa_average(uint32_t rb, uint32_t g) {
+    constexpr uint32_t N = AA * AA;
+    return make_uchar4((unsigned char)(((rb & 0xFFFFu) + N / 2u) / N), (unsigned char)((g + N / 2u) / N), (unsigned char)(((rb >> 16) + N / 2u) / N), 255);
+}
+
+// the output pixels of one wave in k_frame_aa_lanes: W x H of them, lane = pixel * AA*AA + sample.  AA 2: 16 DPP quads, an 8 x 8 fine tile; AA 4:
+// four 16-lane DPP rows, 8 x 8 fine; AA 3: 7 pixels in 63 lanes, 21 x 3 fine, lane 63 idle.
+template <uint32_t AA> struct AaWave;
+template <> struct AaWave<2> { static constexpr uint32_t W = 4, H = 4; };
+template <> struct AaWave<3> { static constexpr uint32_t W = 7, H = 1; };
+template <> struct AaWave<4> { static constexpr uint32_t W = 2, H = 2; };
+template <int CTRL>
+PT_DEV uint32_t dpp_get(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true); }
+// v summed over the AA*AA lanes of the caller's pixel; the pixel's FIRST lane holds the whole sum (for AA 2 and 4 every lane does).  Every lane
+// of the wave must enter.
+template <uint32_t AA>
+PT_DEV uint32_t aa_lane_sum(uint32_t v, uint32_t lane, uint32_t s) {
+    if (AA == 3) {
+        // lanes s .. 8 of the pixel fold down on lane s: after the steps 1, 2, 4, 8 lane 0 holds all nine
+#pragma unroll
+        for (uint32_t d = 1; d < 16u; d *= 2u) {
+            const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane + d) & 63u) * 4u), (int)v);
+            if (s + d < 9u) v += o;
+        }
+        return v;
+    }
+    v += dpp_get<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp_get<0x4E>(v);   // quad_perm [2,3,0,1]
+    if (AA == 4) {
+        v += dpp_get<0x124>(v);   // row_ror:4
+        v += dpp_get<0x128>(v);   // row_ror:8
+    }
+    return v;
+}
+
+template <uint32_t STAGES, bool GROUPS, uint32_t AA>
+__global__ void __launch_bounds__(256) k_frame_aa_lanes(FrameArgs a, uint32_t ow, uint32_t oh) {
+    constexpr uint32_t N = AA * AA, TW = AaWave<AA>::W, TH = AaWave<AA>::H;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t p = lane / N, s = lane % N;
+    const uint32_t x = (blockIdx.x * 4u + wave) * TW + p % TW, y = blockIdx.y * TH + p / TW;
+    // a lane without a sample (outside the image, or AA 3's lane 63) traces nothing and rides along to the cross-lane sums with zeros
+    const bool live = p < TW * TH && x < ow && y < oh;
+    uint32_t rb = 0u, g = 0u;
+    if (live) {
+        const Cam cam = mk_cam(*reinterpret_cast<const F16*>(a.cam));
+        const Box bound = mk_box(*reinterpret_cast<const Box8*>(a.bound));
+        const uchar4 c = frame_sample<STAGES, GROUPS>(a, cam, bound, AA * x + s % AA, AA * y + s / AA);
+        rb = (uint32_t)c.x | ((uint32_t)c.z << 16);
+        g = c.y;
+    }
+    rb = aa_lane_sum<AA>(rb, lane, s);
+    g = aa_lane_sum<AA>(g, lane, s);
+    if (live && s == 0u) ((uchar4*)a.pixels)[(size_t)ow * y + x] = aa_average<AA>(rb, g);
+}
+
 static F16 mk16f(const float* f) { F16 r; for (int i = 0; i < 16; ++i) r.v[i] = f[i]; return r; }
 static Box8 mk8f(const float* f) { Box8 r; for (int i = 0; i < 8; ++i) r.v[i] = f ? f[i] : 0.0f; return r; }
 static dim3 grid2(uint32_t gx, uint32_t gy) { return dim3((gx + 31) / 32, (gy + 7) / 8); }
@@ -448,6 +526,28 @@ void launch_frame_fused(hipStream_t s, FrameArgs a) {
     if (mesh && mol) { if (a.group_slots) launch_frame_fused_t<FS_MOL | FS_MESH, true>(s, a); else launch_frame_fused_t<FS_MOL | FS_MESH, false>(s, a); }
     else if (mesh) { if (a.group_slots) launch_frame_fused_t<FS_MESH, true>(s, a); else launch_frame_fused_t<FS_MESH, false>(s, a); }
     else if (mol) launch_frame_fused_t<FS_MOL, false>(s, a);
+}
+
+template <uint32_t STAGES, bool GROUPS, uint32_t AA>
+static void launch_frame_aa_t(hipStream_t s, const FrameArgs& a, uint32_t ow, uint32_t oh) {
+    // four waves a block, side by side: (4 * W) x H output pixels
+    const dim3 grid((ow + 4u * AaWave<AA>::W - 1u) / (4u * AaWave<AA>::W), (oh + AaWave<AA>::H - 1u) / AaWave<AA>::H);
+    hipLaunchKernelGGL((k_frame_aa_lanes<STAGES, GROUPS, AA>), grid, dim3(256), 0, s, a, ow, oh);
+}
+template <uint32_t STAGES, bool GROUPS>
+static void launch_frame_aa_s(hipStream_t s, const FrameArgs& a, uint32_t aa, uint32_t ow, uint32_t oh) {
+    if (aa == 2u) launch_frame_aa_t<STAGES, GROUPS, 2>(s, a, ow, oh);
+    else if (aa == 3u) launch_frame_aa_t<STAGES, GROUPS, 3>(s, a, ow, oh);
+    else if (aa == 4u) launch_frame_aa_t<STAGES, GROUPS, 4>(s, a, ow, oh);
+}
+void launch_frame_aa(hipStream_t s, FrameArgs a, uint32_t aa, uint32_t ow, uint32_t oh) {
+    if (!ow || !oh) return;
+    if (a.assign == 4) { launch_frame_aa_s<FS_A04, false>(s, a, aa, ow, oh); return; }
+    a.group_slots = a.mesh ? frame_group_slots(a.n_slabs, a.n_slots) : 0u;
+    const bool mesh = a.mesh != 0u, mol = a.mol != 0u;
+    if (mesh && mol) { if (a.group_slots) launch_frame_aa_s<FS_MOL | FS_MESH, true>(s, a, aa, ow, oh); else launch_frame_aa_s<FS_MOL | FS_MESH, false>(s, a, aa, ow, oh); }
+    else if (mesh) { if (a.group_slots) launch_frame_aa_s<FS_MESH, true>(s, a, aa, ow, oh); else launch_frame_aa_s<FS_MESH, false>(s, a, aa, ow, oh); }
+    else if (mol) launch_frame_aa_s<FS_MOL, false>(s, a, aa, ow, oh);
 }
 
 }  // namespace pt

@@ -246,5 +246,8 @@ void launch_frame_fused(hipStream_t s, FrameArgs a);
 // one stage as a launch of its own (k_a04_meshTrace, k_a07_meshTrace, k_a07_molTrace) over the rays initTrace or the stage before left in a.rays
 enum FrameStage : uint32_t { FS_A04 = 1u, FS_MESH = 2u, FS_MOL = 4u };
 void launch_frame_stage(hipStream_t s, const FrameArgs& a, FrameStage stage);
+// the anti-aliased frame in one launch (k_frame_aa_lanes): `a` is launch_frame_fused's for the FINE frame -- a.cam says aa*ow x aa*oh, a.rays is
+// unused -- and a.pixels holds ow x oh pixels, each the box average of its aa x aa fine samples.  aa: 2, 3 or 4.
+void launch_frame_aa(hipStream_t s, FrameArgs a, uint32_t aa, uint32_t ow, uint32_t oh);
 
 }  // namespace pt

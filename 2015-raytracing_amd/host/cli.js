@@ -4,7 +4,7 @@
 //   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]] [--guides PREFIX] [--denoise [iterations]] [--upscale F]
 //                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
-//   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer
+//   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
 //   node cli.js devices                                                             -> what webcl.getPlatforms()/getDevices() report
 "use strict";
@@ -98,8 +98,11 @@ if (cmd === "pack") {
 } else if (cmd === "pack-frame" || cmd === "frame") {
   if (rest.length < 4) usage();
   const frame = require("./frame.js");
-  const oneLaunch = rest.includes("--one-launch");
-  const a = rest.filter((x) => x !== "--one-launch");
+  const ai = rest.indexOf("--aa"), aa = ai >= 0 ? +rest[ai + 1] : undefined;   // --aa K implies one launch
+  if (ai >= 0 && !(Number.isInteger(aa) && aa >= 1)) { console.error("--aa takes the number of samples per axis, 1 to 4"); process.exit(2); }
+  if (ai >= 0 && +rest[0] === 1) { console.error("--aa: Assign01 has no anti-aliased frame (frame 4 and frame 7 do)"); process.exit(2); }
+  const oneLaunch = rest.includes("--one-launch") || ai >= 0;
+  const a = rest.filter((x, i) => x !== "--one-launch" && i !== ai && (ai < 0 || i !== ai + 1));
   const read = (f) => fs.readFileSync(f, "utf8").replace(/^\ufeff/, "");
   const assign = +a[0], text = a[1] === "-" ? null : read(a[1]);
   let model = text === null ? null : /\.pdb$/i.test(a[1]) ? { pdb: text } : JSON.parse(text);   // .pdb: Assign07's molecule mode
@@ -107,9 +110,9 @@ if (cmd === "pack") {
   const p = frame.packFrame(assign, model, +a[2], +a[3], +a[4] || 2);
   if (cmd === "pack-frame") { const j = scene.packedToJSON(p); if (p.mol) j.mol = scene.packedToJSON(p.mol); process.stdout.write(JSON.stringify(j)); }
   else {
-    const px = frame.renderFrame(p, { oneLaunch: oneLaunch });
+    const px = frame.renderFrame(p, { oneLaunch: oneLaunch, aa: aa });
     writeFrame(a[5], px, +a[2], +a[3]);
-    process.stderr.write(`frame ${assign} ${+a[2]}x${+a[3]}: ${oneLaunch ? "one launch" : "kernel by kernel"}; frames the runtime fused from enqueues: ${px.fusedFrames}\n`);
+    process.stderr.write(`frame ${assign} ${+a[2]}x${+a[3]}: ${oneLaunch ? "one launch" : "kernel by kernel"}${aa !== undefined ? `, aa ${aa} (${aa * aa} samples a pixel)` : ""}; frames the runtime fused from enqueues: ${px.fusedFrames}\n`);
   }
 } else if (cmd === "ingest") {
   if (rest.length < 2) usage();

@@ -107,12 +107,14 @@ function renderFrame(p, opt) {
   const buf = (flags, a) => { const b = ctx.createBuffer(flags, Math.max(a.byteLength || a, 16)); res.push(b); if (a.byteLength) q.enqueueWriteBuffer(b, false, 0, a.byteLength, a, []); return b; };
   const pixels = buf(webcl.MEM_WRITE_ONLY, w * h * 4);
   const gws = [ceilTo(w, 8), ceilTo(h, 8)], lws = [8, 8];   // getLocalWS(2, 64)
-  if (opt.oneLaunch && p.assign !== 1) {   // the whole frame in one launch, no ray buffer (queue.renderFrame)
+  if (opt.aa !== undefined && p.assign === 1) throw new Error("aa: Assign01 has no anti-aliased frame (Assign04 and Assign07 do)");
+  if ((opt.oneLaunch || opt.aa !== undefined) && p.assign !== 1) {   // the whole frame in one launch, no ray buffer (queue.renderFrame); opt.aa: aa x aa samples a pixel
     const RO = webcl.MEM_READ_ONLY, d = { assign: p.assign, width: w, height: h, cam: p.cam, bounds: p.bounds, nSlabs: p.n_slabs || 0, pixel: pixels };
     const mol = p.atoms ? p : p.mol;
     if (mol) Object.assign(d, { sSize: mol.s_size, sAtoms: buf(RO, mol.atoms), sMindex: buf(RO, mol.mindex), sMcolor: buf(RO, mol.mcolor), sSlabSize: buf(RO, mol.slab_size) });
     if (p.pos) Object.assign(d, { tSize: p.t_size, tPos: buf(RO, p.pos), tNormal: buf(RO, p.normal), tMindex: buf(RO, p.mindex), tMcolor: buf(RO, p.mcolor) });
     if (p.pos && p.assign === 7) d.tSlabSize = buf(RO, p.slab_size);
+    if (opt.aa !== undefined) d.aa = opt.aa;
     q.renderFrame(d);
   } else if (p.assign === 1) {
     const k = prog.createKernel("raytrace"); res.push(k);

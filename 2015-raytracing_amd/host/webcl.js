@@ -231,6 +231,7 @@ class WebCLCommandQueue {
   // ---- extension: a whole Assign04 / Assign07 frame in one launch (mirt_render_frame): initTrace and the trace kernel(s) on one thread per pixel,
   // no ray buffer unless desc.rays is given.  desc: {assign, width, height, cam, bounds, nSlabs, pixel, rays?} plus the mesh {tSize, tPos, tNormal,
   // tMindex, tMcolor, tSlabSize} and / or the molecule {sSize, sAtoms, sMindex, sMcolor, sSlabSize} as WebCLBuffers; both: molecule, then mesh (computeBoth)
+  // desc.aa (1 to 4), when given: aa x aa samples a pixel, averaged in that launch (mirt_render_frame_aa); it rides along to the addon as it is
   renderFrame(desc) {
     const d = Object.assign({}, desc);
     for (const k of ["tPos", "tNormal", "tMindex", "tMcolor", "tSlabSize", "sAtoms", "sMindex", "sMcolor", "sSlabSize", "pixel", "rays"]) d[k] = desc[k] ? desc[k].h : undefined;

@@ -131,6 +131,7 @@ SYMBOLS = {
     "mirt_ctx_set_fusion": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_fused_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_render_frame": (C.c_int, [C.c_void_p, C.POINTER(_FrameDesc)]),
+    "mirt_render_frame_aa": (C.c_int, [C.c_void_p, C.POINTER(_FrameDesc), C.c_uint32]),
     "mirt_ctx_set_frame_fusion": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_fused_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_seed_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32]),
@@ -346,9 +347,9 @@ class Context:
         self._chk(lib().mirt_ctx_fused_frames(self.h, C.byref(n)))
         return n.value
 
-    def render_frame(self, assign, width, height, cam, pixel, bounds=None, n_slabs=0, mesh=None, mol=None, rays=None):
-        """mirt_render_frame: a whole Assign04 / Assign07 frame in one launch.  mesh: dict(t_size, pos, normal, mindex, mcolor[, slab_size]) of
-        Buffers, mol: dict(s_size, atoms, mindex, mcolor, slab_size); both: the molecule, then the mesh.  rays: optional 48-byte-per-pixel Buffer."""
+    @staticmethod
+    def frame_desc(assign, width, height, cam, pixel, bounds=None, n_slabs=0, mesh=None, mol=None, rays=None):
+        """the mirt_frame_desc of render_frame's arguments"""
         d = _FrameDesc()
         d.struct_size, d.assign, d.width, d.height, d.n_slabs = C.sizeof(_FrameDesc), int(assign), int(width), int(height), int(n_slabs)
         d.cam = _f(cam, 16)
@@ -363,7 +364,17 @@ class Context:
             d.s_size = int(mol.get("s_size", 0))
             d.s_atoms, d.s_mindex, d.s_mcolor, d.s_slab_size = h(mol.get("atoms")), h(mol.get("mindex")), h(mol.get("mcolor")), h(mol.get("slab_size"))
         d.pixel, d.rays = h(pixel), h(rays)
-        self._chk(lib().mirt_render_frame(self.h, C.byref(d)))
+        return d
+
+    def render_frame(self, assign, width, height, cam, pixel, bounds=None, n_slabs=0, mesh=None, mol=None, rays=None, aa=1):
+        """mirt_render_frame: a whole Assign04 / Assign07 frame in one launch.  aa > 1: mirt_render_frame_aa, each of the width x height pixels the
+        box average of aa x aa samples (no ray buffer then).  mesh: dict(t_size, pos, normal, mindex, mcolor[, slab_size]) of
+        Buffers, mol: dict(s_size, atoms, mindex, mcolor, slab_size); both: the molecule, then the mesh.  rays: optional 48-byte-per-pixel Buffer."""
+        d = self.frame_desc(assign, width, height, cam, pixel, bounds, n_slabs, mesh, mol, rays)
+        if aa == 1:
+            self._chk(lib().mirt_render_frame(self.h, C.byref(d)))
+        else:
+            self._chk(lib().mirt_render_frame_aa(self.h, C.byref(d), int(aa)))
 
     def set_profiling(self, on=True):
         self._chk(lib().mirt_ctx_set_profiling(self.h, 1 if on else 0))

@@ -535,10 +535,11 @@ def render_frame_stream(ctx, p, rays_fill=None):
 
 
 class FrameOneLaunch:
-    """An Assign04 / Assign07 frame job uploaded once, rendered by mirt_render_frame: one launch per frame, no ray buffer unless keep_rays."""
+    """An Assign04 / Assign07 frame job uploaded once, rendered by mirt_render_frame: one launch per frame, no ray buffer unless keep_rays.
+    aa > 1: by mirt_render_frame_aa, aa x aa samples a pixel averaged in that launch; the job and the pixel buffer stay p.width x p.height."""
 
-    def __init__(self, ctx, p, keep_rays=False):
-        self.ctx, self.p, self.bufs = ctx, p, []
+    def __init__(self, ctx, p, keep_rays=False, aa=1):
+        self.ctx, self.p, self.bufs, self.aa = ctx, p, [], aa
         up = lambda a: self.bufs.append(ctx.buffer_from(a)) or self.bufs[-1]
         self.pixels = ctx.buffer(p.width * p.height * 4, mirt.MEM_WRITE_ONLY)
         self.rays = ctx.buffer(p.width * p.height * RAY_BYTES) if keep_rays else None
@@ -555,7 +556,7 @@ class FrameOneLaunch:
     def render(self):
         p = self.p
         self.ctx.render_frame(p.assign, p.width, p.height, p.cam, self.pixels, bounds=getattr(p, "bounds", None), n_slabs=getattr(p, "n_slabs", 0),
-                              mesh=self.mesh, mol=self.mol, rays=self.rays)
+                              mesh=self.mesh, mol=self.mol, rays=self.rays, aa=self.aa)
 
     def release(self):
         for b in self.bufs:
@@ -563,11 +564,11 @@ class FrameOneLaunch:
         self.bufs = []
 
 
-def render_frame_one_launch(ctx, p, keep_rays=False, timing=None):
+def render_frame_one_launch(ctx, p, keep_rays=False, timing=None, aa=1):
     """The frame of render_frame (Assign04 / Assign07, the both-models job included) through mirt_render_frame: initTrace and the trace kernel(s) in
     one launch.  Returns (pixels [H*W,4] uint8, rays bytes or None); keep_rays: the kernel also stores every finished ray.
-    timing: a dict that receives "frame_ms", the HIP-event time of the one launch."""
-    f = FrameOneLaunch(ctx, p, keep_rays)
+    timing: a dict that receives "frame_ms", the HIP-event time of the one launch.  aa: samples per axis and pixel (mirt_render_frame_aa)."""
+    f = FrameOneLaunch(ctx, p, keep_rays, aa)
     try:
         if timing is None:
             f.render()

@@ -465,6 +465,23 @@ typedef struct mirt_frame_desc {
 } mirt_frame_desc;
 MIRT_API int mirt_render_frame(mirt_ctx* ctx, const mirt_frame_desc* desc);
 
+/* ---- extension: the anti-aliased frame, aa x aa samples a pixel in one launch ----------------------
+ * `desc` is exactly mirt_render_frame's descriptor of the aliased W x H frame (width = W, height = H, cam[14] = W, cam[15] = H); `aa` is the number of
+ * samples per axis, 1 to 4.  `pixel` receives W x H pixels; the aa*W x aa*H samples never reach memory.  The camera window (cam[12], cam[13]) is given
+ * in scene space, so a camera block that differs only in its column and row counts shows the same frustum on a finer lattice.  Operation by operation:
+ *   - the FINE frame F is what mirt_render_frame writes into `pixel` for the same descriptor with width = aa*W, height = aa*H,
+ *     cam[14] = (float)(aa*W), cam[15] = (float)(aa*H) and everything else bit-identical, cam[12] and cam[13] included;
+ *   - output pixel (x, y), per channel c of R, G, B:  S = the integer sum of byte c of F at (aa*x + i, aa*y + j) over i, j = 0 .. aa-1, and
+ *     out.c = (S + floor(aa*aa / 2)) div (aa*aa): the average, halves rounded up.  The sums are integers, so their order is free.  Alpha is 255.
+ *   - a sample that misses is F's black (0, 0, 0) and counts like any other;
+ *   - the bytes are averaged as the kernels write them: no gamma is undone or applied and every sample weighs the same (a box filter).
+ * aa == 1 is mirt_render_frame, `rays` allowed.  MIRT_E_ARG: aa of 0 or above 4; aa > 1 with `rays` non-NULL (a pixel has no one ray); aa*width or
+ * aa*height above 65535.  Every other check is mirt_render_frame's own, on the same descriptor, made before anything is queued: nothing is written
+ * when one fails.  Assign 4 and 7; the molecule, the mesh and both.  Capture: mirt_render_frame's rule.  The frame fusion of the pages' enqueue
+ * streams (below) is untouched: the pages have no such mode.
+ * MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
+MIRT_API int mirt_render_frame_aa(mirt_ctx* ctx, const mirt_frame_desc* desc, uint32_t aa);
+
 /* Command-stream fusion of the frame dialects: the Assign04 / Assign07 pages' own enqueue stream at the one-launch frame's speed, with no change to
  * the host.  A separate switch from mirt_ctx_set_fusion (whose levels keep their meaning), off by default; MIRT_FRAME_FUSION=1 in the environment
  * turns it on for every new context.  With it on an "A04:" / "A07:" initTrace enqueue is held back, and so are the enqueues that follow it (at most three);
