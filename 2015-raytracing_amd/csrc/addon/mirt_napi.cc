@@ -314,11 +314,13 @@ bool read_grid(napi_env env, napi_value o, mirt_grid* g) {
 // buffers of the tile, either may be null (mirt_render_guides)
 // renderFirstPassGuided(ctx, desc, normalHits, albedoDepth): the frame's first pass of the descriptor and its guides in one call
 // (mirt_render_first_pass_guided)
-enum RenderCall { CALL_PASS, CALL_GUIDES, CALL_FIRST_PASS_GUIDED };
+// renderPassesGuided(ctx, desc, normalHits, albedoDepth): desc.nPasses passes (desc.firstPass, desc.everyPass as for renderPass) and the frame's
+// guides in one call (mirt_render_passes_guided)
+enum RenderCall { CALL_PASS, CALL_GUIDES, CALL_FIRST_PASS_GUIDED, CALL_PASSES_GUIDED };
 static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, RenderCall call, napi_value nhv, napi_value adv) {
     const bool guides = call != CALL_PASS;
     void* c;
-    if (!get_ext(env, ctxv, &c)) return throw_type(env, call == CALL_GUIDES ? "renderGuides(ctx, desc, normalHits, albedoDepth)" : call == CALL_FIRST_PASS_GUIDED ? "renderFirstPassGuided(ctx, desc, normalHits, albedoDepth)" : "renderPass(ctx, desc)");
+    if (!get_ext(env, ctxv, &c)) return throw_type(env, call == CALL_GUIDES ? "renderGuides(ctx, desc, normalHits, albedoDepth)" : call == CALL_FIRST_PASS_GUIDED ? "renderFirstPassGuided(ctx, desc, normalHits, albedoDepth)" : call == CALL_PASSES_GUIDED ? "renderPassesGuided(ctx, desc, normalHits, albedoDepth)" : "renderPass(ctx, desc)");
     mirt_pass_desc p;
     memset(&p, 0, sizeof p);
     p.struct_size = sizeof p;
@@ -365,20 +367,23 @@ static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, Rende
     p.acu = prop_buf(env, d, "acu");
     p.pixel = prop_buf(env, d, "pixel");
     p.radiance = prop_buf(env, d, "radiance");
-    if (guides) {
-        void *nh = nullptr, *ad = nullptr;
-        get_ext(env, nhv, &nh);
-        get_ext(env, adv, &ad);
-        const int rc = call == CALL_GUIDES ? mirt_render_guides((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad)
-                                           : mirt_render_first_pass_guided((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad);
-        if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
-        return undef(env);
-    }
     bool first = false;   // desc.firstPass: initAcu folded into the pass (mirt_render_first_pass)
     { napi_value v; bool has = false; if (napi_has_named_property(env, d, "firstPass", &has) == napi_ok && has && napi_get_named_property(env, d, "firstPass", &v) == napi_ok) napi_get_value_bool(env, v, &first); }
     bool every = false;
     { napi_value v; bool has = false; if (napi_has_named_property(env, d, "everyPass", &has) == napi_ok && has && napi_get_named_property(env, d, "everyPass", &v) == napi_ok) napi_get_value_bool(env, v, &every); }
     uint32_t n_passes = 0;
+    if (guides) {
+        void *nh = nullptr, *ad = nullptr;
+        get_ext(env, nhv, &nh);
+        get_ext(env, adv, &ad);
+        if (call == CALL_PASSES_GUIDED && !prop_u32(env, d, "nPasses", &n_passes)) return throw_type(env, "renderPassesGuided: nPasses");
+        const int rc = call == CALL_GUIDES ? mirt_render_guides((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad)
+                     : call == CALL_PASSES_GUIDED
+                         ? mirt_render_passes_guided((mirt_ctx*)c, &p, n_passes, (first ? MIRT_PASSES_FRESH : 0u) | (every ? MIRT_PASSES_EVERY_FRAME : 0u), (mirt_buf*)nh, (mirt_buf*)ad)
+                         : mirt_render_first_pass_guided((mirt_ctx*)c, &p, (mirt_buf*)nh, (mirt_buf*)ad);
+        if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+        return undef(env);
+    }
     int rc;
     if (prop_u32(env, d, "nPasses", &n_passes))
         rc = mirt_render_passes((mirt_ctx*)c, &p, n_passes, (first ? MIRT_PASSES_FRESH : 0u) | (every ? MIRT_PASSES_EVERY_FRAME : 0u));
@@ -397,6 +402,10 @@ napi_value RenderGuides(napi_env env, napi_callback_info info) {
 napi_value RenderFirstPassGuided(napi_env env, napi_callback_info info) {
     ARGS(4);
     return render_call(env, argv[0], argv[1], CALL_FIRST_PASS_GUIDED, argv[2], argv[3]);
+}
+napi_value RenderPassesGuided(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    return render_call(env, argv[0], argv[1], CALL_PASSES_GUIDED, argv[2], argv[3]);
 }
 
 // filterAtrous(ctx, {width,height,iterations,flags,normalPowerLog2,tone,sigmaDepth,sigmaColour, radiance,normalHits,albedoDepth, filtered?,pixel?}):
@@ -748,7 +757,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

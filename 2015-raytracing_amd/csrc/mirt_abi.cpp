@@ -91,7 +91,7 @@ struct mirt_ctx {
     int fusion = 0;
     std::vector<Enqueue> pending;
     uint64_t fused_passes = 0;    // passes executed as ONE fused launch because their enqueue stream matched executeRender's
-    uint64_t guided_passes = 0;   // mirt_render_first_pass_guided calls whose pass wrote the guides itself (the one-launch route)
+    uint64_t guided_passes = 0;   // mirt_render_first_pass_guided / mirt_render_passes_guided calls whose launch wrote the guides itself (the one-launch route)
     // the same for the frame dialects (mirt_ctx_set_frame_fusion): an A04 / A07 initTrace and the enqueues behind it are held in `pending` too
     bool frame_fusion = false;
     uint64_t fused_frames = 0;
@@ -850,8 +850,13 @@ struct PassOpts {
     bool mark_start = true;
     uint32_t frame = 0;
     bool every = false;
-    mirt_buf* guide_nh = nullptr;   // mirt_render_first_pass_guided: the first-hit guides of the tile are written too (either may be null)
+    mirt_buf* guide_nh = nullptr;   // mirt_render_first_pass_guided, mirt_render_passes_guided: the first-hit guides of the tile are written too (either may be null)
     mirt_buf* guide_ad = nullptr;
+    // which rule sends them to the pass's own launch (pt_pass_plan.hpp): the first-pass call's, or mirt_render_passes_guided's for its one-launch
+    // routes.  That call's ordinary-passes route runs the guides' checks with its first pass (GUIDES_CHECK_ONLY: nothing of them is queued) and
+    // queues the guide launches behind its last (GUIDES_BEHIND).
+    enum GuideMode { GUIDES_FIRST_PASS, GUIDES_PASSES, GUIDES_BEHIND, GUIDES_CHECK_ONLY } guide_mode = GUIDES_FIRST_PASS;
+    const char* guide_fn = "mirt_render_first_pass_guided";   // the entry point its messages name
 };
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
@@ -1318,12 +1323,13 @@ static int queue_guides(mirt_ctx* ctx, const pt::FusedArgs& A, void* nh, void* a
     return MIRT_OK;
 }
 
-// mirt_render_first_pass_guided's own buffer rules, after the pass's: each guide given holds the tile's pixels x 16 B (MIRT_E_RANGE), and its bytes
+// mirt_render_first_pass_guided's and mirt_render_passes_guided's own buffer rules (`fn`: which), after the pass's: each guide given holds the tile's pixels x 16 B (MIRT_E_RANGE), and its bytes
 // meet those of no buffer of the descriptor nor the other guide's (MIRT_E_ARG) -- the pass and the guides are written by the same launches.
-static int guided_check_buffers(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* nh, mirt_buf* ad, uint64_t npix) {
+static int guided_check_buffers(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, mirt_buf* nh, mirt_buf* ad, uint64_t npix) {
     int rc;
-    if (nh && (rc = need(ctx, "mirt_render_first_pass_guided normal_hits", nh, npix * 16))) return rc;
-    if (ad && (rc = need(ctx, "mirt_render_first_pass_guided albedo_depth", ad, npix * 16))) return rc;
+    const std::string nh_name = std::string(fn) + " normal_hits", ad_name = std::string(fn) + " albedo_depth";
+    if (nh && (rc = need(ctx, nh_name.c_str(), nh, npix * 16))) return rc;
+    if (ad && (rc = need(ctx, ad_name.c_str(), ad, npix * 16))) return rc;
     std::vector<pt::PostRange> in;
     const auto add = [&in](const mirt_buf* b) { if (b && live_has(b)) in.push_back({(uint64_t)(uintptr_t)b->ptr, (uint64_t)b->bytes, true}); };
     const auto add_grid = [&add](const mirt_grid* g) { if (g) { add(g->prims); add(g->normals); add(g->matid); add(g->cell_offsets); } };
@@ -1332,11 +1338,11 @@ static int guided_check_buffers(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf
     for (uint32_t m = 0; m < d->n_meshes; ++m) add_grid(&d->meshes[m]);
     const pt::PostRange out[2] = {{nh ? (uint64_t)(uintptr_t)nh->ptr : 0u, npix * 16, nh != nullptr}, {ad ? (uint64_t)(uintptr_t)ad->ptr : 0u, npix * 16, ad != nullptr}};
     const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 2);
-    if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: a guide buffer aliases a buffer of the descriptor");
-    if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: normal_hits aliases albedo_depth");
+    if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: a guide buffer aliases a buffer of the descriptor", fn);
+    if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: normal_hits aliases albedo_depth", fn);
     return MIRT_OK;
 }
-// MIRT_GUIDED_PASS=0: mirt_render_first_pass_guided always queues the pass and then the guide launches -- an A/B and test switch, read per call
+// MIRT_GUIDED_PASS=0: mirt_render_first_pass_guided and mirt_render_passes_guided always queue the pass and then the guide launches -- an A/B and test switch, read per call
 static bool guided_pass_enabled() { const char* e = getenv("MIRT_GUIDED_PASS"); return !(e && e[0] == '0'); }
 
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o) {
@@ -1375,10 +1381,15 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
     if (A.rpp == 1 && d->row0 != 0) return fail(ctx, MIRT_E_ARG, "mirt_render_pass: rays_per_pixel == 1 couples rows through seeds[col] (A10 code.cl:429); render it as one tile");
     // the guides beside the pass (mirt_render_first_pass_guided): the last of the checks -- nothing has been queued yet -- and the route
     const bool guided = o.guide_nh || o.guide_ad;
-    if (guided && (rc = guided_check_buffers(ctx, d, o.guide_nh, o.guide_ad, npix))) return rc;
+    if (guided && (rc = guided_check_buffers(ctx, o.guide_fn, d, o.guide_nh, o.guide_ad, npix))) return rc;
     void* const guide_nh = o.guide_nh ? o.guide_nh->ptr : nullptr;
     void* const guide_ad = o.guide_ad ? o.guide_ad->ptr : nullptr;
-    const bool guides_in_pass = guided && pt::fused_guides_in_pass(plan, o.passes) && guided_pass_enabled();
+    const auto rule = [&] {   // (asked only of a guided call: the pairing is read from the environment)
+        return o.guide_mode == PassOpts::GUIDES_FIRST_PASS ? pt::fused_guides_in_pass(plan, o.passes)
+             : o.guide_mode == PassOpts::GUIDES_PASSES     ? pt::fused_guides_in_passes(plan, o.passes, pt::fused_multipass_default(A), pt::fused_has_grids(A))
+                                                           : false;
+    };
+    const bool guides_in_pass = guided && guided_pass_enabled() && rule();
     if (guides_in_pass) { A.guide_nh = guide_nh; A.guide_ad = guide_ad; }
     if (plan.scratch_bytes && (rc = ensure_scratch(ctx, (size_t)plan.scratch_bytes))) return rc;
     char* const scratch = (char*)ctx->scratch;
@@ -1442,12 +1453,12 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
     if (!plan.resolves && want_out) pt::launch_copyToPixel(ctx->stream, pixel_ptr, A.acu, res_m, (uint32_t)npix, A.rpp, (uint32_t)npix, radiance_ptr);
     if (ctx->profiling && !ctx->capturing) { HIPCHK(ctx, hipEventRecord(ctx->pe[2], ctx->stream)); ctx->pe_valid = true; }
     if (guides_in_pass) ctx->guided_passes++;
-    else if (guided && (rc = queue_guides(ctx, A, guide_nh, guide_ad))) return rc;   // everywhere else: exactly what mirt_render_guides queues
+    else if (guided && o.guide_mode != PassOpts::GUIDES_CHECK_ONLY && (rc = queue_guides(ctx, A, guide_nh, guide_ad))) return rc;   // everywhere else: exactly what mirt_render_guides queues
     HIPCHK(ctx, hipGetLastError());
     d->seeds->version++;
     if (d->acu) d->acu->version++;
-    if (o.guide_nh) o.guide_nh->version++;
-    if (o.guide_ad) o.guide_ad->version++;
+    if (o.guide_nh && o.guide_mode != PassOpts::GUIDES_CHECK_ONLY) o.guide_nh->version++;
+    if (o.guide_ad && o.guide_mode != PassOpts::GUIDES_CHECK_ONLY) o.guide_ad->version++;
     return MIRT_OK;
 }
 
@@ -1478,10 +1489,9 @@ int mirt_render_first_pass_guided(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_b
 // n_passes progressive passes in one call: the same results as mirt_render_first_pass (MIRT_PASSES_FRESH) or mirt_render_pass at pass_index,
 // then mirt_render_pass at pass_index + 1 .. pass_index + n_passes - 1 -- one launch (per block of a pixel's rays) that runs every sample through
 // all of them (pt_kernels_fused.hip k_fusedPass MULTI).
-int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes, uint32_t flags) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_passes: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_render_passes");
+// (the body of mirt_render_passes and of mirt_render_passes_guided, which gives one guide buffer at least)
+static int render_passes_impl(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes, uint32_t flags, mirt_buf* guide_nh, mirt_buf* guide_ad) {
+    const bool guided = guide_nh || guide_ad;
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: descriptor size mismatch");
     if (flags & ~(MIRT_PASSES_FRESH | MIRT_PASSES_EVERY_FRAME)) return fail(ctx, MIRT_E_ARG, "mirt_render_passes: unknown flags 0x%x", flags);
     if (n_passes < 1u || n_passes > MIRT_MAX_PASSES_PER_CALL)
@@ -1507,6 +1517,12 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
             return fail(ctx, MIRT_E_ARG, "mirt_render_passes: radiance holds %zu bytes, %u frames of %llu pixels need %llu", d->radiance->bytes, n_passes,
                         (unsigned long long)npix, (unsigned long long)(npix * 16 * n_passes));
     }
+    if (guided) {
+        o.guide_nh = guide_nh;
+        o.guide_ad = guide_ad;
+        o.guide_fn = "mirt_render_passes_guided";
+        o.guide_mode = PassOpts::GUIDES_PASSES;
+    }
     // one launch: the frame after the last pass, or -- where the passes resolve in the kernel -- every pass's frame
     if (plan.route != pt::ROUTE_ORDINARY_PASSES) return render_pass_impl(ctx, d, o);
     // elsewhere ordinary passes, each writing its own frame slot when every frame is asked for
@@ -1517,11 +1533,36 @@ int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes
         one.fresh = o.fresh && i == 0u;
         one.mark_start = i == 0u;
         one.frame = o.every ? i : 0u;
+        if (guided && (i == 0u || i + 1u == n_passes)) {   // the guides' checks before the first pass queues anything, their launches behind the last
+            one.guide_nh = guide_nh;
+            one.guide_ad = guide_ad;
+            one.guide_fn = o.guide_fn;
+            one.guide_mode = i + 1u == n_passes ? PassOpts::GUIDES_BEHIND : PassOpts::GUIDES_CHECK_ONLY;
+        }
         const int rc = render_pass_impl(ctx, &p, one);
         if (rc) return rc;
     }
     return MIRT_OK;
+}
+int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes, uint32_t flags) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_passes: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_render_passes");
+    return render_passes_impl(ctx, d, n_passes, flags, nullptr, nullptr);
 } MIRT_CATCH("mirt_render_passes", return MIRT_E_DEVICE)
+// mirt_render_passes + mirt_render_guides in one call: the checks of both before anything is queued, then -- where the plan allows
+// (pt_pass_plan.hpp fused_guides_in_passes) -- the multi-pass launch writes the guides in its first pass (k_fusedPass GUIDES with MULTI), elsewhere
+// the guide launches follow what mirt_render_passes queues.
+int mirt_render_passes_guided(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes, uint32_t flags, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_passes_guided: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_render_passes_guided");
+    if (!normal_hits && !albedo_depth) return fail(ctx, MIRT_E_ARG, "mirt_render_passes_guided: normal_hits and albedo_depth are both NULL (either may be, not both)");
+    if (d && d->struct_size == sizeof(mirt_pass_desc) && d->rays_per_pixel == 1u)
+        return fail(ctx, MIRT_E_ARG, "mirt_render_passes_guided: rays_per_pixel == 1 draws its lens sample from seeds[col] (A10 code.cl:429); the guides are defined "
+                                     "for the un-jittered k x k lens grid, rays_per_pixel >= 4 (mirt_render_guides)");
+    return render_passes_impl(ctx, d, n_passes, flags, normal_hits, albedo_depth);
+} MIRT_CATCH("mirt_render_passes_guided", return MIRT_E_DEVICE)
 
 // First-hit guide buffers of the tile (pt_kernels_guides.hip): the descriptor's geometry through the checks of mirt_render_pass, then one launch
 // -- or the optimistic / exact pair -- of one lane per pixel.  Nothing but the two outputs is written.

@@ -440,14 +440,21 @@ PT_DEV void guides_emit(const FusedArgs& A, const Ray& ray, const Poi& poi, bool
 }
 // SEG: the general form of the ray ids of a launch's segment (seg_ray); false for every contiguous one.
 // EVERY: a frame after every pass (FusedArgs::every): instantiated for resolving launches of several passes only.
-// GUIDES: the pass writes the first-hit guides of its pixels too (guides_emit): instantiated for one resolving pass of one contiguous segment only
-// (MULTI 0, SEG and EVERY false).  The optimistic kernel learns its block's verdict only at the end of the path and does not carry eight sums that
+// GUIDES: the pass writes the first-hit guides of its pixels too (guides_emit): instantiated for resolving launches of one contiguous segment only
+// (SEG false).  The optimistic kernel learns its block's verdict only at the end of the path and does not carry eight sums that
 // far: it writes the guides at segment 0 whatever the verdict.  A block that defers afterwards is re-run whole by the exact kernel's redo mode,
 // which writes the same pixels' guides again, later on the same stream: those are the final ones.
+// With MULTI (mirt_render_passes_guided) the guides are taken in pass 0 and nowhere else: the k x k lens grid draws nothing from the seeds, so segment
+// 0 is the same in every pass.  The verdict may come in any pass, and with EVERY a deferring block leaves at a frame barrier: either way the redo
+// re-runs the block from its pass 0.  Instantiated for scenes without grids and the pairing multipass_reuse picks for them by default, MULTI 2, with
+// and without EVERY (launch_seg).  The grid kernels' plain loop (MULTI 1) was built too, every pass reaching that point and the first alone emitting,
+// and was slower than the guide launches behind the unguided kernel (31 -> 62 spilled VGPRs at 6 waves): the route rule keeps
+// grid scenes of several passes on the two launches (pt_pass_plan.hpp fused_guides_in_passes).
 template <bool FAST, int GRIDS, int WAVES = 0, int MULTI = 0, bool SEG = false, bool EVERY = false, bool GUIDES = false>
 __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_GRIDS : (FAST ? PT_FUSED_WAVES_FAST : PT_FUSED_WAVES))) k_fusedPass(const FusedArgs A, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     static_assert(!EVERY || (MULTI != 0 && PT_PARK_LDS), "a frame after every pass resolves from the park rows of the multi-pass loop");
-    static_assert(!GUIDES || (MULTI == 0 && !SEG && !EVERY), "the guides are taken from one resolving pass of one contiguous segment");
+    static_assert(!GUIDES || !SEG, "the guides are taken from a resolving launch of one contiguous segment");
+    static_assert(!GUIDES || MULTI == 0 || (MULTI == 2 && GRIDS == 0), "guided multi-pass kernels exist without grids, for their default reuse pairing only");
     const uint64_t n_local = (uint64_t)A.nrows * A.width * A.rpp;
     stage_block<FAST, GRIDS>(A);
     // Exact kernel in redo mode (`redo_mask`: the bits the optimistic kernel set): one thread per 32-sample word, a loop over its
@@ -555,7 +562,7 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
 #endif
       if (MULTI != 2 || !reused) {
         closest_all<FAST, GRIDS, Park>(P, ray, poi, park, defer);
-        if constexpr (GUIDES) if (seg == 0) {   // the block of the launch as at the resolve below: blockIdx alone, or the marked block of this trip
+        if constexpr (GUIDES) if (seg == 0 && pass == 0u) {   // the block of the launch as at the resolve below: blockIdx alone, or the marked block of this trip
             const uint32_t blk = FAST || stride != 256u ? blockIdx.x : blockIdx.x * 32u + (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(todo));
             guides_emit(A, ray, poi, valid, blk);
         }
@@ -678,9 +685,21 @@ __global__ void __launch_bounds__(256) k_deferCount(const uint32_t* mask, uint32
 // grid kernel a block per CU, and it spills 71 VGPRs) against 20.36 plain (19.89 ordinary).  So: reuse for scenes without grids only.
 // MIRT_MULTIPASS_REUSE=1 / 0 forces one or the other -- an A/B switch, read per launch so that one process can alternate them (profiles/multipass_bench.py).
 static bool multipass_reuse(bool grids) { const char* e = getenv("MIRT_MULTIPASS_REUSE"); return e && e[0] ? e[0] != '0' : !grids; }
+// The guided multi-pass kernels (GUIDES with MULTI) exist for the default pairing only: whether a launch of `a` with several passes would run it now.
+bool fused_has_grids(const FusedArgs& a) {
+    bool grids = false;
+    for (uint32_t i = 0; i < a.n_sets; ++i) grids = grids || a.sets[i].n != 1u;   // as fused_lds_slots
+    return grids;
+}
+bool fused_multipass_default(const FusedArgs& a) { const bool grids = fused_has_grids(a); return multipass_reuse(grids) == !grids; }
 template <bool FAST, int GRIDS, int WAVES, bool SEG>
 static void launch_seg(const dim3& grid, size_t lds, hipStream_t s, const FusedArgs& b, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words) {
     const bool every = b.every != 0u && b.resolve != 0u && b.passes > 1u;   // a frame after every pass (FusedArgs::every)
+    if constexpr (!SEG && GRIDS == 0) if (b.passes > 1u && (b.guide_nh || b.guide_ad)) {   // the caller kept to the route rule (fused_guides_in_passes): no grids, the default pairing
+        if (every) hipLaunchKernelGGL((k_fusedPass<FAST, 0, WAVES, 2, false, true, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+        else hipLaunchKernelGGL((k_fusedPass<FAST, 0, WAVES, 2, false, false, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
+        return;
+    }
     if (every && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2, SEG, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
     else if (every) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 1, SEG, true>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);
     else if (b.passes > 1u && multipass_reuse(GRIDS != 0)) hipLaunchKernelGGL((k_fusedPass<FAST, GRIDS, WAVES, 2, SEG>), grid, dim3(256), lds, s, b, defer_mask, redo_mask, redo_words);

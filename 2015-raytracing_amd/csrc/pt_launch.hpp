@@ -124,9 +124,11 @@ struct FusedArgs {
     uint32_t every;
     uint32_t pass_index;     // the 1-based index of the launch's first pass
     const void* carry;       // float4[passes * nrows * width]; read only by a launch with seg_off != 0
-    // The first-hit guides written BY the pass (mirt_render_first_pass_guided, the one-launch route: pt_pass_plan.hpp fused_guides_in_pass): float4
-    // per pixel of the tile each, as launch_guides writes them; either may be null.  Both null: the pass's ordinary kernels.  One given picks the
-    // GUIDES instantiations of k_fusedPass, which exist for one resolving pass of one contiguous segment only -- the caller keeps to the route rule.
+    // The first-hit guides written BY the pass (mirt_render_first_pass_guided and mirt_render_passes_guided, the one-launch route: pt_pass_plan.hpp
+    // fused_guides_in_pass, fused_guides_in_passes): float4 per pixel of the tile each, as launch_guides writes them; either may be null.  Both null:
+    // the pass's ordinary kernels.  One given picks the GUIDES instantiations of k_fusedPass, which exist for resolving launches of one contiguous
+    // segment only, and with passes > 1 for scenes without grids and their default reuse pairing only (fused_has_grids, fused_multipass_default) --
+    // the caller keeps to the route rule.
     void* guide_nh;          // normal_hits
     void* guide_ad;          // albedo_depth
 };
@@ -135,6 +137,8 @@ inline bool all_sets_fast_ok(const FusedArgs& a) { for (uint32_t i = 0; i < a.n_
 // fast: the optimistic kernel (writes deferred samples' bits into defer_mask); !fast: the exact kernel over `list` (or everything)
 void launch_fused(hipStream_t s, const FusedArgs& a, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, uint32_t redo_words);
 bool fused_fast_available();   // compiled with PT_EXACT_FAST_DIV
+bool fused_has_grids(const FusedArgs& a);           // a set of `a` has more than one cell: the launch runs the grid kernels
+bool fused_multipass_default(const FusedArgs& a);   // a multi-pass launch of `a` would pick the default MULTI pairing (MIRT_MULTIPASS_REUSE unset, or forcing what the default is)
 void launch_deferCount(hipStream_t s, const uint32_t* mask, uint32_t words, uint32_t* count);
 // First-hit guide buffers (pt_kernels_guides.hip): float4 per pixel of the tile, normal_hits = (sum of the hit samples' normals, hits),
 // albedo_depth = (sum of their material colours, sum of their Ray.maxt).  One lane per pixel; the optimistic / exact pair as in launch_fused, the

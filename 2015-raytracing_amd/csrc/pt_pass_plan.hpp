@@ -151,5 +151,17 @@ inline PassPlan pass_plan(const PassRequest& r) {
 inline bool fused_guides_in_pass(const PassPlan& p, uint32_t passes) {
     return p.resolves && p.n_segments == 1u && passes == 1u && (p.rpp == 4u || p.rpp == 16u || p.rpp == 64u);
 }
+// The same question for mirt_render_passes_guided, any passes >= 1: the launch is one of mirt_render_passes's one-launch routes (with or without a
+// frame after every pass) -- the guides are taken in its pass 0, which is the same whichever pass_index the batch starts at -- and the multi-pass
+// kernels are the default pairing (default_pairing: MIRT_MULTIPASS_REUSE does not force the other one; the guided kernels are built for the default
+// only; one pass runs the one-pass kernel, which has no pairing, so the flag does not bear on it).  With one pass and no frame after every pass this is
+// fused_guides_in_pass, whatever the two flags; one pass WITH a frame after every pass is ROUTE_ORDINARY_PASSES, an ordinary pass that the guide
+// launches follow.  Several passes of a scene with grids (`grids`: a set of more than
+// one cell) stay on the guide launches: measured, the grid kernels' multi-pass loop with the guides in it was slower than the two launches (4 passes of
+// cornell_teapot3 1080p x 16: 128.94 and 128.48 ms against 127.59 and 127.83), while scenes without grids gained.
+inline bool fused_guides_in_passes(const PassPlan& p, uint32_t passes, bool default_pairing, bool grids) {
+    return p.resolves && p.n_segments == 1u && (p.rpp == 4u || p.rpp == 16u || p.rpp == 64u) &&
+           (p.route == ROUTE_ONE_LAUNCH || p.route == ROUTE_ONE_LAUNCH_EVERY) && (passes == 1u || (default_pairing && !grids));
+}
 
 }  // namespace pt

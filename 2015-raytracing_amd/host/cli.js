@@ -93,7 +93,7 @@ if (cmd === "pack") {
     }
   }
   process.stderr.write(`rendered ${file} ${w}x${h} rpp ${rpp}, ${passes} pass(es), ${opt.granular ? (opt.fusion ? "kernel-by-kernel, passes fused by the runtime" : "kernel-by-kernel") : "fused"}: ${res.ms.toFixed(2)} ms on ${res.device}; passes the runtime fused from enqueues: ${res.fusedPasses}\n`);
-  process.stderr.write(`first passes that wrote their guides: ${res.guidedPasses || 0}\n`);   // mirt_render_first_pass_guided's one-launch route (ctx.guidedPasses())
+  process.stderr.write(`first passes that wrote their guides: ${res.guidedPasses || 0}\n`);   // calls, of one pass or of several, whose own launch wrote the guides (ctx.guidedPasses(): mirt_render_first_pass_guided and mirt_render_passes_guided); the line keeps the wording it had when only first passes counted, for whoever parses it
   if (res.routes) process.stderr.write(`gather routes per tile: ${res.routes.join(" ")}; peer access root<-tile: ${res.peerAccess.join(" ")}\n`);
 } else if (cmd === "pack-frame" || cmd === "frame") {
   if (rest.length < 4) usage();

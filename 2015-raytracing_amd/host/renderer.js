@@ -295,18 +295,27 @@ class FusedRenderer {
   // accumulator kept, more are split into calls of that many (the frame is the same); without it a frame cannot go on after its first call
   // opt.everyPass: the frame after every pass too (MIRT_PASSES_EVERY_FRAME), into frame buffers of each call's k passes, read back after the call:
   // readFrames() returns them all.  this.pixel / this.radiance then hold the last frame, as without it.
+  // opt.guided: the frame's guides too (queue.renderPassesGuided), from the first call -- they are the same for every pass of a frame.
   executePasses(n, bounces, opt) {
     const every = !!(opt && opt.everyPass);
+    let guides = null;
+    if (opt && opt.guided) {
+      if (!this.normalHits) {
+        this.normalHits = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
+        this.albedoDepth = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 16);
+      }
+      guides = { normalHits: this.normalHits, albedoDepth: this.albedoDepth };
+    }
     if (!this.acu && n > MAX_PASSES_PER_CALL)
       throw new Error(`${n} passes in one launch without a per-ray accumulator: at most ${MAX_PASSES_PER_CALL} (MIRT_MAX_PASSES_PER_CALL); keep the accumulator to split them over calls`);
     if (every) this.frames = { n: 0, pixel: new Uint8ClampedArray(n * this.npix * 4), radiance: new Float32Array(n * this.npix * 4) };
     for (let left = n; left > 0; ) {
       const k = Math.min(left, MAX_PASSES_PER_CALL);
-      if (!every) this.q.renderPasses(this.passDesc(bounces), k);
+      if (!every) this.q.renderPasses(this.passDesc(bounces), k, guides);
       else {
         const fp = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, k * this.npix * 4), fr = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, k * this.npix * 16);
         try {
-          this.q.renderPasses(Object.assign(this.passDesc(bounces), { pixel: fp, radiance: fr, everyPass: true }), k);
+          this.q.renderPasses(Object.assign(this.passDesc(bounces), { pixel: fp, radiance: fr, everyPass: true }), k, guides);
           const f = this.frames, px = f.pixel.subarray(f.n * this.npix * 4, (f.n + k) * this.npix * 4), rd = f.radiance.subarray(f.n * this.npix * 4, (f.n + k) * this.npix * 4);
           this.q.enqueueReadBuffer(fp, true, 0, px.byteLength, px, []);
           this.q.enqueueReadBuffer(fr, true, 0, rd.byteLength, rd, []);
@@ -319,8 +328,12 @@ class FusedRenderer {
       }
       this.passes += k;
       left -= k;
+      guides = null;
     }
   }
+  // n passes in one call and the frame's guides with them (queue.renderPassesGuided): executePasses(n, bounces, opt) and renderGuides() at once
+  canRenderPassesGuided() { return typeof this.q.hasPassesGuided === "function" && this.q.hasPassesGuided(); }
+  executePassesGuided(n, bounces, opt) { this.executePasses(n, bounces, Object.assign({}, opt, { guided: true })); }
   // first-hit guide buffers of this renderer's tile (queue.renderGuides), kept on the device for a gather: normalHits, albedoDepth, float4 per pixel
   renderGuides() {
     if (!this.normalHits) {
@@ -486,9 +499,12 @@ function renderFile(file, width, height, rpp, passes, opt) {
   if (opt.passesInOneLaunch && opt.granular) throw new Error("passes in one launch are the fused pass's (mirt_render_passes): not with the kernel-by-kernel host");
   const R = opt.granular ? new GranularRenderer(packed, opt) : new FusedRenderer(packed, opt);
   // one pass and its guides wanted: the pass writes them too (mirt_render_first_pass_guided), the files are the same bit for bit
-  const guided = !!(opt.guides || opt.denoise) && passes === 1 && !opt.passesInOneLaunch && R.canRenderGuided();
+  // passes in one launch and the guides wanted: that call writes them (mirt_render_passes_guided), with or without a frame after every pass
+  const passesGuided = !!(opt.guides || opt.denoise) && !!opt.passesInOneLaunch && !opt.granular && R.canRenderPassesGuided();
+  const guided = passesGuided || (!!(opt.guides || opt.denoise) && passes === 1 && !opt.passesInOneLaunch && R.canRenderGuided());
   R.q.timerStart();
-  if (guided) R.executeRenderGuided(opt.bounces);
+  if (passesGuided) R.executePassesGuided(passes, opt.bounces, { everyPass: opt.everyPass });
+  else if (guided) R.executeRenderGuided(opt.bounces);
   else if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces, { everyPass: opt.everyPass });
   else for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
   const ms = R.q.timerStopMs();
@@ -523,8 +539,10 @@ function renderUpscaled(file, width, height, rpp, passes, factor, opt) {
   const nh = mk(npix * 16), ad = mk(npix * 16), up = mk(npix * 16), px = mk(npix * 4);
   try {
     R.q.timerStart();
-    const guided = passes === 1 && !opt.passesInOneLaunch && R.canRenderGuided();   // the low frame's one pass writes the low guides too
-    if (guided) R.executeRenderGuided(opt.bounces);
+    const passesGuided = !!opt.passesInOneLaunch && R.canRenderPassesGuided();   // the low frame's passes in one launch write the low guides too
+    const guided = passesGuided || (passes === 1 && !opt.passesInOneLaunch && R.canRenderGuided());   // ... or its one pass does
+    if (passesGuided) R.executePassesGuided(passes, opt.bounces);
+    else if (guided) R.executeRenderGuided(opt.bounces);
     else if (opt.passesInOneLaunch) R.executePasses(passes, opt.bounces);
     else for (let i = 0; i < passes; i++) R.executeRender(opt.bounces);
     if (!guided) R.renderGuides();

@@ -241,7 +241,9 @@ class WebCLCommandQueue {
   // desc.acu may be null where the passes resolve their own pixels (rays_per_pixel > 1 dividing 256, or above 256: mirt.h).
   // At most MAX_PASSES_PER_CALL (checked here: the addon reads the count as a uint32, which would wrap)
   // desc.everyPass: the frame after every pass too (MIRT_PASSES_EVERY_FRAME): desc.pixel / desc.radiance hold n frames back to back (checked here)
-  renderPasses(desc, n) {
+  // guides ({normalHits, albedoDepth}, either may be null, not both): the frame's guide buffers from the same call too (mirt_render_passes_guided,
+  // renderPassesGuided below)
+  renderPasses(desc, n, guides) {
     if (!Number.isInteger(n) || n < 1 || n > MAX_PASSES_PER_CALL)
       throw new WebCLException("INVALID_VALUE", "renderPasses: the pass count is an integer in 1.." + MAX_PASSES_PER_CALL + " (MIRT_MAX_PASSES_PER_CALL), not " + n);
     if (desc.everyPass) {
@@ -251,8 +253,15 @@ class WebCLCommandQueue {
         if (b && b.byteLength < n * npix * per)
           throw new WebCLException("INVALID_BUFFER_SIZE", `renderPasses: ${name} holds ${b.byteLength} bytes, ${n} frames of ${npix} pixels need ${n * npix * per}`);
     }
-    this.renderPass(Object.assign({}, desc, { nPasses: n }));
+    if (!guides) { this.renderPass(Object.assign({}, desc, { nPasses: n })); return; }
+    const d = this._passDesc(Object.assign({}, desc, { nPasses: n }));
+    wrap(() => native().renderPassesGuided(this.ctx.h, d, guides.normalHits ? guides.normalHits.h : null, guides.albedoDepth ? guides.albedoDepth.h : null));
   }
+  // ---- extension: n passes and the frame's guide buffers in one call (mirt_render_passes_guided): every buffer ends as after renderPasses(desc, n)
+  // followed by renderGuides(desc, normalHits, albedoDepth) -- where the launch resolves its pixels at 4, 16 or 64 rays per pixel its first pass
+  // writes the guides (ctx.guidedPasses() counts those calls), elsewhere the guide launches follow.  hasPassesGuided(): the addon binds the entry point (it links the library, so an addon that has it loads only beside a library that has it)
+  hasPassesGuided() { return typeof native().renderPassesGuided === "function"; }
+  renderPassesGuided(desc, n, normalHits, albedoDepth) { this.renderPasses(desc, n, { normalHits: normalHits, albedoDepth: albedoDepth }); }
   // ---- extension: the host's grid builders on the device (mirt_grid_build / mirt_grid_gather_*) ----
   // primsF64: a Float64Array (uploaded here) or a WebCLBuffer that already holds the fp64 soup (meshIngest) with `count` primitives
   gridBuild(kind, primsF64, bounds6, nSlabs, count) {
@@ -353,7 +362,7 @@ class WebCLContext {
   // (mirt_ctx_create) stays at 0 unless asked.
   setFusion(level) { wrap(() => native().ctxSetFusion(this.h, level)); }
   fusedPasses() { return wrap(() => native().ctxFusedPasses(this.h)); }
-  // mirt_ctx_guided_passes: renderFirstPassGuided calls whose pass wrote the guides itself
+  // mirt_ctx_guided_passes: renderFirstPassGuided / renderPassesGuided calls whose launch wrote the guides itself
   guidedPasses() { return typeof native().ctxGuidedPasses === "function" ? wrap(() => native().ctxGuidedPasses(this.h)) : 0; }
   // extension (mirt_ctx_set_frame_fusion): the Assign04 / Assign07 pages' frame stream -- initTrace, then molTrace and / or meshTrace -- runs as one
   // launch and the Ray buffer is not written.  Off unless asked for here or with MIRT_FRAME_FUSION=1 in the environment.

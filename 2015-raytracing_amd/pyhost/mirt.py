@@ -82,6 +82,7 @@ _lib = None
 
 PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
 PASSES_EVERY_FRAME = 2   # MIRT_PASSES_EVERY_FRAME (include/mirt.h)
+MAX_PASSES_PER_CALL = 64   # MIRT_MAX_PASSES_PER_CALL (include/mirt.h)
 
 FILTER_DEMODULATE, FILTER_DIRECT, FILTER_TILED = 1, 2, 4   # MIRT_FILTER_* (include/mirt.h)
 # MIRT_FILTER_DEFAULT_*: the shipped parameters of the a-trous filter (with FILTER_DEMODULATE)
@@ -123,6 +124,7 @@ SYMBOLS = {
     "mirt_render_passes": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32]),
     "mirt_render_guides": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
     "mirt_render_first_pass_guided": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
+    "mirt_render_passes_guided": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mirt_ctx_guided_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
     "mirt_upsample_guided": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc)]),
@@ -496,8 +498,16 @@ class Context:
         render_pass(desc, fresh=True) followed by render_guides(desc, normal_hits, albedo_depth).  Either guide may be None, not both."""
         self._chk(lib().mirt_render_first_pass_guided(self.h, C.byref(desc), normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
 
+    def render_passes_guided(self, desc, n_passes, fresh=False, every_frame=False, normal_hits=None, albedo_depth=None):
+        """n_passes progressive passes and the frame's guide buffers in one call (mirt_render_passes_guided): every buffer ends as after
+        render_passes(desc, n_passes, fresh, every_frame) followed by render_guides(desc, normal_hits, albedo_depth).  Either guide may be None,
+        not both."""
+        flags = (PASSES_FRESH if fresh else 0) | (PASSES_EVERY_FRAME if every_frame else 0)
+        self._chk(lib().mirt_render_passes_guided(self.h, C.byref(desc), int(n_passes), flags, normal_hits.h if normal_hits else None,
+                                                  albedo_depth.h if albedo_depth else None))
+
     def guided_passes(self):
-        """how many render_first_pass_guided calls of this context wrote the guides from the pass's own launch (mirt_ctx_guided_passes)"""
+        """how many render_first_pass_guided / render_passes_guided calls of this context wrote the guides from the pass's own launch (mirt_ctx_guided_passes)"""
         n = C.c_uint64()
         self._chk(lib().mirt_ctx_guided_passes(self.h, C.byref(n)))
         return n.value

@@ -244,12 +244,15 @@ class FusedRenderer:
         if not self.nrays:
             self.passes += n
             return (np.zeros((n, 0, 4), np.uint8), None if self.radiance is None else np.zeros((n, 0, 4), np.float32)) if every_frame else None
+        return self._passes(n, bounces, every_frame, lambda d: self.ctx.render_passes(d, n, fresh=fresh, every_frame=every_frame))
+
+    def _passes(self, n, bounces, every_frame, call):
+        """the body of execute_passes and execute_passes_guided: call(desc) runs the n passes, into n-frame buffers with every_frame"""
         pixel, radiance = self.pixel, self.radiance
         if every_frame:
             pixel = self._frames("_frame_pixel", n * self.npix * 4)
             radiance = None if self.radiance is None else self._frames("_frame_radiance", n * self.npix * 16)
-        d = self.dev.pass_desc(self.seeds, self.acu, pixel, radiance, pass_index=self.passes, bounces=bounces, row0=self.row0, nrows=self.nrows)
-        self.ctx.render_passes(d, n, fresh=fresh, every_frame=every_frame)
+        call(self.dev.pass_desc(self.seeds, self.acu, pixel, radiance, pass_index=self.passes, bounces=bounces, row0=self.row0, nrows=self.nrows))
         self.passes += n
         if not every_frame:
             return None
@@ -331,6 +334,36 @@ class FusedRenderer:
             out.release()
             pix.release()
 
+    def execute_passes_guided(self, n, bounces=5, fresh=False, every_frame=False):
+        """execute_passes(n, bounces, fresh, every_frame) and guides() in one call (mirt_render_passes_guided): the guides go into
+        self.normal_hits / self.albedo_depth as in execute_render_guided, the frames where execute_passes puts them.  Returns what execute_passes
+        returns (None, or with every_frame the n frames)."""
+        if not self.nrays:
+            return self.execute_passes(n, bounces, fresh, every_frame)
+        self.normal_hits, self.albedo_depth = self._frames("normal_hits", self.npix * 16), self._frames("albedo_depth", self.npix * 16)
+        return self._passes(n, bounces, every_frame, lambda d: self.ctx.render_passes_guided(d, n, fresh=fresh, every_frame=every_frame,
+                                                                                               normal_hits=self.normal_hits, albedo_depth=self.albedo_depth))
+
+    def denoised_passes(self, n, bounces=5, **params):
+        """The frame's first n passes with their guides (execute_passes_guided, fresh), then the a-trous filter of that frame guided by the buffers
+        the call wrote: what execute_passes(n, fresh=True) and denoised() give, without the second trace of the primary rays.  params and the
+        result as denoised()."""
+        if self.radiance is None:
+            raise mirt.MirtError(-1, "FusedRenderer.denoised_passes: needs want_radiance")
+        if self.passes != 1:
+            raise mirt.MirtError(-1, "FusedRenderer.denoised_passes: the frame's first passes only")
+        self.execute_passes_guided(n, bounces, fresh=True)
+        if not self.npix:
+            return np.zeros((0, 4), np.uint8), np.zeros((0, 4), np.float32)
+        out, pix = self.ctx.buffer(self.npix * 16), self.ctx.buffer(self.npix * 4)
+        try:
+            tone = np.float32(1.0 / (self.s.rpp * (self.passes - 1)))
+            self.ctx.filter_atrous(self.s.width, self.nrows, tone, self.radiance, self.normal_hits, self.albedo_depth, filtered=out, pixel=pix, **params)
+            return pix.read(np.uint8).reshape(-1, 4), out.read(np.float32).reshape(-1, 4)
+        finally:
+            out.release()
+            pix.release()
+
     def _frames(self, name, nbytes):
         """a frame buffer of at least nbytes, kept for the next call"""
         b = getattr(self, name, None)
@@ -385,6 +418,21 @@ class UpscaledRenderer:
             ctx.render_first_pass_guided(lo.dev.pass_desc(lo.seeds, lo.acu, lo.pixel, lo.radiance, pass_index=1, bounces=bounces), self.nh_lo, self.ad_lo)
             lo.passes += 1
             self.tone = np.float32(1.0 / lo.s.rpp)
+        elif int(passes) > 1:   # several passes: one call runs them and writes the low guides (mirt_render_passes_guided)
+            # a call runs at most mirt.MAX_PASSES_PER_CALL passes: more are split into calls of that many on the accumulator the low renderer keeps
+            # (the frame is the same), and the first call writes the guides -- they are the same for every pass of a frame
+            left, guides = int(passes), dict(normal_hits=self.nh_lo, albedo_depth=self.ad_lo)
+            while left:
+                k = min(left, mirt.MAX_PASSES_PER_CALL)
+                d = lo.dev.pass_desc(lo.seeds, lo.acu, lo.pixel, lo.radiance, pass_index=lo.passes, bounces=bounces)
+                if guides:
+                    ctx.render_passes_guided(d, k, fresh=(lo.passes == 1), **guides)
+                else:
+                    ctx.render_passes(d, k)
+                lo.passes += k
+                left -= k
+                guides = None
+            self.tone = np.float32(1.0 / (lo.s.rpp * (lo.passes - 1)))
         else:
             for _ in range(int(passes)):
                 lo.execute_render(bounces, fresh=(lo.passes == 1))

@@ -258,15 +258,38 @@ MIRT_API int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* desc, mirt_
  * order and writes the guides itself.  EVERYWHERE ELSE -- 256 rays (a pixel spans four waves), counts that do not divide 256 or are above it,
  * MIRT_INPASS_RESOLVE=0, acu given with neither pixel nor radiance -- the call queues the pass and then the guide launches exactly as the two
  * calls would.  MIRT_GUIDED_PASS=0 in the environment forces that everywhere (an A/B switch).  mirt_ctx_guided_passes: how many calls of this
- * context took the one-launch route.  What the call does not do: several passes in one launch (mirt_render_passes has no guided form), a
- * one-launch route at 256 rays per pixel, guides from a later pass (mirt_render_pass) -- they are the same for every pass of a frame, so
- * the first pass is where they are taken.
+ * context took the one-launch route (this call's and mirt_render_passes_guided's).  What the call does not do: several passes in one launch
+ * (that is mirt_render_passes_guided), a one-launch route at 256 rays per pixel, guides from a later pass (mirt_render_pass) -- they are the
+ * same for every pass of a frame, so the first pass is where they are taken.
  * The optimistic kernel writes a block's guides before it knows whether the block stays inside the guard windows; a block that does not is
  * re-run whole by the exact kernel, which writes the same pixels' guides again, later on the same stream.  The outputs are therefore final
  * when the call's launches have completed (stream order, mirt_finish), like every other output of the pass -- not before.
  * MIRT_ABI_VERSION is unchanged: a host detects the two entry points by their symbols. */
 MIRT_API int mirt_render_first_pass_guided(mirt_ctx* ctx, const mirt_pass_desc* desc, mirt_buf* normal_hits, mirt_buf* albedo_depth);
 MIRT_API int mirt_ctx_guided_passes(mirt_ctx* ctx, uint64_t* count);
+/* SEVERAL PASSES AND THE FRAME'S GUIDES in one call.  Every buffer the caller passes -- seeds, acu if given, pixel, radiance (n_passes frames
+ * each with MIRT_PASSES_EVERY_FRAME), normal_hits, albedo_depth -- ends bit for bit as after mirt_render_passes(ctx, desc, n_passes, flags)
+ * followed by mirt_render_guides(ctx, desc, normal_hits, albedo_depth), fresh or not and at any pass_index: the k x k lens grid draws nothing from
+ * the seeds, so the guides are those of every pass of the frame, and the launch takes them from the first pass it runs.
+ * Checks: those of both calls, all before anything is queued -- when one fails nothing is written at all.  n_passes and flags as in
+ * mirt_render_passes; either guide output may be NULL, not both (MIRT_E_ARG); rays_per_pixel == 1 is MIRT_E_ARG; a guide buffer smaller than the
+ * tile's pixels x 16 B is MIRT_E_RANGE; a guide buffer whose bytes are, or overlap, those of any buffer of the descriptor (pixel and radiance at
+ * their whole n_passes frames) or of the other guide is MIRT_E_ARG; not while capturing (MIRT_E_ARG).
+ * ROUTE.  ONE LAUNCH (per kernel of the optimistic / exact pair): where mirt_render_passes runs the batch as one launch -- with or without a
+ * frame after every pass -- that resolves its pixels in the kernel as one segment with rays_per_pixel 4, 16 or 64, the launch's first pass adds a
+ * pixel's eight values lane by lane right after its primary rays' closest-hit stage and writes the guides itself; mirt_ctx_guided_passes counts
+ * the call.  EVERYWHERE ELSE -- 256 rays, counts that do not divide 256 or are above it, acu given with neither pixel nor radiance,
+ * MIRT_INPASS_RESOLVE=0, MIRT_GUIDED_PASS=0, several passes with MIRT_MULTIPASS_REUSE forcing the pairing that is not the default one (the guided
+ * multi-pass kernels are built for the default; one pass has no pairing), several passes of a scene with a grid of more than one cell (measured: writing the guides from the grid kernels'
+ * multi-pass loop was slower than the guide launches behind it), n_passes ordinary passes (MIRT_PASSES_EVERY_FRAME where the passes do not resolve in the kernel, or with n_passes
+ * 1) -- the call queues what mirt_render_passes queues and then the guide launches, exactly as the two calls would.  With n_passes 1 and no
+ * MIRT_PASSES_EVERY_FRAME the call is mirt_render_first_pass_guided (MIRT_PASSES_FRESH) in every buffer.
+ * As there, an optimistic block writes its guides before its verdict, which may come in any pass; the exact kernel re-runs such a block from
+ * its first pass and writes the same pixels' guides again, so the outputs are final when the call's launches have completed.  mirt_pass_deferred
+ * and mirt_pass_timing mean what they mean for mirt_render_passes.  What the call does not do: a one-launch route at 256 rays per pixel or
+ * above, graph capture.  MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
+MIRT_API int mirt_render_passes_guided(mirt_ctx* ctx, const mirt_pass_desc* desc, uint32_t n_passes, uint32_t flags, mirt_buf* normal_hits,
+                                       mirt_buf* albedo_depth);
 /* Edge-avoiding A-TROUS FILTER of a few-rays-per-pixel frame, guided by the first-hit guide buffers: `radiance` as a pass writes it (un-scaled
  * sums), `normal_hits` and `albedo_depth` as mirt_render_guides writes them, all float4 per pixel of a width x height image -- a whole frame, or a
  * gathered one.  Everything stays on the device; the working images live in the context's scratch buffer.
