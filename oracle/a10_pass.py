@@ -198,11 +198,13 @@ class PassState:
         return {k: getattr(self, k).copy() for k in names}
 
 
-def run_pass(k, sc, st, bounces=5, checkpoints=None, init_acu=True, rows=None):
+def run_pass(k, sc, st, bounces=5, checkpoints=None, init_acu=True, rows=None, watch=None):
     """One executeRender() (code.js:1806-1854).  `checkpoints`: optional dict that
     receives snapshots after the primary segment ('primary') and each bounce.
     `rows`: launch the 2-D initTrace over the first `rows` image rows only and every 1-D kernel over their rays -- the camera still
-    says sc.height rows, so these ARE rays 0 .. width*rows*rpp-1 of the full frame (a top band of a frame too big to hold whole)."""
+    says sc.height rows, so these ARE rays 0 .. width*rows*rpp-1 of the full frame (a top band of a frame too big to hold whole).
+    `watch`: optional callable, called as watch("rays", st.rays) after initTrace and after every bouncePaths and as watch("shadow", st.shadow)
+    after every initShadowTrace -- every ray the pass makes, before anything traces it."""
     h = sc.height if rows is None else rows
     n = sc.width * h * sc.rpp
     g1 = _ceil(n, WAVE)
@@ -215,6 +217,13 @@ def run_pass(k, sc, st, bounces=5, checkpoints=None, init_acu=True, rows=None):
     # getLocalWS(2, ...) with a multiple of 64 -> [8, 8]  (code.js:661-663)
     k.initTrace(B(st.seeds), B(st.rays), B(st.pois), bp, cp, sc.focal_length, sc.lens_rad, sc.rpp,
                 _ceil(sc.width, 8), _ceil(h, 8))
+
+    def seen(kind, rays):
+        if watch is not None:
+            k.flush()
+            watch(kind, rays)
+
+    seen("rays", st.rays)
 
     def closest():
         if sc.has_spheres:
@@ -231,6 +240,7 @@ def run_pass(k, sc, st, bounces=5, checkpoints=None, init_acu=True, rows=None):
         for l in sc.lights:
             p, _k = _f(l["shadow"])
             k.initShadowTrace(B(st.shadow), B(st.pois), n, p, B(st.seeds), g1)
+            seen("shadow", st.shadow)
             if sc.has_spheres:
                 p, _k = _f(sc.sphere_bounds)
                 k.sphereShadowTrace(n, B(st.shadow), B(sc.spheres), B(sc.s_box), p, sc.n_slabs, g1)
@@ -253,6 +263,7 @@ def run_pass(k, sc, st, bounces=5, checkpoints=None, init_acu=True, rows=None):
         checkpoints["primary"] = st.snapshot()
     for j in range(bounces):
         k.bouncePaths(B(st.pois), B(st.rays), B(st.seeds), n, g1)
+        seen("rays", st.rays)
         closest()
         direct()
         if checkpoints is not None and j == 0:
