@@ -410,12 +410,7 @@ napi_value RenderPassesGuided(napi_env env, napi_callback_info info) {
 
 // filterAtrous(ctx, {width,height,iterations,flags,normalPowerLog2,tone,sigmaDepth,sigmaColour, radiance,normalHits,albedoDepth, filtered?,pixel?}):
 // the a-trous filter of a frame on the device (mirt_filter_atrous); a number left out is 0, a buffer left out NULL -- the library checks them all
-napi_value FilterAtrous(napi_env env, napi_callback_info info) {
-    ARGS(2);
-    void* c;
-    if (!get_ext(env, argv[0], &c)) return throw_type(env, "filterAtrous(ctx, desc)");
-    napi_value d = argv[1];
-    mirt_filter_desc f;
+void filter_desc(napi_env env, napi_value d, mirt_filter_desc& f) {
     memset(&f, 0, sizeof f);
     f.struct_size = sizeof f;
     prop_u32(env, d, "width", &f.width);
@@ -431,7 +426,31 @@ napi_value FilterAtrous(napi_env env, napi_callback_info info) {
     f.albedo_depth = prop_buf(env, d, "albedoDepth");
     f.filtered = prop_buf(env, d, "filtered");
     f.pixel = prop_buf(env, d, "pixel");
+}
+napi_value FilterAtrous(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "filterAtrous(ctx, desc)");
+    mirt_filter_desc f;
+    filter_desc(env, argv[1], f);
     const int rc = mirt_filter_atrous((mirt_ctx*)c, &f);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+// filterAtrousRows(ctx, desc): the same descriptor read as mirt_filter_atrous_rows reads it -- height: the rows of the window the inputs hold -- and
+// imageHeight, winRow0, row0, nrows beside it
+napi_value FilterAtrousRows(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "filterAtrousRows(ctx, desc)");
+    mirt_filter_desc f;
+    filter_desc(env, argv[1], f);
+    uint32_t image_height = 0, win_row0 = 0, row0 = 0, nrows = 0;
+    prop_u32(env, argv[1], "imageHeight", &image_height);
+    prop_u32(env, argv[1], "winRow0", &win_row0);
+    prop_u32(env, argv[1], "row0", &row0);
+    prop_u32(env, argv[1], "nrows", &nrows);
+    const int rc = mirt_filter_atrous_rows((mirt_ctx*)c, &f, image_height, win_row0, row0, nrows);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);
 }
@@ -439,12 +458,7 @@ napi_value FilterAtrous(napi_env env, napi_callback_info info) {
 // upsampleGuided(ctx, {width,height,factor,flags,normalPowerLog2,tone,sigmaDepth, radianceLo,normalHitsLo,albedoDepthLo, normalHits,albedoDepth,
 // upsampled?,pixel?}): guide-driven upsampling of a frame shaded at 1/factor resolution (mirt_upsample_guided); a number left out is 0, a buffer
 // left out NULL -- the library checks them all
-napi_value UpsampleGuided(napi_env env, napi_callback_info info) {
-    ARGS(2);
-    void* c;
-    if (!get_ext(env, argv[0], &c)) return throw_type(env, "upsampleGuided(ctx, desc)");
-    napi_value d = argv[1];
-    mirt_upsample_desc u;
+void upsample_desc(napi_env env, napi_value d, mirt_upsample_desc& u) {
     memset(&u, 0, sizeof u);
     u.struct_size = sizeof u;
     prop_u32(env, d, "width", &u.width);
@@ -461,7 +475,30 @@ napi_value UpsampleGuided(napi_env env, napi_callback_info info) {
     u.albedo_depth = prop_buf(env, d, "albedoDepth");
     u.upsampled = prop_buf(env, d, "upsampled");
     u.pixel = prop_buf(env, d, "pixel");
+}
+napi_value UpsampleGuided(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "upsampleGuided(ctx, desc)");
+    mirt_upsample_desc u;
+    upsample_desc(env, argv[1], u);
     const int rc = mirt_upsample_guided((mirt_ctx*)c, &u);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+// upsampleGuidedRows(ctx, desc): the same descriptor read as mirt_upsample_guided_rows reads it, and row0, nrows, loRow0, loNrows beside it
+napi_value UpsampleGuidedRows(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "upsampleGuidedRows(ctx, desc)");
+    mirt_upsample_desc u;
+    upsample_desc(env, argv[1], u);
+    uint32_t row0 = 0, nrows = 0, lo_row0 = 0, lo_nrows = 0;
+    prop_u32(env, argv[1], "row0", &row0);
+    prop_u32(env, argv[1], "nrows", &nrows);
+    prop_u32(env, argv[1], "loRow0", &lo_row0);
+    prop_u32(env, argv[1], "loNrows", &lo_nrows);
+    const int rc = mirt_upsample_guided_rows((mirt_ctx*)c, &u, row0, nrows, lo_row0, lo_nrows);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);
 }
@@ -731,6 +768,54 @@ napi_value Gather(napi_env env, napi_callback_info info) {
     return undef(env);
 }
 
+// ---- the post-process stage in row tiles: the two windows and the halo exchange (mirt_filter_window_rows, mirt_upsample_low_rows, mirt_exchange_rows)
+napi_value rows_object(napi_env env, uint32_t r0, uint32_t nr) {
+    napi_value o;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "row0", mk_num(env, r0));
+    napi_set_named_property(env, o, "nrows", mk_num(env, nr));
+    return o;
+}
+napi_value FilterWindowRows(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    uint32_t v[4], r0 = 0, nr = 0;
+    for (int i = 0; i < 4; ++i)
+        if (!get_u32(env, argv[i], &v[i])) return throw_type(env, "filterWindowRows(imageHeight, row0, nrows, iterations)");
+    mirt_filter_window_rows(v[0], v[1], v[2], v[3], &r0, &nr);
+    return rows_object(env, r0, nr);
+}
+napi_value UpsampleLowRows(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    uint32_t v[4], r0 = 0, nr = 0;
+    for (int i = 0; i < 4; ++i)
+        if (!get_u32(env, argv[i], &v[i])) return throw_type(env, "upsampleLowRows(height, factor, row0, nrows)");
+    mirt_upsample_low_rows(v[0], v[1], v[2], v[3], &r0, &nr);
+    return rows_object(env, r0, nr);
+}
+// exchangeRows(group, [source buffer | null], [{row0, nrows}], [destination buffer | null], [{row0, nrows}], rowBytes)
+napi_value ExchangeRows(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    static const char usage[] = "exchangeRows(group, [src | null], [{row0, nrows}], [dst | null], [{row0, nrows}], rowBytes)";
+    void* g; uint32_t n = 0; double row_bytes = 0;
+    if (!get_ext(env, argv[0], &g) || napi_get_array_length(env, argv[1], &n) != napi_ok || !get_f64(env, argv[5], &row_bytes) || row_bytes < 0) return throw_type(env, usage);
+    std::vector<mirt_buf*> buf[2] = {std::vector<mirt_buf*>(n, nullptr), std::vector<mirt_buf*>(n, nullptr)};
+    std::vector<uint32_t> row0[2] = {std::vector<uint32_t>(n, 0), std::vector<uint32_t>(n, 0)}, nrows[2] = {std::vector<uint32_t>(n, 0), std::vector<uint32_t>(n, 0)};
+    for (int side = 0; side < 2; ++side) {
+        uint32_t nb = 0, nr = 0;
+        if (napi_get_array_length(env, argv[1 + 2 * side], &nb) != napi_ok || napi_get_array_length(env, argv[2 + 2 * side], &nr) != napi_ok || nb != n || nr != n) return throw_type(env, usage);
+        for (uint32_t i = 0; i < n; ++i) {
+            napi_value e; void* b = nullptr;
+            if (napi_get_element(env, argv[1 + 2 * side], i, &e) != napi_ok) return throw_type(env, usage);
+            if (get_ext(env, e, &b)) buf[side][i] = (mirt_buf*)b;      // anything else (null, undefined): no buffer
+            if (napi_get_element(env, argv[2 + 2 * side], i, &e) != napi_ok || !prop_u32(env, e, "row0", &row0[side][i]) || !prop_u32(env, e, "nrows", &nrows[side][i]))
+                return throw_type(env, usage);
+        }
+    }
+    int rc = mirt_exchange_rows((mirt_group*)g, buf[0].data(), row0[0].data(), nrows[0].data(), buf[1].data(), row0[1].data(), nrows[1].data(), (int)n, (size_t)row_bytes);
+    if (rc) return throw_mirt(env, rc, mirt_group_ctx((mirt_group*)g, 0));
+    return undef(env);
+}
+
 // mirt_abi_version / mirt_group_peer_access / mirt_gather_route: what a first run on N real devices is diagnosed from
 napi_value AbiVersion(napi_env env, napi_callback_info) { return mk_num(env, mirt_abi_version()); }
 napi_value GroupPeerAccess(napi_env env, napi_callback_info info) {
@@ -762,6 +847,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},
         {"abiVersion", AbiVersion}, {"groupPeerAccess", GroupPeerAccess}, {"gatherRoute", GatherRoute},
+        {"filterAtrousRows", FilterAtrousRows}, {"upsampleGuidedRows", UpsampleGuidedRows}, {"filterWindowRows", FilterWindowRows}, {"upsampleLowRows", UpsampleLowRows}, {"exchangeRows", ExchangeRows},
     };
     for (auto& f : fns) {
         napi_value fn;

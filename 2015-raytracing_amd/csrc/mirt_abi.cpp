@@ -8,6 +8,7 @@
 #include "../../include/mirt.h"
 #include "pt_launch.hpp"
 #include "pt_post_check.hpp"
+#include "pt_rows_plan.hpp"
 #include "pt_set_guard.hpp"
 #include "pt_stream_match.hpp"
 #include "pt_upsample_taps.hpp"
@@ -1716,6 +1717,224 @@ int mirt_upsample_guided(mirt_ctx* ctx, const mirt_upsample_desc* d) try {
     pt::launch_upsample(ctx->stream, A);
     return post_finish(ctx, b + 5);
 } MIRT_CATCH("mirt_upsample_guided", return MIRT_E_DEVICE)
+
+// ---- the post-process stage in row tiles: mirt_filter_atrous_rows, mirt_upsample_guided_rows and the halo exchange between them, mirt_exchange_rows.
+// The row arithmetic and the rules of the rows are pt_rows_plan.hpp's (host-only, CPU-tested); here are their messages.
+static_assert(pt::kRowsMaxIterations == MIRT_FILTER_MAX_ITERATIONS, "pt_rows_plan.hpp restates the header's limit");
+
+void mirt_filter_window_rows(uint32_t image_height, uint32_t row0, uint32_t nrows, uint32_t iterations, uint32_t* win_row0, uint32_t* win_nrows) try {
+    const pt::RowRange w = pt::filter_window(image_height, row0, nrows, iterations);
+    if (win_row0) *win_row0 = w.row0;
+    if (win_nrows) *win_nrows = w.nrows;
+} MIRT_CATCH("mirt_filter_window_rows", return)
+
+void mirt_upsample_low_rows(uint32_t height, uint32_t factor, uint32_t row0, uint32_t nrows, uint32_t* lo_row0, uint32_t* lo_nrows) try {
+    const pt::RowRange w = pt::upsample_low_window(height, factor, row0, nrows);
+    if (lo_row0) *lo_row0 = w.row0;
+    if (lo_nrows) *lo_nrows = w.nrows;
+} MIRT_CATCH("mirt_upsample_low_rows", return)
+
+static int rows_verdict(mirt_ctx* ctx, const char* fn, pt::RowsVerdict v, const char* window, uint32_t w0, uint32_t wn, uint32_t row0, uint32_t nrows, const pt::RowRange& need) {
+    if (v == pt::ROWS_EMPTY) return fail(ctx, MIRT_E_ARG, "%s: no rows asked for, or an empty %s", fn, window);
+    if (v == pt::ROWS_OUTSIDE_IMAGE) return fail(ctx, MIRT_E_ARG, "%s: rows [%u, +%u) or the %s [%u, +%u) reach outside the image", fn, row0, nrows, window, w0, wn);
+    if (v == pt::ROWS_WINDOW_SHORT)
+        return fail(ctx, MIRT_E_ARG, "%s: the %s [%u, +%u) does not contain [%u, +%u), the rows that rows [%u, +%u) depend on", fn, window, w0, wn, need.row0, need.nrows, row0, nrows);
+    return MIRT_OK;
+}
+
+// The a-trous filter of rows [row0, row0 + nrows) from a window of the image (defined in include/mirt.h): mirt_filter_atrous's checks and launches
+// with the window as the image the kernels see; every launch computes its band of the window alone (pt_rows_plan.hpp's filter_band), the last one
+// the own rows.  MIRT_FILTER_ROWS_BAND=0 (a measurement switch: profiles/post_rows_bench.py): every launch but the last computes the whole window.
+int mirt_filter_atrous_rows(mirt_ctx* ctx, const mirt_filter_desc* d, uint32_t image_height, uint32_t win_row0, uint32_t row0, uint32_t nrows) try {
+    static const char fn[] = "mirt_filter_atrous_rows";
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_filter_atrous_rows: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, fn);
+    if (!d || d->struct_size != sizeof(mirt_filter_desc)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous_rows: descriptor size mismatch");
+    int rc;
+    if ((rc = post_check_extent(ctx, fn, d->width, image_height))) return rc;
+    if (d->iterations > MIRT_FILTER_MAX_ITERATIONS) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous_rows: %u iterations > %u", d->iterations, MIRT_FILTER_MAX_ITERATIONS);
+    if ((rc = post_check_terms(ctx, fn, d->normal_power_log2, d->tone))) return rc;
+    const uint32_t both = MIRT_FILTER_DIRECT | MIRT_FILTER_TILED;
+    if ((d->flags & ~(MIRT_FILTER_DEMODULATE | both)) || (d->flags & both) == both) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous_rows: unknown flags 0x%x (or both structures forced)", d->flags);
+    const uint32_t win_nrows = d->height;
+    if ((rc = rows_verdict(ctx, fn, pt::filter_rows_check(image_height, win_row0, win_nrows, row0, nrows, d->iterations), "window", win_row0, win_nrows, row0, nrows,
+                           pt::filter_window(image_height, row0, nrows, d->iterations)))) return rc;
+    const uint64_t nwin = (uint64_t)d->width * win_nrows, nown = (uint64_t)d->width * nrows;
+    const PostBuf b[5] = {{"mirt_filter_atrous_rows radiance", d->radiance, nwin * 16}, {"mirt_filter_atrous_rows normal_hits", d->normal_hits, nwin * 16}, {"mirt_filter_atrous_rows albedo_depth", d->albedo_depth, nwin * 16},
+                          {"mirt_filter_atrous_rows filtered", d->filtered, nown * 16}, {"mirt_filter_atrous_rows pixel", d->pixel, nown * 4}};
+    if ((rc = post_check_buffers(ctx, fn, "filtered", b))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::FilterRowsArgs A;
+    memset(&A, 0, sizeof A);
+    A.width = d->width; A.height = win_nrows;
+    A.demodulate = (d->flags & MIRT_FILTER_DEMODULATE) ? 1u : 0u;
+    A.npow = d->normal_power_log2;
+    A.depth_on = pt::post_finite_positive(d->sigma_depth);
+    A.colour_on = pt::post_finite_positive(d->sigma_colour);
+    A.tone = d->tone; A.sigma_depth = d->sigma_depth;
+    A.radiance = d->radiance->ptr; A.normal_hits = d->normal_hits->ptr; A.albedo_depth = d->albedo_depth->ptr;
+    A.filtered = d->filtered ? d->filtered->ptr : nullptr;
+    A.pixel = d->pixel ? d->pixel->ptr : nullptr;
+    if (d->iterations) {
+        const size_t plane = (size_t)nwin * 16;
+        if ((rc = ensure_scratch(ctx, 3 * plane))) return rc;
+        char* const scratch = (char*)ctx->scratch;
+        A.work[0] = scratch; A.work[1] = scratch + plane; A.guide = scratch + 2 * plane;
+    }
+    const char* const be = getenv("MIRT_FILTER_ROWS_BAND");
+    const bool shrink = !(be && be[0] == '0');
+    // the band of launch i (the prepare: i == iterations), in rows of the window
+    const auto band = [&](uint32_t i) {
+        const bool last = i + 1u == d->iterations || d->iterations == 0u;
+        const pt::RowRange r = shrink || last ? pt::filter_band(win_row0, win_nrows, row0, nrows, d->iterations, i) : pt::RowRange{win_row0, win_nrows};
+        A.band_row0 = r.row0 - win_row0; A.band_nrows = r.nrows;
+    };
+    band(d->iterations);
+    pt::launch_filterPrepareRows(ctx->stream, A, d->iterations == 0u);
+    for (uint32_t i = 0; i < d->iterations; ++i) {
+        // inv_i as in mirt_filter_atrous: three IEEE fp32 operations of the host, each rounded on its own
+        volatile float k = d->sigma_colour * std::ldexp(1.0f, -(int)i);
+        volatile float kk = k * k;
+        volatile float inv = 1.0f / kk;
+        const bool tiled = (d->flags & both) ? (d->flags & MIRT_FILTER_TILED) != 0u : (pt::kFilterTiledSteps >> i & 1u) != 0u;
+        band(i);
+        pt::launch_filterStepRows(ctx->stream, A, i & 1u, i, A.colour_on ? inv : 0.0f, i + 1u == d->iterations, tiled);
+    }
+    return post_finish(ctx, b + 3);
+} MIRT_CATCH("mirt_filter_atrous_rows", return MIRT_E_DEVICE)
+
+// Guide-driven upsampling of high rows [row0, row0 + nrows) (defined in include/mirt.h): mirt_upsample_guided's checks on the whole image, the rule
+// of the low rows, then one launch over the band.
+int mirt_upsample_guided_rows(mirt_ctx* ctx, const mirt_upsample_desc* d, uint32_t row0, uint32_t nrows, uint32_t lo_row0, uint32_t lo_nrows) try {
+    static const char fn[] = "mirt_upsample_guided_rows";
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_upsample_guided_rows: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, fn);
+    if (!d || d->struct_size != sizeof(mirt_upsample_desc)) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided_rows: descriptor size mismatch");
+    int rc;
+    if ((rc = post_check_extent(ctx, fn, d->width, d->height))) return rc;
+    if (!pt::upsample_factor_ok(d->factor))
+        return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided_rows: factor %u is outside %u .. %u", d->factor, MIRT_UPSAMPLE_MIN_FACTOR, MIRT_UPSAMPLE_MAX_FACTOR);
+    const uint32_t wl = pt::upsample_low_extent(d->width, d->factor), hl = pt::upsample_low_extent(d->height, d->factor);
+    if (!wl || !hl)
+        return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided_rows: %ux%u is not a multiple of factor %u (the two images would not show the same frustum)", d->width, d->height, d->factor);
+    if ((rc = post_check_terms(ctx, fn, d->normal_power_log2, d->tone))) return rc;
+    if (d->flags & ~MIRT_UPSAMPLE_DEMODULATE) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided_rows: unknown flags 0x%x", d->flags);
+    if ((rc = rows_verdict(ctx, fn, pt::upsample_rows_check(d->height, d->factor, row0, nrows, lo_row0, lo_nrows), "low rows", lo_row0, lo_nrows, row0, nrows,
+                           pt::upsample_low_window(d->height, d->factor, row0, nrows)))) return rc;
+    const uint64_t npix = (uint64_t)d->width * nrows, nlo = (uint64_t)wl * lo_nrows;
+    const PostBuf b[7] = {{"mirt_upsample_guided_rows radiance_lo", d->radiance_lo, nlo * 16}, {"mirt_upsample_guided_rows normal_hits_lo", d->normal_hits_lo, nlo * 16}, {"mirt_upsample_guided_rows albedo_depth_lo", d->albedo_depth_lo, nlo * 16},
+                          {"mirt_upsample_guided_rows normal_hits", d->normal_hits, npix * 16}, {"mirt_upsample_guided_rows albedo_depth", d->albedo_depth, npix * 16},
+                          {"mirt_upsample_guided_rows upsampled", d->upsampled, npix * 16}, {"mirt_upsample_guided_rows pixel", d->pixel, npix * 4}};
+    if ((rc = post_check_buffers(ctx, fn, "upsampled", b))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::UpsampleRowsArgs A;
+    memset(&A, 0, sizeof A);
+    A.width = d->width; A.height = d->height; A.factor = d->factor;
+    A.demodulate = (d->flags & MIRT_UPSAMPLE_DEMODULATE) ? 1u : 0u;
+    A.npow = d->normal_power_log2;
+    A.depth_on = pt::post_finite_positive(d->sigma_depth);
+    A.tone = d->tone; A.sigma_depth = d->sigma_depth;
+    A.radiance_lo = d->radiance_lo->ptr; A.normal_hits_lo = d->normal_hits_lo->ptr; A.albedo_depth_lo = d->albedo_depth_lo->ptr;
+    A.normal_hits = d->normal_hits->ptr; A.albedo_depth = d->albedo_depth->ptr;
+    A.upsampled = d->upsampled ? d->upsampled->ptr : nullptr;
+    A.pixel = d->pixel ? d->pixel->ptr : nullptr;
+    A.row0 = row0; A.nrows = nrows; A.lo_row0 = lo_row0;
+    pt::launch_upsampleRows(ctx->stream, A);
+    return post_finish(ctx, b + 5);
+} MIRT_CATCH("mirt_upsample_guided_rows", return MIRT_E_DEVICE)
+
+// The halo exchange (defined in include/mirt.h): every check, then the plan of pt_rows_plan.hpp as copies on the destinations' streams, between
+// events that order them after the sources' work and the sources' next work after them.
+namespace {
+struct EventSet {   // events of one call, destroyed when it returns: the runtime releases each once the work queued on it has completed
+    std::vector<hipEvent_t> ev;
+    explicit EventSet(size_t n) : ev(n, nullptr) {}
+    ~EventSet() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+}  // namespace
+int mirt_exchange_rows(mirt_group* g, mirt_buf* const* src, const uint32_t* src_row0, const uint32_t* src_nrows, mirt_buf* const* dst, const uint32_t* dst_row0,
+                       const uint32_t* dst_nrows, int n_ctx, size_t row_bytes) try {
+    if (!live_group(g)) return fail(nullptr, MIRT_E_HANDLE, "mirt_exchange_rows: unknown group");
+    const int n = (int)g->ctxs.size();
+    mirt_ctx* const c0 = g->ctxs[0];
+    // arguments first: nothing is flushed or queued on any device for a call that is going to be refused
+    if (!src || !src_row0 || !src_nrows || !dst || !dst_row0 || !dst_nrows) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows: null argument");
+    if (n_ctx != n) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows: %d entries for a group of %d contexts", n_ctx, n);
+    if (!row_bytes || row_bytes % 4u) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows: row_bytes %zu is not a positive multiple of 4", row_bytes);
+    std::vector<pt::PostRange> rs((size_t)n), rd((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const struct { const char* what; mirt_buf* b; uint32_t rows; pt::PostRange* r; } side[2] = {{"source", src[i], src_nrows[i], &rs[(size_t)i]}, {"destination", dst[i], dst_nrows[i], &rd[(size_t)i]}};
+        for (const auto& e : side) {
+            *e.r = pt::PostRange{0, (uint64_t)e.rows * row_bytes, false};
+            if (!e.b && !e.rows) continue;
+            if (!live_has(e.b) || e.b->ctx != g->ctxs[(size_t)i]) return fail(c0, MIRT_E_HANDLE, "mirt_exchange_rows: %s %d is not a live buffer of the group's context %d", e.what, i, i);
+            if ((uint64_t)e.b->bytes < e.r->bytes)
+                return fail(c0, MIRT_E_RANGE, "mirt_exchange_rows: %s %d holds %zu bytes, %u rows of %zu bytes need %llu", e.what, i, e.b->bytes, e.rows, row_bytes, (unsigned long long)e.r->bytes);
+            e.r->addr = (uint64_t)(uintptr_t)e.b->ptr;
+            e.r->present = e.rows != 0u;
+        }
+    }
+    std::vector<pt::RowCopy> plan;
+    size_t at = 0;
+    const pt::ExchangeVerdict v = pt::exchange_plan(src_row0, src_nrows, dst_row0, dst_nrows, (size_t)n, &plan, &at);
+    if (v == pt::EXCHANGE_OWNERS_OVERLAP) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows: source %zu owns rows that another source owns too", at);
+    if (v == pt::EXCHANGE_ROW_UNOWNED) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows: destination %zu wants a row that no source owns", at);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            if (pt::post_ranges_meet(rd[(size_t)i], rs[(size_t)j])) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows: destination %d's bytes meet source %d's", i, j);
+            if (j < i && pt::post_ranges_meet(rd[(size_t)i], rd[(size_t)j])) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows: destination %d's bytes meet destination %d's", i, j);
+        }
+    for (int i = 0; i < n; ++i)   // (reported on context 0, like every refusal of this call: that is where a host looks)
+        if (g->ctxs[(size_t)i]->capturing) return fail(c0, MIRT_E_ARG, "mirt_exchange_rows is not possible inside mirt_capture_begin/end (context %d is recording)", i);
+    for (auto* c : g->ctxs) FLUSH_PENDING(c);
+    // which destination reads which source across two streams (on one stream the order of the queue is the order)
+    std::vector<uint8_t> reads((size_t)n * n, 0), src_read((size_t)n, 0), dst_waits((size_t)n, 0);
+    for (const pt::RowCopy& c : plan)
+        if (g->ctxs[c.src_ctx]->stream != g->ctxs[c.dst_ctx]->stream) { reads[(size_t)c.dst_ctx * n + c.src_ctx] = 1; src_read[c.src_ctx] = 1; dst_waits[c.dst_ctx] = 1; }
+    EventSet es((size_t)n), ed((size_t)n);
+    // 1. one event on every source's stream: the tile is written
+    for (int s = 0; s < n; ++s) {
+        if (!src_read[(size_t)s]) continue;
+        mirt_ctx* c = g->ctxs[(size_t)s];
+        HIPCHK(c0, hipSetDevice(c->device));
+        HIPCHK(c0, hipEventCreateWithFlags(&es.ev[(size_t)s], hipEventDisableTiming));
+        HIPCHK(c0, hipEventRecord(es.ev[(size_t)s], c->stream));
+    }
+    // 2. every destination's stream waits for the owners it reads, copies, and records that it has read them
+    size_t k = 0;
+    for (int d = 0; d < n; ++d) {
+        if (k == plan.size() || plan[k].dst_ctx != (uint32_t)d) continue;   // the plan is ordered by destination
+        mirt_ctx* c = g->ctxs[(size_t)d];
+        HIPCHK(c0, hipSetDevice(c->device));
+        for (int s = 0; s < n; ++s)
+            if (reads[(size_t)d * n + s]) HIPCHK(c0, hipStreamWaitEvent(c->stream, es.ev[(size_t)s], 0));
+        for (; k < plan.size() && plan[k].dst_ctx == (uint32_t)d; ++k) {
+            const pt::RowCopy& cp = plan[k];
+            mirt_ctx* sc = g->ctxs[cp.src_ctx];
+            char* const to = (char*)dst[d]->ptr + (size_t)cp.dst_row * row_bytes;
+            const char* const from = (const char*)src[cp.src_ctx]->ptr + (size_t)cp.src_row * row_bytes;
+            const size_t bytes = (size_t)cp.nrows * row_bytes;
+            if (sc->device == c->device) HIPCHK(c0, hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, c->stream));
+            else HIPCHK(c0, hipMemcpyPeerAsync(to, c->device, from, sc->device, bytes, c->stream));
+        }
+        dst[d]->version++;
+        if (dst_waits[(size_t)d]) {
+            HIPCHK(c0, hipEventCreateWithFlags(&ed.ev[(size_t)d], hipEventDisableTiming));
+            HIPCHK(c0, hipEventRecord(ed.ev[(size_t)d], c->stream));
+        }
+    }
+    // 3. every source's stream waits for its readers: the next pass may overwrite the tile without a finish
+    for (int s = 0; s < n; ++s) {
+        if (!src_read[(size_t)s]) continue;
+        mirt_ctx* c = g->ctxs[(size_t)s];
+        HIPCHK(c0, hipSetDevice(c->device));
+        for (int d = 0; d < n; ++d)
+            if (reads[(size_t)d * n + s]) HIPCHK(c0, hipStreamWaitEvent(c->stream, ed.ev[(size_t)d], 0));
+    }
+    return MIRT_OK;
+} MIRT_CATCH("mirt_exchange_rows", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_fusion(mirt_ctx* ctx, int level) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_set_fusion: unknown context");

@@ -21,21 +21,34 @@
 
 namespace pt {
 
+// Row tiles (mirt_filter_atrous_rows; the row arithmetic is pt_rows_plan.hpp's): the same kernels instantiated for FilterRowsArgs.  The image they
+// see is the WINDOW -- every index, and every edge test, is the window's, which is wrong only in rows nobody needs -- a launch computes the rows of
+// its band alone, and the last one, whose band is the own rows, stores them where the outputs, which hold no other row, have them.  For FilterArgs
+// both functions fold away: the kernels behind mirt_filter_atrous are the kernels they were.
+PT_DEV bool filter_in_band(const FilterArgs&, uint32_t) { return true; }
+PT_DEV bool filter_in_band(const FilterRowsArgs& A, uint32_t p) { return p - A.band_row0 * A.width < A.band_nrows * A.width; }
+// a block of k_filterTiled whose rows, first .. last, all lie outside the band: it stages nothing
+PT_DEV bool filter_rows_outside(const FilterArgs&, int, int) { return false; }
+PT_DEV bool filter_rows_outside(const FilterRowsArgs& A, int first, int last) { return last < (int)A.band_row0 || first >= (int)(A.band_row0 + A.band_nrows); }
+PT_DEV uint32_t filter_out_index(const FilterArgs&, uint32_t p) { return p; }
+PT_DEV uint32_t filter_out_index(const FilterRowsArgs& A, uint32_t p) { return p - A.band_row0 * A.width; }
+
 // out = I_n (times the albedo where the image was demodulated) -> filtered, pixel
-PT_DEV void filter_finish(const FilterArgs& A, uint32_t p, float ox, float oy, float oz, bool live) {
+template <class ARGS>
+PT_DEV void filter_finish(const ARGS& A, uint32_t p, float ox, float oy, float oz, bool live) {
     if (A.demodulate && live) {
         const float r = post_inv_hits(((const float4*)A.normal_hits)[p].w);
         post_modulate(ox, oy, oz, post_albedo(((const float4*)A.albedo_depth)[p], r));
     }
-    post_store(A.filtered, A.pixel, p, ox, oy, oz, ((const float4*)A.radiance)[p].w, A.tone);
+    post_store(A.filtered, A.pixel, filter_out_index(A, p), ox, oy, oz, ((const float4*)A.radiance)[p].w, A.tone);
 }
 
 // I_0 and the prepared guide of every pixel.  LAST (iterations == 0): the outputs, straight from I_0.
-template <bool LAST>
-__global__ void __launch_bounds__(256) k_filterPrepare(const FilterArgs A) {
+template <bool LAST, class ARGS = FilterArgs>
+__global__ void __launch_bounds__(256) k_filterPrepare(const ARGS A) {
     const uint32_t npix = A.width * A.height;
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= npix) return;
+    if (p >= npix || !filter_in_band(A, p)) return;
     const float4 R = ((const float4*)A.radiance)[p];
     const float4 nh = ((const float4*)A.normal_hits)[p];
     const bool live = nh.w > 0.0f;
@@ -85,21 +98,22 @@ PT_DEV float4 filter_pixel(const FilterArgs& A, float inv_colour, const float4 c
     return make_float4(div_cr(sx, sumw), div_cr(sy, sumw), div_cr(sz, sumw), 1.0f);
 }
 
-template <bool LAST>
-PT_DEV void filter_store(const FilterArgs& A, uint32_t dst, uint32_t p, const float4 v) {
+template <bool LAST, class ARGS>
+PT_DEV void filter_store(const ARGS& A, uint32_t dst, uint32_t p, const float4 v) {
     if (LAST) filter_finish(A, p, v.x, v.y, v.z, v.w != 0.0f);
     else ((float4*)A.work[dst])[p] = v;
 }
 
 // (a) direct reads
-template <bool LAST>
-__global__ void __launch_bounds__(256) k_filterDirect(const FilterArgs A, uint32_t src, int step, float inv_colour) {
+template <bool LAST, class ARGS = FilterArgs>
+__global__ void __launch_bounds__(256) k_filterDirect(const ARGS A, uint32_t src, int step, float inv_colour) {
     const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
     const int W = (int)A.width, H = (int)A.height;
     if (x >= W || y >= H) return;
     const float4* const col = (const float4*)A.work[src];
     const float4* const gd = (const float4*)A.guide;
     const uint32_t p = (uint32_t)y * A.width + (uint32_t)x;
+    if (!filter_in_band(A, p)) return;
     float4 v = col[p];
     if (v.w != 0.0f) {
         v = filter_pixel(A, inv_colour, v, gd[p], [&](int dx, int dy, float4& c, float4& g) {
@@ -118,13 +132,14 @@ __global__ void __launch_bounds__(256) k_filterDirect(const FilterArgs A, uint32
 // kTilePitch: float4 between rows of the LDS tile.  The dense tile (20: 12.8 KB); rows 32 float4 apart (20 KB) measured the same at every step
 // (profiles/filter/timing_pitch32.json against timing.json)
 constexpr int kTileIn = 16, kTileHalo = 2, kTileSide = kTileIn + 2 * kTileHalo, kTilePitch = kTileSide;
-template <bool LAST>
-__global__ void __launch_bounds__(256) k_filterTiled(const FilterArgs A, uint32_t src, int step, float inv_colour) {
+template <bool LAST, class ARGS = FilterArgs>
+__global__ void __launch_bounds__(256) k_filterTiled(const ARGS A, uint32_t src, int step, float inv_colour) {
     __shared__ float4 s_col[kTileSide * kTilePitch];
     __shared__ float4 s_gd[kTileSide * kTilePitch];
     const int W = (int)A.width, H = (int)A.height;
     const int cx = (int)blockIdx.x % step, cy = (int)blockIdx.y % step;
     const int lx0 = ((int)blockIdx.x / step) * kTileIn - kTileHalo, ly0 = ((int)blockIdx.y / step) * kTileIn - kTileHalo;   // lattice coordinates of the tile's corner
+    if (filter_rows_outside(A, (ly0 + kTileHalo) * step + cy, (ly0 + kTileHalo + kTileIn - 1) * step + cy)) return;
     const float4* const col = (const float4*)A.work[src];
     const float4* const gd = (const float4*)A.guide;
     for (int i = (int)threadIdx.x; i < kTileSide * kTileSide; i += 256) {
@@ -145,6 +160,7 @@ __global__ void __launch_bounds__(256) k_filterTiled(const FilterArgs A, uint32_
     const int x = (lx0 + tx) * step + cx, y = (ly0 + ty) * step + cy;
     if (x >= W || y >= H) return;
     const uint32_t p = (uint32_t)y * A.width + (uint32_t)x;
+    if (!filter_in_band(A, p)) return;
     const int at = ty * kTilePitch + tx;
     float4 v = s_col[at];
     if (v.w != 0.0f) {
@@ -158,24 +174,35 @@ __global__ void __launch_bounds__(256) k_filterTiled(const FilterArgs A, uint32_
     filter_store<LAST>(A, src ^ 1u, p, v);
 }
 
-void launch_filterPrepare(hipStream_t s, const FilterArgs& a, bool last) {
+template <class ARGS>
+static void launch_prepare(hipStream_t s, const ARGS& a, bool last) {
     const dim3 grid((unsigned)(((uint64_t)a.width * a.height + 255u) / 256u));
-    if (last) hipLaunchKernelGGL(k_filterPrepare<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_filterPrepare<false>, grid, dim3(256), 0, s, a);
+    if (last) hipLaunchKernelGGL((k_filterPrepare<true, ARGS>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_filterPrepare<false, ARGS>), grid, dim3(256), 0, s, a);
 }
 
-void launch_filterStep(hipStream_t s, const FilterArgs& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled) {
+template <class ARGS>
+static void launch_step(hipStream_t s, const ARGS& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled) {
     const int step = 1 << step_log2;
     if (tiled) {
         const uint32_t lw = (a.width + (uint32_t)step - 1u) / (uint32_t)step, lh = (a.height + (uint32_t)step - 1u) / (uint32_t)step;
         const dim3 grid((lw + kTileIn - 1u) / kTileIn * (uint32_t)step, (lh + kTileIn - 1u) / kTileIn * (uint32_t)step);
-        if (last) hipLaunchKernelGGL(k_filterTiled<true>, grid, dim3(256), 0, s, a, src, step, inv_colour);
-        else hipLaunchKernelGGL(k_filterTiled<false>, grid, dim3(256), 0, s, a, src, step, inv_colour);
+        if (last) hipLaunchKernelGGL((k_filterTiled<true, ARGS>), grid, dim3(256), 0, s, a, src, step, inv_colour);
+        else hipLaunchKernelGGL((k_filterTiled<false, ARGS>), grid, dim3(256), 0, s, a, src, step, inv_colour);
     } else {
         const dim3 grid((a.width + 63u) / 64u, (a.height + 3u) / 4u);
-        if (last) hipLaunchKernelGGL(k_filterDirect<true>, grid, dim3(256), 0, s, a, src, step, inv_colour);
-        else hipLaunchKernelGGL(k_filterDirect<false>, grid, dim3(256), 0, s, a, src, step, inv_colour);
+        if (last) hipLaunchKernelGGL((k_filterDirect<true, ARGS>), grid, dim3(256), 0, s, a, src, step, inv_colour);
+        else hipLaunchKernelGGL((k_filterDirect<false, ARGS>), grid, dim3(256), 0, s, a, src, step, inv_colour);
     }
+}
+
+void launch_filterPrepare(hipStream_t s, const FilterArgs& a, bool last) { launch_prepare(s, a, last); }
+void launch_filterStep(hipStream_t s, const FilterArgs& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled) {
+    launch_step(s, a, src, step_log2, inv_colour, last, tiled);
+}
+void launch_filterPrepareRows(hipStream_t s, const FilterRowsArgs& a, bool last) { launch_prepare(s, a, last); }
+void launch_filterStepRows(hipStream_t s, const FilterRowsArgs& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled) {
+    launch_step(s, a, src, step_log2, inv_colour, last, tiled);
 }
 
 }  // namespace pt

@@ -165,6 +165,14 @@ void launch_filterPrepare(hipStream_t s, const FilterArgs& a, bool last);
 // iteration step_log2 (step 2^step_log2) from work[src] into work[src ^ 1], or -- last -- into the outputs.  inv_colour: 1 / (k_i * k_i), IEEE fp32,
 // from the host.  tiled: the decimated LDS tiles, else one thread per pixel reading its taps directly; the bits are the same.
 void launch_filterStep(hipStream_t s, const FilterArgs& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled);
+// The same filter in row tiles (mirt_filter_atrous_rows): the inputs, work[] and guide hold the rows of a WINDOW of the image, `height` of them, and
+// filtered / pixel the own rows alone.  A launch computes the rows [band_row0, band_row0 + band_nrows) of the window (pt_rows_plan.hpp's filter_band);
+// the last launch's band is the own rows, which it stores from the outputs' first element on.
+struct FilterRowsArgs : FilterArgs {
+    uint32_t band_row0, band_nrows;
+};
+void launch_filterPrepareRows(hipStream_t s, const FilterRowsArgs& a, bool last);
+void launch_filterStepRows(hipStream_t s, const FilterRowsArgs& a, uint32_t src, uint32_t step_log2, float inv_colour, bool last, bool tiled);
 // which structure an iteration of step 2^step_log2 runs as unless the caller forces one: bit step_log2 set = tiled.  Measured at 1080p
 // (profiles/filter/timing.json, step_direct_ms against step_tiled_ms): the LDS tiles win at steps 1 and 2, direct reads at 4, 8 and 16.
 constexpr uint32_t kFilterTiledSteps = 0x03u;
@@ -187,6 +195,12 @@ struct UpsampleArgs {
     void* pixel;                 // uchar4 per high pixel, or null
 };
 void launch_upsample(hipStream_t s, const UpsampleArgs& a);
+// The same upsampler on high rows [row0, row0 + nrows) (mirt_upsample_guided_rows): width / height are the whole high image's, the high guides and
+// the outputs hold those rows alone, the three low inputs the low rows from lo_row0 on (the caller has checked that they contain every tap).
+struct UpsampleRowsArgs : UpsampleArgs {
+    uint32_t row0, nrows, lo_row0;
+};
+void launch_upsampleRows(hipStream_t s, const UpsampleRowsArgs& a);
 // {p0,e1,e2,n} records from the host's 3 x float4 position buffer (see pt_kernels_fused.hip); `out` holds count records of 48 B,
 // behind them ceil(count / kTriGroup) float4 {centre, R'^2}: the bounding spheres of groups of consecutive records, and behind those, for
 // count <= kLdsTriMax, the candidate sweep's plane list (GridArgs::pnorm)

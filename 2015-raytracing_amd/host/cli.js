@@ -1,8 +1,8 @@
 #!/usr/bin/env node
 // host/cli.js -- command-line front end of the JavaScript host.
 //   node cli.js pack   <scene.xml> <width> <height> <raysPerPixel>                 -> packed kernel inputs as JSON (stdout)
-//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl]] [--guides PREFIX] [--denoise [iterations]] [--upscale F]
-//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N
+//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl] [--post-in-tiles]] [--guides PREFIX] [--denoise [iterations]] [--upscale F]
+//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N unless --post-in-tiles; --post-in-tiles (with --gpus N): --denoise and --upscale run tile-local -- every device exchanges halo rows with its neighbours and filters / upsamples its own rows (mirt_exchange_rows, mirt_filter_atrous_rows, mirt_upsample_guided_rows), only finished rows are gathered; the same bytes in <out>, <out>.filtered.f32 and <out>.upsampled.f32, and no <out>.radiance.f32 (the unfiltered sums stay on their devices)
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
@@ -46,6 +46,7 @@ if (cmd === "pack") {
   let i;
   if ((i = rest.indexOf("--bounces")) >= 0) opt.bounces = +rest[i + 1];
   if ((i = rest.indexOf("--gpus")) >= 0) { opt.gpus = +rest[i + 1]; opt.forceRccl = rest.includes("--force-rccl"); }   // row tiles over N devices + gather
+  opt.postInTiles = rest.includes("--post-in-tiles") && !!opt.gpus;   // with --gpus N: --denoise and --upscale filter / upsample every tile where it is, after a halo exchange
   if ((i = rest.indexOf("--guides")) >= 0) { if (!rest[i + 1]) usage(); opt.guides = rest[i + 1]; }   // first-hit guide buffers beside the frame (mirt_render_guides)
   if ((i = rest.indexOf("--denoise")) >= 0) {   // the frame filtered on the device (mirt_filter_atrous); implies the guides; with --gpus N: gathered, then filtered on the root
     opt.denoise = {};
@@ -57,14 +58,14 @@ if (cmd === "pack") {
   if ((i = rest.indexOf("--upscale")) >= 0) {   // shade at 1/F resolution, output at full (mirt_upsample_guided); one context: the upsampler has no tiles
     if (!/^\d+$/.test(rest[i + 1] || "")) usage();
     upscale = +rest[i + 1];
-    if (opt.gpus) { process.stderr.write("--upscale is not available with --gpus N: the upsampler, like the filter, wants whole frames on one context, and gathering the low frame and both pairs of guides is not built\n"); process.exit(2); }
+    if (opt.gpus && !opt.postInTiles) { process.stderr.write("--upscale is not available with --gpus N: the upsampler, like the filter, wants whole frames on one context, and gathering the low frame and both pairs of guides is not built\n"); process.exit(2); }
   }
   if (upscale) {
     const res = renderer.renderUpscaled(file, w, h, rpp, passes, upscale, opt);
     const dump = (f, a) => fs.writeFileSync(f, Buffer.from(a.buffer, a.byteOffset, a.byteLength));
     writeFrame(out, res.pixel, w, h);
     dump(out + ".upsampled.f32", res.upsampled);
-    dump(out + ".radiance.f32", res.radiance);
+    if (res.radiance) dump(out + ".radiance.f32", res.radiance);
     if (res.denoised) dump(out + ".filtered.f32", res.denoised.filtered);
     if (opt.guides) {
       dump(`${opt.guides}.normal_hits.f32`, res.guides.normalHits);
@@ -79,7 +80,7 @@ if (cmd === "pack") {
   const res = renderer.renderFile(file, w, h, rpp, passes, opt);
   writeFrame(out, res.denoised ? res.denoised.pixel : res.pixel, w, h);
   if (res.denoised) fs.writeFileSync(out + ".filtered.f32", Buffer.from(res.denoised.filtered.buffer, res.denoised.filtered.byteOffset, res.denoised.filtered.byteLength));
-  fs.writeFileSync(out + ".radiance.f32", Buffer.from(res.radiance.buffer, res.radiance.byteOffset, res.radiance.byteLength));
+  if (res.radiance) fs.writeFileSync(out + ".radiance.f32", Buffer.from(res.radiance.buffer, res.radiance.byteOffset, res.radiance.byteLength));   // (none from --post-in-tiles: the sums are not gathered)
   if (res.guides) {
     for (const [name, a] of [["normal_hits", res.guides.normalHits], ["albedo_depth", res.guides.albedoDepth]])
       fs.writeFileSync(`${opt.guides}.${name}.f32`, Buffer.from(a.buffer, a.byteOffset, a.byteLength));
@@ -93,6 +94,7 @@ if (cmd === "pack") {
     }
   }
   process.stderr.write(`rendered ${file} ${w}x${h} rpp ${rpp}, ${passes} pass(es), ${opt.granular ? (opt.fusion ? "kernel-by-kernel, passes fused by the runtime" : "kernel-by-kernel") : "fused"}: ${res.ms.toFixed(2)} ms on ${res.device}; passes the runtime fused from enqueues: ${res.fusedPasses}\n`);
+  if (res.postInTiles) process.stderr.write("post-process in row tiles: halo rows exchanged, finished rows gathered\n");
   process.stderr.write(`first passes that wrote their guides: ${res.guidedPasses || 0}\n`);   // calls, of one pass or of several, whose own launch wrote the guides (ctx.guidedPasses(): mirt_render_first_pass_guided and mirt_render_passes_guided); the line keeps the wording it had when only first passes counted, for whoever parses it
   if (res.routes) process.stderr.write(`gather routes per tile: ${res.routes.join(" ")}; peer access root<-tile: ${res.peerAccess.join(" ")}\n`);
 } else if (cmd === "pack-frame" || cmd === "frame") {

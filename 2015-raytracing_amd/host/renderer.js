@@ -404,6 +404,8 @@ function renderTiled(packed, nDevices, passes, opt) {
   const devs = [];
   for (let i = 0; i < nDevices; i++) devs.push(all[i % all.length]);
   const group = webcl.createDeviceGroup(devs);
+  if (opt.upscaleTiled) { try { return renderUpscaledTiled(packed, opt.upscaleTiled.hi, group, passes, opt.upscaleTiled.factor, opt); } finally { group.release(); } }
+  if (opt.postInTiles && opt.denoise && !opt.guides) { try { return renderTiledPost(packed, group, passes, opt); } finally { group.release(); } }   // (--guides PREFIX wants the gathered guides: the root route)
   const tiles = [];
   for (let i = 0; i < nDevices; i++) {
     const t = group.tileRows(packed.height, i);
@@ -461,6 +463,120 @@ function renderTiled(packed, nDevices, passes, opt) {
   live.forEach((t) => t.release());
   group.release();
   return res;
+}
+
+// ---- the post-process chain in row tiles (opt.postInTiles): every context filters / upsamples the rows it rendered after a halo exchange
+// (group.exchangeRows, queue.filterFrameRows, queue.upsampleFrameRows; include/mirt.h), and only finished rows are gathered.  The frames are, bit
+// for bit, those of the single-context chain.  Helpers of renderTiled and renderUpscaled; `bufs` collects what the caller releases.
+function tileRenderers(group, packed, opt) {
+  return group.contexts.map((c, i) => {
+    const t = group.tileRows(packed.height, i);
+    return t.nrows ? new FusedRenderer(packed, Object.assign({}, opt, { ctx: c, row0: t.row0, nrows: t.nrows })) : null;
+  });
+}
+// the frame's passes and the tile's guides, queued on every tile's context: the route renderFile takes on one context
+function renderTilesGuided(live, passes, opt) {
+  live.forEach((t) => {
+    if (opt.passesInOneLaunch && t.canRenderPassesGuided()) t.executePassesGuided(passes, opt.bounces);
+    else if (passes === 1 && !opt.passesInOneLaunch && t.canRenderGuided()) t.executeRenderGuided(opt.bounces);
+    else {
+      if (opt.passesInOneLaunch) t.executePasses(passes, opt.bounces);
+      else for (let p = 0; p < passes; p++) t.executeRender(opt.bounces);
+      t.renderGuides();
+    }
+  });
+}
+const ownRows = (tiles) => tiles.map((t) => (t ? { row0: t.row0, nrows: t.nrows } : { row0: 0, nrows: 0 }));
+// one exchange: src[i] holds the rows own[i] of context i; -> per context a buffer with the rows want[i] (null where it wants none)
+function exchangeTiles(group, bufs, src, own, want, rowBytes) {
+  const dst = want.map((w, i) => (w.nrows ? group.contexts[i].createBuffer(webcl.MEM_READ_WRITE, w.nrows * rowBytes) : null));
+  dst.forEach((b) => b && bufs.push(b));
+  group.exchangeRows(src.map((b, i) => (own[i].nrows ? b : null)), own, dst, want, rowBytes);
+  return dst;
+}
+// three exchanges fill every tile's filter window, then the tile is filtered where it is: -> { filtered, pixel }: per context a buffer of its own rows
+function filterTiles(group, bufs, tiles, packed, tone, f, wantPixel) {
+  const iterations = f.iterations === undefined || f.iterations === null ? webcl.FILTER_DEFAULTS.iterations : f.iterations;
+  const own = ownRows(tiles), rowBytes = packed.width * 16;
+  const want = own.map((o) => (o.nrows ? webcl.filterWindowRows(packed.height, o.row0, o.nrows, iterations) : { row0: 0, nrows: 0 }));
+  const win = ["radiance", "normalHits", "albedoDepth"].map((k) => exchangeTiles(group, bufs, tiles.map((t) => t && t[k]), own, want, rowBytes));
+  const mk = (i, bytes) => { const b = group.contexts[i].createBuffer(webcl.MEM_READ_WRITE, bytes || 16); bufs.push(b); return b; };
+  const filtered = tiles.map((t, i) => mk(i, t ? t.npix * 16 : 0)), pixel = wantPixel ? tiles.map((t, i) => mk(i, t ? t.npix * 4 : 0)) : null;
+  tiles.forEach((t, i) => {
+    if (t) t.q.filterFrameRows(Object.assign({}, f, { width: packed.width, height: want[i].nrows, imageHeight: packed.height, winRow0: want[i].row0, row0: t.row0, nrows: t.nrows,
+      tone: tone, radiance: win[0][i], normalHits: win[1][i], albedoDepth: win[2][i], filtered: filtered[i], pixel: pixel ? pixel[i] : undefined }));
+  });
+  return { filtered: filtered, pixel: pixel };
+}
+// gathers per-context buffers (bytes[i] of each) on context 0 and reads them back into `into`
+function gatherTiles(group, bufs, parts, bytes, into, opt) {
+  const root = group.contexts[0], total = bytes.reduce((a, b) => a + b, 0);
+  const out = root.createBuffer(webcl.MEM_READ_WRITE, total || 16);
+  bufs.push(out);
+  group.gather(parts, bytes, out, 0, opt.forceRccl);
+  group.finish();
+  const q = root.createCommandQueue();
+  q.enqueueReadBuffer(out, true, 0, total, into, []);
+  q.finish();
+  return into;
+}
+// renderTiled with opt.denoise and opt.postInTiles: 4 B per pixel (20 with the filtered sums; opt.filtered === false leaves them) into the root
+// instead of pixel, radiance and both guides
+function renderTiledPost(packed, group, passes, opt) {
+  const tiles = tileRenderers(group, packed, opt), live = tiles.filter((t) => t), bufs = [];
+  try {
+    const q0 = live[0].q, npix = packed.width * packed.height;
+    q0.timerStart();
+    renderTilesGuided(live, passes, opt);
+    const out = filterTiles(group, bufs, tiles, packed, 1 / (packed.rays_per_pixel * passes), opt.denoise, true);
+    group.finish();
+    const ms = q0.timerStopMs();
+    const denoised = { pixel: gatherTiles(group, bufs, out.pixel, tiles.map((t) => (t ? t.npix * 4 : 0)), new Uint8ClampedArray(npix * 4), opt) };
+    if (opt.filtered !== false) denoised.filtered = gatherTiles(group, bufs, out.filtered, tiles.map((t) => (t ? t.npix * 16 : 0)), new Float32Array(npix * 4), opt);
+    return { pixel: denoised.pixel, denoised: denoised, ms: ms, device: live.length + " x " + live[0].device.getInfo(webcl.DEVICE_NAME),
+             tiles: tiles.map((t) => (t ? [t.row0, t.nrows] : [0, 0])), routes: group.routes(), peerAccess: tiles.map((_, i) => group.peerAccess(0, i)), postInTiles: true };
+  } finally {
+    bufs.forEach((b) => b.release());
+    live.forEach((t) => t.release());
+  }
+}
+// renderUpscaled with opt.gpus and opt.postInTiles: the LOW frame in row tiles, filtered there with opt.denoise; one exchange moves the (filtered) low
+// radiance and the two low guides into every context's low window; every context renders the guides of its OUTPUT tile and rebuilds it
+function renderUpscaledTiled(lo, hi, group, passes, factor, opt) {
+  const tiles = tileRenderers(group, lo, opt), live = tiles.filter((t) => t), bufs = [];
+  try {
+    const q0 = live[0].q, npix = hi.width * hi.height, tone = 1 / (lo.rays_per_pixel * passes);
+    q0.timerStart();
+    renderTilesGuided(live, passes, opt);
+    const radiance = opt.denoise ? filterTiles(group, bufs, tiles, lo, tone, opt.denoise, false).filtered : tiles.map((t) => t && t.radiance);
+    const own = ownRows(tiles), high = group.contexts.map((_, i) => group.tileRows(hi.height, i));
+    const want = high.map((h) => (h.nrows ? webcl.upsampleLowRows(hi.height, factor, h.row0, h.nrows) : { row0: 0, nrows: 0 }));
+    const low = [radiance, tiles.map((t) => t && t.normalHits), tiles.map((t) => t && t.albedoDepth)].map((src) => exchangeTiles(group, bufs, src, own, want, lo.width * 16));
+    const mk = (i, bytes) => { const b = group.contexts[i].createBuffer(webcl.MEM_READ_WRITE, bytes || 16); bufs.push(b); return b; };
+    const up = high.map((h, i) => mk(i, h.nrows * hi.width * 16)), px = high.map((h, i) => mk(i, h.nrows * hi.width * 4));
+    let scenes = [];   // a context whose low tile is empty still rebuilds its output rows: it needs the scene for their guides
+    high.forEach((h, i) => {
+      if (!h.nrows) return;
+      let t = tiles[i];
+      if (!t) { t = new FusedRenderer(lo, Object.assign({}, opt, { ctx: group.contexts[i], row0: 0, nrows: 1 })); scenes.push(t); }
+      const nh = mk(i, h.nrows * hi.width * 16), ad = mk(i, h.nrows * hi.width * 16);
+      t.q.renderGuides(Object.assign(t.passDesc(), { width: hi.width, height: hi.height, row0: h.row0, nrows: h.nrows, cam: hi.cam }), nh, ad);
+      t.q.upsampleFrameRows(Object.assign({}, opt.upsample, { width: hi.width, height: hi.height, factor: factor, tone: tone, row0: h.row0, nrows: h.nrows,
+        loRow0: want[i].row0, loNrows: want[i].nrows, radianceLo: low[0][i], normalHitsLo: low[1][i], albedoDepthLo: low[2][i], normalHits: nh, albedoDepth: ad,
+        upsampled: up[i], pixel: px[i] }));
+    });
+    group.finish();
+    const ms = q0.timerStopMs();
+    const res = { pixel: gatherTiles(group, bufs, px, high.map((h) => h.nrows * hi.width * 4), new Uint8ClampedArray(npix * 4), opt),
+                  upsampled: gatherTiles(group, bufs, up, high.map((h) => h.nrows * hi.width * 16), new Float32Array(npix * 4), opt), ms: ms,
+                  device: live.length + " x " + live[0].device.getInfo(webcl.DEVICE_NAME), fusedPasses: 0, guidedPasses: live.reduce((a, t) => a + (t.ctx.guidedPasses ? t.ctx.guidedPasses() : 0), 0),
+                  lowWidth: lo.width, lowHeight: lo.height, postInTiles: true };
+    scenes.forEach((t) => t.release());
+    return res;
+  } finally {
+    bufs.forEach((b) => b.release());
+    live.forEach((t) => t.release());
+  }
 }
 
 // per-pixel sequential fp32 sums of the per-ray accumulators (copyToPixel's order, A10 code.cl:1377-1380)
@@ -526,13 +642,15 @@ function renderFile(file, width, height, rpp, passes, opt) {
 // and whole frames: the upsampler, like the filter, has no tiles.
 function renderUpscaled(file, width, height, rpp, passes, factor, opt) {
   opt = opt || {};
-  if (opt.gpus) throw new Error("--upscale is not available with --gpus N: the upsampler, like the filter, wants whole frames on one context, and gathering the low frame and both pairs of guides is not built");
+  if (opt.gpus && !opt.postInTiles) throw new Error("--upscale is not available with --gpus N: the upsampler, like the filter, wants whole frames on one context, and gathering the low frame and both pairs of guides is not built");
+  if (opt.gpus && opt.guides) throw new Error("--upscale with --gpus N --post-in-tiles gathers the finished rows only: not with --guides");
   if (opt.granular || opt.everyPass || opt.deviceGrid) throw new Error("--upscale drives the fused host on host-built grids: not with --granular, --every-pass or --device-grid");
   if (!(factor >= 2 && factor <= 4) || factor !== Math.floor(factor)) throw new Error(`--upscale ${factor}: the factor is 2, 3 or 4`);
   if (width % factor || height % factor) throw new Error(`--upscale ${factor}: ${width}x${height} is not a multiple of the factor (the two images would not show the same frustum)`);
   const wl = width / factor, hl = height / factor;
   const lo = scene.packScene(scene.loadSceneFile(file, wl, hl), wl, hl, rpp);
   const hi = scene.packScene(scene.loadSceneFile(file, width, height), width, height, rpp);
+  if (opt.gpus) return renderTiled(lo, opt.gpus, passes, Object.assign({}, opt, { upscaleTiled: { hi: hi, factor: factor } }));   // the post chain in row tiles
   const R = new FusedRenderer(lo, opt);
   const npix = width * height;
   const mk = (bytes) => R.ctx.createBuffer(webcl.MEM_READ_WRITE, bytes);

@@ -204,21 +204,37 @@ class WebCLCommandQueue {
   // normalPowerLog2, sigmaDepth, sigmaColour, demodulate (webcl.FILTER_DEFAULTS where left out) and structure ("direct" | "tiled": one kernel
   // structure for every step, for measurement).  radiance as a pass writes it, the guides as renderGuides writes them; filtered: float4 per pixel,
   // un-scaled like radiance; pixel: RGBA8.  Either output may be left out, not both.  The frame is filtered whole: gather row tiles first.
-  filterFrame(desc) {
+  filterFrame(desc) { wrap(() => native().filterAtrous(this.ctx.h, this._filterDesc(desc))); }
+  // the same filter on rows [row0, row0 + nrows) of a width x imageHeight image (mirt_filter_atrous_rows): desc as filterFrame's, read differently --
+  // height: the rows the three inputs hold, image rows from winRow0 on, a window that contains webcl.filterWindowRows(imageHeight, row0, nrows,
+  // iterations); filtered / pixel hold the nrows own rows alone -- plus {imageHeight, winRow0, row0, nrows}.  The bits are the whole frame's.
+  filterFrameRows(desc) {
+    const d = Object.assign(this._filterDesc(desc), { imageHeight: desc.imageHeight, winRow0: desc.winRow0, row0: desc.row0, nrows: desc.nrows });
+    wrap(() => native().filterAtrousRows(this.ctx.h, d));
+  }
+  _filterDesc(desc) {
     const v = Object.assign({}, FILTER_DEFAULTS);
     for (const k of Object.keys(FILTER_DEFAULTS)) if (desc[k] !== undefined && desc[k] !== null) v[k] = desc[k];
     const h = (b) => (b ? b.h : undefined);
     const d = { width: desc.width, height: desc.height, iterations: v.iterations, normalPowerLog2: v.normalPowerLog2, sigmaDepth: v.sigmaDepth,
                 sigmaColour: v.sigmaColour, tone: Math.fround(desc.tone), flags: (v.demodulate ? 1 : 0) | ({ direct: 2, tiled: 4 }[desc.structure] || 0),
                 radiance: h(desc.radiance), normalHits: h(desc.normalHits), albedoDepth: h(desc.albedoDepth), filtered: h(desc.filtered), pixel: h(desc.pixel) };
-    wrap(() => native().filterAtrous(this.ctx.h, d));
+    return d;
   }
   // ---- extension: guide-driven upsampling of a frame shaded at 1/factor resolution (mirt_upsample_guided; include/mirt.h has the definition).
   // desc: {width, height (the OUTPUT size, multiples of factor), factor: 2..4, tone: the low frame's 1 / (raysPerPixel * passes), radianceLo (a pass's
   // radiance or filterFrame's filtered), normalHitsLo, albedoDepthLo (renderGuides at the low size), normalHits, albedoDepth (renderGuides at the
   // output size), upsampled?, pixel?} plus any of normalPowerLog2, sigmaDepth, demodulate (webcl.UPSAMPLE_DEFAULTS where left out).  upsampled:
   // float4 per output pixel, un-scaled like radiance; pixel: RGBA8.  Either output may be left out, not both.  Whole frames: gather row tiles first.
-  upsampleFrame(desc) {
+  upsampleFrame(desc) { wrap(() => native().upsampleGuided(this.ctx.h, this._upsampleDesc(desc))); }
+  // the same upsampler on output rows [row0, row0 + nrows) (mirt_upsample_guided_rows): desc as upsampleFrame's -- width, height: the whole output
+  // image -- with normalHits, albedoDepth, upsampled and pixel holding those rows alone and the three low inputs the low rows [loRow0, loRow0 +
+  // loNrows), a range that contains webcl.upsampleLowRows(height, factor, row0, nrows); plus {row0, nrows, loRow0, loNrows}.
+  upsampleFrameRows(desc) {
+    const d = Object.assign(this._upsampleDesc(desc), { row0: desc.row0, nrows: desc.nrows, loRow0: desc.loRow0, loNrows: desc.loNrows });
+    wrap(() => native().upsampleGuidedRows(this.ctx.h, d));
+  }
+  _upsampleDesc(desc) {
     const v = Object.assign({}, UPSAMPLE_DEFAULTS);
     for (const k of Object.keys(UPSAMPLE_DEFAULTS)) if (desc[k] !== undefined && desc[k] !== null) v[k] = desc[k];
     const h = (b) => (b ? b.h : undefined);
@@ -226,7 +242,7 @@ class WebCLCommandQueue {
                 tone: Math.fround(desc.tone), flags: v.demodulate ? 1 : 0, radianceLo: h(desc.radianceLo), normalHitsLo: h(desc.normalHitsLo),
                 albedoDepthLo: h(desc.albedoDepthLo), normalHits: h(desc.normalHits), albedoDepth: h(desc.albedoDepth), upsampled: h(desc.upsampled),
                 pixel: h(desc.pixel) };
-    wrap(() => native().upsampleGuided(this.ctx.h, d));
+    return d;
   }
   // ---- extension: a whole Assign04 / Assign07 frame in one launch (mirt_render_frame): initTrace and the trace kernel(s) on one thread per pixel,
   // no ray buffer unless desc.rays is given.  desc: {assign, width, height, cam, bounds, nSlabs, pixel, rays?} plus the mesh {tSize, tPos, tNormal,
@@ -385,6 +401,13 @@ class WebCLDeviceGroup {
   gather(tiles, tileBytes, out, root, transport) {
     wrap(() => native().gather(this.h, tiles.map((b) => b.h), tileBytes, out.h, root || 0, transport === true ? 1 : (transport | 0)));
   }
+  // the halo exchange (mirt_exchange_rows): src[i] (a buffer of contexts[i], or null) holds the image rows srcRows[i] = {row0, nrows} from its first
+  // byte on; dst[i] (a buffer of contexts[i], or null) ends holding the image rows dstRows[i], each copied from whichever context owns it.  Ordered
+  // after the work queued on the sources; complete after finish() of the destination's queue.
+  exchangeRows(src, srcRows, dst, dstRows, rowBytes) {
+    const hs = (a) => a.map((b) => (b ? b.h : null));
+    wrap(() => native().exchangeRows(this.h, hs(src), srcRows, hs(dst), dstRows, rowBytes));
+  }
   // 1 when contexts[i]'s device reads contexts[j]'s memory directly (peer access enabled at creation), 0 when copies between them are staged
   peerAccess(i, j) { return wrap(() => native().groupPeerAccess(this.h, i, j)); }
   // how the last gather() moved each tile: "none" | "rccl" | "peer" | "staged" | "local" (mirt.h MIRT_ROUTE_*)
@@ -403,6 +426,10 @@ const webcl = Object.assign({
   createDeviceGroup(devices) { return new WebCLDeviceGroup(devices); },
   FILTER_DEFAULTS,
   UPSAMPLE_DEFAULTS,
+  // {row0, nrows}: the input rows that rows [row0, row0 + nrows) of the filtered image depend on, and the low rows that output rows [row0, row0 +
+  // nrows) of the upsampler read (mirt_filter_window_rows, mirt_upsample_low_rows); {0, 0} on bad input
+  filterWindowRows(imageHeight, row0, nrows, iterations) { return native().filterWindowRows(imageHeight, row0, nrows, iterations); },
+  upsampleLowRows(height, factor, row0, nrows) { return native().upsampleLowRows(height, factor, row0, nrows); },
 }, C);
 
 // `window.WebCL` is only tested for existence by the reference (A10 code.js:468); `webcl` is the entry object.

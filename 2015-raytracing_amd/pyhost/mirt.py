@@ -165,6 +165,12 @@ SYMBOLS = {
     "mirt_gather": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "mirt_group_peer_access": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mirt_gather_route": (C.c_int, [C.c_void_p, C.c_int]),
+    "mirt_filter_window_rows": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "mirt_upsample_low_rows": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "mirt_filter_atrous_rows": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "mirt_upsample_guided_rows": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "mirt_exchange_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int, C.c_size_t]),
 }
 
 
@@ -187,6 +193,22 @@ def lib():
 
 def device_count():
     return lib().mirt_device_count()
+
+
+def filter_window_rows(image_height, row0, nrows, iterations):
+    """-> (win_row0, win_nrows): the input rows that rows [row0, row0 + nrows) of the filtered image depend on (mirt_filter_window_rows);
+    (0, 0) on bad input"""
+    a, b = C.c_uint32(), C.c_uint32()
+    lib().mirt_filter_window_rows(int(image_height), int(row0), int(nrows), int(iterations), C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def upsample_low_rows(height, factor, row0, nrows):
+    """-> (lo_row0, lo_nrows): the low rows that high rows [row0, row0 + nrows) of a `height`-row image read (mirt_upsample_low_rows); (0, 0) on
+    bad input"""
+    a, b = C.c_uint32(), C.c_uint32()
+    lib().mirt_upsample_low_rows(int(height), int(factor), int(row0), int(nrows), C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 class Buffer:
@@ -518,6 +540,21 @@ class Context:
         pass writes it, the guides as render_guides writes them, tone = 1 / (rays_per_pixel * passes).  Writes `filtered` (float4 per pixel,
         un-scaled like radiance) and / or `pixel` (RGBA8).  Parameters left None are FILTER_DEFAULTS; structure: None (the measured choice per
         step), "direct" or "tiled"."""
+        d = self._filter_desc(width, height, tone, radiance, normal_hits, albedo_depth, filtered, pixel, iterations, normal_power_log2, sigma_depth,
+                              sigma_colour, demodulate, structure)
+        self._chk(lib().mirt_filter_atrous(self.h, C.byref(d)))
+
+    def filter_atrous_rows(self, width, image_height, win_row0, win_nrows, row0, nrows, tone, radiance, normal_hits, albedo_depth, filtered=None,
+                           pixel=None, **params):
+        """filter_atrous on rows [row0, row0 + nrows) of a width x image_height image (mirt_filter_atrous_rows): the three inputs hold the image
+        rows [win_row0, win_row0 + win_nrows), a window that contains filter_window_rows(image_height, row0, nrows, iterations); `filtered` /
+        `pixel` hold the nrows own rows alone and end as those rows of the whole-frame call, bit for bit.  params as filter_atrous."""
+        d = self._filter_desc(width, win_nrows, tone, radiance, normal_hits, albedo_depth, filtered, pixel, **params)
+        self._chk(lib().mirt_filter_atrous_rows(self.h, C.byref(d), int(image_height), int(win_row0), int(row0), int(nrows)))
+
+    @staticmethod
+    def _filter_desc(width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,
+                     normal_power_log2=None, sigma_depth=None, sigma_colour=None, demodulate=None, structure=None):
         v = dict(FILTER_DEFAULTS)
         for k, x in (("iterations", iterations), ("normal_power_log2", normal_power_log2), ("sigma_depth", sigma_depth), ("sigma_colour", sigma_colour),
                      ("demodulate", demodulate)):
@@ -530,7 +567,7 @@ class Context:
         d.tone, d.sigma_depth, d.sigma_colour = float(tone), float(v["sigma_depth"]), float(v["sigma_colour"])
         d.radiance, d.normal_hits, d.albedo_depth = (b.h if b else None for b in (radiance, normal_hits, albedo_depth))
         d.filtered, d.pixel = (filtered.h if filtered else None), (pixel.h if pixel else None)
-        self._chk(lib().mirt_filter_atrous(self.h, C.byref(d)))
+        return d
 
     def upsample_guided(self, width, height, factor, tone, radiance_lo, normal_hits_lo, albedo_depth_lo, normal_hits, albedo_depth,
                         upsampled=None, pixel=None, normal_power_log2=None, sigma_depth=None, demodulate=None):
@@ -538,6 +575,21 @@ class Context:
         (height / factor) frame -- as a pass or filter_atrous wrote it, tone = that frame's 1 / (rays_per_pixel * passes) -- rebuilt at
         width x height from the guides of both resolutions (render_guides at each size).  Writes `upsampled` (float4 per high pixel, un-scaled
         like radiance) and / or `pixel` (RGBA8).  Parameters left None are UPSAMPLE_DEFAULTS."""
+        d = self._upsample_desc(width, height, factor, tone, radiance_lo, normal_hits_lo, albedo_depth_lo, normal_hits, albedo_depth, upsampled, pixel,
+                                normal_power_log2, sigma_depth, demodulate)
+        self._chk(lib().mirt_upsample_guided(self.h, C.byref(d)))
+
+    def upsample_guided_rows(self, width, height, factor, row0, nrows, lo_row0, lo_nrows, tone, radiance_lo, normal_hits_lo, albedo_depth_lo,
+                             normal_hits, albedo_depth, upsampled=None, pixel=None, **params):
+        """upsample_guided on high rows [row0, row0 + nrows) of the width x height image (mirt_upsample_guided_rows): the high guides and the outputs
+        hold those rows alone, the three low inputs the low rows [lo_row0, lo_row0 + lo_nrows), a range that contains upsample_low_rows(height,
+        factor, row0, nrows).  The outputs end as those rows of the whole-frame call, bit for bit.  params as upsample_guided."""
+        d = self._upsample_desc(width, height, factor, tone, radiance_lo, normal_hits_lo, albedo_depth_lo, normal_hits, albedo_depth, upsampled, pixel, **params)
+        self._chk(lib().mirt_upsample_guided_rows(self.h, C.byref(d), int(row0), int(nrows), int(lo_row0), int(lo_nrows)))
+
+    @staticmethod
+    def _upsample_desc(width, height, factor, tone, radiance_lo, normal_hits_lo, albedo_depth_lo, normal_hits, albedo_depth,
+                       upsampled=None, pixel=None, normal_power_log2=None, sigma_depth=None, demodulate=None):
         v = dict(UPSAMPLE_DEFAULTS)
         for k, x in (("normal_power_log2", normal_power_log2), ("sigma_depth", sigma_depth), ("demodulate", demodulate)):
             if x is not None:
@@ -550,7 +602,7 @@ class Context:
         d.radiance_lo, d.normal_hits_lo, d.albedo_depth_lo = (b.h if b else None for b in (radiance_lo, normal_hits_lo, albedo_depth_lo))
         d.normal_hits, d.albedo_depth = (b.h if b else None for b in (normal_hits, albedo_depth))
         d.upsampled, d.pixel = (upsampled.h if upsampled else None), (pixel.h if pixel else None)
-        self._chk(lib().mirt_upsample_guided(self.h, C.byref(d)))
+        return d
 
     def destroy(self):
         if self.h:
@@ -661,6 +713,19 @@ class DeviceGroup:
         if transport is None:
             transport = self.GATHER_RCCL if use_rccl else self.GATHER_AUTO
         rc = lib().mirt_gather(self.h, hs, bs, n, out.h, root, transport)
+        if rc != 0:
+            raise MirtError(rc, lib().mirt_last_error(self.contexts[0].h).decode())
+
+    def exchange_rows(self, src, src_rows, dst, dst_rows, row_bytes):
+        """The halo exchange (mirt_exchange_rows).  Per context i: src[i] (a Buffer or None) holds, from its first byte on, the image rows
+        src_rows[i] = (row0, nrows) that the context owns; dst[i] (a Buffer or None) ends holding the image rows dst_rows[i] = (row0, nrows),
+        each copied from whichever context owns it.  Rows are row_bytes bytes.  Ordered after the work queued on the sources; a source may be
+        overwritten right after the call; complete after finish() of the destination's context."""
+        n = len(src)
+        hs = (C.c_void_p * n)(*[b.h if b else None for b in src])
+        hd = (C.c_void_p * max(1, len(dst)))(*[b.h if b else None for b in dst])
+        u = lambda rows, k: (C.c_uint32 * max(1, len(rows)))(*[int(r[k]) for r in rows])
+        rc = lib().mirt_exchange_rows(self.h, hs, u(src_rows, 0), u(src_rows, 1), hd, u(dst_rows, 0), u(dst_rows, 1), n, int(row_bytes))
         if rc != 0:
             raise MirtError(rc, lib().mirt_last_error(self.contexts[0].h).decode())
 

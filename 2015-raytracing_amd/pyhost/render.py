@@ -456,6 +456,147 @@ class UpscaledRenderer:
         self.lo.release()
 
 
+def _tile_passes_guided(fr, passes, bounces):
+    """The first `passes` passes of a tile renderer's frame with the tile's guides (fr.normal_hits / fr.albedo_depth), all queued on the tile's
+    context and nothing read back: mirt_render_first_pass_guided for one pass, mirt_render_passes_guided for several."""
+    passes = int(passes)
+    if not fr.nrays:
+        fr.passes += passes
+        return
+    fr.normal_hits, fr.albedo_depth = fr._frames("normal_hits", fr.npix * 16), fr._frames("albedo_depth", fr.npix * 16)
+    desc = lambda: fr.dev.pass_desc(fr.seeds, fr.acu, fr.pixel, fr.radiance, pass_index=fr.passes, bounces=bounces, row0=fr.row0, nrows=fr.nrows)
+    if passes == 1:
+        fr.ctx.render_first_pass_guided(desc(), fr.normal_hits, fr.albedo_depth)
+        fr.passes += 1
+        return
+    left, guides = passes, dict(normal_hits=fr.normal_hits, albedo_depth=fr.albedo_depth)
+    while left:   # a call runs at most mirt.MAX_PASSES_PER_CALL passes; the first call writes the guides, the same for every pass of a frame
+        k = min(left, mirt.MAX_PASSES_PER_CALL)
+        if guides:
+            fr.ctx.render_passes_guided(desc(), k, fresh=True, **guides)
+        else:
+            fr.ctx.render_passes(desc(), k)
+        fr.passes += k
+        left -= k
+        guides = None
+
+
+class TiledPostRenderer:
+    """The post-process chain in row tiles over the contexts of a mirt.DeviceGroup: every context renders its rows, exchanges halo rows with its
+    neighbours (mirt_exchange_rows) and filters / upsamples where it is (mirt_filter_atrous_rows, mirt_upsample_guided_rows); only the finished
+    rows are gathered.  The frames are, bit for bit, those of FusedRenderer.denoised_first_pass / denoised_passes and UpscaledRenderer.render on
+    one context.  `scene` (a pyhost.scene.PackedScene) names the output size; seeds as FusedRenderer takes them (the array of the frame that is
+    traced -- the LOW frame for upscaled -- or a seed_base for mirt_seed_fill at each tile's first global ray)."""
+
+    def __init__(self, group, scene, seeds=None, seed_base=0, root=0):
+        self.g, self.s, self.seeds, self.seed_base, self.root = group, scene, seeds, seed_base, root
+        self.n = len(group.contexts)
+
+    def _tiles(self, scene):
+        return [FusedRenderer(c, scene, seeds=self.seeds, seed_base=self.seed_base, row0=r0, nrows=nr)
+                for c, (r0, nr) in zip(self.g.contexts, (self.g.tile_rows(scene.height, i) for i in range(self.n)))]
+
+    def _exchange(self, bufs, src, own, want, row_bytes):
+        """one exchange per source buffer list in src: -> per list, the window buffers (None where a context wants nothing)"""
+        out = []
+        for tiles in src:
+            dst = [c.buffer(nr * row_bytes) if nr else None for c, (_, nr) in zip(self.g.contexts, want)]
+            bufs += [b for b in dst if b]
+            self.g.exchange_rows([t if nr else None for t, (_, nr) in zip(tiles, own)], own, dst, want, row_bytes)
+            out.append(dst)
+        return out
+
+    def _filter(self, bufs, trs, tone, want_pixel, params):
+        """the tiles' frames filtered in place: -> (pixel tiles or None, filtered tiles), 16-byte stand-ins where a tile is empty"""
+        s = trs[0].s
+        iterations = mirt.FILTER_DEFAULTS["iterations"] if params.get("iterations") is None else params["iterations"]
+        own = [(t.row0, t.nrows) for t in trs]
+        want = [mirt.filter_window_rows(s.height, r0, nr, iterations) if nr else (0, 0) for r0, nr in own]
+        rad, nh, ad = self._exchange(bufs, ([t.radiance for t in trs], [getattr(t, "normal_hits", None) for t in trs], [getattr(t, "albedo_depth", None) for t in trs]),
+                                     own, want, s.width * 16)
+        pix = [t.ctx.buffer(t.npix * 4 or 16) for t in trs] if want_pixel else None
+        out = [t.ctx.buffer(t.npix * 16 or 16) for t in trs]
+        bufs += out + (pix or [])
+        for i, t in enumerate(trs):
+            if t.nrows:
+                t.ctx.filter_atrous_rows(s.width, s.height, want[i][0], want[i][1], t.row0, t.nrows, tone, rad[i], nh[i], ad[i], filtered=out[i],
+                                         pixel=pix[i] if pix else None, **params)
+        return pix, out
+
+    def _gather(self, bufs, tiles, nbytes, dtype):
+        ctx = self.g.contexts[self.root]
+        out = ctx.buffer(sum(nbytes) or 16)
+        bufs.append(out)
+        self.g.gather(tiles, nbytes, out, root=self.root)
+        ctx.finish()
+        return out.read(dtype, count=sum(nbytes) // np.dtype(dtype).itemsize).reshape(-1, 4)
+
+    def denoised(self, passes=1, bounces=5, want_filtered=True, **params):
+        """-> (pixel [W * H, 4] uint8, filtered [W * H, 4] float32 or None): the a-trous-filtered frame after `passes` passes, params as
+        Context.filter_atrous.  Into the root go 4 B per pixel (20 with want_filtered), not radiance and both guides."""
+        trs, bufs = self._tiles(self.s), []
+        try:
+            for t in trs:
+                _tile_passes_guided(t, passes, bounces)
+            tone = np.float32(1.0 / (self.s.rpp * int(passes)))
+            pix, out = self._filter(bufs, trs, tone, True, params)
+            pixel = self._gather(bufs, pix, [t.npix * 4 for t in trs], np.uint8)
+            filtered = self._gather(bufs, out, [t.npix * 16 for t in trs], np.float32) if want_filtered else None
+            return pixel, filtered
+        finally:
+            self.g.finish()
+            for b in bufs:
+                b.release()
+            for t in trs:
+                t.release()
+
+    def upscaled(self, factor, passes=1, bounces=5, denoise=True, filter_params=None, want_upsampled=True, **params):
+        """-> (pixel [W * H, 4] uint8, upsampled [W * H, 4] float32 or None): the frame traced at (W / factor) x (H / factor) in row tiles of the LOW
+        image, optionally filtered there, and rebuilt in row tiles of the output; arguments as UpscaledRenderer.render."""
+        s, f = self.s, int(factor)
+        if f < 2 or f > 4 or s.width % f or s.height % f:
+            raise mirt.MirtError(-1, f"TiledPostRenderer: {s.width}x{s.height} is not a multiple of a factor {factor} in 2 .. 4")
+        wl, hl = s.width // f, s.height // f
+        trs, bufs = self._tiles(s.resized(wl, hl, s.rpp)), []
+        try:
+            for t in trs:
+                _tile_passes_guided(t, passes, bounces)
+            tone = np.float32(1.0 / (s.rpp * int(passes)))
+            radiance = [t.radiance for t in trs]
+            if denoise:
+                radiance = self._filter(bufs, trs, tone, False, filter_params or {})[1]
+            own = [(t.row0, t.nrows) for t in trs]
+            high = [self.g.tile_rows(s.height, i) for i in range(self.n)]
+            want = [mirt.upsample_low_rows(s.height, f, r0, nr) if nr else (0, 0) for r0, nr in high]
+            rad, nhl, adl = self._exchange(bufs, (radiance, [getattr(t, "normal_hits", None) for t in trs], [getattr(t, "albedo_depth", None) for t in trs]),
+                                           own, want, wl * 16)
+            pix, ups = [], []
+            for i, (t, (r0, nr)) in enumerate(zip(trs, high)):
+                c = t.ctx
+                pix.append(c.buffer(nr * s.width * 4 or 16))
+                ups.append(c.buffer(nr * s.width * 16 or 16))
+                if not nr:
+                    continue
+                nh, ad = c.buffer(nr * s.width * 16), c.buffer(nr * s.width * 16)
+                bufs += [nh, ad]
+                d = t.dev.pass_desc(None, None, row0=r0, nrows=nr)   # the tile's scene seen through the camera pack of the output size
+                d.width, d.height = s.width, s.height
+                d.cam = mirt._f(s.cam, 16)
+                c.render_guides(d, nh, ad)
+                c.upsample_guided_rows(s.width, s.height, f, r0, nr, want[i][0], want[i][1], tone, rad[i], nhl[i], adl[i], nh, ad,
+                                       upsampled=ups[i], pixel=pix[i], **params)
+            bufs += pix + ups
+            pixel = self._gather(bufs, pix, [nr * s.width * 4 for _, nr in high], np.uint8)
+            upsampled = self._gather(bufs, ups, [nr * s.width * 16 for _, nr in high], np.float32) if want_upsampled else None
+            return pixel, upsampled
+        finally:
+            self.g.finish()
+            for b in bufs:
+                b.release()
+            for t in trs:
+                t.release()
+
+
 class FramePacked:
     """Packed inputs of an Assign01 / 04 / 07 frame job (what `node host/cli.js pack-frame` emits)."""
 

@@ -320,8 +320,9 @@ MIRT_API int mirt_render_passes_guided(mirt_ctx* ctx, const mirt_pass_desc* desc
  * with the colour term on, a NaN or infinite pixel stays where it is and does not spread (its c is not a number below 1, so it is nobody's tap and has none);
  * background pixels come out as they went in.  libmirt.so and libmirt_default.so give the same bits: the reference has no filter, there is one
  * contract (csrc/pt_kernels_filter.hip says how the quotients are formed).
- * The filter has NO TILES and no halo exchange: rows near a tile border need the neighbour's rows, so filtering row tiles separately gives a
- * different picture within 2 * (2^iterations - 1) rows of a border.  With N devices, gather radiance and both guides to one context and filter there.
+ * This call has NO TILES: rows near a tile border need the neighbour's rows, so filtering row tiles separately gives a different picture within
+ * 2 * (2^iterations - 1) rows of a border.  With N devices, either gather radiance and both guides to one context and filter there, or exchange
+ * the halo rows and filter every tile where it is (mirt_exchange_rows, mirt_filter_atrous_rows, below): the same bits.
  * Checks, nothing is written when one fails.  MIRT_E_ARG: struct_size, width or height 0 or above 65535, iterations > MIRT_FILTER_MAX_ITERATIONS,
  * normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2, tone not finite or <= 0, unknown flags or both structure flags, both outputs NULL, an
  * output that is (or overlaps) an input or the other output, a call while capturing.  MIRT_E_RANGE: a buffer smaller than width * height elements.
@@ -388,8 +389,8 @@ MIRT_API int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* desc);
  * infinite low pixel is NOT contained the way the filter contains one: it reaches every high pixel that counts it as a tap (up to (2f)^2 of them),
  * with the depth term on or off; only `w > 0` keeps a NaN WEIGHT out.  libmirt.so and libmirt_default.so give the same bits: the reference has
  * no upsampler, there is one contract (csrc/pt_kernels_upsample.hip).
- * NOT built: row tiles (like the filter, the call wants whole frames: with N devices gather all five inputs to one context first), a footprint
- * wider than 2 x 2 taps, a colour term, an LDS-tiled structure, sizes that factor does not divide.
+ * This call wants whole frames; row tiles are mirt_upsample_guided_rows (below).  NOT built: a footprint wider than 2 x 2 taps, a colour term, an
+ * LDS-tiled structure, sizes that factor does not divide.
  * Checks, nothing is written when one fails.  MIRT_E_ARG: struct_size, width or height 0 or above 65535, factor outside 2 .. 4, a size that is not
  * a multiple of factor, normal_power_log2 > MIRT_FILTER_MAX_NORMAL_POWER_LOG2, tone not finite or <= 0, unknown flags, both outputs NULL, an
  * output that is (or overlaps) an input or the other output, a call while capturing.  MIRT_E_RANGE: a buffer smaller than its image.
@@ -644,6 +645,62 @@ enum { MIRT_ROUTE_NONE = 0,   /* no gather yet, or an empty tile                
        MIRT_ROUTE_LOCAL = 4 };/* the tile already lives on the root's device: a device-local copy      */
 MIRT_API int mirt_group_peer_access(const mirt_group* g, int i, int j);
 MIRT_API int mirt_gather_route(const mirt_group* g, int tile);
+
+/* ---- the post-process stage in ROW TILES: every context filters and upsamples the rows it rendered, after a halo exchange -------------------
+ * Neither mirt_filter_atrous nor mirt_upsample_guided depends on a pixel's absolute row, except at the image's top and bottom edge.
+ *   Filter: iteration i reads rows within 2 * 2^i of the row it writes, so rows [row0, row0 + nrows) after n iterations depend on the input rows
+ *   within H = 2 * (2^n - 1) of them and on nothing else.  Filtering the window [row0 - H, row0 + nrows + H), clamped to the image, as if it were
+ *   an image gives those rows bit for bit: a clamped edge IS the image's edge, and at an edge that is not, the rows that come out wrong are rows
+ *   nobody needs.  One row less, at either end, does not (tests/test_post_rows_restatement.py).
+ *   Upsampler: high row y reads low rows Y0(y), Y0(y) + 1 and y div factor, the last always one of the first two inside the low image: high rows
+ *   [row0, row0 + nrows) need low rows max(0, Y0(row0)) up to min(height / factor, Y0(row0 + nrows - 1) + 2).
+ * So the result of the post chain in tiles is defined with no new numerics: the bits of the whole-frame calls, in both libraries.  What moves
+ * between devices is the halo rows, and into the root 4 B per pixel (16 more with `filtered` / `upsampled`) instead of the 52 B per pixel of
+ * pixel, radiance and both guides.  NOT built: an RCCL transport for the exchange, graph capture of any of these calls.  Like everything with N
+ * contexts, none of it has run on N distinct devices: rehearsal groups on one device only.
+ *
+ * The two windows, one definition for every host (csrc/pt_rows_plan.hpp), beside mirt_tile_rows.  Both write 0, 0 on bad input: no rows, rows
+ * outside the image, iterations > MIRT_FILTER_MAX_ITERATIONS, a factor outside 2 .. 4 or one that does not divide height, height above 65535. */
+MIRT_API void mirt_filter_window_rows(uint32_t image_height, uint32_t row0, uint32_t nrows, uint32_t iterations, uint32_t* win_row0, uint32_t* win_nrows);
+MIRT_API void mirt_upsample_low_rows(uint32_t height, uint32_t factor, uint32_t row0, uint32_t nrows, uint32_t* lo_row0, uint32_t* lo_nrows);
+/* mirt_filter_atrous on rows [row0, row0 + nrows) of an image of desc->width x image_height pixels.  The descriptor is read as follows:
+ * desc->height is the number of rows the three INPUT buffers hold, image rows [win_row0, win_row0 + desc->height), the window; `filtered` and
+ * `pixel` hold nrows rows, image rows [row0, row0 + nrows), and nothing else.  The window lies inside [0, image_height) and contains
+ * mirt_filter_window_rows(image_height, row0, nrows, iterations); a larger window is allowed and changes nothing.
+ * Result: both outputs equal, bit for bit, rows [row0, row0 + nrows) of what mirt_filter_atrous writes for the whole frame, with either structure
+ * flag or neither, iterations 0 .. 5, in both libraries.
+ * How: mirt_filter_atrous's kernels, instantiated for a window.  Every iteration's edge test means the window's edge; iteration i of n computes
+ * only the rows still needed, the own rows and 2 * (2^n - 2^(i + 1)) around them; the last step (the prepare, for 0 iterations) reads radiance.w
+ * and the guides at the window's offset and stores the own rows alone.  Working memory: three float4 per pixel of the WINDOW, in the context's scratch buffer.
+ * Checks, all before anything is queued; nothing is written when one fails: those of mirt_filter_atrous (with image_height for the extent), and
+ * MIRT_E_ARG for nrows or desc->height 0, rows or a window that reach outside the image, a window that does not contain the rows needed;
+ * MIRT_E_RANGE for an input smaller than the window or an output smaller than nrows rows. */
+MIRT_API int mirt_filter_atrous_rows(mirt_ctx* ctx, const mirt_filter_desc* desc, uint32_t image_height, uint32_t win_row0, uint32_t row0, uint32_t nrows);
+/* mirt_upsample_guided on high rows [row0, row0 + nrows).  desc->width and desc->height are the WHOLE high image and mirt_upsample_guided's checks
+ * apply to them unchanged; normal_hits, albedo_depth, upsampled and pixel hold high rows [row0, row0 + nrows) and nothing else; the three low
+ * inputs hold low rows [lo_row0, lo_row0 + lo_nrows), a range inside the low image that contains mirt_upsample_low_rows(height, factor, row0,
+ * nrows); a larger one is allowed and changes nothing.
+ * Result: rows [row0, row0 + nrows) of the whole-frame call, bit for bit, in both libraries.
+ * How: the tap geometry is worked on the global row y = row0 + the band's row and the taps are tested against the low IMAGE (0 <= Y < height /
+ * factor); the low buffers are indexed at Y - lo_row0.  Tile borders from mirt_tile_rows are not multiples of factor (1080 rows over 8 is 135).
+ * Checks as above: those of mirt_upsample_guided, MIRT_E_ARG for the rules of the rows, MIRT_E_RANGE for the buffer sizes of the two extents. */
+MIRT_API int mirt_upsample_guided_rows(mirt_ctx* ctx, const mirt_upsample_desc* desc, uint32_t row0, uint32_t nrows, uint32_t lo_row0, uint32_t lo_nrows);
+/* THE HALO EXCHANGE.  All arrays have n entries, n = mirt_group_size; rows are row_bytes bytes each (width * 16 for the float4 images).
+ * src[i] is a buffer of context i whose first src_nrows[i] rows are image rows from src_row0[i] on: a tile as a pass, mirt_render_guides or
+ * mirt_filter_atrous_rows wrote it.  dst[i] is a buffer of context i that ends holding image rows [dst_row0[i], dst_row0[i] + dst_nrows[i]) from
+ * its first byte on: every row copied from whichever source owns it, the context's own rows included.  A window may span several owners (tiles
+ * can be shorter than the halo).  A NULL src[i] or dst[i] with 0 rows is allowed: a context that owns nothing, or wants nothing.
+ * Transport: copies only -- a device copy inside one device, hipMemcpyPeerAsync across devices (mirt_gather's copy transport).
+ * Ordering, so that nothing waits in a circle: (1) one event is recorded on every source context's stream; (2) each destination's stream waits for
+ * the events of the owners it reads, queues its copies and records an event; (3) each source's stream then waits for the events of the
+ * destinations that read it.  So the copies see everything queued on the sources before the call, and a source may overwrite its tile with the
+ * next pass without a mirt_finish.  Complete after mirt_finish of the destination's context.
+ * Refusals; nothing is queued on any device when one applies.  MIRT_E_ARG: a null array, n that is not the group's size, row_bytes 0 or not a
+ * multiple of 4, two sources that own the same row, a wanted row that nobody owns, a destination whose bytes meet a source's or another
+ * destination's, a call while any context is capturing.  MIRT_E_HANDLE: a bad group, a buffer that is not live or not its context's (NULL with
+ * rows included).  MIRT_E_RANGE: a buffer shorter than its rows.  Held command streams are flushed first, as mirt_gather does. */
+MIRT_API int mirt_exchange_rows(mirt_group* g, mirt_buf* const* src, const uint32_t* src_row0, const uint32_t* src_nrows, mirt_buf* const* dst,
+                                const uint32_t* dst_row0, const uint32_t* dst_nrows, int n, size_t row_bytes);
 
 /* ---- measurement: HIP events on the context's stream ---------------------------------- */
 MIRT_API int mirt_timer_start(mirt_ctx* ctx);
