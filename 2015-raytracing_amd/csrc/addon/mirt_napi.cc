@@ -408,6 +408,57 @@ napi_value RenderPassesGuided(napi_env env, napi_callback_info info) {
     return render_call(env, argv[0], argv[1], CALL_PASSES_GUIDED, argv[2], argv[3]);
 }
 
+// Ray queries.  traceClosest(ctx, desc, rays, count, hits, sets): the closest hit of `count` 32-byte rays {o, mint, d, maxt} of buffer `rays`
+// into hits ({normal, t, p, matId}, 32 bytes each) and / or sets (uint32 each), either may be null (mirt_trace_closest).
+// traceOccluded(ctx, desc, rays, count, occluded): a byte per ray (mirt_trace_occluded).  Of desc only spheres, triangles and meshes are read.
+// traceDeferred(ctx) -> how many rays the last of them re-ran in the exact kernel (mirt_trace_deferred).
+static napi_value trace_call(napi_env env, napi_value* argv, bool any) {
+    void *c, *rays = nullptr, *o0 = nullptr, *o1 = nullptr;
+    double count = 0;
+    if (!get_ext(env, argv[0], &c) || !get_f64(env, argv[3], &count) || !(count >= 0) || count > 18446744073709549568.0)
+        return throw_type(env, any ? "traceOccluded(ctx, desc, rays, count, occluded)" : "traceClosest(ctx, desc, rays, count, hits, sets)");
+    get_ext(env, argv[2], &rays);
+    get_ext(env, argv[4], &o0);
+    if (!any) get_ext(env, argv[5], &o1);
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    napi_value v;
+    if (prop(env, argv[1], "spheres", &v)) { if (!read_grid(env, v, &sph)) return throw_type(env, "trace: spheres"); p.spheres = &sph; }
+    if (prop(env, argv[1], "triangles", &v)) { if (!read_grid(env, v, &tri)) return throw_type(env, "trace: triangles"); p.triangles = &tri; }
+    if (prop(env, argv[1], "meshes", &v)) {
+        uint32_t n = 0;
+        napi_get_array_length(env, v, &n);
+        meshes.resize(n);
+        for (uint32_t i = 0; i < n; ++i) { napi_value e; napi_get_element(env, v, i, &e); if (!read_grid(env, e, &meshes[i])) return throw_type(env, "trace: meshes[i]"); }
+    }
+    p.n_meshes = (uint32_t)meshes.size();
+    p.meshes = meshes.data();
+    const int rc = any ? mirt_trace_occluded((mirt_ctx*)c, &p, (mirt_buf*)rays, (uint64_t)count, (mirt_buf*)o0)
+                       : mirt_trace_closest((mirt_ctx*)c, &p, (mirt_buf*)rays, (uint64_t)count, (mirt_buf*)o0, (mirt_buf*)o1);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value TraceClosest(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    return trace_call(env, argv, false);
+}
+napi_value TraceOccluded(napi_env env, napi_callback_info info) {
+    ARGS(5);
+    return trace_call(env, argv, true);
+}
+napi_value TraceDeferred(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "traceDeferred(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_trace_deferred((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
+}
+
 // filterAtrous(ctx, {width,height,iterations,flags,normalPowerLog2,tone,sigmaDepth,sigmaColour, radiance,normalHits,albedoDepth, filtered?,pixel?}):
 // the a-trous filter of a frame on the device (mirt_filter_atrous); a number left out is 0, a buffer left out NULL -- the library checks them all
 void filter_desc(napi_env env, napi_value d, mirt_filter_desc& f) {
@@ -842,7 +893,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

@@ -74,6 +74,9 @@ struct mirt_ctx {
     uint32_t defer_unit = 1;      // samples per mask bit: 1, or 256 when that pass resolved its pixels itself (a bit per block)
     void* guide_mask = nullptr;   // mirt_render_guides, optimistic pair: a bit per pixel of the tile (its own allocation: the pass's mask and what
     size_t guide_mask_bytes = 0;  // mirt_pass_deferred reports of it stay as the last pass left them)
+    void* ray_defer = nullptr;    // mirt_trace_closest / mirt_trace_occluded, optimistic pair: [count, pad, pad, pad | a bit per ray], its own allocation too
+    size_t ray_defer_bytes = 0;
+    uint32_t ray_defer_words = 0; // mask words the last trace call used (0: it ran the exact kernel only, or queued nothing)
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     float res_m_override = NAN;        // try_fuse_pass -> render_pass_impl: the tone factor of the recorded copyToPixel, as the host passed it
@@ -356,6 +359,7 @@ static int destroy_ctx(mirt_ctx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->defer) (void)hipFree(ctx->defer);
     if (ctx->guide_mask) (void)hipFree(ctx->guide_mask);
+    if (ctx->ray_defer) (void)hipFree(ctx->ray_defer);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1245,6 +1249,7 @@ static pt::PassRequest pass_request(const mirt_ctx* ctx, const mirt_pass_desc* d
 
 // What mirt_render_pass and mirt_render_guides check and fill alike, in this order: the descriptor, the k x k ray count, the tile, then the camera,
 // bounds, primitive sets (validated and prepared: fill_grid) and material of `A`.  guides: the lights and pass_index are not looked at.
+static int fill_sets(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, pt::FusedArgs& A);
 static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bool guides, pt::FusedArgs& A) {
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "%s: empty image", fn);
@@ -1276,6 +1281,22 @@ static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bo
     A.row0 = d->row0; A.nrows = nrows; A.bounces = d->bounces;
     A.n_lights = guides ? 0u : d->n_lights;
     int rc;
+    if ((rc = fill_sets(ctx, fn, d, A))) return rc;
+    for (uint32_t l = 0; l < A.n_lights; ++l) {
+        memcpy(A.lights[l].shadow, d->lights[l].shadow, 64);
+        memcpy(A.lights[l].scene, d->lights[l].scene, 64);
+        memcpy(A.lights[l].light, d->lights[l].light, 64);
+    }
+    if ((rc = need(ctx, "material", d->material, 16))) return rc;
+    A.material = d->material->ptr;
+    A.nmat = (uint32_t)(d->material->bytes / 16);
+    return MIRT_OK;
+}
+
+// The primitive sets of a descriptor into A.sets, in upload order, validated and prepared (fill_grid): what a pass, the guides and the ray queries
+// (mirt_trace_closest, mirt_trace_occluded) share.  The caller has checked n_meshes and the mesh array.
+static int fill_sets(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, pt::FusedArgs& A) {
+    int rc;
     if (d->spheres && (rc = fill_grid(ctx, "spheres", d->spheres, false, true, &A.sets[A.n_sets++]))) return rc;
     if (d->triangles && (rc = fill_grid(ctx, "triangles", d->triangles, true, true, &A.sets[A.n_sets++]))) return rc;
     for (uint32_t m = 0; m < d->n_meshes; ++m)
@@ -1293,14 +1314,6 @@ static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bo
                     return fail(ctx, MIRT_E_ARG, "%s: two triangle sets share a position buffer but hold %u and %u slots (one prepared copy per buffer: "
                                                  "give each set its own buffer)", fn, gs[i]->cell_offsets->off_last, gs[j]->cell_offsets->off_last);
     }
-    for (uint32_t l = 0; l < A.n_lights; ++l) {
-        memcpy(A.lights[l].shadow, d->lights[l].shadow, 64);
-        memcpy(A.lights[l].scene, d->lights[l].scene, 64);
-        memcpy(A.lights[l].light, d->lights[l].light, 64);
-    }
-    if ((rc = need(ctx, "material", d->material, 16))) return rc;
-    A.material = d->material->ptr;
-    A.nmat = (uint32_t)(d->material->bytes / 16);
     return MIRT_OK;
 }
 
@@ -1587,6 +1600,93 @@ int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_
     if (albedo_depth) albedo_depth->version++;
     return MIRT_OK;
 } MIRT_CATCH("mirt_render_guides", return MIRT_E_DEVICE)
+
+// ---- ray queries (pt_kernels_rays.hip): mirt_trace_closest and mirt_trace_occluded.  Every check comes before anything is queued; then one launch
+// -- or the optimistic / exact pair, per ray -- of one lane per ray.  Nothing but the outputs is written.
+static int trace_impl(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, mirt_buf* rays, uint64_t count, mirt_buf* hits, mirt_buf* sets, mirt_buf* occluded, bool any) {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, fn);
+    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
+    if (count > 0xFFFFFF00ull) return fail(ctx, MIRT_E_ARG, "%s: %llu rays in one call (the kernels index a call's rays with 32 bits); split the batch", fn, (unsigned long long)count);
+    if (!any && !hits && !sets) return fail(ctx, MIRT_E_ARG, "%s: hits and sets are both NULL (either may be, not both)", fn);
+    if (any && !occluded) return fail(ctx, MIRT_E_ARG, "%s: occluded is NULL", fn);
+    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
+    if (d->n_meshes && !d->meshes) return fail(ctx, MIRT_E_ARG, "%s: null mesh array", fn);
+    int rc;
+    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[4] = {{"rays", rays, count * 32}, {"hits", hits, count * 32}, {"sets", sets, count * 4}, {"occluded", occluded, count}};
+    if (!rays) return fail(ctx, MIRT_E_HANDLE, "%s: rays is NULL", fn);
+    for (const auto& b : io)
+        if (b.buf && (rc = need(ctx, (std::string(fn) + " " + b.label).c_str(), b.buf, b.bytes))) return rc;
+    {   // an output is read by nobody and no input is written: the bytes the call touches, and the geometry's buffers whole
+        std::vector<pt::PostRange> in;
+        in.push_back({(uint64_t)(uintptr_t)rays->ptr, count * 32, true});
+        const auto add = [&in](const mirt_buf* b) { if (b && live_has(b)) in.push_back({(uint64_t)(uintptr_t)b->ptr, (uint64_t)b->bytes, true}); };
+        const auto add_grid = [&add](const mirt_grid* g) { if (g) { add(g->prims); add(g->normals); add(g->matid); add(g->cell_offsets); } };
+        add_grid(d->spheres); add_grid(d->triangles);
+        for (uint32_t m = 0; m < d->n_meshes; ++m) add_grid(&d->meshes[m]);
+        pt::PostRange out[3];
+        for (int i = 0; i < 3; ++i) out[i] = {io[i + 1].buf ? (uint64_t)(uintptr_t)io[i + 1].buf->ptr : 0u, io[i + 1].bytes, io[i + 1].buf != nullptr};
+        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 3);
+        if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: an output's bytes meet the rays' or a geometry buffer's", fn);
+        if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: hits aliases sets", fn);
+    }
+    if (!count) return MIRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::FusedArgs A;
+    memset(&A, 0, sizeof A);
+    if ((rc = fill_sets(ctx, fn, d, A))) return rc;
+    void* const hp = hits ? hits->ptr : nullptr;
+    uint32_t* const sp = sets ? (uint32_t*)sets->ptr : nullptr;
+    uint8_t* const op = occluded ? (uint8_t*)occluded->ptr : nullptr;
+    ctx->ray_defer_words = 0;
+    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
+        const uint32_t words = (uint32_t)((count + 31u) / 32u);
+        const size_t need_bytes = 16u + (size_t)words * 4u;
+        if (ctx->ray_defer_bytes < need_bytes) {
+            if (ctx->ray_defer) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->ray_defer)); ctx->ray_defer = nullptr; ctx->ray_defer_bytes = 0; }
+            HIPCHK(ctx, hipMalloc(&ctx->ray_defer, need_bytes));
+            ctx->ray_defer_bytes = need_bytes;
+        }
+        uint32_t* const mask = (uint32_t*)ctx->ray_defer + 4;
+        HIPCHK(ctx, hipMemsetAsync(ctx->ray_defer, 0, need_bytes, ctx->stream));
+        pt::launch_rays(ctx->stream, A, true, rays->ptr, (uint32_t)count, hp, sp, op, mask, nullptr);
+        pt::launch_rays(ctx->stream, A, false, rays->ptr, (uint32_t)count, hp, sp, op, nullptr, mask);
+        ctx->ray_defer_words = words;
+    } else {
+        pt::launch_rays(ctx->stream, A, false, rays->ptr, (uint32_t)count, hp, sp, op, nullptr, nullptr);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    for (int i = 1; i < 4; ++i) if (io[i].buf) io[i].buf->version++;
+    return MIRT_OK;
+}
+
+int mirt_trace_closest(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* rays, uint64_t count, mirt_buf* hits, mirt_buf* sets) try {
+    return trace_impl(ctx, "mirt_trace_closest", d, rays, count, hits, sets, nullptr, false);
+} MIRT_CATCH("mirt_trace_closest", return MIRT_E_DEVICE)
+
+int mirt_trace_occluded(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* rays, uint64_t count, mirt_buf* occluded) try {
+    return trace_impl(ctx, "mirt_trace_occluded", d, rays, count, nullptr, nullptr, occluded, true);
+} MIRT_CATCH("mirt_trace_occluded", return MIRT_E_DEVICE)
+
+int mirt_trace_deferred(mirt_ctx* ctx, uint64_t* rays) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_trace_deferred: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_trace_deferred");
+    if (!rays) return fail(ctx, MIRT_E_ARG, "mirt_trace_deferred: null output");
+    *rays = 0;
+    if (!ctx->ray_defer_words) return MIRT_OK;
+    // counted on demand: the mask of the last trace call is still in place (the next one clears it)
+    uint32_t* counters = (uint32_t*)ctx->ray_defer;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
+    pt::launch_deferCount(ctx->stream, counters + 4, ctx->ray_defer_words, counters);
+    uint32_t count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *rays = count;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_trace_deferred", return MIRT_E_DEVICE)
 
 // ---- the post-process stage: mirt_filter_atrous and mirt_upsample_guided.  The argument rules they share are pt_post_check.hpp's (host-only,
 // CPU-tested); here are those rules' messages, `fn` being the entry point's name, and the shared epilogue.

@@ -1,0 +1,218 @@
+// pt_kernels_rays.hip -- ray queries (mirt_trace_closest, mirt_trace_occluded): the closest hit, or whether anything is hit at all, for rays
+// the CALLER supplies -- picking, autofocus, visibility between two points, ambient occlusion, baking -- where every other kernel of the library
+// starts at the Assign10 camera.
+//
+// Definition.  Ray i is the record {o, mint, d, maxt} (32 bytes) as given: d is not normalised, t is in units of |d|.
+//   closest   the state the kernel-by-kernel path leaves in Ray.maxt and Poi when Ray{o, d, mint, maxt} and a Poi reset as initTrace resets it
+//             (A10 code.cl:538-541) run through sphereTrace, triangleTrace and every meshTrace in upload order (code.js:1809-1813):
+//             hits[i] = {Poi.normal, Ray.maxt, Poi.p, Poi.matId}, 32 bytes; a miss is (0, 0, 0, the input maxt, 0, 0, 0, -1), and a dead ray
+//             (mint == maxt) is a miss.  sets[i] = the index, in that stage order, of the set whose primitive won, or 0xFFFFFFFF.
+//   occluded  sceneRender's own test (code.cl:1350): occluded[i] = 1 iff mint == maxt after sphereShadowTrace, triangleShadowTrace and a
+//             triangleShadowTrace per mesh have run on the ray in that order -- a ray that enters dead is reported 1.  No t is delivered, so the
+//             sets run the fused pass's cheap any-hit forms (COOP_ANY, the blocked-flag cell loops).
+//
+// The bits are the fused pass's: stage_block, the per-set calls and their template arguments are those of closest_all (pt_closest.hpp) and of
+// the shadow stage of direct_all (pt_kernels_fused.hip), the sets get the LDS slots the pass gives them (fused_lds_slots), and the optimistic /
+// exact pair is the pass's -- here per RAY: a ray the ray-side guard refuses, or whose walk defers, sets its bit and writes nothing, and the exact
+// kernel redoes the marked rays.  Both set loops are RESTATED here, not shared: closest_all has no way to say which set won (`sets`), the shadow
+// loop lives inside direct_all between the shadow ray's construction and the shading, and neither file is touched by this one -- their kernels'
+// resource reports stay the parent's line for line (profiles/rays/kernel_resources.txt).  One shared definition of each loop is a refactor of its own.
+//
+// Structure: one lane per ray, two float4 loads, the query, two float4 stores (and the optional uint32), or one byte.  With grids every lane of a
+// wave enters the shared-test walk (pt_trace_coop.hpp): a lane without a ray, and a redo kernel's unmarked lane, rides along as a dead ray and
+// writes nothing.
+//
+// A caller's rays are not the camera's: they need not be coherent, and axis-parallel directions are common -- a zero component of d fails the
+// guard's |d_k| >= 2^-40, as does a zero-length, infinite or NaN one.  Such batches run mostly in the EXACT kernel (mirt_trace_deferred counts
+// them; profiles/rays/timing.json has the measured cost).  The guard windows are what makes the optimistic kernel's divisions exact and are not
+// widened for this.
+#include "pt_closest.hpp"
+
+namespace pt {
+
+// The default contract only (libmirt_default.so).  The sphere stage's 1 / (2 d.d) depends on the ray alone, so the compiler moves it out of the
+// loop over the sets -- and a division it moves loses the 2.5-ulp licence the build gives every division: it comes out correctly rounded, one
+// ulp off the kernel-by-kernel path's (and the reference's default build's) v_rcp_f32 form wherever the two differ.  A camera's unit-length d
+// never showed it (d.d is within an ulp of 1); a caller's d does.  An empty statement that "changes" d at the top of every trip keeps the
+// division where it is written.  Not a run-time cost: the values stay in their registers.
+PT_DEV void keep_in_loop(Ray& r) {
+#if PT_PLAIN_DIV
+    asm volatile("" : "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z));
+#endif
+}
+
+// The optimistic kernel's ray-side guard (a dead ray divides nothing and is not asked).  A refused ray is the exact kernel's whatever this kernel
+// would compute for it, and nothing of it is written here: it goes on DEAD, riding along in the shared walks like a lane without a ray, so a batch
+// the guard refuses whole -- axis-parallel rays -- costs the optimistic kernel next to nothing.
+PT_DEV void guard_or_retire(Ray& r, bool& defer) {
+    if (r.mint == r.maxt || ray_guard(r)) return;
+    defer = true;
+    r.mint = 0.0f;
+    r.maxt = 0.0f;
+}
+
+// closest_all's loop (pt_closest.hpp), with the index of the last set that won noted in `won`
+template <bool FAST, int GRIDS>
+PT_DEV void rays_closest(const FusedArgs& A, Ray& ray, Poi& poi, uint32_t& won, bool& defer) {
+    if (FAST) guard_or_retire(ray, defer);
+    const RayRcp rr = ray_rcp<FAST>(ray);
+    for (uint32_t s = 0; s < A.n_sets; ++s) {
+        const GridArgs& S = A.sets[s];
+        keep_in_loop(ray);
+        const bool live = !(ray.mint == ray.maxt);
+        Hit ch;
+        ch.idx = UINT32_MAX;
+        if (!GRIDS || S.n == 1u) {
+            if (live) {
+                const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(ray, rr, set_box(S));
+                if (bh.v) ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, false, TRI_A10, FAST>(ray, rr, bh, S) : trace_cell1<TRIANGLES, false, TRI_A10, FAST, false, PT_LANE_LISTS_FOR(FAST, GRIDS)>(ray, rr, bh, S);
+            }
+        } else if (S.kind == KIND_TRIANGLES) {   // every lane of the wave enters: the tests of the walk are shared (pt_trace_coop.hpp)
+            BoxHit bh = {};
+            if (live) bh = inter_aabb_t<FAST, true>(ray, rr, set_box(S));
+            ch = trace_dda_coop<COOP_CLOSEST, FAST, GRIDS == 1>(live && bh.v, ray, rr, bh, S, defer);
+        } else if (live) {
+            const BoxHit bh = inter_aabb_t<FAST, true>(ray, rr, set_box(S));
+            if (bh.v) ch = trace_dda<SPHERES, false, TRI_A10, FAST, GRIDS == 1>(ray, bh, S, defer);
+        }
+        if (ch.idx == UINT32_MAX) continue;
+        won = s;
+        ray.maxt = ch.t;
+        poi.p = fma3(ch.t, ray.d, ray.o);   // getPoint, code.cl:87
+        if (S.kind == KIND_SPHERES) {
+            poi.n = norm3(sub3(poi.p, ld3(((const float4*)S.prims)[ch.idx])));
+            poi.matId = (int32_t)((const uint32_t*)S.matid)[ch.idx];
+        } else {
+            float w = 1.0f - ch.beta - ch.gamma;  // code.cl:409-411
+            if (PT_LANE_LISTS_FOR(FAST, GRIDS) && S.n == 1u && S.lds_off != kNoLds) {   // staged with its vertex normals and material ids (stage_block)
+                const uint32_t base = S.lds_off + 12u * S.nslots;
+                const float4* nn = (const float4*)&pt_lds_dyn[base + __umul24(ch.idx, 12u)];
+                poi.n = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
+                poi.matId = (int32_t)pt_lds_dyn[base + 12u * S.nslots + ch.idx];
+            } else {
+                const float4* nn = (const float4*)S.normals + 3u * (size_t)ch.idx;
+                poi.n = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
+                poi.matId = (int32_t)(S.matid ? ((const uint32_t*)S.matid)[ch.idx] : S.mesh_matid);
+            }
+        }
+    }
+}
+
+// the per-set loop of the fused pass's shadow stage (pt_kernels_fused.hip direct_all) on the caller's ray
+template <bool FAST, int GRIDS>
+PT_DEV void rays_any(const FusedArgs& A, Ray& sh, bool& defer) {
+    if (FAST) guard_or_retire(sh, defer);
+    const RayRcp rr = ray_rcp<FAST>(sh);
+    for (uint32_t s = 0; s < A.n_sets; ++s) {
+        const GridArgs& S = A.sets[s];
+        keep_in_loop(sh);
+        const bool live = !(sh.mint == sh.maxt);
+        Hit ch;
+        ch.idx = UINT32_MAX;
+        ch.t = sh.maxt;
+        bool walked = false;
+        if (!GRIDS || S.n == 1u) {
+            if (live) {
+                const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(sh, rr, set_box(S));
+                if (bh.v) {
+                    ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, true, TRI_A10, FAST, true>(sh, rr, bh, S) : trace_cell1<TRIANGLES, true, TRI_A10, FAST, true, PT_LANE_LISTS_FOR(FAST, GRIDS)>(sh, rr, bh, S);
+                    walked = true;
+                }
+            }
+        } else if (S.kind == KIND_TRIANGLES) {
+            BoxHit bh = {};
+            if (live) bh = inter_aabb_t<FAST, true>(sh, rr, set_box(S));
+            walked = live && bh.v;
+            ch = trace_dda_coop<COOP_ANY, FAST, GRIDS == 1>(walked, sh, rr, bh, S, defer);
+        } else if (live) {
+            const BoxHit bh = inter_aabb_t<FAST, true>(sh, rr, set_box(S));
+            if (bh.v) {
+                ch = trace_dda<SPHERES, true, TRI_A10, FAST, GRIDS == 1>(sh, bh, S, defer);
+                walked = true;
+            }
+        }
+        if (!walked) continue;
+        sh.maxt = ch.t;
+        if (ch.idx != UINT32_MAX) sh.mint = ch.t;
+    }
+}
+
+// rays: two float4 per ray {o, mint} {d, maxt}.  ANY: `occluded` (a byte per ray); else `hits` (two float4 per ray) and / or `sets`.
+// defer_mask (optimistic kernel): a bit per ray.  redo_mask (exact kernel only): the rays the optimistic kernel handed over; null: every ray.
+template <bool FAST, int GRIDS, bool ANY>
+__global__ void __launch_bounds__(256) k_traceRays(const FusedArgs A, const float4* __restrict__ rays, uint32_t count, float4* __restrict__ hits,
+                                                   uint32_t* __restrict__ sets, uint8_t* __restrict__ occluded, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    stage_block<FAST, GRIDS>(A);
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;   // (count <= 2^32 - 256: mirt_trace_closest)
+    bool valid = id < count;
+    if (!FAST && redo_mask && valid) valid = (redo_mask[id >> 5] >> (id & 31u) & 1u) != 0u;
+    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
+    else if (!valid) return;
+    Ray ray;   // a lane without a ray rides along dead: it enters the shared walks and tests nothing of its own
+    ray.o = mk3(0.0f, 0.0f, 0.0f); ray.d = mk3(0.0f, 0.0f, 0.0f); ray.mint = 0.0f; ray.maxt = 0.0f;
+    if (valid) {
+        const float4 a = rays[2u * (size_t)id], b = rays[2u * (size_t)id + 1u];
+        ray.o = mk3(a.x, a.y, a.z); ray.mint = a.w;
+        ray.d = mk3(b.x, b.y, b.z); ray.maxt = b.w;
+    }
+    bool defer = false;
+    // The deferred rays' bits.  A wave holds 64 consecutive ray ids from a multiple of 64 on: two whole words of the mask, which no other wave
+    // touches -- so lanes 0 and 32 store the wave's ballot, a word each (a zero word stays as the host cleared it), instead of one atomic per
+    // ray: a batch the guard refuses whole made 32 atomics on every word of the mask, and they cost more than tracing the batch.
+    const auto hand_over = [&]() {
+        const unsigned long long dm = __builtin_amdgcn_ballot_w64(valid && defer);
+        const uint32_t lane = threadIdx.x & 63u;
+        if (valid && (lane & 31u) == 0u) {
+            const uint32_t w = (uint32_t)(dm >> lane);
+            if (w) defer_mask[id >> 5] = w;
+        }
+    };
+    if (ANY) {
+        rays_any<FAST, GRIDS>(A, ray, defer);
+        if (FAST) hand_over();
+        if (!valid || (FAST && defer)) return;   // the exact kernel redoes a deferred ray: nothing of it is written
+        occluded[id] = ray.mint == ray.maxt ? (uint8_t)1 : (uint8_t)0;
+    } else {
+        Poi poi;
+        poi.p = mk3(0.0f, 0.0f, 0.0f);
+        poi.n = mk3(0.0f, 0.0f, 0.0f);
+        poi.atte = mk3(1.0f, 1.0f, 1.0f);
+        poi.matId = -1;
+        uint32_t won = UINT32_MAX;
+        rays_closest<FAST, GRIDS>(A, ray, poi, won, defer);
+        if (FAST) hand_over();
+        if (!valid || (FAST && defer)) return;
+        if (hits) {
+            hits[2u * (size_t)id] = make_float4(poi.n.x, poi.n.y, poi.n.z, ray.maxt);
+            hits[2u * (size_t)id + 1u] = make_float4(poi.p.x, poi.p.y, poi.p.z, __int_as_float(poi.matId));
+        }
+        if (sets) sets[id] = won;
+    }
+}
+
+template <bool FAST, bool ANY>
+static void launch_rays_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const float4* rays, uint32_t count, float4* hits, uint32_t* sets, uint8_t* occluded,
+                          uint32_t* defer_mask, const uint32_t* redo_mask) {
+    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
+    if (L.grids && L.staged) hipLaunchKernelGGL((k_traceRays<FAST, 1, ANY>), grid, dim3(256), L.lds, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
+    else if (L.grids) hipLaunchKernelGGL((k_traceRays<FAST, 2, ANY>), grid, dim3(256), L.lds2, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
+    else hipLaunchKernelGGL((k_traceRays<FAST, 0, ANY>), grid, dim3(256), L.lds_tri, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
+}
+// fast: the optimistic kernel (sets the deferred rays' bits in defer_mask, one per ray); !fast: the exact kernel over the rays of redo_mask, or
+// over every ray when it is null.  occluded != null: the occlusion query; else the closest hit into hits and / or sets.
+void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, void* hits, uint32_t* sets, uint8_t* occluded,
+                 uint32_t* defer_mask, const uint32_t* redo_mask) {
+    if (!count) return;
+    FusedArgs b = a;
+    b.rpp = 1u;   // stage_block: no lens table
+    const FusedLds L = fused_lds_slots(b, fast);
+    if (occluded) {
+        if (fast) launch_rays_t<true, true>(s, b, L, (const float4*)rays, count, nullptr, nullptr, occluded, defer_mask, nullptr);
+        else launch_rays_t<false, true>(s, b, L, (const float4*)rays, count, nullptr, nullptr, occluded, nullptr, redo_mask);
+    } else {
+        if (fast) launch_rays_t<true, false>(s, b, L, (const float4*)rays, count, (float4*)hits, sets, nullptr, defer_mask, nullptr);
+        else launch_rays_t<false, false>(s, b, L, (const float4*)rays, count, (float4*)hits, sets, nullptr, nullptr, redo_mask);
+    }
+}
+
+}  // namespace pt

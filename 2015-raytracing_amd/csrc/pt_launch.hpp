@@ -144,6 +144,12 @@ void launch_deferCount(hipStream_t s, const uint32_t* mask, uint32_t words, uint
 // albedo_depth = (sum of their material colours, sum of their Ray.maxt).  One lane per pixel; the optimistic / exact pair as in launch_fused, the
 // mask one bit per pixel: (nrows * width + 31) / 32 words.  Reads the camera, bounds, sets and material of `a`; either output may be null.
 void launch_guides(hipStream_t s, const FusedArgs& a, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask, const uint32_t* redo_mask);
+// Ray queries (pt_kernels_rays.hip): `count` caller-supplied rays of 32 bytes {o, mint, d, maxt}, one lane per ray.  occluded != null: a byte per
+// ray, 1 iff the any-hit stage leaves mint == maxt; else the closest hit, hits = {normal, t, p, matId} (32 bytes per ray) and / or sets = the index
+// of the winning set (uint32 per ray).  The optimistic / exact pair as in launch_guides, the mask one bit per ray: (count + 31) / 32 words.  Reads
+// the sets of `a` and nothing else of it.
+void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, void* hits, uint32_t* sets, uint8_t* occluded,
+                 uint32_t* defer_mask, const uint32_t* redo_mask);
 // Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
 // every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
 struct FilterArgs {

@@ -6,6 +6,7 @@
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
+//   node cli.js trace  <scene.xml> <rays.f32> <out.f32> [--occluded] [--sets out.u32]  -> ray queries on the caller's own rays (mirt_trace_closest): rays.f32 holds raw 32-byte records {o.xyz, mint, d.xyz, maxt}, out.f32 receives {normal.xyz, t, p.xyz, matId (int32)} per ray, --sets the uint32 index of the winning set per ray; --occluded: <out.f32> receives one byte per ray instead, 1 iff something blocks it (mirt_trace_occluded)
 //   node cli.js devices                                                             -> what webcl.getPlatforms()/getDevices() report
 "use strict";
 const fs = require("fs");
@@ -22,7 +23,7 @@ function writeFrame(out, px, w, h) {
 }
 
 function usage() {
-  process.stderr.write(fs.readFileSync(__filename, "utf8").split("\n").slice(1, 11).join("\n") + "\n");
+  process.stderr.write(fs.readFileSync(__filename, "utf8").split("\n").slice(1, 12).join("\n") + "\n");
   process.exit(2);
 }
 
@@ -136,6 +137,22 @@ if (cmd === "pack") {
   fs.writeFileSync(rest[1] + ".pos.f64", Buffer.from(pos.buffer));
   fs.writeFileSync(rest[1] + ".nor.f64", Buffer.from(nor.buffer));
   fs.writeFileSync(rest[1] + ".meta.json", JSON.stringify(meta));
+} else if (cmd === "trace") {
+  if (rest.length < 3) usage();
+  const renderer = require("./renderer.js");
+  const si = rest.indexOf("--sets");
+  if (si >= 0 && !rest[si + 1]) usage();
+  const raw = fs.readFileSync(rest[1]);
+  if (raw.length % 32) { process.stderr.write(`${rest[1]}: ${raw.length} bytes is not a whole number of 32-byte rays\n`); process.exit(2); }
+  const rays = new Float32Array(raw.length / 4);
+  Buffer.from(rays.buffer).set(raw);   // (a file's bytes need not sit 4-byte aligned in node's pool)
+  const occluded = rest.includes("--occluded");
+  if (occluded && si >= 0) { process.stderr.write("--sets goes with the closest-hit query, not with --occluded\n"); process.exit(2); }
+  const res = renderer.traceFile(rest[0], rays, { occluded: occluded, sets: si >= 0 });
+  const out = occluded ? res.occluded : res.hits;
+  fs.writeFileSync(rest[2], Buffer.from(out.buffer, out.byteOffset, out.byteLength));
+  if (res.sets) fs.writeFileSync(rest[si + 1], Buffer.from(res.sets.buffer, res.sets.byteOffset, res.sets.byteLength));
+  process.stderr.write(`traced ${rays.length / 8} rays of ${rest[1]} through ${rest[0]}: ${occluded ? "occlusion" : "closest hit"}; rays redone by the exact kernel: ${res.deferred}\n`);
 } else if (cmd === "devices") {
   const { webcl } = require("./webcl.js");
   for (const p of webcl.getPlatforms()) {

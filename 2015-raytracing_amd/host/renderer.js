@@ -683,4 +683,35 @@ function renderUpscaled(file, width, height, rpp, passes, factor, opt) {
   }
 }
 
-module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };
+// Ray queries on a scene file (queue.traceClosest / traceOccluded): `rays` a Float32Array of 8 floats per ray {o.xyz, mint, d.xyz, maxt}.
+// opt.occluded: -> {occluded: Uint8Array}; else -> {hits: Float32Array of 8 per ray (matId as int32 bits in the 8th), sets: Uint32Array | undefined
+// (opt.sets)}; both with `deferred`, the rays the exact kernel redid.  The camera and the image size play no part.
+function traceFile(file, rays, opt) {
+  opt = opt || {};
+  const n = Math.floor(rays.length / 8);
+  const packed = scene.packScene(scene.loadSceneFile(file, 8, 8), 8, 8, 4);
+  const ctx = webcl.createContext(pickDevice(opt.device)), q = ctx.createCommandQueue();
+  const dev = uploadScene(ctx, q, packed);
+  const desc = { spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes };
+  const mk = (bytes) => ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(bytes, 16));
+  const rb = mk(n * 32);
+  if (n) q.enqueueWriteBuffer(rb, false, 0, n * 32, rays.subarray(0, n * 8), []);
+  const res = {};
+  if (opt.occluded) {
+    const ob = mk(n);
+    q.traceOccluded(desc, rb, n, ob);
+    res.occluded = new Uint8Array(n);
+    if (n) q.enqueueReadBuffer(ob, true, 0, n, res.occluded, []);
+  } else {
+    const hb = mk(n * 32), sb = opt.sets ? mk(n * 4) : null;
+    q.traceClosest(desc, rb, n, hb, sb);
+    res.hits = new Float32Array(n * 8);
+    if (n) q.enqueueReadBuffer(hb, true, 0, n * 32, res.hits, []);
+    if (sb) { res.sets = new Uint32Array(n); if (n) q.enqueueReadBuffer(sb, true, 0, n * 4, res.sets, []); }
+  }
+  res.deferred = q.traceDeferred();
+  ctx.release();
+  return res;
+}
+
+module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };

@@ -190,6 +190,25 @@ class WebCLCommandQueue {
     const d = this._passDesc(desc);
     wrap(() => native().renderGuides(this.ctx.h, d, normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
   }
+  // ---- extension: ray queries on the caller's own rays (mirt_trace_closest, mirt_trace_occluded; include/mirt.h has the definition).  rays: a
+  // buffer of `count` 32-byte records {o.xyz, mint, d.xyz, maxt}; hits: {normal.xyz, t, p.xyz, matId (int32)} per ray; sets: a uint32 per ray, the
+  // index of the set whose primitive won (0xFFFFFFFF: none); hits or sets may be null, not both.  occluded: a byte per ray.  Of desc only
+  // spheres, triangles and meshes are read.  traceDeferred(): the rays the last of these calls re-ran in the exact kernel.
+  hasTrace() { return typeof native().traceClosest === "function"; }
+  _setsDesc(desc) {
+    const g = (s) => s && { prims: s.prims.h, normals: s.normals ? s.normals.h : undefined, matid: s.matid ? s.matid.h : undefined,
+                            cellOffsets: s.cellOffsets.h, bounds: s.bounds, nSlabs: s.nSlabs, meshMatId: s.meshMatId || 0 };
+    return { spheres: g(desc.spheres), triangles: g(desc.triangles), meshes: (desc.meshes || []).map(g) };
+  }
+  traceClosest(desc, rays, count, hits, sets) {
+    const d = this._setsDesc(desc);
+    wrap(() => native().traceClosest(this.ctx.h, d, rays ? rays.h : null, count, hits ? hits.h : null, sets ? sets.h : null));
+  }
+  traceOccluded(desc, rays, count, occluded) {
+    const d = this._setsDesc(desc);
+    wrap(() => native().traceOccluded(this.ctx.h, d, rays ? rays.h : null, count, occluded ? occluded.h : null));
+  }
+  traceDeferred() { return wrap(() => native().traceDeferred(this.ctx.h)); }
   // ---- extension: a frame's first pass and its guide buffers in one call (mirt_render_first_pass_guided): every buffer ends as after
   // renderPass(desc with firstPass) followed by renderGuides(desc, normalHits, albedoDepth) -- where the pass resolves its pixels at 4, 16 or 64 rays
   // per pixel the pass's own launch writes the guides (ctx.guidedPasses() counts those calls), elsewhere the guide launches follow it.

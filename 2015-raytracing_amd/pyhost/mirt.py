@@ -126,6 +126,9 @@ SYMBOLS = {
     "mirt_render_first_pass_guided": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_void_p]),
     "mirt_render_passes_guided": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mirt_ctx_guided_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_trace_closest": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "mirt_trace_occluded": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mirt_trace_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
     "mirt_upsample_guided": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc)]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -532,6 +535,25 @@ class Context:
         """how many render_first_pass_guided / render_passes_guided calls of this context wrote the guides from the pass's own launch (mirt_ctx_guided_passes)"""
         n = C.c_uint64()
         self._chk(lib().mirt_ctx_guided_passes(self.h, C.byref(n)))
+        return n.value
+
+    def trace_closest(self, desc, rays, count, hits, sets=None):
+        """The closest hit of `count` caller-supplied rays (mirt_trace_closest): rays holds 32-byte records {o, mint, d, maxt}, hits receives
+        {normal, t, p, mat_id} (32 bytes) and sets (optional) a uint32 per ray, the index of the set that won.  Of desc only the primitive sets
+        are read.  hits or sets may be None, not both."""
+        self._chk(lib().mirt_trace_closest(self.h, C.byref(desc) if desc is not None else None, rays.h if rays else None, int(count),
+                                           hits.h if hits else None, sets.h if sets else None))
+
+    def trace_occluded(self, desc, rays, count, occluded):
+        """Whether anything blocks each of `count` caller-supplied rays (mirt_trace_occluded): occluded receives a uint8 per ray, 1 iff the
+        any-hit stage leaves mint == maxt (a ray that enters dead is reported 1)."""
+        self._chk(lib().mirt_trace_occluded(self.h, C.byref(desc) if desc is not None else None, rays.h if rays else None, int(count),
+                                            occluded.h if occluded else None))
+
+    def trace_deferred(self):
+        """how many rays the last trace_closest / trace_occluded call re-ran in the exact kernel (mirt_trace_deferred)"""
+        n = C.c_uint64()
+        self._chk(lib().mirt_trace_deferred(self.h, C.byref(n)))
         return n.value
 
     def filter_atrous(self, width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,

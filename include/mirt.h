@@ -290,6 +290,36 @@ MIRT_API int mirt_ctx_guided_passes(mirt_ctx* ctx, uint64_t* count);
  * above, graph capture.  MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
 MIRT_API int mirt_render_passes_guided(mirt_ctx* ctx, const mirt_pass_desc* desc, uint32_t n_passes, uint32_t flags, mirt_buf* normal_hits,
                                        mirt_buf* albedo_depth);
+/* RAY QUERIES: the closest hit, or whether anything is hit at all, for `count` rays the CALLER supplies -- picking, autofocus, visibility between
+ * two points, ambient occlusion, baking.  rays[i] is a mirt_ray, used as given: d is not normalised, so t is in units of |d|, as the kernels
+ * treat Ray.d.  `scene` is a pass descriptor of which only struct_size and the primitive sets (spheres, triangles, meshes, n_meshes) are read;
+ * the image size, rays_per_pixel, tile, camera, lens, lights, material, seeds, acu, pixel, radiance, bounces and pass_index are ignored and free
+ * to be 0 or NULL.
+ * CLOSEST.  hits[i] is defined, bit for bit in every field, as what the kernel-by-kernel path leaves in Ray.maxt and Poi when
+ * Ray{o, d, mint, maxt} and a Poi reset as initTrace resets it (A10 code.cl:538-541: p = 0, normal = 0, matId = -1) run through sphereTrace,
+ * triangleTrace and every meshTrace in upload order (code.js:1809-1813): t is the final Ray.maxt; normal, p and mat_id are the final Poi.  A miss
+ * is (0, 0, 0, the input maxt, 0, 0, 0, -1); a dead ray (mint == maxt) is a miss.  mat_id is reported raw: no material is read, an id past the
+ * material table is the caller's to judge.  sets[i] (optional, uint32) is the index, in that stage order, of the set whose primitive won, or
+ * 0xFFFFFFFF: index 0 is the spheres when present, then the loose triangles, then the meshes.  The primitive's slot is not reported (in a grid a
+ * primitive has one slot per cell it touches, and which one wins is the walk's matter).  hits or sets may be NULL, not both.
+ * OCCLUDED.  occluded[i] (uint8) is sceneRender's own test (code.cl:1350): 1 iff mint == maxt after sphereShadowTrace, triangleShadowTrace and a
+ * triangleShadowTrace per mesh in upload order have run on the ray.  A ray that enters dead is therefore reported 1.  No t is delivered.
+ * CHECKS, all before anything is queued; nothing is written when one fails.  MIRT_E_ARG: a NULL descriptor or a wrong struct_size, count above
+ * 2^32 - 256, hits and sets both NULL (occluded NULL), an output whose bytes meet the rays', a geometry buffer's or the other output's, a call
+ * while capturing.  MIRT_E_RANGE: a buffer shorter than count records.  MIRT_E_DATA: a cell table that fails validation.  MIRT_E_HANDLE: a bad
+ * context or buffer.  count == 0 is MIRT_OK and queues nothing.  A held command stream (mirt_ctx_set_fusion, frame fusion) is flushed first;
+ * wrapped geometry is re-validated as for a pass.
+ * KERNELS.  One launch, one lane per ray (csrc/pt_kernels_rays.hip) -- by default the optimistic / exact pair PER RAY: a ray the ray-side guard
+ * refuses (mirt_debug_numerics op 28: every |d_k| in [2^-40, 2^40], every o_k zero or |o_k| in [2^-30, 2^20]) or whose grid walk defers is redone
+ * by the exact kernel; mirt_ctx_set_exact_only is honoured.  A caller's rays need not be coherent, and an axis-parallel direction (a zero
+ * component of d) is outside the guard: such batches run mostly in the exact kernel, with the same results.  mirt_trace_deferred: how many rays
+ * the last trace call re-ran in the exact kernel, counted when asked, like mirt_pass_deferred.  Rays are independent: a caller with N devices
+ * splits its batch.  MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
+typedef struct mirt_ray { float o[3]; float mint; float d[3]; float maxt; } mirt_ray;          /* 32 bytes */
+typedef struct mirt_hit { float normal[3]; float t; float p[3]; int32_t mat_id; } mirt_hit;   /* 32 bytes */
+MIRT_API int mirt_trace_closest(mirt_ctx* ctx, const mirt_pass_desc* scene, mirt_buf* rays, uint64_t count, mirt_buf* hits, mirt_buf* sets);
+MIRT_API int mirt_trace_occluded(mirt_ctx* ctx, const mirt_pass_desc* scene, mirt_buf* rays, uint64_t count, mirt_buf* occluded);
+MIRT_API int mirt_trace_deferred(mirt_ctx* ctx, uint64_t* rays);
 /* Edge-avoiding A-TROUS FILTER of a few-rays-per-pixel frame, guided by the first-hit guide buffers: `radiance` as a pass writes it (un-scaled
  * sums), `normal_hits` and `albedo_depth` as mirt_render_guides writes them, all float4 per pixel of a width x height image -- a whole frame, or a
  * gathered one.  Everything stays on the device; the working images live in the context's scratch buffer.

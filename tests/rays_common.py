@@ -1,0 +1,395 @@
+"""Shared by the ray-query tests (mirt_trace_closest, mirt_trace_occluded): a seeded generator of caller-supplied rays for the stratified random
+scenes of tests/random_scenes_common.py, and the CPU oracle's answer to them.
+
+Scenes: random_scenes_common.scene(stratum, seed, 37, 21, 4), one seed per stratum (SCENE_SEEDS) -- each stratum forces one build of the shared
+functions, and together they force the three GRIDS variants of k_traceRays.  The image size and the camera play no part in a ray query.
+
+Rays: N = 4096 + 37 per scene, 8 floats each {o.xyz, mint, d.xyz, maxt}, in EIGHT CLASSES, every one at least 5 % of N (SHARES; `classes` names
+each ray's), shuffled so that every wave holds a mix:
+  1 inside      an origin inside the scene box; the direction random, or -- two rays in three -- towards a point of a primitive from 0.05 in front
+                of or behind it (the reference's triangle test sees one side), the sets taken in turn so that every set of the scene wins a ray
+  2 axis        one or two zero components in d (outside the ray-side guard: |d_k| >= 2^-40)
+  3 away        an origin outside every set's box, pointing away from the scene
+  4 short       aimed at a primitive like class 1, with a maxt that ends half way to it
+  5 dead        mint == maxt
+  6 nonfinite   a NaN or an infinity in one component of o or d
+  7 face        an origin exactly on a face of one set's box (the coordinate IS the bound's float), pointing inwards, outwards or along the face
+  8 scaled      aimed like class 1, |d| from 2^-3 to 2^3: t comes back in units of |d|
+
+The oracle: the kernel calls a10_pass.run_pass's closest() and direct() make, without initTrace -- Ray{o, d, mint, maxt} and a Poi reset as
+initTrace resets it (p = 0, normal = 0, matId = -1), then sphereTrace, triangleTrace and every meshTrace in upload order; for occlusion
+sphereShadowTrace, triangleShadowTrace and a triangleShadowTrace per mesh.  `sets` comes from running the stages one at a time and noting the last
+one that changed Ray.maxt: the reference's test is a strict `<`, so a winner always changes it."""
+import numpy as np
+
+import a10_pass as A
+import random_scenes_common as S
+
+N_RAYS = 4096 + 37
+SCENE_SIZE = (37, 21, 4)
+# one seed per stratum, of the residue mod 3 that gives the stratum its most particular variant (random_scenes_common): the 97 / 96 / 95 single
+# cells, the tables that sum to exactly 4096 words, the single grid at n = 16, 18 sets with GRIDS 2, and the scaled pinhole's geometry
+SCENE_SEEDS = {"single_cell": 3001, "staged": 3003, "unstaged": 3006, "many_sets": 3010, "open": 1007, "guard": 3022}
+CLASSES = ("inside", "axis", "away", "short", "dead", "nonfinite", "face", "scaled")
+SHARES = {"inside": 0.27, "axis": 0.10, "away": 0.13, "short": 0.13, "dead": 0.07, "nonfinite": 0.07, "face": 0.08, "scaled": 0.15}
+NO_SET = 0xFFFFFFFF
+# the ray-side guard's windows (include/mirt.h, mirt_debug_numerics op 28)
+D_LO, D_HI, O_LO, O_HI = 2.0 ** -40, 2.0 ** 40, 2.0 ** -30, 2.0 ** 20
+
+_SCENES, _RAYS, _CLOSEST, _OCCLUDED = {}, {}, {}, {}
+
+
+def scene(stratum):
+    if stratum not in _SCENES:
+        _SCENES[stratum] = S.scene(stratum, SCENE_SEEDS[stratum], *SCENE_SIZE)
+    return _SCENES[stratum]
+
+
+# ---- the scene's sets, as the library numbers them ------------------------------------------------------------------------------------------
+def set_list(sc):
+    """[(kind, primitives, bounds8)] in stage order: the spheres when present, the loose triangles, the meshes.  primitives: spheres [n, 4]
+    (centre, r^2) or triangles [n, 3, 3]"""
+    out = []
+    if sc.has_spheres:
+        out.append(("spheres", np.asarray(sc.spheres, np.float64).reshape(-1, 4), np.asarray(sc.sphere_bounds, np.float64)))
+    if sc.has_triangles:
+        out.append(("triangles", np.asarray(sc.t_pos, np.float64).reshape(-1, 3, 4)[:, :, :3], np.asarray(sc.triangle_bounds, np.float64)))
+    for m in sc.meshes:
+        out.append(("triangles", np.asarray(m["pos"], np.float64).reshape(-1, 3, 4)[:, :, :3], np.asarray(m["bounds"], np.float64)))
+    return out
+
+
+def _unit(rng, n):
+    v = rng.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def _aimed(rng, sets, n, first=0):
+    """n rays (o, d unit, distance to the aimed point), each towards a point of a primitive from about 0.05 away, the sets in turn from `first`"""
+    o, d, dist = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
+    for i in range(n):
+        kind, prims, _ = sets[(first + i) % len(sets)]
+        k = int(rng.integers(0, len(prims)))
+        if kind == "spheres":
+            c, r = prims[k, :3], np.sqrt(prims[k, 3])
+            u = _unit(rng, 1)[0]
+            target, nrm = c + r * u, u
+        else:
+            p = prims[k]
+            w = rng.dirichlet((1.0, 1.0, 1.0))
+            target = w @ p
+            nrm = np.cross(p[1] - p[0], p[2] - p[0])
+            ln = np.linalg.norm(nrm)
+            nrm = nrm / ln if ln > 0 else _unit(rng, 1)[0]
+        side = 1.0 if (i // len(sets)) % 2 == 0 else -1.0      # both sides of every set in turn
+        oi = target + side * 0.05 * nrm + 0.02 * _unit(rng, 1)[0]
+        v = target - oi
+        dist[i] = np.linalg.norm(v)
+        o[i], d[i] = oi, v / dist[i]
+    return o, d, dist
+
+
+def make_rays(sc, seed=20250):
+    """-> (rays float32 [N_RAYS, 8], classes int [N_RAYS]: the index into CLASSES of each ray)"""
+    rng = np.random.default_rng(seed)
+    sets = set_list(sc)
+    lo, hi = np.asarray(sc.bounds, np.float64)[0:3], np.asarray(sc.bounds, np.float64)[4:7]
+    counts = {c: int(np.ceil(SHARES[c] * N_RAYS)) for c in CLASSES}
+    counts["scaled"] = N_RAYS - sum(v for c, v in counts.items() if c != "scaled")
+    parts, cls = [], []
+    inf = np.inf
+
+    def rec(o, d, mint, maxt):
+        n = len(o)
+        r = np.zeros((n, 8))
+        r[:, 0:3], r[:, 4:7] = o, d
+        r[:, 3], r[:, 7] = mint, maxt
+        return r
+
+    def inside(n):
+        return lo + rng.uniform(0.02, 0.98, size=(n, 3)) * (hi - lo)
+
+    # 1 inside
+    n = counts["inside"]
+    na = (2 * n) // 3
+    o, d, _ = _aimed(rng, sets, na)
+    r1 = np.concatenate([rec(o, d, 0.0, inf), rec(inside(n - na), _unit(rng, n - na), 0.0, inf)])
+    r1[::5, 3] = 0.25          # mint plays no part but in the dead test: some rays carry one
+    r1[1::7, 7] = 1000.0       # ... and some a large finite maxt
+    parts.append(r1)
+    # 2 axis
+    n = counts["axis"]
+    d = _unit(rng, n)
+    for i in range(n):
+        z = rng.permutation(3)[: 1 + (i % 2)]
+        d[i, z] = 0.0
+        if i % 6 == 0:
+            d[i, z[0]] = -0.0
+    parts.append(rec(inside(n), d, 0.0, inf))
+    # 3 away
+    n = counts["away"]
+    u = _unit(rng, n)
+    centre, ext = 0.5 * (lo + hi), np.linalg.norm(hi - lo)
+    parts.append(rec(centre + u * ext * rng.uniform(1.5, 4.0, size=(n, 1)), u, 0.0, inf))
+    # 4 short
+    n = counts["short"]
+    o, d, dist = _aimed(rng, sets, n, first=1)
+    parts.append(rec(o, d, 0.0, 0.5 * dist))
+    # 5 dead
+    n = counts["dead"]
+    t = rng.choice([0.0, 1.0, 0.375, inf, 1e-3], size=n)
+    o, d, _ = _aimed(rng, sets, n, first=2)
+    parts.append(rec(o, d, t, t))
+    # 6 nonfinite
+    n = counts["nonfinite"]
+    o, d, _ = _aimed(rng, sets, n, first=3)
+    r6 = rec(o, d, 0.0, inf)
+    for i in range(n):
+        r6[i, (0, 1, 2, 4, 5, 6)[int(rng.integers(0, 6))]] = (np.nan, inf, -inf)[i % 3]
+    parts.append(r6)
+    # 7 face
+    n = counts["face"]
+    o, d = np.zeros((n, 3)), _unit(rng, n)
+    for i in range(n):
+        b = sets[i % len(sets)][2]
+        blo, bhi = b[0:3], b[4:7]
+        o[i] = blo + rng.uniform(0.05, 0.95, size=3) * (bhi - blo)
+        ax, top = int(rng.integers(0, 3)), bool(rng.integers(0, 2))
+        o[i, ax] = bhi[ax] if top else blo[ax]          # the bound's own float: exactly on the face
+        inward = -1.0 if top else 1.0
+        k = (i // len(sets)) % 4                         # per set in turn: inwards twice, outwards, along the face
+        d[i, ax] = 0.0 if k == 3 else (inward if k < 2 else -inward) * abs(d[i, ax])
+    parts.append(rec(o, d, 0.0, inf))
+    # 8 scaled
+    n = counts["scaled"]
+    o, d, _ = _aimed(rng, sets, n, first=4)
+    d = d * (2.0 ** rng.uniform(-3.0, 3.0, size=(n, 1)))
+    parts.append(rec(o, d, 0.0, inf))
+
+    for k, p in enumerate(parts):
+        cls += [k] * len(p)
+    rays = np.concatenate(parts).astype(np.float32)   # (a face coordinate of class 7 is a float32 already: the narrowing keeps it)
+    order = rng.permutation(len(rays))
+    return np.ascontiguousarray(rays[order]), np.asarray(cls)[order]
+
+
+def rays_of(stratum):
+    if stratum not in _RAYS:
+        r, c = make_rays(scene(stratum))
+        r.setflags(write=False)
+        _RAYS[stratum] = (r, c)
+    return _RAYS[stratum]
+
+
+def live(rays):
+    """not dead when it enters: !(mint == maxt)"""
+    with np.errstate(invalid="ignore"):
+        return ~(rays[:, 3] == rays[:, 7])
+
+
+def guard_accepts(rays):
+    """the ray-side guard's rule, restated: every |d_k| in [2^-40, 2^40], every o_k zero or |o_k| in [2^-30, 2^20] (a NaN fails)"""
+    with np.errstate(invalid="ignore"):
+        o, d = np.abs(rays[:, 0:3].astype(np.float64)), np.abs(rays[:, 4:7].astype(np.float64))
+        return ((d >= D_LO) & (d <= D_HI)).all(axis=1) & ((o == 0) | ((o >= O_LO) & (o <= O_HI))).all(axis=1)
+
+
+# ---- the oracle -----------------------------------------------------------------------------------------------------------------------------
+def _ray_buffer(rays):
+    n = len(rays)
+    g1 = A._ceil(max(n, 1), A.WAVE)
+    buf = np.zeros(g1, A.RAY_DT)
+    buf["o"][:n], buf["mint"][:n], buf["d"][:n], buf["maxt"][:n] = rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7]
+    return buf, g1
+
+
+def _closest_stages(k, sc, n, rb, pb, g1):
+    """the calls of run_pass's closest(), one at a time"""
+    B = k.buf
+    if sc.has_spheres:
+        p, _k = A._f(sc.sphere_bounds)
+        yield lambda p=p: k.sphereTrace(n, B(pb), B(rb), B(sc.spheres), B(sc.s_matid), B(sc.s_box), p, sc.n_slabs, g1)
+    if sc.has_triangles:
+        p, _k = A._f(sc.triangle_bounds)
+        yield lambda p=p: k.triangleTrace(n, B(pb), B(rb), B(sc.t_pos), B(sc.t_normal), B(sc.t_matid), B(sc.t_box), p, sc.n_slabs, g1)
+    for m in sc.meshes:
+        p, _k = A._f(m["bounds"])
+        yield lambda p=p, m=m: k.meshTrace(n, B(pb), B(rb), B(m["pos"]), B(m["normal"]), B(m["box"]), m["matid"], p, m["nslabs"], g1)
+
+
+def expected_closest(sc, rays, k=None):
+    """-> (hits float32 [n, 8] with the material id's bits in column 7, sets uint32 [n])"""
+    k = k or A.load_oracle()
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    n = len(rays)
+    rb, g1 = _ray_buffer(rays)
+    pb = np.zeros(g1, A.POI_DT)
+    pb["matId"] = -1
+    sets = np.full(n, NO_SET, np.uint32)
+    for s, call in enumerate(_closest_stages(k, sc, n, rb, pb, g1)):
+        before = rb["maxt"][:n].copy().view(np.uint32)
+        call()
+        k.flush()
+        sets[rb["maxt"][:n].view(np.uint32) != before] = s
+    hits = np.zeros((n, 8), np.float32)
+    hits[:, 0:3], hits[:, 3], hits[:, 4:7] = pb["normal"][:n], rb["maxt"][:n], pb["p"][:n]
+    hits[:, 7] = pb["matId"][:n].astype(np.int32).view(np.float32)
+    return hits, sets
+
+
+def expected_occluded(sc, rays, k=None):
+    """-> uint8 [n]: 1 iff mint == maxt after the shadow kernels of run_pass's direct() have run on the ray"""
+    k = k or A.load_oracle()
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    n = len(rays)
+    rb, g1 = _ray_buffer(rays)
+    B = k.buf
+    if sc.has_spheres:
+        p, _k = A._f(sc.sphere_bounds)
+        k.sphereShadowTrace(n, B(rb), B(sc.spheres), B(sc.s_box), p, sc.n_slabs, g1)
+    if sc.has_triangles:
+        p, _k = A._f(sc.triangle_bounds)
+        k.triangleShadowTrace(n, B(rb), B(sc.t_pos), B(sc.t_box), p, sc.n_slabs, g1)
+    for m in sc.meshes:
+        p, _k = A._f(m["bounds"])
+        k.triangleShadowTrace(n, B(rb), B(m["pos"]), B(m["box"]), p, m["nslabs"], g1)
+    k.flush()
+    with np.errstate(invalid="ignore"):
+        return (rb["mint"][:n] == rb["maxt"][:n]).astype(np.uint8)
+
+
+def closest_of(stratum):
+    if stratum not in _CLOSEST:
+        out = expected_closest(scene(stratum), rays_of(stratum)[0])
+        for a in out:
+            a.setflags(write=False)
+        _CLOSEST[stratum] = out
+    return _CLOSEST[stratum]
+
+
+def occluded_of(stratum):
+    if stratum not in _OCCLUDED:
+        out = expected_occluded(scene(stratum), rays_of(stratum)[0])
+        out.setflags(write=False)
+        _OCCLUDED[stratum] = out
+    return _OCCLUDED[stratum]
+
+
+# ---- the library ----------------------------------------------------------------------------------------------------------------------------
+class Tracer:
+    """one scene on one context, with ray and output buffers of `cap` rays each followed by `tail` sentinel bytes"""
+    SENTINEL = 0xA7
+
+    def __init__(self, ctx, sc, cap=N_RAYS, tail=64):
+        from raytracing_amd.pyhost import mirt
+        self.ctx, self.cap, self.tail = ctx, cap, tail
+        self.dev = mirt.DeviceScene(ctx, sc)
+        self.desc = self.dev.pass_desc(None, None)
+        self.rays = ctx.buffer(max(cap * 32, 16))
+        self.hits, self.sets, self.occ = ctx.buffer(cap * 32 + tail), ctx.buffer(cap * 4 + tail), ctx.buffer(cap + tail)
+
+    def fill(self):
+        for b in (self.hits, self.sets, self.occ):
+            b.write(np.full(b.nbytes, self.SENTINEL, np.uint8))
+
+    def closest(self, rays, hits=True, sets=True):
+        """-> (hits [n, 8] or None, sets [n] or None, (the bytes behind the n hit records, those behind the n set words): the whole buffer for
+        an output that was not asked for)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(rays)
+        self.fill()
+        if n:
+            self.rays.write(rays)
+        self.ctx.trace_closest(self.desc, self.rays, n, self.hits if hits else None, self.sets if sets else None)
+        h, s = self.hits.read(np.uint8), self.sets.read(np.uint8)
+        return (h[:n * 32].view(np.float32).reshape(-1, 8) if hits else None, s[:n * 4].view(np.uint32) if sets else None,
+                (h[n * 32:] if hits else h, s[n * 4:] if sets else s))
+
+    def occluded(self, rays):
+        """-> (occluded uint8 [n], the bytes behind them)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(rays)
+        self.fill()
+        if n:
+            self.rays.write(rays)
+        self.ctx.trace_occluded(self.desc, self.rays, n, self.occ)
+        o = self.occ.read(np.uint8)
+        return o[:n], o[n:]
+
+    def release(self):
+        for b in (self.rays, self.hits, self.sets, self.occ):
+            b.release()
+        self.dev.release()
+
+
+def kernel_by_kernel(ctx, dev, sc, rays):
+    """The library's own kernel-by-kernel path on the same rays: a 48-byte Ray / 64-byte Poi buffer filled here, then the mirt_enqueue sequence
+    GranularRenderer._closest issues (the sets' maxt read back between the stages, for `sets`), and the shadow kernels of ._direct on a second
+    copy of the rays.  dev: a mirt.DeviceScene of `ctx`.  -> (hits [n, 8], sets [n], occluded [n])"""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    n = len(rays)
+    rb, g1 = _ray_buffer(rays)
+    pb = np.zeros(g1, A.POI_DT)
+    pb["matId"] = -1
+    u32 = lambda v: np.array([v], np.uint32)
+    rbuf, pbuf, sbuf = ctx.buffer(rb.nbytes).write(rb), ctx.buffer(pb.nbytes).write(pb), ctx.buffer(rb.nbytes).write(rb)
+    ks = []
+
+    def kernel(name, *args):
+        k = ctx.kernel(name).set_args(*args)
+        ks.append(k)
+        return k
+    try:
+        stages = []
+        if sc.has_spheres:
+            stages.append(kernel("sphereTrace", u32(n), pbuf, rbuf, dev.sph["prims"], dev.sph["matid"], dev.sph["off"], sc.sphere_bounds, u32(sc.n_slabs)))
+        if sc.has_triangles:
+            stages.append(kernel("triangleTrace", u32(n), pbuf, rbuf, dev.tri["prims"], dev.tri["normals"], dev.tri["matid"], dev.tri["off"],
+                                 sc.triangle_bounds, u32(sc.n_slabs)))
+        for m in dev.meshes:
+            stages.append(kernel("meshTrace", u32(n), pbuf, rbuf, m["prims"], m["normals"], m["off"], u32(m["matid"]), m["bounds"], u32(m["n"])))
+        sets = np.full(n, NO_SET, np.uint32)
+        before = rb["maxt"][:n].copy().view(np.uint32)
+        for s, k in enumerate(stages):
+            k.enqueue([g1], [64])
+            after = rbuf.read(np.uint8).view(A.RAY_DT)["maxt"][:n].copy().view(np.uint32)
+            sets[after != before] = s
+            before = after
+        r, p = rbuf.read(np.uint8).view(A.RAY_DT), pbuf.read(np.uint8).view(A.POI_DT)
+        hits = np.zeros((n, 8), np.float32)
+        hits[:, 0:3], hits[:, 3], hits[:, 4:7] = p["normal"][:n], r["maxt"][:n], p["p"][:n]
+        hits[:, 7] = p["matId"][:n].astype(np.int32).view(np.float32)
+        if sc.has_spheres:
+            kernel("sphereShadowTrace", u32(n), sbuf, dev.sph["prims"], dev.sph["off"], sc.sphere_bounds, u32(sc.n_slabs)).enqueue([g1], [64])
+        if sc.has_triangles:
+            kernel("triangleShadowTrace", u32(n), sbuf, dev.tri["prims"], dev.tri["off"], sc.triangle_bounds, u32(sc.n_slabs)).enqueue([g1], [64])
+        for m in dev.meshes:
+            kernel("triangleShadowTrace", u32(n), sbuf, m["prims"], m["off"], m["bounds"], u32(m["n"])).enqueue([g1], [64])
+        sh = sbuf.read(np.uint8).view(A.RAY_DT)
+        with np.errstate(invalid="ignore"):
+            occluded = (sh["mint"][:n] == sh["maxt"][:n]).astype(np.uint8)
+        return hits, sets, occluded
+    finally:
+        for k in ks:
+            k.release()
+        for b in (rbuf, pbuf, sbuf):
+            b.release()
+
+
+def untouched(tail):
+    return bool((np.asarray(tail) == Tracer.SENTINEL).all())
+
+
+def hits_differ(tag, got, want):
+    """None when the records are equal bit for bit (every NaN equal to every NaN; the material id compared as an integer), else a sentence"""
+    from conftest import bits
+    g, w = np.ascontiguousarray(got, np.float32).reshape(-1, 8), np.ascontiguousarray(want, np.float32).reshape(-1, 8)
+    if g.shape != w.shape:
+        return f"{tag}: {g.shape[0]} records against {w.shape[0]}"
+    gb, wb = bits(g[:, :7].copy()), bits(w[:, :7].copy())
+    gi, wi = g[:, 7].copy().view(np.int32), w[:, 7].copy().view(np.int32)
+    bad = np.flatnonzero((gb != wb).any(axis=1) | (gi != wi))
+    if bad.size == 0:
+        return None
+    i = int(bad[0])
+    return f"{tag}: {bad.size} of {len(g)} records differ; first is ray {i}: got {g[i, :7].tolist()} id {int(gi[i])}, want {w[i, :7].tolist()} id {int(wi[i])}"
