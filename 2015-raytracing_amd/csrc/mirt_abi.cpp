@@ -79,7 +79,6 @@ struct mirt_ctx {
     uint32_t ray_defer_words = 0; // mask words the last trace call used (0: it ran the exact kernel only, or queued nothing)
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
-    float res_m_override = NAN;        // try_fuse_pass -> render_pass_impl: the tone factor of the recorded copyToPixel, as the host passed it
     int force_exact = 0;          // mirt_ctx_set_exact_only: 1 = skip the optimistic kernel, run every sample through the exact one
     bool profiling = false;       // per-kernel events inside mirt_render_pass
     hipEvent_t pe[3] = {nullptr, nullptr, nullptr};
@@ -261,6 +260,26 @@ int ensure_scratch(mirt_ctx* ctx, size_t bytes) {
     HIPCHK(ctx, hipMalloc(&ctx->scratch, bytes));
     ctx->scratch_bytes = bytes;
     return MIRT_OK;
+}
+
+// The bit mask of an optimistic / exact pair (the pass's, the guides', the ray queries': an allocation of the context each): grown to need_bytes
+// where it is smaller, and those bytes cleared on the stream, ahead of the pair.
+int grow_and_clear(mirt_ctx* ctx, void*& ptr, size_t& have, size_t need_bytes) {
+    if (have < need_bytes) {
+        if (ptr) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ptr)); ptr = nullptr; have = 0; }
+        HIPCHK(ctx, hipMalloc(&ptr, need_bytes));
+        have = need_bytes;
+    }
+    HIPCHK(ctx, hipMemsetAsync(ptr, 0, need_bytes, ctx->stream));
+    return MIRT_OK;
+}
+
+// The device ranges of a descriptor's geometry, each buffer whole: what an output of a call on it must not meet (pt_post_check.hpp post_alias)
+void add_range(std::vector<pt::PostRange>& in, const mirt_buf* b) { if (b && live_has(b)) in.push_back({(uint64_t)(uintptr_t)b->ptr, (uint64_t)b->bytes, true}); }
+void add_geometry_ranges(std::vector<pt::PostRange>& in, const mirt_pass_desc* d) {
+    const auto add_grid = [&in](const mirt_grid* g) { if (g) { add_range(in, g->prims); add_range(in, g->normals); add_range(in, g->matid); add_range(in, g->cell_offsets); } };
+    add_grid(d->spheres); add_grid(d->triangles);
+    for (uint32_t m = 0; m < d->n_meshes; ++m) add_grid(&d->meshes[m]);
 }
 
 // release paths shared by the public entry points and by mirt_ctx_destroy's reaping of leftovers
@@ -862,6 +881,7 @@ struct PassOpts {
     // queues the guide launches behind its last (GUIDES_BEHIND).
     enum GuideMode { GUIDES_FIRST_PASS, GUIDES_PASSES, GUIDES_BEHIND, GUIDES_CHECK_ONLY } guide_mode = GUIDES_FIRST_PASS;
     const char* guide_fn = "mirt_render_first_pass_guided";   // the entry point its messages name
+    float tone = NAN;   // try_fuse_pass: the tone factor of the recorded copyToPixel, as the host passed it (one pass).  NaN: computed from the pass index
 };
 static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOpts& o);
 static int launch_kernel(mirt_ctx* ctx, const KernelSpec& S, std::vector<KArg>& a, unsigned dim, const size_t* global);
@@ -913,9 +933,9 @@ static int try_fuse_pass(mirt_ctx* ctx, const std::vector<Enqueue>& P) {
     // the recorded copyToPixel goes into the pass where the pass can resolve its own pixels (whole pixels per block of 256 ray ids): its pixel buffer and
     // its factor as the host passed it; where it cannot, render_pass_impl queues the separate kernel behind the pass, with that factor
     d.pixel = m.pixel;
-    ctx->res_m_override = m.tone;
-    int rc = render_pass_impl(ctx, &d, PassOpts{});
-    ctx->res_m_override = NAN;
+    PassOpts o;
+    o.tone = m.tone;
+    const int rc = render_pass_impl(ctx, &d, o);
     if (rc && rc != MIRT_E_DEVICE) return 1;   // refused before anything was launched (a size, a grid that fails validation ...): run the stream as issued,
     if (rc) return rc;                          // whose own checks then report it against the kernel that trips it
     m.pixel->version++;   // (written by the pass itself, or by the copyToPixel render_pass_impl queued behind it with the recorded factor)
@@ -1322,13 +1342,8 @@ static int queue_guides(mirt_ctx* ctx, const pt::FusedArgs& A, void* nh, void* a
     const uint64_t npix = (uint64_t)A.nrows * A.width;
     const bool optimistic = pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A);
     if (optimistic) {
-        const size_t need_bytes = (size_t)((npix + 31u) / 32u) * 4u;
-        if (ctx->guide_mask_bytes < need_bytes) {
-            if (ctx->guide_mask) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->guide_mask)); ctx->guide_mask = nullptr; ctx->guide_mask_bytes = 0; }
-            HIPCHK(ctx, hipMalloc(&ctx->guide_mask, need_bytes));
-            ctx->guide_mask_bytes = need_bytes;
-        }
-        HIPCHK(ctx, hipMemsetAsync(ctx->guide_mask, 0, need_bytes, ctx->stream));
+        const int rc = grow_and_clear(ctx, ctx->guide_mask, ctx->guide_mask_bytes, (size_t)((npix + 31u) / 32u) * 4u);
+        if (rc) return rc;
         pt::launch_guides(ctx->stream, A, true, nh, ad, (uint32_t*)ctx->guide_mask, nullptr);
         pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, (const uint32_t*)ctx->guide_mask);
     } else {
@@ -1345,11 +1360,8 @@ static int guided_check_buffers(mirt_ctx* ctx, const char* fn, const mirt_pass_d
     if (nh && (rc = need(ctx, nh_name.c_str(), nh, npix * 16))) return rc;
     if (ad && (rc = need(ctx, ad_name.c_str(), ad, npix * 16))) return rc;
     std::vector<pt::PostRange> in;
-    const auto add = [&in](const mirt_buf* b) { if (b && live_has(b)) in.push_back({(uint64_t)(uintptr_t)b->ptr, (uint64_t)b->bytes, true}); };
-    const auto add_grid = [&add](const mirt_grid* g) { if (g) { add(g->prims); add(g->normals); add(g->matid); add(g->cell_offsets); } };
-    add(d->seeds); add(d->acu); add(d->pixel); add(d->radiance); add(d->material);
-    add_grid(d->spheres); add_grid(d->triangles);
-    for (uint32_t m = 0; m < d->n_meshes; ++m) add_grid(&d->meshes[m]);
+    for (const mirt_buf* b : {d->seeds, d->acu, d->pixel, d->radiance, d->material}) add_range(in, b);
+    add_geometry_ranges(in, d);
     const pt::PostRange out[2] = {{nh ? (uint64_t)(uintptr_t)nh->ptr : 0u, npix * 16, nh != nullptr}, {ad ? (uint64_t)(uintptr_t)ad->ptr : 0u, npix * 16, ad != nullptr}};
     const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 2);
     if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: a guide buffer aliases a buffer of the descriptor", fn);
@@ -1370,8 +1382,7 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
     A.fresh = o.fresh ? 1u : 0u;
     A.passes = o.passes;
     // the frame after the last pass: 1 / (rpp * passes so far), A10 code.js:1412 -- or the recorded copyToPixel's own factor, which try_fuse_pass hands over (not a NaN)
-    const float res_m = o.passes == 1u && ctx->res_m_override == ctx->res_m_override ? ctx->res_m_override
-                                                                                     : (float)(1.0 / ((double)d->rays_per_pixel * ((double)d->pass_index + (double)(o.passes - 1u))));
+    const float res_m = o.passes == 1u && o.tone == o.tone ? o.tone : (float)(1.0 / ((double)d->rays_per_pixel * ((double)d->pass_index + (double)(o.passes - 1u))));
     if ((rc = need(ctx, "seeds", d->seeds, nrays * 4))) return rc;
     // what is launched, worked out once (pt_pass_plan.hpp): whether the pass resolves its own pixels -- then, and only then, `acu` is optional --
     // its segments, the mask and the scratch buffer
@@ -1431,16 +1442,13 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
         // the second launch walks the first one's bit mask on the device, so the pair is queued without a host round trip
         // one bit per sample -- or, resolving in the pass, per block of 256 samples (pt_kernels_fused.hip)
         const size_t need_bytes = 16 + (size_t)plan.mask_words * 4;
-        if (ctx->defer_bytes < need_bytes) {
+        if (ctx->defer_bytes < need_bytes) {   // a recording holds the mask's address: it cannot grow inside one, and a graph recorded before is stale
             NOT_WHILE_CAPTURING(ctx, "growing the deferred-sample mask");
-            if (ctx->defer) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->defer)); ctx->defer = nullptr; ctx->defer_bytes = 0; }
             ctx->defer_gen++;
-            HIPCHK(ctx, hipMalloc(&ctx->defer, need_bytes));
-            ctx->defer_bytes = need_bytes;
         }
         if (ctx->capturing) ctx->cap_defer = true;
+        if ((rc = grow_and_clear(ctx, ctx->defer, ctx->defer_bytes, need_bytes))) return rc;
         mask = (uint32_t*)ctx->defer + 4;
-        HIPCHK(ctx, hipMemsetAsync(ctx->defer, 0, need_bytes, ctx->stream));
     }
     // One launch -- optimistic: one pair of launches -- per segment of the plan, in ray order, each on its own region of the mask; the redo launch of
     // a segment runs before the next segment's launches read the sums it leaves (stream order).  A pass that does not resolve is one segment.
@@ -1621,10 +1629,7 @@ static int trace_impl(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, mi
     {   // an output is read by nobody and no input is written: the bytes the call touches, and the geometry's buffers whole
         std::vector<pt::PostRange> in;
         in.push_back({(uint64_t)(uintptr_t)rays->ptr, count * 32, true});
-        const auto add = [&in](const mirt_buf* b) { if (b && live_has(b)) in.push_back({(uint64_t)(uintptr_t)b->ptr, (uint64_t)b->bytes, true}); };
-        const auto add_grid = [&add](const mirt_grid* g) { if (g) { add(g->prims); add(g->normals); add(g->matid); add(g->cell_offsets); } };
-        add_grid(d->spheres); add_grid(d->triangles);
-        for (uint32_t m = 0; m < d->n_meshes; ++m) add_grid(&d->meshes[m]);
+        add_geometry_ranges(in, d);
         pt::PostRange out[3];
         for (int i = 0; i < 3; ++i) out[i] = {io[i + 1].buf ? (uint64_t)(uintptr_t)io[i + 1].buf->ptr : 0u, io[i + 1].bytes, io[i + 1].buf != nullptr};
         const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 3);
@@ -1642,14 +1647,8 @@ static int trace_impl(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, mi
     ctx->ray_defer_words = 0;
     if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
         const uint32_t words = (uint32_t)((count + 31u) / 32u);
-        const size_t need_bytes = 16u + (size_t)words * 4u;
-        if (ctx->ray_defer_bytes < need_bytes) {
-            if (ctx->ray_defer) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->ray_defer)); ctx->ray_defer = nullptr; ctx->ray_defer_bytes = 0; }
-            HIPCHK(ctx, hipMalloc(&ctx->ray_defer, need_bytes));
-            ctx->ray_defer_bytes = need_bytes;
-        }
+        if ((rc = grow_and_clear(ctx, ctx->ray_defer, ctx->ray_defer_bytes, 16u + (size_t)words * 4u))) return rc;
         uint32_t* const mask = (uint32_t*)ctx->ray_defer + 4;
-        HIPCHK(ctx, hipMemsetAsync(ctx->ray_defer, 0, need_bytes, ctx->stream));
         pt::launch_rays(ctx->stream, A, true, rays->ptr, (uint32_t)count, hp, sp, op, mask, nullptr);
         pt::launch_rays(ctx->stream, A, false, rays->ptr, (uint32_t)count, hp, sp, op, nullptr, mask);
         ctx->ray_defer_words = words;

@@ -1,7 +1,10 @@
-// pt_closest.hpp -- what the fused pass (pt_kernels_fused.hip) and the guide-buffer kernel (pt_kernels_guides.hip) share: the block prologue
-// (staged single-cell sets and cell tables, the lens table), the primary ray, the closest-hit query over every set, and the LDS slots a launch
-// gives the sets.  Moved here verbatim from pt_kernels_fused.hip, so that both files run the same instructions on the same operands.
+// pt_closest.hpp -- what the fused pass (pt_kernels_fused.hip), the guide-buffer kernel (pt_kernels_guides.hip) and the ray queries
+// (pt_kernels_rays.hip) share: the block prologue (staged single-cell sets and cell tables, the lens table), the primary ray, the closest-hit
+// query over every set -- the ONE definition of that loop: each kernel adds what is its own through ClosestHooks -- and the LDS slots a launch
+// gives the sets, with the kernel instance they call for.  Moved here verbatim from pt_kernels_fused.hip, so that all three files run the same
+// instructions on the same operands.
 #pragma once
+#include <type_traits>
 #include "pt_trace_coop.hpp"
 
 #ifndef PT_AABB_UNSIGNED_ZERO
@@ -42,14 +45,29 @@ namespace pt {
 PT_DEV Box set_box(const GridArgs& S) { return set_box_of(S); }
 
 
+// What a kernel adds to closest_all's loop: four members, called where the loop names them.
+//   guard   optimistic kernel only, once, ahead of the ray's reciprocals: asks the ray-side guard and notes a refusal in `defer`
+//   top     at the head of every trip of the loop over the sets
+//   won     set s has just delivered the closest hit so far
+//   put_pn  (kernels that park p and n: PT_PARK_PN_FOR) the vertex as the trip leaves it
+// These are the camera kernels': k_guides takes them as they stand, the pass's Park (pt_kernels_fused.hip) replaces put_pn, and k_traceRays
+// (pt_kernels_rays.hip RayHooks) the other three.
+struct ClosestHooks {
+    PT_DEV void guard(Ray& ray, bool& defer) const { if (!(ray.mint == ray.maxt)) defer = defer || !ray_guard(ray); }   // a dead ray divides nothing
+    PT_DEV void top(Ray&) const {}
+    PT_DEV void won(uint32_t) const {}
+    PT_DEV void put_pn(const Poi&) const {}
+};
+
 // closest hit over every set in upload order, z-buffered through ray.maxt
 // (A10 code.cl:675-800, 802-935, 937-1070; order A10 code.js:1809-1813)
-template <bool FAST, int GRIDS, class PARK>
-PT_DEV void closest_all(const FusedArgs& A, Ray& ray, Poi& poi, const PARK& park, bool& defer) {
-    if (FAST && !(ray.mint == ray.maxt)) defer = defer || !ray_guard(ray);   // a dead ray divides nothing
+template <bool FAST, int GRIDS, class HOOKS>
+PT_DEV void closest_all(const FusedArgs& A, Ray& ray, Poi& poi, const HOOKS& hooks, bool& defer) {
+    if (FAST) hooks.guard(ray, defer);
     const RayRcp rr = ray_rcp<FAST>(ray);
     for (uint32_t s = 0; s < A.n_sets; ++s) {
         const GridArgs& S = A.sets[s];
+        hooks.top(ray);
         const bool live = !(ray.mint == ray.maxt);
         Hit ch;
         ch.idx = UINT32_MAX;
@@ -68,6 +86,7 @@ PT_DEV void closest_all(const FusedArgs& A, Ray& ray, Poi& poi, const PARK& park
             if (bh.v) ch = trace_dda<SPHERES, false, TRI_A10, FAST, GRIDS == 1>(ray, bh, S, defer);
         }
         if (ch.idx == UINT32_MAX) continue;
+        hooks.won(s);
         ray.maxt = ch.t;
         poi.p = fma3(ch.t, ray.d, ray.o);   // getPoint, code.cl:87
         if (S.kind == KIND_SPHERES) {
@@ -89,7 +108,7 @@ PT_DEV void closest_all(const FusedArgs& A, Ray& ray, Poi& poi, const PARK& park
             }
         }
 #if PT_PARK_LDS
-        if (PT_PARK_PN_FOR(GRIDS)) park.put_pn(poi);
+        if (PT_PARK_PN_FOR(GRIDS)) hooks.put_pn(poi);
 #endif
     }
 }
@@ -194,8 +213,8 @@ PT_DEV Ray primary_ray(const FusedArgs& A, uint32_t lid) {
 }
 
 // The LDS slots of a launch (GridArgs::lds_off of every set of `b`) and the dynamic LDS its kernel asks for: `lds` with the cell tables staged
-// (GRIDS == 1), `lds2` without (GRIDS == 2), `lds_tri` for a scene without grids (GRIDS == 0).  launch_fused and launch_guides both call it, so a
-// set is staged for the guide kernel exactly where it is staged for the pass.
+// (GRIDS == 1), `lds2` without (GRIDS == 2), `lds_tri` for a scene without grids (GRIDS == 0).  launch_fused, launch_guides and launch_rays all call it, so
+// a set is staged for the guide and ray kernels exactly where it is staged for the pass.
 struct FusedLds { bool grids, staged; size_t lds_tri, lds2, lds; };
 inline FusedLds fused_lds_slots(FusedArgs& b, bool fast) {
     bool grids = false;
@@ -228,6 +247,13 @@ inline FusedLds fused_lds_slots(FusedArgs& b, bool fast) {
     const size_t lds_tri = tri_words ? (size_t)(tri_base4 - tri_base + tri_words) * 4u : 0u;
     const size_t lds2 = (size_t)kCoopWordsPerBlock * 4u + lds_tri, lds = (size_t)kCoopWordsPerBlock * 4u + (staged ? (size_t)used * 4u : 0u) + lds_tri;
     return FusedLds{grids, staged, lds_tri, lds2, lds};
+}
+// ... and the kernel those slots call for: launch(std::integral_constant<int, GRIDS>, the dynamic LDS bytes of that GRIDS)
+template <class LAUNCH>
+inline void fused_lds_dispatch(const FusedLds& L, const LAUNCH& launch) {
+    if (L.grids && L.staged) launch(std::integral_constant<int, 1>{}, L.lds);
+    else if (L.grids) launch(std::integral_constant<int, 2>{}, L.lds2);
+    else launch(std::integral_constant<int, 0>{}, L.lds_tri);
 }
 
 }  // namespace pt

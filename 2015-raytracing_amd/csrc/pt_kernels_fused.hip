@@ -154,9 +154,9 @@ __global__ void __launch_bounds__(64) k_planeList(const float4* prep, uint32_t c
 }
 
 // STRIDE: words between the rows of one lane's record ([word][lane] rows of 256 lanes in k_fusedPass).  ATTE_LDS: the attenuation is
-// parked too (else it stays in registers and the p / n rows move up).
+// parked too (else it stays in registers and the p / n rows move up).  As closest_all's hooks (pt_closest.hpp) it adds put_pn alone.
 template <int STRIDE, bool ATTE_LDS>
-struct ParkT {
+struct ParkT : ClosestHooks {
     static constexpr bool kAtteLds = ATTE_LDS;
     static constexpr int kP = ATTE_LDS ? 7 : 4, kN = kP + 3;
     float* base;   // the lane's word 0
@@ -207,6 +207,8 @@ PT_DEV void direct_all(const FusedArgs& A, Poi& poi, int32_t& seed, float4& acc,
 #endif
         }
         const RayRcp rr = ray_rcp<FAST>(sh);
+        // (this loop is stated a second time, as rays_any in pt_kernels_rays.hip, and the two are kept in step by hand: no shared form left this
+        // kernel's assembly as it is -- profiles/shared_loops/README.md)
         for (uint32_t s = 0; s < A.n_sets; ++s) {
             const GridArgs& S = A.sets[s];
             const bool live = path && !dark && !(sh.mint == sh.maxt);

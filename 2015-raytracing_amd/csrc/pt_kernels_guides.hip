@@ -13,8 +13,9 @@
 // each a sequential fp32 sum from +0 over the HIT samples in sample order, un-normalised like `radiance`.  The guides describe SURFACES: an
 // emitter in front of the surface (lightRender, code.cl:600-629, kills such a ray afterwards) is not considered.
 //
-// The bits are the fused pass's by construction: primary_ray, stage_block and closest_all are the pass's own functions (pt_closest.hpp), the sets
-// get the LDS slots the pass gives them (fused_lds_slots), and the optimistic / exact pair is the pass's -- here per PIXEL: a pixel one of whose
+// The bits are the fused pass's by construction: primary_ray, stage_block and closest_all are the pass's own functions (pt_closest.hpp; the loop over
+// the sets is defined there once, and this kernel adds nothing to it: ClosestHooks as they stand), the sets get the LDS slots the pass gives them
+// and the kernel instance those call for (fused_lds_slots, fused_lds_dispatch), and the optimistic / exact pair is the pass's -- here per PIXEL: a pixel one of whose
 // samples left the guard windows sets its bit and writes nothing, the exact kernel redoes the marked pixels whole.
 //
 // Structure: one lane per pixel, walking its samples in order.  Every k x k count works the same way -- no segment plan, no carried sums, no
@@ -23,10 +24,6 @@
 #include "pt_closest.hpp"
 
 namespace pt {
-
-struct NoPark {   // closest_all parks the vertex for the pass's shadow stage: nothing comes after it here
-    PT_DEV void put_pn(const Poi&) const {}
-};
 
 // redo_mask (exact kernel only): a bit per pixel of the tile, the pixels the optimistic kernel handed over; null: every pixel.
 // GRIDS: the walk shares its tests across the wave (pt_trace_coop.hpp), so a lane without a pixel of its own rides along and writes nothing.
@@ -51,7 +48,7 @@ __global__ void __launch_bounds__(256) k_guides(const FusedArgs A, float4* norma
         poi.n = mk3(0.0f, 0.0f, 0.0f);
         poi.atte = mk3(1.0f, 1.0f, 1.0f);
         poi.matId = -1;
-        closest_all<FAST, GRIDS, NoPark>(A, ray, poi, NoPark{}, defer);
+        closest_all<FAST, GRIDS>(A, ray, poi, ClosestHooks{}, defer);   // the pass parks the vertex for its shadow stage: nothing comes after it here
         if (poi.matId < 0 || (uint32_t)poi.matId >= A.nmat) continue;
         const float4 c = material[poi.matId];
         nx += poi.n.x; ny += poi.n.y; nz += poi.n.z; hits += 1.0f;
@@ -69,9 +66,7 @@ __global__ void __launch_bounds__(256) k_guides(const FusedArgs A, float4* norma
 template <bool FAST>
 static void launch_guides_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, float4* nh, float4* ad, uint32_t* defer_mask, const uint32_t* redo_mask) {
     const dim3 grid((unsigned)(((uint64_t)b.nrows * b.width + 255u) / 256u));
-    if (L.grids && L.staged) hipLaunchKernelGGL((k_guides<FAST, 1>), grid, dim3(256), L.lds, s, b, nh, ad, defer_mask, redo_mask);
-    else if (L.grids) hipLaunchKernelGGL((k_guides<FAST, 2>), grid, dim3(256), L.lds2, s, b, nh, ad, defer_mask, redo_mask);
-    else hipLaunchKernelGGL((k_guides<FAST, 0>), grid, dim3(256), L.lds_tri, s, b, nh, ad, defer_mask, redo_mask);
+    fused_lds_dispatch(L, [&](auto G, size_t lds) { hipLaunchKernelGGL((k_guides<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, nh, ad, defer_mask, redo_mask); });
 }
 // fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
 // of redo_mask, or over every pixel when it is null.  Either output may be null.

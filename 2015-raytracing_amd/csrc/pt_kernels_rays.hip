@@ -11,12 +11,12 @@
 //             triangleShadowTrace per mesh have run on the ray in that order -- a ray that enters dead is reported 1.  No t is delivered, so the
 //             sets run the fused pass's cheap any-hit forms (COOP_ANY, the blocked-flag cell loops).
 //
-// The bits are the fused pass's: stage_block, the per-set calls and their template arguments are those of closest_all (pt_closest.hpp) and of
-// the shadow stage of direct_all (pt_kernels_fused.hip), the sets get the LDS slots the pass gives them (fused_lds_slots), and the optimistic /
-// exact pair is the pass's -- here per RAY: a ray the ray-side guard refuses, or whose walk defers, sets its bit and writes nothing, and the exact
-// kernel redoes the marked rays.  Both set loops are RESTATED here, not shared: closest_all has no way to say which set won (`sets`), the shadow
-// loop lives inside direct_all between the shadow ray's construction and the shading, and neither file is touched by this one -- their kernels'
-// resource reports stay the parent's line for line (profiles/rays/kernel_resources.txt).  One shared definition of each loop is a refactor of its own.
+// The bits are the fused pass's: stage_block and the closest-hit loop are the pass's own functions (pt_closest.hpp: closest_all, to which this
+// kernel adds its guard and the winning set's index through RayHooks), the sets get the LDS slots the pass gives them and the kernel instance
+// those call for (fused_lds_slots, fused_lds_dispatch), and the optimistic / exact pair is the pass's -- here per RAY: a ray the ray-side guard
+// refuses, or whose walk defers, sets its bit and writes nothing, and the exact kernel redoes the marked rays.
+// The any-hit loop (rays_any) is still stated twice, here and in the shadow stage of direct_all (pt_kernels_fused.hip): every shared form that was
+// tried re-allocated registers in k_fusedPass, whose rule is identical assembly (profiles/shared_loops/README.md).  A change to one is a change to both.
 //
 // Structure: one lane per ray, two float4 loads, the query, two float4 stores (and the optional uint32), or one byte.  With grids every lane of a
 // wave enters the shared-test walk (pt_trace_coop.hpp): a lane without a ray, and a redo kernel's unmarked lane, rides along as a dead ray and
@@ -51,54 +51,17 @@ PT_DEV void guard_or_retire(Ray& r, bool& defer) {
     r.maxt = 0.0f;
 }
 
-// closest_all's loop (pt_closest.hpp), with the index of the last set that won noted in `won`
-template <bool FAST, int GRIDS>
-PT_DEV void rays_closest(const FusedArgs& A, Ray& ray, Poi& poi, uint32_t& won, bool& defer) {
-    if (FAST) guard_or_retire(ray, defer);
-    const RayRcp rr = ray_rcp<FAST>(ray);
-    for (uint32_t s = 0; s < A.n_sets; ++s) {
-        const GridArgs& S = A.sets[s];
-        keep_in_loop(ray);
-        const bool live = !(ray.mint == ray.maxt);
-        Hit ch;
-        ch.idx = UINT32_MAX;
-        if (!GRIDS || S.n == 1u) {
-            if (live) {
-                const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(ray, rr, set_box(S));
-                if (bh.v) ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, false, TRI_A10, FAST>(ray, rr, bh, S) : trace_cell1<TRIANGLES, false, TRI_A10, FAST, false, PT_LANE_LISTS_FOR(FAST, GRIDS)>(ray, rr, bh, S);
-            }
-        } else if (S.kind == KIND_TRIANGLES) {   // every lane of the wave enters: the tests of the walk are shared (pt_trace_coop.hpp)
-            BoxHit bh = {};
-            if (live) bh = inter_aabb_t<FAST, true>(ray, rr, set_box(S));
-            ch = trace_dda_coop<COOP_CLOSEST, FAST, GRIDS == 1>(live && bh.v, ray, rr, bh, S, defer);
-        } else if (live) {
-            const BoxHit bh = inter_aabb_t<FAST, true>(ray, rr, set_box(S));
-            if (bh.v) ch = trace_dda<SPHERES, false, TRI_A10, FAST, GRIDS == 1>(ray, bh, S, defer);
-        }
-        if (ch.idx == UINT32_MAX) continue;
-        won = s;
-        ray.maxt = ch.t;
-        poi.p = fma3(ch.t, ray.d, ray.o);   // getPoint, code.cl:87
-        if (S.kind == KIND_SPHERES) {
-            poi.n = norm3(sub3(poi.p, ld3(((const float4*)S.prims)[ch.idx])));
-            poi.matId = (int32_t)((const uint32_t*)S.matid)[ch.idx];
-        } else {
-            float w = 1.0f - ch.beta - ch.gamma;  // code.cl:409-411
-            if (PT_LANE_LISTS_FOR(FAST, GRIDS) && S.n == 1u && S.lds_off != kNoLds) {   // staged with its vertex normals and material ids (stage_block)
-                const uint32_t base = S.lds_off + 12u * S.nslots;
-                const float4* nn = (const float4*)&pt_lds_dyn[base + __umul24(ch.idx, 12u)];
-                poi.n = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
-                poi.matId = (int32_t)pt_lds_dyn[base + 12u * S.nslots + ch.idx];
-            } else {
-                const float4* nn = (const float4*)S.normals + 3u * (size_t)ch.idx;
-                poi.n = norm3(fma3(ch.gamma, ld3(nn[2]), fma3(w, ld3(nn[0]), scl3(ch.beta, ld3(nn[1])))));
-                poi.matId = (int32_t)(S.matid ? ((const uint32_t*)S.matid)[ch.idx] : S.mesh_matid);
-            }
-        }
-    }
-}
+// What this kernel adds to closest_all's loop (pt_closest.hpp ClosestHooks): its own guard, the division kept in the loop, and the index of the
+// last set that won
+struct RayHooks : ClosestHooks {
+    uint32_t& set;
+    PT_DEV void guard(Ray& ray, bool& defer) const { guard_or_retire(ray, defer); }
+    PT_DEV void top(Ray& ray) const { keep_in_loop(ray); }
+    PT_DEV void won(uint32_t s) const { set = s; }
+};
 
-// the per-set loop of the fused pass's shadow stage (pt_kernels_fused.hip direct_all) on the caller's ray
+// the per-set loop of the fused pass's shadow stage (pt_kernels_fused.hip direct_all) on the caller's ray: the second statement of that loop,
+// to be kept in step with the first by hand (see the header)
 template <bool FAST, int GRIDS>
 PT_DEV void rays_any(const FusedArgs& A, Ray& sh, bool& defer) {
     if (FAST) guard_or_retire(sh, defer);
@@ -179,7 +142,7 @@ __global__ void __launch_bounds__(256) k_traceRays(const FusedArgs A, const floa
         poi.atte = mk3(1.0f, 1.0f, 1.0f);
         poi.matId = -1;
         uint32_t won = UINT32_MAX;
-        rays_closest<FAST, GRIDS>(A, ray, poi, won, defer);
+        closest_all<FAST, GRIDS>(A, ray, poi, RayHooks{{}, won}, defer);
         if (FAST) hand_over();
         if (!valid || (FAST && defer)) return;
         if (hits) {
@@ -194,9 +157,9 @@ template <bool FAST, bool ANY>
 static void launch_rays_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const float4* rays, uint32_t count, float4* hits, uint32_t* sets, uint8_t* occluded,
                           uint32_t* defer_mask, const uint32_t* redo_mask) {
     const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
-    if (L.grids && L.staged) hipLaunchKernelGGL((k_traceRays<FAST, 1, ANY>), grid, dim3(256), L.lds, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
-    else if (L.grids) hipLaunchKernelGGL((k_traceRays<FAST, 2, ANY>), grid, dim3(256), L.lds2, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
-    else hipLaunchKernelGGL((k_traceRays<FAST, 0, ANY>), grid, dim3(256), L.lds_tri, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
+    fused_lds_dispatch(L, [&](auto G, size_t lds) {
+        hipLaunchKernelGGL((k_traceRays<FAST, decltype(G)::value, ANY>), grid, dim3(256), lds, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
+    });
 }
 // fast: the optimistic kernel (sets the deferred rays' bits in defer_mask, one per ray); !fast: the exact kernel over the rays of redo_mask, or
 // over every ray when it is null.  occluded != null: the occlusion query; else the closest hit into hits and / or sets.
