@@ -44,9 +44,38 @@ CASES = [
     ("frame_a07_own_octahedra_n3_96x64", 7, "octahedra.json", 96, 64, 3, True),
 ]
 
+# The page's Rotate mode (Camera.rotate, A04 / A07 code.js:73-99): (base fixture, degrees), all at 96 x 64.  frame_rot_<base>_<degrees>.npz holds
+# the base fixture's name, the rotated camera block and the reference's frame -- no geometry: that is the base fixture's.
+ROT_SIZE = (96, 64)
+ROT_CASES = [("frame_a07_teapot_n2_160x120", 90), ("frame_a07_teapot_n2_160x120", 180), ("frame_a04_teapot_160x120", 135),
+             ("frame_a07_mol_c60_n4_160x120", 270)]
+
+
+def rot_name(base, angle):
+    return "frame_rot_" + base[len("frame_"):].rsplit("_", 1)[0] + f"_{angle}"
+
+
+def rotated(only):
+    by_name = {c[0]: c for c in CASES}
+    w, h = ROT_SIZE
+    for base, angle in ROT_CASES:
+        name = rot_name(base, angle)
+        if only and name not in only:
+            continue
+        _, assign, mesh, _, _, n, own = by_name[base]
+        cmd = ["node", os.path.join(HERE, "ref_host_dump_frame.js"), REFROOT, str(assign), mesh, str(w), str(h), str(n)] + ([OWN_PAGE] if own else [])
+        js = subprocess.run(cmd + [f"--rotate={angle}"], check=True, capture_output=True, cwd="/tmp").stdout.decode()
+        d = json.loads(js)
+        pixels, rays = F.run_frame("ref", F.Frame(d))
+        path = os.path.join(OUT, name + ".npz")
+        np.savez_compressed(path, base=np.frombuffer(base.encode(), np.uint8), cam=np.asarray(d["cam"], np.float32), pixel=pixels,
+                            rays_maxt=np.ascontiguousarray(rays["maxt"]), rays_mint=np.ascontiguousarray(rays["mint"]))
+        print(f"{name}: lit {float((pixels[:, :3].max(axis=1) > 0).mean()):.3f}, {os.path.getsize(path) / 1e3:.1f} KB")
+
 
 def main():
     only = set(sys.argv[1:])
+    rotated(only)
     for name, assign, mesh, w, h, n, own in CASES:
         if only and name not in only:
             continue

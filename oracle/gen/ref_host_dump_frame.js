@@ -5,13 +5,17 @@
 // would upload for one mesh: camera pack, AABB, float4-padded positions / normals, material indices, colours,
 // and (A07) the grid-sorted arrays with their cell offsets.
 //
-// usage: node ref_host_dump_frame.js <REFROOT> <1|4|7> <mesh.json|-> <width> <height> [n_slabs] [pageDir]
+// usage: node ref_host_dump_frame.js <REFROOT> <1|4|7> <mesh.json|-> <width> <height> [n_slabs] [pageDir] [--rotate=<degrees>]
+// --rotate (Assign04 / 07): after cam.set(...) the page's own cam.rotate(bounds, degrees), as its Rotate button calls it (A07 code.js:73-99)
 "use strict";
 const fs = require("fs");
 const path = require("path");
 const vm = require("vm");
 
-const [refroot, assign, meshName, W, H, NSLABS, PAGEDIR] = process.argv.slice(2);
+const argv = process.argv.slice(2);
+const rot = argv.filter(function (a) { return /^--rotate=/.test(a); }).map(function (a) { return +a.slice(9); });
+const [refroot, assign, meshName, W, H, NSLABS, PAGEDIR] = argv.filter(function (a) { return !/^--rotate=/.test(a); });
+const ROTATE = rot.length ? "cam.rotate(B, " + rot[0] + ");" : "";
 const dirs = { 1: "Assign01-Sphere_Ray_Tracing", 4: "Assign04-Triangle_Mesh", 7: "Assign07-3D_uniform_grid_acceleration" };
 const adir = path.join(refroot, dirs[assign]);
 const datadir = PAGEDIR ? path.resolve(PAGEDIR) : adir;
@@ -46,7 +50,7 @@ if (assign === "1") {
   out = vm.runInContext(`(function(){
     var f32=${f32}, u32=${u32};
     var molData = parsePDB(loadFromFile("mol/${meshName}"));
-    cam.defaultInit(); cam.set(molData.bounds, width, height);
+    cam.defaultInit(); cam.set(molData.bounds, width, height); var B = molData.bounds; ${ROTATE}
     var pd=[], id=[], sd=[]; splitMolData(molData, pd, id, sd);
     return { assign: 7, mol: "${meshName}", width: width, height: height, cam: f32(cam.toFloat32Array()), n_slabs: n_slabs, s_size: molData.size,
              bounds: f32([molData.bounds.min[0], molData.bounds.min[1], molData.bounds.min[2], 1, molData.bounds.max[0], molData.bounds.max[1], molData.bounds.max[2], 1]),
@@ -58,7 +62,7 @@ if (assign === "1") {
   out = vm.runInContext(`(function(){
     var f32=${f32}, u32=${u32};
     var meshData = parseMeshJSON("tri/${meshName}");
-    cam.defaultInit(); cam.set(meshData.bounds, width, height);           // computeTri (A04 code.js:553-577, A07 code.js:603-628)
+    cam.defaultInit(); cam.set(meshData.bounds, width, height); var B = meshData.bounds; ${ROTATE}         // computeTri (A04 code.js:553-577, A07 code.js:603-628)
     var o = { assign: ${+assign}, mesh: "${meshName}", width: width, height: height, cam: f32(cam.toFloat32Array()),
               bounds: f32([meshData.bounds.min[0], meshData.bounds.min[1], meshData.bounds.min[2], 1, meshData.bounds.max[0], meshData.bounds.max[1], meshData.bounds.max[2], 1]), t_size: meshData.nTriangles, mcolor: f32(meshData.materials) };
     if (${+assign} === 4) {
