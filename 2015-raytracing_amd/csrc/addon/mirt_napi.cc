@@ -7,6 +7,7 @@
 // built on top of these in host/webcl.js, in JavaScript.
 #include <node_api.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -316,11 +317,14 @@ bool read_grid(napi_env env, napi_value o, mirt_grid* g) {
 // (mirt_render_first_pass_guided)
 // renderPassesGuided(ctx, desc, normalHits, albedoDepth): desc.nPasses passes (desc.firstPass, desc.everyPass as for renderPass) and the frame's
 // guides in one call (mirt_render_passes_guided)
-enum RenderCall { CALL_PASS, CALL_GUIDES, CALL_FIRST_PASS_GUIDED, CALL_PASSES_GUIDED };
+// renderAo(ctx, desc, aoDesc, aoOut): ambient occlusion of the first hit of the same descriptor (seeds are read, not written; material, lights,
+// acu, pixel, radiance are not needed), aoDesc = {samples, radius, bias} -- a number left out is the header's default, radius +Infinity --, aoOut
+// uint32 {open, cast} per pixel of the tile (mirt_render_ao).  aoDeferred(ctx) -> the pixels the last renderAo re-ran in the exact kernel.
+enum RenderCall { CALL_PASS, CALL_GUIDES, CALL_FIRST_PASS_GUIDED, CALL_PASSES_GUIDED, CALL_AO };
 static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, RenderCall call, napi_value nhv, napi_value adv) {
     const bool guides = call != CALL_PASS;
     void* c;
-    if (!get_ext(env, ctxv, &c)) return throw_type(env, call == CALL_GUIDES ? "renderGuides(ctx, desc, normalHits, albedoDepth)" : call == CALL_FIRST_PASS_GUIDED ? "renderFirstPassGuided(ctx, desc, normalHits, albedoDepth)" : call == CALL_PASSES_GUIDED ? "renderPassesGuided(ctx, desc, normalHits, albedoDepth)" : "renderPass(ctx, desc)");
+    if (!get_ext(env, ctxv, &c)) return throw_type(env, call == CALL_AO ? "renderAo(ctx, desc, aoDesc, aoOut)" : call == CALL_GUIDES ? "renderGuides(ctx, desc, normalHits, albedoDepth)" : call == CALL_FIRST_PASS_GUIDED ? "renderFirstPassGuided(ctx, desc, normalHits, albedoDepth)" : call == CALL_PASSES_GUIDED ? "renderPassesGuided(ctx, desc, normalHits, albedoDepth)" : "renderPass(ctx, desc)");
     mirt_pass_desc p;
     memset(&p, 0, sizeof p);
     p.struct_size = sizeof p;
@@ -372,6 +376,20 @@ static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, Rende
     bool every = false;
     { napi_value v; bool has = false; if (napi_has_named_property(env, d, "everyPass", &has) == napi_ok && has && napi_get_named_property(env, d, "everyPass", &v) == napi_ok) napi_get_value_bool(env, v, &every); }
     uint32_t n_passes = 0;
+    if (call == CALL_AO) {
+        mirt_ao_desc a = {(uint32_t)sizeof(mirt_ao_desc), MIRT_AO_DEFAULT_SAMPLES, INFINITY, MIRT_AO_DEFAULT_BIAS};
+        napi_valuetype t = napi_undefined;
+        if (nhv && napi_typeof(env, nhv, &t) == napi_ok && t == napi_object) {
+            prop_u32(env, nhv, "samples", &a.samples);
+            prop_f32(env, nhv, "radius", &a.radius);
+            prop_f32(env, nhv, "bias", &a.bias);
+        }
+        void* out = nullptr;
+        get_ext(env, adv, &out);
+        const int rc = mirt_render_ao((mirt_ctx*)c, &p, &a, (mirt_buf*)out);
+        if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+        return undef(env);
+    }
     if (guides) {
         void *nh = nullptr, *ad = nullptr;
         get_ext(env, nhv, &nh);
@@ -398,6 +416,19 @@ napi_value RenderPass(napi_env env, napi_callback_info info) {
 napi_value RenderGuides(napi_env env, napi_callback_info info) {
     ARGS(4);
     return render_call(env, argv[0], argv[1], CALL_GUIDES, argv[2], argv[3]);
+}
+napi_value RenderAo(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    return render_call(env, argv[0], argv[1], CALL_AO, argv[2], argv[3]);
+}
+napi_value AoDeferred(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "aoDeferred(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_ao_deferred((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
 }
 napi_value RenderFirstPassGuided(napi_env env, napi_callback_info info) {
     ARGS(4);
@@ -894,7 +925,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
         {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
-        {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
+        {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"renderAo", RenderAo}, {"aoDeferred", AoDeferred}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},
         {"abiVersion", AbiVersion}, {"groupPeerAccess", GroupPeerAccess}, {"gatherRoute", GatherRoute},

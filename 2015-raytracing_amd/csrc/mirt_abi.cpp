@@ -77,6 +77,9 @@ struct mirt_ctx {
     void* ray_defer = nullptr;    // mirt_trace_closest / mirt_trace_occluded, optimistic pair: [count, pad, pad, pad | a bit per ray], its own allocation too
     size_t ray_defer_bytes = 0;
     uint32_t ray_defer_words = 0; // mask words the last trace call used (0: it ran the exact kernel only, or queued nothing)
+    void* ao_defer = nullptr;     // mirt_render_ao, optimistic pair: [count, pad, pad, pad | a bit per pixel of the tile], its own allocation too
+    size_t ao_defer_bytes = 0;
+    uint32_t ao_defer_words = 0;  // mask words the last mirt_render_ao used (0: it ran the exact kernel only)
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     int force_exact = 0;          // mirt_ctx_set_exact_only: 1 = skip the optimistic kernel, run every sample through the exact one
@@ -379,6 +382,7 @@ static int destroy_ctx(mirt_ctx* ctx) {
     if (ctx->defer) (void)hipFree(ctx->defer);
     if (ctx->guide_mask) (void)hipFree(ctx->guide_mask);
     if (ctx->ray_defer) (void)hipFree(ctx->ray_defer);
+    if (ctx->ao_defer) (void)hipFree(ctx->ao_defer);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1269,8 +1273,9 @@ static pt::PassRequest pass_request(const mirt_ctx* ctx, const mirt_pass_desc* d
 
 // What mirt_render_pass and mirt_render_guides check and fill alike, in this order: the descriptor, the k x k ray count, the tile, then the camera,
 // bounds, primitive sets (validated and prepared: fill_grid) and material of `A`.  guides: the lights and pass_index are not looked at.
+// !with_material (mirt_render_ao, with guides): nor is the material.
 static int fill_sets(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, pt::FusedArgs& A);
-static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bool guides, pt::FusedArgs& A) {
+static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bool guides, pt::FusedArgs& A, bool with_material = true) {
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "%s: empty image", fn);
     {   // the host only ever makes k x k rays per pixel (A10 code.js:540); initTrace's k x k loops leave the tail of any other count
@@ -1307,6 +1312,7 @@ static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bo
         memcpy(A.lights[l].scene, d->lights[l].scene, 64);
         memcpy(A.lights[l].light, d->lights[l].light, 64);
     }
+    if (!with_material) return MIRT_OK;
     if ((rc = need(ctx, "material", d->material, 16))) return rc;
     A.material = d->material->ptr;
     A.nmat = (uint32_t)(d->material->bytes / 16);
@@ -1608,6 +1614,74 @@ int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_
     if (albedo_depth) albedo_depth->version++;
     return MIRT_OK;
 } MIRT_CATCH("mirt_render_guides", return MIRT_E_DEVICE)
+
+// Ambient occlusion of the first hit (pt_kernels_rays.hip k_ao): the guides' checks without the material, the call's own, then one launch -- or the
+// optimistic / exact pair, per pixel -- of one lane per pixel.  Every check comes before anything is queued; nothing but ao_out is written.
+int mirt_render_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_ao_desc* ao, mirt_buf* ao_out) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_ao: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_render_ao");
+    if (!ao || ao->struct_size != sizeof(mirt_ao_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: AO descriptor size mismatch");
+    if (!ao->samples || ao->samples > MIRT_AO_MAX_SAMPLES) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: samples %u outside 1..%u", ao->samples, MIRT_AO_MAX_SAMPLES);
+    if (!(ao->radius > 0.0f)) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: radius %g is not above 0", (double)ao->radius);
+    if (!(ao->bias >= 0.0f) || std::isinf(ao->bias)) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: bias %g is not a finite number >= 0", (double)ao->bias);
+    if (!ao_out) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: ao_out is NULL");
+    if (d && d->struct_size == sizeof(mirt_pass_desc)) {
+        if (d->rays_per_pixel == 1u)
+            return fail(ctx, MIRT_E_ARG, "mirt_render_ao: rays_per_pixel == 1 draws its lens sample from seeds[col] (A10 code.cl:429); the first hit is defined "
+                                         "for the un-jittered k x k lens grid, rays_per_pixel >= 4 (mirt_render_guides)");
+        if (!d->seeds) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: seeds is NULL (the AO rays draw from them; they are not written)");
+    }
+    pt::FusedArgs A;
+    int rc;
+    if ((rc = pass_setup(ctx, "mirt_render_ao", d, true, A, false))) return rc;
+    const uint64_t npix = (uint64_t)A.nrows * A.width;
+    const uint64_t nrays = npix * A.rpp;
+    if ((rc = need(ctx, "mirt_render_ao seeds", d->seeds, nrays * 4))) return rc;
+    if ((rc = need(ctx, "mirt_render_ao ao_out", ao_out, npix * 8))) return rc;
+    {   // the output is read by nobody and no input is written: the bytes the call writes, against the seeds' and the geometry's buffers whole
+        std::vector<pt::PostRange> in;
+        add_range(in, d->seeds);
+        add_geometry_ranges(in, d);
+        const pt::PostRange out[1] = {{(uint64_t)(uintptr_t)ao_out->ptr, npix * 8, true}};
+        if (pt::post_alias(in.data(), in.size(), out, 1) != pt::POST_ALIAS_NONE)
+            return fail(ctx, MIRT_E_ARG, "mirt_render_ao: ao_out's bytes meet the seeds' or a geometry buffer's");
+    }
+    A.seeds = (int32_t*)d->seeds->ptr;
+    ctx->ao_defer_words = 0;
+    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
+        const uint32_t words = (uint32_t)((npix + 31u) / 32u);
+        if ((rc = grow_and_clear(ctx, ctx->ao_defer, ctx->ao_defer_bytes, 16u + (size_t)words * 4u))) return rc;
+        uint32_t* const mask = (uint32_t*)ctx->ao_defer + 4;
+        pt::launch_ao(ctx->stream, A, true, ao->samples, ao->radius, ao->bias, ao_out->ptr, mask, nullptr);
+        pt::launch_ao(ctx->stream, A, false, ao->samples, ao->radius, ao->bias, ao_out->ptr, nullptr, mask);
+        ctx->ao_defer_words = words;
+    } else {
+        pt::launch_ao(ctx->stream, A, false, ao->samples, ao->radius, ao->bias, ao_out->ptr, nullptr, nullptr);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    ao_out->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_render_ao", return MIRT_E_DEVICE)
+
+int mirt_ao_deferred(mirt_ctx* ctx, uint64_t* pixels) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ao_deferred: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_ao_deferred");
+    if (!pixels) return fail(ctx, MIRT_E_ARG, "mirt_ao_deferred: null output");
+    *pixels = 0;
+    if (!ctx->ao_defer_words) return MIRT_OK;
+    // counted on demand: the mask of the last mirt_render_ao is still in place (the next one clears it)
+    uint32_t* counters = (uint32_t*)ctx->ao_defer;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
+    pt::launch_deferCount(ctx->stream, counters + 4, ctx->ao_defer_words, counters);
+    uint32_t count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *pixels = count;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_ao_deferred", return MIRT_E_DEVICE)
 
 // ---- ray queries (pt_kernels_rays.hip): mirt_trace_closest and mirt_trace_occluded.  Every check comes before anything is queued; then one launch
 // -- or the optimistic / exact pair, per ray -- of one lane per ray.  Nothing but the outputs is written.

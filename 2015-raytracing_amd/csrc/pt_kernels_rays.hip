@@ -26,6 +26,8 @@
 // guard's |d_k| >= 2^-40, as does a zero-length, infinite or NaN one.  Such batches run mostly in the EXACT kernel (mirt_trace_deferred counts
 // them; profiles/rays/timing.json has the measured cost).  The guard windows are what makes the optimistic kernel's divisions exact and are not
 // widened for this.
+//
+// Also here, because it runs rays_any: k_ao, ambient occlusion of the first hit (mirt_render_ao) -- at the end of the file.
 #include "pt_closest.hpp"
 
 namespace pt {
@@ -176,6 +178,95 @@ void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays,
         if (fast) launch_rays_t<true, false>(s, b, L, (const float4*)rays, count, (float4*)hits, sets, nullptr, defer_mask, nullptr);
         else launch_rays_t<false, false>(s, b, L, (const float4*)rays, count, (float4*)hits, sets, nullptr, nullptr, redo_mask);
     }
+}
+
+// ---- ambient occlusion of the first hit (mirt_render_ao): the guides' primary ray and closest-hit stage, then `samples` hemisphere rays per
+// casting sample through the any-hit loop above -- in one launch, nothing per ray in memory.  The definition is include/mirt.h's; the pieces are
+// the pass's (primary_ray, closest_all with ClosestHooks as they stand, bounce_ray) and this file's rays_any, which is why the kernel lives here.
+//
+// Structure: k_guides' -- one lane per pixel, walking its samples in order, so every k x k count works with no segment plan -- and behind each
+// sample's closest hit a loop of `samples` trips, a kernel argument and so WAVE-UNIFORM: in the grid variants every lane of the wave enters each
+// shared-test walk of rays_any together (pt_trace_coop.hpp).  A lane whose sample did not cast, a lane without a pixel and a redo kernel's unmarked
+// lane ride along with a dead ray and count nothing.  The optimistic / exact pair is per PIXEL, as in k_guides: a pixel one of whose primary or AO
+// rays the guard refuses, or whose walk defers, sets its bit and writes nothing; the exact kernel redoes the marked pixels whole.
+// seeds: int32 per tile-local ray, read for the casting samples and never written.  ao_out: {open, cast} per tile-local pixel, one 8-byte store.
+// Waves per SIMD the register allocator is held to (A/B switches; profiles/ao/README.md has the measurement).  Left alone the grid kernels take 126 to
+// 129 VGPRs (the optimistic one 3 waves, a register over the fourth) and the single-cell ones 81 to 94 (5 waves); a lane here runs rpp * (1 + samples)
+// rays back to back with nothing to overlap them but other waves, and more waves paid at every step tried, a few spilled registers included:
+// cornell_teapot3 7.25 -> 5.99 (4 waves) -> 5.63 ms (5), cornell 2.29 -> 2.19 (6) -> 2.15 ms (7) at 1920 x 1080 x 16 with 4 AO rays.
+#ifndef PT_AO_GRID_WAVES
+#define PT_AO_GRID_WAVES 5
+#endif
+#ifndef PT_AO_CELL_WAVES
+#define PT_AO_CELL_WAVES 7
+#endif
+#define PT_AO_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_AO_GRID_WAVES : PT_AO_CELL_WAVES)
+template <bool FAST, int GRIDS>
+__global__ void PT_AO_BOUNDS(GRIDS) k_ao(const FusedArgs A, uint32_t samples, float radius, float bias, uint2* __restrict__ ao_out, uint32_t* defer_mask,
+                                            const uint32_t* redo_mask) {
+    stage_block<FAST, GRIDS>(A);
+    const uint32_t npix = A.nrows * A.width;   // (a tile holds fewer than 2^32 rays: mirt_render_ao)
+    uint32_t pix = blockIdx.x * 256u + threadIdx.x;
+    bool valid = pix < npix;
+    if (!FAST && redo_mask && valid) valid = (redo_mask[pix >> 5] >> (pix & 31u) & 1u) != 0u;
+    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
+    else if (!valid) return;
+    if (pix >= npix) pix = npix - 1u;
+    const int32_t* __restrict__ seeds = A.seeds;
+    uint32_t open = 0u, cast = 0u;
+    bool defer = false;
+    const uint32_t first = pix * A.rpp;
+    for (uint32_t i = 0; i < A.rpp; ++i) {
+        Ray ray = primary_ray(A, first + i);
+        if (!valid) { ray.mint = 0.0f; ray.maxt = 0.0f; }   // rides along dead: hits nothing, casts nothing
+        Poi poi;
+        poi.p = mk3(0.0f, 0.0f, 0.0f);
+        poi.n = mk3(0.0f, 0.0f, 0.0f);
+        poi.atte = mk3(1.0f, 1.0f, 1.0f);
+        poi.matId = -1;
+        closest_all<FAST, GRIDS>(A, ray, poi, ClosestHooks{}, defer);
+        const bool casts = poi.matId >= 0;   // bouncePaths' own test (code.cl:592): no material is read
+        int32_t seed = 0;
+        if (casts) seed = seeds[first + i];
+        for (uint32_t j = 0; j < samples; ++j) {
+            Ray sh;
+            sh.o = mk3(0.0f, 0.0f, 0.0f); sh.d = mk3(0.0f, 0.0f, 0.0f); sh.mint = 0.0f; sh.maxt = 0.0f;
+            if (casts) {
+                sh = bounce_ray(poi, seed);   // getHemisphereRay (code.cl:545-579): the seed advances, in its register only
+                if (bias != 0.0f) sh.o = add3(poi.p, scl3(bias, poi.n));   // two fp32 operations, each rounded on its own (-ffp-contract=off)
+                sh.maxt = radius;
+            }
+            rays_any<FAST, GRIDS>(A, sh, defer);
+            if (casts) {
+                cast += 1u;
+                if (!(sh.mint == sh.maxt)) open += 1u;
+            }
+        }
+    }
+    if (!valid) return;
+    if (FAST && defer) {   // the exact kernel redoes the pixel: nothing of it is written
+        atomicOr(&defer_mask[pix >> 5], 1u << (pix & 31u));
+        return;
+    }
+    ao_out[pix] = make_uint2(open, cast);
+}
+
+template <bool FAST>
+static void launch_ao_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, uint32_t samples, float radius, float bias, uint2* ao_out, uint32_t* defer_mask,
+                        const uint32_t* redo_mask) {
+    const dim3 grid((unsigned)(((uint64_t)b.nrows * b.width + 255u) / 256u));
+    fused_lds_dispatch(L, [&](auto G, size_t lds) {
+        hipLaunchKernelGGL((k_ao<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, samples, radius, bias, ao_out, defer_mask, redo_mask);
+    });
+}
+// fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
+// of redo_mask, or over every pixel when it is null.
+void launch_ao(hipStream_t s, const FusedArgs& a, bool fast, uint32_t samples, float radius, float bias, void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    if (!a.nrows || !a.width) return;
+    FusedArgs b = a;
+    const FusedLds L = fused_lds_slots(b, fast);
+    if (fast) launch_ao_t<true>(s, b, L, samples, radius, bias, (uint2*)ao_out, defer_mask, nullptr);
+    else launch_ao_t<false>(s, b, L, samples, radius, bias, (uint2*)ao_out, nullptr, redo_mask);
 }
 
 }  // namespace pt

@@ -150,6 +150,10 @@ void launch_guides(hipStream_t s, const FusedArgs& a, bool fast, void* normal_hi
 // the sets of `a` and nothing else of it.
 void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, void* hits, uint32_t* sets, uint8_t* occluded,
                  uint32_t* defer_mask, const uint32_t* redo_mask);
+// Ambient occlusion of the first hit (pt_kernels_rays.hip k_ao; the definition is mirt_render_ao's comment in include/mirt.h): uint32[2] per pixel
+// of the tile, {open, cast}.  One lane per pixel; the optimistic / exact pair as in launch_guides, the mask one bit per pixel.  Reads the camera,
+// bounds and sets of `a` and a.seeds (int32 per tile-local ray, never written); not its material or lights.
+void launch_ao(hipStream_t s, const FusedArgs& a, bool fast, uint32_t samples, float radius, float bias, void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask);
 // Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
 // every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
 struct FilterArgs {

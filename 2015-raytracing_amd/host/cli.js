@@ -1,8 +1,8 @@
 #!/usr/bin/env node
 // host/cli.js -- command-line front end of the JavaScript host.
 //   node cli.js pack   <scene.xml> <width> <height> <raysPerPixel>                 -> packed kernel inputs as JSON (stdout)
-//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl] [--post-in-tiles]] [--guides PREFIX] [--denoise [iterations]] [--upscale F]
-//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N unless --post-in-tiles; --post-in-tiles (with --gpus N): --denoise and --upscale run tile-local -- every device exchanges halo rows with its neighbours and filters / upsamples its own rows (mirt_exchange_rows, mirt_filter_atrous_rows, mirt_upsample_guided_rows), only finished rows are gathered; the same bytes in <out>, <out>.filtered.f32 and <out>.upsampled.f32, and no <out>.radiance.f32 (the unfiltered sums stay on their devices)
+//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl] [--post-in-tiles]] [--guides PREFIX] [--denoise [iterations]] [--upscale F] [--ao PREFIX [--ao-samples N] [--ao-radius R] [--ao-bias B]]
+//                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --ao: + PREFIX.ao.u32 (ambient occlusion of the first hit, mirt_render_ao: raw uint32 pairs {open, cast} per pixel, N AO rays of length R per hit sample, default 4 and unbounded, displaced by B = 0.001 along the normal; taken before the first pass, the seeds are not advanced) and PREFIX.ao.pgm (a byte per pixel, floor(255 * open / cast + 0.5), 255 where cast is 0), not with --gpus N; --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N unless --post-in-tiles; --post-in-tiles (with --gpus N): --denoise and --upscale run tile-local -- every device exchanges halo rows with its neighbours and filters / upsamples its own rows (mirt_exchange_rows, mirt_filter_atrous_rows, mirt_upsample_guided_rows), only finished rows are gathered; the same bytes in <out>, <out>.filtered.f32 and <out>.upsampled.f32, and no <out>.radiance.f32 (the unfiltered sums stay on their devices)
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
@@ -49,6 +49,17 @@ if (cmd === "pack") {
   if ((i = rest.indexOf("--gpus")) >= 0) { opt.gpus = +rest[i + 1]; opt.forceRccl = rest.includes("--force-rccl"); }   // row tiles over N devices + gather
   opt.postInTiles = rest.includes("--post-in-tiles") && !!opt.gpus;   // with --gpus N: --denoise and --upscale filter / upsample every tile where it is, after a halo exchange
   if ((i = rest.indexOf("--guides")) >= 0) { if (!rest[i + 1]) usage(); opt.guides = rest[i + 1]; }   // first-hit guide buffers beside the frame (mirt_render_guides)
+  if ((i = rest.indexOf("--ao")) >= 0) {   // ambient occlusion of the first hit beside the frame (mirt_render_ao)
+    if (!rest[i + 1]) usage();
+    opt.aoPrefix = rest[i + 1];
+    opt.ao = {};
+    let j;
+    if ((j = rest.indexOf("--ao-samples")) >= 0) opt.ao.samples = +rest[j + 1];
+    if ((j = rest.indexOf("--ao-radius")) >= 0) opt.ao.radius = +rest[j + 1];
+    if ((j = rest.indexOf("--ao-bias")) >= 0) opt.ao.bias = +rest[j + 1];
+    if (opt.gpus) { process.stderr.write("--ao is not available with --gpus N: gathering the tiles' AO pairs is not built\n"); process.exit(2); }
+    if (rest.includes("--upscale") || opt.granular) { process.stderr.write("--ao goes with the fused host's plain frame: not with --upscale or --granular\n"); process.exit(2); }
+  }
   if ((i = rest.indexOf("--denoise")) >= 0) {   // the frame filtered on the device (mirt_filter_atrous); implies the guides; with --gpus N: gathered, then filtered on the root
     opt.denoise = {};
     if (/^\d+$/.test(rest[i + 1] || "")) opt.denoise.iterations = +rest[i + 1];
@@ -85,6 +96,13 @@ if (cmd === "pack") {
   if (res.guides) {
     for (const [name, a] of [["normal_hits", res.guides.normalHits], ["albedo_depth", res.guides.albedoDepth]])
       fs.writeFileSync(`${opt.guides}.${name}.f32`, Buffer.from(a.buffer, a.byteOffset, a.byteLength));
+  }
+  if (res.ao) {
+    const a = res.ao.pairs, gray = Buffer.alloc(w * h);
+    for (let k = 0; k < w * h; k++) gray[k] = a[2 * k + 1] ? Math.floor(255 * a[2 * k] / a[2 * k + 1] + 0.5) : 255;
+    fs.writeFileSync(`${opt.aoPrefix}.ao.u32`, Buffer.from(a.buffer, a.byteOffset, a.byteLength));
+    fs.writeFileSync(`${opt.aoPrefix}.ao.pgm`, Buffer.concat([Buffer.from(`P5\n${w} ${h}\n255\n`, "ascii"), gray]));
+    process.stderr.write(`ambient occlusion: ${opt.aoPrefix}.ao.u32, ${opt.aoPrefix}.ao.pgm; pixels re-run in the exact kernel: ${res.ao.deferred}\n`);
   }
   if (res.frames) {
     const ext = path.extname(out), stem = out.slice(0, out.length - ext.length), n = w * h * 4;

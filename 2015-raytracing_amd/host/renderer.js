@@ -359,6 +359,18 @@ class FusedRenderer {
     this.q.finish();
     return { normalHits: n, albedoDepth: a };
   }
+  // ambient occlusion of the first hit of this renderer's tile (queue.renderAo), from the seeds as they stand (they are not advanced): ao = any of
+  // samples, radius, bias.  readAo(): Uint32Array of {open, cast} per pixel
+  renderAo(ao) {
+    if (!this.ao) this.ao = this.ctx.createBuffer(webcl.MEM_WRITE_ONLY, this.npix * 8);
+    this.q.renderAo(this.passDesc(), ao || {}, this.ao);
+  }
+  readAo() {
+    const o = new Uint32Array(this.npix * 2);
+    this.q.enqueueReadBuffer(this.ao, false, 0, o.byteLength, o, []);
+    this.q.finish();
+    return o;
+  }
   // the a-trous-filtered frame of this renderer's current radiance (queue.filterFrame, guided by renderGuides()'s buffers), all on the device; f: any
   // of iterations, normalPowerLog2, sigmaDepth, sigmaColour, demodulate, structure.  A row tile would be filtered alone: renderTiled gathers first
   // and filters the whole frame on the root (filterGathered)
@@ -384,7 +396,7 @@ class FusedRenderer {
   readRadiance() { const o = new Float32Array(this.npix * 4); this.q.enqueueReadBuffer(this.radiance, false, 0, o.byteLength, o, []); this.q.finish(); return o; }
   readAcu() { const a = new Float32Array(this.nrays * 4); this.q.enqueueReadBuffer(this.acu, false, 0, a.byteLength, a, []); this.q.finish(); return a; }
   release() {
-    [this.seeds, this.acu, this.pixel, this.radiance, this.normalHits, this.albedoDepth, this.filtered, this.filteredPixel].forEach((b) => b && b.release());
+    [this.seeds, this.acu, this.pixel, this.radiance, this.normalHits, this.albedoDepth, this.filtered, this.filteredPixel, this.ao].forEach((b) => b && b.release());
     this.dev.bufs.forEach((b) => b.release());
     this.q.release();
     if (this.ownCtx) this.ctx.release();
@@ -604,16 +616,22 @@ function renderFile(file, width, height, rpp, passes, opt) {
     packed = scene.packScene(sc, width, height, rpp, 1, true);
     opt = Object.assign({}, opt, { sceneObject: sc, ctx: ownCtx });
   } else packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, rpp);
+  if (opt.ao && opt.gpus) throw new Error("--ao is not available with --gpus N: gathering the tiles' AO pairs is not built");
   if (opt.everyPass && opt.gpus > 1) throw new Error("--every-pass is not available with --gpus N > 1: the gather would interleave the tiles' frames");
   if (opt.gpus && !(opt.everyPass && opt.gpus === 1)) {
     // N contexts, one per device: each builds its own copy of the scene (the loader's soups stay on ownCtx until every tile is built)
     if (opt.sceneObject) opt.sceneObject.keepSoups = true;
     try { return renderTiled(packed, opt.gpus, passes, opt); } finally { if (ownCtx) ownCtx.release(); }
   }
+  if (opt.ao && opt.granular) throw new Error("--ao is the fused host's (mirt_render_ao): not with the kernel-by-kernel host");
   if (opt.everyPass && !opt.passesInOneLaunch) throw new Error("--every-pass writes the frames of passes in one launch: give --passes-in-one-launch too");
   if ((opt.guides || opt.denoise) && opt.granular) throw new Error("--guides and --denoise are the fused host's (mirt_render_guides, mirt_filter_atrous): not with the kernel-by-kernel host");
   if (opt.passesInOneLaunch && opt.granular) throw new Error("passes in one launch are the fused pass's (mirt_render_passes): not with the kernel-by-kernel host");
   const R = opt.granular ? new GranularRenderer(packed, opt) : new FusedRenderer(packed, opt);
+  // --ao: ambient occlusion of the first hit, taken before the first pass -- from the seeds the frame starts with, which it does not advance, so the
+  // frame is the same with and without it
+  let ao = null;
+  if (opt.ao) { R.renderAo(opt.ao); ao = { pairs: R.readAo(), deferred: R.q.aoDeferred() }; }
   // one pass and its guides wanted: the pass writes them too (mirt_render_first_pass_guided), the files are the same bit for bit
   // passes in one launch and the guides wanted: that call writes them (mirt_render_passes_guided), with or without a frame after every pass
   const passesGuided = !!(opt.guides || opt.denoise) && !!opt.passesInOneLaunch && !opt.granular && R.canRenderPassesGuided();
@@ -628,6 +646,7 @@ function renderFile(file, width, height, rpp, passes, opt) {
                 device: R.device.getInfo(webcl.DEVICE_NAME), fusedPasses: R.ctx.fusedPasses ? R.ctx.fusedPasses() : 0,
                 guidedPasses: R.ctx.guidedPasses ? R.ctx.guidedPasses() : 0 };
   if (opt.everyPass) res.frames = R.readFrames();
+  if (ao) res.ao = ao;
   if (opt.guides) { if (!guided) R.renderGuides(); res.guides = R.readGuides(); }
   if (opt.denoise) { R.denoise(opt.denoise, guided || !!opt.guides); res.denoised = R.readDenoised(); }
   R.release();

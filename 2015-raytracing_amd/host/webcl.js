@@ -175,7 +175,7 @@ class WebCLCommandQueue {
                             cellOffsets: s.cellOffsets.h, bounds: s.bounds, nSlabs: s.nSlabs, meshMatId: s.meshMatId || 0 };
     return Object.assign({}, desc, {
       spheres: g(desc.spheres), triangles: g(desc.triangles), meshes: (desc.meshes || []).map(g),
-      material: desc.material.h, seeds: desc.seeds ? desc.seeds.h : undefined, acu: desc.acu ? desc.acu.h : undefined,   // no acu: a first pass that resolves its pixels itself (mirt.h)
+      material: desc.material ? desc.material.h : undefined, seeds: desc.seeds ? desc.seeds.h : undefined, acu: desc.acu ? desc.acu.h : undefined,   // no acu: a first pass that resolves its pixels itself (mirt.h)
       pixel: desc.pixel ? desc.pixel.h : undefined, radiance: desc.radiance ? desc.radiance.h : undefined,
     });
   }
@@ -190,6 +190,16 @@ class WebCLCommandQueue {
     const d = this._passDesc(desc);
     wrap(() => native().renderGuides(this.ctx.h, d, normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
   }
+  // ---- extension: ambient occlusion of the first hit of desc's row tile in one launch (mirt_render_ao; include/mirt.h has the definition):
+  // aoDesc = {samples, radius, bias} (left out: 4, Infinity, 0.001), aoOut: uint32 {open, cast} per pixel -- per hit primary sample `samples`
+  // hemisphere rays of length radius from the hit point, cast counts them, open those nothing blocks.  desc.seeds is read and not written;
+  // material, lights, acu, pixel and radiance are not needed.  aoDeferred(): the pixels the last call re-ran in the exact kernel.
+  hasAo() { return typeof native().renderAo === "function"; }
+  renderAo(desc, aoDesc, aoOut) {
+    const d = this._passDesc(desc);
+    wrap(() => native().renderAo(this.ctx.h, d, aoDesc || {}, aoOut ? aoOut.h : null));
+  }
+  aoDeferred() { return wrap(() => native().aoDeferred(this.ctx.h)); }
   // ---- extension: ray queries on the caller's own rays (mirt_trace_closest, mirt_trace_occluded; include/mirt.h has the definition).  rays: a
   // buffer of `count` 32-byte records {o.xyz, mint, d.xyz, maxt}; hits: {normal.xyz, t, p.xyz, matId (int32)} per ray; sets: a uint32 per ray, the
   // index of the set whose primitive won (0xFFFFFFFF: none); hits or sets may be null, not both.  occluded: a byte per ray.  Of desc only

@@ -78,7 +78,13 @@ class _UpsampleDesc(C.Structure):   # mirt_upsample_desc
                 ("normal_hits", C.c_void_p), ("albedo_depth", C.c_void_p), ("upsampled", C.c_void_p), ("pixel", C.c_void_p)]
 
 
+class _AoDesc(C.Structure):   # mirt_ao_desc
+    _fields_ = [("struct_size", C.c_uint32), ("samples", C.c_uint32), ("radius", C.c_float), ("bias", C.c_float)]
+
+
 _lib = None
+
+AO_MAX_SAMPLES, AO_DEFAULT_SAMPLES, AO_DEFAULT_BIAS = 64, 4, 0.001   # MIRT_AO_* (include/mirt.h)
 
 PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
 PASSES_EVERY_FRAME = 2   # MIRT_PASSES_EVERY_FRAME (include/mirt.h)
@@ -129,6 +135,8 @@ SYMBOLS = {
     "mirt_trace_closest": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "mirt_trace_occluded": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_uint64, C.c_void_p]),
     "mirt_trace_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_render_ao": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_AoDesc), C.c_void_p]),
+    "mirt_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
     "mirt_upsample_guided": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc)]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -554,6 +562,20 @@ class Context:
         """how many rays the last trace_closest / trace_occluded call re-ran in the exact kernel (mirt_trace_deferred)"""
         n = C.c_uint64()
         self._chk(lib().mirt_trace_deferred(self.h, C.byref(n)))
+        return n.value
+
+    def render_ao(self, desc, ao_out, samples=AO_DEFAULT_SAMPLES, radius=float("inf"), bias=AO_DEFAULT_BIAS):
+        """Ambient occlusion of the first hit of desc's row tile in one launch (mirt_render_ao): ao_out receives uint32 {open, cast} per pixel --
+        per hit primary sample `samples` hemisphere rays of length `radius` from the hit point, displaced by `bias` along the normal; cast counts
+        them, open those nothing blocks.  desc.seeds is read and not written.  An _AoDesc may be given in place of `samples`."""
+        ao = samples if isinstance(samples, _AoDesc) else _AoDesc(C.sizeof(_AoDesc), int(samples), float(radius), float(bias))
+        self._chk(lib().mirt_render_ao(self.h, C.byref(desc) if desc is not None else None, C.byref(ao) if ao is not None else None,
+                                       ao_out.h if ao_out else None))
+
+    def ao_deferred(self):
+        """how many pixels the last render_ao call re-ran in the exact kernel (mirt_ao_deferred)"""
+        n = C.c_uint64()
+        self._chk(lib().mirt_ao_deferred(self.h, C.byref(n)))
         return n.value
 
     def filter_atrous(self, width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,

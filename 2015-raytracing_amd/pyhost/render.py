@@ -281,6 +281,32 @@ class FusedRenderer:
             nh.release()
             ad.release()
 
+    def ao(self, samples=4, radius=float("inf"), bias=0.001, rows=None):
+        """Ambient occlusion of the first hit (mirt_render_ao) of this renderer's tile, or of rows = (row0, nrows) of the image inside that
+        tile: a uint32 array [pixels, 2] of {open, cast} -- per hit primary sample `samples` hemisphere rays of length `radius`, cast counts
+        them and open those nothing blocks, so open / cast is the pixel's openness.  The AO rays draw from the renderer's seeds as they stand
+        and do not advance them; accumulator and frame are not touched."""
+        row0, nrows = (self.row0, self.nrows) if rows is None else rows
+        npix = nrows * self.s.width
+        if not npix:
+            return np.zeros((0, 2), np.uint32)
+        if row0 < self.row0 or row0 + nrows > self.row0 + self.nrows:
+            raise mirt.MirtError(-1, f"FusedRenderer.ao: rows [{row0}, +{nrows}) lie outside the renderer's tile [{self.row0}, +{self.nrows}): it holds no seeds for them")
+        out = self.ctx.buffer(npix * 8)
+        seeds = self.seeds
+        try:
+            if (row0, nrows) != (self.row0, self.nrows):   # a tile's seeds are its own buffer from element 0 on: the rows' slice of the renderer's
+                per_row = self.s.width * self.s.rpp
+                seeds = self.ctx.buffer(nrows * per_row * 4)
+                seeds.write(self.seeds.read(np.int32, count=nrows * per_row, offset=(row0 - self.row0) * per_row * 4))
+            d = self.dev.pass_desc(seeds, None, row0=row0, nrows=nrows)
+            self.ctx.render_ao(d, out, samples, radius, bias)
+            return out.read(np.uint32).reshape(-1, 2)
+        finally:
+            out.release()
+            if seeds is not self.seeds:
+                seeds.release()
+
     def denoised(self, **params):
         """The a-trous-filtered frame (mirt_filter_atrous) of this renderer's current radiance: the guides of its tile (mirt_render_guides, as
         guides() renders them), then the filter, all on the device.  tone is 1 / (rays_per_pixel * passes rendered so far).  params:

@@ -320,6 +320,46 @@ typedef struct mirt_hit { float normal[3]; float t; float p[3]; int32_t mat_id; 
 MIRT_API int mirt_trace_closest(mirt_ctx* ctx, const mirt_pass_desc* scene, mirt_buf* rays, uint64_t count, mirt_buf* hits, mirt_buf* sets);
 MIRT_API int mirt_trace_occluded(mirt_ctx* ctx, const mirt_pass_desc* scene, mirt_buf* rays, uint64_t count, mirt_buf* occluded);
 MIRT_API int mirt_trace_deferred(mirt_ctx* ctx, uint64_t* rays);
+/* AMBIENT OCCLUSION OF THE FIRST HIT of the row tile, in one launch: the AOV the guides lack.  ao_out holds one uint32[2] per tile-local pixel,
+ * {open, cast}, 8 bytes per pixel.  Pixel p of the row tile has the rays p * rays_per_pixel + i, i = 0 .. rays_per_pixel - 1, each taken as
+ * initTrace and the closest-hit stage leave it -- sphereTrace, triangleTrace, then every meshTrace in upload order -- before lightRender: exactly
+ * the guides' state (mirt_render_guides).
+ *   A sample CASTS iff Poi.matId >= 0: bouncePaths' own test (A10 code.cl:592).  No material is read, an id past the table casts too.
+ *   A casting sample starts with s = seeds[local ray] and makes `samples` AO rays, j = 0 .. samples - 1: AO ray j is the ray
+ *   getHemisphereRay(poi, &s) returns (code.cl:545-579) -- what the j-th of `samples` consecutive bouncePaths calls on the unchanged Poi buffer,
+ *   with the seeds advancing, would store -- then given maxt = radius and, when bias != 0, the origin o.c = p.c + (n.c * bias) per component:
+ *   two fp32 operations, each rounded on its own, not an fma.  bias == 0: the origin is Poi.p bit for bit.
+ *   The AO ray is OCCLUDED by mirt_trace_occluded's definition: mint == maxt after sphereShadowTrace, triangleShadowTrace and a
+ *   triangleShadowTrace per mesh in upload order.
+ *   cast = the number of AO rays made for the pixel (casting samples x `samples`); open = the number of those that are not occluded.  Both are
+ *   integers, so no summation order is involved; a pixel with no hit is {0, 0}.  The lights play no part: an emitter in front of the surface
+ *   is not considered, as in the guides.
+ * READ AND WRITTEN.  `seeds` is read and NEVER written: AO does not advance the frame's random sequence.  Tile-local buffers with global ray ids,
+ * as in a pass: a tile's AO equals the same rows of the whole frame's.  Nothing but ao_out is written.  Reads of the descriptor: the image size,
+ * rays_per_pixel, row0 / nrows, cam, scene_bounds, focal_length, lens_rad, the primitive sets and seeds.  Ignored, and free to be NULL or 0: acu,
+ * pixel, radiance, material, the lights, bounces, pass_index.
+ * CHECKS, all before anything is queued; nothing is written when one fails, and the context works afterwards.  MIRT_E_ARG: a wrong struct_size in
+ * either descriptor, samples 0 or above MIRT_AO_MAX_SAMPLES, radius NaN or <= 0 (+inf is allowed), bias negative, NaN or infinite,
+ * rays_per_pixel that is not k x k, or 1 (the guides' rule: its lens sample draws from seeds[col]), a tile outside the image or of more than
+ * 2^32 - 256 rays, NULL seeds or ao_out, ao_out whose bytes meet the seeds' or a geometry buffer's, a call while capturing.  MIRT_E_RANGE: seeds
+ * shorter than the tile's rays x 4 B, ao_out shorter than the tile's pixels x 8 B.  MIRT_E_DATA: a cell table that fails validation.
+ * MIRT_E_HANDLE: a bad context or buffer.  A held command stream (mirt_ctx_set_fusion, frame fusion) is flushed first; wrapped geometry is
+ * re-validated as for a pass.
+ * KERNEL.  One launch, one lane per pixel walking its samples in order (csrc/pt_kernels_rays.hip k_ao) -- by default the optimistic / exact
+ * pair PER PIXEL, as for the guides: a pixel one of whose primary or AO rays the ray-side guard refuses, or whose grid walk defers, is redone
+ * whole by the exact kernel; mirt_ctx_set_exact_only is honoured.  mirt_ao_deferred: the pixels the last mirt_render_ao re-ran in the exact
+ * kernel, counted when asked, like mirt_trace_deferred.  MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
+#define MIRT_AO_MAX_SAMPLES 64u
+#define MIRT_AO_DEFAULT_SAMPLES 4u
+#define MIRT_AO_DEFAULT_BIAS 0.001f      /* initShadowTrace's own displacement, A10 code.cl:659 */
+typedef struct mirt_ao_desc {
+    uint32_t struct_size;           /* sizeof(mirt_ao_desc)                                        */
+    uint32_t samples;               /* AO rays per hit primary sample, 1 .. MIRT_AO_MAX_SAMPLES     */
+    float radius;                   /* the AO ray's maxt; > 0, +inf allowed                        */
+    float bias;                     /* >= 0, finite; 0: the origin is Poi.p bit for bit            */
+} mirt_ao_desc;
+MIRT_API int mirt_render_ao(mirt_ctx* ctx, const mirt_pass_desc* desc, const mirt_ao_desc* ao, mirt_buf* ao_out);
+MIRT_API int mirt_ao_deferred(mirt_ctx* ctx, uint64_t* pixels);
 /* Edge-avoiding A-TROUS FILTER of a few-rays-per-pixel frame, guided by the first-hit guide buffers: `radiance` as a pass writes it (un-scaled
  * sums), `normal_hits` and `albedo_depth` as mirt_render_guides writes them, all float4 per pixel of a width x height image -- a whole frame, or a
  * gathered one.  Everything stays on the device; the working images live in the context's scratch buffer.
