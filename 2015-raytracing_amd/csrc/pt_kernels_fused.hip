@@ -396,6 +396,18 @@ PT_DEV const FusedArgs& opaque_args() {
     asm volatile("" : "+s"(p));
     return *(const FusedArgs*)p;
 }
+// The arguments for ONE stage of a segment -- the closest hit, lightRender, the shadow stage -- of the kernels without grids: opaque_args() again,
+// made anew at the stage.  What a stage reads of the arguments (the light count and the address of the light records, the set count ...) is
+// loop-invariant, so it was loaded ahead of the segment loop and kept across the other stages' loops, where the 64-register build has no SGPR
+// left for it: 19 v_readlane_b32 / v_writelane_b32 on the straight-line path of every segment of k_fusedPass<true, 0, 0>, VALU issue slots each.
+// Re-read at the stage they are scalar loads from the kernarg segment (cached) and nothing crosses a loop: no lane traffic inside the segment
+// loop, 21 -> 7 spilled SGPRs, 98.68 -> 96.29 ms on the headline frame (profiles/segment_audit).  The grid kernels keep the plain reference:
+// there the extra address registers turned into spilled VGPRs (profiles/segment_audit/README.md has every instance).
+template <int GRIDS>
+PT_DEV const FusedArgs& stage_args(const FusedArgs& P) {
+    if constexpr (GRIDS == 0) return opaque_args();
+    else return P;
+}
 // MULTI: FusedArgs::passes progressive passes in one launch (mirt_render_passes).  Passes interact only through a ray's own seed and its own
 // accumulator, so each lane runs its sample through every pass in a row: the seed stays in a register, the accumulator in the park rows, and
 // both are written once at the end -- bit-identical to that many separate passes.  The unit of the optimistic / exact pair is the same as in
@@ -563,15 +575,16 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
         }
 #endif
       if (MULTI != 2 || !reused) {
-        closest_all<FAST, GRIDS, Park>(P, ray, poi, park, defer);
+        closest_all<FAST, GRIDS, Park>(stage_args<GRIDS>(P), ray, poi, park, defer);
         if constexpr (GUIDES) if (seg == 0 && pass == 0u) {   // the block of the launch as at the resolve below: blockIdx alone, or the marked block of this trip
             const uint32_t blk = FAST || stride != 256u ? blockIdx.x : blockIdx.x * 32u + (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(todo));
             guides_emit(A, ray, poi, valid, blk);
         }
         if (seg == 0) {
-            for (uint32_t l = 0; l < P.n_lights; ++l) {  // lightRender (code.cl:600-629), primary segment only
+            const FusedArgs& PL = stage_args<GRIDS>(P);
+            for (uint32_t l = 0; l < PL.n_lights; ++l) {  // lightRender (code.cl:600-629), primary segment only
                 if (ray.mint == ray.maxt) continue;
-                const LightArgs& L = P.lights[l];
+                const LightArgs& L = PL.lights[l];
                 f3 irr = norm3(ld3(L.light + 6));
                 if (!light_visible(ray, ld3(L.light), ld3(L.light + 3), L.light[9])) continue;
                 ray.mint = PT_INF;
@@ -594,7 +607,7 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : (GRIDS ? PT_FUSED_WAVES_G
         }
 #endif
       }
-        direct_all<FAST, GRIDS, Park>(P, poi, seed, acc, park, defer);
+        direct_all<FAST, GRIDS, Park>(stage_args<GRIDS>(P), poi, seed, acc, park, defer);
     }
 #if PT_PARK_LDS
     if constexpr (EVERY) if (pass + 1u < A.passes) {

@@ -2,6 +2,7 @@
 # profiles/run_profile.sh <tag> -- run on the GPU box (through gpurun) from the repo root.
 # Pass 1: kernel trace + stats of the default bench command.  Passes 2..4: PMC counters, each in
 # its own run with --kernel-trace only (FETCH_SIZE and WRITE_SIZE do not fit one pass on gfx950).
+# PASSES=valu: only SQ_INSTS_VALU and SQ_WAVES, in one run without tracing.
 # Outputs land in gpurun_out/prof_<tag>/; copy the summaries into profiles/ afterwards.
 set -uo pipefail
 TAG="${1:-r1}"
@@ -11,6 +12,11 @@ export TMPDIR=/tmp
 BENCH=(python3 bench.py --steps 2 --warmup 1 --no-cpu --no-depth5 --no-extras)
 # the stamp bench.py checks before it quotes these counters: the kernel sources of THIS tree and the workload of THIS command
 python3 -c 'import json, bench; print(json.dumps({"csrc_sha256": bench.csrc_sha256(), "workload": "cornell_1920x1080_r256_b8_n1", "command": "python3 bench.py --steps 2 --warmup 1 --no-cpu --no-depth5 --no-extras"}))' > "${OUT}/stamp.json" || exit 10
+if [ "${PASSES:-all}" = valu ]; then   # one counter run with nothing traced: the two counters behind "VALU instructions per sample" (an A/B of two builds: MIRT_LIB_PATH)
+  rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d "${OUT}/pmc_valu" -- "${BENCH[@]}" > "${OUT}/pmc_valu.log" 2>&1 || exit 19
+  echo done
+  exit 0
+fi
 rocprofv3 --kernel-trace --stats --output-format csv -d "${OUT}/trace" -- "${BENCH[@]}" > "${OUT}/trace.log" 2>&1 || exit 11
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "${OUT}/pmc_fetch" -- "${BENCH[@]}" > "${OUT}/pmc_fetch.log" 2>&1 || exit 12
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "${OUT}/pmc_write" -- "${BENCH[@]}" > "${OUT}/pmc_write.log" 2>&1 || exit 13

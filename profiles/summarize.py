@@ -7,9 +7,11 @@ import collections, csv, glob, json, os, shutil, sys
 
 src, dst = sys.argv[1], sys.argv[2]
 os.makedirs(dst, exist_ok=True)
-shutil.copy(glob.glob(os.path.join(src, "trace/*/*_kernel_stats.csv"))[0], os.path.join(dst, "kernel_stats.csv"))
+stats = glob.glob(os.path.join(src, "trace/*/*_kernel_stats.csv"))   # (none in a PASSES=valu run)
+if stats:
+    shutil.copy(stats[0], os.path.join(dst, "kernel_stats.csv"))
 out = {}
-for d in ("pmc_fetch", "pmc_write", "pmc_sq", "pmc_sq2", "pmc_mix", "pmc_sq3", "pmc_sqc"):
+for d in ("pmc_fetch", "pmc_write", "pmc_sq", "pmc_sq2", "pmc_mix", "pmc_sq3", "pmc_sqc", "pmc_valu"):
     fs = glob.glob(os.path.join(src, d, "*/*_counter_collection.csv"))
     if not fs:
         continue
@@ -30,7 +32,8 @@ if "_stamp" in out:
     print("stamp:", out["_stamp"])
 g = lambda c: f.get(c, {}).get("mean_per_dispatch", float("nan"))
 waves = g("SQ_WAVES")
-print(open(os.path.join(dst, "kernel_stats.csv")).read().split("\n")[1])
+if stats:
+    print(open(os.path.join(dst, "kernel_stats.csv")).read().split("\n")[1])
 print(f"k_fusedPass: VALU/wave {g('SQ_INSTS_VALU')/waves:.0f}  SALU/wave {g('SQ_INSTS_SALU')/waves:.0f}  VMEM_RD/wave {g('SQ_INSTS_VMEM_RD')/waves:.1f}  "
       f"SMEM/wave {g('SQ_INSTS_SMEM')/waves:.1f}  lane-util {g('SQ_THREAD_CYCLES_VALU')/(g('SQ_INSTS_VALU')*64):.3f}  "
       f"FETCH {g('FETCH_SIZE')*2*1024/1e9:.2f} GB(x2)  WRITE {g('WRITE_SIZE')*1024/1e9:.2f} GB  VGPR {f.get('VGPR_Count')}")
