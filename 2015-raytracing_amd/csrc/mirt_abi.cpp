@@ -133,7 +133,6 @@ struct mirt_buf {
     uint64_t off_version = 0;
     uint32_t off_n = 0;
     uint32_t off_last = 0;
-    uint32_t off_first = 0;       // off[0]: where the first cell's list starts (0 in every table a grid builder makes)
     uint32_t prep_count = 0;   // records in `prep` (the group spheres sit at record index prep_count)
     // prepared-triangle copy of a position buffer (fused path), rebuilt when the contents change
     void* prep = nullptr;
@@ -218,7 +217,6 @@ int check_grid(mirt_ctx* ctx, const char* what, mirt_buf* off, uint32_t n, const
         off->off_version = off->version;
         off->off_n = n;
         off->off_last = h[cells];
-        off->off_first = h[0];
     }
     pin(ctx, off, true);
     const uint64_t count = off->off_last;

@@ -242,6 +242,11 @@ class Buffer:
     def device_ptr(self):
         return lib().mirt_buf_device_ptr(self.h)
 
+    def invalidate(self):
+        """the contents were changed behind the runtime (through device_ptr): mirt_buf_invalidate"""
+        self.ctx._chk(lib().mirt_buf_invalidate(self.h))
+        return self
+
     def release(self):
         if self.h:
             self.ctx._chk(lib().mirt_buf_release(self.h))

@@ -139,11 +139,22 @@ MIRT_API int mirt_enqueue(mirt_ctx* ctx, mirt_kernel* k, unsigned dim, const siz
 #define MIRT_MAX_LIGHTS 8
 #define MIRT_MAX_MESHES 16
 
+/* THE CELL TABLE.  cell_offsets is off = uint[n^3 + 1]: cell c (c = (z * n + y) * n + x) holds the slots [off[c], off[c + 1]) of the
+ * primitive arrays, and its primitives are tested in slot order, exactly as the reference's kernels read the table.  A table is VALID when
+ *   - it is non-decreasing (off[c] <= off[c + 1] for every cell; otherwise MIRT_E_DATA),
+ *   - with n > 1, no cell holds 2^24 slots or more (MIRT_E_RANGE), and
+ *   - prims (and normals, matid where the set has them) hold at least off[n^3] records (MIRT_E_RANGE).
+ * Nothing else is asked of it: off[0] need not be 0, cells may be empty, a primitive may sit in any cell, in several or in none, in any
+ * order and more than once, whether its box touches the cell or not.  The result of every entry point is what the reference's kernels
+ * compute FOR THAT TABLE -- a primitive missing from a cell it crosses is missed there, as in the reference.
+ * The slots before off[0] and the records behind slot off[n^3] belong to no cell: they never influence a result, whatever they hold (a
+ * non-finite record there can only cost time: the optimistic kernel may hand work to the exact one).  The tables of mirt_grid_build and of
+ * the reference's split*Data are the special case off[0] == 0, no slack, input order. */
 typedef struct mirt_grid {          /* one cell-sorted primitive set as the host uploads it        */
     mirt_buf* prims;                /* spheres: float4 (c, r^2) | triangles: 3 x float4 positions  */
     mirt_buf* normals;              /* triangles: 3 x float4 normals; NULL for spheres             */
     mirt_buf* matid;                /* uint per primitive; NULL for a mesh (uses mesh_matid)       */
-    mirt_buf* cell_offsets;         /* uint[n^3 + 1]                                               */
+    mirt_buf* cell_offsets;         /* uint[n^3 + 1]: any valid table (THE CELL TABLE, above)      */
     float bounds[8];                /* (min,1,max,1), bounds2AABB, A10 code.js:610-621             */
     uint32_t n_slabs;
     uint32_t mesh_matid;

@@ -322,10 +322,11 @@ class Tracer:
         self.dev.release()
 
 
-def kernel_by_kernel(ctx, dev, sc, rays):
+def kernel_by_kernel(ctx, dev, sc, rays, shadow_out=None):
     """The library's own kernel-by-kernel path on the same rays: a 48-byte Ray / 64-byte Poi buffer filled here, then the mirt_enqueue sequence
     GranularRenderer._closest issues (the sets' maxt read back between the stages, for `sets`), and the shadow kernels of ._direct on a second
-    copy of the rays.  dev: a mirt.DeviceScene of `ctx`.  -> (hits [n, 8], sets [n], occluded [n])"""
+    copy of the rays.  dev: a mirt.DeviceScene of `ctx`.  shadow_out: a list that receives the n shadow rays (a10_pass.RAY_DT) as the shadow
+    kernels left them.  -> (hits [n, 8], sets [n], occluded [n])"""
     rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
     n = len(rays)
     rb, g1 = _ray_buffer(rays)
@@ -366,6 +367,8 @@ def kernel_by_kernel(ctx, dev, sc, rays):
         for m in dev.meshes:
             kernel("triangleShadowTrace", u32(n), sbuf, m["prims"], m["off"], m["bounds"], u32(m["n"])).enqueue([g1], [64])
         sh = sbuf.read(np.uint8).view(A.RAY_DT)
+        if shadow_out is not None:
+            shadow_out.append(sh[:n].copy())
         with np.errstate(invalid="ignore"):
             occluded = (sh["mint"][:n] == sh["maxt"][:n]).astype(np.uint8)
         return hits, sets, occluded
