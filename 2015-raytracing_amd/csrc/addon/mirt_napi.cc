@@ -320,6 +320,43 @@ bool read_grid(napi_env env, napi_value o, mirt_grid* g) {
 // renderAo(ctx, desc, aoDesc, aoOut): ambient occlusion of the first hit of the same descriptor (seeds are read, not written; material, lights,
 // acu, pixel, radiance are not needed), aoDesc = {samples, radius, bias} -- a number left out is the header's default, radius +Infinity --, aoOut
 // uint32 {open, cast} per pixel of the tile (mirt_render_ao).  aoDeferred(ctx) -> the pixels the last renderAo re-ran in the exact kernel.
+// The primitive sets of a descriptor object -- spheres, triangles, meshes -- into p; sph, tri and meshes are the storage p then points into.
+// `who` names the caller in the TypeError.  false: thrown.
+static bool read_sets(napi_env env, napi_value d, const char* who, mirt_pass_desc& p, mirt_grid& sph, mirt_grid& tri, std::vector<mirt_grid>& meshes) {
+    const auto bad = [&](const char* what) { throw_type(env, (std::string(who) + ": " + what).c_str()); return false; };
+    napi_value v;
+    if (prop(env, d, "spheres", &v)) { if (!read_grid(env, v, &sph)) return bad("spheres"); p.spheres = &sph; }
+    if (prop(env, d, "triangles", &v)) { if (!read_grid(env, v, &tri)) return bad("triangles"); p.triangles = &tri; }
+    if (prop(env, d, "meshes", &v)) {
+        uint32_t n = 0;
+        napi_get_array_length(env, v, &n);
+        meshes.resize(n);
+        for (uint32_t i = 0; i < n; ++i) { napi_value e; napi_get_element(env, v, i, &e); if (!read_grid(env, e, &meshes[i])) return bad("meshes[i]"); }
+    }
+    p.n_meshes = (uint32_t)meshes.size();
+    p.meshes = meshes.data();
+    return true;
+}
+// ... and its lights: [{shadow, scene, light}], 16 floats each
+static bool read_lights(napi_env env, napi_value d, const char* who, mirt_pass_desc& p, std::vector<mirt_light>& lights) {
+    napi_value v;
+    if (prop(env, d, "lights", &v)) {
+        uint32_t n = 0;
+        napi_get_array_length(env, v, &n);
+        lights.resize(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            napi_value e;
+            napi_get_element(env, v, i, &e);
+            if (!prop_floats(env, e, "shadow", lights[i].shadow, 16) || !prop_floats(env, e, "scene", lights[i].scene, 16) || !prop_floats(env, e, "light", lights[i].light, 16)) {
+                throw_type(env, (std::string(who) + ": lights[i] needs shadow/scene/light (16 floats each)").c_str());
+                return false;
+            }
+        }
+    }
+    p.n_lights = (uint32_t)lights.size();
+    p.lights = lights.data();
+    return true;
+}
 enum RenderCall { CALL_PASS, CALL_GUIDES, CALL_FIRST_PASS_GUIDED, CALL_PASSES_GUIDED, CALL_AO };
 static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, RenderCall call, napi_value nhv, napi_value adv) {
     const bool guides = call != CALL_PASS;
@@ -342,30 +379,7 @@ static napi_value render_call(napi_env env, napi_value ctxv, napi_value d, Rende
     mirt_grid sph, tri;
     std::vector<mirt_grid> meshes;
     std::vector<mirt_light> lights;
-    napi_value v;
-    if (prop(env, d, "spheres", &v)) { if (!read_grid(env, v, &sph)) return throw_type(env, "renderPass: spheres"); p.spheres = &sph; }
-    if (prop(env, d, "triangles", &v)) { if (!read_grid(env, v, &tri)) return throw_type(env, "renderPass: triangles"); p.triangles = &tri; }
-    if (prop(env, d, "meshes", &v)) {
-        uint32_t n = 0;
-        napi_get_array_length(env, v, &n);
-        meshes.resize(n);
-        for (uint32_t i = 0; i < n; ++i) { napi_value e; napi_get_element(env, v, i, &e); if (!read_grid(env, e, &meshes[i])) return throw_type(env, "renderPass: meshes[i]"); }
-    }
-    if (prop(env, d, "lights", &v)) {
-        uint32_t n = 0;
-        napi_get_array_length(env, v, &n);
-        lights.resize(n);
-        for (uint32_t i = 0; i < n; ++i) {
-            napi_value e;
-            napi_get_element(env, v, i, &e);
-            if (!prop_floats(env, e, "shadow", lights[i].shadow, 16) || !prop_floats(env, e, "scene", lights[i].scene, 16) || !prop_floats(env, e, "light", lights[i].light, 16))
-                return throw_type(env, "renderPass: lights[i] needs shadow/scene/light (16 floats each)");
-        }
-    }
-    p.n_meshes = (uint32_t)meshes.size();
-    p.meshes = meshes.data();
-    p.n_lights = (uint32_t)lights.size();
-    p.lights = lights.data();
+    if (!read_sets(env, d, "renderPass", p, sph, tri, meshes) || !read_lights(env, d, "renderPass", p, lights)) return nullptr;
     p.material = prop_buf(env, d, "material");
     p.seeds = prop_buf(env, d, "seeds");
     p.acu = prop_buf(env, d, "acu");
@@ -456,17 +470,7 @@ static napi_value trace_call(napi_env env, napi_value* argv, bool any) {
     p.struct_size = sizeof p;
     mirt_grid sph, tri;
     std::vector<mirt_grid> meshes;
-    napi_value v;
-    if (prop(env, argv[1], "spheres", &v)) { if (!read_grid(env, v, &sph)) return throw_type(env, "trace: spheres"); p.spheres = &sph; }
-    if (prop(env, argv[1], "triangles", &v)) { if (!read_grid(env, v, &tri)) return throw_type(env, "trace: triangles"); p.triangles = &tri; }
-    if (prop(env, argv[1], "meshes", &v)) {
-        uint32_t n = 0;
-        napi_get_array_length(env, v, &n);
-        meshes.resize(n);
-        for (uint32_t i = 0; i < n; ++i) { napi_value e; napi_get_element(env, v, i, &e); if (!read_grid(env, e, &meshes[i])) return throw_type(env, "trace: meshes[i]"); }
-    }
-    p.n_meshes = (uint32_t)meshes.size();
-    p.meshes = meshes.data();
+    if (!read_sets(env, argv[1], "trace", p, sph, tri, meshes)) return nullptr;
     const int rc = any ? mirt_trace_occluded((mirt_ctx*)c, &p, (mirt_buf*)rays, (uint64_t)count, (mirt_buf*)o0)
                        : mirt_trace_closest((mirt_ctx*)c, &p, (mirt_buf*)rays, (uint64_t)count, (mirt_buf*)o0, (mirt_buf*)o1);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
@@ -486,6 +490,49 @@ napi_value TraceDeferred(napi_env env, napi_callback_info info) {
     if (!get_ext(env, argv[0], &c)) return throw_type(env, "traceDeferred(ctx)");
     uint64_t n = 0;
     int rc = mirt_trace_deferred((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
+}
+
+// Path radiance of the caller's own rays.  traceRadiance(ctx, desc, radDesc, rays, count, seeds, radiance): the pass's path from each of `count`
+// 32-byte rays on, radDesc = {samples, flags} (left out: 1, 0) -- seeds (int32 per ray) advanced in place, radiance the float4 accumulator per ray
+// (mirt_trace_radiance).  Of desc the sets, lights, material and bounces (left out: 5) are read.  radianceDeferred(ctx) -> how many rays the last
+// call re-ran in the exact kernel (mirt_radiance_deferred).
+napi_value TraceRadiance(napi_env env, napi_callback_info info) {
+    ARGS(7);
+    void *c, *rays = nullptr, *seeds = nullptr, *radiance = nullptr;
+    double count = 0;
+    if (!get_ext(env, argv[0], &c) || !get_f64(env, argv[4], &count) || !(count >= 0) || count > 18446744073709549568.0)
+        return throw_type(env, "traceRadiance(ctx, desc, radDesc, rays, count, seeds, radiance)");
+    get_ext(env, argv[3], &rays);
+    get_ext(env, argv[5], &seeds);
+    get_ext(env, argv[6], &radiance);
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    p.bounces = 5;
+    prop_u32(env, argv[1], "bounces", &p.bounces);
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    std::vector<mirt_light> lights;
+    if (!read_sets(env, argv[1], "traceRadiance", p, sph, tri, meshes) || !read_lights(env, argv[1], "traceRadiance", p, lights)) return nullptr;
+    p.material = prop_buf(env, argv[1], "material");
+    mirt_radiance_desc rd = {(uint32_t)sizeof(mirt_radiance_desc), 1u, 0u, 0u};
+    napi_valuetype t = napi_undefined;
+    if (napi_typeof(env, argv[2], &t) == napi_ok && t == napi_object) {
+        prop_u32(env, argv[2], "samples", &rd.samples);
+        prop_u32(env, argv[2], "flags", &rd.flags);
+    }
+    const int rc = mirt_trace_radiance((mirt_ctx*)c, &p, &rd, (mirt_buf*)rays, (uint64_t)count, (mirt_buf*)seeds, (mirt_buf*)radiance);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value RadianceDeferred(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "radianceDeferred(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_radiance_deferred((mirt_ctx*)c, &n);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return mk_num(env, (double)n);
 }
@@ -924,7 +971,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"renderAo", RenderAo}, {"aoDeferred", AoDeferred}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

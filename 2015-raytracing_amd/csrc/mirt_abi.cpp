@@ -80,6 +80,9 @@ struct mirt_ctx {
     void* ao_defer = nullptr;     // mirt_render_ao, optimistic pair: [count, pad, pad, pad | a bit per pixel of the tile], its own allocation too
     size_t ao_defer_bytes = 0;
     uint32_t ao_defer_words = 0;  // mask words the last mirt_render_ao used (0: it ran the exact kernel only)
+    void* rad_defer = nullptr;    // mirt_trace_radiance, optimistic pair: [count, pad, pad, pad | a bit per ray], its own allocation too
+    size_t rad_defer_bytes = 0;
+    uint32_t rad_defer_words = 0; // mask words the last mirt_trace_radiance used (0: it ran the exact kernel only, or queued nothing)
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     int force_exact = 0;          // mirt_ctx_set_exact_only: 1 = skip the optimistic kernel, run every sample through the exact one
@@ -381,6 +384,7 @@ static int destroy_ctx(mirt_ctx* ctx) {
     if (ctx->guide_mask) (void)hipFree(ctx->guide_mask);
     if (ctx->ray_defer) (void)hipFree(ctx->ray_defer);
     if (ctx->ao_defer) (void)hipFree(ctx->ao_defer);
+    if (ctx->rad_defer) (void)hipFree(ctx->rad_defer);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1273,6 +1277,7 @@ static pt::PassRequest pass_request(const mirt_ctx* ctx, const mirt_pass_desc* d
 // bounds, primitive sets (validated and prepared: fill_grid) and material of `A`.  guides: the lights and pass_index are not looked at.
 // !with_material (mirt_render_ao, with guides): nor is the material.
 static int fill_sets(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, pt::FusedArgs& A);
+static int fill_shading(mirt_ctx* ctx, const mirt_pass_desc* d, pt::FusedArgs& A, bool with_material);
 static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bool guides, pt::FusedArgs& A, bool with_material = true) {
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (!d->width || !d->height || !d->rays_per_pixel) return fail(ctx, MIRT_E_ARG, "%s: empty image", fn);
@@ -1305,12 +1310,19 @@ static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bo
     A.n_lights = guides ? 0u : d->n_lights;
     int rc;
     if ((rc = fill_sets(ctx, fn, d, A))) return rc;
+    return fill_shading(ctx, d, A, with_material);
+}
+
+// The A.n_lights light records of a descriptor and, with_material, its material table: what a pass and mirt_trace_radiance shade with.  The
+// caller has checked n_lights and the light array.
+static int fill_shading(mirt_ctx* ctx, const mirt_pass_desc* d, pt::FusedArgs& A, bool with_material) {
     for (uint32_t l = 0; l < A.n_lights; ++l) {
         memcpy(A.lights[l].shadow, d->lights[l].shadow, 64);
         memcpy(A.lights[l].scene, d->lights[l].scene, 64);
         memcpy(A.lights[l].light, d->lights[l].light, 64);
     }
     if (!with_material) return MIRT_OK;
+    int rc;
     if ((rc = need(ctx, "material", d->material, 16))) return rc;
     A.material = d->material->ptr;
     A.nmat = (uint32_t)(d->material->bytes / 16);
@@ -1758,6 +1770,84 @@ int mirt_trace_deferred(mirt_ctx* ctx, uint64_t* rays) try {
     *rays = count;
     return MIRT_OK;
 } MIRT_CATCH("mirt_trace_deferred", return MIRT_E_DEVICE)
+
+// ---- path radiance of caller-supplied rays (pt_kernels_rays.hip k_traceRadiance): mirt_trace_radiance.  Every check comes before anything is
+// queued; then one launch -- or the optimistic / exact pair, per ray -- of one lane per ray.  Nothing but seeds and radiance is written.
+int mirt_trace_radiance(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_radiance_desc* rd, mirt_buf* rays, uint64_t count, mirt_buf* seeds, mirt_buf* radiance) try {
+    const char* const fn = "mirt_trace_radiance";
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, fn);
+    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
+    if (!rd || rd->struct_size != sizeof(mirt_radiance_desc)) return fail(ctx, MIRT_E_ARG, "%s: radiance descriptor size mismatch", fn);
+    if (!rd->samples || rd->samples > MIRT_RADIANCE_MAX_SAMPLES) return fail(ctx, MIRT_E_ARG, "%s: samples %u outside 1..%u", fn, rd->samples, MIRT_RADIANCE_MAX_SAMPLES);
+    if (rd->flags & ~(MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_NO_EMITTERS)) return fail(ctx, MIRT_E_ARG, "%s: unknown flags 0x%x", fn, rd->flags);
+    if (rd->reserved) return fail(ctx, MIRT_E_ARG, "%s: reserved is %u, not 0", fn, rd->reserved);
+    if (count > 0xFFFFFF00ull) return fail(ctx, MIRT_E_ARG, "%s: %llu rays in one call (the kernels index a call's rays with 32 bits); split the batch", fn, (unsigned long long)count);
+    if (!seeds || !radiance) return fail(ctx, MIRT_E_ARG, "%s: %s is NULL", fn, seeds ? "radiance" : "seeds");
+    // the pass's own limits and rules for its arrays (pass_setup)
+    if (d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
+    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
+    if ((d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
+    if (!rays) return fail(ctx, MIRT_E_HANDLE, "%s: rays is NULL", fn);
+    int rc;
+    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[3] = {{"rays", rays, count * 32}, {"seeds", seeds, count * 4}, {"radiance", radiance, count * 16}};
+    for (const auto& b : io)
+        if ((rc = need(ctx, (std::string(fn) + " " + b.label).c_str(), b.buf, b.bytes))) return rc;
+    if ((rc = need(ctx, "material", d->material, 16))) return rc;
+    {   // seeds and radiance are both written: the bytes the call touches of them, against the rays', the geometry's buffers and the material whole
+        std::vector<pt::PostRange> in;
+        in.push_back({(uint64_t)(uintptr_t)rays->ptr, count * 32, true});
+        add_range(in, d->material);
+        add_geometry_ranges(in, d);
+        const pt::PostRange out[2] = {{(uint64_t)(uintptr_t)seeds->ptr, count * 4, true}, {(uint64_t)(uintptr_t)radiance->ptr, count * 16, true}};
+        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 2);
+        if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: the seeds' or the radiance's bytes meet the rays', a geometry buffer's or the material's", fn);
+        if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: seeds aliases radiance", fn);
+    }
+    if (!count) return MIRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::FusedArgs A;
+    memset(&A, 0, sizeof A);
+    A.bounces = d->bounces;
+    A.n_lights = d->n_lights;
+    if ((rc = fill_sets(ctx, fn, d, A))) return rc;
+    if ((rc = fill_shading(ctx, d, A, true))) return rc;
+    ctx->rad_defer_words = 0;
+    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
+        const uint32_t words = (uint32_t)((count + 31u) / 32u);
+        if ((rc = grow_and_clear(ctx, ctx->rad_defer, ctx->rad_defer_bytes, 16u + (size_t)words * 4u))) return rc;
+        uint32_t* const mask = (uint32_t*)ctx->rad_defer + 4;
+        pt::launch_radiance(ctx->stream, A, true, rays->ptr, (uint32_t)count, rd->samples, rd->flags, (int32_t*)seeds->ptr, radiance->ptr, mask, nullptr);
+        pt::launch_radiance(ctx->stream, A, false, rays->ptr, (uint32_t)count, rd->samples, rd->flags, (int32_t*)seeds->ptr, radiance->ptr, nullptr, mask);
+        ctx->rad_defer_words = words;
+    } else {
+        pt::launch_radiance(ctx->stream, A, false, rays->ptr, (uint32_t)count, rd->samples, rd->flags, (int32_t*)seeds->ptr, radiance->ptr, nullptr, nullptr);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    seeds->version++;
+    radiance->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_trace_radiance", return MIRT_E_DEVICE)
+
+int mirt_radiance_deferred(mirt_ctx* ctx, uint64_t* rays) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_radiance_deferred: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_radiance_deferred");
+    if (!rays) return fail(ctx, MIRT_E_ARG, "mirt_radiance_deferred: null output");
+    *rays = 0;
+    if (!ctx->rad_defer_words) return MIRT_OK;
+    // counted on demand: the mask of the last mirt_trace_radiance is still in place (the next one clears it)
+    uint32_t* counters = (uint32_t*)ctx->rad_defer;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
+    pt::launch_deferCount(ctx->stream, counters + 4, ctx->rad_defer_words, counters);
+    uint32_t count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *rays = count;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_radiance_deferred", return MIRT_E_DEVICE)
 
 // ---- the post-process stage: mirt_filter_atrous and mirt_upsample_guided.  The argument rules they share are pt_post_check.hpp's (host-only,
 // CPU-tested); here are those rules' messages, `fn` being the entry point's name, and the shared epilogue.

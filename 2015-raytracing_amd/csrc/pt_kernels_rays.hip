@@ -15,7 +15,7 @@
 // kernel adds its guard and the winning set's index through RayHooks), the sets get the LDS slots the pass gives them and the kernel instance
 // those call for (fused_lds_slots, fused_lds_dispatch), and the optimistic / exact pair is the pass's -- here per RAY: a ray the ray-side guard
 // refuses, or whose walk defers, sets its bit and writes nothing, and the exact kernel redoes the marked rays.
-// The any-hit loop (rays_any) is still stated twice, here and in the shadow stage of direct_all (pt_kernels_fused.hip): every shared form that was
+// The any-hit loop (rays_any) is still stated twice, here and in the shadow stage of direct_all (pt_direct.hpp): every shared form that was
 // tried re-allocated registers in k_fusedPass, whose rule is identical assembly (profiles/shared_loops/README.md).  A change to one is a change to both.
 //
 // Structure: one lane per ray, two float4 loads, the query, two float4 stores (and the optional uint32), or one byte.  With grids every lane of a
@@ -27,8 +27,9 @@
 // them; profiles/rays/timing.json has the measured cost).  The guard windows are what makes the optimistic kernel's divisions exact and are not
 // widened for this.
 //
-// Also here, because it runs rays_any: k_ao, ambient occlusion of the first hit (mirt_render_ao) -- at the end of the file.
-#include "pt_closest.hpp"
+// Also here, because it runs rays_any: k_ao, ambient occlusion of the first hit (mirt_render_ao); and because it starts at a caller's ray:
+// k_traceRadiance, the pass's path from that ray on (mirt_trace_radiance) -- at the end of the file.
+#include "pt_direct.hpp"
 
 namespace pt {
 
@@ -62,7 +63,7 @@ struct RayHooks : ClosestHooks {
     PT_DEV void won(uint32_t s) const { set = s; }
 };
 
-// the per-set loop of the fused pass's shadow stage (pt_kernels_fused.hip direct_all) on the caller's ray: the second statement of that loop,
+// the per-set loop of the fused pass's shadow stage (pt_direct.hpp direct_all) on the caller's ray: the second statement of that loop,
 // to be kept in step with the first by hand (see the header)
 template <bool FAST, int GRIDS>
 PT_DEV void rays_any(const FusedArgs& A, Ray& sh, bool& defer) {
@@ -267,6 +268,144 @@ void launch_ao(hipStream_t s, const FusedArgs& a, bool fast, uint32_t samples, f
     const FusedLds L = fused_lds_slots(b, fast);
     if (fast) launch_ao_t<true>(s, b, L, samples, radius, bias, (uint2*)ao_out, defer_mask, nullptr);
     else launch_ao_t<false>(s, b, L, samples, radius, bias, (uint2*)ao_out, nullptr, redo_mask);
+}
+
+// ---- path radiance of caller-supplied rays (mirt_trace_radiance): the pass's path -- closest hit, lightRender, then per segment the per-light
+// shadow stage and shade, bouncePaths between the segments -- started at the CALLER's ray instead of initTrace's, `samples` times per ray, in one
+// launch.  The definition is include/mirt.h's: executeRender (A10 code.js:1806-1854) without initTrace and copyToPixel.  The pieces are the pass's:
+// closest_all (with this file's guard and the division kept in the loop: a caller's d is not of unit length), the lightRender loop as k_fusedPass
+// states it, direct_all with the park rows (pt_direct.hpp), bounce_ray.
+//
+// Structure: one lane per ray; two float4 loads per sample for the ray (they hit the cache after the first; held in registers across the path they
+// were eight more live VGPRs), the seed and, with MIRT_RADIANCE_ACCUMULATE, the accumulator once; one float4 store and one seed store.  `samples`,
+// the bounce count and the flags are kernel arguments and so WAVE-UNIFORM: in the grid variants every lane of a wave enters every shared-test walk
+// together (pt_trace_coop.hpp).  A lane without a ray and a redo kernel's unmarked lane ride along dead -- they hit nothing, so they shade and
+// bounce nothing -- and write nothing.  The optimistic / exact pair is per RAY, as in k_traceRays: a ray whose primary, shadow or bounce ray the
+// guard refuses in any sample, or whose walk defers, sets its bit and writes neither its seed nor its accumulator; the exact kernel redoes the
+// marked rays from the start, all samples.
+// Not built: samples after the first reusing the primary ray's closest hit and lightRender verdict (k_fusedPass's MULTI 2 does it for the camera).
+// Waves per SIMD the register allocator is held to, A/B switches like k_ao's (profiles/radiance/README.md has the registers per instance and the
+// measurement).  A lane runs samples * (1 + bounces) segments back to back with nothing to overlap them but other waves, and more waves paid at
+// every step measured, the spilled registers included: at 1920 x 1080 x 4 rays, bounces 5, cornell_teapot3 6.44 (4 waves, 107 VGPRs) -> 5.49 (5,
+// 96 VGPRs) -> 5.08 ms (6, 80 VGPRs, 16 to 20 spilled), cornell 1.29 (5 waves) -> 1.21 (6) -> 1.14 (7, 72 VGPRs, 2 to 8 spilled) -> 1.15 ms (8).
+#ifndef PT_RADIANCE_GRID_WAVES
+#define PT_RADIANCE_GRID_WAVES 6
+#endif
+#ifndef PT_RADIANCE_CELL_WAVES
+#define PT_RADIANCE_CELL_WAVES 7
+#endif
+#define PT_RADIANCE_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_RADIANCE_GRID_WAVES : PT_RADIANCE_CELL_WAVES)
+constexpr uint32_t kRadianceAccumulate = 1u, kRadianceNoEmitters = 2u;   // MIRT_RADIANCE_ACCUMULATE, MIRT_RADIANCE_NO_EMITTERS (include/mirt.h)
+// the pass's park rows as closest_all's hooks, with this file's guard and kept division in place of the camera kernels'
+struct RadiancePark : Park {
+    PT_DEV void guard(Ray& ray, bool& defer) const { guard_or_retire(ray, defer); }
+    PT_DEV void top(Ray& ray) const { keep_in_loop(ray); }
+};
+template <bool FAST, int GRIDS>
+__global__ void PT_RADIANCE_BOUNDS(GRIDS) k_traceRadiance(const FusedArgs A, const float4* __restrict__ rays, uint32_t count, uint32_t samples, uint32_t flags,
+                                                           int32_t* __restrict__ seeds, float4* __restrict__ radiance, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    stage_block<FAST, GRIDS>(A);
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;   // (count <= 2^32 - 256: mirt_trace_radiance)
+    bool valid = id < count;
+    if (!FAST && redo_mask && valid) valid = (redo_mask[id >> 5] >> (id & 31u) & 1u) != 0u;
+    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
+    else if (!valid) return;
+    int32_t seed = 0;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // initAcu (A10 code.cl:448-456)
+    if (valid) {
+        seed = seeds[id];
+        if (flags & kRadianceAccumulate) acc = radiance[id];
+    }
+    RadiancePark park;
+#if PT_PARK_LDS
+    __shared__ __attribute__((aligned(16))) float park_mem[PT_PARK_WORDS(GRIDS)][256];
+    park.base = &park_mem[0][threadIdx.x];
+    park.put(0, acc.x); park.put(1, acc.y); park.put(2, acc.z); park.put(3, acc.w);
+#endif
+    bool defer = false;
+    for (uint32_t j = 0; j < samples; ++j) {
+        Ray ray;   // a lane without a ray rides along dead: it enters the shared walks and tests nothing of its own
+        ray.o = mk3(0.0f, 0.0f, 0.0f); ray.d = mk3(0.0f, 0.0f, 0.0f); ray.mint = 0.0f; ray.maxt = 0.0f;
+        if (valid) {
+            const float4 a = rays[2u * (size_t)id], b = rays[2u * (size_t)id + 1u];
+            ray.o = mk3(a.x, a.y, a.z); ray.mint = a.w;
+            ray.d = mk3(b.x, b.y, b.z); ray.maxt = b.w;
+        }
+        Poi poi;   // as initTrace resets it (code.cl:538-541)
+        poi.p = mk3(0.0f, 0.0f, 0.0f);
+        poi.n = mk3(0.0f, 0.0f, 0.0f);
+        poi.atte = mk3(1.0f, 1.0f, 1.0f);
+        poi.matId = -1;
+#if PT_PARK_LDS
+        park.put(4, 1.0f); park.put(5, 1.0f); park.put(6, 1.0f);   // every sample's path starts unattenuated; the accumulator goes on
+#endif
+        // segment 0 is the caller's ray; segments 1..bounces start with bouncePaths (code.js:1829-1846)
+        for (uint32_t seg = 0; seg <= A.bounces; ++seg) {
+            if (seg > 0) {
+                if (poi.matId >= 0) {
+#if PT_PARK_LDS
+                    if (PT_PARK_PN_FOR(GRIDS)) park.get_pn(poi);
+#endif
+                    ray = bounce_ray(poi, seed);
+                } else {
+                    ray.mint = PT_INF;
+                    ray.maxt = PT_INF;
+                }
+            }
+            closest_all<FAST, GRIDS>(A, ray, poi, park, defer);
+            if (seg == 0 && !(flags & kRadianceNoEmitters)) {
+                for (uint32_t l = 0; l < A.n_lights; ++l) {  // lightRender (code.cl:600-629), on the caller's ray only
+                    if (ray.mint == ray.maxt) continue;
+                    const LightArgs& L = A.lights[l];
+                    f3 irr = norm3(ld3(L.light + 6));
+                    if (!light_visible(ray, ld3(L.light), ld3(L.light + 3), L.light[9])) continue;
+                    ray.mint = PT_INF;
+                    ray.maxt = PT_INF;
+                    poi.matId = -1;
+#if PT_PARK_LDS
+                    park.acc_add(irr.x, irr.y, irr.z);
+#else
+                    acc.x += irr.x; acc.y += irr.y; acc.z += irr.z; acc.w += 1.0f;
+#endif
+                }
+            }
+            direct_all<FAST, GRIDS>(A, poi, seed, acc, park, defer);
+        }
+    }
+    if (FAST) {   // the deferred rays' bits: a wave's ballot, a word each from lanes 0 and 32 (see k_traceRays)
+        const unsigned long long dm = __builtin_amdgcn_ballot_w64(valid && defer);
+        const uint32_t lane = threadIdx.x & 63u;
+        if (valid && (lane & 31u) == 0u) {
+            const uint32_t w = (uint32_t)(dm >> lane);
+            if (w) defer_mask[id >> 5] = w;
+        }
+    }
+    if (!valid || (FAST && defer)) return;   // the exact kernel redoes a deferred ray: nothing of it is written
+    seeds[id] = seed;
+#if PT_PARK_LDS
+    acc = make_float4(park.get(0), park.get(1), park.get(2), park.get(3));
+#endif
+    radiance[id] = acc;
+}
+
+template <bool FAST>
+static void launch_radiance_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const float4* rays, uint32_t count, uint32_t samples, uint32_t flags, int32_t* seeds,
+                              float4* radiance, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
+    fused_lds_dispatch(L, [&](auto G, size_t lds) {
+        hipLaunchKernelGGL((k_traceRadiance<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, rays, count, samples, flags, seeds, radiance, defer_mask, redo_mask);
+    });
+}
+// fast: the optimistic kernel (sets the deferred rays' bits in defer_mask, one per ray); !fast: the exact kernel over the rays of redo_mask, or
+// over every ray when it is null.
+void launch_radiance(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, uint32_t samples, uint32_t flags, int32_t* seeds, void* radiance,
+                     uint32_t* defer_mask, const uint32_t* redo_mask) {
+    if (!count) return;
+    FusedArgs b = a;
+    b.rpp = 1u;   // stage_block: no lens table
+    const FusedLds L = fused_lds_slots(b, fast);
+    if (fast) launch_radiance_t<true>(s, b, L, (const float4*)rays, count, samples, flags, seeds, (float4*)radiance, defer_mask, nullptr);
+    else launch_radiance_t<false>(s, b, L, (const float4*)rays, count, samples, flags, seeds, (float4*)radiance, nullptr, redo_mask);
 }
 
 }  // namespace pt

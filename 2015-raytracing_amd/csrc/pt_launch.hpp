@@ -154,6 +154,12 @@ void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays,
 // of the tile, {open, cast}.  One lane per pixel; the optimistic / exact pair as in launch_guides, the mask one bit per pixel.  Reads the camera,
 // bounds and sets of `a` and a.seeds (int32 per tile-local ray, never written); not its material or lights.
 void launch_ao(hipStream_t s, const FusedArgs& a, bool fast, uint32_t samples, float radius, float bias, void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask);
+// Path radiance of caller-supplied rays (pt_kernels_rays.hip k_traceRadiance; the definition is mirt_trace_radiance's comment in include/mirt.h):
+// `samples` runs of the pass's path per ray, from the caller's ray on.  rays: two float4 per ray; seeds: int32 per ray, read and written; radiance:
+// float4 per ray, the accumulator (read first with flags & 1).  The optimistic / exact pair as in launch_rays, the mask one bit per ray.  Reads the
+// sets, lights, material, nmat and bounces of `a` and nothing else of it.
+void launch_radiance(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, uint32_t samples, uint32_t flags, int32_t* seeds, void* radiance,
+                     uint32_t* defer_mask, const uint32_t* redo_mask);
 // Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
 // every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
 struct FilterArgs {

@@ -7,6 +7,7 @@
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
 //   node cli.js trace  <scene.xml> <rays.f32> <out.f32> [--occluded] [--sets out.u32]  -> ray queries on the caller's own rays (mirt_trace_closest): rays.f32 holds raw 32-byte records {o.xyz, mint, d.xyz, maxt}, out.f32 receives {normal.xyz, t, p.xyz, matId (int32)} per ray, --sets the uint32 index of the winning set per ray; --occluded: <out.f32> receives one byte per ray instead, 1 iff something blocks it (mirt_trace_occluded)
+//   node cli.js trace  <scene.xml> <rays.f32> <out.f32> --radiance [--samples S] [--bounces B] [--seed-base X] [--no-emitters]  -> path radiance of the caller's own rays in one launch (mirt_trace_radiance): out.f32 receives 16 bytes per ray, the accumulator {r, g, b sums, number of contributions} of S (default 1) runs of the pass's path with B (default 5) bounces from each ray on; seeds from mirt_seed_fill(first_ray = 0, count, X); --no-emitters: the lights are not rendered on the caller's ray (it continues a path whose vertex already sampled them)
 //   node cli.js devices                                                             -> what webcl.getPlatforms()/getDevices() report
 "use strict";
 const fs = require("fs");
@@ -23,7 +24,7 @@ function writeFrame(out, px, w, h) {
 }
 
 function usage() {
-  process.stderr.write(fs.readFileSync(__filename, "utf8").split("\n").slice(1, 12).join("\n") + "\n");
+  process.stderr.write(fs.readFileSync(__filename, "utf8").split("\n").slice(1, 13).join("\n") + "\n");
   process.exit(2);
 }
 
@@ -164,6 +165,14 @@ if (cmd === "pack") {
   if (raw.length % 32) { process.stderr.write(`${rest[1]}: ${raw.length} bytes is not a whole number of 32-byte rays\n`); process.exit(2); }
   const rays = new Float32Array(raw.length / 4);
   Buffer.from(rays.buffer).set(raw);   // (a file's bytes need not sit 4-byte aligned in node's pool)
+  if (rest.includes("--radiance")) {
+    if (si >= 0 || rest.includes("--occluded")) { process.stderr.write("--radiance goes without --sets and --occluded\n"); process.exit(2); }
+    const num = (flag, dflt) => { const i = rest.indexOf(flag); if (i < 0) return dflt; const v = Number(rest[i + 1]); if (!Number.isInteger(v) || v < 0) usage(); return v; };
+    const res = renderer.traceFile(rest[0], rays, { radiance: { samples: num("--samples", 1), bounces: num("--bounces", 5), seedBase: num("--seed-base", 0), noEmitters: rest.includes("--no-emitters") } });
+    fs.writeFileSync(rest[2], Buffer.from(res.radiance.buffer, res.radiance.byteOffset, res.radiance.byteLength));
+    process.stderr.write(`traced ${rays.length / 8} rays of ${rest[1]} through ${rest[0]}: path radiance; rays redone by the exact kernel: ${res.deferred}\n`);
+    process.exit(0);
+  }
   const occluded = rest.includes("--occluded");
   if (occluded && si >= 0) { process.stderr.write("--sets goes with the closest-hit query, not with --occluded\n"); process.exit(2); }
   const res = renderer.traceFile(rest[0], rays, { occluded: occluded, sets: si >= 0 });

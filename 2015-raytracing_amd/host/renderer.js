@@ -705,6 +705,8 @@ function renderUpscaled(file, width, height, rpp, passes, factor, opt) {
 // Ray queries on a scene file (queue.traceClosest / traceOccluded): `rays` a Float32Array of 8 floats per ray {o.xyz, mint, d.xyz, maxt}.
 // opt.occluded: -> {occluded: Uint8Array}; else -> {hits: Float32Array of 8 per ray (matId as int32 bits in the 8th), sets: Uint32Array | undefined
 // (opt.sets)}; both with `deferred`, the rays the exact kernel redid.  The camera and the image size play no part.
+// opt.radiance = {samples, bounces, seedBase, noEmitters}: -> {radiance: Float32Array of 4 per ray, the accumulator of the pass's path from
+// each ray on (queue.traceRadiance), deferred}.
 function traceFile(file, rays, opt) {
   opt = opt || {};
   const n = Math.floor(rays.length / 8);
@@ -716,6 +718,18 @@ function traceFile(file, rays, opt) {
   const rb = mk(n * 32);
   if (n) q.enqueueWriteBuffer(rb, false, 0, n * 32, rays.subarray(0, n * 8), []);
   const res = {};
+  if (opt.radiance) {
+    // path radiance (queue.traceRadiance): opt.radiance = {samples, bounces, seedBase, noEmitters}; seeds from seedFill(0, n, seedBase)
+    const o = opt.radiance, sb = mk(n * 4), ab = mk(n * 16);
+    if (n) q.seedFill(sb, 0, n, o.seedBase || 0);
+    q.traceRadiance({ spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, lights: packed.lights, material: dev.material, bounces: o.bounces === undefined ? 5 : o.bounces },
+                    { samples: o.samples === undefined ? 1 : o.samples, flags: o.noEmitters ? 2 : 0 }, rb, n, sb, ab);
+    res.radiance = new Float32Array(n * 4);
+    if (n) q.enqueueReadBuffer(ab, true, 0, n * 16, res.radiance, []);
+    res.deferred = q.radianceDeferred();
+    ctx.release();
+    return res;
+  }
   if (opt.occluded) {
     const ob = mk(n);
     q.traceOccluded(desc, rb, n, ob);

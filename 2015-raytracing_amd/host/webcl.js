@@ -219,6 +219,18 @@ class WebCLCommandQueue {
     wrap(() => native().traceOccluded(this.ctx.h, d, rays ? rays.h : null, count, occluded ? occluded.h : null));
   }
   traceDeferred() { return wrap(() => native().traceDeferred(this.ctx.h)); }
+  // ---- extension: path radiance of the caller's own rays in one launch (mirt_trace_radiance; include/mirt.h has the definition): the pass's path
+  // -- closest hit, lightRender, per-light shadow and shade, desc.bounces bounces (left out: 5) -- from each of `count` 32-byte rays on,
+  // radDesc = {samples, flags} (left out: 1, 0; flags: RADIANCE_ACCUMULATE 1, RADIANCE_NO_EMITTERS 2).  seeds: an int32 per ray, advanced in
+  // place; radiance: the float4 accumulator per ray, rgb sums and the number of contributions.  Of desc spheres, triangles, meshes, lights,
+  // material and bounces are read.  radianceDeferred(): the rays the last call re-ran in the exact kernel.
+  hasTraceRadiance() { return typeof native().traceRadiance === "function"; }
+  traceRadiance(desc, radDesc, rays, count, seeds, radiance) {
+    const d = Object.assign(this._setsDesc(desc), { lights: desc.lights || [], material: desc.material ? desc.material.h : undefined });
+    if (desc.bounces !== undefined) d.bounces = desc.bounces;
+    wrap(() => native().traceRadiance(this.ctx.h, d, radDesc || {}, rays ? rays.h : null, count, seeds ? seeds.h : null, radiance ? radiance.h : null));
+  }
+  radianceDeferred() { return wrap(() => native().radianceDeferred(this.ctx.h)); }
   // ---- extension: a frame's first pass and its guide buffers in one call (mirt_render_first_pass_guided): every buffer ends as after
   // renderPass(desc with firstPass) followed by renderGuides(desc, normalHits, albedoDepth) -- where the pass resolves its pixels at 4, 16 or 64 rays
   // per pixel the pass's own launch writes the guides (ctx.guidedPasses() counts those calls), elsewhere the guide launches follow it.

@@ -82,8 +82,13 @@ class _AoDesc(C.Structure):   # mirt_ao_desc
     _fields_ = [("struct_size", C.c_uint32), ("samples", C.c_uint32), ("radius", C.c_float), ("bias", C.c_float)]
 
 
+class _RadianceDesc(C.Structure):   # mirt_radiance_desc
+    _fields_ = [("struct_size", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 _lib = None
 
+RADIANCE_ACCUMULATE, RADIANCE_NO_EMITTERS, RADIANCE_MAX_SAMPLES = 1, 2, 64   # MIRT_RADIANCE_* (include/mirt.h)
 AO_MAX_SAMPLES, AO_DEFAULT_SAMPLES, AO_DEFAULT_BIAS = 64, 4, 0.001   # MIRT_AO_* (include/mirt.h)
 
 PASSES_FRESH = 1   # MIRT_PASSES_FRESH (include/mirt.h)
@@ -135,6 +140,8 @@ SYMBOLS = {
     "mirt_trace_closest": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "mirt_trace_occluded": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.c_void_p, C.c_uint64, C.c_void_p]),
     "mirt_trace_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_trace_radiance": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_RadianceDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "mirt_radiance_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_render_ao": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_AoDesc), C.c_void_p]),
     "mirt_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
@@ -567,6 +574,21 @@ class Context:
         """how many rays the last trace_closest / trace_occluded call re-ran in the exact kernel (mirt_trace_deferred)"""
         n = C.c_uint64()
         self._chk(lib().mirt_trace_deferred(self.h, C.byref(n)))
+        return n.value
+
+    def trace_radiance(self, desc, rays, count, seeds, radiance, samples=1, flags=0):
+        """Path radiance of `count` caller-supplied rays in one launch (mirt_trace_radiance): the pass's path -- closest hit, lightRender, per-light
+        shadow and shade, desc.bounces bounces -- from each 32-byte ray record on, `samples` times per ray.  seeds (int32 per ray) is advanced in
+        place; radiance (float4 per ray) receives the accumulator: rgb sums and the number of contributions, continued from its contents with
+        RADIANCE_ACCUMULATE.  Of desc the primitive sets, lights, material and bounces are read.  A _RadianceDesc may be given in place of `samples`."""
+        rd = samples if isinstance(samples, _RadianceDesc) else _RadianceDesc(C.sizeof(_RadianceDesc), int(samples), int(flags), 0)
+        self._chk(lib().mirt_trace_radiance(self.h, C.byref(desc) if desc is not None else None, C.byref(rd) if rd is not None else None,
+                                            rays.h if rays else None, int(count), seeds.h if seeds else None, radiance.h if radiance else None))
+
+    def radiance_deferred(self):
+        """how many rays the last trace_radiance call re-ran in the exact kernel (mirt_radiance_deferred)"""
+        n = C.c_uint64()
+        self._chk(lib().mirt_radiance_deferred(self.h, C.byref(n)))
         return n.value
 
     def render_ao(self, desc, ao_out, samples=AO_DEFAULT_SAMPLES, radius=float("inf"), bias=AO_DEFAULT_BIAS):

@@ -1,5 +1,5 @@
-"""Ray queries on torch tensors: the closest hit, or occlusion, of rays the caller holds as a cuda tensor (mirt_trace_closest,
-mirt_trace_occluded; the definition is include/mirt.h's).
+"""Ray queries on torch tensors: the closest hit, occlusion, or the path radiance of rays the caller holds as a cuda tensor (mirt_trace_closest,
+mirt_trace_occluded, mirt_trace_radiance; the definitions are include/mirt.h's).
 
 The tensors are not copied: each is wrapped as a buffer of the context (Context.wrap) for the length of the call, and the launches are queued on
 torch's CURRENT stream (Context.set_stream), so they are ordered after whatever produced `rays` there and before whatever reads the result there.
@@ -8,6 +8,8 @@ torch's CURRENT stream (Context.set_stream), so they are ordered after whatever 
     hits  float32 [N, 8]: normal.xyz, t, p.xyz, and the material id in column 7 -- hits[:, 7].view(torch.int32); -1 is a miss
     sets  int32 [N] (uint32 bits: the index of the set whose primitive won, -1 = 0xFFFFFFFF for a miss)
     occluded  uint8 [N]: 1 iff something blocks the ray (a ray with mint == maxt is reported 1)
+    seeds     int32 [N], contiguous: a ray's random sequence, advanced in place by trace_radiance
+    radiance  float32 [N, 4]: a ray's accumulator -- rgb sums and, in column 3, the number of contributions
 """
 import torch
 
@@ -63,3 +65,29 @@ def trace_occluded(ctx, dev_scene, rays):
                 for b in wrapped:
                     b.release()
     return occluded
+
+
+def trace_radiance(ctx, dev_scene, rays, seeds, samples=1, bounces=5, accumulate_into=None, emitters=True):
+    """-> radiance [N, 4] float32: the pass's path from each ray on, `samples` times per ray (mirt_trace_radiance).  seeds: int32 cuda [N],
+    advanced in place.  accumulate_into: a float32 cuda [N, 4] of accumulators to continue (written in place and returned).  emitters=False: the
+    rays continue paths whose vertices already sampled the lights (MIRT_RADIANCE_NO_EMITTERS)."""
+    from . import mirt
+    _check(ctx, rays)
+    n = rays.shape[0]
+    if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.shape == (n,) and seeds.is_contiguous() and seeds.device == rays.device):
+        raise ValueError("seeds: a contiguous int32 cuda tensor [N] on the rays' device")
+    out = accumulate_into
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == (n, 4) and out.is_contiguous() and out.device == rays.device):
+        raise ValueError("accumulate_into: a contiguous float32 cuda tensor [N, 4] on the rays' device")
+    flags = (mirt.RADIANCE_ACCUMULATE if accumulate_into is not None else 0) | (0 if emitters else mirt.RADIANCE_NO_EMITTERS)
+    if n:
+        with _OnTorchStream(ctx, rays.device):
+            wrapped = [ctx.wrap(rays.data_ptr(), n * 32), ctx.wrap(seeds.data_ptr(), n * 4), ctx.wrap(out.data_ptr(), n * 16)]
+            try:
+                ctx.trace_radiance(dev_scene.pass_desc(None, None, bounces=bounces), wrapped[0], n, wrapped[1], wrapped[2], samples=samples, flags=flags)
+            finally:
+                for b in wrapped:
+                    b.release()
+    return out

@@ -331,6 +331,52 @@ typedef struct mirt_hit { float normal[3]; float t; float p[3]; int32_t mat_id; 
 MIRT_API int mirt_trace_closest(mirt_ctx* ctx, const mirt_pass_desc* scene, mirt_buf* rays, uint64_t count, mirt_buf* hits, mirt_buf* sets);
 MIRT_API int mirt_trace_occluded(mirt_ctx* ctx, const mirt_pass_desc* scene, mirt_buf* rays, uint64_t count, mirt_buf* occluded);
 MIRT_API int mirt_trace_deferred(mirt_ctx* ctx, uint64_t* rays);
+/* PATH RADIANCE OF CALLER-SUPPLIED RAYS: what the path tracer computes along `count` rays of the caller's own -- a panoramic, fisheye or
+ * orthographic camera, a light probe, a light-map texel, the continuation of a path whose first hit came from a rasteriser.  It is
+ * executeRender (A10 code.js:1806-1854) without initTrace and copyToPixel, in one launch.
+ * BUFFERS.  rays[i] is a mirt_ray, 32 bytes, used as given: d is not normalised.  seeds[i] is an int32, read and written.  radiance[i] is a
+ * float4, the ray's ACCUMULATOR exactly as the kernel-by-kernel path's acu[i] ends: rgb are sums, w is the number of contributions; dividing is
+ * the caller's.  Of `scene` are read: struct_size, the primitive sets (spheres, triangles, meshes, n_meshes), lights / n_lights, material and
+ * bounces; everything else -- image size, rays_per_pixel, tile, camera, lens, seeds, acu, pixel, radiance, pass_index -- is ignored and free to
+ * be 0 or NULL.
+ * DEFINITION, bit for bit in every field.  Ray i runs rd->samples times, j = 0 .. samples - 1, its seed and its accumulator carried from one
+ * sample to the next; the accumulator starts at (0, 0, 0, 0), initAcu (code.cl:448-456), or with MIRT_RADIANCE_ACCUMULATE at radiance[i] as
+ * given.  Each sample is what the kernel-by-kernel path leaves in acu[i] and seeds[i] when
+ *   1. the Ray buffer entry is the caller's {o, d, mint, maxt};
+ *   2. the Poi is reset as initTrace resets it (code.cl:538-541): matId = -1, atte = (1, 1, 1);
+ *   3. sphereTrace, triangleTrace and every meshTrace run in upload order (code.js:1809-1813);
+ *   4. lightRender runs once per light (code.cl:600-629) -- unless MIRT_RADIANCE_NO_EMITTERS is set: the ray continues a path whose vertex
+ *      already sampled the lights, so an emitter it meets adds nothing and does not end it;
+ *   5. per light: initShadowTrace, then sphereShadowTrace, triangleShadowTrace and a triangleShadowTrace per mesh, then sceneRender
+ *      (code.js:1817-1826);
+ *   6. `bounces` times: bouncePaths, then the closest-hit kernels of step 3, then the per-light block of step 5 (code.js:1829-1846)
+ * have run.  CONSEQUENCES.  A ray that enters dead (mint == maxt) or misses everything adds nothing and draws nothing: its seed is unchanged
+ * and its radiance is (0, 0, 0, 0), or its previous value with MIRT_RADIANCE_ACCUMULATE.  A material id past the table shades nothing, as in the
+ * pass.  One call with samples = a + b equals a call with a followed by a call with b and MIRT_RADIANCE_ACCUMULATE.  The camera's own rays, as
+ * initTrace stores them at a k x k count above 1, run with the pass's seeds, samples = 1 and the pass's bounces, give a pass: radiance equals the
+ * acu a fresh mirt_render_first_pass writes, and the seeds end equal to the pass's.
+ * CHECKS, all before anything is queued; nothing is written when one fails, and the context works afterwards.  MIRT_E_ARG: a wrong struct_size
+ * in either descriptor, samples 0 or above MIRT_RADIANCE_MAX_SAMPLES, unknown flags, reserved != 0, count above 2^32 - 256, NULL seeds or
+ * radiance, n_lights above MIRT_MAX_LIGHTS or n_meshes above MIRT_MAX_MESHES, a NULL light or mesh array with a count above 0, seeds or radiance
+ * whose bytes meet the rays', each other's, a geometry buffer's or the material's (both are written), a call while capturing.  MIRT_E_RANGE: a
+ * buffer shorter than count records, a material table shorter than one entry.  MIRT_E_DATA: a cell table that fails validation.  MIRT_E_HANDLE:
+ * a bad context or buffer, the material included.  count == 0 is MIRT_OK and queues nothing.  A held command stream (mirt_ctx_set_fusion, frame
+ * fusion) is flushed first; wrapped geometry is re-validated as for a pass.
+ * KERNEL.  One launch, one lane per ray walking its samples in order (csrc/pt_kernels_rays.hip k_traceRadiance: the pass's closest-hit loop,
+ * lightRender, per-light stage and bounce) -- by default the optimistic / exact pair PER RAY, like the ray queries: a ray whose primary ray, or
+ * any shadow or bounce ray of any of its samples, the ray-side guard refuses, or whose grid walk defers, writes neither its seed nor its
+ * radiance and is redone from the start, all samples, by the exact kernel; mirt_ctx_set_exact_only is honoured.  mirt_radiance_deferred: the
+ * rays the last mirt_trace_radiance re-ran in the exact kernel, counted when asked, like mirt_trace_deferred.  Not built: a per-pixel reduction
+ * of the output, tiling over N devices (rays are independent: a caller splits its batch), graph capture, importance other than the pass's own,
+ * reuse of the primary ray's hit by the samples after the first.  MIRT_ABI_VERSION is unchanged: a host detects the entry points by their
+ * symbols. */
+#define MIRT_RADIANCE_ACCUMULATE 1u    /* radiance[i] is read and carried on; without it every accumulator starts at (0,0,0,0), initAcu */
+#define MIRT_RADIANCE_NO_EMITTERS 2u   /* lightRender is not run on the caller's ray: the ray continues a path whose vertex already sampled the lights */
+#define MIRT_RADIANCE_MAX_SAMPLES 64u
+typedef struct mirt_radiance_desc { uint32_t struct_size, samples, flags, reserved; } mirt_radiance_desc;
+MIRT_API int mirt_trace_radiance(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_radiance_desc* rd, mirt_buf* rays, uint64_t count,
+                                 mirt_buf* seeds, mirt_buf* radiance);
+MIRT_API int mirt_radiance_deferred(mirt_ctx* ctx, uint64_t* rays);
 /* AMBIENT OCCLUSION OF THE FIRST HIT of the row tile, in one launch: the AOV the guides lack.  ao_out holds one uint32[2] per tile-local pixel,
  * {open, cast}, 8 bytes per pixel.  Pixel p of the row tile has the rays p * rays_per_pixel + i, i = 0 .. rays_per_pixel - 1, each taken as
  * initTrace and the closest-hit stage leave it -- sphereTrace, triangleTrace, then every meshTrace in upload order -- before lightRender: exactly
