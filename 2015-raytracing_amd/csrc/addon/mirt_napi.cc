@@ -537,6 +537,72 @@ napi_value RadianceDeferred(napi_env env, napi_callback_info info) {
     return mk_num(env, (double)n);
 }
 
+// Panoramic, fisheye and orthographic cameras.  viewDesc = {model, width, height, k, row0, nrows, flags, eye, right, up, forward (Float32Array of
+// 3 each, used as given), halfW, halfH, halfAngle, tMin, tMax, tone} -- left out: model 0, k 1, the whole image, no flags, half extents 1,
+// halfAngle pi / 2, tMin 0, tMax +Infinity, tone 1.  viewRays(ctx, viewDesc, rays): the tile's 32-byte rays (mirt_view_rays).
+// renderView(ctx, desc, viewDesc, seeds, radiance, pixel): the frame in one launch (mirt_render_view) -- seeds (int32 per tile ray) advanced in
+// place, radiance (float4 per tile pixel) and / or pixel (RGBA8), either may be null; of desc the sets, lights, material and bounces (left out: 5)
+// are read.  viewDeferred(ctx) -> how many rays the last renderView re-ran in the exact kernel, in whole blocks (mirt_view_deferred).
+static bool read_view(napi_env env, napi_value d, const char* who, mirt_view_desc& v) {
+    memset(&v, 0, sizeof v);
+    v.struct_size = sizeof v;
+    v.k = 1u;
+    v.half_w = 1.0f; v.half_h = 1.0f; v.half_angle = 0x1.921fb6p+0f; v.t_min = 0.0f; v.t_max = INFINITY; v.tone = 1.0f;
+    napi_valuetype t = napi_undefined;
+    if (napi_typeof(env, d, &t) != napi_ok || t != napi_object || !prop_u32(env, d, "width", &v.width) || !prop_u32(env, d, "height", &v.height) ||
+        !prop_floats(env, d, "eye", v.eye, 3) || !prop_floats(env, d, "right", v.right, 3) || !prop_floats(env, d, "up", v.up, 3) || !prop_floats(env, d, "forward", v.forward, 3)) {
+        throw_type(env, (std::string(who) + ": the view needs width, height and eye / right / up / forward (Float32Array of 3 each)").c_str());
+        return false;
+    }
+    prop_u32(env, d, "model", &v.model); prop_u32(env, d, "k", &v.k); prop_u32(env, d, "row0", &v.row0); prop_u32(env, d, "nrows", &v.nrows); prop_u32(env, d, "flags", &v.flags);
+    prop_f32(env, d, "halfW", &v.half_w); prop_f32(env, d, "halfH", &v.half_h); prop_f32(env, d, "halfAngle", &v.half_angle);
+    prop_f32(env, d, "tMin", &v.t_min); prop_f32(env, d, "tMax", &v.t_max); prop_f32(env, d, "tone", &v.tone);
+    return true;
+}
+napi_value ViewRays(napi_env env, napi_callback_info info) {
+    ARGS(3);
+    void *c, *rays = nullptr;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "viewRays(ctx, viewDesc, rays)");
+    get_ext(env, argv[2], &rays);
+    mirt_view_desc v;
+    if (!read_view(env, argv[1], "viewRays", v)) return nullptr;
+    const int rc = mirt_view_rays((mirt_ctx*)c, &v, (mirt_buf*)rays);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value RenderView(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    void *c, *seeds = nullptr, *radiance = nullptr, *pixel = nullptr;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "renderView(ctx, desc, viewDesc, seeds, radiance, pixel)");
+    get_ext(env, argv[3], &seeds);
+    get_ext(env, argv[4], &radiance);
+    get_ext(env, argv[5], &pixel);
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    p.bounces = 5;
+    prop_u32(env, argv[1], "bounces", &p.bounces);
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    std::vector<mirt_light> lights;
+    if (!read_sets(env, argv[1], "renderView", p, sph, tri, meshes) || !read_lights(env, argv[1], "renderView", p, lights)) return nullptr;
+    p.material = prop_buf(env, argv[1], "material");
+    mirt_view_desc v;
+    if (!read_view(env, argv[2], "renderView", v)) return nullptr;
+    const int rc = mirt_render_view((mirt_ctx*)c, &p, &v, (mirt_buf*)seeds, (mirt_buf*)radiance, (mirt_buf*)pixel);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value ViewDeferred(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "viewDeferred(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_view_deferred((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
+}
+
 // filterAtrous(ctx, {width,height,iterations,flags,normalPowerLog2,tone,sigmaDepth,sigmaColour, radiance,normalHits,albedoDepth, filtered?,pixel?}):
 // the a-trous filter of a frame on the device (mirt_filter_atrous); a number left out is 0, a buffer left out NULL -- the library checks them all
 void filter_desc(napi_env env, napi_value d, mirt_filter_desc& f) {
@@ -971,7 +1037,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"renderAo", RenderAo}, {"aoDeferred", AoDeferred}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

@@ -9,6 +9,7 @@
 #include "pt_launch.hpp"
 #include "pt_post_check.hpp"
 #include "pt_rows_plan.hpp"
+#include "pt_view_plan.hpp"
 #include "pt_set_guard.hpp"
 #include "pt_stream_match.hpp"
 #include "pt_upsample_taps.hpp"
@@ -83,6 +84,9 @@ struct mirt_ctx {
     void* rad_defer = nullptr;    // mirt_trace_radiance, optimistic pair: [count, pad, pad, pad | a bit per ray], its own allocation too
     size_t rad_defer_bytes = 0;
     uint32_t rad_defer_words = 0; // mask words the last mirt_trace_radiance used (0: it ran the exact kernel only, or queued nothing)
+    void* view_defer = nullptr;   // mirt_render_view, optimistic pair: [count, pad, pad, pad | a bit per BLOCK of 256 rays], its own allocation too
+    size_t view_defer_bytes = 0;
+    uint32_t view_defer_words = 0; // mask words the last mirt_render_view used (0: it ran the exact kernel only)
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     int force_exact = 0;          // mirt_ctx_set_exact_only: 1 = skip the optimistic kernel, run every sample through the exact one
@@ -385,6 +389,7 @@ static int destroy_ctx(mirt_ctx* ctx) {
     if (ctx->ray_defer) (void)hipFree(ctx->ray_defer);
     if (ctx->ao_defer) (void)hipFree(ctx->ao_defer);
     if (ctx->rad_defer) (void)hipFree(ctx->rad_defer);
+    if (ctx->view_defer) (void)hipFree(ctx->view_defer);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1848,6 +1853,143 @@ int mirt_radiance_deferred(mirt_ctx* ctx, uint64_t* rays) try {
     *rays = count;
     return MIRT_OK;
 } MIRT_CATCH("mirt_radiance_deferred", return MIRT_E_DEVICE)
+
+// ---- panoramic, fisheye and orthographic cameras (pt_kernels_rays.hip k_viewRays, k_viewPass): mirt_view_rays, mirt_render_view.  The rules of
+// the descriptor and the launch plan are pt_view_plan.hpp's (host-only, CPU-tested); here are their messages.  Every check comes before anything
+// is queued.
+static_assert(sizeof(pt::ViewDesc) == sizeof(mirt_view_desc) && offsetof(pt::ViewDesc, eye) == offsetof(mirt_view_desc, eye) &&
+              offsetof(pt::ViewDesc, half_w) == offsetof(mirt_view_desc, half_w) && offsetof(pt::ViewDesc, tone) == offsetof(mirt_view_desc, tone),
+              "pt_view_plan.hpp restates the header's descriptor");
+static_assert(pt::kViewOrthographic == MIRT_VIEW_ORTHOGRAPHIC && pt::kViewEquirect == MIRT_VIEW_EQUIRECT && pt::kViewFisheye == MIRT_VIEW_FISHEYE &&
+              pt::kViewAccumulate == MIRT_VIEW_ACCUMULATE && pt::kViewStatusArg == MIRT_E_ARG, "pt_view_plan.hpp restates the header's constants");
+static int view_verdict(mirt_ctx* ctx, const char* fn, pt::ViewVerdict v, const pt::ViewDesc& d) {
+    const int code = pt::view_status(v);
+    switch (v) {
+        case pt::VIEW_OK: return MIRT_OK;
+        case pt::VIEW_STRUCT_SIZE: return fail(ctx, code, "%s: view descriptor size mismatch", fn);
+        case pt::VIEW_MODEL: return fail(ctx, code, "%s: unknown model %u", fn, d.model);
+        case pt::VIEW_FLAGS: return fail(ctx, code, "%s: unknown flags 0x%x", fn, d.flags);
+        case pt::VIEW_SAMPLES: return fail(ctx, code, "%s: k = %u is not 1, 2, 4, 8 or 16", fn, d.k);
+        case pt::VIEW_EXTENT: return fail(ctx, code, "%s: image %u x %u outside 1..65535", fn, d.width, d.height);
+        case pt::VIEW_TILE: return fail(ctx, code, "%s: row tile [%u,+%u) outside the image", fn, d.row0, pt::view_tile_rows(d));
+        case pt::VIEW_TILE_RAYS: return fail(ctx, code, "%s: a tile of more than 2^32 - 256 rays (the kernels index a tile's rays with 32 bits); render fewer rows per call", fn);
+        case pt::VIEW_BASIS: return fail(ctx, code, "%s: a component of eye, right, up or forward is not finite", fn);
+        case pt::VIEW_ORTHO_WINDOW: return fail(ctx, code, "%s: ORTHOGRAPHIC half extents %g x %g are not finite numbers above 0", fn, (double)d.half_w, (double)d.half_h);
+        case pt::VIEW_FISHEYE_ANGLE: return fail(ctx, code, "%s: FISHEYE half_angle %g is not in (0, pi]", fn, (double)d.half_angle);
+        case pt::VIEW_T_MIN: return fail(ctx, code, "%s: t_min %g is not a finite number >= 0", fn, (double)d.t_min);
+        case pt::VIEW_T_MAX: return fail(ctx, code, "%s: t_max %g is not above t_min %g", fn, (double)d.t_max, (double)d.t_min);
+        case pt::VIEW_TONE: return fail(ctx, code, "%s: tone %g is not a finite number above 0 (it is read because a pixel buffer is given)", fn, (double)d.tone);
+        case pt::VIEW_NO_SEEDS: return fail(ctx, code, "%s: seeds is NULL", fn);
+        case pt::VIEW_NO_OUTPUT: return fail(ctx, code, "%s: radiance and pixel are both NULL (either may be, not both)", fn);
+        case pt::VIEW_ACCUMULATE_NEEDS_RADIANCE: return fail(ctx, code, "%s: MIRT_VIEW_ACCUMULATE without a radiance buffer to go on from", fn);
+    }
+    return fail(ctx, MIRT_E_ARG, "%s: view descriptor refused", fn);
+}
+static pt::ViewArgs view_args(const pt::ViewDesc& d, const pt::ViewPlan& plan) {
+    pt::ViewArgs V;
+    memset(&V, 0, sizeof V);
+    V.model = d.model; V.width = d.width; V.height = d.height; V.k = d.k; V.row0 = d.row0; V.nrows = plan.nrows;
+    for (int c = 0; c < 3; ++c) { V.eye[c] = d.eye[c]; V.right[c] = d.right[c]; V.up[c] = d.up[c]; V.forward[c] = d.forward[c]; }
+    V.half_w = d.half_w; V.half_h = d.half_h; V.half_angle = d.half_angle; V.t_min = d.t_min; V.t_max = d.t_max;
+    return V;
+}
+
+int mirt_view_rays(mirt_ctx* ctx, const mirt_view_desc* vd, mirt_buf* rays) try {
+    const char* const fn = "mirt_view_rays";
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, fn);
+    if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
+    pt::ViewDesc d;
+    memcpy(&d, vd, sizeof d);
+    int rc;
+    if ((rc = view_verdict(ctx, fn, pt::view_check_desc(d), d))) return rc;
+    const pt::ViewPlan plan = pt::view_plan(d);
+    if (!rays) return fail(ctx, MIRT_E_HANDLE, "%s: rays is NULL", fn);
+    if ((rc = need(ctx, "mirt_view_rays rays", rays, plan.rays * 32))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::launch_viewRays(ctx->stream, view_args(d, plan), rays->ptr);
+    HIPCHK(ctx, hipGetLastError());
+    rays->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_view_rays", return MIRT_E_DEVICE)
+
+int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel) try {
+    const char* const fn = "mirt_render_view";
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, fn);
+    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
+    if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
+    pt::ViewDesc v;
+    memcpy(&v, vd, sizeof v);
+    int rc;
+    if ((rc = view_verdict(ctx, fn, pt::view_check_render(v, seeds != nullptr, radiance != nullptr, pixel != nullptr), v))) return rc;
+    const pt::ViewPlan plan = pt::view_plan(v);
+    // the pass's own limits and rules for its arrays, as mirt_trace_radiance has them
+    if (d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
+    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
+    if ((d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
+    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[3] = {{"seeds", seeds, plan.rays * 4}, {"radiance", radiance, plan.pixels * 16}, {"pixel", pixel, plan.pixels * 4}};
+    for (const auto& b : io)
+        if (b.buf && (rc = need(ctx, (std::string(fn) + " " + b.label).c_str(), b.buf, b.bytes))) return rc;
+    if ((rc = need(ctx, "material", d->material, 16))) return rc;
+    {   // all three are written: the bytes the call touches of them, against each other's, the geometry's buffers and the material whole
+        std::vector<pt::PostRange> in;
+        add_range(in, d->material);
+        add_geometry_ranges(in, d);
+        pt::PostRange out[3];
+        for (int i = 0; i < 3; ++i) out[i] = {io[i].buf ? (uint64_t)(uintptr_t)io[i].buf->ptr : 0u, io[i].bytes, io[i].buf != nullptr};
+        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 3);
+        if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: the seeds', the radiance's or the pixel's bytes meet a geometry buffer's or the material's", fn);
+        if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: seeds, radiance and pixel meet one another", fn);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::FusedArgs A;
+    memset(&A, 0, sizeof A);
+    A.bounces = d->bounces;
+    A.n_lights = d->n_lights;
+    if ((rc = fill_sets(ctx, fn, d, A))) return rc;
+    if ((rc = fill_shading(ctx, d, A, true))) return rc;
+    const pt::ViewArgs V = view_args(v, plan);
+    const bool accumulate = (v.flags & MIRT_VIEW_ACCUMULATE) != 0u;
+    void* const rp = radiance ? radiance->ptr : nullptr;
+    void* const pp = pixel ? pixel->ptr : nullptr;
+    ctx->view_defer_words = 0;
+    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
+        if ((rc = grow_and_clear(ctx, ctx->view_defer, ctx->view_defer_bytes, 16u + (size_t)plan.mask_words * 4u))) return rc;
+        uint32_t* const mask = (uint32_t*)ctx->view_defer + 4;
+        pt::launch_viewPass(ctx->stream, A, V, true, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask, nullptr);
+        pt::launch_viewPass(ctx->stream, A, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, mask);
+        ctx->view_defer_words = plan.mask_words;
+    } else {
+        pt::launch_viewPass(ctx->stream, A, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, nullptr);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    seeds->version++;
+    if (radiance) radiance->version++;
+    if (pixel) pixel->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_render_view", return MIRT_E_DEVICE)
+
+int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_view_deferred: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_view_deferred");
+    if (!rays) return fail(ctx, MIRT_E_ARG, "mirt_view_deferred: null output");
+    *rays = 0;
+    if (!ctx->view_defer_words) return MIRT_OK;
+    // counted on demand: the mask of the last mirt_render_view is still in place (the next one clears it); a bit is a block of 256 rays
+    uint32_t* counters = (uint32_t*)ctx->view_defer;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
+    pt::launch_deferCount(ctx->stream, counters + 4, ctx->view_defer_words, counters);
+    uint32_t count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *rays = (uint64_t)count * 256u;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_view_deferred", return MIRT_E_DEVICE)
 
 // ---- the post-process stage: mirt_filter_atrous and mirt_upsample_guided.  The argument rules they share are pt_post_check.hpp's (host-only,
 // CPU-tested); here are those rules' messages, `fn` being the entry point's name, and the shared epilogue.

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 #include "pt_closest.hpp"
 #include "pt_direct.hpp"   // direct_all and the park rows, shared with k_traceRadiance (pt_kernels_rays.hip)
+#include "pt_resolve.hpp"  // resolve_rows and PT_RESOLVE_PRIO, shared with k_viewPass (pt_kernels_rays.hip)
 
 namespace pt {
 
@@ -157,9 +158,6 @@ __global__ void __launch_bounds__(64) k_planeList(const float4* prep, uint32_t c
 // in i, from +0 or from the sum the segments before it left: the fp32 sum is order-dependent -- reading them four at a time (a channel's row is
 // contiguous in LDS); the four lanes of a pixel (one DPP quad) hand their sums to the first, which writes `radiance` (the sums) and `pixel`
 // (the tone-scaled RGBA8, truncating).
-#ifndef PT_RESOLVE_PRIO
-#define PT_RESOLVE_PRIO 1
-#endif
 // The ray id of lane t of block `blk` of this launch -- the one place it is derived (FusedArgs::seg_off): sample seg_off + t % seg_len of pixel
 // blk * (256 / seg_len) + t / seg_len.  SEG = false, a contiguous segment (seg_len == rpp, or 256, and every launch that does not resolve in the
 // pass): the block's first id, scalar arithmetic on kernel arguments, plus the lane.  In 64 bits: the caller checks it against the tile's ray
@@ -207,44 +205,8 @@ PT_DEV void resolve_block(const FusedArgs& A, const float* rows, uint32_t blk, u
     }
 }
 
-// resolve_block with its inputs spelled out, for a launch that writes a frame after every pass (FusedArgs::every): the chain goes on from `carry` and
-// writes `radiance` / `pixel` (either may be null) with the tone factor `res_m`.  (A copy, not a generalisation: the single-frame kernels keep
-// resolve_block's instructions -- routed through this function the compiler schedules their resolve differently.)
-PT_DEV void resolve_rows(const FusedArgs& A, const float* rows, uint32_t blk, uint64_t n_local, const float* carry, void* radiance, void* pixel, float res_m) {
-    const uint32_t rpp = A.rpp, per = A.seg_len, ppb = 256u / per;   // per: the rays of ONE pixel this block holds (FusedArgs::seg_len)
-    const uint32_t pix0 = blk * ppb, npix = (uint32_t)(n_local / rpp);
-#if PT_RESOLVE_PRIO
-    // The sums are chains of dependent additions (256 long at 256 rays per pixel, on four lanes) at the very end of a block whose other waves
-    // have left: until the chain ends the block's LDS and this wave's slot are held.  At the top priority the chain's instructions issue as they
-    // become ready instead of waiting their turn among the SIMD's other waves.
-    __builtin_amdgcn_s_setprio(3);
-#endif
-    for (uint32_t q = threadIdx.x; q < 4u * ppb; q += 256u) {   // whole quads: 4 ppb is a multiple of 4, and so is every q - threadIdx.x
-        const uint32_t j = q >> 2, c = q & 3u;
-        const float* r = rows + c * 256u + j * per;
-        float s = 0.0f;
-        // a later segment of a pixel of more than 256 rays: the chain goes on from the sum over the segments before it (FusedArgs::seg_off)
-        if (A.seg_off != 0u && pix0 + j < npix) s = carry[4u * (size_t)(pix0 + j) + c];
-        if (per >= 4u) {
-            const float4* r4 = (const float4*)r;   // 16-byte aligned: the rows are, and `per` is a multiple of 4 (a power of two)
-            for (uint32_t i = 0; i < per / 4u; ++i) { const float4 v = r4[i]; s += v.x; s += v.y; s += v.z; s += v.w; }
-        } else {
-            for (uint32_t i = 0; i < per; ++i) s += r[i];
-        }
-        const int si = (int)__float_as_uint(s);
-        const float x = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0x00, 0xf, 0xf, true));   // quad_perm [0,0,0,0]
-        const float y = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0x55, 0xf, 0xf, true));   // [1,1,1,1]
-        const float z = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0xaa, 0xf, 0xf, true));   // [2,2,2,2]
-        const float w = __uint_as_float((uint32_t)__builtin_amdgcn_mov_dpp(si, 0xff, 0xf, 0xf, true));   // [3,3,3,3]
-        if (c != 0u || pix0 + j >= npix) continue;
-        if (radiance) ((float4*)radiance)[pix0 + j] = make_float4(x, y, z, w);
-        if (pixel) {
-            const float sc = 255.0f * res_m;
-            const float cx = cl_clamp((x * sc) * 1.8f, 0.0f, 255.0f), cy = cl_clamp((y * sc) * 1.8f, 0.0f, 255.0f), cz = cl_clamp((z * sc) * 1.8f, 0.0f, 255.0f);
-            ((uchar4*)pixel)[pix0 + j] = make_uchar4((unsigned char)f2u(cx), (unsigned char)f2u(cy), (unsigned char)f2u(cz), 255);
-        }
-    }
-}
+// resolve_rows -- resolve_block with its inputs spelled out, for a launch that writes a frame after every pass (FusedArgs::every) -- is
+// pt_resolve.hpp's: the view cameras' pass (pt_kernels_rays.hip k_viewPass) resolves its blocks with it too.
 // Frame p of the launch's `passes` (pixel, radiance and carry hold that many frames of nrows * width pixels).  Its factor is render_pass_impl's res_m for
 // pass pass_index + p, the same double operations: the sum of two integers below 2^32 is exact, and so the product and quotient round as the host's.
 PT_DEV void resolve_frame(const FusedArgs& A, const float* rows, uint32_t blk, uint64_t n_local, uint32_t p) {

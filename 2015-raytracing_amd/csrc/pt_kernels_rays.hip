@@ -28,8 +28,11 @@
 // widened for this.
 //
 // Also here, because it runs rays_any: k_ao, ambient occlusion of the first hit (mirt_render_ao); and because it starts at a caller's ray:
-// k_traceRadiance, the pass's path from that ray on (mirt_trace_radiance) -- at the end of the file.
+// k_traceRadiance, the pass's path from that ray on (mirt_trace_radiance); and because they are k_traceRadiance with the ray made in registers:
+// k_viewRays and k_viewPass, the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view) -- at the end of the file.
 #include "pt_direct.hpp"
+#include "pt_resolve.hpp"   // resolve_rows: k_viewPass resolves its blocks' pixels as the pass does
+#include "pt_view.hpp"      // view_ray: a sample's ray
 
 namespace pt {
 
@@ -406,6 +409,147 @@ void launch_radiance(hipStream_t s, const FusedArgs& a, bool fast, const void* r
     const FusedLds L = fused_lds_slots(b, fast);
     if (fast) launch_radiance_t<true>(s, b, L, (const float4*)rays, count, samples, flags, seeds, (float4*)radiance, defer_mask, nullptr);
     else launch_radiance_t<false>(s, b, L, (const float4*)rays, count, samples, flags, seeds, (float4*)radiance, nullptr, redo_mask);
+}
+
+// ---- panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view): the ray of a sample is pt_view.hpp's view_ray, the one
+// definition both kernels call; include/mirt.h defines it operation by operation.
+// k_viewRays: the rays as 32-byte records, one lane per ray, two float4 stores -- memory-bound, nothing else to it.
+__global__ void __launch_bounds__(256) k_viewRays(const ViewArgs V, uint32_t count, float4* __restrict__ rays) {
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;   // (count <= 2^32 - 256: pt_view_plan.hpp)
+    if (id >= count) return;
+    const Ray r = view_ray(V, id);
+    rays[2u * (size_t)id] = make_float4(r.o.x, r.o.y, r.o.z, r.mint);
+    rays[2u * (size_t)id + 1u] = make_float4(r.d.x, r.d.y, r.d.z, r.maxt);
+}
+void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays) {
+    const uint64_t count = (uint64_t)v.nrows * v.width * v.k * v.k;
+    if (!count) return;
+    hipLaunchKernelGGL(k_viewRays, dim3((unsigned)((count + 255u) / 256u)), dim3(256), 0, s, v, (uint32_t)count, (float4*)rays);
+}
+
+// k_viewPass: k_traceRadiance's body at one sample per ray with the ray made in registers by view_ray instead of loaded, and behind the block's
+// barrier the pass's own resolve (pt_resolve.hpp resolve_rows) -- in one launch; neither the rays nor the per-ray accumulators reach memory.
+// A.rpp = A.seg_len = k * k (1, 4, 16, 64 or 256: it divides 256, so a block of 256 consecutive ray ids holds 256 / rpp WHOLE pixels) and
+// A.seg_off != 0 iff the sums go on from `radiance` (MIRT_VIEW_ACCUMULATE: resolve_rows' carry); A.width / A.nrows are the tile's.
+//
+// Structure: one lane per ray.  The generator's registers are dead before the segment loop; the four accumulator words are parked as
+// [channel][lane] rows from the start (they begin at +0: ACCUMULATE is the resolve's business, not the ray's) and read by the resolve where they
+// lie.  Every lane stays to the barrier: a lane past the end of the tile rides along dead -- it hits nothing, shades nothing, draws nothing.
+// The model, the bounce count and the sizes are kernel arguments and so WAVE-UNIFORM: in the grid variants every lane of a wave enters every
+// shared-test walk together (pt_trace_coop.hpp).
+// The optimistic / exact pair is per BLOCK, as in the pass's in-block resolve: a block one of whose primary, shadow or bounce rays the guard
+// refuses, or one of whose walks defers, writes neither its seeds nor its pixels and sets its bit (a bit per block of the launch); the exact
+// kernel runs the same grid and every block without its bit leaves at once.  An ORTHOGRAPHIC camera whose `forward` has a zero component is
+// outside the ray-side guard for EVERY ray (|d_k| >= 2^-40): every block is handed over and the frame comes from the exact kernel, same bits.
+// Waves per SIMD the register allocator is held to: A/B switches of this kernel's own, starting from k_traceRadiance's (profiles/view/README.md
+// has the registers per instance and the measurement).  At 1920 x 1080 x 4 rays, bounces 5, equirect: cornell_teapot3 5.57 (5 waves, 96 VGPRs, no
+// spill) -> 5.20 (6, 80 VGPRs, 17 spilled) -> 5.47 (7) -> 6.90 ms (8 waves, 64 VGPRs, 51 spilled), cornell 1.01 (5 waves) -> 1.00 (6) -> 0.97 (7) -> 0.97 ms (8):
+// the bounds stay k_traceRadiance's.
+#ifndef PT_VIEW_GRID_WAVES
+#define PT_VIEW_GRID_WAVES PT_RADIANCE_GRID_WAVES
+#endif
+#ifndef PT_VIEW_CELL_WAVES
+#define PT_VIEW_CELL_WAVES PT_RADIANCE_CELL_WAVES
+#endif
+#define PT_VIEW_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_VIEW_GRID_WAVES : PT_VIEW_CELL_WAVES)
+template <bool FAST, int GRIDS>
+__global__ void PT_VIEW_BOUNDS(GRIDS) k_viewPass(const FusedArgs A, const ViewArgs V, uint32_t count, int32_t* __restrict__ seeds, float4* radiance,
+                                                   uchar4* __restrict__ pixel, float tone, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    const uint32_t blk = blockIdx.x;
+    if (!FAST && redo_mask && (redo_mask[blk >> 5] >> (blk & 31u) & 1u) == 0u) return;   // block-uniform: nothing of the block has begun
+    stage_block<FAST, GRIDS>(A);
+    const uint32_t id = blk * 256u + threadIdx.x;   // (count <= 2^32 - 256: pt_view_plan.hpp)
+    const bool valid = id < count;
+    int32_t seed = 0;
+    Ray ray;   // a lane without a ray rides along dead: it enters the shared walks and tests nothing of its own
+    ray.o = mk3(0.0f, 0.0f, 0.0f); ray.d = mk3(0.0f, 0.0f, 0.0f); ray.mint = 0.0f; ray.maxt = 0.0f;
+    if (valid) {
+        seed = seeds[id];
+        ray = view_ray(V, id);
+    }
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // initAcu (A10 code.cl:448-456)
+    RadiancePark park;
+#if PT_PARK_LDS
+    __shared__ __attribute__((aligned(16))) float park_mem[PT_PARK_WORDS(GRIDS)][256];
+    park.base = &park_mem[0][threadIdx.x];
+    park.put(0, 0.0f); park.put(1, 0.0f); park.put(2, 0.0f); park.put(3, 0.0f);
+    park.put(4, 1.0f); park.put(5, 1.0f); park.put(6, 1.0f);
+#else
+    __shared__ __attribute__((aligned(16))) float park_mem[4][256];
+#endif
+    bool defer = false;
+    Poi poi;   // as initTrace resets it (code.cl:538-541)
+    poi.p = mk3(0.0f, 0.0f, 0.0f);
+    poi.n = mk3(0.0f, 0.0f, 0.0f);
+    poi.atte = mk3(1.0f, 1.0f, 1.0f);
+    poi.matId = -1;
+    // segment 0 is the camera's ray; segments 1..bounces start with bouncePaths (code.js:1829-1846)
+    for (uint32_t seg = 0; seg <= A.bounces; ++seg) {
+        if (seg > 0) {
+            if (poi.matId >= 0) {
+#if PT_PARK_LDS
+                if (PT_PARK_PN_FOR(GRIDS)) park.get_pn(poi);
+#endif
+                ray = bounce_ray(poi, seed);
+            } else {
+                ray.mint = PT_INF;
+                ray.maxt = PT_INF;
+            }
+        }
+        closest_all<FAST, GRIDS>(A, ray, poi, park, defer);
+        if (seg == 0) {
+            for (uint32_t l = 0; l < A.n_lights; ++l) {  // lightRender (code.cl:600-629), on the camera's ray only
+                if (ray.mint == ray.maxt) continue;
+                const LightArgs& L = A.lights[l];
+                f3 irr = norm3(ld3(L.light + 6));
+                if (!light_visible(ray, ld3(L.light), ld3(L.light + 3), L.light[9])) continue;
+                ray.mint = PT_INF;
+                ray.maxt = PT_INF;
+                poi.matId = -1;
+#if PT_PARK_LDS
+                park.acc_add(irr.x, irr.y, irr.z);
+#else
+                acc.x += irr.x; acc.y += irr.y; acc.z += irr.z; acc.w += 1.0f;
+#endif
+            }
+        }
+        direct_all<FAST, GRIDS>(A, poi, seed, acc, park, defer);
+    }
+#if !PT_PARK_LDS
+    park_mem[0][threadIdx.x] = acc.x; park_mem[1][threadIdx.x] = acc.y; park_mem[2][threadIdx.x] = acc.z; park_mem[3][threadIdx.x] = acc.w;
+#endif
+    if (FAST && valid && defer) pt_blk_defer[0] = 1u;
+    __syncthreads();   // every lane's accumulator is final in LDS, and so is the flag (stage_block cleared it)
+    if (FAST && pt_blk_defer[0] != 0u) {   // the whole block goes to the exact kernel: its seeds stay as they were, no pixel of it is written
+        if (threadIdx.x == 0u) atomicOr(&defer_mask[blk >> 5], 1u << (blk & 31u));
+        return;
+    }
+    if (valid) seeds[id] = seed;
+    resolve_rows(A, &park_mem[0][0], blk, count, (const float*)radiance, radiance, pixel, tone);
+}
+
+template <bool FAST>
+static void launch_viewPass_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const ViewArgs& v, uint32_t count, int32_t* seeds, float4* radiance, uchar4* pixel,
+                              float tone, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
+    fused_lds_dispatch(L, [&](auto G, size_t lds) {
+        hipLaunchKernelGGL((k_viewPass<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, count, seeds, radiance, pixel, tone, defer_mask, redo_mask);
+    });
+}
+// fast: the optimistic kernel (sets the bits of the blocks it hands over in defer_mask); !fast: the exact kernel over the blocks of redo_mask, or
+// over every block when it is null.
+void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
+                     uint32_t* defer_mask, const uint32_t* redo_mask) {
+    const uint64_t count = (uint64_t)v.nrows * v.width * v.k * v.k;
+    if (!count) return;
+    FusedArgs b = a;
+    b.width = v.width; b.nrows = v.nrows;
+    b.rpp = v.k * v.k;            // resolve_rows: the rays of a pixel (stage_block's lens table of it is k words nobody reads)
+    b.seg_len = b.rpp;            // ... all of them in one block
+    b.seg_off = accumulate ? 1u : 0u;   // ... and whether the chain goes on from the carry
+    const FusedLds L = fused_lds_slots(b, fast);
+    if (fast) launch_viewPass_t<true>(s, b, L, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, defer_mask, nullptr);
+    else launch_viewPass_t<false>(s, b, L, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, nullptr, redo_mask);
 }
 
 }  // namespace pt

@@ -160,6 +160,24 @@ void launch_ao(hipStream_t s, const FusedArgs& a, bool fast, uint32_t samples, f
 // sets, lights, material, nmat and bounces of `a` and nothing else of it.
 void launch_radiance(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, uint32_t samples, uint32_t flags, int32_t* seeds, void* radiance,
                      uint32_t* defer_mask, const uint32_t* redo_mask);
+// Panoramic, fisheye and orthographic cameras (pt_kernels_rays.hip k_viewRays, k_viewPass; the definition is mirt_view_rays's comment in
+// include/mirt.h, the ray of a sample pt_view.hpp's view_ray).  The caller has checked everything (pt_view_plan.hpp).
+struct ViewArgs {
+    uint32_t model;              // MIRT_VIEW_ORTHOGRAPHIC / _EQUIRECT / _FISHEYE
+    uint32_t width, height;      // the WHOLE image
+    uint32_t k;                  // samples per axis: 1, 2, 4, 8 or 16
+    uint32_t row0, nrows;        // the row tile; ray ids are tile-local
+    float eye[3], right[3], up[3], forward[3];
+    float half_w, half_h, half_angle, t_min, t_max;
+};
+// the tile's nrows * width * k * k rays as 32-byte records, one lane per ray
+void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays);
+// mirt_render_view: those rays through k_traceRadiance's path at one sample each and the block's resolve, in one launch.  seeds: int32 per tile
+// ray, read and written; radiance (float4) / pixel (uchar4) per tile pixel, either may be null; accumulate: the sums go on from `radiance`.  The
+// optimistic / exact pair per BLOCK of 256 ray ids: the mask is one bit per block, (blocks + 31) / 32 words.  Reads the sets, lights, material,
+// nmat and bounces of `a` and nothing else of it.
+void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
+                     uint32_t* defer_mask, const uint32_t* redo_mask);
 // Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
 // every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
 struct FilterArgs {

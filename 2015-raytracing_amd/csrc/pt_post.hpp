@@ -14,6 +14,9 @@
 namespace pt {
 
 PT_DEV float div_cr(float n, float d) { return (float)((double)n / (double)d); }
+// ... and the correctly rounded fp32 square root the same way, for the same reason (fp64 sqrt is correctly rounded in both builds, 53 >= 2 * 24 + 2).
+// The view cameras' ray generator (pt_view.hpp) is its one user: the post-process stage itself takes no root.
+PT_DEV float sqrt_cr(float x) { return (float)__builtin_sqrt((double)x); }
 
 // A live pixel's guides, normalised by its hit count: r = 1 / hits, then (n^.x, n^.y, n^.z, z) = (n * r, depth * r) -- the filter's prepared
 // guide -- and a = albedo * r.  Two functions of r, because a is wanted only where the image is demodulated.

@@ -1,0 +1,111 @@
+// pt_view_plan.hpp -- the host side of the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view; include/mirt.h): the
+// descriptor checks that need no device, and the launch plan -- the tile's rays, its blocks of 256 consecutive ray ids, the whole pixels a block
+// holds and those of the ragged last block.  Plain integers and floats: no HIP header and no device, so a plain C++ compiler builds it and
+// tests/test_view_plan.py checks it on the CPU (tests/view_plan_dump.cpp).  mirt_abi.cpp is the caller and owns the messages.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace pt {
+
+constexpr uint32_t kViewOrthographic = 0u, kViewEquirect = 1u, kViewFisheye = 2u;   // MIRT_VIEW_ORTHOGRAPHIC, _EQUIRECT, _FISHEYE
+constexpr uint32_t kViewAccumulate = 1u;                                            // MIRT_VIEW_ACCUMULATE
+constexpr uint32_t kViewMaxExtent = 65535u;
+constexpr uint64_t kViewMaxRays = 0xFFFFFF00ull;   // 2^32 - 256: the kernels index a tile's rays with 32 bits, and a block reaches 255 ids past the last
+constexpr int kViewStatusArg = -1;                 // MIRT_E_ARG
+
+// mirt_view_desc, field for field (mirt_abi.cpp asserts the size and copies the bytes)
+struct ViewDesc {
+    uint32_t struct_size, model, width, height;
+    uint32_t k;
+    uint32_t row0, nrows;
+    uint32_t flags;
+    float eye[3], right[3], up[3], forward[3];
+    float half_w, half_h;
+    float half_angle;
+    float t_min, t_max;
+    float tone;
+};
+
+enum ViewVerdict {
+    VIEW_OK,
+    VIEW_STRUCT_SIZE,     // struct_size is not sizeof(mirt_view_desc)
+    VIEW_MODEL,           // not one of the three models
+    VIEW_FLAGS,           // a flag nobody defined
+    VIEW_SAMPLES,         // k not in {1, 2, 4, 8, 16}
+    VIEW_EXTENT,          // width or height 0 or above 65535
+    VIEW_TILE,            // the row tile reaches outside the image
+    VIEW_TILE_RAYS,       // the tile holds more than 2^32 - 256 rays
+    VIEW_BASIS,           // a non-finite component of eye, right, up or forward
+    VIEW_ORTHO_WINDOW,    // ORTHOGRAPHIC: half_w or half_h not finite or <= 0
+    VIEW_FISHEYE_ANGLE,   // FISHEYE: half_angle not finite, <= 0 or > pi
+    VIEW_T_MIN,           // t_min negative or not finite
+    VIEW_T_MAX,           // t_max NaN or <= t_min
+    VIEW_TONE,            // a pixel buffer is given and tone is not finite or <= 0
+    VIEW_NO_SEEDS,        // mirt_render_view without seeds
+    VIEW_NO_OUTPUT,       // mirt_render_view with neither radiance nor pixel
+    VIEW_ACCUMULATE_NEEDS_RADIANCE
+};
+// the status every refusal above is reported with: 0, or MIRT_E_ARG
+inline int view_status(ViewVerdict v) { return v == VIEW_OK ? 0 : kViewStatusArg; }
+
+inline bool view_samples_ok(uint32_t k) { return k == 1u || k == 2u || k == 4u || k == 8u || k == 16u; }
+// the rows of the tile: nrows 0 means the whole image, as in mirt_pass_desc
+inline uint32_t view_tile_rows(const ViewDesc& v) { return v.nrows ? v.nrows : v.height; }
+
+// what both calls ask of the descriptor (mirt_view_rays reads neither flags' meaning nor tone, but refuses an unknown flag all the same)
+inline ViewVerdict view_check_desc(const ViewDesc& v) {
+    if (v.struct_size != sizeof(ViewDesc)) return VIEW_STRUCT_SIZE;
+    if (v.model > kViewFisheye) return VIEW_MODEL;
+    if (v.flags & ~kViewAccumulate) return VIEW_FLAGS;
+    if (!view_samples_ok(v.k)) return VIEW_SAMPLES;
+    if (!v.width || !v.height || v.width > kViewMaxExtent || v.height > kViewMaxExtent) return VIEW_EXTENT;
+    const uint32_t nrows = view_tile_rows(v);
+    if (v.row0 >= v.height || nrows > v.height - v.row0) return VIEW_TILE;
+    if ((uint64_t)nrows * v.width * (v.k * v.k) > kViewMaxRays) return VIEW_TILE_RAYS;
+    for (int c = 0; c < 3; ++c)
+        if (!isfinite(v.eye[c]) || !isfinite(v.right[c]) || !isfinite(v.up[c]) || !isfinite(v.forward[c])) return VIEW_BASIS;
+    if (v.model == kViewOrthographic && !(isfinite(v.half_w) && isfinite(v.half_h) && v.half_w > 0.0f && v.half_h > 0.0f)) return VIEW_ORTHO_WINDOW;
+    if (v.model == kViewFisheye && !(isfinite(v.half_angle) && v.half_angle > 0.0f && v.half_angle <= 0x1.921fb6p+1f)) return VIEW_FISHEYE_ANGLE;
+    if (!(isfinite(v.t_min) && v.t_min >= 0.0f)) return VIEW_T_MIN;
+    if (!(v.t_max > v.t_min)) return VIEW_T_MAX;   // a NaN compares false; +inf passes
+    return VIEW_OK;
+}
+// ... and what mirt_render_view asks on top, of the descriptor and of which buffers were given
+inline ViewVerdict view_check_render(const ViewDesc& v, bool seeds, bool radiance, bool pixel) {
+    const ViewVerdict d = view_check_desc(v);
+    if (d != VIEW_OK) return d;
+    if (pixel && !(isfinite(v.tone) && v.tone > 0.0f)) return VIEW_TONE;
+    if (!seeds) return VIEW_NO_SEEDS;
+    if (!radiance && !pixel) return VIEW_NO_OUTPUT;
+    if ((v.flags & kViewAccumulate) && !radiance) return VIEW_ACCUMULATE_NEEDS_RADIANCE;
+    return VIEW_OK;
+}
+
+// The launch plan of a descriptor that passed view_check_desc.  A block is 256 consecutive tile-local ray ids; rpp = k * k is 1, 4, 16, 64 or 256
+// and divides 256, so a block holds pixels_per_block WHOLE pixels -- the unit the in-block resolve and the optimistic / exact pair work in.
+struct ViewPlan {
+    uint32_t nrows;               // the tile's rows
+    uint32_t rpp;                 // k * k
+    uint64_t pixels, rays;        // of the tile
+    uint32_t blocks;              // ceil(rays / 256): the grid of k_viewRays and k_viewPass
+    uint32_t pixels_per_block;    // 256 / rpp
+    uint32_t last_block_pixels;   // the pixels of the last block: pixels_per_block unless it is ragged
+    uint32_t mask_words;          // the optimistic kernel's mask, a bit per block
+};
+inline ViewPlan view_plan(const ViewDesc& v) {
+    ViewPlan p;
+    p.nrows = view_tile_rows(v);
+    p.rpp = v.k * v.k;
+    p.pixels = (uint64_t)p.nrows * v.width;
+    p.rays = p.pixels * p.rpp;
+    p.blocks = (uint32_t)((p.rays + 255u) / 256u);
+    p.pixels_per_block = 256u / p.rpp;
+    const uint32_t rest = (uint32_t)(p.pixels % p.pixels_per_block);
+    p.last_block_pixels = rest ? rest : p.pixels_per_block;
+    p.mask_words = (p.blocks + 31u) / 32u;
+    return p;
+}
+
+}  // namespace pt

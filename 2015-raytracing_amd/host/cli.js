@@ -3,11 +3,13 @@
 //   node cli.js pack   <scene.xml> <width> <height> <raysPerPixel>                 -> packed kernel inputs as JSON (stdout)
 //   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl] [--post-in-tiles]] [--guides PREFIX] [--denoise [iterations]] [--upscale F] [--ao PREFIX [--ao-samples N] [--ao-radius R] [--ao-bias B]]
 //                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --ao: + PREFIX.ao.u32 (ambient occlusion of the first hit, mirt_render_ao: raw uint32 pairs {open, cast} per pixel, N AO rays of length R per hit sample, default 4 and unbounded, displaced by B = 0.001 along the normal; taken before the first pass, the seeds are not advanced) and PREFIX.ao.pgm (a byte per pixel, floor(255 * open / cast + 0.5), 255 where cast is 0), not with --gpus N; --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N unless --post-in-tiles; --post-in-tiles (with --gpus N): --denoise and --upscale run tile-local -- every device exchanges halo rows with its neighbours and filters / upsamples its own rows (mirt_exchange_rows, mirt_filter_atrous_rows, mirt_upsample_guided_rows), only finished rows are gathered; the same bytes in <out>, <out>.filtered.f32 and <out>.upsampled.f32, and no <out>.radiance.f32 (the unfiltered sums stay on their devices)
+//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.ppm> --view equirect|fisheye|ortho [--eye x,y,z] [--look x,y,z] [--up x,y,z] [--fov degrees] [--ortho-size w,h] [--bounces N] [--seeds file.i32]  -> a frame of a panoramic (360 x 180 degrees), fisheye (equidistant, --fov the full field of view, default 180) or orthographic (--ortho-size the window, default the scene box's extents in x and y) camera, one launch per pass (mirt_render_view): raysPerPixel 1, 4, 16, 64 or 256, un-jittered; the default eye is the scene box's centre, looking down -z; passes are progressive (MIRT_VIEW_ACCUMULATE, tone 1 / (raysPerPixel * p)); + <out>.radiance.f32; not with --gpus, --guides, --denoise, --upscale, --ao
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
 //   node cli.js trace  <scene.xml> <rays.f32> <out.f32> [--occluded] [--sets out.u32]  -> ray queries on the caller's own rays (mirt_trace_closest): rays.f32 holds raw 32-byte records {o.xyz, mint, d.xyz, maxt}, out.f32 receives {normal.xyz, t, p.xyz, matId (int32)} per ray, --sets the uint32 index of the winning set per ray; --occluded: <out.f32> receives one byte per ray instead, 1 iff something blocks it (mirt_trace_occluded)
 //   node cli.js trace  <scene.xml> <rays.f32> <out.f32> --radiance [--samples S] [--bounces B] [--seed-base X] [--no-emitters]  -> path radiance of the caller's own rays in one launch (mirt_trace_radiance): out.f32 receives 16 bytes per ray, the accumulator {r, g, b sums, number of contributions} of S (default 1) runs of the pass's path with B (default 5) bounces from each ray on; seeds from mirt_seed_fill(first_ray = 0, count, X); --no-emitters: the lights are not rendered on the caller's ray (it continues a path whose vertex already sampled them)
+//   node cli.js trace  <scene.xml> <W>x<H>x<raysPerPixel> <rays-out.f32> --view-rays --view equirect|fisheye|ortho [camera options as above]  -> the camera's rays themselves (mirt_view_rays): raw 32-byte records in (pixel, sy, sx) order, ready for the queries above
 //   node cli.js devices                                                             -> what webcl.getPlatforms()/getDevices() report
 "use strict";
 const fs = require("fs");
@@ -23,8 +25,27 @@ function writeFrame(out, px, w, h) {
   fs.writeFileSync(out, Buffer.concat([Buffer.from(`P6\n${w} ${h}\n255\n`, "ascii"), rgb]));
 }
 
+// the camera options of --view (render) and --view-rays (trace): -> renderer.makeView's v
+function viewOptions(rest) {
+  const vi = rest.indexOf("--view");
+  if (vi < 0 || !rest[vi + 1]) usage();
+  const v = { model: rest[vi + 1] };
+  if (!["equirect", "fisheye", "ortho"].includes(v.model)) { process.stderr.write(`--view ${v.model}: equirect, fisheye or ortho\n`); process.exit(2); }
+  const list = (flag, n) => {
+    const i = rest.indexOf(flag);
+    if (i < 0) return undefined;
+    const a = String(rest[i + 1] || "").split(",").map(Number);
+    if (a.length !== n || a.some((x) => !Number.isFinite(x))) { process.stderr.write(`${flag} takes ${n} numbers separated by commas\n`); process.exit(2); }
+    return a;
+  };
+  v.eye = list("--eye", 3); v.look = list("--look", 3); v.up = list("--up", 3); v.orthoSize = list("--ortho-size", 2);
+  const f = list("--fov", 1);
+  if (f) v.fov = f[0];
+  return v;
+}
+
 function usage() {
-  process.stderr.write(fs.readFileSync(__filename, "utf8").split("\n").slice(1, 13).join("\n") + "\n");
+  process.stderr.write(fs.readFileSync(__filename, "utf8").split("\n").slice(1, 15).join("\n") + "\n");
   process.exit(2);
 }
 
@@ -39,6 +60,21 @@ if (cmd === "pack") {
 } else if (cmd === "render") {
   if (rest.length < 6) usage();
   const renderer = require("./renderer.js");
+  if (rest.includes("--view")) {   // a panoramic, fisheye or orthographic camera: one launch per pass (mirt_render_view)
+    for (const flag of ["--gpus", "--guides", "--denoise", "--upscale", "--ao"])
+      if (rest.includes(flag)) { process.stderr.write(`--view is not available with ${flag}: guides, the filter, the upsampler, AO and row tiles over N devices are not built for these cameras\n`); process.exit(2); }
+    const vopt = { view: viewOptions(rest), bounces: 5, seeds: null, countDeferred: true };
+    let j;
+    if ((j = rest.indexOf("--bounces")) >= 0) vopt.bounces = +rest[j + 1];
+    if ((j = rest.indexOf("--seeds")) >= 0) { const b = fs.readFileSync(rest[j + 1]); vopt.seeds = new Int32Array(b.buffer.slice(b.byteOffset, b.byteOffset + b.length)); }
+    const [vf, vw, vh, vrpp, vpasses, vout] = [rest[0], +rest[1], +rest[2], +rest[3], +rest[4], rest[5]];
+    let res;
+    try { res = renderer.renderViewFile(vf, vw, vh, vrpp, vpasses, vopt); } catch (e) { process.stderr.write(e.message + "\n"); process.exit(2); }
+    writeFrame(vout, res.pixel, vw, vh);
+    fs.writeFileSync(vout + ".radiance.f32", Buffer.from(res.radiance.buffer, res.radiance.byteOffset, res.radiance.byteLength));
+    process.stderr.write(`rendered ${vf} ${vw}x${vh} rpp ${vrpp}, ${vpasses} pass(es), ${vopt.view.model} camera: ${res.ms.toFixed(2)} ms on ${res.device}; rays redone by the exact kernel: ${res.deferred}\n`);
+    process.exit(0);
+  }
   const opt = { granular: rest.includes("--granular"), graph: rest.includes("--graph"), fusion: rest.includes("--fusion"), deviceGrid: rest.includes("--device-grid"), bounces: 5, seeds: null,
                 keepAcu: !rest.includes("--no-acu"),   // --no-acu: a frame without the 16 bytes per ray: the pass resolves its own pixels (mirt.h; raysPerPixel
                                                         // dividing 256 or above 256) -- one pass, or
@@ -161,6 +197,15 @@ if (cmd === "pack") {
   const renderer = require("./renderer.js");
   const si = rest.indexOf("--sets");
   if (si >= 0 && !rest[si + 1]) usage();
+  if (rest.includes("--view-rays")) {   // the rays of a panoramic, fisheye or orthographic camera (mirt_view_rays): <W>x<H>x<raysPerPixel> in place of the ray file
+    const m = /^(\d+)x(\d+)x(\d+)$/.exec(rest[1]);
+    if (!m) { process.stderr.write("--view-rays: the second argument is <W>x<H>x<raysPerPixel>\n"); process.exit(2); }
+    let rays;
+    try { rays = renderer.viewRaysFile(rest[0], +m[1], +m[2], +m[3], { view: viewOptions(rest) }); } catch (e) { process.stderr.write(e.message + "\n"); process.exit(2); }
+    fs.writeFileSync(rest[2], Buffer.from(rays.buffer, rays.byteOffset, rays.byteLength));
+    process.stderr.write(`wrote ${rays.length / 8} rays of the ${rest[rest.indexOf("--view") + 1]} camera of ${rest[0]} at ${rest[1]} to ${rest[2]}\n`);
+    process.exit(0);
+  }
   const raw = fs.readFileSync(rest[1]);
   if (raw.length % 32) { process.stderr.write(`${rest[1]}: ${raw.length} bytes is not a whole number of 32-byte rays\n`); process.exit(2); }
   const rays = new Float32Array(raw.length / 4);

@@ -747,4 +747,74 @@ function traceFile(file, rays, opt) {
   return res;
 }
 
-module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };
+// ---- panoramic, fisheye and orthographic cameras on a scene file (queue.viewRays / renderView; include/mirt.h has the definition).
+// v = {model: "equirect" | "fisheye" | "ortho", eye, look, up (3 numbers each), fov (FISHEYE: the full field of view in degrees, default 180),
+// orthoSize ([w, h], the ORTHOGRAPHIC window, default the scene box's extents in x and y)}.  Left out: the eye is the scene box's centre, looking
+// down -z with +y up.  The basis is computed in double -- forward = normalize(look - eye), right = normalize(forward x up), up' = right x forward
+// -- and narrowed once, as pyhost/mirt.py view_desc does.
+const VIEW_MODELS = { ortho: 0, orthographic: 0, equirect: 1, fisheye: 2 };
+function makeView(packed, width, height, rpp, v) {
+  v = v || {};
+  if (!(v.model in VIEW_MODELS)) throw new Error(`--view ${v.model}: equirect, fisheye or ortho`);
+  const k = Math.round(Math.sqrt(rpp));
+  if (k * k !== rpp || ![1, 2, 4, 8, 16].includes(k)) throw new Error(`--view: raysPerPixel ${rpp} is not 1, 4, 16, 64 or 256`);
+  const b = packed.bounds, lo = [b[0], b[1], b[2]], hi = [b[4], b[5], b[6]];
+  const eye = v.eye || lo.map((x, c) => (x + hi[c]) / 2);
+  const look = v.look || [eye[0], eye[1], eye[2] - 1];
+  const up0 = v.up || [0, 1, 0];
+  const norm = (a) => { const l = Math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); return [a[0] / l, a[1] / l, a[2] / l]; };
+  const cross = (a, c) => [a[1] * c[2] - a[2] * c[1], a[2] * c[0] - a[0] * c[2], a[0] * c[1] - a[1] * c[0]];
+  const forward = norm([look[0] - eye[0], look[1] - eye[1], look[2] - eye[2]]);
+  const right = norm(cross(forward, up0));
+  const up = cross(right, forward);
+  const size = v.orthoSize || [hi[0] - lo[0], hi[1] - lo[1]];
+  const fov = v.fov === undefined ? 180 : v.fov;
+  return { model: VIEW_MODELS[v.model], width: width, height: height, k: k, eye: eye, right: right, up: up, forward: forward,
+           halfW: size[0] / 2, halfH: size[1] / 2, halfAngle: fov / 2 * Math.PI / 180, tMin: 0, tMax: Infinity, tone: 1 };
+}
+// -> {pixel: Uint8ClampedArray, radiance: Float32Array (the sums after the last pass), ms, device, deferred}: `passes` progressive frames,
+// MIRT_VIEW_ACCUMULATE from the second on, tone 1 / (rpp * p).  opt.view: makeView's v; opt.bounces; opt.seeds (Int32Array) or seedFill(0, n, 0).
+function renderViewFile(file, width, height, rpp, passes, opt) {
+  opt = opt || {};
+  const packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, 4);
+  const view = makeView(packed, width, height, rpp, opt.view);
+  const ctx = webcl.createContext(pickDevice(opt.device)), q = ctx.createCommandQueue();
+  if (!q.hasView()) throw new Error("the loaded addon has no renderView");
+  const dev = uploadScene(ctx, q, packed);
+  const npix = width * height, n = npix * rpp;
+  const mk = (bytes) => ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(bytes, 16));
+  const sb = mk(n * 4), rb = mk(npix * 16), pb = mk(npix * 4);
+  if (opt.seeds) q.enqueueWriteBuffer(sb, false, 0, n * 4, opt.seeds.subarray(0, n), []);
+  else q.seedFill(sb, 0, n, 0);
+  const desc = { spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, lights: packed.lights, material: dev.material, bounces: opt.bounces === undefined ? 5 : opt.bounces };
+  q.finish();
+  const t0 = process.hrtime.bigint();
+  let deferred = 0;
+  for (let p = 1; p <= passes; p++) {
+    q.renderView(desc, Object.assign({}, view, { flags: p > 1 ? 1 : 0, tone: 1 / (rpp * p) }), sb, rb, pb);
+    if (opt.countDeferred) deferred += q.viewDeferred();
+  }
+  q.finish();
+  const ms = Number(process.hrtime.bigint() - t0) / 1e6;
+  const res = { pixel: new Uint8ClampedArray(npix * 4), radiance: new Float32Array(npix * 4), ms: ms, device: pickDevice(opt.device).getInfo(webcl.DEVICE_NAME), deferred: deferred };
+  q.enqueueReadBuffer(pb, true, 0, npix * 4, res.pixel, []);
+  q.enqueueReadBuffer(rb, true, 0, npix * 16, res.radiance, []);
+  ctx.release();
+  return res;
+}
+// -> Float32Array of 8 per ray: the view's rays themselves (queue.viewRays), for callers who want them
+function viewRaysFile(file, width, height, rpp, opt) {
+  opt = opt || {};
+  const packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, 4);
+  const view = makeView(packed, width, height, rpp, opt.view);
+  const ctx = webcl.createContext(pickDevice(opt.device)), q = ctx.createCommandQueue();
+  const n = width * height * rpp;
+  const rb = ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(n * 32, 16));
+  q.viewRays(view, rb);
+  const rays = new Float32Array(n * 8);
+  q.enqueueReadBuffer(rb, true, 0, n * 32, rays, []);
+  ctx.release();
+  return rays;
+}
+
+module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderViewFile, viewRaysFile, makeView, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };

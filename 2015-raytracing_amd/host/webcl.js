@@ -231,6 +231,26 @@ class WebCLCommandQueue {
     wrap(() => native().traceRadiance(this.ctx.h, d, radDesc || {}, rays ? rays.h : null, count, seeds ? seeds.h : null, radiance ? radiance.h : null));
   }
   radianceDeferred() { return wrap(() => native().radianceDeferred(this.ctx.h)); }
+  // ---- extension: panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view; include/mirt.h has the definition).  view =
+  // {model: VIEW_ORTHOGRAPHIC 0 | VIEW_EQUIRECT 1 | VIEW_FISHEYE 2, width, height (the whole image), k (samples per axis: 1, 2, 4, 8, 16), row0, nrows
+  // (left out: the whole image), flags (VIEW_ACCUMULATE 1), eye, right, up, forward (3 numbers each, used as given), halfW, halfH (ORTHOGRAPHIC),
+  // halfAngle (FISHEYE, radians), tMin, tMax, tone}.  viewRays(view, rays): the tile's width * nrows * k * k 32-byte rays.  renderView(desc, view,
+  // seeds, radiance, pixel): the frame in one launch -- seeds: an int32 per tile ray, advanced in place; radiance: float4 per tile pixel, the sums in
+  // copyToPixel's order (continued from its contents with VIEW_ACCUMULATE); pixel: RGBA8, tone-mapped with view.tone; either output may be null.  Of
+  // desc spheres, triangles, meshes, lights, material and bounces (left out: 5) are read.  viewDeferred(): the rays the last renderView re-ran in
+  // the exact kernel, in whole blocks of 256.
+  hasView() { return typeof native().renderView === "function"; }
+  _viewDesc(view) {
+    const v3 = (a) => Float32Array.from(a || []);
+    return Object.assign({}, view, { eye: v3(view.eye), right: v3(view.right), up: v3(view.up), forward: v3(view.forward) });
+  }
+  viewRays(view, rays) { wrap(() => native().viewRays(this.ctx.h, this._viewDesc(view), rays ? rays.h : null)); }
+  renderView(desc, view, seeds, radiance, pixel) {
+    const d = Object.assign(this._setsDesc(desc), { lights: desc.lights || [], material: desc.material ? desc.material.h : undefined });
+    if (desc.bounces !== undefined) d.bounces = desc.bounces;
+    wrap(() => native().renderView(this.ctx.h, d, this._viewDesc(view), seeds ? seeds.h : null, radiance ? radiance.h : null, pixel ? pixel.h : null));
+  }
+  viewDeferred() { return wrap(() => native().viewDeferred(this.ctx.h)); }
   // ---- extension: a frame's first pass and its guide buffers in one call (mirt_render_first_pass_guided): every buffer ends as after
   // renderPass(desc with firstPass) followed by renderGuides(desc, normalHits, albedoDepth) -- where the pass resolves its pixels at 4, 16 or 64 rays
   // per pixel the pass's own launch writes the guides (ctx.guidedPasses() counts those calls), elsewhere the guide launches follow it.

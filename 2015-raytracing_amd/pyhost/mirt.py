@@ -7,6 +7,7 @@ mirt_last_error().  There is NO CPU fallback here or below: without libmirt.so o
 a gfx950 device every entry point raises.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -86,7 +87,18 @@ class _RadianceDesc(C.Structure):   # mirt_radiance_desc
     _fields_ = [("struct_size", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _ViewDesc(C.Structure):   # mirt_view_desc
+    _fields_ = [("struct_size", C.c_uint32), ("model", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("k", C.c_uint32),
+                ("row0", C.c_uint32), ("nrows", C.c_uint32), ("flags", C.c_uint32),
+                ("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3),
+                ("half_w", C.c_float), ("half_h", C.c_float), ("half_angle", C.c_float), ("t_min", C.c_float), ("t_max", C.c_float), ("tone", C.c_float)]
+
+
 _lib = None
+
+VIEW_ORTHOGRAPHIC, VIEW_EQUIRECT, VIEW_FISHEYE = 0, 1, 2   # MIRT_VIEW_* models (include/mirt.h)
+VIEW_ACCUMULATE = 1   # MIRT_VIEW_ACCUMULATE
+VIEW_MODELS = {"ortho": VIEW_ORTHOGRAPHIC, "orthographic": VIEW_ORTHOGRAPHIC, "equirect": VIEW_EQUIRECT, "fisheye": VIEW_FISHEYE}
 
 RADIANCE_ACCUMULATE, RADIANCE_NO_EMITTERS, RADIANCE_MAX_SAMPLES = 1, 2, 64   # MIRT_RADIANCE_* (include/mirt.h)
 AO_MAX_SAMPLES, AO_DEFAULT_SAMPLES, AO_DEFAULT_BIAS = 64, 4, 0.001   # MIRT_AO_* (include/mirt.h)
@@ -142,6 +154,9 @@ SYMBOLS = {
     "mirt_trace_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_trace_radiance": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_RadianceDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "mirt_radiance_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_view_rays": (C.c_int, [C.c_void_p, C.POINTER(_ViewDesc), C.c_void_p]),
+    "mirt_render_view": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mirt_view_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_render_ao": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_AoDesc), C.c_void_p]),
     "mirt_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
@@ -591,6 +606,25 @@ class Context:
         self._chk(lib().mirt_radiance_deferred(self.h, C.byref(n)))
         return n.value
 
+    def view_rays(self, view, rays):
+        """The rays of a panoramic, fisheye or orthographic camera's row tile as 32-byte records (mirt_view_rays): view.width * nrows * k * k of
+        them, in (pixel, sy, sx) order.  view: a _ViewDesc (view_desc())."""
+        self._chk(lib().mirt_view_rays(self.h, C.byref(view) if view is not None else None, rays.h if rays else None))
+
+    def render_view(self, scene_desc, view, seeds, radiance=None, pixel=None):
+        """A frame of a panoramic, fisheye or orthographic camera in one launch (mirt_render_view): the rays of view_rays, the pass's path along
+        each (the sets, lights, material and bounces of scene_desc), and the per-pixel sums in copyToPixel's order -- into radiance (float4 per tile
+        pixel, continued from its contents with VIEW_ACCUMULATE in view.flags) and / or pixel (RGBA8, tone-mapped with view.tone).  seeds (int32
+        per tile ray) is advanced in place."""
+        self._chk(lib().mirt_render_view(self.h, C.byref(scene_desc) if scene_desc is not None else None, C.byref(view) if view is not None else None,
+                                         seeds.h if seeds else None, radiance.h if radiance else None, pixel.h if pixel else None))
+
+    def view_deferred(self):
+        """how many rays the last render_view call re-ran in the exact kernel, in whole blocks of 256 (mirt_view_deferred)"""
+        n = C.c_uint64()
+        self._chk(lib().mirt_view_deferred(self.h, C.byref(n)))
+        return n.value
+
     def render_ao(self, desc, ao_out, samples=AO_DEFAULT_SAMPLES, radius=float("inf"), bias=AO_DEFAULT_BIAS):
         """Ambient occlusion of the first hit of desc's row tile in one launch (mirt_render_ao): ao_out receives uint32 {open, cast} per pixel --
         per hit primary sample `samples` hemisphere rays of length `radius` from the hit point, displaced by `bias` along the normal; cast counts
@@ -679,6 +713,31 @@ class Context:
         if self.h:
             lib().mirt_ctx_destroy(self.h)
             self.h = None
+
+
+def view_desc(model, width, height, k=1, eye=(0.0, 0.0, 0.0), look_at=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), half_w=1.0, half_h=1.0,
+              half_angle=float(np.pi) / 2, t_min=0.0, t_max=float("inf"), tone=1.0, row0=0, nrows=0, flags=0):
+    """-> a _ViewDesc (mirt_view_desc) for a camera at `eye` looking at `look_at`: forward = normalize(look_at - eye), right = normalize(forward x
+    up), up' = right x forward -- computed in double and narrowed to fp32 once.  model: VIEW_* or one of VIEW_MODELS' names.  The fields stay
+    writable: a caller with a basis of its own assigns eye / right / up / forward afterwards."""
+    def norm(a):
+        l = math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
+        return [a[0] / l, a[1] / l, a[2] / l]
+
+    def cross(a, b):
+        return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+    e, t, u = ([float(c) for c in v] for v in (eye, look_at, up))   # the same double operations as host/renderer.js makeView
+    f = norm([t[0] - e[0], t[1] - e[1], t[2] - e[2]])
+    r = norm(cross(f, u))
+    u = cross(r, f)
+    d = _ViewDesc()
+    d.struct_size = C.sizeof(_ViewDesc)
+    d.model = VIEW_MODELS[model] if isinstance(model, str) else int(model)
+    d.width, d.height, d.k, d.row0, d.nrows, d.flags = int(width), int(height), int(k), int(row0), int(nrows), int(flags)
+    for name, v in (("eye", e), ("right", r), ("up", u), ("forward", f)):
+        setattr(d, name, (C.c_float * 3)(*(float(np.float32(c)) for c in v)))
+    d.half_w, d.half_h, d.half_angle, d.t_min, d.t_max, d.tone = (float(np.float32(x)) for x in (half_w, half_h, half_angle, t_min, t_max, tone))
+    return d
 
 
 def _f(arr, n):

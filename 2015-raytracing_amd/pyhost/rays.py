@@ -1,5 +1,6 @@
 """Ray queries on torch tensors: the closest hit, occlusion, or the path radiance of rays the caller holds as a cuda tensor (mirt_trace_closest,
-mirt_trace_occluded, mirt_trace_radiance; the definitions are include/mirt.h's).
+mirt_trace_occluded, mirt_trace_radiance; the definitions are include/mirt.h's) -- and, beside trace_radiance, render_view: a frame of a
+panoramic, fisheye or orthographic camera into cuda tensors (mirt_render_view).
 
 The tensors are not copied: each is wrapped as a buffer of the context (Context.wrap) for the length of the call, and the launches are queued on
 torch's CURRENT stream (Context.set_stream), so they are ordered after whatever produced `rays` there and before whatever reads the result there.
@@ -91,3 +92,33 @@ def trace_radiance(ctx, dev_scene, rays, seeds, samples=1, bounces=5, accumulate
                 for b in wrapped:
                     b.release()
     return out
+
+
+def render_view(ctx, dev_scene, view, seeds, bounces=5, accumulate_into=None, want_pixel=False):
+    """-> radiance [rows * width, 4] float32, or (radiance, pixel [rows * width, 4] uint8) with want_pixel: a frame (or row tile) of a panoramic,
+    fisheye or orthographic camera in one launch (mirt_render_view).  view: mirt.view_desc(...); its ACCUMULATE flag is set here from
+    accumulate_into, a float32 cuda [rows * width, 4] of sums to continue (written in place and returned).  seeds: int32 cuda [rows * width * k * k],
+    advanced in place."""
+    from . import mirt
+    rows = view.nrows or view.height
+    npix = rows * view.width
+    n = npix * view.k * view.k
+    if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.shape == (n,) and seeds.is_contiguous()):
+        raise ValueError(f"seeds: a contiguous int32 cuda tensor [{n}]")
+    if seeds.device.index != ctx.device:
+        raise ValueError(f"seeds live on cuda:{seeds.device.index}, the context on device {ctx.device}")
+    out = accumulate_into
+    if out is None:
+        out = torch.empty((npix, 4), dtype=torch.float32, device=seeds.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == (npix, 4) and out.is_contiguous() and out.device == seeds.device):
+        raise ValueError("accumulate_into: a contiguous float32 cuda tensor [rows * width, 4] on the seeds' device")
+    pixel = torch.empty((npix, 4), dtype=torch.uint8, device=seeds.device) if want_pixel else None
+    view.flags = mirt.VIEW_ACCUMULATE if accumulate_into is not None else 0
+    with _OnTorchStream(ctx, seeds.device):
+        wrapped = [ctx.wrap(seeds.data_ptr(), n * 4), ctx.wrap(out.data_ptr(), npix * 16)] + ([ctx.wrap(pixel.data_ptr(), npix * 4)] if want_pixel else [])
+        try:
+            ctx.render_view(dev_scene.pass_desc(None, None, bounces=bounces), view, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None)
+        finally:
+            for b in wrapped:
+                b.release()
+    return (out, pixel) if want_pixel else out

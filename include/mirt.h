@@ -377,6 +377,67 @@ typedef struct mirt_radiance_desc { uint32_t struct_size, samples, flags, reserv
 MIRT_API int mirt_trace_radiance(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_radiance_desc* rd, mirt_buf* rays, uint64_t count,
                                  mirt_buf* seeds, mirt_buf* radiance);
 MIRT_API int mirt_radiance_deferred(mirt_ctx* ctx, uint64_t* rays);
+/* PANORAMIC, FISHEYE AND ORTHOGRAPHIC CAMERAS: a frame of a camera other than the reference's thin lens in ONE launch -- the rays made in
+ * registers, traced as mirt_trace_radiance traces them and reduced to pixels inside the block.  By hand it was three launches and three trips
+ * through memory per sample (32 B per ray written and read, 16 B per accumulator written and read); here a sample costs its seed, 8 B.
+ * THE RAYS, defined once for both calls.  Every operation is ONE fp32 operation rounded on its own, in the order written; nothing is an fma
+ * except inside sincos.  `/` is the correctly rounded fp32 quotient, sqrt_cr(x) = (float)sqrt((double)x) the correctly rounded root, sincos the
+ * contract's sin and cos (csrc/pt_numerics.hpp cl_sincos): ONE contract, libmirt.so and libmirt_default.so give the same bits.
+ *   Global pixel (x, y), y = row0 + tile row; sample i = 0 .. rpp - 1, rpp = k * k, sy = i div k, sx = i mod k.  The tile-local ray id is
+ *   ((y - row0) * width + x) * rpp + i; seeds and rays are tile-local, positions use the global y: a tile's rays equal the same rows of the frame's.
+ *     fx = (float)x + ((float)sx + 0.5f) * ik, ik = 1 / k (exact: k is a power of two); fy likewise from y and sy
+ *     u = fx / (float)width, v = fy / (float)height;   a = (u + u) - 1.0f, b = 1.0f - (v + v)        (row 0 is the top)
+ *   ORTHOGRAPHIC   ta = a * half_w, tb = b * half_h;  o.c = (eye.c + right.c * ta) + up.c * tb;  d = forward
+ *   EQUIRECT       phi = a * 0x1.921fb6p+1f, th = b * 0x1.921fb6p+0f;  (sp, cp) = sincos(phi), (st, ct) = sincos(th);
+ *                  lx = sp * ct, ly = st, lz = cp * ct;  d.c = (right.c * lx + up.c * ly) + forward.c * lz;  o = eye
+ *   FISHEYE        r = sqrt_cr(a * a + b * b).  When r <= 1.0f is false the sample is DEAD: o = eye, d = forward, mint = maxt = 0.  Otherwise
+ *                  ang = r * half_angle, (sa, ca) = sincos(ang), q = r > 0 ? sa / r : 0;  lx = a * q, ly = b * q, lz = ca;  d and o as EQUIRECT
+ *   Every live ray has mint = t_min and maxt = t_max.  No jitter: nothing is drawn from the seeds, like the reference's k x k lens grid.  eye,
+ *   right, up and forward are used as given, neither normalised nor orthogonalised.
+ * mirt_view_rays writes the tile's width * nrows * rpp mirt_ray records and nothing else.
+ * mirt_render_view: everything the caller passes ends, bit for bit, as after (1) mirt_view_rays into a ray buffer, (2) mirt_trace_radiance(ctx,
+ * scene, {samples 1, flags 0}, rays, count, seeds, acc) on them -- the same fields of `scene` are read: the sets, lights, material, bounces; a
+ * dead sample adds nothing and draws nothing -- (3) per tile pixel p, radiance[p] = the sequential fp32 sum of acc[p * rpp + i], i = 0 .. rpp - 1,
+ * all four channels, from +0 or, with MIRT_VIEW_ACCUMULATE, from radiance[p] as given: copyToPixel's order (A10 code.cl:1377-1380), (4) pixel[p] =
+ * copyToPixel's own tone map of that sum with m = tone.  The rays and the per-ray accumulators never reach memory.  seeds (int32 per tile ray)
+ * are read and written; radiance (float4 per tile pixel) and pixel (RGBA8 per tile pixel) may each be NULL, not both; ACCUMULATE needs radiance.
+ * Progressive frames: call p = 1, 2, ... with ACCUMULATE from the second on and tone = 1 / (rpp * p).
+ * CHECKS, all before anything is queued; nothing is written when one fails, and the context works afterwards.  MIRT_E_ARG: a wrong struct_size
+ * in either descriptor, an unknown model or flag, k not in {1, 2, 4, 8, 16}, width or height 0 or above 65535, a tile outside the image or of
+ * more than 2^32 - 256 rays, a non-finite eye or basis component, ORTHOGRAPHIC half_w or half_h not finite or <= 0, FISHEYE half_angle not
+ * finite, <= 0 or > pi, t_min negative or not finite, t_max NaN or <= t_min, tone not finite or <= 0 when pixel is given, NULL seeds, both
+ * outputs NULL, ACCUMULATE without radiance, outputs whose bytes meet each other's, the seeds', a geometry buffer's or the material's, the light
+ * and mesh count rules of mirt_trace_radiance, a call while capturing.  MIRT_E_RANGE: a buffer shorter than the tile's rays or pixels, a material
+ * table shorter than one entry.  MIRT_E_DATA: a cell table that fails validation.  MIRT_E_HANDLE: a bad context or buffer.  A held command
+ * stream is flushed first; wrapped geometry is re-validated as for a pass.
+ * KERNELS (csrc/pt_kernels_rays.hip; a sample's ray is csrc/pt_view.hpp's, the checks and the plan csrc/pt_view_plan.hpp's).  k_viewRays: one
+ * lane per ray.  k_viewPass: k_traceRadiance's body with the ray made in registers, then the pass's in-block resolve; a block is 256 consecutive
+ * ray ids = 256 / rpp whole pixels.  By default the optimistic / exact pair PER BLOCK: a block with a primary, shadow or bounce ray the ray-side
+ * guard refuses, or a walk that defers, writes neither its seeds nor its pixels and is re-run whole by the exact kernel;
+ * mirt_ctx_set_exact_only is honoured.  An ORTHOGRAPHIC camera whose `forward` has a zero component is outside the ray-side guard for every ray
+ * (|d_k| >= 2^-40): its frames run wholly in the exact kernel, with the same results.  mirt_view_deferred: the rays the last mirt_render_view
+ * re-ran in the exact kernel, counted when asked, like mirt_radiance_deferred, in whole blocks of 256.
+ * NOT BUILT: guides, ambient occlusion or the filter for these cameras; jitter or a lens on them; k that is not a power of two, or above 16; more
+ * than one sample per ray per call; a multi-device helper (tiles take global positions, so a caller can split the rows); graph capture.
+ * MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
+#define MIRT_VIEW_ORTHOGRAPHIC 0u
+#define MIRT_VIEW_EQUIRECT     1u   /* 360 x 180 degrees, longitude along x, latitude along y */
+#define MIRT_VIEW_FISHEYE      2u   /* equidistant, the circle inscribed in the image window  */
+#define MIRT_VIEW_ACCUMULATE   1u   /* flags: radiance[pixel] is read and the chain of additions goes on from it */
+typedef struct mirt_view_desc {
+    uint32_t struct_size, model, width, height;   /* the WHOLE image, 1 .. 65535 each                  */
+    uint32_t k;                                   /* samples per axis: 1, 2, 4, 8 or 16; rpp = k * k   */
+    uint32_t row0, nrows;                         /* row tile as in mirt_pass_desc; nrows 0 = whole    */
+    uint32_t flags;
+    float eye[3], right[3], up[3], forward[3];    /* used as given: not normalised, not orthogonalised */
+    float half_w, half_h;                         /* ORTHOGRAPHIC: half extents of the window, > 0     */
+    float half_angle;                             /* FISHEYE: radians at the circle's rim, (0, pi]     */
+    float t_min, t_max;                           /* every live ray's mint / maxt; 0 <= t_min < t_max, t_max may be +inf */
+    float tone;                                   /* copyToPixel's m; read only when `pixel` is given  */
+} mirt_view_desc;
+MIRT_API int mirt_view_rays(mirt_ctx* ctx, const mirt_view_desc* view, mirt_buf* rays);
+MIRT_API int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel);
+MIRT_API int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays);
 /* AMBIENT OCCLUSION OF THE FIRST HIT of the row tile, in one launch: the AOV the guides lack.  ao_out holds one uint32[2] per tile-local pixel,
  * {open, cast}, 8 bytes per pixel.  Pixel p of the row tile has the rays p * rays_per_pixel + i, i = 0 .. rays_per_pixel - 1, each taken as
  * initTrace and the closest-hit stage leave it -- sphereTrace, triangleTrace, then every meshTrace in upload order -- before lightRender: exactly
