@@ -19,8 +19,11 @@ SENTINEL = 0xA7
 _EXPECTED = {}
 
 
-def expected_radiance(sc, rays, seeds, samples, bounces, acu=None, emitters=True, k=None):
-    """-> (radiance float32 [n, 4], seeds int32 [n]): the accumulators and seeds the kernel sequence leaves.  acu: the accumulators to go on from."""
+def expected_radiance(sc, rays, seeds, samples, bounces, acu=None, emitters=True, k=None, watch=None):
+    """-> (radiance float32 [n, 4], seeds int32 [n]): the accumulators and seeds the kernel sequence leaves.  acu: the accumulators to go on from.
+    watch: optional callable, called as watch("rays", ray buffer) with the caller's rays before the first closest() of a sample and after every
+    bouncePaths, and as watch("shadow", shadow buffer) after every initShadowTrace (a10_pass.run_pass's `watch`: every ray the sequence makes,
+    before anything traces it; the buffers are a10_pass.RAY_DT records, the first n of them the caller's).  It changes no result."""
     k = k or A.load_oracle()
     rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
     n = len(rays)
@@ -32,6 +35,12 @@ def expected_radiance(sc, rays, seeds, samples, bounces, acu=None, emitters=True
     sd = np.zeros(g1, np.int32)
     sd[:n] = seeds
     shadow = np.zeros(g1, A.RAY_DT)
+
+    def seen(kind, buf):
+        if watch is not None:
+            k.flush()
+            watch(kind, buf)
+
     for _ in range(samples):
         rb = rb0.copy()
         pb = np.zeros(g1, A.POI_DT)
@@ -46,6 +55,7 @@ def expected_radiance(sc, rays, seeds, samples, bounces, acu=None, emitters=True
             for l in sc.lights:
                 p, _k = A._f(l["shadow"])
                 k.initShadowTrace(B(shadow), B(pb), n, p, B(sd), g1)
+                seen("shadow", shadow)
                 if sc.has_spheres:
                     p, _k = A._f(sc.sphere_bounds)
                     k.sphereShadowTrace(n, B(shadow), B(sc.spheres), B(sc.s_box), p, sc.n_slabs, g1)
@@ -58,6 +68,7 @@ def expected_radiance(sc, rays, seeds, samples, bounces, acu=None, emitters=True
                 p, _k = A._f(l["scene"])
                 k.sceneRender(B(acc), B(pb), B(shadow), B(sc.materials), p, n, g1)
 
+        seen("rays", rb)
         closest()
         if emitters:
             for l in sc.lights:
@@ -66,6 +77,7 @@ def expected_radiance(sc, rays, seeds, samples, bounces, acu=None, emitters=True
         direct()
         for _j in range(bounces):
             k.bouncePaths(B(pb), B(rb), B(sd), n, g1)
+            seen("rays", rb)
             closest()
             direct()
         k.flush()
