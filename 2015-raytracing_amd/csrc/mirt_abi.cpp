@@ -11,6 +11,7 @@
 #include "pt_rows_plan.hpp"
 #include "pt_view_plan.hpp"
 #include "pt_set_guard.hpp"
+#include "pt_shadow_gap.hpp"
 #include "pt_stream_match.hpp"
 #include "pt_upsample_taps.hpp"
 
@@ -147,6 +148,8 @@ struct mirt_buf {
     uint64_t prep_version = 0;
     uint64_t prep_gen = 1;    // bumped whenever `prep` is freed or replaced
     bool prep_sane = false;   // every plane-normal component is 0 or in [2^-40, 2^40]
+    bool gap_planes_ok = false;   // `gap_planes` holds the axis planes of the prepared copy's plane list (at most kLdsTriMax records)
+    pt::GapPlanes gap_planes;     // read back once per buffer content (ensure_prepared); fill_grid makes a set's plane-free gap from it (pt_shadow_gap.hpp)
 };
 
 struct mirt_kernel {
@@ -251,8 +254,15 @@ int ensure_prepared(mirt_ctx* ctx, mirt_buf* pb, uint32_t count) {
     HIPCHK(ctx, hipMemsetAsync(ctx->scratch, 0, 4, ctx->stream));
     pt::launch_prepTriangles(ctx->stream, pb->ptr, pb->prep, count, (uint32_t*)ctx->scratch);
     HIPCHK(ctx, hipMemcpyAsync(&insane, ctx->scratch, 4, hipMemcpyDeviceToHost, ctx->stream));
+    // the plane list of a small set, once per buffer content: the host takes the axis planes from it (pt_shadow_gap.hpp)
+    std::vector<uint32_t> planes;
+    if (count && count <= pt::kLdsTriMax) {
+        planes.resize(pt::prepared_planes_bytes(count) / 4);
+        HIPCHK(ctx, hipMemcpyAsync(planes.data(), (const char*)pb->prep + pt::prepared_planes_offset(count), planes.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     pb->prep_sane = insane == 0;
+    pb->gap_planes_ok = !planes.empty() && pt::gap_planes_from_list(planes.data(), (uint32_t)planes.size(), count, &pb->gap_planes) != 0;
     pb->prep_version = pb->version;
     if (pb->prep_count != count) pb->prep_gen++;   // rebuilt in place for another count: the group spheres and the sweep array moved, a recorded graph must not replay against it
     pb->prep_count = count;
@@ -1260,6 +1270,14 @@ static int fill_grid(mirt_ctx* ctx, const char* what, const mirt_grid* g, bool t
     memcpy(o->exit_up, v.exit_up, sizeof o->exit_up);
     memcpy(o->delta, v.delta, sizeof o->delta);
     memcpy(o->rdelta, v.rdelta, sizeof o->rdelta);
+    // the plane-free gap of a single-cell triangle set with a plane list, for these bounds (pt_shadow_gap.hpp)
+    o->gap_ok = 0u;
+    memset(o->gap, 0, sizeof o->gap);
+    if (tri && o->pnorm && g->n_slabs == 1u && v.fast_ok && g->prims->gap_planes_ok && g->prims->prep_count == g->cell_offsets->off_last) {
+        const pt::ShadowGap sg = pt::shadow_gap(g->bounds, v.exit_up, &g->prims->gap_planes, 1.0);
+        memcpy(o->gap, sg.qlo, 12); memcpy(o->gap + 3, sg.qhi, 12); memcpy(o->gap + 6, sg.gm, 12); memcpy(o->gap + 9, sg.hm, 12);
+        o->gap_ok = sg.ok;
+    }
     return MIRT_OK;
 }
 

@@ -8,7 +8,30 @@
 #ifndef PT_SKIP_DARK_SHADOWS
 #define PT_SKIP_DARK_SHADOWS 1   // grid kernels: a shadow ray whose vertex the light cannot light is not traced (direct_all)
 #endif
+#ifndef PT_SHADOW_GAP
+#define PT_SHADOW_GAP 1          // optimistic kernels without grids: a wave whose shadow segments all stay inside a single-cell triangle set's plane-free
+                                 // gap skips the set's box test and the axis entries of its plane list (gap_test below; pt_shadow_gap.hpp).  0: the
+                                 // shadow stage as it was
+#endif
+#define PT_SHADOW_GAP_FOR(FAST, GRIDS) (PT_SHADOW_GAP && (GRIDS) == 0 && PT_LANE_LISTS_FOR(FAST, GRIDS))
 namespace pt {
+
+// The gap test of one shadow segment against a set's plane-free gap, gap = GridArgs::gap = {qlo[3], qhi[3], Gm[3], Hm[3]} (scalar operands: kernel
+// arguments).  Both ends of the segment [0, hi+], hi+ the sweep's own widened window end, lie inside the open interval (qlo_a, qhi_a) on every axis
+// by more than m_a = Gm_a |o|_1 + Hm_a; pt_shadow_gap.hpp derives the constants and what a pass implies.  A NaN anywhere compares false: no pass.
+PT_DEV bool gap_test(const Ray& r, const float* gap) {
+    const float o1 = __builtin_fabsf(r.o.x) + __builtin_fabsf(r.o.y) + __builtin_fabsf(r.o.z);
+    const float hi_p = __builtin_fmaxf(r.maxt * 1.00000095367431640625f, 0x1p-100f);
+    const float oo[3] = {r.o.x, r.o.y, r.o.z}, dd[3] = {r.d.x, r.d.y, r.d.z};
+    int pass = 1;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float e = cl_fma(hi_p, dd[a], oo[a]);
+        const float m = cl_fma(gap[6 + a], o1, gap[9 + a]);
+        pass &= (int)(__builtin_fminf(oo[a], e) - gap[a] > m) & (int)(gap[3 + a] - __builtin_fmaxf(oo[a], e) > m);
+    }
+    return pass != 0;
+}
 
 // STRIDE: words between the rows of one lane's record ([word][lane] rows of 256 lanes in k_fusedPass).  ATTE_LDS: the attenuation is
 // parked too (else it stays in registers and the p / n rows move up).  As closest_all's hooks (pt_closest.hpp) it adds put_pn alone.
@@ -73,11 +96,26 @@ PT_DEV void direct_all(const FusedArgs& A, Poi& poi, int32_t& seed, float4& acc,
             bool walked = false;
             if (!GRIDS || S.n == 1u) {
                 if (live) {
-                    pt_count(PC_BOX_TESTS); pt_count(PC_BOX_LANES, true);
-                    const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(sh, rr, set_box(S));
-                    if (bh.v) {
-                        ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, true, TRI_A10, FAST, true>(sh, rr, bh, S) : trace_cell1<TRIANGLES, true, TRI_A10, FAST, true, PT_LANE_LISTS_FOR(FAST, GRIDS)>(sh, rr, bh, S);
+                    bool gap = false;
+                    if (PT_SHADOW_GAP_FOR(FAST, GRIDS) && S.gap_ok != 0u && S.lds_off != kNoLds) {   // wave-uniform: kernel arguments
+                        const bool pass = gap_test(sh, S.gap);
+                        gap = __builtin_amdgcn_ballot_w64(!pass) == 0ull;   // (the live lanes: the others are masked off here)
+                        pt_count(PC_GAP_ASKED);
+                        if (gap) pt_count(PC_GAP_TAKEN);
+                        if (PT_COUNT && !pass) pt_count(PC_GAP_REFUSED_LANES, true);
+                    }
+                    if (gap) {
+                        // every live lane's segment stays inside the set's plane-free gap: the box test would say v, tmin = 0, exit >= maxt
+                        BoxHit bh = {};
+                        ch = trace_cell1<TRIANGLES, true, TRI_A10, FAST, true, PT_LANE_LISTS_FOR(FAST, GRIDS), true>(sh, rr, bh, S);
                         walked = true;
+                    } else {
+                        pt_count(PC_BOX_TESTS); pt_count(PC_BOX_LANES, true);
+                        const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(sh, rr, set_box(S));
+                        if (bh.v) {
+                            ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, true, TRI_A10, FAST, true>(sh, rr, bh, S) : trace_cell1<TRIANGLES, true, TRI_A10, FAST, true, PT_LANE_LISTS_FOR(FAST, GRIDS)>(sh, rr, bh, S);
+                            walked = true;
+                        }
                     }
                 }
             } else if (S.kind == KIND_TRIANGLES) {

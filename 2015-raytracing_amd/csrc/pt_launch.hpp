@@ -73,6 +73,11 @@ struct GridArgs {            // one cell-sorted primitive set, device pointers
                              // walks a set without it hands its sample to the exact kernel
     uint32_t exit_is_far_face; // n == 1 only: lo + 1*((hi-lo)/1) == hi and lo + 0*((hi-lo)/1) == lo hold bitwise on all three
                              // axes (checked on the host: pt_set_guard.hpp set_exit_is_far_face), so the single cell's exit t equals the AABB slab's far t
+    uint32_t gap_ok;         // n == 1, triangles with a plane list, optimistic kernel: `gap` holds the set's PLANE-FREE GAP (pt_shadow_gap.hpp; the host
+                             // makes it from its copy of the plane list and these bounds).  A wave whose shadow segments all pass the gap test skips the
+                             // set's box test and the axis entries of the list (pt_direct.hpp direct_all).  0: no gap, every query runs the box test
+    float gap[12];           // {qlo[3], qhi[3], Gm[3], Hm[3]}: per axis the open interval between the neighbouring axis planes / box faces / exit planes
+                             // around the box centre, and the margin constants m_a = Gm_a |o|_1 + Hm_a.  Kernel arguments: scalar operands where they are used
 };
 struct LightArgs {           // the three float16 packings of one light (A10 code.js:323-352)
     float shadow[16];        // pos, T, B, radius

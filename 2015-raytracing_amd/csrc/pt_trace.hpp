@@ -28,7 +28,9 @@ enum PtCounter { PC_WAVES = 0, PC_SEGMENTS, PC_SEG_LANES, PC_Q_CLOSEST, PC_Q_CLO
                  // the shared-test grid walk (pt_trace_coop.hpp): walks a wave enters, lanes that want one, outer phases, wave-level empty-cell steps and the lanes
                  // taking them, pooled rounds, pairs; [closest, shadow] each
                  PC_GRID_WALKS, PC_GRID_WANT_LANES = PC_GRID_WALKS + 2, PC_GRID_PHASES = PC_GRID_WALKS + 4, PC_GRID_A_STEPS = PC_GRID_WALKS + 6,
-                 PC_GRID_A_LANE_STEPS = PC_GRID_WALKS + 8, PC_GRID_ROUNDS = PC_GRID_WALKS + 10, PC_GRID_PAIRS = PC_GRID_WALKS + 12, PC_COUNT = 48 };
+                 PC_GRID_A_LANE_STEPS = PC_GRID_WALKS + 8, PC_GRID_ROUNDS = PC_GRID_WALKS + 10, PC_GRID_PAIRS = PC_GRID_WALKS + 12,
+                 // the shadow stage's plane-free gap (pt_direct.hpp): queries that asked, queries whose wave took the early-out, live lanes that refused it
+                 PC_GAP_ASKED = PC_GRID_WALKS + 14, PC_GAP_TAKEN, PC_GAP_REFUSED_LANES, PC_COUNT = 48 };
 #if PT_COUNT
 static __device__ unsigned long long pt_counters[PC_COUNT];
 __device__ __forceinline__ void pt_count(int i, bool lanes = false, unsigned long long n = 1ull) {
@@ -438,7 +440,10 @@ PT_DEV float cell1_exit(const Ray& ray, const RayRcp& rr, const BoxHit& bh, cons
 // candidates -- sign bit clear -- in list order, fetching each record from LDS by ds_read_b128 (twelve-dword records: up to sixteen
 // distinct triangles are conflict-free).  In a closed room 5-7 of cornell.xml's 12 triangles survive the sweep.  Same predicates, same
 // arithmetic, same order within a lane (ties on t go to the lower index exactly as in the reference's loop).
-template <int KIND, bool ANY, int RULE = TRI_A10, bool FAST = false, bool FLAG_ONLY = false, bool LANES = false>
+// GAP (with LANES, ANY: the shadow stage, pt_direct.hpp direct_all): every active lane's segment [0, maxt] passed the set's gap test
+// (pt_shadow_gap.hpp) -- the box test was not run and `bh` is not read: cmin = 0 and cmax = maxt stand for what it would have given
+// (tmin = 0, exit >= maxt), and the sweep steps past the axis entries of every chunk, whose verdict is "drop" for such a segment.
+template <int KIND, bool ANY, int RULE = TRI_A10, bool FAST = false, bool FLAG_ONLY = false, bool LANES = false, bool GAP = false>
 PT_DEV Hit trace_cell1(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const GridArgs& S) {   // rr: ray_rcp<FAST>(ray), the caller's
     Hit ch;
     ch.idx = UINT32_MAX;
@@ -447,8 +452,8 @@ PT_DEV Hit trace_cell1(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const
     ch.gamma = 0.0f;
     SphereRay sr;
     if (KIND == SPHERES) sr = sphere_ray<FAST>(ray.d);
-    const float cmin = bh.tmin;
-    const float cmax = cell1_exit<FAST>(ray, rr, bh, S);
+    const float cmin = GAP ? 0.0f : bh.tmin;
+    const float cmax = GAP ? ray.maxt : cell1_exit<FAST>(ray, rr, bh, S);
     const uint32_t begin = __builtin_amdgcn_readfirstlane(ldc_u32(S.off, 0));
     const uint32_t end = __builtin_amdgcn_readfirstlane(ldc_u32(S.off, 1));
     bool done = false;
@@ -479,7 +484,7 @@ PT_DEV Hit trace_cell1(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const
         // min3(-div, -fma(hi+, div, sn - M), fma(lo-, div, sn + M)) -- two more fused operations on sums the front verdict already made.
         // In cornell.xml a closest query keeps 2-4 of the 5-7 front-facing triangles, a shadow query 0-2.
         const float o1 = __builtin_fabsf(ray.o.x) + __builtin_fabsf(ray.o.y) + __builtin_fabsf(ray.o.z);
-        const float hi_p = __builtin_fmaxf(__builtin_fminf(cmax, ray.maxt) * 1.00000095367431640625f, 0x1p-100f);
+        const float hi_p = __builtin_fmaxf((GAP ? ray.maxt : __builtin_fminf(cmax, ray.maxt)) * 1.00000095367431640625f, 0x1p-100f);
         const float lo_m = cmin * 0.99999904632568359375f;
         pt_count(ANY ? PC_Q_SHADOW : PC_Q_CLOSEST); pt_count(ANY ? PC_Q_SHADOW_LANES : PC_Q_CLOSEST_LANES, true);
         for (uint32_t c0 = 0u; c0 < end; c0 += 32u) {
@@ -509,9 +514,13 @@ PT_DEV Hit trace_cell1(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const
                     verdict(v[4 * k + 1] * (DA), v[4 * k + 1] * ((OA) - v[4 * k]), mask, back);                         \
                 }                                                                                                       \
             }
-            PT_AXIS_GROUPS(0, ray.o.x, ray.d.x)
-            PT_AXIS_GROUPS(8, ray.o.y, ray.d.y)
-            PT_AXIS_GROUPS(16, ray.o.z, ray.d.z)
+            if (GAP) {
+                g += (groups & 255u) + ((groups >> 8) & 255u) + ((groups >> 16) & 255u);   // no axis plane of the set is met inside the gap
+            } else {
+                PT_AXIS_GROUPS(0, ray.o.x, ray.d.x)
+                PT_AXIS_GROUPS(8, ray.o.y, ray.d.y)
+                PT_AXIS_GROUPS(16, ray.o.z, ray.d.z)
+            }
 #undef PT_AXIS_GROUPS
             for (uint32_t i = 0; i < groups >> 24; ++i, ++g) {
                 const pt_v16f v = *g;

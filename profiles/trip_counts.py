@@ -22,7 +22,7 @@ NAMES = ["waves", "segments", "seg_lanes", "q_closest", "q_closest_lanes", "swee
          "box_tests", "box_lanes", "shade", "shade_lanes", "bounce", "bounce_lanes",
          "grid_walks_closest", "grid_walks_shadow", "grid_want_lanes_closest", "grid_want_lanes_shadow", "grid_phases_closest", "grid_phases_shadow",
          "grid_a_steps_closest", "grid_a_steps_shadow", "grid_a_lane_steps_closest", "grid_a_lane_steps_shadow", "grid_rounds_closest", "grid_rounds_shadow",
-         "grid_pairs_closest", "grid_pairs_shadow"]
+         "grid_pairs_closest", "grid_pairs_shadow", "gap_asked", "gap_taken", "gap_refused_lanes"]
 
 
 def main():
