@@ -570,6 +570,60 @@ napi_value ViewRays(napi_env env, napi_callback_info info) {
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);
 }
+// viewGuides(ctx, desc, viewDesc, normalHits, albedoDepth): the first-hit guides of the tile (mirt_view_guides), float4 per tile pixel each, either
+// may be null.  renderViewGuided(ctx, desc, viewDesc, seeds, radiance, pixel, normalHits, albedoDepth): the frame and its guides in one call
+// (mirt_render_view_guided).  ctxGuidedViews(ctx) -> the calls whose frame launch wrote the guides itself (mirt_ctx_guided_views).
+enum ViewCall { VIEW_GUIDES, VIEW_FRAME_GUIDED };
+static napi_value view_call(napi_env env, napi_value* argv, ViewCall call) {
+    const char* const who = call == VIEW_GUIDES ? "viewGuides" : "renderViewGuided";
+    void *c, *seeds = nullptr, *radiance = nullptr, *pixel = nullptr, *nh = nullptr, *ad = nullptr;
+    if (!get_ext(env, argv[0], &c))
+        return throw_type(env, call == VIEW_GUIDES ? "viewGuides(ctx, desc, viewDesc, normalHits, albedoDepth)"
+                                                   : "renderViewGuided(ctx, desc, viewDesc, seeds, radiance, pixel, normalHits, albedoDepth)");
+    if (call == VIEW_GUIDES) {
+        get_ext(env, argv[3], &nh);
+        get_ext(env, argv[4], &ad);
+    } else {
+        get_ext(env, argv[3], &seeds);
+        get_ext(env, argv[4], &radiance);
+        get_ext(env, argv[5], &pixel);
+        get_ext(env, argv[6], &nh);
+        get_ext(env, argv[7], &ad);
+    }
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    p.bounces = 5;
+    prop_u32(env, argv[1], "bounces", &p.bounces);
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    std::vector<mirt_light> lights;
+    if (!read_sets(env, argv[1], who, p, sph, tri, meshes) || (call != VIEW_GUIDES && !read_lights(env, argv[1], who, p, lights))) return nullptr;
+    p.material = prop_buf(env, argv[1], "material");
+    mirt_view_desc v;
+    if (!read_view(env, argv[2], who, v)) return nullptr;
+    const int rc = call == VIEW_GUIDES ? mirt_view_guides((mirt_ctx*)c, &p, &v, (mirt_buf*)nh, (mirt_buf*)ad)
+                                       : mirt_render_view_guided((mirt_ctx*)c, &p, &v, (mirt_buf*)seeds, (mirt_buf*)radiance, (mirt_buf*)pixel, (mirt_buf*)nh, (mirt_buf*)ad);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value ViewGuides(napi_env env, napi_callback_info info) {
+    ARGS(5);
+    return view_call(env, argv, VIEW_GUIDES);
+}
+napi_value RenderViewGuided(napi_env env, napi_callback_info info) {
+    ARGS(8);
+    return view_call(env, argv, VIEW_FRAME_GUIDED);
+}
+napi_value CtxGuidedViews(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "ctxGuidedViews(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_ctx_guided_views((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
+}
 napi_value RenderView(napi_env env, napi_callback_info info) {
     ARGS(6);
     void *c, *seeds = nullptr, *radiance = nullptr, *pixel = nullptr;
@@ -1037,7 +1091,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"viewGuides", ViewGuides}, {"renderViewGuided", RenderViewGuided}, {"ctxGuidedViews", CtxGuidedViews}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"renderAo", RenderAo}, {"aoDeferred", AoDeferred}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

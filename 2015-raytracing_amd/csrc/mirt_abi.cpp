@@ -106,6 +106,7 @@ struct mirt_ctx {
     std::vector<Enqueue> pending;
     uint64_t fused_passes = 0;    // passes executed as ONE fused launch because their enqueue stream matched executeRender's
     uint64_t guided_passes = 0;   // mirt_render_first_pass_guided / mirt_render_passes_guided calls whose launch wrote the guides itself (the one-launch route)
+    uint64_t guided_views = 0;    // the same for mirt_render_view_guided
     // the same for the frame dialects (mirt_ctx_set_frame_fusion): an A04 / A07 initTrace and the enqueues behind it are held in `pending` too
     bool frame_fusion = false;
     uint64_t fused_frames = 0;
@@ -1900,6 +1901,7 @@ static int view_verdict(mirt_ctx* ctx, const char* fn, pt::ViewVerdict v, const 
         case pt::VIEW_NO_SEEDS: return fail(ctx, code, "%s: seeds is NULL", fn);
         case pt::VIEW_NO_OUTPUT: return fail(ctx, code, "%s: radiance and pixel are both NULL (either may be, not both)", fn);
         case pt::VIEW_ACCUMULATE_NEEDS_RADIANCE: return fail(ctx, code, "%s: MIRT_VIEW_ACCUMULATE without a radiance buffer to go on from", fn);
+        case pt::VIEW_NO_GUIDE: return fail(ctx, code, "%s: normal_hits and albedo_depth are both NULL (either may be, not both)", fn);
     }
     return fail(ctx, MIRT_E_ARG, "%s: view descriptor refused", fn);
 }
@@ -1932,8 +1934,27 @@ int mirt_view_rays(mirt_ctx* ctx, const mirt_view_desc* vd, mirt_buf* rays) try 
     return MIRT_OK;
 } MIRT_CATCH("mirt_view_rays", return MIRT_E_DEVICE)
 
-int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel) try {
-    const char* const fn = "mirt_render_view";
+// The guide launches of an already validated tile of a view camera: the optimistic / exact pair of one lane per pixel, or the exact kernel alone
+// (the mask is mirt_render_guides's allocation: both are a bit per pixel, cleared by the call that uses them).
+static int queue_view_guides(mirt_ctx* ctx, const pt::FusedArgs& A, const pt::ViewArgs& V, const pt::ViewPlan& plan, void* nh, void* ad) {
+    const pt::ViewGuidesPlan g = pt::view_guides_plan(plan);
+    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
+        const int rc = grow_and_clear(ctx, ctx->guide_mask, ctx->guide_mask_bytes, (size_t)g.mask_words * 4u);
+        if (rc) return rc;
+        pt::launch_viewGuides(ctx->stream, A, V, g.blocks, true, nh, ad, (uint32_t*)ctx->guide_mask, nullptr);
+        pt::launch_viewGuides(ctx->stream, A, V, g.blocks, false, nh, ad, nullptr, (const uint32_t*)ctx->guide_mask);
+    } else {
+        pt::launch_viewGuides(ctx->stream, A, V, g.blocks, false, nh, ad, nullptr, nullptr);
+    }
+    return MIRT_OK;
+}
+// MIRT_GUIDED_VIEW=0: mirt_render_view_guided always queues the frame and then the guide launches -- an A/B and test switch, read per call
+static bool guided_view_enabled() { const char* e = getenv("MIRT_GUIDED_VIEW"); return !(e && e[0] == '0'); }
+
+// mirt_render_view (guided false: seeds, radiance, pixel), mirt_view_guides (frame false: normal_hits, albedo_depth) and mirt_render_view_guided
+// (all five): one list of checks, every one before anything is queued, then the launches.
+static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guided, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance,
+                            mirt_buf* pixel, mirt_buf* normal_hits, mirt_buf* albedo_depth) {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
     FLUSH_PENDING(ctx);
     NOT_WHILE_CAPTURING(ctx, fn);
@@ -1942,53 +1963,97 @@ int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_des
     pt::ViewDesc v;
     memcpy(&v, vd, sizeof v);
     int rc;
-    if ((rc = view_verdict(ctx, fn, pt::view_check_render(v, seeds != nullptr, radiance != nullptr, pixel != nullptr), v))) return rc;
+    const bool nh = normal_hits != nullptr, ad = albedo_depth != nullptr;
+    const pt::ViewVerdict verdict = !frame   ? pt::view_check_guides(v, nh, ad)
+                                    : guided ? pt::view_check_render_guided(v, seeds != nullptr, radiance != nullptr, pixel != nullptr, nh, ad)
+                                             : pt::view_check_render(v, seeds != nullptr, radiance != nullptr, pixel != nullptr);
+    if ((rc = view_verdict(ctx, fn, verdict, v))) return rc;
     const pt::ViewPlan plan = pt::view_plan(v);
-    // the pass's own limits and rules for its arrays, as mirt_trace_radiance has them
-    if (d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
+    // the pass's own limits and rules for its arrays, as mirt_trace_radiance has them (the guides alone read no light)
+    if (frame && d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
     if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
-    if ((d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
-    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[3] = {{"seeds", seeds, plan.rays * 4}, {"radiance", radiance, plan.pixels * 16}, {"pixel", pixel, plan.pixels * 4}};
+    if ((frame && d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
+    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[5] = {{"seeds", seeds, plan.rays * 4}, {"radiance", radiance, plan.pixels * 16}, {"pixel", pixel, plan.pixels * 4},
+                                                                                 {"normal_hits", normal_hits, plan.pixels * 16}, {"albedo_depth", albedo_depth, plan.pixels * 16}};
     for (const auto& b : io)
         if (b.buf && (rc = need(ctx, (std::string(fn) + " " + b.label).c_str(), b.buf, b.bytes))) return rc;
     if ((rc = need(ctx, "material", d->material, 16))) return rc;
-    {   // all three are written: the bytes the call touches of them, against each other's, the geometry's buffers and the material whole
+    {   // everything given is written: the bytes the call touches of them, against each other's, the geometry's buffers and the material whole
         std::vector<pt::PostRange> in;
         add_range(in, d->material);
         add_geometry_ranges(in, d);
-        pt::PostRange out[3];
-        for (int i = 0; i < 3; ++i) out[i] = {io[i].buf ? (uint64_t)(uintptr_t)io[i].buf->ptr : 0u, io[i].bytes, io[i].buf != nullptr};
-        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 3);
-        if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: the seeds', the radiance's or the pixel's bytes meet a geometry buffer's or the material's", fn);
-        if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: seeds, radiance and pixel meet one another", fn);
+        pt::PostRange out[5];
+        for (int i = 0; i < 5; ++i) out[i] = {io[i].buf ? (uint64_t)(uintptr_t)io[i].buf->ptr : 0u, io[i].bytes, io[i].buf != nullptr};
+        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 5);
+        // (mirt_render_view's two messages are the ones it had before the guides: that call has none)
+        if (alias == pt::POST_ALIAS_OUTPUT_INPUT)
+            return fail(ctx, MIRT_E_ARG, !frame   ? "%s: a guide's bytes meet a geometry buffer's or the material's"
+                                         : guided ? "%s: the seeds', the radiance's, the pixel's or a guide's bytes meet a geometry buffer's or the material's"
+                                                  : "%s: the seeds', the radiance's or the pixel's bytes meet a geometry buffer's or the material's", fn);
+        if (alias == pt::POST_ALIAS_OUTPUTS)
+            return fail(ctx, MIRT_E_ARG, !frame   ? "%s: normal_hits aliases albedo_depth"
+                                         : guided ? "%s: seeds, radiance, pixel and the guides meet one another"
+                                                  : "%s: seeds, radiance and pixel meet one another", fn);
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::FusedArgs A;
     memset(&A, 0, sizeof A);
     A.bounces = d->bounces;
-    A.n_lights = d->n_lights;
+    A.n_lights = frame ? d->n_lights : 0u;
     if ((rc = fill_sets(ctx, fn, d, A))) return rc;
     if ((rc = fill_shading(ctx, d, A, true))) return rc;
     const pt::ViewArgs V = view_args(v, plan);
-    const bool accumulate = (v.flags & MIRT_VIEW_ACCUMULATE) != 0u;
-    void* const rp = radiance ? radiance->ptr : nullptr;
-    void* const pp = pixel ? pixel->ptr : nullptr;
-    ctx->view_defer_words = 0;
-    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
-        if ((rc = grow_and_clear(ctx, ctx->view_defer, ctx->view_defer_bytes, 16u + (size_t)plan.mask_words * 4u))) return rc;
-        uint32_t* const mask = (uint32_t*)ctx->view_defer + 4;
-        pt::launch_viewPass(ctx->stream, A, V, true, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask, nullptr);
-        pt::launch_viewPass(ctx->stream, A, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, mask);
-        ctx->view_defer_words = plan.mask_words;
-    } else {
-        pt::launch_viewPass(ctx->stream, A, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, nullptr);
-    }
+    void* const nhp = normal_hits ? normal_hits->ptr : nullptr;
+    void* const adp = albedo_depth ? albedo_depth->ptr : nullptr;
+    if (frame) {
+        const bool accumulate = (v.flags & MIRT_VIEW_ACCUMULATE) != 0u;
+        void* const rp = radiance ? radiance->ptr : nullptr;
+        void* const pp = pixel ? pixel->ptr : nullptr;
+        const bool in_pass = guided && pt::view_guides_in_pass(plan.rpp, pt::fused_has_grids(A), guided_view_enabled());
+        pt::FusedArgs F = A;
+        if (in_pass) { F.guide_nh = nhp; F.guide_ad = adp; }
+        ctx->view_defer_words = 0;
+        if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
+            if ((rc = grow_and_clear(ctx, ctx->view_defer, ctx->view_defer_bytes, 16u + (size_t)plan.mask_words * 4u))) return rc;
+            uint32_t* const mask = (uint32_t*)ctx->view_defer + 4;
+            pt::launch_viewPass(ctx->stream, F, V, true, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask, nullptr);
+            pt::launch_viewPass(ctx->stream, F, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, mask);
+            ctx->view_defer_words = plan.mask_words;
+        } else {
+            pt::launch_viewPass(ctx->stream, F, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, nullptr);
+        }
+        if (in_pass) ctx->guided_views++;
+        else if (guided && (rc = queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;   // everywhere else: exactly what mirt_view_guides queues
+    } else if ((rc = queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;
     HIPCHK(ctx, hipGetLastError());
-    seeds->version++;
-    if (radiance) radiance->version++;
-    if (pixel) pixel->version++;
+    for (const auto& b : io)
+        if (b.buf) b.buf->version++;
     return MIRT_OK;
+}
+
+int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel) try {
+    return render_view_impl(ctx, "mirt_render_view", true, false, d, vd, seeds, radiance, pixel, nullptr, nullptr);
 } MIRT_CATCH("mirt_render_view", return MIRT_E_DEVICE)
+
+// First-hit guides of a view camera's tile (pt_kernels_rays.hip k_viewGuides): one launch -- or the optimistic / exact pair, per pixel -- of one
+// lane per pixel.  Nothing but the two outputs is written.
+int mirt_view_guides(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
+    return render_view_impl(ctx, "mirt_view_guides", false, true, d, vd, nullptr, nullptr, nullptr, normal_hits, albedo_depth);
+} MIRT_CATCH("mirt_view_guides", return MIRT_E_DEVICE)
+
+// The frame and its guides in one call: where a pixel's samples are consecutive lanes of one wave (pt_view_plan.hpp view_guides_in_pass) the
+// frame's own launches write the guides (k_viewPass GUIDES), elsewhere the guide launches follow.
+int mirt_render_view_guided(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel, mirt_buf* normal_hits,
+                            mirt_buf* albedo_depth) try {
+    return render_view_impl(ctx, "mirt_render_view_guided", true, true, d, vd, seeds, radiance, pixel, normal_hits, albedo_depth);
+} MIRT_CATCH("mirt_render_view_guided", return MIRT_E_DEVICE)
+
+int mirt_ctx_guided_views(mirt_ctx* ctx, uint64_t* count) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_guided_views: unknown context");
+    if (!count) return fail(ctx, MIRT_E_ARG, "mirt_ctx_guided_views: null output");
+    *count = ctx->guided_views;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_ctx_guided_views", return MIRT_E_DEVICE)
 
 int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_view_deferred: unknown context");

@@ -29,9 +29,10 @@
 //
 // Also here, because it runs rays_any: k_ao, ambient occlusion of the first hit (mirt_render_ao); and because it starts at a caller's ray:
 // k_traceRadiance, the pass's path from that ray on (mirt_trace_radiance); and because they are k_traceRadiance with the ray made in registers:
-// k_viewRays and k_viewPass, the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view) -- at the end of the file.
+// k_viewRays and k_viewPass, the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view), and k_viewGuides, their
+// first-hit guides (mirt_view_guides) -- at the end of the file.
 #include "pt_direct.hpp"
-#include "pt_resolve.hpp"   // resolve_rows: k_viewPass resolves its blocks' pixels as the pass does
+#include "pt_resolve.hpp"   // resolve_rows: k_viewPass resolves its blocks' pixels as the pass does; guides_emit: its GUIDES instances write the guides
 #include "pt_view.hpp"      // view_ray: a sample's ray
 
 namespace pt {
@@ -452,7 +453,12 @@ void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays) {
 #define PT_VIEW_CELL_WAVES PT_RADIANCE_CELL_WAVES
 #endif
 #define PT_VIEW_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_VIEW_GRID_WAVES : PT_VIEW_CELL_WAVES)
-template <bool FAST, int GRIDS>
+// GUIDES (mirt_render_view_guided, the one-launch route: pt_view_plan.hpp view_guides_in_pass): the frame writes the first-hit guides of its
+// pixels too, A.guide_nh / A.guide_ad, by the pass's own lane walk (pt_resolve.hpp guides_emit) right after segment 0's closest_all -- the state
+// k_viewGuides takes them at, reached by the same functions on the same ray ids.  rpp is 1, 4, 16 or 64: a pixel's samples are consecutive lanes
+// of one wave.  As in the pass, the optimistic kernel writes a block's guides before its verdict; a block that defers is re-run whole by the
+// exact kernel, which writes the same pixels' guides again, later on the same stream.  The default, false, keeps the unguided instances' code.
+template <bool FAST, int GRIDS, bool GUIDES = false>
 __global__ void PT_VIEW_BOUNDS(GRIDS) k_viewPass(const FusedArgs A, const ViewArgs V, uint32_t count, int32_t* __restrict__ seeds, float4* radiance,
                                                    uchar4* __restrict__ pixel, float tone, uint32_t* defer_mask, const uint32_t* redo_mask) {
     const uint32_t blk = blockIdx.x;
@@ -497,6 +503,7 @@ __global__ void PT_VIEW_BOUNDS(GRIDS) k_viewPass(const FusedArgs A, const ViewAr
             }
         }
         closest_all<FAST, GRIDS>(A, ray, poi, park, defer);
+        if constexpr (GUIDES) if (seg == 0) guides_emit(A, ray, poi, valid, blk);   // every lane of the block is here: none leaves before the barrier
         if (seg == 0) {
             for (uint32_t l = 0; l < A.n_lights; ++l) {  // lightRender (code.cl:600-629), on the camera's ray only
                 if (ray.mint == ray.maxt) continue;
@@ -533,11 +540,12 @@ static void launch_viewPass_t(hipStream_t s, const FusedArgs& b, const FusedLds&
                               float tone, uint32_t* defer_mask, const uint32_t* redo_mask) {
     const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
     fused_lds_dispatch(L, [&](auto G, size_t lds) {
-        hipLaunchKernelGGL((k_viewPass<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, count, seeds, radiance, pixel, tone, defer_mask, redo_mask);
+        if (b.guide_nh || b.guide_ad) hipLaunchKernelGGL((k_viewPass<FAST, decltype(G)::value, true>), grid, dim3(256), lds, s, b, v, count, seeds, radiance, pixel, tone, defer_mask, redo_mask);
+        else hipLaunchKernelGGL((k_viewPass<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, count, seeds, radiance, pixel, tone, defer_mask, redo_mask);
     });
 }
 // fast: the optimistic kernel (sets the bits of the blocks it hands over in defer_mask); !fast: the exact kernel over the blocks of redo_mask, or
-// over every block when it is null.
+// over every block when it is null.  a.guide_nh / a.guide_ad (either given): the GUIDES instances, which the caller asks for at rpp 1, 4, 16 or 64 only.
 void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
                      uint32_t* defer_mask, const uint32_t* redo_mask) {
     const uint64_t count = (uint64_t)v.nrows * v.width * v.k * v.k;
@@ -550,6 +558,75 @@ void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool 
     const FusedLds L = fused_lds_slots(b, fast);
     if (fast) launch_viewPass_t<true>(s, b, L, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, defer_mask, nullptr);
     else launch_viewPass_t<false>(s, b, L, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, nullptr, redo_mask);
+}
+
+// ---- first-hit guides of a view camera's tile (mirt_view_guides): k_guides (pt_kernels_guides.hip) with the ray of a sample made by view_ray
+// instead of primary_ray.  The definition is include/mirt.h's: pixel p has the rays p * rpp + i in sample order, exactly as k_viewRays writes
+// them; each runs through closest_all as k_traceRays runs a caller's ray (this file's guard, the division kept in the loop: a view ray's d is the
+// caller's basis as given, not of unit length); a sample is a hit iff 0 <= Poi.matId < A.nmat.
+// Structure: k_guides' -- one lane per pixel walking its samples in order, the eight sums in registers, no barrier behind the prologue.  V is a
+// kernel argument: the model's branch is WAVE-UNIFORM, and a DEAD fisheye sample (r > 1) rides through the shared walk as a dead ray and is never
+// a hit.  In the grid variants a lane past the end of the tile rides along on the last pixel (clamped) and a wave without a pixel leaves at the
+// ballot.  The optimistic / exact pair is per PIXEL, a bit per pixel: a pixel one of whose samples the ray-side guard refuses (it goes on dead,
+// guard_or_retire) or whose walk defers sets its bit and writes nothing; the exact kernel redoes the marked pixels whole.
+struct ViewGuideHooks : ClosestHooks {
+    PT_DEV void guard(Ray& ray, bool& defer) const { guard_or_retire(ray, defer); }
+    PT_DEV void top(Ray& ray) const { keep_in_loop(ray); }
+};
+template <bool FAST, int GRIDS>
+__global__ void __launch_bounds__(256) k_viewGuides(const FusedArgs A, const ViewArgs V, float4* normal_hits, float4* albedo_depth, uint32_t* defer_mask,
+                                                    const uint32_t* redo_mask) {
+    stage_block<FAST, GRIDS>(A);
+    const uint32_t npix = V.nrows * V.width;   // (a tile holds at most 2^32 - 256 rays: pt_view_plan.hpp)
+    uint32_t pix = blockIdx.x * 256u + threadIdx.x;
+    bool valid = pix < npix;
+    if (!FAST && redo_mask && valid) valid = (redo_mask[pix >> 5] >> (pix & 31u) & 1u) != 0u;
+    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
+    else if (!valid) return;
+    if (pix >= npix) pix = npix - 1u;
+    const float4* material = (const float4*)A.material;
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, depth = 0.0f;
+    bool defer = false;
+    const uint32_t rpp = V.k * V.k, first = pix * rpp;
+    for (uint32_t i = 0; i < rpp; ++i) {
+        Ray ray = view_ray(V, first + i);
+        Poi poi;   // as initTrace resets it (code.cl:538-541)
+        poi.p = mk3(0.0f, 0.0f, 0.0f);
+        poi.n = mk3(0.0f, 0.0f, 0.0f);
+        poi.atte = mk3(1.0f, 1.0f, 1.0f);
+        poi.matId = -1;
+        closest_all<FAST, GRIDS>(A, ray, poi, ViewGuideHooks{}, defer);
+        if (poi.matId < 0 || (uint32_t)poi.matId >= A.nmat) continue;
+        const float4 c = material[poi.matId];
+        nx += poi.n.x; ny += poi.n.y; nz += poi.n.z; hits += 1.0f;
+        ar += c.x; ag += c.y; ab += c.z; depth += ray.maxt;
+    }
+    if (!valid) return;
+    if (FAST && defer) {   // the exact kernel redoes the pixel: nothing of it is written
+        atomicOr(&defer_mask[pix >> 5], 1u << (pix & 31u));
+        return;
+    }
+    if (normal_hits) normal_hits[pix] = make_float4(nx, ny, nz, hits);
+    if (albedo_depth) albedo_depth[pix] = make_float4(ar, ag, ab, depth);
+}
+
+template <bool FAST>
+static void launch_viewGuides_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const ViewArgs& v, uint32_t blocks, float4* nh, float4* ad, uint32_t* defer_mask,
+                                const uint32_t* redo_mask) {
+    const dim3 grid(blocks);
+    fused_lds_dispatch(L, [&](auto G, size_t lds) { hipLaunchKernelGGL((k_viewGuides<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, nh, ad, defer_mask, redo_mask); });
+}
+// fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
+// of redo_mask, or over every pixel when it is null.  Either output may be null.  blocks: ceil(pixels / 256), the plan's (pt_view_plan.hpp).
+void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask,
+                       const uint32_t* redo_mask) {
+    if (!blocks) return;
+    FusedArgs b = a;
+    b.width = v.width; b.nrows = v.nrows;
+    b.rpp = v.k * v.k;   // stage_block, as launch_viewPass sets it (the lens table of it is k words nobody reads)
+    const FusedLds L = fused_lds_slots(b, fast);
+    if (fast) launch_viewGuides_t<true>(s, b, L, v, blocks, (float4*)normal_hits, (float4*)albedo_depth, defer_mask, nullptr);
+    else launch_viewGuides_t<false>(s, b, L, v, blocks, (float4*)normal_hits, (float4*)albedo_depth, nullptr, redo_mask);
 }
 
 }  // namespace pt

@@ -180,9 +180,15 @@ void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays);
 // mirt_render_view: those rays through k_traceRadiance's path at one sample each and the block's resolve, in one launch.  seeds: int32 per tile
 // ray, read and written; radiance (float4) / pixel (uchar4) per tile pixel, either may be null; accumulate: the sums go on from `radiance`.  The
 // optimistic / exact pair per BLOCK of 256 ray ids: the mask is one bit per block, (blocks + 31) / 32 words.  Reads the sets, lights, material,
-// nmat and bounces of `a` and nothing else of it.
+// nmat and bounces of `a` and nothing else of it -- but a.guide_nh / a.guide_ad: either given, the frame writes the first-hit guides of its
+// pixels too (k_viewPass GUIDES; mirt_render_view_guided's one-launch route, which the caller takes at k * k = 1, 4, 16 or 64 only).
 void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
                      uint32_t* defer_mask, const uint32_t* redo_mask);
+// mirt_view_guides: the first-hit guides of those rays (k_viewGuides), float4 per tile pixel each as launch_guides writes them; either may be
+// null.  One lane per pixel, `blocks` blocks of 256; the optimistic / exact pair per PIXEL, the mask one bit per pixel: both are the plan's
+// (pt_view_plan.hpp view_guides_plan).  Reads the sets, material and nmat of `a` and nothing else of it.
+void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask,
+                       const uint32_t* redo_mask);
 // Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
 // every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
 struct FilterArgs {

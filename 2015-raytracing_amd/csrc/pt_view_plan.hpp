@@ -1,7 +1,9 @@
-// pt_view_plan.hpp -- the host side of the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view; include/mirt.h): the
-// descriptor checks that need no device, and the launch plan -- the tile's rays, its blocks of 256 consecutive ray ids, the whole pixels a block
-// holds and those of the ragged last block.  Plain integers and floats: no HIP header and no device, so a plain C++ compiler builds it and
-// tests/test_view_plan.py checks it on the CPU (tests/view_plan_dump.cpp).  mirt_abi.cpp is the caller and owns the messages.
+// pt_view_plan.hpp -- the host side of the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view, mirt_view_guides,
+// mirt_render_view_guided; include/mirt.h): the descriptor checks that need no device, the launch plan -- the tile's rays, its blocks of 256
+// consecutive ray ids, the whole pixels a block holds and those of the ragged last block -- and the route rule of the guided frame.  Plain
+// integers and floats: no HIP header and no device, so a plain C++ compiler builds it and tests/test_view_plan.py and
+// tests/test_view_guides_plan.py check it on the CPU (tests/view_plan_dump.cpp, tests/view_guides_plan_dump.cpp).  mirt_abi.cpp is the caller
+// and owns the messages.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -45,7 +47,8 @@ enum ViewVerdict {
     VIEW_TONE,            // a pixel buffer is given and tone is not finite or <= 0
     VIEW_NO_SEEDS,        // mirt_render_view without seeds
     VIEW_NO_OUTPUT,       // mirt_render_view with neither radiance nor pixel
-    VIEW_ACCUMULATE_NEEDS_RADIANCE
+    VIEW_ACCUMULATE_NEEDS_RADIANCE,
+    VIEW_NO_GUIDE         // mirt_view_guides, mirt_render_view_guided with neither normal_hits nor albedo_depth
 };
 // the status every refusal above is reported with: 0, or MIRT_E_ARG
 inline int view_status(ViewVerdict v) { return v == VIEW_OK ? 0 : kViewStatusArg; }
@@ -82,6 +85,18 @@ inline ViewVerdict view_check_render(const ViewDesc& v, bool seeds, bool radianc
     if ((v.flags & kViewAccumulate) && !radiance) return VIEW_ACCUMULATE_NEEDS_RADIANCE;
     return VIEW_OK;
 }
+// what mirt_view_guides asks: the descriptor as mirt_view_rays reads it (tone and the meaning of flags are not looked at), and an output
+inline ViewVerdict view_check_guides(const ViewDesc& v, bool normal_hits, bool albedo_depth) {
+    const ViewVerdict d = view_check_desc(v);
+    if (d != VIEW_OK) return d;
+    return normal_hits || albedo_depth ? VIEW_OK : VIEW_NO_GUIDE;
+}
+// ... and mirt_render_view_guided: both calls' rules, the frame's first
+inline ViewVerdict view_check_render_guided(const ViewDesc& v, bool seeds, bool radiance, bool pixel, bool normal_hits, bool albedo_depth) {
+    const ViewVerdict d = view_check_render(v, seeds, radiance, pixel);
+    if (d != VIEW_OK) return d;
+    return normal_hits || albedo_depth ? VIEW_OK : VIEW_NO_GUIDE;
+}
 
 // The launch plan of a descriptor that passed view_check_desc.  A block is 256 consecutive tile-local ray ids; rpp = k * k is 1, 4, 16, 64 or 256
 // and divides 256, so a block holds pixels_per_block WHOLE pixels -- the unit the in-block resolve and the optimistic / exact pair work in.
@@ -106,6 +121,30 @@ inline ViewPlan view_plan(const ViewDesc& v) {
     p.last_block_pixels = rest ? rest : p.pixels_per_block;
     p.mask_words = (p.blocks + 31u) / 32u;
     return p;
+}
+
+// mirt_view_guides runs one lane per PIXEL (k_viewGuides): its grid, which launch_viewGuides is handed, and the optimistic kernel's mask of a
+// bit per pixel of the tile, which mirt_abi.cpp allocates
+struct ViewGuidesPlan {
+    uint32_t blocks;       // ceil(pixels / 256)
+    uint32_t mask_words;   // ceil(pixels / 32)
+};
+inline ViewGuidesPlan view_guides_plan(const ViewPlan& p) {
+    ViewGuidesPlan g;
+    g.blocks = (uint32_t)((p.pixels + 255u) / 256u);
+    g.mask_words = (uint32_t)((p.pixels + 31u) / 32u);
+    return g;
+}
+
+// Whether mirt_render_view_guided writes the guides from the frame's own launch (k_viewPass GUIDES) instead of queueing k_viewGuides behind it:
+// a pixel's samples must be consecutive lanes of ONE wave, which the kernel sums by lane shuffles -- rpp 1, 4, 16 or 64.  Not at 256 rays (a
+// pixel spans four waves), and nowhere with MIRT_GUIDED_VIEW=0 (env_on false).  has_grids (a set of more than one cell: the grid kernels run)
+// does not bear on it: measured at 1920 x 1080 x 4, the guided grid kernels beat the two launches by 0.34 to 0.41 ms in 5.7 to 6.4
+// (cornell_teapot3) as the single-cell ones do by 0.07 ms in 0.98 to 1.18 (cornell), far beyond the spread of the two runs
+// (profiles/view_guided/timing.json).  A family that stops doing so goes to the two launches HERE.
+inline bool view_guides_in_pass(uint32_t rpp, bool has_grids, bool env_on) {
+    (void)has_grids;
+    return env_on && (rpp == 1u || rpp == 4u || rpp == 16u || rpp == 64u);
 }
 
 }  // namespace pt

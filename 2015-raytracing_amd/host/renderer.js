@@ -774,6 +774,10 @@ function makeView(packed, width, height, rpp, v) {
 }
 // -> {pixel: Uint8ClampedArray, radiance: Float32Array (the sums after the last pass), ms, device, deferred}: `passes` progressive frames,
 // MIRT_VIEW_ACCUMULATE from the second on, tone 1 / (rpp * p).  opt.view: makeView's v; opt.bounces; opt.seeds (Int32Array) or seedFill(0, n, 0).
+// opt.guides: + guides {normalHits, albedoDepth} (Float32Array, float4 per pixel) and guidedViews -- pass 1 goes through queue.renderViewGuided
+// (the guides are the same for every pass), the later ones are plain.  opt.denoise ({iterations, ...}: filterFrame's parameters, webcl.FILTER_DEFAULTS
+// where left out; implies the guides on the device): + denoised {pixel, filtered}, the a-trous filter run once behind the last pass with tone
+// 1 / (rpp * passes); nothing leaves the device between the passes and the filter.
 function renderViewFile(file, width, height, rpp, passes, opt) {
   opt = opt || {};
   const packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, 4);
@@ -784,6 +788,10 @@ function renderViewFile(file, width, height, rpp, passes, opt) {
   const npix = width * height, n = npix * rpp;
   const mk = (bytes) => ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(bytes, 16));
   const sb = mk(n * 4), rb = mk(npix * 16), pb = mk(npix * 4);
+  const guided = !!(opt.guides || opt.denoise);
+  if (guided && !q.hasViewGuides()) throw new Error("the loaded addon has no renderViewGuided");
+  const nhb = guided ? mk(npix * 16) : null, adb = guided ? mk(npix * 16) : null;
+  const fb = opt.denoise ? mk(npix * 16) : null, fpb = opt.denoise ? mk(npix * 4) : null;
   if (opt.seeds) q.enqueueWriteBuffer(sb, false, 0, n * 4, opt.seeds.subarray(0, n), []);
   else q.seedFill(sb, 0, n, 0);
   const desc = { spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, lights: packed.lights, material: dev.material, bounces: opt.bounces === undefined ? 5 : opt.bounces };
@@ -791,14 +799,28 @@ function renderViewFile(file, width, height, rpp, passes, opt) {
   const t0 = process.hrtime.bigint();
   let deferred = 0;
   for (let p = 1; p <= passes; p++) {
-    q.renderView(desc, Object.assign({}, view, { flags: p > 1 ? 1 : 0, tone: 1 / (rpp * p) }), sb, rb, pb);
+    const vp = Object.assign({}, view, { flags: p > 1 ? 1 : 0, tone: 1 / (rpp * p) });
+    if (guided && p === 1) q.renderViewGuided(desc, vp, sb, rb, pb, nhb, adb);
+    else q.renderView(desc, vp, sb, rb, pb);
     if (opt.countDeferred) deferred += q.viewDeferred();
   }
+  if (opt.denoise) q.filterFrame(Object.assign({}, opt.denoise, { width: width, height: height, tone: 1 / (rpp * passes), radiance: rb, normalHits: nhb, albedoDepth: adb, filtered: fb, pixel: fpb }));
   q.finish();
   const ms = Number(process.hrtime.bigint() - t0) / 1e6;
   const res = { pixel: new Uint8ClampedArray(npix * 4), radiance: new Float32Array(npix * 4), ms: ms, device: pickDevice(opt.device).getInfo(webcl.DEVICE_NAME), deferred: deferred };
   q.enqueueReadBuffer(pb, true, 0, npix * 4, res.pixel, []);
   q.enqueueReadBuffer(rb, true, 0, npix * 16, res.radiance, []);
+  if (guided) res.guidedViews = q.guidedViews();
+  if (opt.guides) {
+    res.guides = { normalHits: new Float32Array(npix * 4), albedoDepth: new Float32Array(npix * 4) };
+    q.enqueueReadBuffer(nhb, true, 0, npix * 16, res.guides.normalHits, []);
+    q.enqueueReadBuffer(adb, true, 0, npix * 16, res.guides.albedoDepth, []);
+  }
+  if (opt.denoise) {
+    res.denoised = { pixel: new Uint8ClampedArray(npix * 4), filtered: new Float32Array(npix * 4) };
+    q.enqueueReadBuffer(fpb, true, 0, npix * 4, res.denoised.pixel, []);
+    q.enqueueReadBuffer(fb, true, 0, npix * 16, res.denoised.filtered, []);
+  }
   ctx.release();
   return res;
 }
@@ -816,5 +838,23 @@ function viewRaysFile(file, width, height, rpp, opt) {
   ctx.release();
   return rays;
 }
+// -> {normalHits, albedoDepth}: Float32Array of 4 per pixel each, the view's first-hit guides alone (queue.viewGuides: mirt_view_guides), no
+// frame.  opt.view: makeView's v; opt.normalHits === false or opt.albedoDepth === false leaves that output out of the call (null in the result)
+function viewGuidesFile(file, width, height, rpp, opt) {
+  opt = opt || {};
+  const packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, 4);
+  const view = makeView(packed, width, height, rpp, opt.view);
+  const ctx = webcl.createContext(pickDevice(opt.device)), q = ctx.createCommandQueue();
+  if (!q.hasViewGuides()) throw new Error("the loaded addon has no viewGuides");
+  const dev = uploadScene(ctx, q, packed);
+  const npix = width * height;
+  const mk = (wanted) => (wanted === false ? null : ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(npix * 16, 16)));
+  const nhb = mk(opt.normalHits), adb = mk(opt.albedoDepth);
+  q.viewGuides({ spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, material: dev.material }, view, nhb, adb);
+  const read = (b) => { if (!b) return null; const a = new Float32Array(npix * 4); q.enqueueReadBuffer(b, true, 0, npix * 16, a, []); return a; };
+  const res = { normalHits: read(nhb), albedoDepth: read(adb) };
+  ctx.release();
+  return res;
+}
 
-module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderViewFile, viewRaysFile, makeView, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };
+module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderViewFile, viewRaysFile, viewGuidesFile, makeView, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };

@@ -251,6 +251,23 @@ class WebCLCommandQueue {
     wrap(() => native().renderView(this.ctx.h, d, this._viewDesc(view), seeds ? seeds.h : null, radiance ? radiance.h : null, pixel ? pixel.h : null));
   }
   viewDeferred() { return wrap(() => native().viewDeferred(this.ctx.h)); }
+  // ---- extension: the first-hit guides of those cameras (mirt_view_guides, mirt_render_view_guided).  viewGuides(desc, view, normalHits,
+  // albedoDepth): float4 per tile pixel each, as renderGuides writes them for the thin lens -- what filterAtrous reads; either may be null; of desc
+  // the sets and material are read; depth is in units of |forward| and the basis as given.  renderViewGuided(desc, view, seeds, radiance, pixel,
+  // normalHits, albedoDepth): every buffer ends as after renderView then viewGuides; at k = 1, 2, 4 and 8 the frame's own launch writes the guides
+  // (guidedViews() counts those calls), elsewhere the guide launches follow it.  hasViewGuides(): the loaded library has the entry points
+  hasViewGuides() { return typeof native().renderViewGuided === "function" && typeof native().viewGuides === "function"; }
+  viewGuides(desc, view, normalHits, albedoDepth) {
+    const d = Object.assign(this._setsDesc(desc), { material: desc.material ? desc.material.h : undefined });
+    wrap(() => native().viewGuides(this.ctx.h, d, this._viewDesc(view), normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
+  }
+  renderViewGuided(desc, view, seeds, radiance, pixel, normalHits, albedoDepth) {
+    const d = Object.assign(this._setsDesc(desc), { lights: desc.lights || [], material: desc.material ? desc.material.h : undefined });
+    if (desc.bounces !== undefined) d.bounces = desc.bounces;
+    wrap(() => native().renderViewGuided(this.ctx.h, d, this._viewDesc(view), seeds ? seeds.h : null, radiance ? radiance.h : null, pixel ? pixel.h : null,
+                                         normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
+  }
+  guidedViews() { return wrap(() => native().ctxGuidedViews(this.ctx.h)); }
   // ---- extension: a frame's first pass and its guide buffers in one call (mirt_render_first_pass_guided): every buffer ends as after
   // renderPass(desc with firstPass) followed by renderGuides(desc, normalHits, albedoDepth) -- where the pass resolves its pixels at 4, 16 or 64 rays
   // per pixel the pass's own launch writes the guides (ctx.guidedPasses() counts those calls), elsewhere the guide launches follow it.

@@ -157,6 +157,9 @@ SYMBOLS = {
     "mirt_view_rays": (C.c_int, [C.c_void_p, C.POINTER(_ViewDesc), C.c_void_p]),
     "mirt_render_view": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mirt_view_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_view_guides": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_void_p]),
+    "mirt_render_view_guided": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mirt_ctx_guided_views": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_render_ao": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_AoDesc), C.c_void_p]),
     "mirt_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
@@ -623,6 +626,26 @@ class Context:
         """how many rays the last render_view call re-ran in the exact kernel, in whole blocks of 256 (mirt_view_deferred)"""
         n = C.c_uint64()
         self._chk(lib().mirt_view_deferred(self.h, C.byref(n)))
+        return n.value
+
+    def view_guides(self, scene_desc, view, normal_hits=None, albedo_depth=None):
+        """The first-hit guides of a panoramic, fisheye or orthographic camera's row tile in one launch (mirt_view_guides): float4 per tile pixel
+        each, as render_guides writes them for the thin lens -- what filter_atrous reads.  Either may be None, not both.  Depth is in units of
+        |forward| and the basis as given."""
+        self._chk(lib().mirt_view_guides(self.h, C.byref(scene_desc) if scene_desc is not None else None, C.byref(view) if view is not None else None,
+                                         normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
+    def render_view_guided(self, scene_desc, view, seeds, radiance=None, pixel=None, normal_hits=None, albedo_depth=None):
+        """render_view and view_guides in one call (mirt_render_view_guided): the same bytes in every buffer; at k = 1, 2, 4 and 8 the frame's own
+        launch writes the guides (guided_views counts those calls).  The outputs are final in stream order."""
+        self._chk(lib().mirt_render_view_guided(self.h, C.byref(scene_desc) if scene_desc is not None else None, C.byref(view) if view is not None else None,
+                                                seeds.h if seeds else None, radiance.h if radiance else None, pixel.h if pixel else None,
+                                                normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
+    def guided_views(self):
+        """how many render_view_guided calls of this context wrote the guides from the frame's own launch (mirt_ctx_guided_views)"""
+        n = C.c_uint64()
+        self._chk(lib().mirt_ctx_guided_views(self.h, C.byref(n)))
         return n.value
 
     def render_ao(self, desc, ao_out, samples=AO_DEFAULT_SAMPLES, radius=float("inf"), bias=AO_DEFAULT_BIAS):

@@ -1,6 +1,7 @@
 """Ray queries on torch tensors: the closest hit, occlusion, or the path radiance of rays the caller holds as a cuda tensor (mirt_trace_closest,
 mirt_trace_occluded, mirt_trace_radiance; the definitions are include/mirt.h's) -- and, beside trace_radiance, render_view: a frame of a
-panoramic, fisheye or orthographic camera into cuda tensors (mirt_render_view).
+panoramic, fisheye or orthographic camera into cuda tensors (mirt_render_view), view_guides: its first-hit guides (mirt_view_guides), and
+denoised_view: progressive frames, the guides from the first (mirt_render_view_guided), and the a-trous filter behind the last.
 
 The tensors are not copied: each is wrapped as a buffer of the context (Context.wrap) for the length of the call, and the launches are queued on
 torch's CURRENT stream (Context.set_stream), so they are ordered after whatever produced `rays` there and before whatever reads the result there.
@@ -94,11 +95,29 @@ def trace_radiance(ctx, dev_scene, rays, seeds, samples=1, bounces=5, accumulate
     return out
 
 
-def render_view(ctx, dev_scene, view, seeds, bounces=5, accumulate_into=None, want_pixel=False):
+def view_guides(ctx, dev_scene, view):
+    """-> (normal_hits, albedo_depth), float32 cuda [rows * width, 4] each on the context's device: the first-hit guides of a panoramic, fisheye
+    or orthographic camera's frame (or row tile) in one launch (mirt_view_guides).  view: mirt.view_desc(...)."""
+    npix = (view.nrows or view.height) * view.width
+    device = torch.device("cuda", ctx.device)
+    nh = torch.empty((npix, 4), dtype=torch.float32, device=device)
+    ad = torch.empty((npix, 4), dtype=torch.float32, device=device)
+    with _OnTorchStream(ctx, device):
+        wrapped = [ctx.wrap(nh.data_ptr(), npix * 16), ctx.wrap(ad.data_ptr(), npix * 16)]
+        try:
+            ctx.view_guides(dev_scene.pass_desc(None, None), view, wrapped[0], wrapped[1])
+        finally:
+            for b in wrapped:
+                b.release()
+    return nh, ad
+
+
+def render_view(ctx, dev_scene, view, seeds, bounces=5, accumulate_into=None, want_pixel=False, want_guides=False):
     """-> radiance [rows * width, 4] float32, or (radiance, pixel [rows * width, 4] uint8) with want_pixel: a frame (or row tile) of a panoramic,
     fisheye or orthographic camera in one launch (mirt_render_view).  view: mirt.view_desc(...); its ACCUMULATE flag is set here from
     accumulate_into, a float32 cuda [rows * width, 4] of sums to continue (written in place and returned).  seeds: int32 cuda [rows * width * k * k],
-    advanced in place."""
+    advanced in place.  want_guides: the frame's first-hit guides too (mirt_render_view_guided) -- the result ends with normal_hits and
+    albedo_depth, float32 [rows * width, 4] each."""
     from . import mirt
     rows = view.nrows or view.height
     npix = rows * view.width
@@ -113,12 +132,44 @@ def render_view(ctx, dev_scene, view, seeds, bounces=5, accumulate_into=None, wa
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == (npix, 4) and out.is_contiguous() and out.device == seeds.device):
         raise ValueError("accumulate_into: a contiguous float32 cuda tensor [rows * width, 4] on the seeds' device")
     pixel = torch.empty((npix, 4), dtype=torch.uint8, device=seeds.device) if want_pixel else None
+    guides = [torch.empty((npix, 4), dtype=torch.float32, device=seeds.device) for _ in range(2)] if want_guides else []
     view.flags = mirt.VIEW_ACCUMULATE if accumulate_into is not None else 0
     with _OnTorchStream(ctx, seeds.device):
         wrapped = [ctx.wrap(seeds.data_ptr(), n * 4), ctx.wrap(out.data_ptr(), npix * 16)] + ([ctx.wrap(pixel.data_ptr(), npix * 4)] if want_pixel else [])
+        gw = [ctx.wrap(g.data_ptr(), npix * 16) for g in guides]
         try:
-            ctx.render_view(dev_scene.pass_desc(None, None, bounces=bounces), view, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None)
+            desc = dev_scene.pass_desc(None, None, bounces=bounces)
+            if want_guides:
+                ctx.render_view_guided(desc, view, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None, gw[0], gw[1])
+            else:
+                ctx.render_view(desc, view, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None)
+        finally:
+            for b in wrapped + gw:
+                b.release()
+    result = (out,) + ((pixel,) if want_pixel else ()) + tuple(guides)
+    return result if len(result) > 1 else out
+
+
+def denoised_view(ctx, dev_scene, view, seeds, passes=1, bounces=5, **filter_params):
+    """-> (filtered [rows * width, 4] float32, pixel [rows * width, 4] uint8): `passes` progressive frames of a WHOLE view-camera image -- the
+    first through mirt_render_view_guided, which leaves the guides too, the later ones plain with ACCUMULATE -- and then, once, the a-trous
+    filter (mirt_filter_atrous) with the shipped defaults and tone = 1 / (rpp * passes); filter_params override the defaults.  Nothing leaves
+    the device.  seeds: int32 cuda [height * width * k * k], advanced in place."""
+    if view.row0 or (view.nrows and view.nrows != view.height):
+        raise ValueError("denoised_view filters a whole image: view.row0 and view.nrows must be 0")
+    if passes < 1:
+        raise ValueError("passes >= 1")
+    npix = view.height * view.width
+    radiance, nh, ad = render_view(ctx, dev_scene, view, seeds, bounces=bounces, want_guides=True)
+    for _ in range(1, passes):
+        render_view(ctx, dev_scene, view, seeds, bounces=bounces, accumulate_into=radiance)
+    filtered = torch.empty((npix, 4), dtype=torch.float32, device=seeds.device)
+    pixel = torch.empty((npix, 4), dtype=torch.uint8, device=seeds.device)
+    with _OnTorchStream(ctx, seeds.device):
+        wrapped = [ctx.wrap(t.data_ptr(), t.numel() * t.element_size()) for t in (radiance, nh, ad, filtered, pixel)]
+        try:
+            ctx.filter_atrous(view.width, view.height, 1.0 / (view.k * view.k * passes), *wrapped, **filter_params)
         finally:
             for b in wrapped:
                 b.release()
-    return (out, pixel) if want_pixel else out
+    return filtered, pixel

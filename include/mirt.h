@@ -417,8 +417,9 @@ MIRT_API int mirt_radiance_deferred(mirt_ctx* ctx, uint64_t* rays);
  * mirt_ctx_set_exact_only is honoured.  An ORTHOGRAPHIC camera whose `forward` has a zero component is outside the ray-side guard for every ray
  * (|d_k| >= 2^-40): its frames run wholly in the exact kernel, with the same results.  mirt_view_deferred: the rays the last mirt_render_view
  * re-ran in the exact kernel, counted when asked, like mirt_radiance_deferred, in whole blocks of 256.
- * NOT BUILT: guides, ambient occlusion or the filter for these cameras; jitter or a lens on them; k that is not a power of two, or above 16; more
- * than one sample per ray per call; a multi-device helper (tiles take global positions, so a caller can split the rows); graph capture.
+ * The first-hit guides of these cameras are mirt_view_guides and mirt_render_view_guided, below; what they write is what mirt_filter_atrous reads,
+ * so a few-rays-per-pixel panorama is filtered like a thin-lens frame.  NOT BUILT: ambient occlusion or the upsampler for these cameras; jitter
+ * or a lens on them; k that is not a power of two, or above 16; more than one sample per ray per call; a multi-device helper (tiles take global positions, so a caller can split the rows); graph capture.
  * MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
 #define MIRT_VIEW_ORTHOGRAPHIC 0u
 #define MIRT_VIEW_EQUIRECT     1u   /* 360 x 180 degrees, longitude along x, latitude along y */
@@ -438,6 +439,44 @@ typedef struct mirt_view_desc {
 MIRT_API int mirt_view_rays(mirt_ctx* ctx, const mirt_view_desc* view, mirt_buf* rays);
 MIRT_API int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel);
 MIRT_API int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays);
+/* FIRST-HIT GUIDES OF A VIEW CAMERA'S TILE, one launch: what mirt_render_guides is to the thin lens, for the cameras above -- the two float4
+ * images per pixel that mirt_filter_atrous and mirt_upsample_guided consume, whichever camera made them.
+ * DEFINITION, by composition.  Pixel p of the tile has the rays p * rpp + i, i = 0 .. rpp - 1, exactly as mirt_view_rays writes them.  Each runs
+ * with a Poi reset as initTrace resets it through sphereTrace, triangleTrace and every meshTrace in upload order: mirt_trace_closest's CLOSEST.
+ * A sample is a HIT iff 0 <= Poi.matId < the number of material entries (mirt_render_guides's rule: an id past the table is not a hit and reads
+ * nothing -- so the material buffer is needed even when only normal_hits is asked for).
+ *   normal_hits [p] = float4(sum Poi.normal.x, sum .y, sum .z, number of hit samples)
+ *   albedo_depth[p] = float4(sum material[matId].x, sum .y, sum .z, sum Ray.maxt)
+ * sequential fp32 sums from +0 over the hit samples in sample order; a pixel without a hit is all +0 in both.  A DEAD fisheye sample (r > 1)
+ * enters dead and is never a hit: a pixel wholly outside the circle is background for the filter.  DEPTH IS IN UNITS OF |d|, as the ray
+ * queries report t: `forward` and the basis are used as given, so an ORTHOGRAPHIC camera with |forward| = 2 reports half the distance.  k = 1 is
+ * allowed here, unlike rays_per_pixel == 1 in mirt_render_guides: these cameras draw nothing from the seeds.
+ * Of `scene` only struct_size, the primitive sets and material are read; of `view` everything but tone and the meaning of flags (an unknown
+ * flag is still refused).  Nothing but the two outputs is written.  Positions use the global y: a tile's guides equal the same rows of the frame's.
+ * CHECKS, all before anything is queued; nothing is written when one fails.  MIRT_E_ARG: mirt_view_rays's descriptor checks, a wrong struct_size
+ * of `scene`, both outputs NULL, an output whose bytes meet the other's, a geometry buffer's or the material's, the mesh count rule of
+ * mirt_trace_radiance, a call while capturing.  MIRT_E_RANGE: an output shorter than the tile's pixels x 16 B, a material table shorter than one
+ * entry.  MIRT_E_DATA: a cell table that fails validation.  MIRT_E_HANDLE: a bad context or buffer.  A held command stream is flushed first;
+ * wrapped geometry is re-validated as for a pass.
+ * KERNEL (csrc/pt_kernels_rays.hip k_viewGuides): one lane per pixel walking its samples in order -- by default the optimistic / exact pair PER
+ * PIXEL, a bit per pixel; mirt_ctx_set_exact_only is honoured.  MIRT_ABI_VERSION is unchanged: a host detects the entry point by its symbol. */
+MIRT_API int mirt_view_guides(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, mirt_buf* normal_hits, mirt_buf* albedo_depth);
+/* THE FRAME AND ITS GUIDES in one call.  Every buffer the caller passes -- seeds, radiance, pixel, normal_hits, albedo_depth -- ends bit for bit
+ * as after mirt_render_view(ctx, scene, view, seeds, radiance, pixel) followed by mirt_view_guides(ctx, scene, view, normal_hits, albedo_depth),
+ * with or without MIRT_VIEW_ACCUMULATE: the guides are the same for every progressive pass, so a host takes them with the first and renders the
+ * later ones plain.  CHECKS: those of both calls, plus a guide buffer whose bytes meet the seeds', the radiance's or the pixel's (MIRT_E_ARG),
+ * all before anything is queued -- when one fails nothing is written at all.  mirt_view_deferred means what it means after mirt_render_view.
+ * ROUTE.  ONE LAUNCH (per kernel of the optimistic / exact pair) where a pixel's samples are consecutive lanes of one wave -- rpp 1, 4, 16 or
+ * 64, k = 1, 2, 4 or 8: the frame's kernel adds a pixel's eight values lane by lane right after its camera rays' closest-hit stage and writes
+ * the guides itself.  EVERYWHERE ELSE -- k = 16, where a pixel spans four waves, and MIRT_GUIDED_VIEW=0 in the environment (an A/B switch, read
+ * per call) -- the call queues the two calls' launches.  mirt_ctx_guided_views: the calls of this context that took the one-launch route.
+ * The optimistic kernel writes a block's guides before its verdict; a block that defers is re-run whole by the exact kernel, which writes the
+ * same pixels' guides again, later on the same stream.  The outputs are therefore FINAL IN STREAM ORDER -- when the call's launches have
+ * completed (mirt_finish) -- like every other output of the frame, not before.  Not built: a one-launch route at k = 16, graph capture.
+ * MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
+MIRT_API int mirt_render_view_guided(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, mirt_buf* seeds, mirt_buf* radiance,
+                                     mirt_buf* pixel, mirt_buf* normal_hits, mirt_buf* albedo_depth);
+MIRT_API int mirt_ctx_guided_views(mirt_ctx* ctx, uint64_t* count);
 /* AMBIENT OCCLUSION OF THE FIRST HIT of the row tile, in one launch: the AOV the guides lack.  ao_out holds one uint32[2] per tile-local pixel,
  * {open, cast}, 8 bytes per pixel.  Pixel p of the row tile has the rays p * rays_per_pixel + i, i = 0 .. rays_per_pixel - 1, each taken as
  * initTrace and the closest-hit stage leave it -- sphereTrace, triangleTrace, then every meshTrace in upload order -- before lightRender: exactly
