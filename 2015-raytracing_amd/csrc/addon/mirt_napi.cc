@@ -624,6 +624,43 @@ napi_value CtxGuidedViews(napi_env env, napi_callback_info info) {
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return mk_num(env, (double)n);
 }
+// viewAo(ctx, desc, viewDesc, aoDesc, seeds, aoOut): ambient occlusion of the tile (mirt_view_ao) -- of desc the primitive sets alone are read,
+// aoDesc = {samples, radius, bias} as for renderAo, seeds (int32 per tile ray) read and not written, aoOut uint32 {open, cast} per tile pixel.
+// viewAoDeferred(ctx) -> the pixels the last viewAo re-ran in the exact kernel (mirt_view_ao_deferred).
+napi_value ViewAo(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    void *c, *seeds = nullptr, *out = nullptr;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "viewAo(ctx, desc, viewDesc, aoDesc, seeds, aoOut)");
+    get_ext(env, argv[4], &seeds);
+    get_ext(env, argv[5], &out);
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    if (!read_sets(env, argv[1], "viewAo", p, sph, tri, meshes)) return nullptr;
+    mirt_view_desc v;
+    if (!read_view(env, argv[2], "viewAo", v)) return nullptr;
+    mirt_ao_desc a = {(uint32_t)sizeof(mirt_ao_desc), MIRT_AO_DEFAULT_SAMPLES, INFINITY, MIRT_AO_DEFAULT_BIAS};
+    napi_valuetype t = napi_undefined;
+    if (napi_typeof(env, argv[3], &t) == napi_ok && t == napi_object) {
+        prop_u32(env, argv[3], "samples", &a.samples);
+        prop_f32(env, argv[3], "radius", &a.radius);
+        prop_f32(env, argv[3], "bias", &a.bias);
+    }
+    const int rc = mirt_view_ao((mirt_ctx*)c, &p, &v, &a, (mirt_buf*)seeds, (mirt_buf*)out);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value ViewAoDeferred(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    void* c;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "viewAoDeferred(ctx)");
+    uint64_t n = 0;
+    int rc = mirt_view_ao_deferred((mirt_ctx*)c, &n);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return mk_num(env, (double)n);
+}
 napi_value RenderView(napi_env env, napi_callback_info info) {
     ARGS(6);
     void *c, *seeds = nullptr, *radiance = nullptr, *pixel = nullptr;
@@ -1091,7 +1128,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"viewGuides", ViewGuides}, {"renderViewGuided", RenderViewGuided}, {"ctxGuidedViews", CtxGuidedViews}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"viewGuides", ViewGuides}, {"viewAo", ViewAo}, {"viewAoDeferred", ViewAoDeferred}, {"renderViewGuided", RenderViewGuided}, {"ctxGuidedViews", CtxGuidedViews}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"renderAo", RenderAo}, {"aoDeferred", AoDeferred}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

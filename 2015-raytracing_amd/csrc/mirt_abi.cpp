@@ -88,6 +88,9 @@ struct mirt_ctx {
     void* view_defer = nullptr;   // mirt_render_view, optimistic pair: [count, pad, pad, pad | a bit per BLOCK of 256 rays], its own allocation too
     size_t view_defer_bytes = 0;
     uint32_t view_defer_words = 0; // mask words the last mirt_render_view used (0: it ran the exact kernel only)
+    void* view_ao_defer = nullptr;   // mirt_view_ao, optimistic pair: [count, pad, pad, pad | a bit per pixel of the tile], its own allocation too
+    size_t view_ao_defer_bytes = 0;
+    uint32_t view_ao_defer_words = 0; // mask words the last mirt_view_ao used (0: it ran the exact kernel only)
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     int force_exact = 0;          // mirt_ctx_set_exact_only: 1 = skip the optimistic kernel, run every sample through the exact one
@@ -401,6 +404,7 @@ static int destroy_ctx(mirt_ctx* ctx) {
     if (ctx->ao_defer) (void)hipFree(ctx->ao_defer);
     if (ctx->rad_defer) (void)hipFree(ctx->rad_defer);
     if (ctx->view_defer) (void)hipFree(ctx->view_defer);
+    if (ctx->view_ao_defer) (void)hipFree(ctx->view_ao_defer);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1902,6 +1906,12 @@ static int view_verdict(mirt_ctx* ctx, const char* fn, pt::ViewVerdict v, const 
         case pt::VIEW_NO_OUTPUT: return fail(ctx, code, "%s: radiance and pixel are both NULL (either may be, not both)", fn);
         case pt::VIEW_ACCUMULATE_NEEDS_RADIANCE: return fail(ctx, code, "%s: MIRT_VIEW_ACCUMULATE without a radiance buffer to go on from", fn);
         case pt::VIEW_NO_GUIDE: return fail(ctx, code, "%s: normal_hits and albedo_depth are both NULL (either may be, not both)", fn);
+        case pt::VIEW_AO_STRUCT_SIZE: return fail(ctx, code, "%s: AO descriptor size mismatch", fn);
+        case pt::VIEW_AO_SAMPLES: return fail(ctx, code, "%s: samples outside 1..%u", fn, MIRT_AO_MAX_SAMPLES);
+        case pt::VIEW_AO_RADIUS: return fail(ctx, code, "%s: radius is not above 0", fn);
+        case pt::VIEW_AO_BIAS: return fail(ctx, code, "%s: bias is not a finite number >= 0", fn);
+        case pt::VIEW_AO_NO_SEEDS: return fail(ctx, code, "%s: seeds is NULL (the AO rays draw from them; they are not written)", fn);
+        case pt::VIEW_AO_NO_OUTPUT: return fail(ctx, code, "%s: ao_out is NULL", fn);
     }
     return fail(ctx, MIRT_E_ARG, "%s: view descriptor refused", fn);
 }
@@ -2054,6 +2064,80 @@ int mirt_ctx_guided_views(mirt_ctx* ctx, uint64_t* count) try {
     *count = ctx->guided_views;
     return MIRT_OK;
 } MIRT_CATCH("mirt_ctx_guided_views", return MIRT_E_DEVICE)
+
+// Ambient occlusion of a view camera's tile (pt_kernels_rays.hip k_viewAo): mirt_view_guides's checks without the material, mirt_render_ao's own
+// (pt_view_plan.hpp view_check_ao), then one launch -- or the optimistic / exact pair, per pixel -- of one lane per pixel.  Every check comes
+// before anything is queued; nothing but ao_out is written.
+static_assert(sizeof(pt::ViewAoDesc) == sizeof(mirt_ao_desc) && offsetof(pt::ViewAoDesc, samples) == offsetof(mirt_ao_desc, samples) &&
+              offsetof(pt::ViewAoDesc, radius) == offsetof(mirt_ao_desc, radius) && offsetof(pt::ViewAoDesc, bias) == offsetof(mirt_ao_desc, bias) &&
+              pt::kViewAoMaxSamples == MIRT_AO_MAX_SAMPLES, "pt_view_plan.hpp restates the header's AO descriptor");
+int mirt_view_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, const mirt_ao_desc* ao, mirt_buf* seeds, mirt_buf* ao_out) try {
+    const char* const fn = "mirt_view_ao";
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, fn);
+    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
+    if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
+    if (!ao || ao->struct_size != sizeof(mirt_ao_desc)) return fail(ctx, MIRT_E_ARG, "%s: AO descriptor size mismatch", fn);
+    pt::ViewDesc v;
+    memcpy(&v, vd, sizeof v);
+    pt::ViewAoDesc a;
+    memcpy(&a, ao, sizeof a);
+    int rc;
+    if ((rc = view_verdict(ctx, fn, pt::view_check_ao(v, a, seeds != nullptr, ao_out != nullptr), v))) return rc;
+    const pt::ViewPlan plan = pt::view_plan(v);
+    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
+    if (d->n_meshes && !d->meshes) return fail(ctx, MIRT_E_ARG, "%s: null mesh array", fn);
+    if ((rc = need(ctx, "mirt_view_ao seeds", seeds, plan.rays * 4))) return rc;
+    if ((rc = need(ctx, "mirt_view_ao ao_out", ao_out, plan.pixels * 8))) return rc;
+    {   // the output is read by nobody and no input is written: the bytes the call writes, against the seeds' and the geometry's buffers whole
+        std::vector<pt::PostRange> in;
+        add_range(in, seeds);
+        add_geometry_ranges(in, d);
+        const pt::PostRange out[1] = {{(uint64_t)(uintptr_t)ao_out->ptr, plan.pixels * 8, true}};
+        if (pt::post_alias(in.data(), in.size(), out, 1) != pt::POST_ALIAS_NONE)
+            return fail(ctx, MIRT_E_ARG, "%s: ao_out's bytes meet the seeds' or a geometry buffer's", fn);
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::FusedArgs A;
+    memset(&A, 0, sizeof A);
+    if ((rc = fill_sets(ctx, fn, d, A))) return rc;
+    const pt::ViewArgs V = view_args(v, plan);
+    const pt::ViewGuidesPlan g = pt::view_guides_plan(plan);
+    const int32_t* const sp = (const int32_t*)seeds->ptr;
+    ctx->view_ao_defer_words = 0;
+    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
+        if ((rc = grow_and_clear(ctx, ctx->view_ao_defer, ctx->view_ao_defer_bytes, 16u + (size_t)g.mask_words * 4u))) return rc;
+        uint32_t* const mask = (uint32_t*)ctx->view_ao_defer + 4;
+        pt::launch_viewAo(ctx->stream, A, V, g.blocks, true, a.samples, a.radius, a.bias, sp, ao_out->ptr, mask, nullptr);
+        pt::launch_viewAo(ctx->stream, A, V, g.blocks, false, a.samples, a.radius, a.bias, sp, ao_out->ptr, nullptr, mask);
+        ctx->view_ao_defer_words = g.mask_words;
+    } else {
+        pt::launch_viewAo(ctx->stream, A, V, g.blocks, false, a.samples, a.radius, a.bias, sp, ao_out->ptr, nullptr, nullptr);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    ao_out->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_view_ao", return MIRT_E_DEVICE)
+
+int mirt_view_ao_deferred(mirt_ctx* ctx, uint64_t* pixels) try {
+    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_view_ao_deferred: unknown context");
+    FLUSH_PENDING(ctx);
+    NOT_WHILE_CAPTURING(ctx, "mirt_view_ao_deferred");
+    if (!pixels) return fail(ctx, MIRT_E_ARG, "mirt_view_ao_deferred: null output");
+    *pixels = 0;
+    if (!ctx->view_ao_defer_words) return MIRT_OK;
+    // counted on demand: the mask of the last mirt_view_ao is still in place (the next one clears it)
+    uint32_t* counters = (uint32_t*)ctx->view_ao_defer;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
+    pt::launch_deferCount(ctx->stream, counters + 4, ctx->view_ao_defer_words, counters);
+    uint32_t count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *pixels = count;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_view_ao_deferred", return MIRT_E_DEVICE)
 
 int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_view_deferred: unknown context");

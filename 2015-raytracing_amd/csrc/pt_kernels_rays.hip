@@ -29,8 +29,8 @@
 //
 // Also here, because it runs rays_any: k_ao, ambient occlusion of the first hit (mirt_render_ao); and because it starts at a caller's ray:
 // k_traceRadiance, the pass's path from that ray on (mirt_trace_radiance); and because they are k_traceRadiance with the ray made in registers:
-// k_viewRays and k_viewPass, the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view), and k_viewGuides, their
-// first-hit guides (mirt_view_guides) -- at the end of the file.
+// k_viewRays and k_viewPass, the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view), k_viewGuides, their
+// first-hit guides (mirt_view_guides), and k_viewAo, their ambient occlusion (mirt_view_ao) -- at the end of the file.
 #include "pt_direct.hpp"
 #include "pt_resolve.hpp"   // resolve_rows: k_viewPass resolves its blocks' pixels as the pass does; guides_emit: its GUIDES instances write the guides
 #include "pt_view.hpp"      // view_ray: a sample's ray
@@ -627,6 +627,97 @@ void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uin
     const FusedLds L = fused_lds_slots(b, fast);
     if (fast) launch_viewGuides_t<true>(s, b, L, v, blocks, (float4*)normal_hits, (float4*)albedo_depth, defer_mask, nullptr);
     else launch_viewGuides_t<false>(s, b, L, v, blocks, (float4*)normal_hits, (float4*)albedo_depth, nullptr, redo_mask);
+}
+
+// ---- ambient occlusion of a view camera's tile (mirt_view_ao): k_ao with the ray of a sample made by view_ray instead of primary_ray, and so
+// through closest_all with ViewGuideHooks (a view ray's d is not of unit length); behind each sample's closest hit k_ao's own `samples` trips of
+// bounce_ray + rays_any, stated here a second time: a device function shared with k_ao re-allocated k_ao's registers (spill offsets and
+// scalar loads moved in all six instances), and that kernel's rule is identical code.  A change to one is a change to both.  The definition is
+// include/mirt.h's.
+// Structure: k_ao's and k_viewGuides' -- one lane per pixel walking its samples in order; V and `samples` are kernel arguments, so the model's
+// branch and the trip count are WAVE-UNIFORM.  A DEAD fisheye sample, a sample the guard retired, a lane past the tile (on the clamped last
+// pixel) and a redo kernel's unmarked lane ride along with a dead ray: they hit nothing, cast nothing and count nothing.  A wave without a pixel
+// leaves at the ballot.  The optimistic / exact pair is per PIXEL, a bit per pixel: a pixel one of whose view or AO rays the guard refuses, or
+// whose walk defers, sets its bit and writes nothing; the exact kernel redoes the marked pixels whole.  seeds: int32 per tile-local ray, read
+// for the casting samples and never written.  ao_out: {open, cast} per tile-local pixel, one 8-byte store.
+// Waves per SIMD the register allocator is held to: A/B switches of this kernel's own, starting from k_ao's (profiles/view_ao/README.md has the
+// registers per instance and the measurement).  At 1920 x 1080 x 4 with 4 AO rays on cornell_teapot3, equirect / oblique orthographic: 2.39 / 1.79 ms
+// (4 waves) -> 2.22 / 1.77 (5) -> 2.22 / 1.85 (6): the bounds stay k_ao's.
+#ifndef PT_VIEW_AO_GRID_WAVES
+#define PT_VIEW_AO_GRID_WAVES PT_AO_GRID_WAVES
+#endif
+#ifndef PT_VIEW_AO_CELL_WAVES
+#define PT_VIEW_AO_CELL_WAVES PT_AO_CELL_WAVES
+#endif
+#define PT_VIEW_AO_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_VIEW_AO_GRID_WAVES : PT_VIEW_AO_CELL_WAVES)
+template <bool FAST, int GRIDS>
+__global__ void PT_VIEW_AO_BOUNDS(GRIDS) k_viewAo(const FusedArgs A, const ViewArgs V, uint32_t samples, float radius, float bias, const int32_t* __restrict__ seeds,
+                                                    uint2* __restrict__ ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    stage_block<FAST, GRIDS>(A);
+    const uint32_t npix = V.nrows * V.width;   // (a tile holds at most 2^32 - 256 rays: pt_view_plan.hpp)
+    uint32_t pix = blockIdx.x * 256u + threadIdx.x;
+    bool valid = pix < npix;
+    if (!FAST && redo_mask && valid) valid = (redo_mask[pix >> 5] >> (pix & 31u) & 1u) != 0u;
+    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
+    else if (!valid) return;
+    if (pix >= npix) pix = npix - 1u;
+    uint32_t open = 0u, cast = 0u;
+    bool defer = false;
+    const uint32_t rpp = V.k * V.k, first = pix * rpp;
+    for (uint32_t i = 0; i < rpp; ++i) {
+        Ray ray = view_ray(V, first + i);
+        if (!valid) { ray.mint = 0.0f; ray.maxt = 0.0f; }   // rides along dead: hits nothing, casts nothing
+        Poi poi;   // as initTrace resets it (code.cl:538-541)
+        poi.p = mk3(0.0f, 0.0f, 0.0f);
+        poi.n = mk3(0.0f, 0.0f, 0.0f);
+        poi.atte = mk3(1.0f, 1.0f, 1.0f);
+        poi.matId = -1;
+        closest_all<FAST, GRIDS>(A, ray, poi, ViewGuideHooks{}, defer);
+        const bool casts = poi.matId >= 0;   // bouncePaths' own test (code.cl:592): no material is read
+        int32_t seed = 0;
+        if (casts) seed = seeds[first + i];
+        for (uint32_t j = 0; j < samples; ++j) {
+            Ray sh;
+            sh.o = mk3(0.0f, 0.0f, 0.0f); sh.d = mk3(0.0f, 0.0f, 0.0f); sh.mint = 0.0f; sh.maxt = 0.0f;
+            if (casts) {
+                sh = bounce_ray(poi, seed);   // getHemisphereRay (code.cl:545-579): the seed advances, in its register only
+                if (bias != 0.0f) sh.o = add3(poi.p, scl3(bias, poi.n));   // two fp32 operations, each rounded on its own (-ffp-contract=off)
+                sh.maxt = radius;
+            }
+            rays_any<FAST, GRIDS>(A, sh, defer);
+            if (casts) {
+                cast += 1u;
+                if (!(sh.mint == sh.maxt)) open += 1u;
+            }
+        }
+    }
+    if (!valid) return;
+    if (FAST && defer) {   // the exact kernel redoes the pixel: nothing of it is written
+        atomicOr(&defer_mask[pix >> 5], 1u << (pix & 31u));
+        return;
+    }
+    ao_out[pix] = make_uint2(open, cast);
+}
+
+template <bool FAST>
+static void launch_viewAo_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const ViewArgs& v, uint32_t blocks, uint32_t samples, float radius, float bias,
+                            const int32_t* seeds, uint2* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    const dim3 grid(blocks);
+    fused_lds_dispatch(L, [&](auto G, size_t lds) {
+        hipLaunchKernelGGL((k_viewAo<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, samples, radius, bias, seeds, ao_out, defer_mask, redo_mask);
+    });
+}
+// fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
+// of redo_mask, or over every pixel when it is null.  blocks: ceil(pixels / 256), the plan's (pt_view_plan.hpp).
+void launch_viewAo(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, uint32_t samples, float radius, float bias, const int32_t* seeds,
+                   void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
+    if (!blocks) return;
+    FusedArgs b = a;
+    b.width = v.width; b.nrows = v.nrows;
+    b.rpp = v.k * v.k;   // stage_block, as launch_viewGuides sets it
+    const FusedLds L = fused_lds_slots(b, fast);
+    if (fast) launch_viewAo_t<true>(s, b, L, v, blocks, samples, radius, bias, seeds, (uint2*)ao_out, defer_mask, nullptr);
+    else launch_viewAo_t<false>(s, b, L, v, blocks, samples, radius, bias, seeds, (uint2*)ao_out, nullptr, redo_mask);
 }
 
 }  // namespace pt

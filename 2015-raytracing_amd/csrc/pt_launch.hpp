@@ -189,6 +189,11 @@ void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool 
 // (pt_view_plan.hpp view_guides_plan).  Reads the sets, material and nmat of `a` and nothing else of it.
 void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask,
                        const uint32_t* redo_mask);
+// mirt_view_ao: ambient occlusion of those rays' first hits (k_viewAo: k_ao with the ray made by view_ray), uint32[2] per tile pixel, {open, cast}.
+// One lane per pixel, `blocks` blocks of 256; the optimistic / exact pair per PIXEL, the mask one bit per pixel: both are view_guides_plan's.
+// seeds: int32 per tile ray, never written.  Reads the sets of `a` and nothing else of it.
+void launch_viewAo(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, uint32_t samples, float radius, float bias, const int32_t* seeds,
+                   void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask);
 // Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
 // every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
 struct FilterArgs {

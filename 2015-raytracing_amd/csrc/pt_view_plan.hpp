@@ -1,9 +1,9 @@
 // pt_view_plan.hpp -- the host side of the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view, mirt_view_guides,
-// mirt_render_view_guided; include/mirt.h): the descriptor checks that need no device, the launch plan -- the tile's rays, its blocks of 256
+// mirt_render_view_guided, mirt_view_ao; include/mirt.h): the descriptor checks that need no device, the launch plan -- the tile's rays, its blocks of 256
 // consecutive ray ids, the whole pixels a block holds and those of the ragged last block -- and the route rule of the guided frame.  Plain
-// integers and floats: no HIP header and no device, so a plain C++ compiler builds it and tests/test_view_plan.py and
-// tests/test_view_guides_plan.py check it on the CPU (tests/view_plan_dump.cpp, tests/view_guides_plan_dump.cpp).  mirt_abi.cpp is the caller
-// and owns the messages.
+// integers and floats: no HIP header and no device, so a plain C++ compiler builds it and tests/test_view_plan.py,
+// tests/test_view_guides_plan.py and tests/test_view_ao_plan.py check it on the CPU (tests/view_plan_dump.cpp, tests/view_guides_plan_dump.cpp,
+// tests/view_ao_plan_dump.cpp).  mirt_abi.cpp is the caller and owns the messages.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -16,6 +16,7 @@ constexpr uint32_t kViewAccumulate = 1u;                                        
 constexpr uint32_t kViewMaxExtent = 65535u;
 constexpr uint64_t kViewMaxRays = 0xFFFFFF00ull;   // 2^32 - 256: the kernels index a tile's rays with 32 bits, and a block reaches 255 ids past the last
 constexpr int kViewStatusArg = -1;                 // MIRT_E_ARG
+constexpr uint32_t kViewAoMaxSamples = 64u;        // MIRT_AO_MAX_SAMPLES
 
 // mirt_view_desc, field for field (mirt_abi.cpp asserts the size and copies the bytes)
 struct ViewDesc {
@@ -28,6 +29,11 @@ struct ViewDesc {
     float half_angle;
     float t_min, t_max;
     float tone;
+};
+// mirt_ao_desc, field for field
+struct ViewAoDesc {
+    uint32_t struct_size, samples;
+    float radius, bias;
 };
 
 enum ViewVerdict {
@@ -48,7 +54,13 @@ enum ViewVerdict {
     VIEW_NO_SEEDS,        // mirt_render_view without seeds
     VIEW_NO_OUTPUT,       // mirt_render_view with neither radiance nor pixel
     VIEW_ACCUMULATE_NEEDS_RADIANCE,
-    VIEW_NO_GUIDE         // mirt_view_guides, mirt_render_view_guided with neither normal_hits nor albedo_depth
+    VIEW_NO_GUIDE,        // mirt_view_guides, mirt_render_view_guided with neither normal_hits nor albedo_depth
+    VIEW_AO_STRUCT_SIZE,  // mirt_view_ao: struct_size is not sizeof(mirt_ao_desc)
+    VIEW_AO_SAMPLES,      // samples 0 or above MIRT_AO_MAX_SAMPLES
+    VIEW_AO_RADIUS,       // radius NaN or <= 0
+    VIEW_AO_BIAS,         // bias negative, NaN or infinite
+    VIEW_AO_NO_SEEDS,     // mirt_view_ao without seeds
+    VIEW_AO_NO_OUTPUT     // mirt_view_ao without ao_out
 };
 // the status every refusal above is reported with: 0, or MIRT_E_ARG
 inline int view_status(ViewVerdict v) { return v == VIEW_OK ? 0 : kViewStatusArg; }
@@ -91,6 +103,19 @@ inline ViewVerdict view_check_guides(const ViewDesc& v, bool normal_hits, bool a
     if (d != VIEW_OK) return d;
     return normal_hits || albedo_depth ? VIEW_OK : VIEW_NO_GUIDE;
 }
+// what mirt_view_ao asks: the descriptor as mirt_view_rays reads it, then mirt_render_ao's rules for the AO descriptor, then both buffers.  Its
+// grid and mask are view_guides_plan's: one lane and one bit per pixel
+inline ViewVerdict view_check_ao(const ViewDesc& v, const ViewAoDesc& ao, bool seeds, bool ao_out) {
+    const ViewVerdict d = view_check_desc(v);
+    if (d != VIEW_OK) return d;
+    if (ao.struct_size != sizeof(ViewAoDesc)) return VIEW_AO_STRUCT_SIZE;
+    if (!ao.samples || ao.samples > kViewAoMaxSamples) return VIEW_AO_SAMPLES;
+    if (!(ao.radius > 0.0f)) return VIEW_AO_RADIUS;   // a NaN compares false; +inf passes
+    if (!(ao.bias >= 0.0f) || isinf(ao.bias)) return VIEW_AO_BIAS;
+    if (!seeds) return VIEW_AO_NO_SEEDS;
+    if (!ao_out) return VIEW_AO_NO_OUTPUT;
+    return VIEW_OK;
+}
 // ... and mirt_render_view_guided: both calls' rules, the frame's first
 inline ViewVerdict view_check_render_guided(const ViewDesc& v, bool seeds, bool radiance, bool pixel, bool normal_hits, bool albedo_depth) {
     const ViewVerdict d = view_check_render(v, seeds, radiance, pixel);
@@ -123,8 +148,8 @@ inline ViewPlan view_plan(const ViewDesc& v) {
     return p;
 }
 
-// mirt_view_guides runs one lane per PIXEL (k_viewGuides): its grid, which launch_viewGuides is handed, and the optimistic kernel's mask of a
-// bit per pixel of the tile, which mirt_abi.cpp allocates
+// mirt_view_guides and mirt_view_ao run one lane per PIXEL (k_viewGuides, k_viewAo): the grid, which the launcher is handed, and the optimistic
+// kernel's mask of a bit per pixel of the tile, which mirt_abi.cpp allocates
 struct ViewGuidesPlan {
     uint32_t blocks;       // ceil(pixels / 256)
     uint32_t mask_words;   // ceil(pixels / 32)

@@ -3,7 +3,7 @@
 //   node cli.js pack   <scene.xml> <width> <height> <raysPerPixel>                 -> packed kernel inputs as JSON (stdout)
 //   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl] [--post-in-tiles]] [--guides PREFIX] [--denoise [iterations]] [--upscale F] [--ao PREFIX [--ao-samples N] [--ao-radius R] [--ao-bias B]]
 //                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --ao: + PREFIX.ao.u32 (ambient occlusion of the first hit, mirt_render_ao: raw uint32 pairs {open, cast} per pixel, N AO rays of length R per hit sample, default 4 and unbounded, displaced by B = 0.001 along the normal; taken before the first pass, the seeds are not advanced) and PREFIX.ao.pgm (a byte per pixel, floor(255 * open / cast + 0.5), 255 where cast is 0), not with --gpus N; --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N unless --post-in-tiles; --post-in-tiles (with --gpus N): --denoise and --upscale run tile-local -- every device exchanges halo rows with its neighbours and filters / upsamples its own rows (mirt_exchange_rows, mirt_filter_atrous_rows, mirt_upsample_guided_rows), only finished rows are gathered; the same bytes in <out>, <out>.filtered.f32 and <out>.upsampled.f32, and no <out>.radiance.f32 (the unfiltered sums stay on their devices)
-//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.ppm> --view equirect|fisheye|ortho [--eye x,y,z] [--look x,y,z] [--up x,y,z] [--fov degrees] [--ortho-size w,h] [--bounces N] [--seeds file.i32] [--view-guides PREFIX] [--view-denoise [iterations]]  -> a frame of a panoramic (360 x 180 degrees), fisheye (equidistant, --fov the full field of view, default 180) or orthographic (--ortho-size the window, default the scene box's extents in x and y) camera, one launch per pass (mirt_render_view): raysPerPixel 1, 4, 16, 64 or 256, un-jittered; the default eye is the scene box's centre, looking down -z; passes are progressive (MIRT_VIEW_ACCUMULATE, tone 1 / (raysPerPixel * p)); + <out>.radiance.f32; --view-guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32, the camera's first-hit guides (mirt_view_guides' definition; taken by the first pass, mirt_render_view_guided); --view-denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous behind the last pass, on the device; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; not with --gpus, --guides, --denoise (the thin-lens camera's), --upscale, --ao
+//   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.ppm> --view equirect|fisheye|ortho [--eye x,y,z] [--look x,y,z] [--up x,y,z] [--fov degrees] [--ortho-size w,h] [--bounces N] [--seeds file.i32] [--view-guides PREFIX] [--view-denoise [iterations]] [--view-ao PREFIX [--ao-samples N] [--ao-radius R] [--ao-bias B]]  -> a frame of a panoramic (360 x 180 degrees), fisheye (equidistant, --fov the full field of view, default 180) or orthographic (--ortho-size the window, default the scene box's extents in x and y) camera, one launch per pass (mirt_render_view): raysPerPixel 1, 4, 16, 64 or 256, un-jittered; the default eye is the scene box's centre, looking down -z; passes are progressive (MIRT_VIEW_ACCUMULATE, tone 1 / (raysPerPixel * p)); + <out>.radiance.f32; --view-guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32, the camera's first-hit guides (mirt_view_guides' definition; taken by the first pass, mirt_render_view_guided); --view-denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous behind the last pass, on the device; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --view-ao: + PREFIX.ao.u32 (the camera's ambient occlusion, mirt_view_ao: raw uint32 pairs {open, cast} per pixel, N, R and B as for --ao; taken before the first pass, the seeds are not advanced) and PREFIX.ao.pgm (a byte per pixel, floor(255 * open / cast + 0.5), 0 where cast is 0); not with --gpus, --guides, --denoise, --ao (the thin-lens camera's), --upscale
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
@@ -61,16 +61,25 @@ if (cmd === "pack") {
   if (rest.length < 6) usage();
   const renderer = require("./renderer.js");
   if (rest.includes("--view")) {   // a panoramic, fisheye or orthographic camera: one launch per pass (mirt_render_view)
-    // --guides and --denoise name the thin-lens camera's routes and stay refused beside --view, as they were; these cameras' own are
-    // --view-guides and --view-denoise
+    // --guides, --denoise and --ao name the thin-lens camera's routes and stay refused beside --view, as they were; these cameras' own are
+    // --view-guides, --view-denoise and --view-ao
     for (const flag of ["--gpus", "--guides", "--denoise", "--upscale", "--ao"])
-      if (rest.includes(flag)) { process.stderr.write(`--view is not available with ${flag}: these cameras' guides and filter are --view-guides PREFIX and --view-denoise [iterations]; the upsampler, AO and row tiles over N devices are not built for them\n`); process.exit(2); }
+      if (rest.includes(flag)) { process.stderr.write(`--view is not available with ${flag}: these cameras' guides, filter and AO are --view-guides PREFIX, --view-denoise [iterations] and --view-ao PREFIX; the upsampler and row tiles over N devices are not built for them\n`); process.exit(2); }
     const vopt = { view: viewOptions(rest), bounces: 5, seeds: null, countDeferred: true };
     let j;
     if ((j = rest.indexOf("--view-guides")) >= 0) { if (!rest[j + 1]) usage(); vopt.guides = rest[j + 1]; }   // the camera's first-hit guides beside the frame
     if ((j = rest.indexOf("--view-denoise")) >= 0) {   // the frame filtered on the device behind the last pass (mirt_filter_atrous); implies the guides
       vopt.denoise = {};
       if (/^\d+$/.test(rest[j + 1] || "")) vopt.denoise.iterations = +rest[j + 1];
+    }
+    let aoPrefix = null;
+    if ((j = rest.indexOf("--view-ao")) >= 0) {   // the camera's ambient occlusion beside the frame (mirt_view_ao), before the first pass
+      if (!rest[j + 1]) usage();
+      aoPrefix = rest[j + 1];
+      vopt.ao = {};
+      if ((j = rest.indexOf("--ao-samples")) >= 0) vopt.ao.samples = +rest[j + 1];
+      if ((j = rest.indexOf("--ao-radius")) >= 0) vopt.ao.radius = +rest[j + 1];
+      if ((j = rest.indexOf("--ao-bias")) >= 0) vopt.ao.bias = +rest[j + 1];
     }
     if ((j = rest.indexOf("--bounces")) >= 0) vopt.bounces = +rest[j + 1];
     if ((j = rest.indexOf("--seeds")) >= 0) { const b = fs.readFileSync(rest[j + 1]); vopt.seeds = new Int32Array(b.buffer.slice(b.byteOffset, b.byteOffset + b.length)); }
@@ -84,8 +93,16 @@ if (cmd === "pack") {
     if (res.guides) { vdump(`${vopt.guides}.normal_hits.f32`, res.guides.normalHits); vdump(`${vopt.guides}.albedo_depth.f32`, res.guides.albedoDepth); }
     process.stderr.write(`rendered ${vf} ${vw}x${vh} rpp ${vrpp}, ${vpasses} pass(es), ${vopt.view.model} camera${res.denoised ? ", filtered" : ""}: ${res.ms.toFixed(2)} ms on ${res.device}; rays redone by the exact kernel: ${res.deferred}\n`);
     if (res.guidedViews !== undefined) process.stderr.write(`frames that wrote their guides: ${res.guidedViews}\n`);
+    if (res.ao) {
+      const a = res.ao.pairs, gray = Buffer.alloc(vw * vh);
+      for (let k = 0; k < vw * vh; k++) gray[k] = a[2 * k + 1] ? Math.floor(255 * a[2 * k] / a[2 * k + 1] + 0.5) : 0;
+      vdump(`${aoPrefix}.ao.u32`, a);
+      fs.writeFileSync(`${aoPrefix}.ao.pgm`, Buffer.concat([Buffer.from(`P5\n${vw} ${vh}\n255\n`, "ascii"), gray]));
+      process.stderr.write(`ambient occlusion: ${aoPrefix}.ao.u32, ${aoPrefix}.ao.pgm; pixels re-run in the exact kernel: ${res.ao.deferred}\n`);
+    }
     process.exit(0);
   }
+  if (rest.includes("--view-ao")) { process.stderr.write("--view-ao needs --view equirect|fisheye|ortho: the thin-lens camera's AO is --ao PREFIX\n"); process.exit(2); }
   const opt = { granular: rest.includes("--granular"), graph: rest.includes("--graph"), fusion: rest.includes("--fusion"), deviceGrid: rest.includes("--device-grid"), bounces: 5, seeds: null,
                 keepAcu: !rest.includes("--no-acu"),   // --no-acu: a frame without the 16 bytes per ray: the pass resolves its own pixels (mirt.h; raysPerPixel
                                                         // dividing 256 or above 256) -- one pass, or

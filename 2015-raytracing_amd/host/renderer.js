@@ -778,6 +778,8 @@ function makeView(packed, width, height, rpp, v) {
 // (the guides are the same for every pass), the later ones are plain.  opt.denoise ({iterations, ...}: filterFrame's parameters, webcl.FILTER_DEFAULTS
 // where left out; implies the guides on the device): + denoised {pixel, filtered}, the a-trous filter run once behind the last pass with tone
 // 1 / (rpp * passes); nothing leaves the device between the passes and the filter.
+// opt.ao ({samples, radius, bias}): + ao {pairs: Uint32Array {open, cast} per pixel, deferred} -- queue.viewAo (mirt_view_ao) before the first
+// pass, from the seeds as they stand there (it does not advance them), outside the timed span.
 function renderViewFile(file, width, height, rpp, passes, opt) {
   opt = opt || {};
   const packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, 4);
@@ -795,6 +797,14 @@ function renderViewFile(file, width, height, rpp, passes, opt) {
   if (opt.seeds) q.enqueueWriteBuffer(sb, false, 0, n * 4, opt.seeds.subarray(0, n), []);
   else q.seedFill(sb, 0, n, 0);
   const desc = { spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, lights: packed.lights, material: dev.material, bounces: opt.bounces === undefined ? 5 : opt.bounces };
+  let ao = null;
+  if (opt.ao) {
+    if (!q.hasViewAo()) throw new Error("the loaded addon has no viewAo");
+    const ab = mk(npix * 8);
+    q.viewAo(desc, view, opt.ao, sb, ab);
+    ao = { pairs: new Uint32Array(npix * 2), deferred: q.viewAoDeferred() };
+    q.enqueueReadBuffer(ab, true, 0, npix * 8, ao.pairs, []);
+  }
   q.finish();
   const t0 = process.hrtime.bigint();
   let deferred = 0;
@@ -811,6 +821,7 @@ function renderViewFile(file, width, height, rpp, passes, opt) {
   q.enqueueReadBuffer(pb, true, 0, npix * 4, res.pixel, []);
   q.enqueueReadBuffer(rb, true, 0, npix * 16, res.radiance, []);
   if (guided) res.guidedViews = q.guidedViews();
+  if (ao) res.ao = ao;
   if (opt.guides) {
     res.guides = { normalHits: new Float32Array(npix * 4), albedoDepth: new Float32Array(npix * 4) };
     q.enqueueReadBuffer(nhb, true, 0, npix * 16, res.guides.normalHits, []);

@@ -268,6 +268,16 @@ class WebCLCommandQueue {
                                          normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
   }
   guidedViews() { return wrap(() => native().ctxGuidedViews(this.ctx.h)); }
+  // ---- extension: ambient occlusion of those cameras in one launch (mirt_view_ao).  viewAo(desc, view, aoDesc, seeds, aoOut): aoDesc = {samples,
+  // radius, bias} (left out: 4, Infinity, 0.001); seeds: an int32 per tile ray, read and not written; aoOut: uint32 {open, cast} per tile pixel, as
+  // renderAo writes them for the thin lens.  Of desc only spheres, triangles and meshes are read.  viewAoDeferred(): the pixels the last call re-ran
+  // in the exact kernel.  hasViewAo(): the loaded library has the entry point
+  hasViewAo() { return typeof native().viewAo === "function"; }
+  viewAo(desc, view, aoDesc, seeds, aoOut) {
+    const d = this._setsDesc(desc);
+    wrap(() => native().viewAo(this.ctx.h, d, this._viewDesc(view), aoDesc || {}, seeds ? seeds.h : null, aoOut ? aoOut.h : null));
+  }
+  viewAoDeferred() { return wrap(() => native().viewAoDeferred(this.ctx.h)); }
   // ---- extension: a frame's first pass and its guide buffers in one call (mirt_render_first_pass_guided): every buffer ends as after
   // renderPass(desc with firstPass) followed by renderGuides(desc, normalHits, albedoDepth) -- where the pass resolves its pixels at 4, 16 or 64 rays
   // per pixel the pass's own launch writes the guides (ctx.guidedPasses() counts those calls), elsewhere the guide launches follow it.

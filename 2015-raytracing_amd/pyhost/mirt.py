@@ -162,6 +162,8 @@ SYMBOLS = {
     "mirt_ctx_guided_views": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_render_ao": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_AoDesc), C.c_void_p]),
     "mirt_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_view_ao": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.POINTER(_AoDesc), C.c_void_p, C.c_void_p]),
+    "mirt_view_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
     "mirt_upsample_guided": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc)]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -660,6 +662,20 @@ class Context:
         """how many pixels the last render_ao call re-ran in the exact kernel (mirt_ao_deferred)"""
         n = C.c_uint64()
         self._chk(lib().mirt_ao_deferred(self.h, C.byref(n)))
+        return n.value
+
+    def view_ao(self, scene_desc, view, seeds, ao_out, samples=AO_DEFAULT_SAMPLES, radius=float("inf"), bias=AO_DEFAULT_BIAS):
+        """Ambient occlusion of a panoramic, fisheye or orthographic camera's row tile in one launch (mirt_view_ao): ao_out receives uint32
+        {open, cast} per tile pixel, as render_ao writes them for the thin lens, from the rays of view_rays.  seeds (int32 per tile ray) is read
+        and not written; of scene_desc only the primitive sets are read.  An _AoDesc may be given in place of `samples`."""
+        ao = samples if isinstance(samples, _AoDesc) else _AoDesc(C.sizeof(_AoDesc), int(samples), float(radius), float(bias))
+        self._chk(lib().mirt_view_ao(self.h, C.byref(scene_desc) if scene_desc is not None else None, C.byref(view) if view is not None else None,
+                                     C.byref(ao) if ao is not None else None, seeds.h if seeds else None, ao_out.h if ao_out else None))
+
+    def view_ao_deferred(self):
+        """how many pixels the last view_ao call re-ran in the exact kernel (mirt_view_ao_deferred)"""
+        n = C.c_uint64()
+        self._chk(lib().mirt_view_ao_deferred(self.h, C.byref(n)))
         return n.value
 
     def filter_atrous(self, width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,

@@ -1,6 +1,7 @@
 """Ray queries on torch tensors: the closest hit, occlusion, or the path radiance of rays the caller holds as a cuda tensor (mirt_trace_closest,
 mirt_trace_occluded, mirt_trace_radiance; the definitions are include/mirt.h's) -- and, beside trace_radiance, render_view: a frame of a
-panoramic, fisheye or orthographic camera into cuda tensors (mirt_render_view), view_guides: its first-hit guides (mirt_view_guides), and
+panoramic, fisheye or orthographic camera into cuda tensors (mirt_render_view), view_guides: its first-hit guides (mirt_view_guides),
+view_ao: its ambient occlusion (mirt_view_ao), and
 denoised_view: progressive frames, the guides from the first (mirt_render_view_guided), and the a-trous filter behind the last.
 
 The tensors are not copied: each is wrapped as a buffer of the context (Context.wrap) for the length of the call, and the launches are queued on
@@ -110,6 +111,29 @@ def view_guides(ctx, dev_scene, view):
             for b in wrapped:
                 b.release()
     return nh, ad
+
+
+def view_ao(ctx, dev_scene, view, seeds, samples=None, radius=float("inf"), bias=None):
+    """-> ao, uint32 cuda [rows * width, 2] on the context's device: {open, cast} per pixel of a panoramic, fisheye or orthographic camera's frame
+    (or row tile) in one launch (mirt_view_ao).  view: mirt.view_desc(...).  seeds: int32 cuda [rows * width * k * k], read and not written.
+    samples / bias left None are MIRT_AO_DEFAULT_*."""
+    from . import mirt
+    npix = (view.nrows or view.height) * view.width
+    n = npix * view.k * view.k
+    if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.shape == (n,) and seeds.is_contiguous()):
+        raise ValueError(f"seeds: a contiguous int32 cuda tensor [{n}]")
+    if seeds.device.index != ctx.device:
+        raise ValueError(f"seeds live on cuda:{seeds.device.index}, the context on device {ctx.device}")
+    ao = torch.empty((npix, 2), dtype=torch.uint32, device=seeds.device)
+    with _OnTorchStream(ctx, seeds.device):
+        wrapped = [ctx.wrap(seeds.data_ptr(), n * 4), ctx.wrap(ao.data_ptr(), npix * 8)]
+        try:
+            ctx.view_ao(dev_scene.pass_desc(None, None), view, wrapped[0], wrapped[1], samples=mirt.AO_DEFAULT_SAMPLES if samples is None else samples, radius=radius,
+                        bias=mirt.AO_DEFAULT_BIAS if bias is None else bias)
+        finally:
+            for b in wrapped:
+                b.release()
+    return ao
 
 
 def render_view(ctx, dev_scene, view, seeds, bounces=5, accumulate_into=None, want_pixel=False, want_guides=False):

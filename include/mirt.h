@@ -418,7 +418,8 @@ MIRT_API int mirt_radiance_deferred(mirt_ctx* ctx, uint64_t* rays);
  * (|d_k| >= 2^-40): its frames run wholly in the exact kernel, with the same results.  mirt_view_deferred: the rays the last mirt_render_view
  * re-ran in the exact kernel, counted when asked, like mirt_radiance_deferred, in whole blocks of 256.
  * The first-hit guides of these cameras are mirt_view_guides and mirt_render_view_guided, below; what they write is what mirt_filter_atrous reads,
- * so a few-rays-per-pixel panorama is filtered like a thin-lens frame.  NOT BUILT: ambient occlusion or the upsampler for these cameras; jitter
+ * so a few-rays-per-pixel panorama is filtered like a thin-lens frame.  Their ambient occlusion is mirt_view_ao, below mirt_render_ao.
+ * NOT BUILT: the upsampler for these cameras; jitter
  * or a lens on them; k that is not a power of two, or above 16; more than one sample per ray per call; a multi-device helper (tiles take global positions, so a caller can split the rows); graph capture.
  * MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
 #define MIRT_VIEW_ORTHOGRAPHIC 0u
@@ -517,6 +518,32 @@ typedef struct mirt_ao_desc {
 } mirt_ao_desc;
 MIRT_API int mirt_render_ao(mirt_ctx* ctx, const mirt_pass_desc* desc, const mirt_ao_desc* ao, mirt_buf* ao_out);
 MIRT_API int mirt_ao_deferred(mirt_ctx* ctx, uint64_t* pixels);
+/* AMBIENT OCCLUSION OF A VIEW CAMERA'S TILE, one launch: what mirt_render_ao is to the thin lens, for the panoramic, fisheye and orthographic
+ * cameras.  ao_out holds one uint32[2] per tile-local pixel, {open, cast}, 8 bytes per pixel.
+ * DEFINITION, by composition.  Pixel p of the tile has the rays p * rpp + i, i = 0 .. rpp - 1, rpp = k * k, exactly as mirt_view_rays writes
+ * them (global y; a DEAD fisheye sample enters dead).  Each runs as mirt_trace_closest's CLOSEST: a Poi reset as initTrace resets it, then
+ * sphereTrace, triangleTrace and every meshTrace in upload order.  From there on the words are mirt_render_ao's, above: a sample CASTS iff
+ * Poi.matId >= 0 (no material is read, an id past the table casts too; a dead or missing sample casts nothing); a casting sample starts with
+ * s = seeds[tile-local ray id] and makes ao->samples AO rays, ray j what getHemisphereRay(poi, &s) returns, then given maxt = radius and, when
+ * bias != 0, the origin o.c = p.c + (n.c * bias) -- two fp32 operations, each rounded on its own; bias == 0: Poi.p bit for bit; the AO ray is
+ * OCCLUDED by mirt_trace_occluded's definition; cast = casting samples x samples, open = the number of those rays not occluded; a pixel with no
+ * hit is {0, 0}.
+ * READ AND WRITTEN.  `seeds` (int32 per tile ray) is read and NEVER written.  Of `scene` only struct_size and the primitive sets are read: no
+ * material, no lights.  Of `view` everything but tone and the meaning of flags (an unknown flag is still refused).  k = 1 is allowed: these
+ * cameras draw nothing from the seeds.  Nothing but ao_out is written.  A tile's AO equals the same rows of the frame's when its seeds carry the
+ * global ids (mirt_seed_fill with first = row0 * width * rpp).
+ * CHECKS, all before anything is queued; nothing is written when one fails, and the context works afterwards.  MIRT_E_ARG: mirt_view_rays's
+ * descriptor checks, a wrong struct_size in any of the three descriptors, samples 0 or above MIRT_AO_MAX_SAMPLES, radius NaN or <= 0 (+inf is
+ * allowed), bias negative, NaN or infinite, NULL seeds or ao_out, ao_out whose bytes meet the seeds' or a geometry buffer's, the mesh count rule
+ * of mirt_trace_radiance, a call while capturing.  MIRT_E_RANGE: seeds shorter than the tile's rays x 4 B, ao_out shorter than the tile's
+ * pixels x 8 B.  MIRT_E_DATA: a cell table that fails validation.  MIRT_E_HANDLE: a bad context or buffer.  A held command stream is flushed
+ * first; wrapped geometry is re-validated as for a pass.
+ * KERNEL (csrc/pt_kernels_rays.hip k_viewAo; the argument rules csrc/pt_view_plan.hpp view_check_ao): one lane per pixel walking its samples in
+ * order -- by default the optimistic / exact pair PER PIXEL, a bit per pixel; mirt_ctx_set_exact_only is honoured.  mirt_view_ao_deferred: the
+ * pixels the last mirt_view_ao re-ran in the exact kernel, counted when asked, like mirt_ao_deferred.  Not built: AO folded into the frame's own
+ * launch, graph capture.  MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
+MIRT_API int mirt_view_ao(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, const mirt_ao_desc* ao, mirt_buf* seeds, mirt_buf* ao_out);
+MIRT_API int mirt_view_ao_deferred(mirt_ctx* ctx, uint64_t* pixels);
 /* Edge-avoiding A-TROUS FILTER of a few-rays-per-pixel frame, guided by the first-hit guide buffers: `radiance` as a pass writes it (un-scaled
  * sums), `normal_hits` and `albedo_depth` as mirt_render_guides writes them, all float4 per pixel of a width x height image -- a whole frame, or a
  * gathered one.  Everything stays on the device; the working images live in the context's scratch buffer.
