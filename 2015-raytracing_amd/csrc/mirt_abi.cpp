@@ -54,6 +54,18 @@ bool live_is(const void* p, HandleKind k) {
     return it != g_live.end() && it->second == k;
 }
 
+// The bit mask of an optimistic / exact pair, an allocation of the context: [count, cursor, pad, pad | mask words...].  The optimistic kernel sets
+// the bit of what it hands over, the exact kernel walks the bits on the device, and the counter is taken from them when it is asked for.
+struct DeferMask {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    uint32_t words = 0;   // mask words the last call used (0: it ran the exact kernel only, or queued nothing)
+    uint32_t unit = 1;    // what a bit stands for in the counter: 1 sample, ray or pixel, or 256 where a bit is a block of 256 samples
+    static size_t bytes_for(uint32_t words) { return 16 + (size_t)words * 4; }
+    uint32_t* counters() const { return (uint32_t*)ptr; }
+    uint32_t* bits() const { return (uint32_t*)ptr + 4; }
+};
+
 }  // namespace
 
 struct mirt_graph;
@@ -70,27 +82,11 @@ struct mirt_ctx {
     void* scratch = nullptr;  // lens draws of the rpp==1 mode
     size_t scratch_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    void* defer = nullptr;        // optimistic pass: [count, cursor, pad, pad | mask words...]
-    size_t defer_bytes = 0;
-    uint32_t defer_words = 0;     // mask words the last mirt_render_pass used (0: it ran the exact kernel only)
-    uint32_t defer_unit = 1;      // samples per mask bit: 1, or 256 when that pass resolved its pixels itself (a bit per block)
-    void* guide_mask = nullptr;   // mirt_render_guides, optimistic pair: a bit per pixel of the tile (its own allocation: the pass's mask and what
-    size_t guide_mask_bytes = 0;  // mirt_pass_deferred reports of it stay as the last pass left them)
-    void* ray_defer = nullptr;    // mirt_trace_closest / mirt_trace_occluded, optimistic pair: [count, pad, pad, pad | a bit per ray], its own allocation too
-    size_t ray_defer_bytes = 0;
-    uint32_t ray_defer_words = 0; // mask words the last trace call used (0: it ran the exact kernel only, or queued nothing)
-    void* ao_defer = nullptr;     // mirt_render_ao, optimistic pair: [count, pad, pad, pad | a bit per pixel of the tile], its own allocation too
-    size_t ao_defer_bytes = 0;
-    uint32_t ao_defer_words = 0;  // mask words the last mirt_render_ao used (0: it ran the exact kernel only)
-    void* rad_defer = nullptr;    // mirt_trace_radiance, optimistic pair: [count, pad, pad, pad | a bit per ray], its own allocation too
-    size_t rad_defer_bytes = 0;
-    uint32_t rad_defer_words = 0; // mask words the last mirt_trace_radiance used (0: it ran the exact kernel only, or queued nothing)
-    void* view_defer = nullptr;   // mirt_render_view, optimistic pair: [count, pad, pad, pad | a bit per BLOCK of 256 rays], its own allocation too
-    size_t view_defer_bytes = 0;
-    uint32_t view_defer_words = 0; // mask words the last mirt_render_view used (0: it ran the exact kernel only)
-    void* view_ao_defer = nullptr;   // mirt_view_ao, optimistic pair: [count, pad, pad, pad | a bit per pixel of the tile], its own allocation too
-    size_t view_ao_defer_bytes = 0;
-    uint32_t view_ao_defer_words = 0; // mask words the last mirt_view_ao used (0: it ran the exact kernel only)
+    // One mask per family of calls, because the counter of one call survives calls of every other kind (mirt_pass_deferred after a mirt_render_ao is
+    // still the pass's): the pass (a bit per sample, or per block of 256 where it resolves its own pixels), the guides of both cameras (a bit per pixel;
+    // no counter), mirt_trace_closest / mirt_trace_occluded (per ray), mirt_render_ao (per pixel), mirt_trace_radiance (per ray), mirt_render_view (per
+    // block of 256 rays) and mirt_view_ao (per pixel).
+    DeferMask pass_mask, guide_mask, ray_mask, ao_mask, rad_mask, view_mask, view_ao_mask;
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     int force_exact = 0;          // mirt_ctx_set_exact_only: 1 = skip the optimistic kernel, run every sample through the exact one
@@ -190,6 +186,14 @@ int fail(mirt_ctx* ctx, int code, const char* fmt, ...) {
 #define NOT_WHILE_CAPTURING(ctx, what) \
     do { if ((ctx)->capturing) return fail((ctx), MIRT_E_ARG, "%s is not possible inside mirt_capture_begin/end: run the sequence once before recording it", (what)); } while (0)
 
+// The prologue of an entry point that works on the stream and cannot be recorded: a live context, the held-back enqueues run, no recording open.
+#define ENTRY_PROLOGUE(ctx, fn)                                                                    \
+    do {                                                                                           \
+        if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", (fn));      \
+        FLUSH_PENDING(ctx);                                                                        \
+        NOT_WHILE_CAPTURING(ctx, (fn));                                                            \
+    } while (0)
+
 // A recording captures raw device pointers.  Every buffer a recorded launch touches is pinned: (handle, allocation uid), plus --
 // `content` -- the version of its contents and the generation of its prepared copy when the launch relies on host-side
 // validation or preparation of those contents (cell-offset tables, triangle positions).
@@ -207,6 +211,13 @@ int need(mirt_ctx* ctx, const char* what, const mirt_buf* b, uint64_t bytes) {
         return fail(ctx, MIRT_E_RANGE, "%s: buffer holds %zu bytes, launch needs %llu", what, b->bytes, (unsigned long long)bytes);
     pin(ctx, b, false);
     return MIRT_OK;
+}
+
+// The same with the label "fn label" (the bare label where fn is nullptr), put together only when the check fails: a successful call formats and
+// allocates nothing.
+int need(mirt_ctx* ctx, const char* fn, const char* label, const mirt_buf* b, uint64_t bytes) {
+    if (live_has(b) && b->ctx == ctx && (uint64_t)b->bytes >= bytes) { pin(ctx, b, false); return MIRT_OK; }
+    return need(ctx, fn ? (std::string(fn) + " " + label).c_str() : label, b, bytes);
 }
 
 // Checks a cell-offset table (uint[n^3+1], non-decreasing) and that the primitive arrays hold
@@ -284,15 +295,57 @@ int ensure_scratch(mirt_ctx* ctx, size_t bytes) {
     return MIRT_OK;
 }
 
-// The bit mask of an optimistic / exact pair (the pass's, the guides', the ray queries': an allocation of the context each): grown to need_bytes
-// where it is smaller, and those bytes cleared on the stream, ahead of the pair.
-int grow_and_clear(mirt_ctx* ctx, void*& ptr, size_t& have, size_t need_bytes) {
-    if (have < need_bytes) {
-        if (ptr) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ptr)); ptr = nullptr; have = 0; }
-        HIPCHK(ctx, hipMalloc(&ptr, need_bytes));
-        have = need_bytes;
+// A mask grown to its header and `words` mask words where it is smaller, and those bytes cleared on the stream, ahead of the pair.
+int grow_and_clear(mirt_ctx* ctx, DeferMask& m, uint32_t words) {
+    const size_t need_bytes = DeferMask::bytes_for(words);
+    if (m.bytes < need_bytes) {
+        if (m.ptr) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(m.ptr)); m.ptr = nullptr; m.bytes = 0; }
+        HIPCHK(ctx, hipMalloc(&m.ptr, need_bytes));
+        m.bytes = need_bytes;
     }
-    HIPCHK(ctx, hipMemsetAsync(ptr, 0, need_bytes, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(m.ptr, 0, need_bytes, ctx->stream));
+    return MIRT_OK;
+}
+
+// Whether a call runs the optimistic / exact pair: the optimistic kernels are built, the context does not force the exact one, and every set of
+// the call passes the geometry-side guard (pt_set_guard.hpp).
+bool optimistic(const mirt_ctx* ctx, const pt::FusedArgs& A) { return pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A); }
+
+// The launches of a call that is one launch: launch(optimistic, mask_out, mask_in).  The pair -- the optimistic kernel writing the cleared mask, then
+// the exact kernel over its bits, queued without a host round trip -- or the exact kernel alone; `m` remembers what the counter needs.
+template <class Launch>
+int queue_pair(mirt_ctx* ctx, DeferMask& m, const pt::FusedArgs& A, uint32_t words, uint32_t unit, Launch launch) {
+    m.words = 0;
+    if (!optimistic(ctx, A)) { launch(false, nullptr, nullptr); return MIRT_OK; }
+    if (int rc = grow_and_clear(ctx, m, words)) return rc;
+    launch(true, m.bits(), nullptr);
+    launch(false, nullptr, m.bits());
+    m.words = words;
+    m.unit = unit;
+    return MIRT_OK;
+}
+
+// What the exact kernel redid in the last call on `m`, counted on demand (one small launch and a stream sync): the mask of that call is still in
+// place, the next one clears it.
+int count_deferred(mirt_ctx* ctx, const char* fn, const DeferMask& m, uint64_t* out) {
+    if (!out) return fail(ctx, MIRT_E_ARG, "%s: null output", fn);
+    *out = 0;
+    if (!m.words) return MIRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemsetAsync(m.counters(), 0, 16, ctx->stream));
+    pt::launch_deferCount(ctx->stream, m.bits(), m.words, m.counters());
+    uint32_t count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&count, m.counters(), 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out = (uint64_t)count * m.unit;
+    return MIRT_OK;
+}
+
+// The limits of a descriptor's light and mesh arrays (with_lights false: the call reads no light).  arrays: how the message names them.
+int check_desc_arrays(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bool with_lights, const char* arrays) {
+    if (with_lights && d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
+    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
+    if ((with_lights && d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null %s array", fn, arrays);
     return MIRT_OK;
 }
 
@@ -302,6 +355,46 @@ void add_geometry_ranges(std::vector<pt::PostRange>& in, const mirt_pass_desc* d
     const auto add_grid = [&in](const mirt_grid* g) { if (g) { add_range(in, g->prims); add_range(in, g->normals); add_range(in, g->matid); add_range(in, g->cell_offsets); } };
     add_grid(d->spheres); add_grid(d->triangles);
     for (uint32_t m = 0; m < d->n_meshes; ++m) add_grid(&d->meshes[m]);
+}
+
+// A buffer of a call: need()'s label, the handle (nullptr: not given), the bytes the call takes of it, and whether it is written.  BUF_IN_WHOLE: an
+// input that no output may meet anywhere, not only in the bytes the call reads.
+enum BufRole : uint8_t { BUF_OUT, BUF_IN, BUF_IN_WHOLE };
+struct CallBuf { const char* label; mirt_buf* buf; uint64_t bytes; BufRole role = BUF_OUT; };
+
+// What a call on a descriptor's geometry checks of its buffers before anything is queued, in this order: every buffer given is live, this context's
+// and large enough (need(fn, label)); with_material, d->material holds an entry; then an output is read by nobody and no input is written -- no
+// output's bytes meet an input's, the material's or a geometry buffer's (message out_in, "%s" being fn), nor another output's (message outs; a call
+// with one output has none).  out_in == nullptr: the call has no aliasing rule.
+template <size_t N>
+int check_call_buffers(mirt_ctx* ctx, const char* fn, const CallBuf (&b)[N], const mirt_pass_desc* d, bool with_material, const char* out_in, const char* outs) {
+    std::vector<pt::PostRange> in;
+    pt::PostRange out[N];
+    size_t n_out = 0;
+    for (const CallBuf& c : b) {
+        if (!c.buf) continue;
+        if (int rc = need(ctx, fn, c.label, c.buf, c.bytes)) return rc;
+        const pt::PostRange r = {(uint64_t)(uintptr_t)c.buf->ptr, c.role == BUF_IN_WHOLE ? (uint64_t)c.buf->bytes : c.bytes, true};
+        if (c.role == BUF_OUT) out[n_out++] = r;
+        else in.push_back(r);
+    }
+    if (with_material) {
+        if (int rc = need(ctx, "material", d->material, 16)) return rc;
+        add_range(in, d->material);
+    }
+    if (!out_in) return MIRT_OK;
+    add_geometry_ranges(in, d);
+    const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, n_out);
+    if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, out_in, fn);
+    if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, outs, fn);
+    return MIRT_OK;
+}
+// After the launches: their error, and the outputs given have new contents.
+int finish_call(mirt_ctx* ctx, const CallBuf* b, size_t n) {
+    HIPCHK(ctx, hipGetLastError());
+    for (size_t i = 0; i < n; ++i)
+        if (b[i].buf && b[i].role == BUF_OUT) b[i].buf->version++;
+    return MIRT_OK;
 }
 
 // release paths shared by the public entry points and by mirt_ctx_destroy's reaping of leftovers
@@ -398,13 +491,8 @@ static int destroy_ctx(mirt_ctx* ctx) {
     while (!ctx->kernels.empty()) free_kernel(*ctx->kernels.begin(), true);
     while (!ctx->bufs.empty()) free_buf(*ctx->bufs.begin(), true);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->defer) (void)hipFree(ctx->defer);
-    if (ctx->guide_mask) (void)hipFree(ctx->guide_mask);
-    if (ctx->ray_defer) (void)hipFree(ctx->ray_defer);
-    if (ctx->ao_defer) (void)hipFree(ctx->ao_defer);
-    if (ctx->rad_defer) (void)hipFree(ctx->rad_defer);
-    if (ctx->view_defer) (void)hipFree(ctx->view_defer);
-    if (ctx->view_ao_defer) (void)hipFree(ctx->view_ao_defer);
+    for (DeferMask* m : {&ctx->pass_mask, &ctx->guide_mask, &ctx->ray_mask, &ctx->ao_mask, &ctx->rad_mask, &ctx->view_mask, &ctx->view_ao_mask})
+        if (m->ptr) (void)hipFree(m->ptr);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1316,9 +1404,7 @@ static int pass_setup(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, bo
         if (kk * kk != d->rays_per_pixel)
             return fail(ctx, MIRT_E_ARG, "%s: rays_per_pixel %u is not a square (the lens grid is k x k, A10 code.js:540)", fn, d->rays_per_pixel);
     }
-    if (!guides && d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
-    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
-    if ((!guides && d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
+    if (int rc = check_desc_arrays(ctx, fn, d, !guides, "light/mesh")) return rc;
     if (!guides && !d->pass_index) return fail(ctx, MIRT_E_ARG, "%s: pass_index is 1-based", fn);
     const uint32_t cols = f2u_host(d->cam[14]), rows = f2u_host(d->cam[15]);
     if (cols != d->width || rows != d->height) return fail(ctx, MIRT_E_ARG, "%s: camera says %ux%u, descriptor %ux%u", fn, cols, rows, d->width, d->height);
@@ -1384,33 +1470,18 @@ static int fill_sets(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, pt:
 // The guide launches of an already validated tile: the optimistic / exact pair of one lane per pixel, or the exact kernel alone.
 static int queue_guides(mirt_ctx* ctx, const pt::FusedArgs& A, void* nh, void* ad) {
     const uint64_t npix = (uint64_t)A.nrows * A.width;
-    const bool optimistic = pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A);
-    if (optimistic) {
-        const int rc = grow_and_clear(ctx, ctx->guide_mask, ctx->guide_mask_bytes, (size_t)((npix + 31u) / 32u) * 4u);
-        if (rc) return rc;
-        pt::launch_guides(ctx->stream, A, true, nh, ad, (uint32_t*)ctx->guide_mask, nullptr);
-        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, (const uint32_t*)ctx->guide_mask);
-    } else {
-        pt::launch_guides(ctx->stream, A, false, nh, ad, nullptr, nullptr);
-    }
-    return MIRT_OK;
+    return queue_pair(ctx, ctx->guide_mask, A, (uint32_t)((npix + 31u) / 32u), 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_guides(ctx->stream, A, fast, nh, ad, mask_out, mask_in);
+    });
 }
 
 // mirt_render_first_pass_guided's and mirt_render_passes_guided's own buffer rules (`fn`: which), after the pass's: each guide given holds the tile's pixels x 16 B (MIRT_E_RANGE), and its bytes
 // meet those of no buffer of the descriptor nor the other guide's (MIRT_E_ARG) -- the pass and the guides are written by the same launches.
+// (The pass has checked the descriptor's own buffers: nothing more is asked of them here, and they count whole.)
 static int guided_check_buffers(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, mirt_buf* nh, mirt_buf* ad, uint64_t npix) {
-    int rc;
-    const std::string nh_name = std::string(fn) + " normal_hits", ad_name = std::string(fn) + " albedo_depth";
-    if (nh && (rc = need(ctx, nh_name.c_str(), nh, npix * 16))) return rc;
-    if (ad && (rc = need(ctx, ad_name.c_str(), ad, npix * 16))) return rc;
-    std::vector<pt::PostRange> in;
-    for (const mirt_buf* b : {d->seeds, d->acu, d->pixel, d->radiance, d->material}) add_range(in, b);
-    add_geometry_ranges(in, d);
-    const pt::PostRange out[2] = {{nh ? (uint64_t)(uintptr_t)nh->ptr : 0u, npix * 16, nh != nullptr}, {ad ? (uint64_t)(uintptr_t)ad->ptr : 0u, npix * 16, ad != nullptr}};
-    const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 2);
-    if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: a guide buffer aliases a buffer of the descriptor", fn);
-    if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: normal_hits aliases albedo_depth", fn);
-    return MIRT_OK;
+    const CallBuf b[6] = {{"normal_hits", nh, npix * 16}, {"albedo_depth", ad, npix * 16}, {"seeds", d->seeds, 0, BUF_IN_WHOLE}, {"acu", d->acu, 0, BUF_IN_WHOLE},
+                          {"pixel", d->pixel, 0, BUF_IN_WHOLE}, {"radiance", d->radiance, 0, BUF_IN_WHOLE}};
+    return check_call_buffers(ctx, fn, b, d, true, "%s: a guide buffer aliases a buffer of the descriptor", "%s: normal_hits aliases albedo_depth");
 }
 // MIRT_GUIDED_PASS=0: mirt_render_first_pass_guided and mirt_render_passes_guided always queue the pass and then the guide launches -- an A/B and test switch, read per call
 static bool guided_pass_enabled() { const char* e = getenv("MIRT_GUIDED_PASS"); return !(e && e[0] == '0'); }
@@ -1479,20 +1550,18 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
         pt::launch_lensDraws(ctx->stream, A.seeds, scratch + plan.lens.off, d->width, d->height, d->width, d->height, d->row0, nrows);
     }
     if (ctx->profiling && !ctx->capturing && o.mark_start) HIPCHK(ctx, hipEventRecord(ctx->pe[0], ctx->stream));
-    const bool optimistic = pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A);
-    uint32_t* mask = nullptr;
-    if (optimistic) {
+    const bool pair = optimistic(ctx, A);
+    DeferMask& m = ctx->pass_mask;
+    if (pair) {
         // optimistic kernel (exact cheap divisions inside their window) + exact kernel over the samples that left the window:
         // the second launch walks the first one's bit mask on the device, so the pair is queued without a host round trip
         // one bit per sample -- or, resolving in the pass, per block of 256 samples (pt_kernels_fused.hip)
-        const size_t need_bytes = 16 + (size_t)plan.mask_words * 4;
-        if (ctx->defer_bytes < need_bytes) {   // a recording holds the mask's address: it cannot grow inside one, and a graph recorded before is stale
+        if (m.bytes < DeferMask::bytes_for(plan.mask_words)) {   // a recording holds the mask's address: it cannot grow inside one, and a graph recorded before is stale
             NOT_WHILE_CAPTURING(ctx, "growing the deferred-sample mask");
             ctx->defer_gen++;
         }
         if (ctx->capturing) ctx->cap_defer = true;
-        if ((rc = grow_and_clear(ctx, ctx->defer, ctx->defer_bytes, need_bytes))) return rc;
-        mask = (uint32_t*)ctx->defer + 4;
+        if ((rc = grow_and_clear(ctx, m, plan.mask_words))) return rc;
     }
     // One launch -- optimistic: one pair of launches -- per segment of the plan, in ray order, each on its own region of the mask; the redo launch of
     // a segment runs before the next segment's launches read the sums it leaves (stream order).  A pass that does not resolve is one segment.
@@ -1506,15 +1575,15 @@ static int render_pass_impl(mirt_ctx* ctx, const mirt_pass_desc* d, const PassOp
             A.radiance = carry[seg.carry_write];
             A.carry = carry[seg.carry_read];
         }
-        if (optimistic) {
-            pt::launch_fused(ctx->stream, A, true, mask + seg.mask_first, nullptr, 0);
-            pt::launch_fused(ctx->stream, A, false, nullptr, mask + seg.mask_first, seg.mask_words);
+        if (pair) {
+            pt::launch_fused(ctx->stream, A, true, m.bits() + seg.mask_first, nullptr, 0);
+            pt::launch_fused(ctx->stream, A, false, nullptr, m.bits() + seg.mask_first, seg.mask_words);
         } else {
             pt::launch_fused(ctx->stream, A, false, nullptr, nullptr, 0);
         }
     }
-    ctx->defer_words = optimistic ? plan.mask_words : 0u;
-    if (optimistic) ctx->defer_unit = plan.mask_unit;
+    m.words = pair ? plan.mask_words : 0u;
+    if (pair) m.unit = plan.mask_unit;
     if (ctx->profiling && !ctx->capturing) HIPCHK(ctx, hipEventRecord(ctx->pe[1], ctx->stream));
     if (!plan.resolves && want_out) pt::launch_copyToPixel(ctx->stream, pixel_ptr, A.acu, res_m, (uint32_t)npix, A.rpp, (uint32_t)npix, radiance_ptr);
     if (ctx->profiling && !ctx->capturing) { HIPCHK(ctx, hipEventRecord(ctx->pe[2], ctx->stream)); ctx->pe_valid = true; }
@@ -1538,9 +1607,7 @@ int mirt_render_first_pass(mirt_ctx* ctx, const mirt_pass_desc* d) try {
 // mirt_render_first_pass + mirt_render_guides in one call: the checks of both before anything is queued, then -- where the plan allows
 // (pt_pass_plan.hpp fused_guides_in_pass) -- the pass's own launches write the guides (k_fusedPass GUIDES), elsewhere the guide launches follow.
 int mirt_render_first_pass_guided(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_first_pass_guided: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_render_first_pass_guided");
+    ENTRY_PROLOGUE(ctx, "mirt_render_first_pass_guided");
     if (!normal_hits && !albedo_depth) return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: normal_hits and albedo_depth are both NULL (either may be, not both)");
     if (d && d->struct_size == sizeof(mirt_pass_desc) && d->rays_per_pixel == 1u)
         return fail(ctx, MIRT_E_ARG, "mirt_render_first_pass_guided: rays_per_pixel == 1 draws its lens sample from seeds[col] (A10 code.cl:429); the guides are defined "
@@ -1611,18 +1678,14 @@ static int render_passes_impl(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n
     return MIRT_OK;
 }
 int mirt_render_passes(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes, uint32_t flags) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_passes: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_render_passes");
+    ENTRY_PROLOGUE(ctx, "mirt_render_passes");
     return render_passes_impl(ctx, d, n_passes, flags, nullptr, nullptr);
 } MIRT_CATCH("mirt_render_passes", return MIRT_E_DEVICE)
 // mirt_render_passes + mirt_render_guides in one call: the checks of both before anything is queued, then -- where the plan allows
 // (pt_pass_plan.hpp fused_guides_in_passes) -- the multi-pass launch writes the guides in its first pass (k_fusedPass GUIDES with MULTI), elsewhere
 // the guide launches follow what mirt_render_passes queues.
 int mirt_render_passes_guided(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n_passes, uint32_t flags, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_passes_guided: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_render_passes_guided");
+    ENTRY_PROLOGUE(ctx, "mirt_render_passes_guided");
     if (!normal_hits && !albedo_depth) return fail(ctx, MIRT_E_ARG, "mirt_render_passes_guided: normal_hits and albedo_depth are both NULL (either may be, not both)");
     if (d && d->struct_size == sizeof(mirt_pass_desc) && d->rays_per_pixel == 1u)
         return fail(ctx, MIRT_E_ARG, "mirt_render_passes_guided: rays_per_pixel == 1 draws its lens sample from seeds[col] (A10 code.cl:429); the guides are defined "
@@ -1633,9 +1696,7 @@ int mirt_render_passes_guided(mirt_ctx* ctx, const mirt_pass_desc* d, uint32_t n
 // First-hit guide buffers of the tile (pt_kernels_guides.hip): the descriptor's geometry through the checks of mirt_render_pass, then one launch
 // -- or the optimistic / exact pair -- of one lane per pixel.  Nothing but the two outputs is written.
 int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_guides: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_render_guides");
+    ENTRY_PROLOGUE(ctx, "mirt_render_guides");
     if (!normal_hits && !albedo_depth) return fail(ctx, MIRT_E_ARG, "mirt_render_guides: normal_hits and albedo_depth are both NULL (either may be, not both)");
     if (d && d->struct_size == sizeof(mirt_pass_desc) && d->rays_per_pixel == 1u)
         return fail(ctx, MIRT_E_ARG, "mirt_render_guides: rays_per_pixel == 1 draws its lens sample from seeds[col] (A10 code.cl:429), so its guides would change "
@@ -1644,21 +1705,16 @@ int mirt_render_guides(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* normal_
     int rc;
     if ((rc = pass_setup(ctx, "mirt_render_guides", d, true, A))) return rc;
     const uint64_t npix = (uint64_t)A.nrows * A.width;
-    if (normal_hits && (rc = need(ctx, "normal_hits", normal_hits, npix * 16))) return rc;
-    if (albedo_depth && (rc = need(ctx, "albedo_depth", albedo_depth, npix * 16))) return rc;
+    const CallBuf io[2] = {{"normal_hits", normal_hits, npix * 16}, {"albedo_depth", albedo_depth, npix * 16}};
+    if ((rc = check_call_buffers(ctx, nullptr, io, d, false, nullptr, nullptr))) return rc;   // (bare labels, and no aliasing rule: the call never had one)
     if ((rc = queue_guides(ctx, A, normal_hits ? normal_hits->ptr : nullptr, albedo_depth ? albedo_depth->ptr : nullptr))) return rc;
-    HIPCHK(ctx, hipGetLastError());
-    if (normal_hits) normal_hits->version++;
-    if (albedo_depth) albedo_depth->version++;
-    return MIRT_OK;
+    return finish_call(ctx, io, 2);
 } MIRT_CATCH("mirt_render_guides", return MIRT_E_DEVICE)
 
 // Ambient occlusion of the first hit (pt_kernels_rays.hip k_ao): the guides' checks without the material, the call's own, then one launch -- or the
 // optimistic / exact pair, per pixel -- of one lane per pixel.  Every check comes before anything is queued; nothing but ao_out is written.
 int mirt_render_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_ao_desc* ao, mirt_buf* ao_out) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_render_ao: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_render_ao");
+    ENTRY_PROLOGUE(ctx, "mirt_render_ao");
     if (!ao || ao->struct_size != sizeof(mirt_ao_desc)) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: AO descriptor size mismatch");
     if (!ao->samples || ao->samples > MIRT_AO_MAX_SAMPLES) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: samples %u outside 1..%u", ao->samples, MIRT_AO_MAX_SAMPLES);
     if (!(ao->radius > 0.0f)) return fail(ctx, MIRT_E_ARG, "mirt_render_ao: radius %g is not above 0", (double)ao->radius);
@@ -1675,80 +1731,36 @@ int mirt_render_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_ao_desc* a
     if ((rc = pass_setup(ctx, "mirt_render_ao", d, true, A, false))) return rc;
     const uint64_t npix = (uint64_t)A.nrows * A.width;
     const uint64_t nrays = npix * A.rpp;
-    if ((rc = need(ctx, "mirt_render_ao seeds", d->seeds, nrays * 4))) return rc;
-    if ((rc = need(ctx, "mirt_render_ao ao_out", ao_out, npix * 8))) return rc;
-    {   // the output is read by nobody and no input is written: the bytes the call writes, against the seeds' and the geometry's buffers whole
-        std::vector<pt::PostRange> in;
-        add_range(in, d->seeds);
-        add_geometry_ranges(in, d);
-        const pt::PostRange out[1] = {{(uint64_t)(uintptr_t)ao_out->ptr, npix * 8, true}};
-        if (pt::post_alias(in.data(), in.size(), out, 1) != pt::POST_ALIAS_NONE)
-            return fail(ctx, MIRT_E_ARG, "mirt_render_ao: ao_out's bytes meet the seeds' or a geometry buffer's");
-    }
+    // the output is read by nobody and no input is written: the bytes the call writes, against the seeds' and the geometry's buffers whole
+    const CallBuf io[2] = {{"seeds", d->seeds, nrays * 4, BUF_IN_WHOLE}, {"ao_out", ao_out, npix * 8}};
+    if ((rc = check_call_buffers(ctx, "mirt_render_ao", io, d, false, "%s: ao_out's bytes meet the seeds' or a geometry buffer's", nullptr))) return rc;
     A.seeds = (int32_t*)d->seeds->ptr;
-    ctx->ao_defer_words = 0;
-    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
-        const uint32_t words = (uint32_t)((npix + 31u) / 32u);
-        if ((rc = grow_and_clear(ctx, ctx->ao_defer, ctx->ao_defer_bytes, 16u + (size_t)words * 4u))) return rc;
-        uint32_t* const mask = (uint32_t*)ctx->ao_defer + 4;
-        pt::launch_ao(ctx->stream, A, true, ao->samples, ao->radius, ao->bias, ao_out->ptr, mask, nullptr);
-        pt::launch_ao(ctx->stream, A, false, ao->samples, ao->radius, ao->bias, ao_out->ptr, nullptr, mask);
-        ctx->ao_defer_words = words;
-    } else {
-        pt::launch_ao(ctx->stream, A, false, ao->samples, ao->radius, ao->bias, ao_out->ptr, nullptr, nullptr);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    ao_out->version++;
-    return MIRT_OK;
+    rc = queue_pair(ctx, ctx->ao_mask, A, (uint32_t)((npix + 31u) / 32u), 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_ao(ctx->stream, A, fast, ao->samples, ao->radius, ao->bias, ao_out->ptr, mask_out, mask_in);
+    });
+    return rc ? rc : finish_call(ctx, io, 2);
 } MIRT_CATCH("mirt_render_ao", return MIRT_E_DEVICE)
 
 int mirt_ao_deferred(mirt_ctx* ctx, uint64_t* pixels) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ao_deferred: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_ao_deferred");
-    if (!pixels) return fail(ctx, MIRT_E_ARG, "mirt_ao_deferred: null output");
-    *pixels = 0;
-    if (!ctx->ao_defer_words) return MIRT_OK;
-    // counted on demand: the mask of the last mirt_render_ao is still in place (the next one clears it)
-    uint32_t* counters = (uint32_t*)ctx->ao_defer;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
-    pt::launch_deferCount(ctx->stream, counters + 4, ctx->ao_defer_words, counters);
-    uint32_t count = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *pixels = count;
-    return MIRT_OK;
+    ENTRY_PROLOGUE(ctx, "mirt_ao_deferred");
+    return count_deferred(ctx, "mirt_ao_deferred", ctx->ao_mask, pixels);
 } MIRT_CATCH("mirt_ao_deferred", return MIRT_E_DEVICE)
 
 // ---- ray queries (pt_kernels_rays.hip): mirt_trace_closest and mirt_trace_occluded.  Every check comes before anything is queued; then one launch
 // -- or the optimistic / exact pair, per ray -- of one lane per ray.  Nothing but the outputs is written.
 static int trace_impl(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, mirt_buf* rays, uint64_t count, mirt_buf* hits, mirt_buf* sets, mirt_buf* occluded, bool any) {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, fn);
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (count > 0xFFFFFF00ull) return fail(ctx, MIRT_E_ARG, "%s: %llu rays in one call (the kernels index a call's rays with 32 bits); split the batch", fn, (unsigned long long)count);
     if (!any && !hits && !sets) return fail(ctx, MIRT_E_ARG, "%s: hits and sets are both NULL (either may be, not both)", fn);
     if (any && !occluded) return fail(ctx, MIRT_E_ARG, "%s: occluded is NULL", fn);
-    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
-    if (d->n_meshes && !d->meshes) return fail(ctx, MIRT_E_ARG, "%s: null mesh array", fn);
     int rc;
-    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[4] = {{"rays", rays, count * 32}, {"hits", hits, count * 32}, {"sets", sets, count * 4}, {"occluded", occluded, count}};
+    if ((rc = check_desc_arrays(ctx, fn, d, false, "mesh"))) return rc;
     if (!rays) return fail(ctx, MIRT_E_HANDLE, "%s: rays is NULL", fn);
-    for (const auto& b : io)
-        if (b.buf && (rc = need(ctx, (std::string(fn) + " " + b.label).c_str(), b.buf, b.bytes))) return rc;
-    {   // an output is read by nobody and no input is written: the bytes the call touches, and the geometry's buffers whole
-        std::vector<pt::PostRange> in;
-        in.push_back({(uint64_t)(uintptr_t)rays->ptr, count * 32, true});
-        add_geometry_ranges(in, d);
-        pt::PostRange out[3];
-        for (int i = 0; i < 3; ++i) out[i] = {io[i + 1].buf ? (uint64_t)(uintptr_t)io[i + 1].buf->ptr : 0u, io[i + 1].bytes, io[i + 1].buf != nullptr};
-        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 3);
-        if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: an output's bytes meet the rays' or a geometry buffer's", fn);
-        if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: hits aliases sets", fn);
-    }
-    if (!count) return MIRT_OK;
+    // an output is read by nobody and no input is written: the bytes the call touches, and the geometry's buffers whole
+    const CallBuf io[4] = {{"rays", rays, count * 32, BUF_IN}, {"hits", hits, count * 32}, {"sets", sets, count * 4}, {"occluded", occluded, count}};
+    if ((rc = check_call_buffers(ctx, fn, io, d, false, "%s: an output's bytes meet the rays' or a geometry buffer's", "%s: hits aliases sets"))) return rc;
+    if (!count) return MIRT_OK;   // (nothing is queued, and the counter of the last batch stays)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::FusedArgs A;
     memset(&A, 0, sizeof A);
@@ -1756,20 +1768,10 @@ static int trace_impl(mirt_ctx* ctx, const char* fn, const mirt_pass_desc* d, mi
     void* const hp = hits ? hits->ptr : nullptr;
     uint32_t* const sp = sets ? (uint32_t*)sets->ptr : nullptr;
     uint8_t* const op = occluded ? (uint8_t*)occluded->ptr : nullptr;
-    ctx->ray_defer_words = 0;
-    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
-        const uint32_t words = (uint32_t)((count + 31u) / 32u);
-        if ((rc = grow_and_clear(ctx, ctx->ray_defer, ctx->ray_defer_bytes, 16u + (size_t)words * 4u))) return rc;
-        uint32_t* const mask = (uint32_t*)ctx->ray_defer + 4;
-        pt::launch_rays(ctx->stream, A, true, rays->ptr, (uint32_t)count, hp, sp, op, mask, nullptr);
-        pt::launch_rays(ctx->stream, A, false, rays->ptr, (uint32_t)count, hp, sp, op, nullptr, mask);
-        ctx->ray_defer_words = words;
-    } else {
-        pt::launch_rays(ctx->stream, A, false, rays->ptr, (uint32_t)count, hp, sp, op, nullptr, nullptr);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    for (int i = 1; i < 4; ++i) if (io[i].buf) io[i].buf->version++;
-    return MIRT_OK;
+    rc = queue_pair(ctx, ctx->ray_mask, A, (uint32_t)((count + 31u) / 32u), 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_rays(ctx->stream, A, fast, rays->ptr, (uint32_t)count, hp, sp, op, mask_out, mask_in);
+    });
+    return rc ? rc : finish_call(ctx, io, 4);
 }
 
 int mirt_trace_closest(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* rays, uint64_t count, mirt_buf* hits, mirt_buf* sets) try {
@@ -1781,31 +1783,15 @@ int mirt_trace_occluded(mirt_ctx* ctx, const mirt_pass_desc* d, mirt_buf* rays, 
 } MIRT_CATCH("mirt_trace_occluded", return MIRT_E_DEVICE)
 
 int mirt_trace_deferred(mirt_ctx* ctx, uint64_t* rays) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_trace_deferred: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_trace_deferred");
-    if (!rays) return fail(ctx, MIRT_E_ARG, "mirt_trace_deferred: null output");
-    *rays = 0;
-    if (!ctx->ray_defer_words) return MIRT_OK;
-    // counted on demand: the mask of the last trace call is still in place (the next one clears it)
-    uint32_t* counters = (uint32_t*)ctx->ray_defer;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
-    pt::launch_deferCount(ctx->stream, counters + 4, ctx->ray_defer_words, counters);
-    uint32_t count = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *rays = count;
-    return MIRT_OK;
+    ENTRY_PROLOGUE(ctx, "mirt_trace_deferred");
+    return count_deferred(ctx, "mirt_trace_deferred", ctx->ray_mask, rays);
 } MIRT_CATCH("mirt_trace_deferred", return MIRT_E_DEVICE)
 
 // ---- path radiance of caller-supplied rays (pt_kernels_rays.hip k_traceRadiance): mirt_trace_radiance.  Every check comes before anything is
 // queued; then one launch -- or the optimistic / exact pair, per ray -- of one lane per ray.  Nothing but seeds and radiance is written.
 int mirt_trace_radiance(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_radiance_desc* rd, mirt_buf* rays, uint64_t count, mirt_buf* seeds, mirt_buf* radiance) try {
     const char* const fn = "mirt_trace_radiance";
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, fn);
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (!rd || rd->struct_size != sizeof(mirt_radiance_desc)) return fail(ctx, MIRT_E_ARG, "%s: radiance descriptor size mismatch", fn);
     if (!rd->samples || rd->samples > MIRT_RADIANCE_MAX_SAMPLES) return fail(ctx, MIRT_E_ARG, "%s: samples %u outside 1..%u", fn, rd->samples, MIRT_RADIANCE_MAX_SAMPLES);
@@ -1813,27 +1799,13 @@ int mirt_trace_radiance(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_radia
     if (rd->reserved) return fail(ctx, MIRT_E_ARG, "%s: reserved is %u, not 0", fn, rd->reserved);
     if (count > 0xFFFFFF00ull) return fail(ctx, MIRT_E_ARG, "%s: %llu rays in one call (the kernels index a call's rays with 32 bits); split the batch", fn, (unsigned long long)count);
     if (!seeds || !radiance) return fail(ctx, MIRT_E_ARG, "%s: %s is NULL", fn, seeds ? "radiance" : "seeds");
-    // the pass's own limits and rules for its arrays (pass_setup)
-    if (d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
-    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
-    if ((d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
-    if (!rays) return fail(ctx, MIRT_E_HANDLE, "%s: rays is NULL", fn);
     int rc;
-    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[3] = {{"rays", rays, count * 32}, {"seeds", seeds, count * 4}, {"radiance", radiance, count * 16}};
-    for (const auto& b : io)
-        if ((rc = need(ctx, (std::string(fn) + " " + b.label).c_str(), b.buf, b.bytes))) return rc;
-    if ((rc = need(ctx, "material", d->material, 16))) return rc;
-    {   // seeds and radiance are both written: the bytes the call touches of them, against the rays', the geometry's buffers and the material whole
-        std::vector<pt::PostRange> in;
-        in.push_back({(uint64_t)(uintptr_t)rays->ptr, count * 32, true});
-        add_range(in, d->material);
-        add_geometry_ranges(in, d);
-        const pt::PostRange out[2] = {{(uint64_t)(uintptr_t)seeds->ptr, count * 4, true}, {(uint64_t)(uintptr_t)radiance->ptr, count * 16, true}};
-        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 2);
-        if (alias == pt::POST_ALIAS_OUTPUT_INPUT) return fail(ctx, MIRT_E_ARG, "%s: the seeds' or the radiance's bytes meet the rays', a geometry buffer's or the material's", fn);
-        if (alias == pt::POST_ALIAS_OUTPUTS) return fail(ctx, MIRT_E_ARG, "%s: seeds aliases radiance", fn);
-    }
-    if (!count) return MIRT_OK;
+    if ((rc = check_desc_arrays(ctx, fn, d, true, "light/mesh"))) return rc;
+    if (!rays) return fail(ctx, MIRT_E_HANDLE, "%s: rays is NULL", fn);
+    // seeds and radiance are both written: the bytes the call touches of them, against the rays', the geometry's buffers and the material whole
+    const CallBuf io[3] = {{"rays", rays, count * 32, BUF_IN}, {"seeds", seeds, count * 4}, {"radiance", radiance, count * 16}};
+    if ((rc = check_call_buffers(ctx, fn, io, d, true, "%s: the seeds' or the radiance's bytes meet the rays', a geometry buffer's or the material's", "%s: seeds aliases radiance"))) return rc;
+    if (!count) return MIRT_OK;   // (nothing is queued, and the counter of the last batch stays)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::FusedArgs A;
     memset(&A, 0, sizeof A);
@@ -1841,40 +1813,15 @@ int mirt_trace_radiance(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_radia
     A.n_lights = d->n_lights;
     if ((rc = fill_sets(ctx, fn, d, A))) return rc;
     if ((rc = fill_shading(ctx, d, A, true))) return rc;
-    ctx->rad_defer_words = 0;
-    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
-        const uint32_t words = (uint32_t)((count + 31u) / 32u);
-        if ((rc = grow_and_clear(ctx, ctx->rad_defer, ctx->rad_defer_bytes, 16u + (size_t)words * 4u))) return rc;
-        uint32_t* const mask = (uint32_t*)ctx->rad_defer + 4;
-        pt::launch_radiance(ctx->stream, A, true, rays->ptr, (uint32_t)count, rd->samples, rd->flags, (int32_t*)seeds->ptr, radiance->ptr, mask, nullptr);
-        pt::launch_radiance(ctx->stream, A, false, rays->ptr, (uint32_t)count, rd->samples, rd->flags, (int32_t*)seeds->ptr, radiance->ptr, nullptr, mask);
-        ctx->rad_defer_words = words;
-    } else {
-        pt::launch_radiance(ctx->stream, A, false, rays->ptr, (uint32_t)count, rd->samples, rd->flags, (int32_t*)seeds->ptr, radiance->ptr, nullptr, nullptr);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    seeds->version++;
-    radiance->version++;
-    return MIRT_OK;
+    rc = queue_pair(ctx, ctx->rad_mask, A, (uint32_t)((count + 31u) / 32u), 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_radiance(ctx->stream, A, fast, rays->ptr, (uint32_t)count, rd->samples, rd->flags, (int32_t*)seeds->ptr, radiance->ptr, mask_out, mask_in);
+    });
+    return rc ? rc : finish_call(ctx, io, 3);
 } MIRT_CATCH("mirt_trace_radiance", return MIRT_E_DEVICE)
 
 int mirt_radiance_deferred(mirt_ctx* ctx, uint64_t* rays) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_radiance_deferred: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_radiance_deferred");
-    if (!rays) return fail(ctx, MIRT_E_ARG, "mirt_radiance_deferred: null output");
-    *rays = 0;
-    if (!ctx->rad_defer_words) return MIRT_OK;
-    // counted on demand: the mask of the last mirt_trace_radiance is still in place (the next one clears it)
-    uint32_t* counters = (uint32_t*)ctx->rad_defer;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
-    pt::launch_deferCount(ctx->stream, counters + 4, ctx->rad_defer_words, counters);
-    uint32_t count = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *rays = count;
-    return MIRT_OK;
+    ENTRY_PROLOGUE(ctx, "mirt_radiance_deferred");
+    return count_deferred(ctx, "mirt_radiance_deferred", ctx->rad_mask, rays);
 } MIRT_CATCH("mirt_radiance_deferred", return MIRT_E_DEVICE)
 
 // ---- panoramic, fisheye and orthographic cameras (pt_kernels_rays.hip k_viewRays, k_viewPass): mirt_view_rays, mirt_render_view.  The rules of
@@ -1926,9 +1873,7 @@ static pt::ViewArgs view_args(const pt::ViewDesc& d, const pt::ViewPlan& plan) {
 
 int mirt_view_rays(mirt_ctx* ctx, const mirt_view_desc* vd, mirt_buf* rays) try {
     const char* const fn = "mirt_view_rays";
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, fn);
     if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
     pt::ViewDesc d;
     memcpy(&d, vd, sizeof d);
@@ -1948,15 +1893,9 @@ int mirt_view_rays(mirt_ctx* ctx, const mirt_view_desc* vd, mirt_buf* rays) try 
 // (the mask is mirt_render_guides's allocation: both are a bit per pixel, cleared by the call that uses them).
 static int queue_view_guides(mirt_ctx* ctx, const pt::FusedArgs& A, const pt::ViewArgs& V, const pt::ViewPlan& plan, void* nh, void* ad) {
     const pt::ViewGuidesPlan g = pt::view_guides_plan(plan);
-    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
-        const int rc = grow_and_clear(ctx, ctx->guide_mask, ctx->guide_mask_bytes, (size_t)g.mask_words * 4u);
-        if (rc) return rc;
-        pt::launch_viewGuides(ctx->stream, A, V, g.blocks, true, nh, ad, (uint32_t*)ctx->guide_mask, nullptr);
-        pt::launch_viewGuides(ctx->stream, A, V, g.blocks, false, nh, ad, nullptr, (const uint32_t*)ctx->guide_mask);
-    } else {
-        pt::launch_viewGuides(ctx->stream, A, V, g.blocks, false, nh, ad, nullptr, nullptr);
-    }
-    return MIRT_OK;
+    return queue_pair(ctx, ctx->guide_mask, A, g.mask_words, 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_viewGuides(ctx->stream, A, V, g.blocks, fast, nh, ad, mask_out, mask_in);
+    });
 }
 // MIRT_GUIDED_VIEW=0: mirt_render_view_guided always queues the frame and then the guide launches -- an A/B and test switch, read per call
 static bool guided_view_enabled() { const char* e = getenv("MIRT_GUIDED_VIEW"); return !(e && e[0] == '0'); }
@@ -1965,9 +1904,7 @@ static bool guided_view_enabled() { const char* e = getenv("MIRT_GUIDED_VIEW"); 
 // (all five): one list of checks, every one before anything is queued, then the launches.
 static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guided, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance,
                             mirt_buf* pixel, mirt_buf* normal_hits, mirt_buf* albedo_depth) {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, fn);
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
     pt::ViewDesc v;
@@ -1980,31 +1917,18 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
     if ((rc = view_verdict(ctx, fn, verdict, v))) return rc;
     const pt::ViewPlan plan = pt::view_plan(v);
     // the pass's own limits and rules for its arrays, as mirt_trace_radiance has them (the guides alone read no light)
-    if (frame && d->n_lights > MIRT_MAX_LIGHTS) return fail(ctx, MIRT_E_ARG, "%s: %u lights > %d (enqueue the kernels one by one instead)", fn, d->n_lights, MIRT_MAX_LIGHTS);
-    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
-    if ((frame && d->n_lights && !d->lights) || (d->n_meshes && !d->meshes)) return fail(ctx, MIRT_E_ARG, "%s: null light/mesh array", fn);
-    const struct { const char* label; mirt_buf* buf; uint64_t bytes; } io[5] = {{"seeds", seeds, plan.rays * 4}, {"radiance", radiance, plan.pixels * 16}, {"pixel", pixel, plan.pixels * 4},
-                                                                                 {"normal_hits", normal_hits, plan.pixels * 16}, {"albedo_depth", albedo_depth, plan.pixels * 16}};
-    for (const auto& b : io)
-        if (b.buf && (rc = need(ctx, (std::string(fn) + " " + b.label).c_str(), b.buf, b.bytes))) return rc;
-    if ((rc = need(ctx, "material", d->material, 16))) return rc;
-    {   // everything given is written: the bytes the call touches of them, against each other's, the geometry's buffers and the material whole
-        std::vector<pt::PostRange> in;
-        add_range(in, d->material);
-        add_geometry_ranges(in, d);
-        pt::PostRange out[5];
-        for (int i = 0; i < 5; ++i) out[i] = {io[i].buf ? (uint64_t)(uintptr_t)io[i].buf->ptr : 0u, io[i].bytes, io[i].buf != nullptr};
-        const pt::PostAlias alias = pt::post_alias(in.data(), in.size(), out, 5);
-        // (mirt_render_view's two messages are the ones it had before the guides: that call has none)
-        if (alias == pt::POST_ALIAS_OUTPUT_INPUT)
-            return fail(ctx, MIRT_E_ARG, !frame   ? "%s: a guide's bytes meet a geometry buffer's or the material's"
-                                         : guided ? "%s: the seeds', the radiance's, the pixel's or a guide's bytes meet a geometry buffer's or the material's"
-                                                  : "%s: the seeds', the radiance's or the pixel's bytes meet a geometry buffer's or the material's", fn);
-        if (alias == pt::POST_ALIAS_OUTPUTS)
-            return fail(ctx, MIRT_E_ARG, !frame   ? "%s: normal_hits aliases albedo_depth"
-                                         : guided ? "%s: seeds, radiance, pixel and the guides meet one another"
-                                                  : "%s: seeds, radiance and pixel meet one another", fn);
-    }
+    if ((rc = check_desc_arrays(ctx, fn, d, frame, "light/mesh"))) return rc;
+    // everything given is written: the bytes the call touches of them, against each other's, the geometry's buffers and the material whole
+    // (mirt_render_view's two messages are the ones it had before the guides: that call has none)
+    const CallBuf io[5] = {{"seeds", seeds, plan.rays * 4}, {"radiance", radiance, plan.pixels * 16}, {"pixel", pixel, plan.pixels * 4},
+                           {"normal_hits", normal_hits, plan.pixels * 16}, {"albedo_depth", albedo_depth, plan.pixels * 16}};
+    if ((rc = check_call_buffers(ctx, fn, io, d, true,
+                                 !frame   ? "%s: a guide's bytes meet a geometry buffer's or the material's"
+                                 : guided ? "%s: the seeds', the radiance's, the pixel's or a guide's bytes meet a geometry buffer's or the material's"
+                                          : "%s: the seeds', the radiance's or the pixel's bytes meet a geometry buffer's or the material's",
+                                 !frame   ? "%s: normal_hits aliases albedo_depth"
+                                 : guided ? "%s: seeds, radiance, pixel and the guides meet one another"
+                                          : "%s: seeds, radiance and pixel meet one another"))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::FusedArgs A;
     memset(&A, 0, sizeof A);
@@ -2022,23 +1946,14 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
         const bool in_pass = guided && pt::view_guides_in_pass(plan.rpp, pt::fused_has_grids(A), guided_view_enabled());
         pt::FusedArgs F = A;
         if (in_pass) { F.guide_nh = nhp; F.guide_ad = adp; }
-        ctx->view_defer_words = 0;
-        if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
-            if ((rc = grow_and_clear(ctx, ctx->view_defer, ctx->view_defer_bytes, 16u + (size_t)plan.mask_words * 4u))) return rc;
-            uint32_t* const mask = (uint32_t*)ctx->view_defer + 4;
-            pt::launch_viewPass(ctx->stream, F, V, true, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask, nullptr);
-            pt::launch_viewPass(ctx->stream, F, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, mask);
-            ctx->view_defer_words = plan.mask_words;
-        } else {
-            pt::launch_viewPass(ctx->stream, F, V, false, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, nullptr, nullptr);
-        }
+        rc = queue_pair(ctx, ctx->view_mask, A, plan.mask_words, 256u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {   // a bit is a block of 256 rays
+            pt::launch_viewPass(ctx->stream, F, V, fast, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask_out, mask_in);
+        });
+        if (rc) return rc;
         if (in_pass) ctx->guided_views++;
         else if (guided && (rc = queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;   // everywhere else: exactly what mirt_view_guides queues
     } else if ((rc = queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;
-    HIPCHK(ctx, hipGetLastError());
-    for (const auto& b : io)
-        if (b.buf) b.buf->version++;
-    return MIRT_OK;
+    return finish_call(ctx, io, 5);
 }
 
 int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel) try {
@@ -2073,9 +1988,7 @@ static_assert(sizeof(pt::ViewAoDesc) == sizeof(mirt_ao_desc) && offsetof(pt::Vie
               pt::kViewAoMaxSamples == MIRT_AO_MAX_SAMPLES, "pt_view_plan.hpp restates the header's AO descriptor");
 int mirt_view_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, const mirt_ao_desc* ao, mirt_buf* seeds, mirt_buf* ao_out) try {
     const char* const fn = "mirt_view_ao";
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "%s: unknown context", fn);
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, fn);
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
     if (!ao || ao->struct_size != sizeof(mirt_ao_desc)) return fail(ctx, MIRT_E_ARG, "%s: AO descriptor size mismatch", fn);
@@ -2086,18 +1999,10 @@ int mirt_view_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* v
     int rc;
     if ((rc = view_verdict(ctx, fn, pt::view_check_ao(v, a, seeds != nullptr, ao_out != nullptr), v))) return rc;
     const pt::ViewPlan plan = pt::view_plan(v);
-    if (d->n_meshes > MIRT_MAX_MESHES) return fail(ctx, MIRT_E_ARG, "%s: %u meshes > %d (enqueue the kernels one by one instead)", fn, d->n_meshes, MIRT_MAX_MESHES);
-    if (d->n_meshes && !d->meshes) return fail(ctx, MIRT_E_ARG, "%s: null mesh array", fn);
-    if ((rc = need(ctx, "mirt_view_ao seeds", seeds, plan.rays * 4))) return rc;
-    if ((rc = need(ctx, "mirt_view_ao ao_out", ao_out, plan.pixels * 8))) return rc;
-    {   // the output is read by nobody and no input is written: the bytes the call writes, against the seeds' and the geometry's buffers whole
-        std::vector<pt::PostRange> in;
-        add_range(in, seeds);
-        add_geometry_ranges(in, d);
-        const pt::PostRange out[1] = {{(uint64_t)(uintptr_t)ao_out->ptr, plan.pixels * 8, true}};
-        if (pt::post_alias(in.data(), in.size(), out, 1) != pt::POST_ALIAS_NONE)
-            return fail(ctx, MIRT_E_ARG, "%s: ao_out's bytes meet the seeds' or a geometry buffer's", fn);
-    }
+    if ((rc = check_desc_arrays(ctx, fn, d, false, "mesh"))) return rc;
+    // the output is read by nobody and no input is written: the bytes the call writes, against the seeds' and the geometry's buffers whole
+    const CallBuf io[2] = {{"seeds", seeds, plan.rays * 4, BUF_IN_WHOLE}, {"ao_out", ao_out, plan.pixels * 8}};
+    if ((rc = check_call_buffers(ctx, fn, io, d, false, "%s: ao_out's bytes meet the seeds' or a geometry buffer's", nullptr))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::FusedArgs A;
     memset(&A, 0, sizeof A);
@@ -2105,63 +2010,25 @@ int mirt_view_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* v
     const pt::ViewArgs V = view_args(v, plan);
     const pt::ViewGuidesPlan g = pt::view_guides_plan(plan);
     const int32_t* const sp = (const int32_t*)seeds->ptr;
-    ctx->view_ao_defer_words = 0;
-    if (pt::fused_fast_available() && !ctx->force_exact && pt::all_sets_fast_ok(A)) {
-        if ((rc = grow_and_clear(ctx, ctx->view_ao_defer, ctx->view_ao_defer_bytes, 16u + (size_t)g.mask_words * 4u))) return rc;
-        uint32_t* const mask = (uint32_t*)ctx->view_ao_defer + 4;
-        pt::launch_viewAo(ctx->stream, A, V, g.blocks, true, a.samples, a.radius, a.bias, sp, ao_out->ptr, mask, nullptr);
-        pt::launch_viewAo(ctx->stream, A, V, g.blocks, false, a.samples, a.radius, a.bias, sp, ao_out->ptr, nullptr, mask);
-        ctx->view_ao_defer_words = g.mask_words;
-    } else {
-        pt::launch_viewAo(ctx->stream, A, V, g.blocks, false, a.samples, a.radius, a.bias, sp, ao_out->ptr, nullptr, nullptr);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    ao_out->version++;
-    return MIRT_OK;
+    rc = queue_pair(ctx, ctx->view_ao_mask, A, g.mask_words, 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_viewAo(ctx->stream, A, V, g.blocks, fast, a.samples, a.radius, a.bias, sp, ao_out->ptr, mask_out, mask_in);
+    });
+    return rc ? rc : finish_call(ctx, io, 2);
 } MIRT_CATCH("mirt_view_ao", return MIRT_E_DEVICE)
 
 int mirt_view_ao_deferred(mirt_ctx* ctx, uint64_t* pixels) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_view_ao_deferred: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_view_ao_deferred");
-    if (!pixels) return fail(ctx, MIRT_E_ARG, "mirt_view_ao_deferred: null output");
-    *pixels = 0;
-    if (!ctx->view_ao_defer_words) return MIRT_OK;
-    // counted on demand: the mask of the last mirt_view_ao is still in place (the next one clears it)
-    uint32_t* counters = (uint32_t*)ctx->view_ao_defer;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
-    pt::launch_deferCount(ctx->stream, counters + 4, ctx->view_ao_defer_words, counters);
-    uint32_t count = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *pixels = count;
-    return MIRT_OK;
+    ENTRY_PROLOGUE(ctx, "mirt_view_ao_deferred");
+    return count_deferred(ctx, "mirt_view_ao_deferred", ctx->view_ao_mask, pixels);
 } MIRT_CATCH("mirt_view_ao_deferred", return MIRT_E_DEVICE)
 
 int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_view_deferred: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_view_deferred");
-    if (!rays) return fail(ctx, MIRT_E_ARG, "mirt_view_deferred: null output");
-    *rays = 0;
-    if (!ctx->view_defer_words) return MIRT_OK;
-    // counted on demand: the mask of the last mirt_render_view is still in place (the next one clears it); a bit is a block of 256 rays
-    uint32_t* counters = (uint32_t*)ctx->view_defer;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
-    pt::launch_deferCount(ctx->stream, counters + 4, ctx->view_defer_words, counters);
-    uint32_t count = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *rays = (uint64_t)count * 256u;
-    return MIRT_OK;
+    ENTRY_PROLOGUE(ctx, "mirt_view_deferred");
+    return count_deferred(ctx, "mirt_view_deferred", ctx->view_mask, rays);
 } MIRT_CATCH("mirt_view_deferred", return MIRT_E_DEVICE)
 
 // ---- the post-process stage: mirt_filter_atrous and mirt_upsample_guided.  The argument rules they share are pt_post_check.hpp's (host-only,
-// CPU-tested); here are those rules' messages, `fn` being the entry point's name, and the shared epilogue.
+// CPU-tested); here are those rules' messages, `fn` being the entry point's name.
 static_assert(pt::kPostMaxNormalPowerLog2 == MIRT_FILTER_MAX_NORMAL_POWER_LOG2, "pt_post_check.hpp restates the header's limit");
-struct PostBuf { const char* label; mirt_buf* buf; uint64_t bytes; };   // an image of the call: need()'s label, its buffer, the bytes it takes; buf == nullptr: an output not asked for
 
 static int post_check_extent(mirt_ctx* ctx, const char* fn, uint32_t w, uint32_t h) {
     const pt::PostExtent e = pt::post_extent(w, h);
@@ -2179,7 +2046,7 @@ static int post_check_terms(mirt_ctx* ctx, const char* fn, uint32_t npow, float 
 // twice is refused.  Nothing is formatted or allocated unless a check fails: a caller that times the call times this too.
 extern "C++" {
 template <size_t N>
-int post_check_buffers(mirt_ctx* ctx, const char* fn, const char* first, const PostBuf (&b)[N]) {
+int post_check_buffers(mirt_ctx* ctx, const char* fn, const char* first, const CallBuf (&b)[N]) {
     if (!b[N - 2].buf && !b[N - 1].buf) return fail(ctx, MIRT_E_ARG, "%s: %s and pixel are both NULL (either may be, not both)", fn, first);
     pt::PostRange r[N];
     for (size_t i = 0; i < N; ++i) {
@@ -2194,22 +2061,13 @@ int post_check_buffers(mirt_ctx* ctx, const char* fn, const char* first, const P
     return MIRT_OK;
 }
 }  // extern "C++"
-// after the launches: their error, and the outputs given have new contents
-static int post_finish(mirt_ctx* ctx, const PostBuf* out) {
-    HIPCHK(ctx, hipGetLastError());
-    for (int o = 0; o < 2; ++o)
-        if (out[o].buf) out[o].buf->version++;
-    return MIRT_OK;
-}
 
 // The a-trous filter (pt_kernels_filter.hip; defined in include/mirt.h): every check first, then the prepare launch and one launch per iteration,
 // the last of which writes the outputs.  The two working images and the prepared guide are three float4 arrays of the context's scratch buffer,
 // asked for ONCE (growing the buffer frees the old one: pt_pass_plan.hpp).
 int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* d) try {
     static const char fn[] = "mirt_filter_atrous";
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_filter_atrous: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, "mirt_filter_atrous");
     if (!d || d->struct_size != sizeof(mirt_filter_desc)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: descriptor size mismatch");
     int rc;
     if ((rc = post_check_extent(ctx, fn, d->width, d->height))) return rc;
@@ -2218,7 +2076,7 @@ int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* d) try {
     const uint32_t both = MIRT_FILTER_DIRECT | MIRT_FILTER_TILED;
     if ((d->flags & ~(MIRT_FILTER_DEMODULATE | both)) || (d->flags & both) == both) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous: unknown flags 0x%x (or both structures forced)", d->flags);
     const uint64_t npix = (uint64_t)d->width * d->height;
-    const PostBuf b[5] = {{"mirt_filter_atrous radiance", d->radiance, npix * 16}, {"mirt_filter_atrous normal_hits", d->normal_hits, npix * 16}, {"mirt_filter_atrous albedo_depth", d->albedo_depth, npix * 16},
+    const CallBuf b[5] = {{"mirt_filter_atrous radiance", d->radiance, npix * 16}, {"mirt_filter_atrous normal_hits", d->normal_hits, npix * 16}, {"mirt_filter_atrous albedo_depth", d->albedo_depth, npix * 16},
                           {"mirt_filter_atrous filtered", d->filtered, npix * 16}, {"mirt_filter_atrous pixel", d->pixel, npix * 4}};
     if ((rc = post_check_buffers(ctx, fn, "filtered", b))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2248,15 +2106,13 @@ int mirt_filter_atrous(mirt_ctx* ctx, const mirt_filter_desc* d) try {
         const bool tiled = (d->flags & both) ? (d->flags & MIRT_FILTER_TILED) != 0u : (pt::kFilterTiledSteps >> i & 1u) != 0u;
         pt::launch_filterStep(ctx->stream, A, i & 1u, i, A.colour_on ? inv : 0.0f, i + 1u == d->iterations, tiled);
     }
-    return post_finish(ctx, b + 3);
+    return finish_call(ctx, b + 3, 2);
 } MIRT_CATCH("mirt_filter_atrous", return MIRT_E_DEVICE)
 
 // Guide-driven upsampling (pt_kernels_upsample.hip; defined in include/mirt.h): every check first, then one launch.  No working memory.
 int mirt_upsample_guided(mirt_ctx* ctx, const mirt_upsample_desc* d) try {
     static const char fn[] = "mirt_upsample_guided";
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_upsample_guided: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, "mirt_upsample_guided");
     if (!d || d->struct_size != sizeof(mirt_upsample_desc)) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: descriptor size mismatch");
     int rc;
     if ((rc = post_check_extent(ctx, fn, d->width, d->height))) return rc;
@@ -2268,7 +2124,7 @@ int mirt_upsample_guided(mirt_ctx* ctx, const mirt_upsample_desc* d) try {
     if ((rc = post_check_terms(ctx, fn, d->normal_power_log2, d->tone))) return rc;
     if (d->flags & ~MIRT_UPSAMPLE_DEMODULATE) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided: unknown flags 0x%x", d->flags);
     const uint64_t npix = (uint64_t)d->width * d->height, nlo = (uint64_t)wl * hl;
-    const PostBuf b[7] = {{"mirt_upsample_guided radiance_lo", d->radiance_lo, nlo * 16}, {"mirt_upsample_guided normal_hits_lo", d->normal_hits_lo, nlo * 16}, {"mirt_upsample_guided albedo_depth_lo", d->albedo_depth_lo, nlo * 16},
+    const CallBuf b[7] = {{"mirt_upsample_guided radiance_lo", d->radiance_lo, nlo * 16}, {"mirt_upsample_guided normal_hits_lo", d->normal_hits_lo, nlo * 16}, {"mirt_upsample_guided albedo_depth_lo", d->albedo_depth_lo, nlo * 16},
                           {"mirt_upsample_guided normal_hits", d->normal_hits, npix * 16}, {"mirt_upsample_guided albedo_depth", d->albedo_depth, npix * 16},
                           {"mirt_upsample_guided upsampled", d->upsampled, npix * 16}, {"mirt_upsample_guided pixel", d->pixel, npix * 4}};
     if ((rc = post_check_buffers(ctx, fn, "upsampled", b))) return rc;
@@ -2285,7 +2141,7 @@ int mirt_upsample_guided(mirt_ctx* ctx, const mirt_upsample_desc* d) try {
     A.upsampled = d->upsampled ? d->upsampled->ptr : nullptr;
     A.pixel = d->pixel ? d->pixel->ptr : nullptr;
     pt::launch_upsample(ctx->stream, A);
-    return post_finish(ctx, b + 5);
+    return finish_call(ctx, b + 5, 2);
 } MIRT_CATCH("mirt_upsample_guided", return MIRT_E_DEVICE)
 
 // ---- the post-process stage in row tiles: mirt_filter_atrous_rows, mirt_upsample_guided_rows and the halo exchange between them, mirt_exchange_rows.
@@ -2317,9 +2173,7 @@ static int rows_verdict(mirt_ctx* ctx, const char* fn, pt::RowsVerdict v, const 
 // the own rows.  MIRT_FILTER_ROWS_BAND=0 (a measurement switch: profiles/post_rows_bench.py): every launch but the last computes the whole window.
 int mirt_filter_atrous_rows(mirt_ctx* ctx, const mirt_filter_desc* d, uint32_t image_height, uint32_t win_row0, uint32_t row0, uint32_t nrows) try {
     static const char fn[] = "mirt_filter_atrous_rows";
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_filter_atrous_rows: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, "mirt_filter_atrous_rows");
     if (!d || d->struct_size != sizeof(mirt_filter_desc)) return fail(ctx, MIRT_E_ARG, "mirt_filter_atrous_rows: descriptor size mismatch");
     int rc;
     if ((rc = post_check_extent(ctx, fn, d->width, image_height))) return rc;
@@ -2331,7 +2185,7 @@ int mirt_filter_atrous_rows(mirt_ctx* ctx, const mirt_filter_desc* d, uint32_t i
     if ((rc = rows_verdict(ctx, fn, pt::filter_rows_check(image_height, win_row0, win_nrows, row0, nrows, d->iterations), "window", win_row0, win_nrows, row0, nrows,
                            pt::filter_window(image_height, row0, nrows, d->iterations)))) return rc;
     const uint64_t nwin = (uint64_t)d->width * win_nrows, nown = (uint64_t)d->width * nrows;
-    const PostBuf b[5] = {{"mirt_filter_atrous_rows radiance", d->radiance, nwin * 16}, {"mirt_filter_atrous_rows normal_hits", d->normal_hits, nwin * 16}, {"mirt_filter_atrous_rows albedo_depth", d->albedo_depth, nwin * 16},
+    const CallBuf b[5] = {{"mirt_filter_atrous_rows radiance", d->radiance, nwin * 16}, {"mirt_filter_atrous_rows normal_hits", d->normal_hits, nwin * 16}, {"mirt_filter_atrous_rows albedo_depth", d->albedo_depth, nwin * 16},
                           {"mirt_filter_atrous_rows filtered", d->filtered, nown * 16}, {"mirt_filter_atrous_rows pixel", d->pixel, nown * 4}};
     if ((rc = post_check_buffers(ctx, fn, "filtered", b))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2371,16 +2225,14 @@ int mirt_filter_atrous_rows(mirt_ctx* ctx, const mirt_filter_desc* d, uint32_t i
         band(i);
         pt::launch_filterStepRows(ctx->stream, A, i & 1u, i, A.colour_on ? inv : 0.0f, i + 1u == d->iterations, tiled);
     }
-    return post_finish(ctx, b + 3);
+    return finish_call(ctx, b + 3, 2);
 } MIRT_CATCH("mirt_filter_atrous_rows", return MIRT_E_DEVICE)
 
 // Guide-driven upsampling of high rows [row0, row0 + nrows) (defined in include/mirt.h): mirt_upsample_guided's checks on the whole image, the rule
 // of the low rows, then one launch over the band.
 int mirt_upsample_guided_rows(mirt_ctx* ctx, const mirt_upsample_desc* d, uint32_t row0, uint32_t nrows, uint32_t lo_row0, uint32_t lo_nrows) try {
     static const char fn[] = "mirt_upsample_guided_rows";
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_upsample_guided_rows: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, fn);
+    ENTRY_PROLOGUE(ctx, "mirt_upsample_guided_rows");
     if (!d || d->struct_size != sizeof(mirt_upsample_desc)) return fail(ctx, MIRT_E_ARG, "mirt_upsample_guided_rows: descriptor size mismatch");
     int rc;
     if ((rc = post_check_extent(ctx, fn, d->width, d->height))) return rc;
@@ -2394,7 +2246,7 @@ int mirt_upsample_guided_rows(mirt_ctx* ctx, const mirt_upsample_desc* d, uint32
     if ((rc = rows_verdict(ctx, fn, pt::upsample_rows_check(d->height, d->factor, row0, nrows, lo_row0, lo_nrows), "low rows", lo_row0, lo_nrows, row0, nrows,
                            pt::upsample_low_window(d->height, d->factor, row0, nrows)))) return rc;
     const uint64_t npix = (uint64_t)d->width * nrows, nlo = (uint64_t)wl * lo_nrows;
-    const PostBuf b[7] = {{"mirt_upsample_guided_rows radiance_lo", d->radiance_lo, nlo * 16}, {"mirt_upsample_guided_rows normal_hits_lo", d->normal_hits_lo, nlo * 16}, {"mirt_upsample_guided_rows albedo_depth_lo", d->albedo_depth_lo, nlo * 16},
+    const CallBuf b[7] = {{"mirt_upsample_guided_rows radiance_lo", d->radiance_lo, nlo * 16}, {"mirt_upsample_guided_rows normal_hits_lo", d->normal_hits_lo, nlo * 16}, {"mirt_upsample_guided_rows albedo_depth_lo", d->albedo_depth_lo, nlo * 16},
                           {"mirt_upsample_guided_rows normal_hits", d->normal_hits, npix * 16}, {"mirt_upsample_guided_rows albedo_depth", d->albedo_depth, npix * 16},
                           {"mirt_upsample_guided_rows upsampled", d->upsampled, npix * 16}, {"mirt_upsample_guided_rows pixel", d->pixel, npix * 4}};
     if ((rc = post_check_buffers(ctx, fn, "upsampled", b))) return rc;
@@ -2412,7 +2264,7 @@ int mirt_upsample_guided_rows(mirt_ctx* ctx, const mirt_upsample_desc* d, uint32
     A.pixel = d->pixel ? d->pixel->ptr : nullptr;
     A.row0 = row0; A.nrows = nrows; A.lo_row0 = lo_row0;
     pt::launch_upsampleRows(ctx->stream, A);
-    return post_finish(ctx, b + 5);
+    return finish_call(ctx, b + 5, 2);
 } MIRT_CATCH("mirt_upsample_guided_rows", return MIRT_E_DEVICE)
 
 // The halo exchange (defined in include/mirt.h): every check, then the plan of pt_rows_plan.hpp as copies on the destinations' streams, between
@@ -2613,22 +2465,8 @@ int mirt_ctx_set_exact_only(mirt_ctx* ctx, int on) try {
 } MIRT_CATCH("mirt_ctx_set_exact_only", return MIRT_E_DEVICE)
 
 int mirt_pass_deferred(mirt_ctx* ctx, uint64_t* samples) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_pass_deferred: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_pass_deferred");
-    if (!samples) return fail(ctx, MIRT_E_ARG, "mirt_pass_deferred: null output");
-    *samples = 0;
-    if (!ctx->defer_words) return MIRT_OK;
-    // counted on demand: the mask of the last pass is still in place (the next pass clears it)
-    uint32_t* counters = (uint32_t*)ctx->defer;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipMemsetAsync(counters, 0, 16, ctx->stream));
-    pt::launch_deferCount(ctx->stream, counters + 4, ctx->defer_words, counters);
-    uint32_t count = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&count, counters, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *samples = (uint64_t)count * ctx->defer_unit;   // resolving in the pass the exact kernel re-runs whole blocks of 256 samples
-    return MIRT_OK;
+    ENTRY_PROLOGUE(ctx, "mirt_pass_deferred");
+    return count_deferred(ctx, "mirt_pass_deferred", ctx->pass_mask, samples);   // (resolving in the pass the exact kernel re-runs whole blocks of 256 samples)
 } MIRT_CATCH("mirt_pass_deferred", return MIRT_E_DEVICE)
 
 int mirt_ctx_set_profiling(mirt_ctx* ctx, int on) try {
@@ -2676,9 +2514,7 @@ int mirt_zero(mirt_ctx* ctx, mirt_buf* buf) try {
 } MIRT_CATCH("mirt_zero", return MIRT_E_DEVICE)
 
 int mirt_debug_prepared(mirt_ctx* ctx, mirt_buf* positions, uint32_t count, void* out, size_t bytes, size_t* total) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_debug_prepared: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_debug_prepared");
+    ENTRY_PROLOGUE(ctx, "mirt_debug_prepared");
     if (!live_has(positions) || positions->ctx != ctx) return fail(ctx, MIRT_E_HANDLE, "mirt_debug_prepared: unknown buffer");
     int rc = need(ctx, "mirt_debug_prepared positions", positions, (uint64_t)count * 48);
     if (rc) return rc;
@@ -2939,17 +2775,13 @@ int mirt_graph_release(mirt_graph* graph) try {
 } MIRT_CATCH("mirt_graph_release", return MIRT_E_DEVICE)
 
 int mirt_timer_start(mirt_ctx* ctx) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_timer_start: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_timer_start");
+    ENTRY_PROLOGUE(ctx, "mirt_timer_start");
     HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     return MIRT_OK;
 } MIRT_CATCH("mirt_timer_start", return MIRT_E_DEVICE)
 
 int mirt_timer_stop_ms(mirt_ctx* ctx, float* ms) try {
-    if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_timer_stop_ms: unknown context");
-    FLUSH_PENDING(ctx);
-    NOT_WHILE_CAPTURING(ctx, "mirt_timer_stop_ms");
+    ENTRY_PROLOGUE(ctx, "mirt_timer_stop_ms");
     if (!ms) return fail(ctx, MIRT_E_ARG, "mirt_timer_stop_ms: null output");
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     HIPCHK(ctx, hipEventSynchronize(ctx->ev1));

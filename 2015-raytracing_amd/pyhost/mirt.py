@@ -336,6 +336,12 @@ class Context:
     def last_error(self):
         return lib().mirt_last_error(self.h).decode()
 
+    def _deferred(self, fn):
+        """one mirt_*_deferred counter"""
+        n = C.c_uint64()
+        self._chk(fn(self.h, C.byref(n)))
+        return n.value
+
     def buffer(self, nbytes, flags=MEM_READ_WRITE):
         h = C.c_void_p()
         self._chk(lib().mirt_buf_create(self.h, nbytes, flags, C.byref(h)))
@@ -389,9 +395,7 @@ class Context:
         return ms.value
 
     def pass_deferred(self):
-        n = C.c_uint64()
-        self._chk(lib().mirt_pass_deferred(self.h, C.byref(n)))
-        return n.value
+        return self._deferred(lib().mirt_pass_deferred)
 
     def set_exact_only(self, on=True):
         self._chk(lib().mirt_ctx_set_exact_only(self.h, 1 if on else 0))
@@ -592,9 +596,7 @@ class Context:
 
     def trace_deferred(self):
         """how many rays the last trace_closest / trace_occluded call re-ran in the exact kernel (mirt_trace_deferred)"""
-        n = C.c_uint64()
-        self._chk(lib().mirt_trace_deferred(self.h, C.byref(n)))
-        return n.value
+        return self._deferred(lib().mirt_trace_deferred)
 
     def trace_radiance(self, desc, rays, count, seeds, radiance, samples=1, flags=0):
         """Path radiance of `count` caller-supplied rays in one launch (mirt_trace_radiance): the pass's path -- closest hit, lightRender, per-light
@@ -607,9 +609,7 @@ class Context:
 
     def radiance_deferred(self):
         """how many rays the last trace_radiance call re-ran in the exact kernel (mirt_radiance_deferred)"""
-        n = C.c_uint64()
-        self._chk(lib().mirt_radiance_deferred(self.h, C.byref(n)))
-        return n.value
+        return self._deferred(lib().mirt_radiance_deferred)
 
     def view_rays(self, view, rays):
         """The rays of a panoramic, fisheye or orthographic camera's row tile as 32-byte records (mirt_view_rays): view.width * nrows * k * k of
@@ -626,9 +626,7 @@ class Context:
 
     def view_deferred(self):
         """how many rays the last render_view call re-ran in the exact kernel, in whole blocks of 256 (mirt_view_deferred)"""
-        n = C.c_uint64()
-        self._chk(lib().mirt_view_deferred(self.h, C.byref(n)))
-        return n.value
+        return self._deferred(lib().mirt_view_deferred)
 
     def view_guides(self, scene_desc, view, normal_hits=None, albedo_depth=None):
         """The first-hit guides of a panoramic, fisheye or orthographic camera's row tile in one launch (mirt_view_guides): float4 per tile pixel
@@ -660,9 +658,7 @@ class Context:
 
     def ao_deferred(self):
         """how many pixels the last render_ao call re-ran in the exact kernel (mirt_ao_deferred)"""
-        n = C.c_uint64()
-        self._chk(lib().mirt_ao_deferred(self.h, C.byref(n)))
-        return n.value
+        return self._deferred(lib().mirt_ao_deferred)
 
     def view_ao(self, scene_desc, view, seeds, ao_out, samples=AO_DEFAULT_SAMPLES, radius=float("inf"), bias=AO_DEFAULT_BIAS):
         """Ambient occlusion of a panoramic, fisheye or orthographic camera's row tile in one launch (mirt_view_ao): ao_out receives uint32
@@ -674,9 +670,7 @@ class Context:
 
     def view_ao_deferred(self):
         """how many pixels the last view_ao call re-ran in the exact kernel (mirt_view_ao_deferred)"""
-        n = C.c_uint64()
-        self._chk(lib().mirt_view_ao_deferred(self.h, C.byref(n)))
-        return n.value
+        return self._deferred(lib().mirt_view_ao_deferred)
 
     def filter_atrous(self, width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,
                       normal_power_log2=None, sigma_depth=None, sigma_colour=None, demodulate=None, structure=None):
