@@ -2,7 +2,8 @@
 // (pt_kernels_rays.hip) share: the block prologue (staged single-cell sets and cell tables, the lens table), the primary ray, the closest-hit
 // query over every set -- the ONE definition of that loop: each kernel adds what is its own through ClosestHooks -- and the LDS slots a launch
 // gives the sets, with the kernel instance they call for.  Moved here verbatim from pt_kernels_fused.hip, so that all three files run the same
-// instructions on the same operands.
+// instructions on the same operands.  Also here, each once: the rules of the optimistic / exact pair that every query kernel of the guides and
+// the rays file follows (fresh_poi .. defer_wave behind stage_block) and the launch of such a pair (query_dispatch, at the end).
 #pragma once
 #include <type_traits>
 #include "pt_trace_coop.hpp"
@@ -168,6 +169,61 @@ PT_DEV void stage_block(const FusedArgs& A) {
     }
 }
 
+// ---- The rules of the optimistic / exact pair that every QUERY kernel restates (k_guides, k_traceRays, k_ao, k_traceRadiance, k_viewPass,
+// k_viewGuides, k_viewAo), each defined once.  A unit is what the kernel's mask holds a bit for: a ray or a pixel, a lane each.
+
+// a Poi as initTrace resets it (A10 code.cl:538-541)
+PT_DEV Poi fresh_poi() {
+    Poi poi;
+    poi.p = mk3(0.0f, 0.0f, 0.0f);
+    poi.n = mk3(0.0f, 0.0f, 0.0f);
+    poi.atte = mk3(1.0f, 1.0f, 1.0f);
+    poi.matId = -1;
+    return poi;
+}
+
+// what a lane without a ray rides along with: dead (mint == maxt), so it enters the shared walks and tests nothing of its own
+PT_DEV Ray dead_ray() {
+    Ray ray;
+    ray.o = mk3(0.0f, 0.0f, 0.0f); ray.d = mk3(0.0f, 0.0f, 0.0f); ray.mint = 0.0f; ray.maxt = 0.0f;
+    return ray;
+}
+
+// The work-item prologue, in two steps (as ONE function with a `bool& valid` the exact kernels' instructions came out reordered:
+// profiles/query_helpers/README.md).  Has lane `id` a unit of its own?  It has when the id is inside the launch and -- exact kernel only --
+// when redo_mask is null (every unit) or holds the unit's bit (the units the optimistic kernel handed over).
+template <bool FAST>
+PT_DEV bool unit_valid(uint32_t id, uint32_t count, const uint32_t* redo_mask) {
+    bool valid = id < count;
+    if (!FAST && redo_mask && valid) valid = (redo_mask[id >> 5] >> (id & 31u) & 1u) != 0u;
+    return valid;
+}
+// ... and may the lane leave?  With grids the walk shares its tests across the wave (pt_trace_coop.hpp): a wave without work leaves at the
+// ballot, and in a wave with work a lane without a unit of its own STAYS -- it rides along dead and writes nothing.  Without grids a lane
+// without work leaves.
+template <int GRIDS>
+PT_DEV bool nothing_to_do(bool valid) {
+    if (GRIDS) return __builtin_amdgcn_ballot_w64(valid) == 0ull;
+    return !valid;
+}
+
+// The deferred hand-over of the optimistic kernel: the unit's bit in defer_mask, and nothing of the unit is written -- the exact kernel redoes
+// it whole.  Per unit: one atomic (the pixel kernels, where deferral is the exception).
+PT_DEV void defer_unit(uint32_t* defer_mask, uint32_t id) { atomicOr(&defer_mask[id >> 5], 1u << (id & 31u)); }
+// Per wave (the ray kernels; EVERY lane of the wave calls it: k_traceRadiance does, k_traceRays keeps the same lines as its own lambda, which
+// is the only form that leaves its code as it was).  A wave holds 64 consecutive ids from a multiple of 64 on: two whole words of
+// the mask, which no other wave touches -- so lanes 0 and 32 store the wave's ballot, a word each (a zero word stays as the host cleared it),
+// instead of one atomic per ray: a batch the guard refuses whole made 32 atomics on every word of the mask, and they cost more than tracing
+// the batch.
+PT_DEV void defer_wave(uint32_t* defer_mask, uint32_t id, bool valid, bool defer) {
+    const unsigned long long dm = __builtin_amdgcn_ballot_w64(valid && defer);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (valid && (lane & 31u) == 0u) {
+        const uint32_t w = (uint32_t)(dm >> lane);
+        if (w) defer_mask[id >> 5] = w;
+    }
+}
+
 // initTrace (code.cl:458-543) for one ray id of the tile: thin-lens ray through its pixel, clipped to the scene box
 // (tile-local ray ids fit 32 bits: mirt_render_pass refuses a tile of more than 2^32 - 256 rays)
 PT_DEV Ray primary_ray(const FusedArgs& A, uint32_t lid) {
@@ -254,6 +310,17 @@ inline void fused_lds_dispatch(const FusedLds& L, const LAUNCH& launch) {
     if (L.grids && L.staged) launch(std::integral_constant<int, 1>{}, L.lds);
     else if (L.grids) launch(std::integral_constant<int, 2>{}, L.lds2);
     else launch(std::integral_constant<int, 0>{}, L.lds_tri);
+}
+// ... and the launch of a query kernel's optimistic / exact pair, either half of it.  `b`: the launch's own copy of the arguments, the fields
+// that are the caller's already set; it gets its LDS slots here.  fast: the optimistic kernel, which sets the bits of the units it hands over
+// in defer_mask (the host cleared it) and has no redo mask; !fast: the exact kernel, over the units of redo_mask or over every unit when it
+// is null, and with no defer mask.  launch(std::bool_constant<FAST>, std::integral_constant<int, GRIDS>, the dynamic LDS bytes, the defer mask
+// and the redo mask THAT kernel gets).
+template <class LAUNCH>
+inline void query_dispatch(FusedArgs& b, bool fast, uint32_t* defer_mask, const uint32_t* redo_mask, const LAUNCH& launch) {
+    const FusedLds L = fused_lds_slots(b, fast);
+    if (fast) fused_lds_dispatch(L, [&](auto G, size_t lds) { launch(std::true_type{}, G, lds, defer_mask, (const uint32_t*)nullptr); });
+    else fused_lds_dispatch(L, [&](auto G, size_t lds) { launch(std::false_type{}, G, lds, (uint32_t*)nullptr, redo_mask); });
 }
 
 }  // namespace pt

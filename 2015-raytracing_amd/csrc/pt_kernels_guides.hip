@@ -25,17 +25,16 @@
 
 namespace pt {
 
-// redo_mask (exact kernel only): a bit per pixel of the tile, the pixels the optimistic kernel handed over; null: every pixel.
-// GRIDS: the walk shares its tests across the wave (pt_trace_coop.hpp), so a lane without a pixel of its own rides along and writes nothing.
+// defer_mask / redo_mask: a bit per pixel of the tile.  Which lane has a pixel of its own, which lane may leave and how a deferred pixel is handed
+// over are the query kernels' common rules (pt_closest.hpp: unit_valid, nothing_to_do, defer_unit); a lane that rides along does so on the
+// clamped last pixel.
 template <bool FAST, int GRIDS>
 __global__ void __launch_bounds__(256) k_guides(const FusedArgs A, float4* normal_hits, float4* albedo_depth, uint32_t* defer_mask, const uint32_t* redo_mask) {
     stage_block<FAST, GRIDS>(A);
     const uint32_t npix = A.nrows * A.width;   // (a tile holds fewer than 2^32 rays: mirt_render_guides)
     uint32_t pix = blockIdx.x * 256u + threadIdx.x;
-    bool valid = pix < npix;
-    if (!FAST && redo_mask && valid) valid = (redo_mask[pix >> 5] >> (pix & 31u) & 1u) != 0u;
-    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
-    else if (!valid) return;
+    const bool valid = unit_valid<FAST>(pix, npix, redo_mask);
+    if (nothing_to_do<GRIDS>(valid)) return;
     if (pix >= npix) pix = npix - 1u;
     const float4* material = (const float4*)A.material;
     float nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, depth = 0.0f;
@@ -43,11 +42,7 @@ __global__ void __launch_bounds__(256) k_guides(const FusedArgs A, float4* norma
     const uint32_t first = pix * A.rpp;
     for (uint32_t i = 0; i < A.rpp; ++i) {
         Ray ray = primary_ray(A, first + i);
-        Poi poi;
-        poi.p = mk3(0.0f, 0.0f, 0.0f);
-        poi.n = mk3(0.0f, 0.0f, 0.0f);
-        poi.atte = mk3(1.0f, 1.0f, 1.0f);
-        poi.matId = -1;
+        Poi poi = fresh_poi();
         closest_all<FAST, GRIDS>(A, ray, poi, ClosestHooks{}, defer);   // the pass parks the vertex for its shadow stage: nothing comes after it here
         if (poi.matId < 0 || (uint32_t)poi.matId >= A.nmat) continue;
         const float4 c = material[poi.matId];
@@ -55,27 +50,19 @@ __global__ void __launch_bounds__(256) k_guides(const FusedArgs A, float4* norma
         ar += c.x; ag += c.y; ab += c.z; depth += ray.maxt;
     }
     if (!valid) return;
-    if (FAST && defer) {   // the exact kernel redoes the pixel: nothing of it is written
-        atomicOr(&defer_mask[pix >> 5], 1u << (pix & 31u));
-        return;
-    }
+    if (FAST && defer) { defer_unit(defer_mask, pix); return; }
     if (normal_hits) normal_hits[pix] = make_float4(nx, ny, nz, hits);
     if (albedo_depth) albedo_depth[pix] = make_float4(ar, ag, ab, depth);
 }
 
-template <bool FAST>
-static void launch_guides_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, float4* nh, float4* ad, uint32_t* defer_mask, const uint32_t* redo_mask) {
-    const dim3 grid((unsigned)(((uint64_t)b.nrows * b.width + 255u) / 256u));
-    fused_lds_dispatch(L, [&](auto G, size_t lds) { hipLaunchKernelGGL((k_guides<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, nh, ad, defer_mask, redo_mask); });
-}
-// fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
-// of redo_mask, or over every pixel when it is null.  Either output may be null.
+// fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per pixel of the tile.  Either output may be null.
 void launch_guides(hipStream_t s, const FusedArgs& a, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask, const uint32_t* redo_mask) {
     if (!a.nrows || !a.width) return;
     FusedArgs b = a;
-    const FusedLds L = fused_lds_slots(b, fast);
-    if (fast) launch_guides_t<true>(s, b, L, (float4*)normal_hits, (float4*)albedo_depth, defer_mask, nullptr);
-    else launch_guides_t<false>(s, b, L, (float4*)normal_hits, (float4*)albedo_depth, nullptr, redo_mask);
+    const dim3 grid((unsigned)(((uint64_t)b.nrows * b.width + 255u) / 256u));
+    query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+        hipLaunchKernelGGL((k_guides<decltype(F)::value, decltype(G)::value>), grid, dim3(256), lds, s, b, (float4*)normal_hits, (float4*)albedo_depth, dm, rm);
+    });
 }
 
 }  // namespace pt

@@ -15,12 +15,16 @@
 // kernel adds its guard and the winning set's index through RayHooks), the sets get the LDS slots the pass gives them and the kernel instance
 // those call for (fused_lds_slots, fused_lds_dispatch), and the optimistic / exact pair is the pass's -- here per RAY: a ray the ray-side guard
 // refuses, or whose walk defers, sets its bit and writes nothing, and the exact kernel redoes the marked rays.
+// The rules of that pair which every kernel of this file follows are stated ONCE, in pt_closest.hpp, and the kernels call them: which lane has
+// a unit of its own and which lane may leave (unit_valid, nothing_to_do), what a lane without one rides along with (dead_ray), the vertex a ray
+// starts from (fresh_poi), how a deferred unit is handed over (defer_unit per pixel, defer_wave per wave of rays), and which mask each kernel
+// of the pair is launched with (query_dispatch).  Every kernel's code is the parent's, symbol for symbol; where a call would have changed it the
+// lines stay hand-written and say so: k_traceRays' prologue and hand-over, and the lightRender loop, which k_traceRadiance and k_viewPass
+// still state twice -- a change to one is a change to both (profiles/query_helpers/README.md has the forms tried and the figures).
 // The any-hit loop (rays_any) is still stated twice, here and in the shadow stage of direct_all (pt_direct.hpp): every shared form that was
 // tried re-allocated registers in k_fusedPass, whose rule is identical assembly (profiles/shared_loops/README.md).  A change to one is a change to both.
 //
-// Structure: one lane per ray, two float4 loads, the query, two float4 stores (and the optional uint32), or one byte.  With grids every lane of a
-// wave enters the shared-test walk (pt_trace_coop.hpp): a lane without a ray, and a redo kernel's unmarked lane, rides along as a dead ray and
-// writes nothing.
+// Structure: one lane per ray, two float4 loads, the query, two float4 stores (and the optional uint32), or one byte.
 //
 // A caller's rays are not the camera's: they need not be coherent, and axis-parallel directions are common -- a zero component of d fails the
 // guard's |d_k| >= 2^-40, as does a zero-length, infinite or NaN one.  Such batches run mostly in the EXACT kernel (mirt_trace_deferred counts
@@ -114,21 +118,19 @@ __global__ void __launch_bounds__(256) k_traceRays(const FusedArgs A, const floa
                                                    uint32_t* __restrict__ sets, uint8_t* __restrict__ occluded, uint32_t* defer_mask, const uint32_t* redo_mask) {
     stage_block<FAST, GRIDS>(A);
     const uint32_t id = blockIdx.x * 256u + threadIdx.x;   // (count <= 2^32 - 256: mirt_trace_closest)
+    // (the prologue and the hand-over are hand-written here: called as unit_valid / nothing_to_do and defer_wave, pt_closest.hpp, whose rules they
+    // follow word for word, six instances of this kernel came out as other code and missed the timing rule -- profiles/query_helpers/README.md)
     bool valid = id < count;
     if (!FAST && redo_mask && valid) valid = (redo_mask[id >> 5] >> (id & 31u) & 1u) != 0u;
     if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
     else if (!valid) return;
-    Ray ray;   // a lane without a ray rides along dead: it enters the shared walks and tests nothing of its own
-    ray.o = mk3(0.0f, 0.0f, 0.0f); ray.d = mk3(0.0f, 0.0f, 0.0f); ray.mint = 0.0f; ray.maxt = 0.0f;
+    Ray ray = dead_ray();
     if (valid) {
         const float4 a = rays[2u * (size_t)id], b = rays[2u * (size_t)id + 1u];
         ray.o = mk3(a.x, a.y, a.z); ray.mint = a.w;
         ray.d = mk3(b.x, b.y, b.z); ray.maxt = b.w;
     }
     bool defer = false;
-    // The deferred rays' bits.  A wave holds 64 consecutive ray ids from a multiple of 64 on: two whole words of the mask, which no other wave
-    // touches -- so lanes 0 and 32 store the wave's ballot, a word each (a zero word stays as the host cleared it), instead of one atomic per
-    // ray: a batch the guard refuses whole made 32 atomics on every word of the mask, and they cost more than tracing the batch.
     const auto hand_over = [&]() {
         const unsigned long long dm = __builtin_amdgcn_ballot_w64(valid && defer);
         const uint32_t lane = threadIdx.x & 63u;
@@ -143,11 +145,7 @@ __global__ void __launch_bounds__(256) k_traceRays(const FusedArgs A, const floa
         if (!valid || (FAST && defer)) return;   // the exact kernel redoes a deferred ray: nothing of it is written
         occluded[id] = ray.mint == ray.maxt ? (uint8_t)1 : (uint8_t)0;
     } else {
-        Poi poi;
-        poi.p = mk3(0.0f, 0.0f, 0.0f);
-        poi.n = mk3(0.0f, 0.0f, 0.0f);
-        poi.atte = mk3(1.0f, 1.0f, 1.0f);
-        poi.matId = -1;
+        Poi poi = fresh_poi();
         uint32_t won = UINT32_MAX;
         closest_all<FAST, GRIDS>(A, ray, poi, RayHooks{{}, won}, defer);
         if (FAST) hand_over();
@@ -160,28 +158,22 @@ __global__ void __launch_bounds__(256) k_traceRays(const FusedArgs A, const floa
     }
 }
 
-template <bool FAST, bool ANY>
-static void launch_rays_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const float4* rays, uint32_t count, float4* hits, uint32_t* sets, uint8_t* occluded,
-                          uint32_t* defer_mask, const uint32_t* redo_mask) {
-    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
-    fused_lds_dispatch(L, [&](auto G, size_t lds) {
-        hipLaunchKernelGGL((k_traceRays<FAST, decltype(G)::value, ANY>), grid, dim3(256), lds, s, b, rays, count, hits, sets, occluded, defer_mask, redo_mask);
-    });
-}
-// fast: the optimistic kernel (sets the deferred rays' bits in defer_mask, one per ray); !fast: the exact kernel over the rays of redo_mask, or
-// over every ray when it is null.  occluded != null: the occlusion query; else the closest hit into hits and / or sets.
+// fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per ray.  occluded != null: the occlusion query; else the closest hit
+// into hits and / or sets.
 void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, void* hits, uint32_t* sets, uint8_t* occluded,
                  uint32_t* defer_mask, const uint32_t* redo_mask) {
     if (!count) return;
     FusedArgs b = a;
     b.rpp = 1u;   // stage_block: no lens table
-    const FusedLds L = fused_lds_slots(b, fast);
+    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
     if (occluded) {
-        if (fast) launch_rays_t<true, true>(s, b, L, (const float4*)rays, count, nullptr, nullptr, occluded, defer_mask, nullptr);
-        else launch_rays_t<false, true>(s, b, L, (const float4*)rays, count, nullptr, nullptr, occluded, nullptr, redo_mask);
+        query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+            hipLaunchKernelGGL((k_traceRays<decltype(F)::value, decltype(G)::value, true>), grid, dim3(256), lds, s, b, (const float4*)rays, count, nullptr, nullptr, occluded, dm, rm);
+        });
     } else {
-        if (fast) launch_rays_t<true, false>(s, b, L, (const float4*)rays, count, (float4*)hits, sets, nullptr, defer_mask, nullptr);
-        else launch_rays_t<false, false>(s, b, L, (const float4*)rays, count, (float4*)hits, sets, nullptr, nullptr, redo_mask);
+        query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+            hipLaunchKernelGGL((k_traceRays<decltype(F)::value, decltype(G)::value, false>), grid, dim3(256), lds, s, b, (const float4*)rays, count, (float4*)hits, sets, nullptr, dm, rm);
+        });
     }
 }
 
@@ -191,9 +183,9 @@ void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays,
 //
 // Structure: k_guides' -- one lane per pixel, walking its samples in order, so every k x k count works with no segment plan -- and behind each
 // sample's closest hit a loop of `samples` trips, a kernel argument and so WAVE-UNIFORM: in the grid variants every lane of the wave enters each
-// shared-test walk of rays_any together (pt_trace_coop.hpp).  A lane whose sample did not cast, a lane without a pixel and a redo kernel's unmarked
-// lane ride along with a dead ray and count nothing.  The optimistic / exact pair is per PIXEL, as in k_guides: a pixel one of whose primary or AO
-// rays the guard refuses, or whose walk defers, sets its bit and writes nothing; the exact kernel redoes the marked pixels whole.
+// shared-test walk of rays_any together (pt_trace_coop.hpp).  A lane whose sample did not cast rides along with a dead ray and counts nothing,
+// like a lane without a pixel (nothing_to_do).  The optimistic / exact pair is per PIXEL (defer_unit): a pixel defers when the guard refuses one
+// of its primary or AO rays or one of its walks defers.
 // seeds: int32 per tile-local ray, read for the casting samples and never written.  ao_out: {open, cast} per tile-local pixel, one 8-byte store.
 // Waves per SIMD the register allocator is held to (A/B switches; profiles/ao/README.md has the measurement).  Left alone the grid kernels take 126 to
 // 129 VGPRs (the optimistic one 3 waves, a register over the fourth) and the single-cell ones 81 to 94 (5 waves); a lane here runs rpp * (1 + samples)
@@ -212,10 +204,8 @@ __global__ void PT_AO_BOUNDS(GRIDS) k_ao(const FusedArgs A, uint32_t samples, fl
     stage_block<FAST, GRIDS>(A);
     const uint32_t npix = A.nrows * A.width;   // (a tile holds fewer than 2^32 rays: mirt_render_ao)
     uint32_t pix = blockIdx.x * 256u + threadIdx.x;
-    bool valid = pix < npix;
-    if (!FAST && redo_mask && valid) valid = (redo_mask[pix >> 5] >> (pix & 31u) & 1u) != 0u;
-    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
-    else if (!valid) return;
+    const bool valid = unit_valid<FAST>(pix, npix, redo_mask);
+    if (nothing_to_do<GRIDS>(valid)) return;
     if (pix >= npix) pix = npix - 1u;
     const int32_t* __restrict__ seeds = A.seeds;
     uint32_t open = 0u, cast = 0u;
@@ -224,18 +214,13 @@ __global__ void PT_AO_BOUNDS(GRIDS) k_ao(const FusedArgs A, uint32_t samples, fl
     for (uint32_t i = 0; i < A.rpp; ++i) {
         Ray ray = primary_ray(A, first + i);
         if (!valid) { ray.mint = 0.0f; ray.maxt = 0.0f; }   // rides along dead: hits nothing, casts nothing
-        Poi poi;
-        poi.p = mk3(0.0f, 0.0f, 0.0f);
-        poi.n = mk3(0.0f, 0.0f, 0.0f);
-        poi.atte = mk3(1.0f, 1.0f, 1.0f);
-        poi.matId = -1;
+        Poi poi = fresh_poi();
         closest_all<FAST, GRIDS>(A, ray, poi, ClosestHooks{}, defer);
         const bool casts = poi.matId >= 0;   // bouncePaths' own test (code.cl:592): no material is read
         int32_t seed = 0;
         if (casts) seed = seeds[first + i];
         for (uint32_t j = 0; j < samples; ++j) {
-            Ray sh;
-            sh.o = mk3(0.0f, 0.0f, 0.0f); sh.d = mk3(0.0f, 0.0f, 0.0f); sh.mint = 0.0f; sh.maxt = 0.0f;
+            Ray sh = dead_ray();
             if (casts) {
                 sh = bounce_ray(poi, seed);   // getHemisphereRay (code.cl:545-579): the seed advances, in its register only
                 if (bias != 0.0f) sh.o = add3(poi.p, scl3(bias, poi.n));   // two fp32 operations, each rounded on its own (-ffp-contract=off)
@@ -249,44 +234,32 @@ __global__ void PT_AO_BOUNDS(GRIDS) k_ao(const FusedArgs A, uint32_t samples, fl
         }
     }
     if (!valid) return;
-    if (FAST && defer) {   // the exact kernel redoes the pixel: nothing of it is written
-        atomicOr(&defer_mask[pix >> 5], 1u << (pix & 31u));
-        return;
-    }
+    if (FAST && defer) { defer_unit(defer_mask, pix); return; }
     ao_out[pix] = make_uint2(open, cast);
 }
 
-template <bool FAST>
-static void launch_ao_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, uint32_t samples, float radius, float bias, uint2* ao_out, uint32_t* defer_mask,
-                        const uint32_t* redo_mask) {
-    const dim3 grid((unsigned)(((uint64_t)b.nrows * b.width + 255u) / 256u));
-    fused_lds_dispatch(L, [&](auto G, size_t lds) {
-        hipLaunchKernelGGL((k_ao<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, samples, radius, bias, ao_out, defer_mask, redo_mask);
-    });
-}
-// fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
-// of redo_mask, or over every pixel when it is null.
+// fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per pixel of the tile
 void launch_ao(hipStream_t s, const FusedArgs& a, bool fast, uint32_t samples, float radius, float bias, void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
     if (!a.nrows || !a.width) return;
     FusedArgs b = a;
-    const FusedLds L = fused_lds_slots(b, fast);
-    if (fast) launch_ao_t<true>(s, b, L, samples, radius, bias, (uint2*)ao_out, defer_mask, nullptr);
-    else launch_ao_t<false>(s, b, L, samples, radius, bias, (uint2*)ao_out, nullptr, redo_mask);
+    const dim3 grid((unsigned)(((uint64_t)b.nrows * b.width + 255u) / 256u));
+    query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+        hipLaunchKernelGGL((k_ao<decltype(F)::value, decltype(G)::value>), grid, dim3(256), lds, s, b, samples, radius, bias, (uint2*)ao_out, dm, rm);
+    });
 }
 
 // ---- path radiance of caller-supplied rays (mirt_trace_radiance): the pass's path -- closest hit, lightRender, then per segment the per-light
 // shadow stage and shade, bouncePaths between the segments -- started at the CALLER's ray instead of initTrace's, `samples` times per ray, in one
 // launch.  The definition is include/mirt.h's: executeRender (A10 code.js:1806-1854) without initTrace and copyToPixel.  The pieces are the pass's:
 // closest_all (with this file's guard and the division kept in the loop: a caller's d is not of unit length), the lightRender loop as k_fusedPass
-// states it, direct_all with the park rows (pt_direct.hpp), bounce_ray.
+// states it (and k_viewPass below, verbatim), direct_all with the park rows (pt_direct.hpp), bounce_ray.
 //
 // Structure: one lane per ray; two float4 loads per sample for the ray (they hit the cache after the first; held in registers across the path they
 // were eight more live VGPRs), the seed and, with MIRT_RADIANCE_ACCUMULATE, the accumulator once; one float4 store and one seed store.  `samples`,
 // the bounce count and the flags are kernel arguments and so WAVE-UNIFORM: in the grid variants every lane of a wave enters every shared-test walk
-// together (pt_trace_coop.hpp).  A lane without a ray and a redo kernel's unmarked lane ride along dead -- they hit nothing, so they shade and
-// bounce nothing -- and write nothing.  The optimistic / exact pair is per RAY, as in k_traceRays: a ray whose primary, shadow or bounce ray the
-// guard refuses in any sample, or whose walk defers, sets its bit and writes neither its seed nor its accumulator; the exact kernel redoes the
-// marked rays from the start, all samples.
+// together (pt_trace_coop.hpp).  A lane that rides along dead (nothing_to_do) hits nothing, so it shades and bounces nothing.  The optimistic /
+// exact pair is per RAY (defer_wave): a ray defers when the guard refuses its primary, a shadow or a bounce ray in any sample or one of its
+// walks defers; neither its seed nor its accumulator is written, and the exact kernel redoes it from the start, all samples.
 // Not built: samples after the first reusing the primary ray's closest hit and lightRender verdict (k_fusedPass's MULTI 2 does it for the camera).
 // Waves per SIMD the register allocator is held to, A/B switches like k_ao's (profiles/radiance/README.md has the registers per instance and the
 // measurement).  A lane runs samples * (1 + bounces) segments back to back with nothing to overlap them but other waves, and more waves paid at
@@ -310,10 +283,8 @@ __global__ void PT_RADIANCE_BOUNDS(GRIDS) k_traceRadiance(const FusedArgs A, con
                                                            int32_t* __restrict__ seeds, float4* __restrict__ radiance, uint32_t* defer_mask, const uint32_t* redo_mask) {
     stage_block<FAST, GRIDS>(A);
     const uint32_t id = blockIdx.x * 256u + threadIdx.x;   // (count <= 2^32 - 256: mirt_trace_radiance)
-    bool valid = id < count;
-    if (!FAST && redo_mask && valid) valid = (redo_mask[id >> 5] >> (id & 31u) & 1u) != 0u;
-    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
-    else if (!valid) return;
+    const bool valid = unit_valid<FAST>(id, count, redo_mask);
+    if (nothing_to_do<GRIDS>(valid)) return;
     int32_t seed = 0;
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // initAcu (A10 code.cl:448-456)
     if (valid) {
@@ -328,18 +299,13 @@ __global__ void PT_RADIANCE_BOUNDS(GRIDS) k_traceRadiance(const FusedArgs A, con
 #endif
     bool defer = false;
     for (uint32_t j = 0; j < samples; ++j) {
-        Ray ray;   // a lane without a ray rides along dead: it enters the shared walks and tests nothing of its own
-        ray.o = mk3(0.0f, 0.0f, 0.0f); ray.d = mk3(0.0f, 0.0f, 0.0f); ray.mint = 0.0f; ray.maxt = 0.0f;
+        Ray ray = dead_ray();
         if (valid) {
             const float4 a = rays[2u * (size_t)id], b = rays[2u * (size_t)id + 1u];
             ray.o = mk3(a.x, a.y, a.z); ray.mint = a.w;
             ray.d = mk3(b.x, b.y, b.z); ray.maxt = b.w;
         }
-        Poi poi;   // as initTrace resets it (code.cl:538-541)
-        poi.p = mk3(0.0f, 0.0f, 0.0f);
-        poi.n = mk3(0.0f, 0.0f, 0.0f);
-        poi.atte = mk3(1.0f, 1.0f, 1.0f);
-        poi.matId = -1;
+        Poi poi = fresh_poi();
 #if PT_PARK_LDS
         park.put(4, 1.0f); park.put(5, 1.0f); park.put(6, 1.0f);   // every sample's path starts unattenuated; the accumulator goes on
 #endif
@@ -376,14 +342,7 @@ __global__ void PT_RADIANCE_BOUNDS(GRIDS) k_traceRadiance(const FusedArgs A, con
             direct_all<FAST, GRIDS>(A, poi, seed, acc, park, defer);
         }
     }
-    if (FAST) {   // the deferred rays' bits: a wave's ballot, a word each from lanes 0 and 32 (see k_traceRays)
-        const unsigned long long dm = __builtin_amdgcn_ballot_w64(valid && defer);
-        const uint32_t lane = threadIdx.x & 63u;
-        if (valid && (lane & 31u) == 0u) {
-            const uint32_t w = (uint32_t)(dm >> lane);
-            if (w) defer_mask[id >> 5] = w;
-        }
-    }
+    if (FAST) defer_wave(defer_mask, id, valid, defer);
     if (!valid || (FAST && defer)) return;   // the exact kernel redoes a deferred ray: nothing of it is written
     seeds[id] = seed;
 #if PT_PARK_LDS
@@ -392,24 +351,17 @@ __global__ void PT_RADIANCE_BOUNDS(GRIDS) k_traceRadiance(const FusedArgs A, con
     radiance[id] = acc;
 }
 
-template <bool FAST>
-static void launch_radiance_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const float4* rays, uint32_t count, uint32_t samples, uint32_t flags, int32_t* seeds,
-                              float4* radiance, uint32_t* defer_mask, const uint32_t* redo_mask) {
-    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
-    fused_lds_dispatch(L, [&](auto G, size_t lds) {
-        hipLaunchKernelGGL((k_traceRadiance<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, rays, count, samples, flags, seeds, radiance, defer_mask, redo_mask);
-    });
-}
-// fast: the optimistic kernel (sets the deferred rays' bits in defer_mask, one per ray); !fast: the exact kernel over the rays of redo_mask, or
-// over every ray when it is null.
+// fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per ray
 void launch_radiance(hipStream_t s, const FusedArgs& a, bool fast, const void* rays, uint32_t count, uint32_t samples, uint32_t flags, int32_t* seeds, void* radiance,
                      uint32_t* defer_mask, const uint32_t* redo_mask) {
     if (!count) return;
     FusedArgs b = a;
     b.rpp = 1u;   // stage_block: no lens table
-    const FusedLds L = fused_lds_slots(b, fast);
-    if (fast) launch_radiance_t<true>(s, b, L, (const float4*)rays, count, samples, flags, seeds, (float4*)radiance, defer_mask, nullptr);
-    else launch_radiance_t<false>(s, b, L, (const float4*)rays, count, samples, flags, seeds, (float4*)radiance, nullptr, redo_mask);
+    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
+    query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+        hipLaunchKernelGGL((k_traceRadiance<decltype(F)::value, decltype(G)::value>), grid, dim3(256), lds, s, b, (const float4*)rays, count, samples, flags, seeds,
+                           (float4*)radiance, dm, rm);
+    });
 }
 
 // ---- panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view): the ray of a sample is pt_view.hpp's view_ray, the one
@@ -435,7 +387,8 @@ void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays) {
 //
 // Structure: one lane per ray.  The generator's registers are dead before the segment loop; the four accumulator words are parked as
 // [channel][lane] rows from the start (they begin at +0: ACCUMULATE is the resolve's business, not the ray's) and read by the resolve where they
-// lie.  Every lane stays to the barrier: a lane past the end of the tile rides along dead -- it hits nothing, shades nothing, draws nothing.
+// lie.  Every lane stays to the barrier, so the prologue is the block's own, not unit_valid / nothing_to_do: a lane past the end of the tile
+// rides along dead (dead_ray) -- it hits nothing, shades nothing, draws nothing.
 // The model, the bounce count and the sizes are kernel arguments and so WAVE-UNIFORM: in the grid variants every lane of a wave enters every
 // shared-test walk together (pt_trace_coop.hpp).
 // The optimistic / exact pair is per BLOCK, as in the pass's in-block resolve: a block one of whose primary, shadow or bounce rays the guard
@@ -467,8 +420,7 @@ __global__ void PT_VIEW_BOUNDS(GRIDS) k_viewPass(const FusedArgs A, const ViewAr
     const uint32_t id = blk * 256u + threadIdx.x;   // (count <= 2^32 - 256: pt_view_plan.hpp)
     const bool valid = id < count;
     int32_t seed = 0;
-    Ray ray;   // a lane without a ray rides along dead: it enters the shared walks and tests nothing of its own
-    ray.o = mk3(0.0f, 0.0f, 0.0f); ray.d = mk3(0.0f, 0.0f, 0.0f); ray.mint = 0.0f; ray.maxt = 0.0f;
+    Ray ray = dead_ray();
     if (valid) {
         seed = seeds[id];
         ray = view_ray(V, id);
@@ -484,11 +436,7 @@ __global__ void PT_VIEW_BOUNDS(GRIDS) k_viewPass(const FusedArgs A, const ViewAr
     __shared__ __attribute__((aligned(16))) float park_mem[4][256];
 #endif
     bool defer = false;
-    Poi poi;   // as initTrace resets it (code.cl:538-541)
-    poi.p = mk3(0.0f, 0.0f, 0.0f);
-    poi.n = mk3(0.0f, 0.0f, 0.0f);
-    poi.atte = mk3(1.0f, 1.0f, 1.0f);
-    poi.matId = -1;
+    Poi poi = fresh_poi();
     // segment 0 is the camera's ray; segments 1..bounces start with bouncePaths (code.js:1829-1846)
     for (uint32_t seg = 0; seg <= A.bounces; ++seg) {
         if (seg > 0) {
@@ -528,24 +476,15 @@ __global__ void PT_VIEW_BOUNDS(GRIDS) k_viewPass(const FusedArgs A, const ViewAr
     if (FAST && valid && defer) pt_blk_defer[0] = 1u;
     __syncthreads();   // every lane's accumulator is final in LDS, and so is the flag (stage_block cleared it)
     if (FAST && pt_blk_defer[0] != 0u) {   // the whole block goes to the exact kernel: its seeds stay as they were, no pixel of it is written
-        if (threadIdx.x == 0u) atomicOr(&defer_mask[blk >> 5], 1u << (blk & 31u));
+        if (threadIdx.x == 0u) defer_unit(defer_mask, blk);
         return;
     }
     if (valid) seeds[id] = seed;
     resolve_rows(A, &park_mem[0][0], blk, count, (const float*)radiance, radiance, pixel, tone);
 }
 
-template <bool FAST>
-static void launch_viewPass_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const ViewArgs& v, uint32_t count, int32_t* seeds, float4* radiance, uchar4* pixel,
-                              float tone, uint32_t* defer_mask, const uint32_t* redo_mask) {
-    const dim3 grid((unsigned)(((uint64_t)count + 255u) / 256u));
-    fused_lds_dispatch(L, [&](auto G, size_t lds) {
-        if (b.guide_nh || b.guide_ad) hipLaunchKernelGGL((k_viewPass<FAST, decltype(G)::value, true>), grid, dim3(256), lds, s, b, v, count, seeds, radiance, pixel, tone, defer_mask, redo_mask);
-        else hipLaunchKernelGGL((k_viewPass<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, count, seeds, radiance, pixel, tone, defer_mask, redo_mask);
-    });
-}
-// fast: the optimistic kernel (sets the bits of the blocks it hands over in defer_mask); !fast: the exact kernel over the blocks of redo_mask, or
-// over every block when it is null.  a.guide_nh / a.guide_ad (either given): the GUIDES instances, which the caller asks for at rpp 1, 4, 16 or 64 only.
+// fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per BLOCK of the launch.  a.guide_nh / a.guide_ad (either given): the
+// GUIDES instances, which the caller asks for at rpp 1, 4, 16 or 64 only.
 void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
                      uint32_t* defer_mask, const uint32_t* redo_mask) {
     const uint64_t count = (uint64_t)v.nrows * v.width * v.k * v.k;
@@ -555,9 +494,13 @@ void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool 
     b.rpp = v.k * v.k;            // resolve_rows: the rays of a pixel (stage_block's lens table of it is k words nobody reads)
     b.seg_len = b.rpp;            // ... all of them in one block
     b.seg_off = accumulate ? 1u : 0u;   // ... and whether the chain goes on from the carry
-    const FusedLds L = fused_lds_slots(b, fast);
-    if (fast) launch_viewPass_t<true>(s, b, L, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, defer_mask, nullptr);
-    else launch_viewPass_t<false>(s, b, L, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, nullptr, redo_mask);
+    const dim3 grid((unsigned)((count + 255u) / 256u));
+    query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+        constexpr bool FAST = decltype(F)::value;
+        constexpr int GRIDS = decltype(G)::value;
+        if (b.guide_nh || b.guide_ad) hipLaunchKernelGGL((k_viewPass<FAST, GRIDS, true>), grid, dim3(256), lds, s, b, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, dm, rm);
+        else hipLaunchKernelGGL((k_viewPass<FAST, GRIDS>), grid, dim3(256), lds, s, b, v, (uint32_t)count, seeds, (float4*)radiance, (uchar4*)pixel, tone, dm, rm);
+    });
 }
 
 // ---- first-hit guides of a view camera's tile (mirt_view_guides): k_guides (pt_kernels_guides.hip) with the ray of a sample made by view_ray
@@ -566,9 +509,9 @@ void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool 
 // caller's basis as given, not of unit length); a sample is a hit iff 0 <= Poi.matId < A.nmat.
 // Structure: k_guides' -- one lane per pixel walking its samples in order, the eight sums in registers, no barrier behind the prologue.  V is a
 // kernel argument: the model's branch is WAVE-UNIFORM, and a DEAD fisheye sample (r > 1) rides through the shared walk as a dead ray and is never
-// a hit.  In the grid variants a lane past the end of the tile rides along on the last pixel (clamped) and a wave without a pixel leaves at the
-// ballot.  The optimistic / exact pair is per PIXEL, a bit per pixel: a pixel one of whose samples the ray-side guard refuses (it goes on dead,
-// guard_or_retire) or whose walk defers sets its bit and writes nothing; the exact kernel redoes the marked pixels whole.
+// a hit.  In the grid variants a lane past the end of the tile rides along (nothing_to_do) on the last pixel (clamped).  The optimistic / exact
+// pair is per PIXEL (defer_unit): a pixel defers when the ray-side guard refuses one of its samples (it goes on dead, guard_or_retire) or one of
+// its walks defers.
 struct ViewGuideHooks : ClosestHooks {
     PT_DEV void guard(Ray& ray, bool& defer) const { guard_or_retire(ray, defer); }
     PT_DEV void top(Ray& ray) const { keep_in_loop(ray); }
@@ -579,10 +522,8 @@ __global__ void __launch_bounds__(256) k_viewGuides(const FusedArgs A, const Vie
     stage_block<FAST, GRIDS>(A);
     const uint32_t npix = V.nrows * V.width;   // (a tile holds at most 2^32 - 256 rays: pt_view_plan.hpp)
     uint32_t pix = blockIdx.x * 256u + threadIdx.x;
-    bool valid = pix < npix;
-    if (!FAST && redo_mask && valid) valid = (redo_mask[pix >> 5] >> (pix & 31u) & 1u) != 0u;
-    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
-    else if (!valid) return;
+    const bool valid = unit_valid<FAST>(pix, npix, redo_mask);
+    if (nothing_to_do<GRIDS>(valid)) return;
     if (pix >= npix) pix = npix - 1u;
     const float4* material = (const float4*)A.material;
     float nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, depth = 0.0f;
@@ -590,11 +531,7 @@ __global__ void __launch_bounds__(256) k_viewGuides(const FusedArgs A, const Vie
     const uint32_t rpp = V.k * V.k, first = pix * rpp;
     for (uint32_t i = 0; i < rpp; ++i) {
         Ray ray = view_ray(V, first + i);
-        Poi poi;   // as initTrace resets it (code.cl:538-541)
-        poi.p = mk3(0.0f, 0.0f, 0.0f);
-        poi.n = mk3(0.0f, 0.0f, 0.0f);
-        poi.atte = mk3(1.0f, 1.0f, 1.0f);
-        poi.matId = -1;
+        Poi poi = fresh_poi();
         closest_all<FAST, GRIDS>(A, ray, poi, ViewGuideHooks{}, defer);
         if (poi.matId < 0 || (uint32_t)poi.matId >= A.nmat) continue;
         const float4 c = material[poi.matId];
@@ -602,31 +539,22 @@ __global__ void __launch_bounds__(256) k_viewGuides(const FusedArgs A, const Vie
         ar += c.x; ag += c.y; ab += c.z; depth += ray.maxt;
     }
     if (!valid) return;
-    if (FAST && defer) {   // the exact kernel redoes the pixel: nothing of it is written
-        atomicOr(&defer_mask[pix >> 5], 1u << (pix & 31u));
-        return;
-    }
+    if (FAST && defer) { defer_unit(defer_mask, pix); return; }
     if (normal_hits) normal_hits[pix] = make_float4(nx, ny, nz, hits);
     if (albedo_depth) albedo_depth[pix] = make_float4(ar, ag, ab, depth);
 }
 
-template <bool FAST>
-static void launch_viewGuides_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const ViewArgs& v, uint32_t blocks, float4* nh, float4* ad, uint32_t* defer_mask,
-                                const uint32_t* redo_mask) {
-    const dim3 grid(blocks);
-    fused_lds_dispatch(L, [&](auto G, size_t lds) { hipLaunchKernelGGL((k_viewGuides<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, nh, ad, defer_mask, redo_mask); });
-}
-// fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
-// of redo_mask, or over every pixel when it is null.  Either output may be null.  blocks: ceil(pixels / 256), the plan's (pt_view_plan.hpp).
+// fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per pixel of the tile.  Either output may be null.
+// blocks: ceil(pixels / 256), the plan's (pt_view_plan.hpp).
 void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask,
                        const uint32_t* redo_mask) {
     if (!blocks) return;
     FusedArgs b = a;
     b.width = v.width; b.nrows = v.nrows;
     b.rpp = v.k * v.k;   // stage_block, as launch_viewPass sets it (the lens table of it is k words nobody reads)
-    const FusedLds L = fused_lds_slots(b, fast);
-    if (fast) launch_viewGuides_t<true>(s, b, L, v, blocks, (float4*)normal_hits, (float4*)albedo_depth, defer_mask, nullptr);
-    else launch_viewGuides_t<false>(s, b, L, v, blocks, (float4*)normal_hits, (float4*)albedo_depth, nullptr, redo_mask);
+    query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+        hipLaunchKernelGGL((k_viewGuides<decltype(F)::value, decltype(G)::value>), dim3(blocks), dim3(256), lds, s, b, v, (float4*)normal_hits, (float4*)albedo_depth, dm, rm);
+    });
 }
 
 // ---- ambient occlusion of a view camera's tile (mirt_view_ao): k_ao with the ray of a sample made by view_ray instead of primary_ray, and so
@@ -635,11 +563,10 @@ void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uin
 // scalar loads moved in all six instances), and that kernel's rule is identical code.  A change to one is a change to both.  The definition is
 // include/mirt.h's.
 // Structure: k_ao's and k_viewGuides' -- one lane per pixel walking its samples in order; V and `samples` are kernel arguments, so the model's
-// branch and the trip count are WAVE-UNIFORM.  A DEAD fisheye sample, a sample the guard retired, a lane past the tile (on the clamped last
-// pixel) and a redo kernel's unmarked lane ride along with a dead ray: they hit nothing, cast nothing and count nothing.  A wave without a pixel
-// leaves at the ballot.  The optimistic / exact pair is per PIXEL, a bit per pixel: a pixel one of whose view or AO rays the guard refuses, or
-// whose walk defers, sets its bit and writes nothing; the exact kernel redoes the marked pixels whole.  seeds: int32 per tile-local ray, read
-// for the casting samples and never written.  ao_out: {open, cast} per tile-local pixel, one 8-byte store.
+// branch and the trip count are WAVE-UNIFORM.  A DEAD fisheye sample, a sample the guard retired and a lane that rides along (nothing_to_do; on
+// the clamped last pixel when it is past the tile) go on with a dead ray: they hit nothing, cast nothing and count nothing.  The optimistic /
+// exact pair is per PIXEL (defer_unit): a pixel defers when the guard refuses one of its view or AO rays or one of its walks defers.
+// seeds: int32 per tile-local ray, read for the casting samples and never written.  ao_out: {open, cast} per tile-local pixel, one 8-byte store.
 // Waves per SIMD the register allocator is held to: A/B switches of this kernel's own, starting from k_ao's (profiles/view_ao/README.md has the
 // registers per instance and the measurement).  At 1920 x 1080 x 4 with 4 AO rays on cornell_teapot3, equirect / oblique orthographic: 2.39 / 1.79 ms
 // (4 waves) -> 2.22 / 1.77 (5) -> 2.22 / 1.85 (6): the bounds stay k_ao's.
@@ -656,10 +583,8 @@ __global__ void PT_VIEW_AO_BOUNDS(GRIDS) k_viewAo(const FusedArgs A, const ViewA
     stage_block<FAST, GRIDS>(A);
     const uint32_t npix = V.nrows * V.width;   // (a tile holds at most 2^32 - 256 rays: pt_view_plan.hpp)
     uint32_t pix = blockIdx.x * 256u + threadIdx.x;
-    bool valid = pix < npix;
-    if (!FAST && redo_mask && valid) valid = (redo_mask[pix >> 5] >> (pix & 31u) & 1u) != 0u;
-    if (GRIDS) { if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return; }
-    else if (!valid) return;
+    const bool valid = unit_valid<FAST>(pix, npix, redo_mask);
+    if (nothing_to_do<GRIDS>(valid)) return;
     if (pix >= npix) pix = npix - 1u;
     uint32_t open = 0u, cast = 0u;
     bool defer = false;
@@ -667,18 +592,13 @@ __global__ void PT_VIEW_AO_BOUNDS(GRIDS) k_viewAo(const FusedArgs A, const ViewA
     for (uint32_t i = 0; i < rpp; ++i) {
         Ray ray = view_ray(V, first + i);
         if (!valid) { ray.mint = 0.0f; ray.maxt = 0.0f; }   // rides along dead: hits nothing, casts nothing
-        Poi poi;   // as initTrace resets it (code.cl:538-541)
-        poi.p = mk3(0.0f, 0.0f, 0.0f);
-        poi.n = mk3(0.0f, 0.0f, 0.0f);
-        poi.atte = mk3(1.0f, 1.0f, 1.0f);
-        poi.matId = -1;
+        Poi poi = fresh_poi();
         closest_all<FAST, GRIDS>(A, ray, poi, ViewGuideHooks{}, defer);
         const bool casts = poi.matId >= 0;   // bouncePaths' own test (code.cl:592): no material is read
         int32_t seed = 0;
         if (casts) seed = seeds[first + i];
         for (uint32_t j = 0; j < samples; ++j) {
-            Ray sh;
-            sh.o = mk3(0.0f, 0.0f, 0.0f); sh.d = mk3(0.0f, 0.0f, 0.0f); sh.mint = 0.0f; sh.maxt = 0.0f;
+            Ray sh = dead_ray();
             if (casts) {
                 sh = bounce_ray(poi, seed);   // getHemisphereRay (code.cl:545-579): the seed advances, in its register only
                 if (bias != 0.0f) sh.o = add3(poi.p, scl3(bias, poi.n));   // two fp32 operations, each rounded on its own (-ffp-contract=off)
@@ -692,32 +612,21 @@ __global__ void PT_VIEW_AO_BOUNDS(GRIDS) k_viewAo(const FusedArgs A, const ViewA
         }
     }
     if (!valid) return;
-    if (FAST && defer) {   // the exact kernel redoes the pixel: nothing of it is written
-        atomicOr(&defer_mask[pix >> 5], 1u << (pix & 31u));
-        return;
-    }
+    if (FAST && defer) { defer_unit(defer_mask, pix); return; }
     ao_out[pix] = make_uint2(open, cast);
 }
 
-template <bool FAST>
-static void launch_viewAo_t(hipStream_t s, const FusedArgs& b, const FusedLds& L, const ViewArgs& v, uint32_t blocks, uint32_t samples, float radius, float bias,
-                            const int32_t* seeds, uint2* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
-    const dim3 grid(blocks);
-    fused_lds_dispatch(L, [&](auto G, size_t lds) {
-        hipLaunchKernelGGL((k_viewAo<FAST, decltype(G)::value>), grid, dim3(256), lds, s, b, v, samples, radius, bias, seeds, ao_out, defer_mask, redo_mask);
-    });
-}
-// fast: the optimistic kernel (sets the deferred pixels' bits in defer_mask, one per pixel of the tile); !fast: the exact kernel over the pixels
-// of redo_mask, or over every pixel when it is null.  blocks: ceil(pixels / 256), the plan's (pt_view_plan.hpp).
+// fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per pixel of the tile.  blocks: ceil(pixels / 256), the plan's
+// (pt_view_plan.hpp).
 void launch_viewAo(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, uint32_t samples, float radius, float bias, const int32_t* seeds,
                    void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
     if (!blocks) return;
     FusedArgs b = a;
     b.width = v.width; b.nrows = v.nrows;
     b.rpp = v.k * v.k;   // stage_block, as launch_viewGuides sets it
-    const FusedLds L = fused_lds_slots(b, fast);
-    if (fast) launch_viewAo_t<true>(s, b, L, v, blocks, samples, radius, bias, seeds, (uint2*)ao_out, defer_mask, nullptr);
-    else launch_viewAo_t<false>(s, b, L, v, blocks, samples, radius, bias, seeds, (uint2*)ao_out, nullptr, redo_mask);
+    query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
+        hipLaunchKernelGGL((k_viewAo<decltype(F)::value, decltype(G)::value>), dim3(blocks), dim3(256), lds, s, b, v, samples, radius, bias, seeds, (uint2*)ao_out, dm, rm);
+    });
 }
 
 }  // namespace pt
