@@ -543,14 +543,17 @@ napi_value RadianceDeferred(napi_env env, napi_callback_info info) {
 // renderView(ctx, desc, viewDesc, seeds, radiance, pixel): the frame in one launch (mirt_render_view) -- seeds (int32 per tile ray) advanced in
 // place, radiance (float4 per tile pixel) and / or pixel (RGBA8), either may be null; of desc the sets, lights, material and bounces (left out: 5)
 // are read.  viewDeferred(ctx) -> how many rays the last renderView re-ran in the exact kernel, in whole blocks (mirt_view_deferred).
-static bool read_view(napi_env env, napi_value d, const char* who, mirt_view_desc& v) {
+static bool read_view(napi_env env, napi_value d, const char* who, mirt_view_desc& v, bool with_basis = true) {
     memset(&v, 0, sizeof v);
     v.struct_size = sizeof v;
     v.k = 1u;
     v.half_w = 1.0f; v.half_h = 1.0f; v.half_angle = 0x1.921fb6p+0f; v.t_min = 0.0f; v.t_max = INFINITY; v.tone = 1.0f;
     napi_valuetype t = napi_undefined;
-    if (napi_typeof(env, d, &t) != napi_ok || t != napi_object || !prop_u32(env, d, "width", &v.width) || !prop_u32(env, d, "height", &v.height) ||
-        !prop_floats(env, d, "eye", v.eye, 3) || !prop_floats(env, d, "right", v.right, 3) || !prop_floats(env, d, "up", v.up, 3) || !prop_floats(env, d, "forward", v.forward, 3)) {
+    if (napi_typeof(env, d, &t) != napi_ok || t != napi_object || !prop_u32(env, d, "width", &v.width) || !prop_u32(env, d, "height", &v.height)) {
+        throw_type(env, (std::string(who) + ": the view needs width and height").c_str());
+        return false;
+    }
+    if (with_basis && (!prop_floats(env, d, "eye", v.eye, 3) || !prop_floats(env, d, "right", v.right, 3) || !prop_floats(env, d, "up", v.up, 3) || !prop_floats(env, d, "forward", v.forward, 3))) {
         throw_type(env, (std::string(who) + ": the view needs width, height and eye / right / up / forward (Float32Array of 3 each)").c_str());
         return false;
     }
@@ -681,6 +684,65 @@ napi_value RenderView(napi_env env, napi_callback_info info) {
     mirt_view_desc v;
     if (!read_view(env, argv[2], "renderView", v)) return nullptr;
     const int rc = mirt_render_view((mirt_ctx*)c, &p, &v, (mirt_buf*)seeds, (mirt_buf*)radiance, (mirt_buf*)pixel);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+// Batched view cameras.  cameras: a Float32Array of 12 per frame -- eye, right, up, forward -- whose length gives the number of frames; viewDesc as
+// above without eye / right / up / forward, which a batch does not read.  viewRaysBatch(ctx, viewDesc, cameras, rays): the frames' rays, frame
+// after frame (mirt_view_rays_batch).  renderViewBatch(ctx, desc, viewDesc, cameras, seeds, radiance, pixel): the frames in one launch
+// (mirt_render_view_batch), the buffers holding them back to back.
+static bool read_cameras(napi_env env, napi_value a, const char* who, const mirt_view_camera** cams, uint32_t* n) {
+    void* data = nullptr;
+    size_t nb = 0;
+    bool is_typed = false;
+    napi_typedarray_type type = napi_uint8_array;
+    size_t length = 0, offset = 0;
+    napi_value buffer;
+    if (napi_is_typedarray(env, a, &is_typed) != napi_ok || !is_typed || napi_get_typedarray_info(env, a, &type, &length, &data, &buffer, &offset) != napi_ok ||
+        type != napi_float32_array || !get_bytes(env, a, &data, &nb) || nb % sizeof(mirt_view_camera) != 0 ||
+        nb / sizeof(mirt_view_camera) > 0xFFFFFFFFull) {
+        throw_type(env, (std::string(who) + ": cameras is a Float32Array of 12 per frame (eye, right, up, forward)").c_str());
+        return false;
+    }
+    *cams = nb ? (const mirt_view_camera*)data : nullptr;
+    *n = (uint32_t)(nb / sizeof(mirt_view_camera));
+    return true;
+}
+napi_value ViewRaysBatch(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    void *c, *rays = nullptr;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "viewRaysBatch(ctx, viewDesc, cameras, rays)");
+    get_ext(env, argv[3], &rays);
+    mirt_view_desc v;
+    const mirt_view_camera* cams = nullptr;
+    uint32_t n = 0;
+    if (!read_view(env, argv[1], "viewRaysBatch", v, false) || !read_cameras(env, argv[2], "viewRaysBatch", &cams, &n)) return nullptr;
+    const int rc = mirt_view_rays_batch((mirt_ctx*)c, &v, cams, n, (mirt_buf*)rays);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value RenderViewBatch(napi_env env, napi_callback_info info) {
+    ARGS(7);
+    void *c, *seeds = nullptr, *radiance = nullptr, *pixel = nullptr;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "renderViewBatch(ctx, desc, viewDesc, cameras, seeds, radiance, pixel)");
+    get_ext(env, argv[4], &seeds);
+    get_ext(env, argv[5], &radiance);
+    get_ext(env, argv[6], &pixel);
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    p.bounces = 5;
+    prop_u32(env, argv[1], "bounces", &p.bounces);
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    std::vector<mirt_light> lights;
+    if (!read_sets(env, argv[1], "renderViewBatch", p, sph, tri, meshes) || !read_lights(env, argv[1], "renderViewBatch", p, lights)) return nullptr;
+    p.material = prop_buf(env, argv[1], "material");
+    mirt_view_desc v;
+    const mirt_view_camera* cams = nullptr;
+    uint32_t n = 0;
+    if (!read_view(env, argv[2], "renderViewBatch", v, false) || !read_cameras(env, argv[3], "renderViewBatch", &cams, &n)) return nullptr;
+    const int rc = mirt_render_view_batch((mirt_ctx*)c, &p, &v, cams, n, (mirt_buf*)seeds, (mirt_buf*)radiance, (mirt_buf*)pixel);
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);
 }
@@ -1128,7 +1190,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"viewGuides", ViewGuides}, {"viewAo", ViewAo}, {"viewAoDeferred", ViewAoDeferred}, {"renderViewGuided", RenderViewGuided}, {"ctxGuidedViews", CtxGuidedViews}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"viewRaysBatch", ViewRaysBatch}, {"renderViewBatch", RenderViewBatch}, {"viewGuides", ViewGuides}, {"viewAo", ViewAo}, {"viewAoDeferred", ViewAoDeferred}, {"renderViewGuided", RenderViewGuided}, {"ctxGuidedViews", CtxGuidedViews}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"renderAo", RenderAo}, {"aoDeferred", AoDeferred}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

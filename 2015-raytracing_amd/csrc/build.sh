@@ -11,7 +11,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden
        -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize
        -Wall -Wextra -Wno-unused-parameter)
-SRC=("${HERE}/mirt_abi.cpp" "${HERE}/pt_kernels_granular.hip" "${HERE}/pt_kernels_fused.hip" "${HERE}/pt_kernels_guides.hip" "${HERE}/pt_kernels_rays.hip" "${HERE}/pt_kernels_filter.hip" "${HERE}/pt_kernels_upsample.hip" "${HERE}/pt_kernels_frame.hip" "${HERE}/pt_grid_build.hip")
+SRC=("${HERE}/mirt_abi.cpp" "${HERE}/pt_kernels_granular.hip" "${HERE}/pt_kernels_fused.hip" "${HERE}/pt_kernels_guides.hip" "${HERE}/pt_kernels_rays.hip" "${HERE}/pt_kernels_view_batch.hip" "${HERE}/pt_kernels_filter.hip" "${HERE}/pt_kernels_upsample.hip" "${HERE}/pt_kernels_frame.hip" "${HERE}/pt_grid_build.hip")
 # libmirt_default.so -- the SECOND numerics contract: the reference as its own host builds it, program.build() without options (A10 code.js:599),
 # i.e. AMD's default 2.5-ulp division and 3-ulp sqrt.  Same sources: -fno-hip-fp32-correctly-rounded-divide-sqrt makes every `/` and sqrt the
 # sequence AMD's OpenCL compiler emits without -cl-fp32-correctly-rounded-divide-sqrt (the same LLVM lowering: frexp-scaled v_rcp_f32, ldexp-scaled

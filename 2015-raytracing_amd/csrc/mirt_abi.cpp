@@ -87,6 +87,12 @@ struct mirt_ctx {
     // no counter), mirt_trace_closest / mirt_trace_occluded (per ray), mirt_render_ao (per pixel), mirt_trace_radiance (per ray), mirt_render_view (per
     // block of 256 rays) and mirt_view_ao (per pixel).
     DeferMask pass_mask, guide_mask, ray_mask, ao_mask, rad_mask, view_mask, view_ao_mask;
+    // The camera table of the batch calls (mirt_view_rays_batch, mirt_render_view_batch): ONE device allocation, filled on the stream by launches
+    // whose ARGUMENTS carry the cameras (pt_launch.hpp launch_viewCameras) -- the host array is read while the call runs, and a call queued behind
+    // a running one overwrites the table only after that one's kernels.  A call with more frames than the table holds waits for the stream once,
+    // frees it and allocates twice the need (upload_cameras); every other call waits for nothing.
+    void* camera_table = nullptr;
+    size_t camera_table_bytes = 0;
     bool inpass_resolve = true;   // a pass writes pixel / radiance itself where it can (MIRT_INPASS_RESOLVE=0: always the separate copyToPixel)
     bool last_pass_resolved = false;   // render_pass_impl: the pass just queued resolved its own pixels
     int force_exact = 0;          // mirt_ctx_set_exact_only: 1 = skip the optimistic kernel, run every sample through the exact one
@@ -493,6 +499,7 @@ static int destroy_ctx(mirt_ctx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     for (DeferMask* m : {&ctx->pass_mask, &ctx->guide_mask, &ctx->ray_mask, &ctx->ao_mask, &ctx->rad_mask, &ctx->view_mask, &ctx->view_ao_mask})
         if (m->ptr) (void)hipFree(m->ptr);
+    if (ctx->camera_table) (void)hipFree(ctx->camera_table);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (auto& e : ctx->pe) if (e) (void)hipEventDestroy(e);
@@ -1859,6 +1866,7 @@ static int view_verdict(mirt_ctx* ctx, const char* fn, pt::ViewVerdict v, const 
         case pt::VIEW_AO_BIAS: return fail(ctx, code, "%s: bias is not a finite number >= 0", fn);
         case pt::VIEW_AO_NO_SEEDS: return fail(ctx, code, "%s: seeds is NULL (the AO rays draw from them; they are not written)", fn);
         case pt::VIEW_AO_NO_OUTPUT: return fail(ctx, code, "%s: ao_out is NULL", fn);
+        case pt::VIEW_BATCH_TILE: case pt::VIEW_BATCH_NO_CAMERAS: case pt::VIEW_BATCH_CAMERA: case pt::VIEW_BATCH_RAYS: break;   // view_batch_verdict's, below
     }
     return fail(ctx, MIRT_E_ARG, "%s: view descriptor refused", fn);
 }
@@ -1900,10 +1908,52 @@ static int queue_view_guides(mirt_ctx* ctx, const pt::FusedArgs& A, const pt::Vi
 // MIRT_GUIDED_VIEW=0: mirt_render_view_guided always queues the frame and then the guide launches -- an A/B and test switch, read per call
 static bool guided_view_enabled() { const char* e = getenv("MIRT_GUIDED_VIEW"); return !(e && e[0] == '0'); }
 
+// ---- batched view cameras (mirt_view_rays_batch, mirt_render_view_batch): n_frames cameras' frames of one descriptor as ONE image of
+// n_frames * height rows through k_viewRaysBatch and k_viewPassBatch (pt_kernels_view_batch.hip).  The checks and the plan are pt_view_plan.hpp's
+// (view_check_batch, view_batch_plan); here are the messages and the camera table.
+static_assert(sizeof(pt::ViewCamera) == sizeof(mirt_view_camera) && sizeof(mirt_view_camera) == 48 && offsetof(pt::ViewCamera, right) == offsetof(mirt_view_camera, right) &&
+              offsetof(pt::ViewCamera, up) == offsetof(mirt_view_camera, up) && offsetof(pt::ViewCamera, forward) == offsetof(mirt_view_camera, forward),
+              "pt_view_plan.hpp restates the header's camera");
+static int view_batch_verdict(mirt_ctx* ctx, const char* fn, pt::ViewVerdict v, const pt::ViewDesc& d, uint32_t n_frames, uint32_t bad_frame) {
+    switch (v) {
+        case pt::VIEW_BATCH_TILE: return fail(ctx, MIRT_E_ARG, "%s: row tile [%u,+%u): a batch renders whole frames only (row0 0, nrows 0 or height)", fn, d.row0, d.nrows);
+        case pt::VIEW_BATCH_NO_CAMERAS: return fail(ctx, MIRT_E_ARG, "%s: cameras is NULL with %u frames", fn, n_frames);
+        case pt::VIEW_BATCH_CAMERA: return fail(ctx, MIRT_E_ARG, "%s: a component of eye, right, up or forward of the camera of frame %u is not finite", fn, bad_frame);
+        case pt::VIEW_BATCH_RAYS: return fail(ctx, MIRT_E_ARG, "%s: %u frames of %u x %u x %u rays are more than 2^32 - 256 rays (the kernels index the batch's rays with 32 bits); render fewer frames per call", fn, n_frames, d.width, d.height, d.k * d.k);
+        default: return view_verdict(ctx, fn, v, d);
+    }
+}
+// The host array into the context's device table, in stream order.  *table: where the kernels read it.  Only growing the table waits for the
+// stream (the one in place may still be read); it grows to twice the need, so a caller whose batches grow stalls a logarithmic number of times.
+static int upload_cameras(mirt_ctx* ctx, const mirt_view_camera* cameras, uint32_t n_frames, const float** table) {
+    const size_t bytes = (size_t)n_frames * sizeof(mirt_view_camera);
+    if (ctx->camera_table_bytes < bytes) {
+        if (ctx->camera_table) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->camera_table)); ctx->camera_table = nullptr; ctx->camera_table_bytes = 0; }
+        HIPCHK(ctx, hipMalloc(&ctx->camera_table, 2 * bytes));
+        ctx->camera_table_bytes = 2 * bytes;
+    }
+    pt::launch_viewCameras(ctx->stream, &cameras[0].eye[0], n_frames, (float*)ctx->camera_table);
+    HIPCHK(ctx, hipGetLastError());
+    *table = (const float*)ctx->camera_table;
+    return MIRT_OK;
+}
+static pt::ViewBatchArgs view_batch_args(const pt::ViewDesc& d, const pt::ViewBatchPlan& plan, const float* table) {
+    pt::ViewBatchArgs V;
+    memset(&V, 0, sizeof V);
+    static_cast<pt::ViewArgs&>(V) = view_args(d, plan.all);
+    for (int c = 0; c < 3; ++c) V.eye[c] = V.right[c] = V.up[c] = V.forward[c] = 0.0f;   // not read: the table has the cameras
+    V.row0 = 0u;
+    V.cameras = table;
+    V.frame_rows = plan.frame_rows;
+    return V;
+}
+
 // mirt_render_view (guided false: seeds, radiance, pixel), mirt_view_guides (frame false: normal_hits, albedo_depth) and mirt_render_view_guided
 // (all five): one list of checks, every one before anything is queued, then the launches.
-static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guided, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance,
-                            mirt_buf* pixel, mirt_buf* normal_hits, mirt_buf* albedo_depth) {
+// The frames of a batch: the host array and its length (mirt_render_view_batch); nullptr for the single calls
+struct ViewBatch { const mirt_view_camera* cameras; uint32_t n_frames; };
+static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guided, const mirt_pass_desc* d, const mirt_view_desc* vd, const ViewBatch* batch, mirt_buf* seeds,
+                            mirt_buf* radiance, mirt_buf* pixel, mirt_buf* normal_hits, mirt_buf* albedo_depth) {
     ENTRY_PROLOGUE(ctx, fn);
     if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
     if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
@@ -1911,11 +1961,14 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
     memcpy(&v, vd, sizeof v);
     int rc;
     const bool nh = normal_hits != nullptr, ad = albedo_depth != nullptr;
-    const pt::ViewVerdict verdict = !frame   ? pt::view_check_guides(v, nh, ad)
+    uint32_t bad_frame = 0;
+    const pt::ViewVerdict verdict = batch    ? pt::view_check_render_batch(v, (const pt::ViewCamera*)batch->cameras, batch->n_frames, seeds != nullptr, radiance != nullptr, pixel != nullptr, &bad_frame)
+                                    : !frame ? pt::view_check_guides(v, nh, ad)
                                     : guided ? pt::view_check_render_guided(v, seeds != nullptr, radiance != nullptr, pixel != nullptr, nh, ad)
                                              : pt::view_check_render(v, seeds != nullptr, radiance != nullptr, pixel != nullptr);
-    if ((rc = view_verdict(ctx, fn, verdict, v))) return rc;
-    const pt::ViewPlan plan = pt::view_plan(v);
+    if ((rc = batch ? view_batch_verdict(ctx, fn, verdict, v, batch->n_frames, bad_frame) : view_verdict(ctx, fn, verdict, v))) return rc;
+    const pt::ViewBatchPlan bplan = batch ? pt::view_batch_plan(v, batch->n_frames) : pt::ViewBatchPlan();
+    const pt::ViewPlan plan = batch ? bplan.all : pt::view_plan(v);   // the batch: the plan of the stacked image, the checks below on the whole batch buffers
     // the pass's own limits and rules for its arrays, as mirt_trace_radiance has them (the guides alone read no light)
     if ((rc = check_desc_arrays(ctx, fn, d, frame, "light/mesh"))) return rc;
     // everything given is written: the bytes the call touches of them, against each other's, the geometry's buffers and the material whole
@@ -1929,6 +1982,7 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
                                  !frame   ? "%s: normal_hits aliases albedo_depth"
                                  : guided ? "%s: seeds, radiance, pixel and the guides meet one another"
                                           : "%s: seeds, radiance and pixel meet one another"))) return rc;
+    if (batch && !batch->n_frames) return MIRT_OK;   // no frames: nothing is queued, not even the geometry's preparation
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pt::FusedArgs A;
     memset(&A, 0, sizeof A);
@@ -1937,6 +1991,13 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
     if ((rc = fill_sets(ctx, fn, d, A))) return rc;
     if ((rc = fill_shading(ctx, d, A, true))) return rc;
     const pt::ViewArgs V = view_args(v, plan);
+    pt::ViewBatchArgs VB;
+    memset(&VB, 0, sizeof VB);
+    if (batch) {
+        const float* table = nullptr;
+        if ((rc = upload_cameras(ctx, batch->cameras, batch->n_frames, &table))) return rc;
+        VB = view_batch_args(v, bplan, table);
+    }
     void* const nhp = normal_hits ? normal_hits->ptr : nullptr;
     void* const adp = albedo_depth ? albedo_depth->ptr : nullptr;
     if (frame) {
@@ -1947,7 +2008,8 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
         pt::FusedArgs F = A;
         if (in_pass) { F.guide_nh = nhp; F.guide_ad = adp; }
         rc = queue_pair(ctx, ctx->view_mask, A, plan.mask_words, 256u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {   // a bit is a block of 256 rays
-            pt::launch_viewPass(ctx->stream, F, V, fast, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask_out, mask_in);
+            if (batch) pt::launch_viewPassBatch(ctx->stream, F, VB, fast, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask_out, mask_in);
+            else pt::launch_viewPass(ctx->stream, F, V, fast, accumulate, (int32_t*)seeds->ptr, rp, pp, v.tone, mask_out, mask_in);
         });
         if (rc) return rc;
         if (in_pass) ctx->guided_views++;
@@ -1957,20 +2019,51 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
 }
 
 int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel) try {
-    return render_view_impl(ctx, "mirt_render_view", true, false, d, vd, seeds, radiance, pixel, nullptr, nullptr);
+    return render_view_impl(ctx, "mirt_render_view", true, false, d, vd, nullptr, seeds, radiance, pixel, nullptr, nullptr);
 } MIRT_CATCH("mirt_render_view", return MIRT_E_DEVICE)
+
+int mirt_view_rays_batch(mirt_ctx* ctx, const mirt_view_desc* vd, const mirt_view_camera* cameras, uint32_t n_frames, mirt_buf* rays) try {
+    const char* const fn = "mirt_view_rays_batch";
+    ENTRY_PROLOGUE(ctx, fn);
+    if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
+    pt::ViewDesc d;
+    memcpy(&d, vd, sizeof d);
+    int rc;
+    uint32_t bad = 0;
+    const pt::ViewVerdict verdict = pt::view_check_batch(d, (const pt::ViewCamera*)cameras, n_frames, &bad);
+    if ((rc = view_batch_verdict(ctx, fn, verdict, d, n_frames, bad))) return rc;
+    const pt::ViewBatchPlan plan = pt::view_batch_plan(d, n_frames);
+    if (!rays) return fail(ctx, MIRT_E_HANDLE, "%s: rays is NULL", fn);
+    if ((rc = need(ctx, "mirt_view_rays_batch rays", rays, plan.all.rays * 32))) return rc;
+    if (!n_frames) return MIRT_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const float* table = nullptr;
+    if ((rc = upload_cameras(ctx, cameras, n_frames, &table))) return rc;
+    pt::launch_viewRaysBatch(ctx->stream, view_batch_args(d, plan, table), rays->ptr);
+    HIPCHK(ctx, hipGetLastError());
+    rays->version++;
+    return MIRT_OK;
+} MIRT_CATCH("mirt_view_rays_batch", return MIRT_E_DEVICE)
+
+// The frames of n_frames cameras: mirt_render_view's list of checks on the whole batch buffers, its fills and its pair, with the batch's verdicts,
+// plan and kernel instances (render_view_impl).
+int mirt_render_view_batch(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, const mirt_view_camera* cameras, uint32_t n_frames, mirt_buf* seeds,
+                           mirt_buf* radiance, mirt_buf* pixel) try {
+    const ViewBatch batch = {cameras, n_frames};
+    return render_view_impl(ctx, "mirt_render_view_batch", true, false, d, vd, &batch, seeds, radiance, pixel, nullptr, nullptr);
+} MIRT_CATCH("mirt_render_view_batch", return MIRT_E_DEVICE)
 
 // First-hit guides of a view camera's tile (pt_kernels_rays.hip k_viewGuides): one launch -- or the optimistic / exact pair, per pixel -- of one
 // lane per pixel.  Nothing but the two outputs is written.
 int mirt_view_guides(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
-    return render_view_impl(ctx, "mirt_view_guides", false, true, d, vd, nullptr, nullptr, nullptr, normal_hits, albedo_depth);
+    return render_view_impl(ctx, "mirt_view_guides", false, true, d, vd, nullptr, nullptr, nullptr, nullptr, normal_hits, albedo_depth);
 } MIRT_CATCH("mirt_view_guides", return MIRT_E_DEVICE)
 
 // The frame and its guides in one call: where a pixel's samples are consecutive lanes of one wave (pt_view_plan.hpp view_guides_in_pass) the
 // frame's own launches write the guides (k_viewPass GUIDES), elsewhere the guide launches follow.
 int mirt_render_view_guided(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel, mirt_buf* normal_hits,
                             mirt_buf* albedo_depth) try {
-    return render_view_impl(ctx, "mirt_render_view_guided", true, true, d, vd, seeds, radiance, pixel, normal_hits, albedo_depth);
+    return render_view_impl(ctx, "mirt_render_view_guided", true, true, d, vd, nullptr, seeds, radiance, pixel, normal_hits, albedo_depth);
 } MIRT_CATCH("mirt_render_view_guided", return MIRT_E_DEVICE)
 
 int mirt_ctx_guided_views(mirt_ctx* ctx, uint64_t* count) try {

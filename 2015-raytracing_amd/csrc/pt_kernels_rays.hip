@@ -36,31 +36,13 @@
 // k_viewRays and k_viewPass, the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view), k_viewGuides, their
 // first-hit guides (mirt_view_guides), and k_viewAo, their ambient occlusion (mirt_view_ao) -- at the end of the file.
 #include "pt_direct.hpp"
+#include "pt_rays_guard.hpp"   // keep_in_loop, guard_or_retire, RadiancePark
 #include "pt_resolve.hpp"   // resolve_rows: k_viewPass resolves its blocks' pixels as the pass does; guides_emit: its GUIDES instances write the guides
 #include "pt_view.hpp"      // view_ray: a sample's ray
 
 namespace pt {
 
-// The default contract only (libmirt_default.so).  The sphere stage's 1 / (2 d.d) depends on the ray alone, so the compiler moves it out of the
-// loop over the sets -- and a division it moves loses the 2.5-ulp licence the build gives every division: it comes out correctly rounded, one
-// ulp off the kernel-by-kernel path's (and the reference's default build's) v_rcp_f32 form wherever the two differ.  A camera's unit-length d
-// never showed it (d.d is within an ulp of 1); a caller's d does.  An empty statement that "changes" d at the top of every trip keeps the
-// division where it is written.  Not a run-time cost: the values stay in their registers.
-PT_DEV void keep_in_loop(Ray& r) {
-#if PT_PLAIN_DIV
-    asm volatile("" : "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z));
-#endif
-}
-
-// The optimistic kernel's ray-side guard (a dead ray divides nothing and is not asked).  A refused ray is the exact kernel's whatever this kernel
-// would compute for it, and nothing of it is written here: it goes on DEAD, riding along in the shared walks like a lane without a ray, so a batch
-// the guard refuses whole -- axis-parallel rays -- costs the optimistic kernel next to nothing.
-PT_DEV void guard_or_retire(Ray& r, bool& defer) {
-    if (r.mint == r.maxt || ray_guard(r)) return;
-    defer = true;
-    r.mint = 0.0f;
-    r.maxt = 0.0f;
-}
+// keep_in_loop, guard_or_retire: pt_rays_guard.hpp
 
 // What this kernel adds to closest_all's loop (pt_closest.hpp ClosestHooks): its own guard, the division kept in the loop, and the index of the
 // last set that won
@@ -265,19 +247,8 @@ void launch_ao(hipStream_t s, const FusedArgs& a, bool fast, uint32_t samples, f
 // measurement).  A lane runs samples * (1 + bounces) segments back to back with nothing to overlap them but other waves, and more waves paid at
 // every step measured, the spilled registers included: at 1920 x 1080 x 4 rays, bounces 5, cornell_teapot3 6.44 (4 waves, 107 VGPRs) -> 5.49 (5,
 // 96 VGPRs) -> 5.08 ms (6, 80 VGPRs, 16 to 20 spilled), cornell 1.29 (5 waves) -> 1.21 (6) -> 1.14 (7, 72 VGPRs, 2 to 8 spilled) -> 1.15 ms (8).
-#ifndef PT_RADIANCE_GRID_WAVES
-#define PT_RADIANCE_GRID_WAVES 6
-#endif
-#ifndef PT_RADIANCE_CELL_WAVES
-#define PT_RADIANCE_CELL_WAVES 7
-#endif
-#define PT_RADIANCE_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_RADIANCE_GRID_WAVES : PT_RADIANCE_CELL_WAVES)
+// (PT_RADIANCE_GRID_WAVES, PT_RADIANCE_CELL_WAVES, PT_RADIANCE_BOUNDS and RadiancePark: pt_rays_guard.hpp)
 constexpr uint32_t kRadianceAccumulate = 1u, kRadianceNoEmitters = 2u;   // MIRT_RADIANCE_ACCUMULATE, MIRT_RADIANCE_NO_EMITTERS (include/mirt.h)
-// the pass's park rows as closest_all's hooks, with this file's guard and kept division in place of the camera kernels'
-struct RadiancePark : Park {
-    PT_DEV void guard(Ray& ray, bool& defer) const { guard_or_retire(ray, defer); }
-    PT_DEV void top(Ray& ray) const { keep_in_loop(ray); }
-};
 template <bool FAST, int GRIDS>
 __global__ void PT_RADIANCE_BOUNDS(GRIDS) k_traceRadiance(const FusedArgs A, const float4* __restrict__ rays, uint32_t count, uint32_t samples, uint32_t flags,
                                                            int32_t* __restrict__ seeds, float4* __restrict__ radiance, uint32_t* defer_mask, const uint32_t* redo_mask) {
@@ -366,134 +337,30 @@ void launch_radiance(hipStream_t s, const FusedArgs& a, bool fast, const void* r
 
 // ---- panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view): the ray of a sample is pt_view.hpp's view_ray, the one
 // definition both kernels call; include/mirt.h defines it operation by operation.
-// k_viewRays: the rays as 32-byte records, one lane per ray, two float4 stores -- memory-bound, nothing else to it.
-__global__ void __launch_bounds__(256) k_viewRays(const ViewArgs V, uint32_t count, float4* __restrict__ rays) {
-    const uint32_t id = blockIdx.x * 256u + threadIdx.x;   // (count <= 2^32 - 256: pt_view_plan.hpp)
-    if (id >= count) return;
-    const Ray r = view_ray(V, id);
-    rays[2u * (size_t)id] = make_float4(r.o.x, r.o.y, r.o.z, r.mint);
-    rays[2u * (size_t)id + 1u] = make_float4(r.d.x, r.d.y, r.d.z, r.maxt);
-}
+}  // namespace pt
+#include "pt_view_pass.hpp"   // the launch bounds and set-up that k_viewRays / k_viewPass share with the batch's translation unit
+namespace pt {
+// k_viewRays, k_viewPass: the single calls' kernels -- the text of pt_view_kernels.inc at BATCH false (the batch calls' are in
+// pt_kernels_view_batch.hip)
+#define PT_VIEW_BATCH false
+#define PT_VIEW_ARGS ViewArgs
+#define PT_VIEW_RAYS_KERNEL k_viewRays
+#define PT_VIEW_PASS_TEMPLATE template <bool FAST, int GRIDS, bool GUIDES = false>
+#define PT_VIEW_PASS_KERNEL k_viewPass
+#include "pt_view_kernels.inc"
 void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays) {
-    const uint64_t count = (uint64_t)v.nrows * v.width * v.k * v.k;
+    const uint64_t count = view_pass_rays(v);
     if (!count) return;
     hipLaunchKernelGGL(k_viewRays, dim3((unsigned)((count + 255u) / 256u)), dim3(256), 0, s, v, (uint32_t)count, (float4*)rays);
-}
-
-// k_viewPass: k_traceRadiance's body at one sample per ray with the ray made in registers by view_ray instead of loaded, and behind the block's
-// barrier the pass's own resolve (pt_resolve.hpp resolve_rows) -- in one launch; neither the rays nor the per-ray accumulators reach memory.
-// A.rpp = A.seg_len = k * k (1, 4, 16, 64 or 256: it divides 256, so a block of 256 consecutive ray ids holds 256 / rpp WHOLE pixels) and
-// A.seg_off != 0 iff the sums go on from `radiance` (MIRT_VIEW_ACCUMULATE: resolve_rows' carry); A.width / A.nrows are the tile's.
-//
-// Structure: one lane per ray.  The generator's registers are dead before the segment loop; the four accumulator words are parked as
-// [channel][lane] rows from the start (they begin at +0: ACCUMULATE is the resolve's business, not the ray's) and read by the resolve where they
-// lie.  Every lane stays to the barrier, so the prologue is the block's own, not unit_valid / nothing_to_do: a lane past the end of the tile
-// rides along dead (dead_ray) -- it hits nothing, shades nothing, draws nothing.
-// The model, the bounce count and the sizes are kernel arguments and so WAVE-UNIFORM: in the grid variants every lane of a wave enters every
-// shared-test walk together (pt_trace_coop.hpp).
-// The optimistic / exact pair is per BLOCK, as in the pass's in-block resolve: a block one of whose primary, shadow or bounce rays the guard
-// refuses, or one of whose walks defers, writes neither its seeds nor its pixels and sets its bit (a bit per block of the launch); the exact
-// kernel runs the same grid and every block without its bit leaves at once.  An ORTHOGRAPHIC camera whose `forward` has a zero component is
-// outside the ray-side guard for EVERY ray (|d_k| >= 2^-40): every block is handed over and the frame comes from the exact kernel, same bits.
-// Waves per SIMD the register allocator is held to: A/B switches of this kernel's own, starting from k_traceRadiance's (profiles/view/README.md
-// has the registers per instance and the measurement).  At 1920 x 1080 x 4 rays, bounces 5, equirect: cornell_teapot3 5.57 (5 waves, 96 VGPRs, no
-// spill) -> 5.20 (6, 80 VGPRs, 17 spilled) -> 5.47 (7) -> 6.90 ms (8 waves, 64 VGPRs, 51 spilled), cornell 1.01 (5 waves) -> 1.00 (6) -> 0.97 (7) -> 0.97 ms (8):
-// the bounds stay k_traceRadiance's.
-#ifndef PT_VIEW_GRID_WAVES
-#define PT_VIEW_GRID_WAVES PT_RADIANCE_GRID_WAVES
-#endif
-#ifndef PT_VIEW_CELL_WAVES
-#define PT_VIEW_CELL_WAVES PT_RADIANCE_CELL_WAVES
-#endif
-#define PT_VIEW_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_VIEW_GRID_WAVES : PT_VIEW_CELL_WAVES)
-// GUIDES (mirt_render_view_guided, the one-launch route: pt_view_plan.hpp view_guides_in_pass): the frame writes the first-hit guides of its
-// pixels too, A.guide_nh / A.guide_ad, by the pass's own lane walk (pt_resolve.hpp guides_emit) right after segment 0's closest_all -- the state
-// k_viewGuides takes them at, reached by the same functions on the same ray ids.  rpp is 1, 4, 16 or 64: a pixel's samples are consecutive lanes
-// of one wave.  As in the pass, the optimistic kernel writes a block's guides before its verdict; a block that defers is re-run whole by the
-// exact kernel, which writes the same pixels' guides again, later on the same stream.  The default, false, keeps the unguided instances' code.
-template <bool FAST, int GRIDS, bool GUIDES = false>
-__global__ void PT_VIEW_BOUNDS(GRIDS) k_viewPass(const FusedArgs A, const ViewArgs V, uint32_t count, int32_t* __restrict__ seeds, float4* radiance,
-                                                   uchar4* __restrict__ pixel, float tone, uint32_t* defer_mask, const uint32_t* redo_mask) {
-    const uint32_t blk = blockIdx.x;
-    if (!FAST && redo_mask && (redo_mask[blk >> 5] >> (blk & 31u) & 1u) == 0u) return;   // block-uniform: nothing of the block has begun
-    stage_block<FAST, GRIDS>(A);
-    const uint32_t id = blk * 256u + threadIdx.x;   // (count <= 2^32 - 256: pt_view_plan.hpp)
-    const bool valid = id < count;
-    int32_t seed = 0;
-    Ray ray = dead_ray();
-    if (valid) {
-        seed = seeds[id];
-        ray = view_ray(V, id);
-    }
-    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // initAcu (A10 code.cl:448-456)
-    RadiancePark park;
-#if PT_PARK_LDS
-    __shared__ __attribute__((aligned(16))) float park_mem[PT_PARK_WORDS(GRIDS)][256];
-    park.base = &park_mem[0][threadIdx.x];
-    park.put(0, 0.0f); park.put(1, 0.0f); park.put(2, 0.0f); park.put(3, 0.0f);
-    park.put(4, 1.0f); park.put(5, 1.0f); park.put(6, 1.0f);
-#else
-    __shared__ __attribute__((aligned(16))) float park_mem[4][256];
-#endif
-    bool defer = false;
-    Poi poi = fresh_poi();
-    // segment 0 is the camera's ray; segments 1..bounces start with bouncePaths (code.js:1829-1846)
-    for (uint32_t seg = 0; seg <= A.bounces; ++seg) {
-        if (seg > 0) {
-            if (poi.matId >= 0) {
-#if PT_PARK_LDS
-                if (PT_PARK_PN_FOR(GRIDS)) park.get_pn(poi);
-#endif
-                ray = bounce_ray(poi, seed);
-            } else {
-                ray.mint = PT_INF;
-                ray.maxt = PT_INF;
-            }
-        }
-        closest_all<FAST, GRIDS>(A, ray, poi, park, defer);
-        if constexpr (GUIDES) if (seg == 0) guides_emit(A, ray, poi, valid, blk);   // every lane of the block is here: none leaves before the barrier
-        if (seg == 0) {
-            for (uint32_t l = 0; l < A.n_lights; ++l) {  // lightRender (code.cl:600-629), on the camera's ray only
-                if (ray.mint == ray.maxt) continue;
-                const LightArgs& L = A.lights[l];
-                f3 irr = norm3(ld3(L.light + 6));
-                if (!light_visible(ray, ld3(L.light), ld3(L.light + 3), L.light[9])) continue;
-                ray.mint = PT_INF;
-                ray.maxt = PT_INF;
-                poi.matId = -1;
-#if PT_PARK_LDS
-                park.acc_add(irr.x, irr.y, irr.z);
-#else
-                acc.x += irr.x; acc.y += irr.y; acc.z += irr.z; acc.w += 1.0f;
-#endif
-            }
-        }
-        direct_all<FAST, GRIDS>(A, poi, seed, acc, park, defer);
-    }
-#if !PT_PARK_LDS
-    park_mem[0][threadIdx.x] = acc.x; park_mem[1][threadIdx.x] = acc.y; park_mem[2][threadIdx.x] = acc.z; park_mem[3][threadIdx.x] = acc.w;
-#endif
-    if (FAST && valid && defer) pt_blk_defer[0] = 1u;
-    __syncthreads();   // every lane's accumulator is final in LDS, and so is the flag (stage_block cleared it)
-    if (FAST && pt_blk_defer[0] != 0u) {   // the whole block goes to the exact kernel: its seeds stay as they were, no pixel of it is written
-        if (threadIdx.x == 0u) defer_unit(defer_mask, blk);
-        return;
-    }
-    if (valid) seeds[id] = seed;
-    resolve_rows(A, &park_mem[0][0], blk, count, (const float*)radiance, radiance, pixel, tone);
 }
 
 // fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per BLOCK of the launch.  a.guide_nh / a.guide_ad (either given): the
 // GUIDES instances, which the caller asks for at rpp 1, 4, 16 or 64 only.
 void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
                      uint32_t* defer_mask, const uint32_t* redo_mask) {
-    const uint64_t count = (uint64_t)v.nrows * v.width * v.k * v.k;
+    const uint64_t count = view_pass_rays(v);
     if (!count) return;
-    FusedArgs b = a;
-    b.width = v.width; b.nrows = v.nrows;
-    b.rpp = v.k * v.k;            // resolve_rows: the rays of a pixel (stage_block's lens table of it is k words nobody reads)
-    b.seg_len = b.rpp;            // ... all of them in one block
-    b.seg_off = accumulate ? 1u : 0u;   // ... and whether the chain goes on from the carry
+    FusedArgs b = view_pass_args(a, v, accumulate);
     const dim3 grid((unsigned)((count + 255u) / 256u));
     query_dispatch(b, fast, defer_mask, redo_mask, [&](auto F, auto G, size_t lds, uint32_t* dm, const uint32_t* rm) {
         constexpr bool FAST = decltype(F)::value;

@@ -175,8 +175,21 @@ struct ViewArgs {
     float eye[3], right[3], up[3], forward[3];
     float half_w, half_h, half_angle, t_min, t_max;
 };
-// the tile's nrows * width * k * k rays as 32-byte records, one lane per ray
+// The batch calls (mirt_view_rays_batch, mirt_render_view_batch): n frames of frame_rows = height rows each, stacked into one image of nrows =
+// n * frame_rows rows, row0 = 0; `cameras` is the device table of 12 floats per frame (eye, right, up, forward), which the batch kernels read
+// INSTEAD of the four arrays of ViewArgs.  A struct of its own, handed to those kernels only: a member more in ViewArgs moves the kernel
+// arguments behind it, and the single calls' instances keep their code (profiles/view_batch/README.md).
+struct ViewBatchArgs : ViewArgs {
+    const float* cameras;
+    uint32_t frame_rows;
+};
+// n cameras of 12 floats from HOST memory into the device table (n * 12 floats), in stream order: launches of k_viewCameras whose kernel arguments
+// carry kViewCameraChunk cameras each, so the host array is read before this returns and no staging memory outlives the call
+constexpr uint32_t kViewCameraChunk = 64u;   // 3072 bytes of arguments a launch
+void launch_viewCameras(hipStream_t s, const float* host_cameras, uint32_t n, float* table);
+// the tile's nrows * width * k * k rays as 32-byte records, one lane per ray; the batch's n * height * width * k * k likewise
 void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays);
+void launch_viewRaysBatch(hipStream_t s, const ViewBatchArgs& v, void* rays);
 // mirt_render_view: those rays through k_traceRadiance's path at one sample each and the block's resolve, in one launch.  seeds: int32 per tile
 // ray, read and written; radiance (float4) / pixel (uchar4) per tile pixel, either may be null; accumulate: the sums go on from `radiance`.  The
 // optimistic / exact pair per BLOCK of 256 ray ids: the mask is one bit per block, (blocks + 31) / 32 words.  Reads the sets, lights, material,
@@ -184,6 +197,9 @@ void launch_viewRays(hipStream_t s, const ViewArgs& v, void* rays);
 // pixels too (k_viewPass GUIDES; mirt_render_view_guided's one-launch route, which the caller takes at k * k = 1, 4, 16 or 64 only).
 void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
                      uint32_t* defer_mask, const uint32_t* redo_mask);
+// mirt_render_view_batch: the same of the stacked frames (k_viewPassBatch, pt_kernels_view_batch.hip; there is no batch of guides, a.guide_nh / a.guide_ad are not read)
+void launch_viewPassBatch(hipStream_t s, const FusedArgs& a, const ViewBatchArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
+                          uint32_t* defer_mask, const uint32_t* redo_mask);
 // mirt_view_guides: the first-hit guides of those rays (k_viewGuides), float4 per tile pixel each as launch_guides writes them; either may be
 // null.  One lane per pixel, `blocks` blocks of 256; the optimistic / exact pair per PIXEL, the mask one bit per pixel: both are the plan's
 // (pt_view_plan.hpp view_guides_plan).  Reads the sets, material and nmat of `a` and nothing else of it.

@@ -1,6 +1,7 @@
 // pt_view_plan.hpp -- the host side of the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view, mirt_view_guides,
 // mirt_render_view_guided, mirt_view_ao; include/mirt.h): the descriptor checks that need no device, the launch plan -- the tile's rays, its blocks of 256
-// consecutive ray ids, the whole pixels a block holds and those of the ragged last block -- and the route rule of the guided frame.  Plain
+// consecutive ray ids, the whole pixels a block holds and those of the ragged last block -- the route rule of the guided frame, and the checks and
+// the plan of the batch calls (mirt_view_rays_batch, mirt_render_view_batch; tests/view_batch_plan_dump.cpp).  Plain
 // integers and floats: no HIP header and no device, so a plain C++ compiler builds it and tests/test_view_plan.py,
 // tests/test_view_guides_plan.py and tests/test_view_ao_plan.py check it on the CPU (tests/view_plan_dump.cpp, tests/view_guides_plan_dump.cpp,
 // tests/view_ao_plan_dump.cpp).  mirt_abi.cpp is the caller and owns the messages.
@@ -60,7 +61,11 @@ enum ViewVerdict {
     VIEW_AO_RADIUS,       // radius NaN or <= 0
     VIEW_AO_BIAS,         // bias negative, NaN or infinite
     VIEW_AO_NO_SEEDS,     // mirt_view_ao without seeds
-    VIEW_AO_NO_OUTPUT     // mirt_view_ao without ao_out
+    VIEW_AO_NO_OUTPUT,    // mirt_view_ao without ao_out
+    VIEW_BATCH_TILE,      // mirt_view_rays_batch, mirt_render_view_batch: row0 != 0, or nrows neither 0 nor height (whole frames only)
+    VIEW_BATCH_NO_CAMERAS,   // cameras NULL with n_frames > 0
+    VIEW_BATCH_CAMERA,    // a non-finite component of a camera (view_check_batch reports which frame)
+    VIEW_BATCH_RAYS       // n_frames * width * height * k * k above 2^32 - 256
 };
 // the status every refusal above is reported with: 0, or MIRT_E_ARG
 inline int view_status(ViewVerdict v) { return v == VIEW_OK ? 0 : kViewStatusArg; }
@@ -123,6 +128,50 @@ inline ViewVerdict view_check_render_guided(const ViewDesc& v, bool seeds, bool 
     return normal_hits || albedo_depth ? VIEW_OK : VIEW_NO_GUIDE;
 }
 
+// The batch calls (mirt_view_rays_batch, mirt_render_view_batch): n_frames cameras' frames of one descriptor, stacked -- for the kernels one image
+// of n_frames * height rows.  mirt_view_camera, field for field: the twelve floats view_ray reads of a camera.
+struct ViewCamera {
+    float eye[3], right[3], up[3], forward[3];
+};
+inline bool view_camera_ok(const ViewCamera& c) {
+    for (int i = 0; i < 3; ++i)
+        if (!isfinite(c.eye[i]) || !isfinite(c.right[i]) || !isfinite(c.up[i]) || !isfinite(c.forward[i])) return false;
+    return true;
+}
+// What both batch calls ask, in view_check_desc's order with the batch's rules where the single call has its own: whole frames where it checks
+// the tile, the batch's ray count where it checks the tile's, the cameras where it checks the descriptor's basis -- which is neither read nor
+// checked.  *bad_frame (may be null): the first frame whose camera is refused, with VIEW_BATCH_CAMERA.  n_frames 0 asks nothing of `cameras`.
+inline ViewVerdict view_check_batch(const ViewDesc& v, const ViewCamera* cameras, uint32_t n_frames, uint32_t* bad_frame = nullptr) {
+    if (v.struct_size != sizeof(ViewDesc)) return VIEW_STRUCT_SIZE;
+    if (v.model > kViewFisheye) return VIEW_MODEL;
+    if (v.flags & ~kViewAccumulate) return VIEW_FLAGS;
+    if (!view_samples_ok(v.k)) return VIEW_SAMPLES;
+    if (!v.width || !v.height || v.width > kViewMaxExtent || v.height > kViewMaxExtent) return VIEW_EXTENT;
+    if (v.row0 != 0u || (v.nrows != 0u && v.nrows != v.height)) return VIEW_BATCH_TILE;
+    if ((uint64_t)v.height * v.width * (v.k * v.k) > kViewMaxRays / (n_frames ? n_frames : 1u)) return VIEW_BATCH_RAYS;   // R <= 2^32: the quotient's floor decides n * R <= max
+    if (n_frames && !cameras) return VIEW_BATCH_NO_CAMERAS;
+    for (uint32_t f = 0; f < n_frames; ++f)
+        if (!view_camera_ok(cameras[f])) {
+            if (bad_frame) *bad_frame = f;
+            return VIEW_BATCH_CAMERA;
+        }
+    if (v.model == kViewOrthographic && !(isfinite(v.half_w) && isfinite(v.half_h) && v.half_w > 0.0f && v.half_h > 0.0f)) return VIEW_ORTHO_WINDOW;
+    if (v.model == kViewFisheye && !(isfinite(v.half_angle) && v.half_angle > 0.0f && v.half_angle <= 0x1.921fb6p+1f)) return VIEW_FISHEYE_ANGLE;
+    if (!(isfinite(v.t_min) && v.t_min >= 0.0f)) return VIEW_T_MIN;
+    if (!(v.t_max > v.t_min)) return VIEW_T_MAX;
+    return VIEW_OK;
+}
+// ... and what mirt_render_view_batch asks on top: view_check_render's rules
+inline ViewVerdict view_check_render_batch(const ViewDesc& v, const ViewCamera* cameras, uint32_t n_frames, bool seeds, bool radiance, bool pixel, uint32_t* bad_frame = nullptr) {
+    const ViewVerdict d = view_check_batch(v, cameras, n_frames, bad_frame);
+    if (d != VIEW_OK) return d;
+    if (pixel && !(isfinite(v.tone) && v.tone > 0.0f)) return VIEW_TONE;
+    if (!seeds) return VIEW_NO_SEEDS;
+    if (!radiance && !pixel) return VIEW_NO_OUTPUT;
+    if ((v.flags & kViewAccumulate) && !radiance) return VIEW_ACCUMULATE_NEEDS_RADIANCE;
+    return VIEW_OK;
+}
+
 // The launch plan of a descriptor that passed view_check_desc.  A block is 256 consecutive tile-local ray ids; rpp = k * k is 1, 4, 16, 64 or 256
 // and divides 256, so a block holds pixels_per_block WHOLE pixels -- the unit the in-block resolve and the optimistic / exact pair work in.
 struct ViewPlan {
@@ -146,6 +195,26 @@ inline ViewPlan view_plan(const ViewDesc& v) {
     p.last_block_pixels = rest ? rest : p.pixels_per_block;
     p.mask_words = (p.blocks + 31u) / 32u;
     return p;
+}
+
+// The batch's plan, of a descriptor that passed view_check_batch: view_plan of the stacked image.  Its row count n_frames * height may pass 65535
+// (and 2^16 * 65535 passes 2^31: nrows is the one product here that needs care); every other product is 64 bits wide as in view_plan.
+struct ViewBatchPlan {
+    uint32_t frame_rows;               // height: the rows of a frame
+    uint64_t frame_pixels, frame_rays; // P and R of include/mirt.h: a frame's share of radiance / pixel and of rays / seeds
+    ViewPlan all;                      // nrows = n_frames * height; pixels, rays, blocks, mask words of the whole batch
+};
+inline ViewBatchPlan view_batch_plan(const ViewDesc& v, uint32_t n_frames) {
+    ViewBatchPlan b;
+    b.frame_rows = v.height;
+    b.frame_pixels = (uint64_t)v.height * v.width;
+    b.frame_rays = b.frame_pixels * (v.k * v.k);
+    ViewDesc s = v;
+    s.row0 = 0u;
+    s.nrows = (uint32_t)((uint64_t)n_frames * v.height);   // n_frames * R <= 2^32 - 256 and width, rpp >= 1: it fits
+    b.all = view_plan(s);
+    if (!n_frames) { b.all.nrows = 0u; b.all.pixels = b.all.rays = 0u; b.all.blocks = b.all.mask_words = 0u; b.all.last_block_pixels = b.all.pixels_per_block; }
+    return b;
 }
 
 // mirt_view_guides and mirt_view_ao run one lane per PIXEL (k_viewGuides, k_viewAo): the grid, which the launcher is handed, and the optimistic

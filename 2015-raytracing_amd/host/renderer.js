@@ -835,6 +835,49 @@ function renderViewFile(file, width, height, rpp, passes, opt) {
   ctx.release();
   return res;
 }
+// -> {pixel: Uint8ClampedArray, radiance: Float32Array (the sums after the last pass), frames, ms, device, deferred}, each holding N frames back to
+// back: the frames of N cameras in one launch per pass (queue.renderViewBatch: mirt_render_view_batch), `passes` progressive calls with
+// MIRT_VIEW_ACCUMULATE from the second on and tone 1 / (rpp * p).  cameras: Float32Array of 12 per frame -- eye, right, up, forward, used as
+// given -- or, with opt.eyes, of 3 per frame: the eyes of cameras with the basis right = +x, up = +y, forward = -z.  opt.view: makeView's v
+// (the model and what all frames share; its eye, look and up are not used); opt.bounces; opt.seedBase: seedFill(0, n, seedBase).
+function renderViewBatchFile(file, cameras, width, height, rpp, passes, opt) {
+  opt = opt || {};
+  const per = opt.eyes ? 3 : 12;
+  if (cameras.length % per) throw new Error(`cameras: ${cameras.length} floats is not a whole number of ${per} per frame`);
+  const frames = cameras.length / per;
+  let table = cameras;
+  if (opt.eyes) {
+    table = new Float32Array(frames * 12);
+    for (let f = 0; f < frames; f++) table.set([cameras[3 * f], cameras[3 * f + 1], cameras[3 * f + 2], 1, 0, 0, 0, 1, 0, 0, 0, -1], 12 * f);
+  }
+  const packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, 4);
+  const view = makeView(packed, width, height, rpp, opt.view);
+  for (const name of ["eye", "right", "up", "forward"]) delete view[name];
+  const ctx = webcl.createContext(pickDevice(opt.device)), q = ctx.createCommandQueue();
+  if (!q.hasViewBatch()) throw new Error("the loaded addon has no renderViewBatch");
+  const dev = uploadScene(ctx, q, packed);
+  const npix = frames * width * height, n = npix * rpp;
+  const mk = (bytes) => ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(bytes, 16));
+  const sb = mk(n * 4), rb = mk(npix * 16), pb = mk(npix * 4);
+  if (n) q.seedFill(sb, 0, n, opt.seedBase || 0);
+  const desc = { spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, lights: packed.lights, material: dev.material, bounces: opt.bounces === undefined ? 5 : opt.bounces };
+  q.finish();
+  const t0 = process.hrtime.bigint();
+  let deferred = 0;
+  for (let p = 1; p <= passes; p++) {
+    q.renderViewBatch(desc, Object.assign({}, view, { flags: p > 1 ? 1 : 0, tone: 1 / (rpp * p) }), table, sb, rb, pb);
+    if (opt.countDeferred) deferred += q.viewDeferred();
+  }
+  q.finish();
+  const ms = Number(process.hrtime.bigint() - t0) / 1e6;
+  const res = { pixel: new Uint8ClampedArray(npix * 4), radiance: new Float32Array(npix * 4), frames: frames, ms: ms, device: pickDevice(opt.device).getInfo(webcl.DEVICE_NAME), deferred: deferred };
+  if (npix) {
+    q.enqueueReadBuffer(pb, true, 0, npix * 4, res.pixel, []);
+    q.enqueueReadBuffer(rb, true, 0, npix * 16, res.radiance, []);
+  }
+  ctx.release();
+  return res;
+}
 // -> Float32Array of 8 per ray: the view's rays themselves (queue.viewRays), for callers who want them
 function viewRaysFile(file, width, height, rpp, opt) {
   opt = opt || {};
@@ -868,4 +911,4 @@ function viewGuidesFile(file, width, height, rpp, opt) {
   return res;
 }
 
-module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderViewFile, viewRaysFile, viewGuidesFile, makeView, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };
+module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderViewFile, renderViewBatchFile, viewRaysFile, viewGuidesFile, makeView, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };

@@ -251,6 +251,18 @@ class WebCLCommandQueue {
     wrap(() => native().renderView(this.ctx.h, d, this._viewDesc(view), seeds ? seeds.h : null, radiance ? radiance.h : null, pixel ? pixel.h : null));
   }
   viewDeferred() { return wrap(() => native().viewDeferred(this.ctx.h)); }
+  // ---- extension: batched view cameras (mirt_view_rays_batch, mirt_render_view_batch): the frames of N cameras that share everything of `view`
+  // but the basis, in one launch.  cameras: 12 numbers per frame -- eye, right, up, forward -- as a Float32Array or an array; view.eye / right /
+  // up / forward are not read; whole frames only (no row0 / nrows).  The buffers hold the frames back to back: frame f ends in each as after
+  // viewRays / renderView on its slice with cameras[f].  viewDeferred() reports the batch as it reports renderView.
+  hasViewBatch() { return typeof native().renderViewBatch === "function"; }
+  _cameras(cameras) { return cameras instanceof Float32Array ? cameras : Float32Array.from(cameras || []); }
+  viewRaysBatch(view, cameras, rays) { wrap(() => native().viewRaysBatch(this.ctx.h, Object.assign({}, view), this._cameras(cameras), rays ? rays.h : null)); }
+  renderViewBatch(desc, view, cameras, seeds, radiance, pixel) {
+    const d = Object.assign(this._setsDesc(desc), { lights: desc.lights || [], material: desc.material ? desc.material.h : undefined });
+    if (desc.bounces !== undefined) d.bounces = desc.bounces;
+    wrap(() => native().renderViewBatch(this.ctx.h, d, Object.assign({}, view), this._cameras(cameras), seeds ? seeds.h : null, radiance ? radiance.h : null, pixel ? pixel.h : null));
+  }
   // ---- extension: the first-hit guides of those cameras (mirt_view_guides, mirt_render_view_guided).  viewGuides(desc, view, normalHits,
   // albedoDepth): float4 per tile pixel each, as renderGuides writes them for the thin lens -- what filterAtrous reads; either may be null; of desc
   // the sets and material are read; depth is in units of |forward| and the basis as given.  renderViewGuided(desc, view, seeds, radiance, pixel,

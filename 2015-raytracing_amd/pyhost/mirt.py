@@ -157,6 +157,8 @@ SYMBOLS = {
     "mirt_view_rays": (C.c_int, [C.c_void_p, C.POINTER(_ViewDesc), C.c_void_p]),
     "mirt_render_view": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mirt_view_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_view_rays_batch": (C.c_int, [C.c_void_p, C.POINTER(_ViewDesc), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mirt_render_view_batch": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mirt_view_guides": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_void_p]),
     "mirt_render_view_guided": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mirt_ctx_guided_views": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -625,8 +627,35 @@ class Context:
                                          seeds.h if seeds else None, radiance.h if radiance else None, pixel.h if pixel else None))
 
     def view_deferred(self):
-        """how many rays the last render_view call re-ran in the exact kernel, in whole blocks of 256 (mirt_view_deferred)"""
+        """how many rays the last render_view or render_view_batch call re-ran in the exact kernel, in whole blocks of 256 (mirt_view_deferred)"""
         return self._deferred(lib().mirt_view_deferred)
+
+    @staticmethod
+    def _cameras(cameras):
+        """-> (host pointer or None, n_frames, the array that keeps the pointer alive): cameras is None or anything np.asarray(..., float32)
+        turns into [N, 12] -- eye, right, up, forward per frame (mirt_view_camera)"""
+        if cameras is None:
+            return None, 0, None
+        cam = np.ascontiguousarray(np.asarray(cameras, np.float32))
+        if cam.size == 0:
+            return None, 0, cam
+        if cam.ndim != 2 or cam.shape[1] != 12:
+            raise ValueError(f"cameras: expected [N, 12] floats (eye, right, up, forward per frame), got {cam.shape}")
+        return cam.ctypes.data_as(C.c_void_p), cam.shape[0], cam
+
+    def view_rays_batch(self, view, cameras, rays):
+        """The rays of N cameras' frames of one descriptor, frame after frame (mirt_view_rays_batch): N * view.width * view.height * k * k
+        records, frame f's as view_rays writes them for `view` with the basis cameras[f].  cameras: [N, 12], a host array."""
+        ptr, n, keep = self._cameras(cameras)
+        self._chk(lib().mirt_view_rays_batch(self.h, C.byref(view) if view is not None else None, ptr, n, rays.h if rays else None))
+
+    def render_view_batch(self, scene_desc, view, cameras, seeds, radiance=None, pixel=None):
+        """N cameras' frames of one descriptor in one launch (mirt_render_view_batch): the buffers hold the frames back to back, and frame f
+        ends in each as after render_view on its slice with the basis cameras[f] ([N, 12] floats on the host: eye, right, up, forward;
+        view's own basis is not read).  VIEW_ACCUMULATE and view.tone apply to every frame."""
+        ptr, n, keep = self._cameras(cameras)
+        self._chk(lib().mirt_render_view_batch(self.h, C.byref(scene_desc) if scene_desc is not None else None, C.byref(view) if view is not None else None,
+                                               ptr, n, seeds.h if seeds else None, radiance.h if radiance else None, pixel.h if pixel else None))
 
     def view_guides(self, scene_desc, view, normal_hits=None, albedo_depth=None):
         """The first-hit guides of a panoramic, fisheye or orthographic camera's row tile in one launch (mirt_view_guides): float4 per tile pixel

@@ -2,7 +2,9 @@
 mirt_trace_occluded, mirt_trace_radiance; the definitions are include/mirt.h's) -- and, beside trace_radiance, render_view: a frame of a
 panoramic, fisheye or orthographic camera into cuda tensors (mirt_render_view), view_guides: its first-hit guides (mirt_view_guides),
 view_ao: its ambient occlusion (mirt_view_ao), and
-denoised_view: progressive frames, the guides from the first (mirt_render_view_guided), and the a-trous filter behind the last.
+denoised_view: progressive frames, the guides from the first (mirt_render_view_guided), and the a-trous filter behind the last;
+render_views: the frames of N cameras in one launch (mirt_render_view_batch), and probe_sh: the order-2 spherical-harmonic coefficients of the
+radiance arriving at N positions, from N small equirect frames and one matmul against sh9_basis.
 
 The tensors are not copied: each is wrapped as a buffer of the context (Context.wrap) for the length of the call, and the launches are queued on
 torch's CURRENT stream (Context.set_stream), so they are ordered after whatever produced `rays` there and before whatever reads the result there.
@@ -14,6 +16,7 @@ torch's CURRENT stream (Context.set_stream), so they are ordered after whatever 
     seeds     int32 [N], contiguous: a ray's random sequence, advanced in place by trace_radiance
     radiance  float32 [N, 4]: a ray's accumulator -- rgb sums and, in column 3, the number of contributions
 """
+import numpy as np
 import torch
 
 
@@ -197,3 +200,105 @@ def denoised_view(ctx, dev_scene, view, seeds, passes=1, bounces=5, **filter_par
             for b in wrapped:
                 b.release()
     return filtered, pixel
+
+
+def render_views(ctx, dev_scene, view, cameras, seeds, bounces=5, accumulate_into=None, want_pixel=False):
+    """-> radiance [N, height, width, 4] float32 cuda, or (radiance, pixel [N, height, width, 4] uint8) with want_pixel: the whole frames of N
+    cameras that share everything of `view` but the basis, in one launch (mirt_render_view_batch).  cameras: anything np.asarray(..., float32)
+    turns into [N, 12] -- eye, right, up, forward per frame; a cuda tensor is brought to the host (48 bytes a frame).  The call's ACCUMULATE flag
+    comes from accumulate_into (view.flags is neither read nor changed), a float32 cuda [N, height, width, 4] of sums to continue (written in place and returned).  seeds: int32 cuda
+    [N * height * width * k * k], frame after frame, advanced in place."""
+    from . import mirt
+    if isinstance(cameras, torch.Tensor):
+        cameras = cameras.detach().cpu().numpy()
+    cam = np.ascontiguousarray(np.asarray(cameras, np.float32))
+    if cam.ndim != 2 or cam.shape[1] != 12:
+        raise ValueError(f"cameras: expected [N, 12] floats (eye, right, up, forward per frame), got {cam.shape}")
+    if view.row0 or (view.nrows and view.nrows != view.height):
+        raise ValueError("render_views renders whole frames: view.row0 and view.nrows must be 0")
+    nf = cam.shape[0]
+    npix = nf * view.height * view.width
+    n = npix * view.k * view.k
+    shape = (nf, view.height, view.width, 4)
+    if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.shape == (n,) and seeds.is_contiguous()):
+        raise ValueError(f"seeds: a contiguous int32 cuda tensor [{n}]")
+    if seeds.device.index != ctx.device:
+        raise ValueError(f"seeds live on cuda:{seeds.device.index}, the context on device {ctx.device}")
+    out = accumulate_into
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=seeds.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == shape and out.is_contiguous() and out.device == seeds.device):
+        raise ValueError("accumulate_into: a contiguous float32 cuda tensor [N, height, width, 4] on the seeds' device")
+    pixel = torch.empty(shape, dtype=torch.uint8, device=seeds.device) if want_pixel else None
+    view = type(view).from_buffer_copy(view)   # the caller's descriptor keeps its flags
+    view.flags = mirt.VIEW_ACCUMULATE if accumulate_into is not None else 0
+    if nf:
+        with _OnTorchStream(ctx, seeds.device):
+            wrapped = [ctx.wrap(seeds.data_ptr(), n * 4), ctx.wrap(out.data_ptr(), npix * 16)] + ([ctx.wrap(pixel.data_ptr(), npix * 4)] if want_pixel else [])
+            try:
+                ctx.render_view_batch(dev_scene.pass_desc(None, None, bounces=bounces), view, cam, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None)
+            finally:
+                for b in wrapped:
+                    b.release()
+    return (out, pixel) if want_pixel else out
+
+
+def sh9_directions(width, height):
+    """-> (d [height * width, 3], latitude [height * width]) float64 numpy: the directions of the pixel CENTRES of a width x height EQUIRECT
+    frame under include/mirt.h's formula with right = +x, up = +y, forward = -z, row-major like the frame."""
+    x, y = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    a = 2.0 * (x + 0.5) / width - 1.0
+    b = 1.0 - 2.0 * (y + 0.5) / height
+    phi, th = (a * np.pi).ravel(), (b * (np.pi / 2)).ravel()
+    lx, ly, lz = np.sin(phi) * np.cos(th), np.sin(th), np.cos(phi) * np.cos(th)
+    return np.stack([lx, ly, -lz], axis=1), th
+
+
+def sh9_weights(width, height):
+    """-> w [height * width] float64 numpy: the solid-angle weights of those pixels, cos(latitude) scaled so that they sum to 4 pi"""
+    w = np.cos(sh9_directions(width, height)[1])
+    return w * (4.0 * np.pi / w.sum())
+
+
+def sh9_basis(width, height):
+    """-> B [height * width, 9] float64 numpy: the real orthonormal spherical harmonics of order 0..2 (index l * l + l + m) at those
+    directions; integral of B_i * B_j over the sphere = delta_ij, which sum(w * B_i * B_j) with sh9_weights approaches at the midpoint rule's rate."""
+    d = sh9_directions(width, height)[0]
+    x, y, z = d[:, 0], d[:, 1], d[:, 2]
+    c0, c1, c2, c3, c4 = 0.5 * np.sqrt(1.0 / np.pi), np.sqrt(3.0 / (4.0 * np.pi)), 0.5 * np.sqrt(15.0 / np.pi), 0.25 * np.sqrt(5.0 / np.pi), 0.25 * np.sqrt(15.0 / np.pi)
+    return np.stack([np.full_like(x, c0), c1 * y, c1 * z, c1 * x, c2 * x * y, c2 * y * z, c3 * (3.0 * z * z - 1.0), c2 * x * z, c4 * (x * x - y * y)], axis=1)
+
+
+def probe_sh(ctx, dev_scene, positions, width=32, height=16, k=2, passes=1, bounces=5, seeds=None):
+    """-> [N, 9, 3] float32 cuda: the order-2 spherical-harmonic coefficients (sh9_basis's order) of the radiance arriving at each of the N
+    positions ([N, 3]).  `passes` progressive batch calls of N width x height EQUIRECT frames at k x k samples with the basis right = +x, up =
+    +y, forward = -z (render_views), then ONE matmul of the pixels' values -- sums.xyz / (k * k * passes) -- against sh9_weights * sh9_basis.
+    seeds: int32 cuda [N * height * width * k * k], advanced in place; None draws them from mirt_seed_fill's sequence."""
+    from . import mirt
+    if isinstance(positions, torch.Tensor):
+        positions = positions.detach().cpu().numpy()
+    pos = np.asarray(positions, np.float32).reshape(-1, 3)
+    if passes < 1:
+        raise ValueError("passes >= 1")
+    nf = pos.shape[0]
+    cam = np.zeros((nf, 12), np.float32)
+    cam[:, 0:3] = pos
+    cam[:, 3], cam[:, 7], cam[:, 11] = 1.0, 1.0, -1.0
+    device = torch.device("cuda", ctx.device)
+    n = nf * height * width * k * k
+    if seeds is None:
+        seeds = torch.empty((n,), dtype=torch.int32, device=device)
+        if n:
+            with _OnTorchStream(ctx, device):
+                w = ctx.wrap(seeds.data_ptr(), n * 4)
+                try:
+                    ctx.seed_fill(w, 0, n)
+                finally:
+                    w.release()
+    view = mirt.view_desc(mirt.VIEW_EQUIRECT, width, height, k=k)
+    sums = render_views(ctx, dev_scene, view, cam, seeds, bounces=bounces)
+    for _ in range(1, passes):
+        render_views(ctx, dev_scene, view, cam, seeds, bounces=bounces, accumulate_into=sums)
+    m = (sh9_basis(width, height) * sh9_weights(width, height)[:, None] / (k * k * passes)).T   # [9, P], the pixel's scale folded in
+    m = torch.from_numpy(np.ascontiguousarray(m.astype(np.float32))).to(device)
+    return torch.matmul(m, sums.reshape(nf, height * width, 4)[:, :, :3])

@@ -440,6 +440,35 @@ typedef struct mirt_view_desc {
 MIRT_API int mirt_view_rays(mirt_ctx* ctx, const mirt_view_desc* view, mirt_buf* rays);
 MIRT_API int mirt_render_view(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel);
 MIRT_API int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays);
+/* BATCHED VIEW CAMERAS: the frames of n_frames cameras in ONE call and one launch (pair) -- a light probe or a data-set view is a small frame,
+ * a 32 x 16 panorama at k = 2 is 8 blocks on a device of 256 CUs, and an irradiance volume is a thousand of them.  The frames share everything
+ * of `view` but the camera: model, width, height, k, half_w, half_h, half_angle, t_min, t_max, tone, flags.
+ * DEFINITION, by composition.  R = width * height * k * k, P = width * height.  The buffers are n_frames frames back to back: frame f owns rays
+ * and seeds [f * R, (f + 1) * R) and radiance and pixel [f * P, (f + 1) * P).  Frame f ends, bit for bit in every buffer the caller passes, as
+ * after the single call -- mirt_view_rays for the rays, mirt_render_view for seeds, radiance and pixel, MIRT_VIEW_ACCUMULATE, tone and the dead
+ * FISHEYE samples included -- on buffers holding just that slice, with a descriptor equal to *view but eye / right / up / forward = cameras[f].
+ * Both libraries give the same bits, as for the single call.  view->eye / right / up / forward are neither read nor checked.
+ * `cameras` is a HOST array of n_frames entries, borrowed for the call like every host pointer of this header, and so checked completely before
+ * anything is queued; the call copies it to device memory of the context in stream order, so a batch call queued behind a running one does not
+ * disturb the table that one reads.  (A caller with cameras in device memory brings them to the host: 48 bytes a frame.)
+ * mirt_view_deferred reports mirt_render_view_batch as it reports mirt_render_view: the rays re-run in the exact kernel, in whole blocks of 256
+ * (a block may hold rays of two frames).
+ * CHECKS, all before anything is queued; nothing is written when one fails, and the context works afterwards.  MIRT_E_ARG: everything
+ * mirt_view_rays / mirt_render_view refuse in the descriptor except the basis; row0 != 0, or nrows neither 0 nor height (whole frames only);
+ * cameras NULL with n_frames > 0; a non-finite component in any camera (the message names the frame); n_frames * R above 2^32 - 256; the overlap
+ * rules of mirt_render_view on the whole batch buffers; a call while capturing.  MIRT_E_RANGE: a buffer shorter than n_frames frames, a material
+ * table shorter than one entry.  MIRT_E_DATA and MIRT_E_HANDLE as in the single call.  n_frames == 0 is MIRT_OK and queues nothing.  A held
+ * command stream is flushed first; wrapped geometry is re-validated once per call.
+ * KERNELS: k_viewRaysBatch and k_viewPassBatch (csrc/pt_kernels_view_batch.hip: the text of k_viewRays and k_viewPass, csrc/pt_view_kernels.inc,
+ * with the compile-time flag BATCH set, in a translation unit of their own) -- the stacked frames are one image of n_frames * height
+ * rows to them; a lane takes its frame from its row and loads that camera from the table (csrc/pt_view.hpp).  The single calls keep their code.
+ * NOT BUILT: batched guides and ambient occlusion (view_ray is shared with k_viewGuides and k_viewAo, so they can follow); row tiles of a batch;
+ * frames that differ in model, size or k; cameras in device memory; graph capture.
+ * MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
+typedef struct mirt_view_camera { float eye[3], right[3], up[3], forward[3]; } mirt_view_camera;   /* 48 bytes */
+MIRT_API int mirt_view_rays_batch(mirt_ctx* ctx, const mirt_view_desc* view, const mirt_view_camera* cameras, uint32_t n_frames, mirt_buf* rays);
+MIRT_API int mirt_render_view_batch(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, const mirt_view_camera* cameras,
+                                    uint32_t n_frames, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel);
 /* FIRST-HIT GUIDES OF A VIEW CAMERA'S TILE, one launch: what mirt_render_guides is to the thin lens, for the cameras above -- the two float4
  * images per pixel that mirt_filter_atrous and mirt_upsample_guided consume, whichever camera made them.
  * DEFINITION, by composition.  Pixel p of the tile has the rays p * rpp + i, i = 0 .. rpp - 1, exactly as mirt_view_rays writes them.  Each runs
