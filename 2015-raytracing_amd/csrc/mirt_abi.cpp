@@ -11,6 +11,7 @@
 #include "pt_rows_plan.hpp"
 #include "pt_view_plan.hpp"
 #include "pt_set_guard.hpp"
+#include "pt_box_exit.hpp"
 #include "pt_shadow_gap.hpp"
 #include "pt_stream_match.hpp"
 #include "pt_upsample_taps.hpp"
@@ -1368,6 +1369,10 @@ static int fill_grid(mirt_ctx* ctx, const char* what, const mirt_grid* g, bool t
     o->exit_is_far_face = v.exit_is_far_face;
     o->exit_far_axes = v.exit_far_axes;
     memcpy(o->exit_up, v.exit_up, sizeof o->exit_up);
+    // the constant of the one slab pass of a single-cell set (pt_box_exit.hpp; zero where no exit plane lies above its face, and for a grid)
+    const pt::BoxExit be = pt::box_exit_consts(g->bounds, v.exit_up);
+    o->exit_above_axes = v.exit_above_axes;
+    memcpy(&o->exit_gap_max, &be.gap_max, 4);   // (GridArgs holds its bits)
     memcpy(o->delta, v.delta, sizeof o->delta);
     memcpy(o->rdelta, v.rdelta, sizeof o->rdelta);
     // the plane-free gap of a single-cell triangle set with a plane list, for these bounds (pt_shadow_gap.hpp)

@@ -75,7 +75,7 @@ PT_DEV void closest_all(const FusedArgs& A, Ray& ray, Poi& poi, const HOOKS& hoo
         if (!GRIDS || S.n == 1u) {
             if (live) {
                 pt_count(PC_BOX_TESTS); pt_count(PC_BOX_LANES, true);
-                const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(ray, rr, set_box(S));
+                const BoxHit bh = cell1_box<FAST>(ray, rr, S);
                 if (bh.v) ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, false, TRI_A10, FAST>(ray, rr, bh, S) : trace_cell1<TRIANGLES, false, TRI_A10, FAST, false, PT_LANE_LISTS_FOR(FAST, GRIDS)>(ray, rr, bh, S);
             }
         } else if (S.kind == KIND_TRIANGLES) {   // every lane of the wave enters: the tests of the walk are shared (pt_trace_coop.hpp)

@@ -111,7 +111,7 @@ PT_DEV void direct_all(const FusedArgs& A, Poi& poi, int32_t& seed, float4& acc,
                         walked = true;
                     } else {
                         pt_count(PC_BOX_TESTS); pt_count(PC_BOX_LANES, true);
-                        const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(sh, rr, set_box(S));
+                        const BoxHit bh = cell1_box<FAST>(sh, rr, S);
                         if (bh.v) {
                             ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, true, TRI_A10, FAST, true>(sh, rr, bh, S) : trace_cell1<TRIANGLES, true, TRI_A10, FAST, true, PT_LANE_LISTS_FOR(FAST, GRIDS)>(sh, rr, bh, S);
                             walked = true;

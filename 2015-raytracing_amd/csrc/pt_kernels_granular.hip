@@ -224,6 +224,7 @@ PT_DEV GridArgs mk_set(const float4* prims, const uint32_t* off, const Box8& b, 
     for (int i = 0; i < 3; ++i) { S.delta[i] = 0.0f; S.rdelta[i] = 0.0f; }   // the optimistic kernel's (these kernels divide for themselves)
     S.walk_ok = 0; S.nslots = 0;
     S.exit_far_axes = 0; S.exit_up[0] = S.exit_up[1] = S.exit_up[2] = 0.0f;   // (the optimistic kernel's as well)
+    S.exit_above_axes = 0; S.exit_gap_max = 0;
     return S;
 }
 template <int KIND>

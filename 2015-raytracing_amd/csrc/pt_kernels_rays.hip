@@ -69,7 +69,7 @@ PT_DEV void rays_any(const FusedArgs& A, Ray& sh, bool& defer) {
         bool walked = false;
         if (!GRIDS || S.n == 1u) {
             if (live) {
-                const BoxHit bh = inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(sh, rr, set_box(S));
+                const BoxHit bh = cell1_box<FAST>(sh, rr, S);
                 if (bh.v) {
                     ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, true, TRI_A10, FAST, true>(sh, rr, bh, S) : trace_cell1<TRIANGLES, true, TRI_A10, FAST, true, PT_LANE_LISTS_FOR(FAST, GRIDS)>(sh, rr, bh, S);
                     walked = true;

@@ -58,7 +58,7 @@ struct GridArgs {            // one cell-sorted primitive set, device pointers
     uint32_t kind;           // KIND_SPHERES | KIND_TRIANGLES
     uint32_t fast_ok;        // geometry-side guard of the exact 3-operation divisions (pt_trace.hpp ray_recip): every bound is 0 or
                              // in [2^-30, 2^20]; for triangles every plane-normal component is 0 or in [2^-40, 2^40].  The host's verdict:
-                             // this field and delta, rdelta, exit_far_axes, exit_up, walk_ok, exit_is_far_face below are pt_set_guard.hpp's
+                             // this field and delta, rdelta, exit_far_axes, exit_up, exit_above_axes, walk_ok, exit_is_far_face below are pt_set_guard.hpp's
                              // SetGuard, copied (mirt_abi.cpp fill_grid)
     uint32_t lds_off;        // fused pass (launch_fused assigns it).  n > 1: dword index of this set's cell-offset table inside the block's
                              // LDS copy, or kNoLds when the tables of the scene do not fit.  n == 1, triangles: dword index (a multiple of
@@ -68,6 +68,12 @@ struct GridArgs {            // one cell-sorted primitive set, device pointers
     uint32_t exit_far_axes;  // n == 1, optimistic kernel: bit k set where the cell's forward exit plane x_up = lo + 1*((hi-lo)/1) (A10 code.cl:699-707)
                              // equals hi, so a ray with d_k >= 0 leaves the cell where it leaves the box (pt_trace.hpp cell1_exit)
     float exit_up[3];        // ... and x_up itself per axis, for the axes whose bit is clear (the backward plane lo + 0*((hi-lo)/1) is lo: host-checked)
+    uint32_t exit_gap_max;   // (the BITS of a float: the kernel asks "is it 0" as a scalar compare.)  n == 1, optimistic kernel, the one slab pass (pt_trace.hpp
+                             // box_exit1; pt_box_exit.hpp: the derivation and the constant).  Where x_up lies ABOVE hi, "tmin <= exit" may hold for a ray the
+                             // box's far face drops; a lane whose window is shorter than this constant times its largest reciprocal sends its wave to the
+                             // box's own comparison.  The largest (x_up - hi) (1 + 2^-20) of the three axes, 0 when no axis has x_up > hi (then nothing is
+                             // tested); it sits behind exit_up so that one scalar load brings both
+    uint32_t exit_above_axes; // ... bit k set where x_up > hi (pt_set_guard.hpp)
     uint32_t walk_ok;      // what every lane would compute for itself from wave-uniform inputs (pt_trace.hpp axis_setup_t).  walk_ok: the
                              // widths and spans sit inside the windows in which the kernel's 3-operation divisions are exact; a lane that
                              // walks a set without it hands its sample to the exact kernel

@@ -1,6 +1,6 @@
 // pt_set_guard.hpp -- the geometry side of "may this launch be optimistic": what the host works out once per primitive set from its bounds and
 // slab count, before launch, because no lane can catch it (a ray outside the windows defers itself in the kernel; a SET outside them would be wrong
-// for every ray).  The result is copied into GridArgs (pt_launch.hpp: fast_ok, walk_ok, exit_is_far_face, exit_far_axes, exit_up, delta, rdelta).
+// for every ray).  The result is copied into GridArgs (pt_launch.hpp: fast_ok, walk_ok, exit_is_far_face, exit_far_axes, exit_up, exit_above_axes, delta, rdelta).
 // Plain fp32 arithmetic on eight floats -- no HIP header, no context and no buffer, so a plain C++ compiler builds it and tests/test_set_guard.py
 // checks it on the CPU (tests/set_guard_dump.cpp) against the same rules in numpy.float32.  mirt_abi.cpp is the caller (fill_grid; launch_kernel's
 // single-cell launches for set_exit_is_far_face alone).
@@ -48,6 +48,10 @@ struct SetGuard {
     uint32_t exit_is_far_face;   // set_exit_is_far_face
     uint32_t exit_far_axes;      // n == 1: bit k where the forward exit plane is hi (7 otherwise)
     float exit_up[3];            // n == 1: the forward exit plane per axis (hi otherwise)
+    uint32_t exit_above_axes;    // n == 1: bit k where the forward exit plane lies ABOVE hi (0 otherwise).  There the one slab pass of the optimistic kernel
+                                 // (pt_trace.hpp box_exit1) asks the box's far face as well when a lane's window is shorter than a constant made from
+                                 // exit_up and the bounds: pt_box_exit.hpp box_exit_consts, a header of its own in the common subset of C and C++ (its CPU
+                                 // check is a C program), which the caller of set_guard includes
     float delta[3], rdelta[3];   // the slab width (hi - lo) / n and its reciprocal
 };
 
@@ -74,6 +78,8 @@ inline SetGuard set_guard(const float* b8, uint32_t n, bool records_sane) {
         fast = fast && p.dn_is_lo;
         g.exit_far_axes = p.up_is_hi;
         g.exit_is_far_face = planes_are_far_face(p) ? 1u : 0u;
+        for (int k = 0; k < 3; ++k)
+            if (p.up[k] > b8[4 + k]) g.exit_above_axes |= 1u << k;
     }
     g.fast_ok = fast ? 1u : 0u;
     // the walk's wave-uniform quotients, once, in the arithmetic the kernel would use: fp32, correctly rounded.  The span is a numerator of the

@@ -399,11 +399,21 @@ PT_DEV Box set_box_of(const GridArgs& S) {
 //     inside div_exact3's window, as the slab numerators are.  A zero numerator may give a zero of either sign: the exit is only compared
 //     (cmin <= t <= cmax, and min(cmax, maxt) in the plane window), as the slab quotients of slab1_fast without SIGNED_ZERO.
 // The exact kernel and the default contract keep the reference's divisions.
+// PT_BOX_EXIT_FOR: the sets of the optimistic kernels whose box comes from box_exit1 below (cell1_box picks it), exit included: bh.tmax IS the exit.
+#ifndef PT_AABB_UNSIGNED_ZERO
+#define PT_AABB_UNSIGNED_ZERO 1  // (pt_closest.hpp states it for the callers)
+#endif
+#ifndef PT_BOX_EXIT
+#define PT_BOX_EXIT 1           // 0: the box test and the exit as two functions, nine quotients (an A/B build)
+#endif
+#define PT_BOX_EXIT_FOR(FAST) ((FAST) && PT_BOX_EXIT && PT_AABB_UNSIGNED_ZERO && !PT_PLAIN_DIV)
 template <bool FAST>
 PT_DEV float cell1_exit(const Ray& ray, const RayRcp& rr, const BoxHit& bh, const GridArgs& S) {
     float tn[3];
     if (S.exit_is_far_face) {  // host-verified: the cell's exit planes ARE the box's far planes (pt_set_guard.hpp set_exit_is_far_face)
         tn[0] = bh.tfx; tn[1] = bh.tfy; tn[2] = bh.tfz;
+    } else if (PT_BOX_EXIT_FOR(FAST)) {
+        return bh.tmax;
 #if !PT_PLAIN_DIV
     } else if (FAST) {
         const float tf[3] = {bh.tfx, bh.tfy, bh.tfz}, up[3] = {S.exit_up[0], S.exit_up[1], S.exit_up[2]};
@@ -425,6 +435,61 @@ PT_DEV float cell1_exit(const Ray& ray, const RayRcp& rr, const BoxHit& bh, cons
         }
     }
     return cl_min(cl_min(tn[0], tn[1]), tn[2]);   // one v_min3_f32
+}
+// The box verdict and the cell exit of a single-cell set in ONE slab pass (the optimistic kernels, sets whose exit planes are not the box's far
+// faces -- cornell.xml's sphere set): per axis the quotient of the plane the ray enters by -- lo for d >= 0, hi for d < 0 -- and of the one it
+// leaves by -- x_up or lo -- where inter_aabb_t and cell1_exit together form three.  tmin and the exit (returned in tmax; tf* are not set) have the
+// bits those two give.  The verdict is the box's own, reached through !(tmin > exit): the two can differ only on an axis with x_up > hi, for a
+// lane whose window is shorter than a bound the host made (GridArgs::exit_gap_max); a wave with such a lane forms the box's far quotient on those
+// axes after all and takes the box's comparison.  pt_box_exit.hpp has the derivation and the constant.  The planes and the bits are kernel
+// arguments: scalar branches.
+PT_DEV BoxHit box_exit1(const Ray& r, const RayRcp& q, const GridArgs& S) {
+    auto quo = [](float num, float d, float rr) { const float q0 = num * rr; return __builtin_fmaf(__builtin_fmaf(-d, q0, num), rr, q0); };
+    const float oo[3] = {r.o.x, r.o.y, r.o.z}, dd[3] = {r.d.x, r.d.y, r.d.z}, rc[3] = {q.x, q.y, q.z};
+    float nr[3], fr[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // the three numerators first (scalar planes), then the two the ray's direction picks: selected as values, two quotients an axis and no
+        // min / max (selected as planes they became a select of ADDRESSES and a vector load per axis).  exit_up[k] is hi where bit k of
+        // exit_far_axes is set (pt_set_guard.hpp), so one form serves every axis.
+        const float nl = S.bound[k] - oo[k], nh = S.bound[4 + k] - oo[k], nu = S.exit_up[k] - oo[k];
+        const bool fwd = dd[k] >= 0.0f;
+        nr[k] = quo(fwd ? nl : nh, dd[k], rc[k]);
+        fr[k] = quo(fwd ? nu : nl, dd[k], rc[k]);
+    }
+    BoxHit h;
+    h.tmin = __builtin_fmaxf(__builtin_fmaxf(nr[0], nr[1]), __builtin_fmaxf(nr[2], 0.0f));
+    h.tmax = __builtin_fminf(__builtin_fminf(fr[0], fr[1]), fr[2]);
+    h.tfx = h.tfy = h.tfz = h.tmax;
+    h.v = !(h.tmin > h.tmax);
+    if (S.exit_gap_max != 0u) {   // some axis has x_up > hi (exit_above_axes != 0)
+        // every lane: is the verdict's spare room, fl(exit (1 - 2^-20) - tmin), at least the largest gap times the largest reciprocal?  It nearly
+        // always is (four instructions), and then the box's far faces cannot say otherwise; a wave with a lane where it is not -- a NaN included --
+        // asks them
+        const float room = __builtin_fmaf(h.tmax, 0.99999904632568359375f, -h.tmin);
+        const float rmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(rc[0]), __builtin_fabsf(rc[1])), __builtin_fabsf(rc[2]));
+        // (the wave's mask from the compares themselves -- 12: unordered or less, 13: unordered or less or equal: as a ballot of the two as one bool
+        // the branch was made from a select and a third compare)
+        if ((__builtin_amdgcn_fcmpf(room, __uint_as_float(S.exit_gap_max) * rmax, 12) & __builtin_amdgcn_fcmpf(h.tmin, h.tmax, 13)) != 0ull) {
+            // the box's far quotient (hi - o) / d on the axes with x_up > hi, for d >= 0 (for d < 0 it is (lo - o) / d, which the exit holds already):
+            // with them tmin <= tmax is the reference's comparison itself.  Every lane of the wave may take it: the lanes that had room have it here too
+            float tmax = h.tmax;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (((S.exit_above_axes >> k) & 1u) != 0u) {
+                    const float qh = quo(S.bound[4 + k] - oo[k], dd[k], rc[k]);
+                    tmax = __builtin_fminf(tmax, dd[k] >= 0.0f ? qh : tmax);
+                }
+            h.v = !(h.tmin > tmax);
+        }
+    }
+    return h;
+}
+// the box of a single-cell set as closest_all, direct_all and rays_any ask for it
+template <bool FAST>
+PT_DEV BoxHit cell1_box(const Ray& r, const RayRcp& q, const GridArgs& S) {
+    if (PT_BOX_EXIT_FOR(FAST) && !S.exit_is_far_face) return box_exit1(r, q, S);
+    return inter_aabb_t<FAST, !PT_AABB_UNSIGNED_ZERO>(r, q, set_box_of(S));
 }
 
 // One primitive set.  KIND / ANY as in pt_device.hpp.
