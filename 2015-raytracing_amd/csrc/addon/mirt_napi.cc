@@ -746,6 +746,80 @@ napi_value RenderViewBatch(napi_env env, napi_callback_info info) {
     if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
     return undef(env);
 }
+// The batch's guides and ambient occlusion, the buffers holding the frames back to back.  viewGuidesBatch(ctx, desc, viewDesc, cameras,
+// normalHits, albedoDepth) (mirt_view_guides_batch); renderViewGuidedBatch(ctx, desc, viewDesc, cameras, seeds, radiance, pixel, normalHits,
+// albedoDepth) (mirt_render_view_guided_batch); viewAoBatch(ctx, desc, viewDesc, cameras, aoDesc, seeds, aoOut) (mirt_view_ao_batch).
+static napi_value view_batch_call(napi_env env, napi_value* argv, ViewCall call) {
+    const char* const who = call == VIEW_GUIDES ? "viewGuidesBatch" : "renderViewGuidedBatch";
+    void *c, *seeds = nullptr, *radiance = nullptr, *pixel = nullptr, *nh = nullptr, *ad = nullptr;
+    if (!get_ext(env, argv[0], &c))
+        return throw_type(env, call == VIEW_GUIDES ? "viewGuidesBatch(ctx, desc, viewDesc, cameras, normalHits, albedoDepth)"
+                                                   : "renderViewGuidedBatch(ctx, desc, viewDesc, cameras, seeds, radiance, pixel, normalHits, albedoDepth)");
+    if (call == VIEW_GUIDES) {
+        get_ext(env, argv[4], &nh);
+        get_ext(env, argv[5], &ad);
+    } else {
+        get_ext(env, argv[4], &seeds);
+        get_ext(env, argv[5], &radiance);
+        get_ext(env, argv[6], &pixel);
+        get_ext(env, argv[7], &nh);
+        get_ext(env, argv[8], &ad);
+    }
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    p.bounces = 5;
+    prop_u32(env, argv[1], "bounces", &p.bounces);
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    std::vector<mirt_light> lights;
+    if (!read_sets(env, argv[1], who, p, sph, tri, meshes) || (call != VIEW_GUIDES && !read_lights(env, argv[1], who, p, lights))) return nullptr;
+    p.material = prop_buf(env, argv[1], "material");
+    mirt_view_desc v;
+    const mirt_view_camera* cams = nullptr;
+    uint32_t n = 0;
+    if (!read_view(env, argv[2], who, v, false) || !read_cameras(env, argv[3], who, &cams, &n)) return nullptr;
+    const int rc = call == VIEW_GUIDES ? mirt_view_guides_batch((mirt_ctx*)c, &p, &v, cams, n, (mirt_buf*)nh, (mirt_buf*)ad)
+                                       : mirt_render_view_guided_batch((mirt_ctx*)c, &p, &v, cams, n, (mirt_buf*)seeds, (mirt_buf*)radiance, (mirt_buf*)pixel,
+                                                                       (mirt_buf*)nh, (mirt_buf*)ad);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
+napi_value ViewGuidesBatch(napi_env env, napi_callback_info info) {
+    ARGS(6);
+    return view_batch_call(env, argv, VIEW_GUIDES);
+}
+napi_value RenderViewGuidedBatch(napi_env env, napi_callback_info info) {
+    ARGS(9);
+    return view_batch_call(env, argv, VIEW_FRAME_GUIDED);
+}
+napi_value ViewAoBatch(napi_env env, napi_callback_info info) {
+    ARGS(7);
+    void *c, *seeds = nullptr, *out = nullptr;
+    if (!get_ext(env, argv[0], &c)) return throw_type(env, "viewAoBatch(ctx, desc, viewDesc, cameras, aoDesc, seeds, aoOut)");
+    get_ext(env, argv[5], &seeds);
+    get_ext(env, argv[6], &out);
+    mirt_pass_desc p;
+    memset(&p, 0, sizeof p);
+    p.struct_size = sizeof p;
+    mirt_grid sph, tri;
+    std::vector<mirt_grid> meshes;
+    if (!read_sets(env, argv[1], "viewAoBatch", p, sph, tri, meshes)) return nullptr;
+    mirt_view_desc v;
+    const mirt_view_camera* cams = nullptr;
+    uint32_t n = 0;
+    if (!read_view(env, argv[2], "viewAoBatch", v, false) || !read_cameras(env, argv[3], "viewAoBatch", &cams, &n)) return nullptr;
+    mirt_ao_desc a = {(uint32_t)sizeof(mirt_ao_desc), MIRT_AO_DEFAULT_SAMPLES, INFINITY, MIRT_AO_DEFAULT_BIAS};
+    napi_valuetype t = napi_undefined;
+    if (napi_typeof(env, argv[4], &t) == napi_ok && t == napi_object) {
+        prop_u32(env, argv[4], "samples", &a.samples);
+        prop_f32(env, argv[4], "radius", &a.radius);
+        prop_f32(env, argv[4], "bias", &a.bias);
+    }
+    const int rc = mirt_view_ao_batch((mirt_ctx*)c, &p, &v, cams, n, &a, (mirt_buf*)seeds, (mirt_buf*)out);
+    if (rc) return throw_mirt(env, rc, (mirt_ctx*)c);
+    return undef(env);
+}
 napi_value ViewDeferred(napi_env env, napi_callback_info info) {
     ARGS(1);
     void* c;
@@ -1190,7 +1264,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"bufCreate", BufCreate}, {"bufRelease", BufRelease}, {"bufSize", BufSize}, {"bufWrite", BufWrite}, {"bufRead", BufRead},
         {"programCheck", ProgramCheck}, {"programDialect", ProgramDialect}, {"kernelGet", KernelGet}, {"kernelRelease", KernelRelease}, {"kernelNumArgs", KernelNumArgs},
         {"kernelPreferredMultiple", KernelPreferredMultiple}, {"kernelSetArg", KernelSetArg}, {"enqueue", Enqueue},
-        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"viewRaysBatch", ViewRaysBatch}, {"renderViewBatch", RenderViewBatch}, {"viewGuides", ViewGuides}, {"viewAo", ViewAo}, {"viewAoDeferred", ViewAoDeferred}, {"renderViewGuided", RenderViewGuided}, {"ctxGuidedViews", CtxGuidedViews}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
+        {"renderPass", RenderPass}, {"renderGuides", RenderGuides}, {"renderFirstPassGuided", RenderFirstPassGuided}, {"renderPassesGuided", RenderPassesGuided}, {"traceClosest", TraceClosest}, {"traceOccluded", TraceOccluded}, {"traceDeferred", TraceDeferred}, {"traceRadiance", TraceRadiance}, {"radianceDeferred", RadianceDeferred}, {"viewRays", ViewRays}, {"renderView", RenderView}, {"viewDeferred", ViewDeferred}, {"viewRaysBatch", ViewRaysBatch}, {"renderViewBatch", RenderViewBatch}, {"viewGuidesBatch", ViewGuidesBatch}, {"renderViewGuidedBatch", RenderViewGuidedBatch}, {"viewAoBatch", ViewAoBatch}, {"viewGuides", ViewGuides}, {"viewAo", ViewAo}, {"viewAoDeferred", ViewAoDeferred}, {"renderViewGuided", RenderViewGuided}, {"ctxGuidedViews", CtxGuidedViews}, {"filterAtrous", FilterAtrous}, {"upsampleGuided", UpsampleGuided}, {"renderFrame", RenderFrame}, {"ctxSetFrameFusion", CtxSetFrameFusion}, {"ctxFusedFrames", CtxFusedFrames}, {"gridBuild", GridBuild}, {"gridGatherTriangles", GridGatherTriangles},
         {"gridGatherSpheres", GridGatherSpheres}, {"gridGatherU32", GridGatherU32}, {"renderAo", RenderAo}, {"aoDeferred", AoDeferred}, {"seedFill", SeedFill}, {"zero", Zero}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
         {"captureBegin", CaptureBegin}, {"captureEnd", CaptureEnd}, {"graphLaunch", GraphLaunch}, {"graphRelease", GraphRelease},
         {"groupCreate", GroupCreate}, {"groupCtx", GroupCtx}, {"groupDestroy", GroupDestroy}, {"groupFinish", GroupFinish}, {"tileRows", TileRows}, {"gather", Gather}, {"meshIngest", MeshIngest},

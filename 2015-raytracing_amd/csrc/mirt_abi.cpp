@@ -1910,11 +1910,19 @@ static int queue_view_guides(mirt_ctx* ctx, const pt::FusedArgs& A, const pt::Vi
         pt::launch_viewGuides(ctx->stream, A, V, g.blocks, fast, nh, ad, mask_out, mask_in);
     });
 }
-// MIRT_GUIDED_VIEW=0: mirt_render_view_guided always queues the frame and then the guide launches -- an A/B and test switch, read per call
+// ... and of a batch's stacked image (k_viewGuidesBatch): the same pair and mask, one lane and one bit per pixel of all the frames
+static int queue_view_guides_batch(mirt_ctx* ctx, const pt::FusedArgs& A, const pt::ViewBatchArgs& VB, const pt::ViewBatchPlan& bplan, void* nh, void* ad) {
+    const pt::ViewGuidesPlan g = pt::view_batch_pixel_plan(bplan);
+    return queue_pair(ctx, ctx->guide_mask, A, g.mask_words, 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_viewGuidesBatch(ctx->stream, A, VB, g.blocks, fast, nh, ad, mask_out, mask_in);
+    });
+}
+// MIRT_GUIDED_VIEW=0: mirt_render_view_guided (and its batch) always queues the frame and then the guide launches -- an A/B and test switch, read per call
 static bool guided_view_enabled() { const char* e = getenv("MIRT_GUIDED_VIEW"); return !(e && e[0] == '0'); }
 
-// ---- batched view cameras (mirt_view_rays_batch, mirt_render_view_batch): n_frames cameras' frames of one descriptor as ONE image of
-// n_frames * height rows through k_viewRaysBatch and k_viewPassBatch (pt_kernels_view_batch.hip).  The checks and the plan are pt_view_plan.hpp's
+// ---- batched view cameras (mirt_view_rays_batch, mirt_render_view_batch, mirt_view_guides_batch, mirt_render_view_guided_batch,
+// mirt_view_ao_batch): n_frames cameras' frames of one descriptor as ONE image of n_frames * height rows through k_viewRaysBatch,
+// k_viewPassBatch, k_viewGuidesBatch and k_viewAoBatch (pt_kernels_view_batch.hip).  The checks and the plan are pt_view_plan.hpp's
 // (view_check_batch, view_batch_plan); here are the messages and the camera table.
 static_assert(sizeof(pt::ViewCamera) == sizeof(mirt_view_camera) && sizeof(mirt_view_camera) == 48 && offsetof(pt::ViewCamera, right) == offsetof(mirt_view_camera, right) &&
               offsetof(pt::ViewCamera, up) == offsetof(mirt_view_camera, up) && offsetof(pt::ViewCamera, forward) == offsetof(mirt_view_camera, forward),
@@ -1955,7 +1963,8 @@ static pt::ViewBatchArgs view_batch_args(const pt::ViewDesc& d, const pt::ViewBa
 
 // mirt_render_view (guided false: seeds, radiance, pixel), mirt_view_guides (frame false: normal_hits, albedo_depth) and mirt_render_view_guided
 // (all five): one list of checks, every one before anything is queued, then the launches.
-// The frames of a batch: the host array and its length (mirt_render_view_batch); nullptr for the single calls
+// The frames of a batch: the host array and its length (mirt_render_view_batch, mirt_view_guides_batch, mirt_render_view_guided_batch); nullptr
+// for the single calls
 struct ViewBatch { const mirt_view_camera* cameras; uint32_t n_frames; };
 static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guided, const mirt_pass_desc* d, const mirt_view_desc* vd, const ViewBatch* batch, mirt_buf* seeds,
                             mirt_buf* radiance, mirt_buf* pixel, mirt_buf* normal_hits, mirt_buf* albedo_depth) {
@@ -1967,7 +1976,10 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
     int rc;
     const bool nh = normal_hits != nullptr, ad = albedo_depth != nullptr;
     uint32_t bad_frame = 0;
-    const pt::ViewVerdict verdict = batch    ? pt::view_check_render_batch(v, (const pt::ViewCamera*)batch->cameras, batch->n_frames, seeds != nullptr, radiance != nullptr, pixel != nullptr, &bad_frame)
+    const pt::ViewCamera* const cams = batch ? (const pt::ViewCamera*)batch->cameras : nullptr;
+    const pt::ViewVerdict verdict = batch    ? (!frame   ? pt::view_check_guides_batch(v, cams, batch->n_frames, nh, ad, &bad_frame)
+                                                : guided ? pt::view_check_render_guided_batch(v, cams, batch->n_frames, seeds != nullptr, radiance != nullptr, pixel != nullptr, nh, ad, &bad_frame)
+                                                         : pt::view_check_render_batch(v, cams, batch->n_frames, seeds != nullptr, radiance != nullptr, pixel != nullptr, &bad_frame))
                                     : !frame ? pt::view_check_guides(v, nh, ad)
                                     : guided ? pt::view_check_render_guided(v, seeds != nullptr, radiance != nullptr, pixel != nullptr, nh, ad)
                                              : pt::view_check_render(v, seeds != nullptr, radiance != nullptr, pixel != nullptr);
@@ -2009,7 +2021,8 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
         const bool accumulate = (v.flags & MIRT_VIEW_ACCUMULATE) != 0u;
         void* const rp = radiance ? radiance->ptr : nullptr;
         void* const pp = pixel ? pixel->ptr : nullptr;
-        const bool in_pass = guided && pt::view_guides_in_pass(plan.rpp, pt::fused_has_grids(A), guided_view_enabled());
+        const bool in_pass = guided && (batch ? pt::view_batch_guides_in_pass(plan.rpp, pt::fused_has_grids(A), guided_view_enabled())
+                                              : pt::view_guides_in_pass(plan.rpp, pt::fused_has_grids(A), guided_view_enabled()));
         pt::FusedArgs F = A;
         if (in_pass) { F.guide_nh = nhp; F.guide_ad = adp; }
         rc = queue_pair(ctx, ctx->view_mask, A, plan.mask_words, 256u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {   // a bit is a block of 256 rays
@@ -2018,8 +2031,8 @@ static int render_view_impl(mirt_ctx* ctx, const char* fn, bool frame, bool guid
         });
         if (rc) return rc;
         if (in_pass) ctx->guided_views++;
-        else if (guided && (rc = queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;   // everywhere else: exactly what mirt_view_guides queues
-    } else if ((rc = queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;
+        else if (guided && (rc = batch ? queue_view_guides_batch(ctx, A, VB, bplan, nhp, adp) : queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;   // everywhere else: exactly what mirt_view_guides (_batch) queues
+    } else if ((rc = batch ? queue_view_guides_batch(ctx, A, VB, bplan, nhp, adp) : queue_view_guides(ctx, A, V, plan, nhp, adp))) return rc;
     return finish_call(ctx, io, 5);
 }
 
@@ -2071,6 +2084,20 @@ int mirt_render_view_guided(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_v
     return render_view_impl(ctx, "mirt_render_view_guided", true, true, d, vd, nullptr, seeds, radiance, pixel, normal_hits, albedo_depth);
 } MIRT_CATCH("mirt_render_view_guided", return MIRT_E_DEVICE)
 
+// The guides of n_frames cameras' frames, alone and from the frames' launch: mirt_view_guides' and mirt_render_view_guided's lists of checks on the
+// whole batch buffers behind the batch's own, and the batch's kernel instances (render_view_impl)
+int mirt_view_guides_batch(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, const mirt_view_camera* cameras, uint32_t n_frames, mirt_buf* normal_hits,
+                           mirt_buf* albedo_depth) try {
+    const ViewBatch batch = {cameras, n_frames};
+    return render_view_impl(ctx, "mirt_view_guides_batch", false, true, d, vd, &batch, nullptr, nullptr, nullptr, normal_hits, albedo_depth);
+} MIRT_CATCH("mirt_view_guides_batch", return MIRT_E_DEVICE)
+
+int mirt_render_view_guided_batch(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, const mirt_view_camera* cameras, uint32_t n_frames, mirt_buf* seeds,
+                                  mirt_buf* radiance, mirt_buf* pixel, mirt_buf* normal_hits, mirt_buf* albedo_depth) try {
+    const ViewBatch batch = {cameras, n_frames};
+    return render_view_impl(ctx, "mirt_render_view_guided_batch", true, true, d, vd, &batch, seeds, radiance, pixel, normal_hits, albedo_depth);
+} MIRT_CATCH("mirt_render_view_guided_batch", return MIRT_E_DEVICE)
+
 int mirt_ctx_guided_views(mirt_ctx* ctx, uint64_t* count) try {
     if (!live_has(ctx)) return fail(nullptr, MIRT_E_HANDLE, "mirt_ctx_guided_views: unknown context");
     if (!count) return fail(ctx, MIRT_E_ARG, "mirt_ctx_guided_views: null output");
@@ -2113,6 +2140,43 @@ int mirt_view_ao(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* v
     });
     return rc ? rc : finish_call(ctx, io, 2);
 } MIRT_CATCH("mirt_view_ao", return MIRT_E_DEVICE)
+
+// Ambient occlusion of n_frames cameras' frames (k_viewAoBatch): mirt_view_ao's shape on the whole batch buffers, with the batch's verdicts first,
+// the camera table and the plan of the stacked image.  A descriptor of another size is read no further than its first word.
+int mirt_view_ao_batch(mirt_ctx* ctx, const mirt_pass_desc* d, const mirt_view_desc* vd, const mirt_view_camera* cameras, uint32_t n_frames, const mirt_ao_desc* ao,
+                       mirt_buf* seeds, mirt_buf* ao_out) try {
+    const char* const fn = "mirt_view_ao_batch";
+    ENTRY_PROLOGUE(ctx, fn);
+    if (!d || d->struct_size != sizeof(mirt_pass_desc)) return fail(ctx, MIRT_E_ARG, "%s: descriptor size mismatch", fn);
+    if (!vd || vd->struct_size != sizeof(mirt_view_desc)) return fail(ctx, MIRT_E_ARG, "%s: view descriptor size mismatch", fn);
+    pt::ViewDesc v;
+    memcpy(&v, vd, sizeof v);
+    pt::ViewAoDesc a;
+    memset(&a, 0, sizeof a);
+    if (ao && ao->struct_size == sizeof(mirt_ao_desc)) memcpy(&a, ao, sizeof a);
+    int rc;
+    uint32_t bad_frame = 0;
+    const pt::ViewVerdict verdict = pt::view_check_ao_batch(v, (const pt::ViewCamera*)cameras, n_frames, a, seeds != nullptr, ao_out != nullptr, &bad_frame);
+    if ((rc = view_batch_verdict(ctx, fn, verdict, v, n_frames, bad_frame))) return rc;
+    const pt::ViewBatchPlan bplan = pt::view_batch_plan(v, n_frames);
+    if ((rc = check_desc_arrays(ctx, fn, d, false, "mesh"))) return rc;
+    const CallBuf io[2] = {{"seeds", seeds, bplan.all.rays * 4, BUF_IN_WHOLE}, {"ao_out", ao_out, bplan.all.pixels * 8}};
+    if ((rc = check_call_buffers(ctx, fn, io, d, false, "%s: ao_out's bytes meet the seeds' or a geometry buffer's", nullptr))) return rc;
+    if (!n_frames) return MIRT_OK;   // no frames: nothing is queued, and the counter of the last call stays
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    pt::FusedArgs A;
+    memset(&A, 0, sizeof A);
+    if ((rc = fill_sets(ctx, fn, d, A))) return rc;
+    const float* table = nullptr;
+    if ((rc = upload_cameras(ctx, cameras, n_frames, &table))) return rc;
+    const pt::ViewBatchArgs VB = view_batch_args(v, bplan, table);
+    const pt::ViewGuidesPlan g = pt::view_batch_pixel_plan(bplan);
+    const int32_t* const sp = (const int32_t*)seeds->ptr;
+    rc = queue_pair(ctx, ctx->view_ao_mask, A, g.mask_words, 1u, [&](bool fast, uint32_t* mask_out, const uint32_t* mask_in) {
+        pt::launch_viewAoBatch(ctx->stream, A, VB, g.blocks, fast, a.samples, a.radius, a.bias, sp, ao_out->ptr, mask_out, mask_in);
+    });
+    return rc ? rc : finish_call(ctx, io, 2);
+} MIRT_CATCH("mirt_view_ao_batch", return MIRT_E_DEVICE)
 
 int mirt_view_ao_deferred(mirt_ctx* ctx, uint64_t* pixels) try {
     ENTRY_PROLOGUE(ctx, "mirt_view_ao_deferred");

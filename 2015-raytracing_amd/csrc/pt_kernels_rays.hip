@@ -53,45 +53,8 @@ struct RayHooks : ClosestHooks {
     PT_DEV void won(uint32_t s) const { set = s; }
 };
 
-// the per-set loop of the fused pass's shadow stage (pt_direct.hpp direct_all) on the caller's ray: the second statement of that loop,
-// to be kept in step with the first by hand (see the header)
-template <bool FAST, int GRIDS>
-PT_DEV void rays_any(const FusedArgs& A, Ray& sh, bool& defer) {
-    if (FAST) guard_or_retire(sh, defer);
-    const RayRcp rr = ray_rcp<FAST>(sh);
-    for (uint32_t s = 0; s < A.n_sets; ++s) {
-        const GridArgs& S = A.sets[s];
-        keep_in_loop(sh);
-        const bool live = !(sh.mint == sh.maxt);
-        Hit ch;
-        ch.idx = UINT32_MAX;
-        ch.t = sh.maxt;
-        bool walked = false;
-        if (!GRIDS || S.n == 1u) {
-            if (live) {
-                const BoxHit bh = cell1_box<FAST>(sh, rr, S);
-                if (bh.v) {
-                    ch = (S.kind == KIND_SPHERES) ? trace_cell1<SPHERES, true, TRI_A10, FAST, true>(sh, rr, bh, S) : trace_cell1<TRIANGLES, true, TRI_A10, FAST, true, PT_LANE_LISTS_FOR(FAST, GRIDS)>(sh, rr, bh, S);
-                    walked = true;
-                }
-            }
-        } else if (S.kind == KIND_TRIANGLES) {
-            BoxHit bh = {};
-            if (live) bh = inter_aabb_t<FAST, true>(sh, rr, set_box(S));
-            walked = live && bh.v;
-            ch = trace_dda_coop<COOP_ANY, FAST, GRIDS == 1>(walked, sh, rr, bh, S, defer);
-        } else if (live) {
-            const BoxHit bh = inter_aabb_t<FAST, true>(sh, rr, set_box(S));
-            if (bh.v) {
-                ch = trace_dda<SPHERES, true, TRI_A10, FAST, GRIDS == 1>(sh, bh, S, defer);
-                walked = true;
-            }
-        }
-        if (!walked) continue;
-        sh.maxt = ch.t;
-        if (ch.idx != UINT32_MAX) sh.mint = ch.t;
-    }
-}
+// rays_any, the any-hit loop: pt_rays_any.inc, one text for this file and for the batch's translation unit
+#include "pt_rays_any.inc"
 
 // rays: two float4 per ray {o, mint} {d, maxt}.  ANY: `occluded` (a byte per ray); else `hits` (two float4 per ray) and / or `sets`.
 // defer_mask (optimistic kernel): a bit per ray.  redo_mask (exact kernel only): the rays the optimistic kernel handed over; null: every ray.
@@ -173,12 +136,7 @@ void launch_rays(hipStream_t s, const FusedArgs& a, bool fast, const void* rays,
 // 129 VGPRs (the optimistic one 3 waves, a register over the fourth) and the single-cell ones 81 to 94 (5 waves); a lane here runs rpp * (1 + samples)
 // rays back to back with nothing to overlap them but other waves, and more waves paid at every step tried, a few spilled registers included:
 // cornell_teapot3 7.25 -> 5.99 (4 waves) -> 5.63 ms (5), cornell 2.29 -> 2.19 (6) -> 2.15 ms (7) at 1920 x 1080 x 16 with 4 AO rays.
-#ifndef PT_AO_GRID_WAVES
-#define PT_AO_GRID_WAVES 5
-#endif
-#ifndef PT_AO_CELL_WAVES
-#define PT_AO_CELL_WAVES 7
-#endif
+// (PT_AO_GRID_WAVES 5, PT_AO_CELL_WAVES 7: pt_rays_guard.hpp, where the batch's translation unit finds them too)
 #define PT_AO_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_AO_GRID_WAVES : PT_AO_CELL_WAVES)
 template <bool FAST, int GRIDS>
 __global__ void PT_AO_BOUNDS(GRIDS) k_ao(const FusedArgs A, uint32_t samples, float radius, float bias, uint2* __restrict__ ao_out, uint32_t* defer_mask,
@@ -379,37 +337,12 @@ void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool 
 // a hit.  In the grid variants a lane past the end of the tile rides along (nothing_to_do) on the last pixel (clamped).  The optimistic / exact
 // pair is per PIXEL (defer_unit): a pixel defers when the ray-side guard refuses one of its samples (it goes on dead, guard_or_retire) or one of
 // its walks defers.
-struct ViewGuideHooks : ClosestHooks {
-    PT_DEV void guard(Ray& ray, bool& defer) const { guard_or_retire(ray, defer); }
-    PT_DEV void top(Ray& ray) const { keep_in_loop(ray); }
-};
-template <bool FAST, int GRIDS>
-__global__ void __launch_bounds__(256) k_viewGuides(const FusedArgs A, const ViewArgs V, float4* normal_hits, float4* albedo_depth, uint32_t* defer_mask,
-                                                    const uint32_t* redo_mask) {
-    stage_block<FAST, GRIDS>(A);
-    const uint32_t npix = V.nrows * V.width;   // (a tile holds at most 2^32 - 256 rays: pt_view_plan.hpp)
-    uint32_t pix = blockIdx.x * 256u + threadIdx.x;
-    const bool valid = unit_valid<FAST>(pix, npix, redo_mask);
-    if (nothing_to_do<GRIDS>(valid)) return;
-    if (pix >= npix) pix = npix - 1u;
-    const float4* material = (const float4*)A.material;
-    float nx = 0.0f, ny = 0.0f, nz = 0.0f, hits = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, depth = 0.0f;
-    bool defer = false;
-    const uint32_t rpp = V.k * V.k, first = pix * rpp;
-    for (uint32_t i = 0; i < rpp; ++i) {
-        Ray ray = view_ray(V, first + i);
-        Poi poi = fresh_poi();
-        closest_all<FAST, GRIDS>(A, ray, poi, ViewGuideHooks{}, defer);
-        if (poi.matId < 0 || (uint32_t)poi.matId >= A.nmat) continue;
-        const float4 c = material[poi.matId];
-        nx += poi.n.x; ny += poi.n.y; nz += poi.n.z; hits += 1.0f;
-        ar += c.x; ag += c.y; ab += c.z; depth += ray.maxt;
-    }
-    if (!valid) return;
-    if (FAST && defer) { defer_unit(defer_mask, pix); return; }
-    if (normal_hits) normal_hits[pix] = make_float4(nx, ny, nz, hits);
-    if (albedo_depth) albedo_depth[pix] = make_float4(ar, ag, ab, depth);
-}
+// k_viewGuides, k_viewAo: the single calls' kernels -- the text of pt_view_aov_kernels.inc at BATCH false (the batch calls' are in
+// pt_kernels_view_batch.hip)
+#define PT_VIEW_RAY view_ray
+#define PT_VIEW_GUIDES_KERNEL k_viewGuides
+#define PT_VIEW_AO_KERNEL k_viewAo
+#include "pt_view_aov_kernels.inc"
 
 // fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per pixel of the tile.  Either output may be null.
 // blocks: ceil(pixels / 256), the plan's (pt_view_plan.hpp).
@@ -437,52 +370,6 @@ void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uin
 // Waves per SIMD the register allocator is held to: A/B switches of this kernel's own, starting from k_ao's (profiles/view_ao/README.md has the
 // registers per instance and the measurement).  At 1920 x 1080 x 4 with 4 AO rays on cornell_teapot3, equirect / oblique orthographic: 2.39 / 1.79 ms
 // (4 waves) -> 2.22 / 1.77 (5) -> 2.22 / 1.85 (6): the bounds stay k_ao's.
-#ifndef PT_VIEW_AO_GRID_WAVES
-#define PT_VIEW_AO_GRID_WAVES PT_AO_GRID_WAVES
-#endif
-#ifndef PT_VIEW_AO_CELL_WAVES
-#define PT_VIEW_AO_CELL_WAVES PT_AO_CELL_WAVES
-#endif
-#define PT_VIEW_AO_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_VIEW_AO_GRID_WAVES : PT_VIEW_AO_CELL_WAVES)
-template <bool FAST, int GRIDS>
-__global__ void PT_VIEW_AO_BOUNDS(GRIDS) k_viewAo(const FusedArgs A, const ViewArgs V, uint32_t samples, float radius, float bias, const int32_t* __restrict__ seeds,
-                                                    uint2* __restrict__ ao_out, uint32_t* defer_mask, const uint32_t* redo_mask) {
-    stage_block<FAST, GRIDS>(A);
-    const uint32_t npix = V.nrows * V.width;   // (a tile holds at most 2^32 - 256 rays: pt_view_plan.hpp)
-    uint32_t pix = blockIdx.x * 256u + threadIdx.x;
-    const bool valid = unit_valid<FAST>(pix, npix, redo_mask);
-    if (nothing_to_do<GRIDS>(valid)) return;
-    if (pix >= npix) pix = npix - 1u;
-    uint32_t open = 0u, cast = 0u;
-    bool defer = false;
-    const uint32_t rpp = V.k * V.k, first = pix * rpp;
-    for (uint32_t i = 0; i < rpp; ++i) {
-        Ray ray = view_ray(V, first + i);
-        if (!valid) { ray.mint = 0.0f; ray.maxt = 0.0f; }   // rides along dead: hits nothing, casts nothing
-        Poi poi = fresh_poi();
-        closest_all<FAST, GRIDS>(A, ray, poi, ViewGuideHooks{}, defer);
-        const bool casts = poi.matId >= 0;   // bouncePaths' own test (code.cl:592): no material is read
-        int32_t seed = 0;
-        if (casts) seed = seeds[first + i];
-        for (uint32_t j = 0; j < samples; ++j) {
-            Ray sh = dead_ray();
-            if (casts) {
-                sh = bounce_ray(poi, seed);   // getHemisphereRay (code.cl:545-579): the seed advances, in its register only
-                if (bias != 0.0f) sh.o = add3(poi.p, scl3(bias, poi.n));   // two fp32 operations, each rounded on its own (-ffp-contract=off)
-                sh.maxt = radius;
-            }
-            rays_any<FAST, GRIDS>(A, sh, defer);
-            if (casts) {
-                cast += 1u;
-                if (!(sh.mint == sh.maxt)) open += 1u;
-            }
-        }
-    }
-    if (!valid) return;
-    if (FAST && defer) { defer_unit(defer_mask, pix); return; }
-    ao_out[pix] = make_uint2(open, cast);
-}
-
 // fast / defer_mask / redo_mask: query_dispatch's (pt_closest.hpp), a bit per pixel of the tile.  blocks: ceil(pixels / 256), the plan's
 // (pt_view_plan.hpp).
 void launch_viewAo(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, uint32_t samples, float radius, float bias, const int32_t* seeds,

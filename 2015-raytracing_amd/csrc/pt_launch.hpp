@@ -203,7 +203,8 @@ void launch_viewRaysBatch(hipStream_t s, const ViewBatchArgs& v, void* rays);
 // pixels too (k_viewPass GUIDES; mirt_render_view_guided's one-launch route, which the caller takes at k * k = 1, 4, 16 or 64 only).
 void launch_viewPass(hipStream_t s, const FusedArgs& a, const ViewArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
                      uint32_t* defer_mask, const uint32_t* redo_mask);
-// mirt_render_view_batch: the same of the stacked frames (k_viewPassBatch, pt_kernels_view_batch.hip; there is no batch of guides, a.guide_nh / a.guide_ad are not read)
+// mirt_render_view_batch, mirt_render_view_guided_batch: the same of the stacked frames (k_viewPassBatch, pt_kernels_view_batch.hip), a.guide_nh /
+// a.guide_ad included
 void launch_viewPassBatch(hipStream_t s, const FusedArgs& a, const ViewBatchArgs& v, bool fast, bool accumulate, int32_t* seeds, void* radiance, void* pixel, float tone,
                           uint32_t* defer_mask, const uint32_t* redo_mask);
 // mirt_view_guides: the first-hit guides of those rays (k_viewGuides), float4 per tile pixel each as launch_guides writes them; either may be
@@ -216,6 +217,12 @@ void launch_viewGuides(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uin
 // seeds: int32 per tile ray, never written.  Reads the sets of `a` and nothing else of it.
 void launch_viewAo(hipStream_t s, const FusedArgs& a, const ViewArgs& v, uint32_t blocks, bool fast, uint32_t samples, float radius, float bias, const int32_t* seeds,
                    void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask);
+// mirt_view_guides_batch, mirt_view_ao_batch: the two above of the stacked frames (k_viewGuidesBatch, k_viewAoBatch, pt_kernels_view_batch.hip);
+// blocks and the mask are of the image of n_frames * height rows (pt_view_plan.hpp view_batch_pixel_plan)
+void launch_viewGuidesBatch(hipStream_t s, const FusedArgs& a, const ViewBatchArgs& v, uint32_t blocks, bool fast, void* normal_hits, void* albedo_depth, uint32_t* defer_mask,
+                            const uint32_t* redo_mask);
+void launch_viewAoBatch(hipStream_t s, const FusedArgs& a, const ViewBatchArgs& v, uint32_t blocks, bool fast, uint32_t samples, float radius, float bias, const int32_t* seeds,
+                        void* ao_out, uint32_t* defer_mask, const uint32_t* redo_mask);
 // Edge-avoiding a-trous filter (pt_kernels_filter.hip; the definition is mirt_filter_atrous's comment in include/mirt.h).  The caller has checked
 // every extent: each input and output holds width * height elements, work[0], work[1] and guide width * height float4 each.
 struct FilterArgs {

@@ -35,6 +35,13 @@ PT_DEV void guard_or_retire(Ray& r, bool& defer) {
 #define PT_RADIANCE_CELL_WAVES 7
 #endif
 #define PT_RADIANCE_BOUNDS(GRIDS) __launch_bounds__(256, (GRIDS) ? PT_RADIANCE_GRID_WAVES : PT_RADIANCE_CELL_WAVES)
+// Waves per SIMD of k_ao (the measurement is at the kernel, pt_kernels_rays.hip) and of k_viewAo / k_viewAoBatch, which start from them
+#ifndef PT_AO_GRID_WAVES
+#define PT_AO_GRID_WAVES 5
+#endif
+#ifndef PT_AO_CELL_WAVES
+#define PT_AO_CELL_WAVES 7
+#endif
 // the pass's park rows as closest_all's hooks, with this file's guard and kept division in place of the camera kernels'
 struct RadiancePark : Park {
     PT_DEV void guard(Ray& ray, bool& defer) const { guard_or_retire(ray, defer); }

@@ -2,7 +2,7 @@
 //   PT_VIEW_BATCH          false / true: the compile-time flag of both kernels (view_ray<PT_VIEW_BATCH>)
 //   PT_VIEW_ARGS           ViewArgs / ViewBatchArgs
 //   PT_VIEW_RAYS_KERNEL    k_viewRays / k_viewRaysBatch
-//   PT_VIEW_PASS_TEMPLATE  template <bool FAST, int GRIDS, bool GUIDES = false> / template <bool FAST, int GRIDS>
+//   PT_VIEW_PASS_TEMPLATE  template <bool FAST, int GRIDS, bool GUIDES = false>, in both
 //   PT_VIEW_PASS_KERNEL    k_viewPass / k_viewPassBatch
 // pt_kernels_rays.hip includes it with the first of each (the single calls: mirt_view_rays, mirt_render_view, mirt_render_view_guided) and gets,
 // token for token, the kernels it had before there was a batch; pt_kernels_view_batch.hip includes it with the second.  Text and not a shared
@@ -46,13 +46,11 @@ __global__ void __launch_bounds__(256) PT_VIEW_RAYS_KERNEL(const PT_VIEW_ARGS V,
 // BATCH (mirt_render_view_batch): N cameras' frames of one size stacked into one image of N * height rows.  Only the ray differs -- each lane
 // loads its frame's camera from the table V.cameras (view_ray<true>), twelve registers that are dead before the segment loop like the rest of
 // the generator's.  A frame's rays are a multiple of rpp, so a block still holds whole pixels, possibly of two frames: the resolve, the
-// per-block verdict and the redo pass see an image of width x (N * height) and need nothing new.  No GUIDES variant.
+// per-block verdict and the redo pass see an image of width x (N * height) and need nothing new -- nor does GUIDES (mirt_render_view_guided_batch):
+// guides_emit's pixel index is tile-local in the stacked image.
 PT_VIEW_PASS_TEMPLATE
 __global__ void PT_VIEW_BOUNDS(GRIDS) PT_VIEW_PASS_KERNEL(const FusedArgs A, const PT_VIEW_ARGS V, uint32_t count, int32_t* __restrict__ seeds, float4* radiance,
                                                    uchar4* __restrict__ pixel, float tone, uint32_t* defer_mask, const uint32_t* redo_mask) {
-#if PT_VIEW_BATCH
-    constexpr bool GUIDES = false;   // there is no batch of guides
-#endif
     const uint32_t blk = blockIdx.x;
     if (!FAST && redo_mask && (redo_mask[blk >> 5] >> (blk & 31u) & 1u) == 0u) return;   // block-uniform: nothing of the block has begun
     stage_block<FAST, GRIDS>(A);

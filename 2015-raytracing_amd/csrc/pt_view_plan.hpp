@@ -1,7 +1,8 @@
 // pt_view_plan.hpp -- the host side of the panoramic, fisheye and orthographic cameras (mirt_view_rays, mirt_render_view, mirt_view_guides,
 // mirt_render_view_guided, mirt_view_ao; include/mirt.h): the descriptor checks that need no device, the launch plan -- the tile's rays, its blocks of 256
 // consecutive ray ids, the whole pixels a block holds and those of the ragged last block -- the route rule of the guided frame, and the checks and
-// the plan of the batch calls (mirt_view_rays_batch, mirt_render_view_batch; tests/view_batch_plan_dump.cpp).  Plain
+// the plan of the batch calls (mirt_view_rays_batch, mirt_render_view_batch; tests/view_batch_plan_dump.cpp -- mirt_view_guides_batch,
+// mirt_render_view_guided_batch, mirt_view_ao_batch; tests/view_batch_aov_plan_dump.cpp).  Plain
 // integers and floats: no HIP header and no device, so a plain C++ compiler builds it and tests/test_view_plan.py,
 // tests/test_view_guides_plan.py and tests/test_view_ao_plan.py check it on the CPU (tests/view_plan_dump.cpp, tests/view_guides_plan_dump.cpp,
 // tests/view_ao_plan_dump.cpp).  mirt_abi.cpp is the caller and owns the messages.
@@ -172,6 +173,31 @@ inline ViewVerdict view_check_render_batch(const ViewDesc& v, const ViewCamera* 
     return VIEW_OK;
 }
 
+// What mirt_view_guides_batch, mirt_view_ao_batch and mirt_render_view_guided_batch ask: the batch's rules first (view_check_batch, in its order),
+// then the single call's own in the single call's order -- view_check_guides', view_check_ao's, view_check_render_guided's
+inline ViewVerdict view_check_guides_batch(const ViewDesc& v, const ViewCamera* cameras, uint32_t n_frames, bool normal_hits, bool albedo_depth, uint32_t* bad_frame = nullptr) {
+    const ViewVerdict d = view_check_batch(v, cameras, n_frames, bad_frame);
+    if (d != VIEW_OK) return d;
+    return normal_hits || albedo_depth ? VIEW_OK : VIEW_NO_GUIDE;
+}
+inline ViewVerdict view_check_ao_batch(const ViewDesc& v, const ViewCamera* cameras, uint32_t n_frames, const ViewAoDesc& ao, bool seeds, bool ao_out, uint32_t* bad_frame = nullptr) {
+    const ViewVerdict d = view_check_batch(v, cameras, n_frames, bad_frame);
+    if (d != VIEW_OK) return d;
+    if (ao.struct_size != sizeof(ViewAoDesc)) return VIEW_AO_STRUCT_SIZE;
+    if (!ao.samples || ao.samples > kViewAoMaxSamples) return VIEW_AO_SAMPLES;
+    if (!(ao.radius > 0.0f)) return VIEW_AO_RADIUS;   // a NaN compares false; +inf passes
+    if (!(ao.bias >= 0.0f) || isinf(ao.bias)) return VIEW_AO_BIAS;
+    if (!seeds) return VIEW_AO_NO_SEEDS;
+    if (!ao_out) return VIEW_AO_NO_OUTPUT;
+    return VIEW_OK;
+}
+inline ViewVerdict view_check_render_guided_batch(const ViewDesc& v, const ViewCamera* cameras, uint32_t n_frames, bool seeds, bool radiance, bool pixel, bool normal_hits,
+                                                  bool albedo_depth, uint32_t* bad_frame = nullptr) {
+    const ViewVerdict d = view_check_render_batch(v, cameras, n_frames, seeds, radiance, pixel, bad_frame);
+    if (d != VIEW_OK) return d;
+    return normal_hits || albedo_depth ? VIEW_OK : VIEW_NO_GUIDE;
+}
+
 // The launch plan of a descriptor that passed view_check_desc.  A block is 256 consecutive tile-local ray ids; rpp = k * k is 1, 4, 16, 64 or 256
 // and divides 256, so a block holds pixels_per_block WHOLE pixels -- the unit the in-block resolve and the optimistic / exact pair work in.
 struct ViewPlan {
@@ -230,6 +256,9 @@ inline ViewGuidesPlan view_guides_plan(const ViewPlan& p) {
     return g;
 }
 
+// ... and of the batch (k_viewGuidesBatch, k_viewAoBatch): the same of the stacked image's n_frames * P pixels, 0 and 0 without frames
+inline ViewGuidesPlan view_batch_pixel_plan(const ViewBatchPlan& b) { return view_guides_plan(b.all); }
+
 // Whether mirt_render_view_guided writes the guides from the frame's own launch (k_viewPass GUIDES) instead of queueing k_viewGuides behind it:
 // a pixel's samples must be consecutive lanes of ONE wave, which the kernel sums by lane shuffles -- rpp 1, 4, 16 or 64.  Not at 256 rays (a
 // pixel spans four waves), and nowhere with MIRT_GUIDED_VIEW=0 (env_on false).  has_grids (a set of more than one cell: the grid kernels run)
@@ -239,6 +268,13 @@ inline ViewGuidesPlan view_guides_plan(const ViewPlan& p) {
 inline bool view_guides_in_pass(uint32_t rpp, bool has_grids, bool env_on) {
     (void)has_grids;
     return env_on && (rpp == 1u || rpp == 4u || rpp == 16u || rpp == 64u);
+}
+// The same decision for mirt_render_view_guided_batch (k_viewPassBatch GUIDES against k_viewPassBatch then k_viewGuidesBatch), made on the batch's
+// own measurement: 1024 frames of 32 x 16 x 4, the one launch beats the two by 0.069 to 0.076 ms in 0.51 (cornell, single-cell sets) and by 0.30 ms
+// in 2.57 (cornell_teapot3, grids), against a spread of 0.007 ms between the two runs (profiles/view_batch_aov/timing.json).  Both families keep
+// the one launch; a family that stops beating the two launches by more than the runs' spread goes to them HERE.
+inline bool view_batch_guides_in_pass(uint32_t rpp, bool has_grids, bool env_on) {
+    return view_guides_in_pass(rpp, has_grids, env_on);
 }
 
 }  // namespace pt

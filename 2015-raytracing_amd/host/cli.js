@@ -4,7 +4,7 @@
 //   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.rgba> [--granular [--graph|--fusion]] [--device-grid] [--no-acu] [--passes-in-one-launch [--every-pass]] [--bounces N] [--seeds file.i32] [--gpus N [--force-rccl] [--post-in-tiles]] [--guides PREFIX] [--denoise [iterations]] [--upscale F] [--ao PREFIX [--ao-samples N] [--ao-radius R] [--ao-bias B]]
 //                                                                                   -> RGBA8 frame, or a PPM when <out> ends in .ppm (+ <out>.radiance.f32) via the N-API addon; --guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32 (first-hit guide buffers, raw float4 rows); --ao: + PREFIX.ao.u32 (ambient occlusion of the first hit, mirt_render_ao: raw uint32 pairs {open, cast} per pixel, N AO rays of length R per hit sample, default 4 and unbounded, displaced by B = 0.001 along the normal; taken before the first pass, the seeds are not advanced) and PREFIX.ao.pgm (a byte per pixel, floor(255 * open / cast + 0.5), 255 where cast is 0), not with --gpus N; --denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous, guided by those buffers; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --upscale F (2..4): width x height is the OUTPUT size and raysPerPixel is per pixel of the (width / F) x (height / F) frame that is traced -- <out> is that frame rebuilt at full resolution from the guides of both sizes (mirt_upsample_guided; + <out>.upsampled.f32), <out>.radiance.f32 (and with --denoise <out>.filtered.f32) are the LOW frame, --guides PREFIX writes the full-resolution guides and PREFIX.normal_hits_lo.f32 / .albedo_depth_lo.f32; not with --gpus N unless --post-in-tiles; --post-in-tiles (with --gpus N): --denoise and --upscale run tile-local -- every device exchanges halo rows with its neighbours and filters / upsamples its own rows (mirt_exchange_rows, mirt_filter_atrous_rows, mirt_upsample_guided_rows), only finished rows are gathered; the same bytes in <out>, <out>.filtered.f32 and <out>.upsampled.f32, and no <out>.radiance.f32 (the unfiltered sums stay on their devices)
 //   node cli.js render <scene.xml> <width> <height> <raysPerPixel> <passes> <out.ppm> --view equirect|fisheye|ortho [--eye x,y,z] [--look x,y,z] [--up x,y,z] [--fov degrees] [--ortho-size w,h] [--bounces N] [--seeds file.i32] [--view-guides PREFIX] [--view-denoise [iterations]] [--view-ao PREFIX [--ao-samples N] [--ao-radius R] [--ao-bias B]]  -> a frame of a panoramic (360 x 180 degrees), fisheye (equidistant, --fov the full field of view, default 180) or orthographic (--ortho-size the window, default the scene box's extents in x and y) camera, one launch per pass (mirt_render_view): raysPerPixel 1, 4, 16, 64 or 256, un-jittered; the default eye is the scene box's centre, looking down -z; passes are progressive (MIRT_VIEW_ACCUMULATE, tone 1 / (raysPerPixel * p)); + <out>.radiance.f32; --view-guides: + PREFIX.normal_hits.f32, PREFIX.albedo_depth.f32, the camera's first-hit guides (mirt_view_guides' definition; taken by the first pass, mirt_render_view_guided); --view-denoise: <out> is the a-trous-filtered frame (mirt_filter_atrous behind the last pass, on the device; + <out>.filtered.f32), <out>.radiance.f32 stays the unfiltered sums; --view-ao: + PREFIX.ao.u32 (the camera's ambient occlusion, mirt_view_ao: raw uint32 pairs {open, cast} per pixel, N, R and B as for --ao; taken before the first pass, the seeds are not advanced) and PREFIX.ao.pgm (a byte per pixel, floor(255 * open / cast + 0.5), 0 where cast is 0); not with --gpus, --guides, --denoise, --ao (the thin-lens camera's), --upscale
-//   node cli.js views <scene.xml> cameras.f32 <width> <height> <raysPerPixel> <passes> out.radiance.f32 --view equirect|fisheye|ortho [--eyes] [--bounces N] [--seed-base X] [--ppm PREFIX] [camera options shared by all frames]  -> the frames of N cameras in one launch per pass (mirt_render_view_batch): cameras.f32 holds 12 raw floats per frame -- eye, right, up, forward, used as given -- or, with --eyes, 3 per frame: the eyes of cameras with right = +x, up = +y, forward = -z; out.radiance.f32 receives the N frames of float4 sums back to back; --ppm PREFIX: + PREFIX.<frame>.ppm, one picture per frame; the camera options that all frames share are --fov and --ortho-size; seeds from mirt_seed_fill(first_ray = 0, count, X)
+//   node cli.js views <scene.xml> cameras.f32 <width> <height> <raysPerPixel> <passes> out.radiance.f32 --view equirect|fisheye|ortho [--eyes] [--bounces N] [--seed-base X] [--ppm PREFIX] [--guides PREFIX] [--ao PREFIX [--ao-samples N] [--ao-radius R] [--ao-bias B]] [camera options shared by all frames]  -> the frames of N cameras in one launch per pass (mirt_render_view_batch): cameras.f32 holds 12 raw floats per frame -- eye, right, up, forward, used as given -- or, with --eyes, 3 per frame: the eyes of cameras with right = +x, up = +y, forward = -z; out.radiance.f32 receives the N frames of float4 sums back to back; --ppm PREFIX: + PREFIX.<frame>.ppm, one picture per frame; --guides PREFIX: + PREFIX.normal_hits.f32 and PREFIX.albedo_depth.f32, the N frames' first-hit guides back to back (taken by the first pass, mirt_render_view_guided_batch); --ao PREFIX: + PREFIX.ao.u32, the N frames' ambient occlusion back to back (mirt_view_ao_batch: raw uint32 pairs {open, cast} per pixel, N, R and B as for render's --ao; taken before the first pass, the seeds are not advanced); the camera options that all frames share are --fov and --ortho-size; seeds from mirt_seed_fill(first_ray = 0, count, X)
 //   node cli.js pack-frame <1|4|7> <mesh.json|mol.pdb|-> <width> <height> [nSlabs]  -> packed inputs of an Assign01/04/07 frame job (stdout)
 //   node cli.js frame      <1|4|7> <mesh.json|mol.pdb|-> [<mol.pdb>] <width> <height> <nSlabs|0> <out.rgba> [--one-launch] [--aa K]  -> RGBA8 frame of that job; 7 with a mesh AND a molecule: both models (computeBoth); --one-launch: the whole frame in one launch, no ray buffer; --aa K (1 to 4, not with 1): K x K samples a pixel averaged in that one launch
 //   node cli.js ingest <mesh.json> <out-prefix> [--device]                          -> parseMeshJSON's arrays (<out>.pos.f64, .nor.f64, .meta.json) by the host or the device
@@ -266,13 +266,33 @@ if (cmd === "pack") {
   const num = (flag, dflt) => { const i = rest.indexOf(flag); if (i < 0) return dflt; const v = Number(rest[i + 1]); if (!Number.isInteger(v) || v < 0) usage(); return v; };
   const pi = rest.indexOf("--ppm");
   if (pi >= 0 && !rest[pi + 1]) usage();
+  const bopt = { view: viewOptions(rest), eyes: eyes, bounces: num("--bounces", 5), seedBase: num("--seed-base", 0), countDeferred: true };
+  let j, guidesPrefix = null, aoPrefix = null;
+  if ((j = rest.indexOf("--guides")) >= 0) {   // the frames' first-hit guides, from the first pass (mirt_render_view_guided_batch)
+    if (!rest[j + 1]) usage();
+    guidesPrefix = rest[j + 1];
+    bopt.guides = true;
+  }
+  if ((j = rest.indexOf("--ao")) >= 0) {   // the frames' ambient occlusion (mirt_view_ao_batch), before the first pass
+    if (!rest[j + 1]) usage();
+    aoPrefix = rest[j + 1];
+    bopt.ao = {};
+    if ((j = rest.indexOf("--ao-samples")) >= 0) bopt.ao.samples = +rest[j + 1];
+    if ((j = rest.indexOf("--ao-radius")) >= 0) bopt.ao.radius = +rest[j + 1];
+    if ((j = rest.indexOf("--ao-bias")) >= 0) bopt.ao.bias = +rest[j + 1];
+  }
   let res;
   try {
-    res = renderer.renderViewBatchFile(vf, cameras, vw, vh, vrpp, vpasses, { view: viewOptions(rest), eyes: eyes, bounces: num("--bounces", 5), seedBase: num("--seed-base", 0), countDeferred: true });
+    res = renderer.renderViewBatchFile(vf, cameras, vw, vh, vrpp, vpasses, bopt);
   } catch (e) { process.stderr.write(e.message + "\n"); process.exit(2); }
-  fs.writeFileSync(vout, Buffer.from(res.radiance.buffer, res.radiance.byteOffset, res.radiance.byteLength));
+  const bdump = (name, a) => fs.writeFileSync(name, Buffer.from(a.buffer, a.byteOffset, a.byteLength));
+  bdump(vout, res.radiance);
+  if (res.guides) { bdump(`${guidesPrefix}.normal_hits.f32`, res.guides.normalHits); bdump(`${guidesPrefix}.albedo_depth.f32`, res.guides.albedoDepth); }
+  if (res.ao) bdump(`${aoPrefix}.ao.u32`, res.ao.pairs);
   if (pi >= 0) for (let f = 0; f < res.frames; f++) writeFrame(`${rest[pi + 1]}.${f}.ppm`, res.pixel.subarray(f * vw * vh * 4, (f + 1) * vw * vh * 4), vw, vh);
   process.stderr.write(`rendered ${res.frames} ${vw}x${vh} frames of ${vf}, rpp ${vrpp}, ${vpasses} pass(es), ${rest[rest.indexOf("--view") + 1]} cameras: ${res.ms.toFixed(2)} ms on ${res.device}; rays redone by the exact kernel: ${res.deferred}\n`);
+  if (res.guidedViews !== undefined) process.stderr.write(`batch calls that wrote their guides: ${res.guidedViews}\n`);
+  if (res.ao) process.stderr.write(`ambient occlusion of ${res.frames} frames; pixels redone by the exact kernel: ${res.ao.deferred}\n`);
 } else if (cmd === "devices") {
   const { webcl } = require("./webcl.js");
   for (const p of webcl.getPlatforms()) {

@@ -840,6 +840,10 @@ function renderViewFile(file, width, height, rpp, passes, opt) {
 // MIRT_VIEW_ACCUMULATE from the second on and tone 1 / (rpp * p).  cameras: Float32Array of 12 per frame -- eye, right, up, forward, used as
 // given -- or, with opt.eyes, of 3 per frame: the eyes of cameras with the basis right = +x, up = +y, forward = -z.  opt.view: makeView's v
 // (the model and what all frames share; its eye, look and up are not used); opt.bounces; opt.seedBase: seedFill(0, n, seedBase).
+// opt.guides: + guides {normalHits, albedoDepth} (Float32Array, float4 per pixel, N frames back to back) and guidedViews -- pass 1 goes through
+// queue.renderViewGuidedBatch (mirt_render_view_guided_batch), the later ones are plain.  opt.ao ({samples, radius, bias}): + ao {pairs:
+// Uint32Array {open, cast} per pixel, deferred} -- queue.viewAoBatch (mirt_view_ao_batch) before the first pass, from the seeds as they stand
+// there (it does not advance them), outside the timed span.
 function renderViewBatchFile(file, cameras, width, height, rpp, passes, opt) {
   opt = opt || {};
   const per = opt.eyes ? 3 : 12;
@@ -859,13 +863,24 @@ function renderViewBatchFile(file, cameras, width, height, rpp, passes, opt) {
   const npix = frames * width * height, n = npix * rpp;
   const mk = (bytes) => ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(bytes, 16));
   const sb = mk(n * 4), rb = mk(npix * 16), pb = mk(npix * 4);
+  if ((opt.guides || opt.ao) && !q.hasViewBatchAov()) throw new Error("the loaded addon has no renderViewGuidedBatch / viewAoBatch");
+  const nhb = opt.guides ? mk(npix * 16) : null, adb = opt.guides ? mk(npix * 16) : null;
   if (n) q.seedFill(sb, 0, n, opt.seedBase || 0);
   const desc = { spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, lights: packed.lights, material: dev.material, bounces: opt.bounces === undefined ? 5 : opt.bounces };
+  let ao = null;
+  if (opt.ao) {
+    const ab = mk(npix * 8);
+    q.viewAoBatch(desc, view, table, opt.ao, sb, ab);
+    ao = { pairs: new Uint32Array(npix * 2), deferred: npix ? q.viewAoDeferred() : 0 };
+    if (npix) q.enqueueReadBuffer(ab, true, 0, npix * 8, ao.pairs, []);
+  }
   q.finish();
   const t0 = process.hrtime.bigint();
   let deferred = 0;
   for (let p = 1; p <= passes; p++) {
-    q.renderViewBatch(desc, Object.assign({}, view, { flags: p > 1 ? 1 : 0, tone: 1 / (rpp * p) }), table, sb, rb, pb);
+    const vp = Object.assign({}, view, { flags: p > 1 ? 1 : 0, tone: 1 / (rpp * p) });
+    if (opt.guides && p === 1) q.renderViewGuidedBatch(desc, vp, table, sb, rb, pb, nhb, adb);
+    else q.renderViewBatch(desc, vp, table, sb, rb, pb);
     if (opt.countDeferred) deferred += q.viewDeferred();
   }
   q.finish();
@@ -874,6 +889,15 @@ function renderViewBatchFile(file, cameras, width, height, rpp, passes, opt) {
   if (npix) {
     q.enqueueReadBuffer(pb, true, 0, npix * 4, res.pixel, []);
     q.enqueueReadBuffer(rb, true, 0, npix * 16, res.radiance, []);
+  }
+  if (ao) res.ao = ao;
+  if (opt.guides) {
+    res.guidedViews = q.guidedViews();
+    res.guides = { normalHits: new Float32Array(npix * 4), albedoDepth: new Float32Array(npix * 4) };
+    if (npix) {
+      q.enqueueReadBuffer(nhb, true, 0, npix * 16, res.guides.normalHits, []);
+      q.enqueueReadBuffer(adb, true, 0, npix * 16, res.guides.albedoDepth, []);
+    }
   }
   ctx.release();
   return res;
@@ -911,4 +935,27 @@ function viewGuidesFile(file, width, height, rpp, opt) {
   return res;
 }
 
-module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderViewFile, renderViewBatchFile, viewRaysFile, viewGuidesFile, makeView, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };
+// -> {normalHits, albedoDepth, frames}: the first-hit guides alone of N cameras' frames, back to back, in one launch (queue.viewGuidesBatch:
+// mirt_view_guides_batch).  cameras: Float32Array of 12 per frame, as for renderViewBatchFile; opt.view: makeView's v (what all frames share);
+// opt.normalHits === false or opt.albedoDepth === false leaves that output out of the call (null in the result)
+function viewGuidesBatchFile(file, cameras, width, height, rpp, opt) {
+  opt = opt || {};
+  if (cameras.length % 12) throw new Error(`cameras: ${cameras.length} floats is not a whole number of 12 per frame`);
+  const frames = cameras.length / 12;
+  const packed = scene.packScene(scene.loadSceneFile(file, width, height), width, height, 4);
+  const view = makeView(packed, width, height, rpp, opt.view);
+  for (const name of ["eye", "right", "up", "forward"]) delete view[name];
+  const ctx = webcl.createContext(pickDevice(opt.device)), q = ctx.createCommandQueue();
+  if (!q.hasViewBatchAov()) throw new Error("the loaded addon has no viewGuidesBatch");
+  const dev = uploadScene(ctx, q, packed);
+  const npix = frames * width * height;
+  const mk = (wanted) => (wanted === false ? null : ctx.createBuffer(webcl.MEM_READ_WRITE, Math.max(npix * 16, 16)));
+  const nhb = mk(opt.normalHits), adb = mk(opt.albedoDepth);
+  q.viewGuidesBatch({ spheres: dev.sph, triangles: dev.tri, meshes: dev.meshes, material: dev.material }, view, cameras, nhb, adb);
+  const read = (b) => { if (!b) return null; const a = new Float32Array(npix * 4); if (npix) q.enqueueReadBuffer(b, true, 0, npix * 16, a, []); return a; };
+  const res = { normalHits: read(nhb), albedoDepth: read(adb), frames: frames };
+  ctx.release();
+  return res;
+}
+
+module.exports = { GranularRenderer, FusedRenderer, renderFile, renderUpscaled, traceFile, renderViewFile, renderViewBatchFile, viewRaysFile, viewGuidesFile, viewGuidesBatchFile, makeView, renderTiled, radianceSums, getLocalWS, KERNELS, setWebCL };

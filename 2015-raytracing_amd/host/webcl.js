@@ -263,6 +263,27 @@ class WebCLCommandQueue {
     if (desc.bounces !== undefined) d.bounces = desc.bounces;
     wrap(() => native().renderViewBatch(this.ctx.h, d, Object.assign({}, view), this._cameras(cameras), seeds ? seeds.h : null, radiance ? radiance.h : null, pixel ? pixel.h : null));
   }
+  // ---- extension: the batch's guides and ambient occlusion (mirt_view_guides_batch, mirt_render_view_guided_batch, mirt_view_ao_batch): what
+  // viewGuides, renderViewGuided and viewAo (below) are to one camera, for the N frames of `cameras` in one launch, the buffers holding the
+  // frames back to back.  guidedViews() counts a guided batch call on the one-launch route once; viewAoDeferred() reports the last viewAoBatch.
+  // hasViewBatchAov(): the loaded library has the three entry points
+  hasViewBatchAov() {
+    return typeof native().viewGuidesBatch === "function" && typeof native().renderViewGuidedBatch === "function" && typeof native().viewAoBatch === "function";
+  }
+  viewGuidesBatch(desc, view, cameras, normalHits, albedoDepth) {
+    const d = Object.assign(this._setsDesc(desc), { material: desc.material ? desc.material.h : undefined });
+    wrap(() => native().viewGuidesBatch(this.ctx.h, d, Object.assign({}, view), this._cameras(cameras), normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
+  }
+  renderViewGuidedBatch(desc, view, cameras, seeds, radiance, pixel, normalHits, albedoDepth) {
+    const d = Object.assign(this._setsDesc(desc), { lights: desc.lights || [], material: desc.material ? desc.material.h : undefined });
+    if (desc.bounces !== undefined) d.bounces = desc.bounces;
+    wrap(() => native().renderViewGuidedBatch(this.ctx.h, d, Object.assign({}, view), this._cameras(cameras), seeds ? seeds.h : null, radiance ? radiance.h : null,
+                                              pixel ? pixel.h : null, normalHits ? normalHits.h : null, albedoDepth ? albedoDepth.h : null));
+  }
+  viewAoBatch(desc, view, cameras, aoDesc, seeds, aoOut) {
+    const d = this._setsDesc(desc);
+    wrap(() => native().viewAoBatch(this.ctx.h, d, Object.assign({}, view), this._cameras(cameras), aoDesc || {}, seeds ? seeds.h : null, aoOut ? aoOut.h : null));
+  }
   // ---- extension: the first-hit guides of those cameras (mirt_view_guides, mirt_render_view_guided).  viewGuides(desc, view, normalHits,
   // albedoDepth): float4 per tile pixel each, as renderGuides writes them for the thin lens -- what filterAtrous reads; either may be null; of desc
   // the sets and material are read; depth is in units of |forward| and the basis as given.  renderViewGuided(desc, view, seeds, radiance, pixel,

@@ -166,6 +166,10 @@ SYMBOLS = {
     "mirt_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mirt_view_ao": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.POINTER(_AoDesc), C.c_void_p, C.c_void_p]),
     "mirt_view_ao_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mirt_view_guides_batch": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mirt_render_view_guided_batch": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "mirt_view_ao_batch": (C.c_int, [C.c_void_p, C.POINTER(_PassDesc), C.POINTER(_ViewDesc), C.c_void_p, C.c_uint32, C.POINTER(_AoDesc), C.c_void_p, C.c_void_p]),
     "mirt_filter_atrous": (C.c_int, [C.c_void_p, C.POINTER(_FilterDesc)]),
     "mirt_upsample_guided": (C.c_int, [C.c_void_p, C.POINTER(_UpsampleDesc)]),
     "mirt_pass_deferred": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -627,7 +631,7 @@ class Context:
                                          seeds.h if seeds else None, radiance.h if radiance else None, pixel.h if pixel else None))
 
     def view_deferred(self):
-        """how many rays the last render_view or render_view_batch call re-ran in the exact kernel, in whole blocks of 256 (mirt_view_deferred)"""
+        """how many rays the last render_view, render_view_batch or render_view_guided_batch call re-ran in the exact kernel, in whole blocks of 256 (mirt_view_deferred)"""
         return self._deferred(lib().mirt_view_deferred)
 
     @staticmethod
@@ -672,7 +676,7 @@ class Context:
                                                 normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
 
     def guided_views(self):
-        """how many render_view_guided calls of this context wrote the guides from the frame's own launch (mirt_ctx_guided_views)"""
+        """how many render_view_guided and render_view_guided_batch calls of this context wrote the guides from the frame's own launch (mirt_ctx_guided_views)"""
         n = C.c_uint64()
         self._chk(lib().mirt_ctx_guided_views(self.h, C.byref(n)))
         return n.value
@@ -698,8 +702,33 @@ class Context:
                                      C.byref(ao) if ao is not None else None, seeds.h if seeds else None, ao_out.h if ao_out else None))
 
     def view_ao_deferred(self):
-        """how many pixels the last view_ao call re-ran in the exact kernel (mirt_view_ao_deferred)"""
+        """how many pixels the last view_ao or view_ao_batch call re-ran in the exact kernel (mirt_view_ao_deferred)"""
         return self._deferred(lib().mirt_view_ao_deferred)
+
+    def view_guides_batch(self, scene_desc, view, cameras, normal_hits=None, albedo_depth=None):
+        """The first-hit guides of N cameras' frames in one launch (mirt_view_guides_batch): the buffers hold the frames back to back, and
+        frame f ends in each as after view_guides on its slice with the basis cameras[f] ([N, 12] floats on the host)."""
+        ptr, n, keep = self._cameras(cameras)
+        self._chk(lib().mirt_view_guides_batch(self.h, C.byref(scene_desc) if scene_desc is not None else None, C.byref(view) if view is not None else None,
+                                               ptr, n, normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
+    def render_view_guided_batch(self, scene_desc, view, cameras, seeds, radiance=None, pixel=None, normal_hits=None, albedo_depth=None):
+        """render_view_batch and view_guides_batch in one call (mirt_render_view_guided_batch): the same bytes in every buffer; at k = 1, 2, 4
+        and 8 the frames' own launch writes the guides (guided_views counts the call once).  The outputs are final in stream order."""
+        ptr, n, keep = self._cameras(cameras)
+        self._chk(lib().mirt_render_view_guided_batch(self.h, C.byref(scene_desc) if scene_desc is not None else None,
+                                                      C.byref(view) if view is not None else None, ptr, n, seeds.h if seeds else None,
+                                                      radiance.h if radiance else None, pixel.h if pixel else None,
+                                                      normal_hits.h if normal_hits else None, albedo_depth.h if albedo_depth else None))
+
+    def view_ao_batch(self, scene_desc, view, cameras, seeds, ao_out, samples=AO_DEFAULT_SAMPLES, radius=float("inf"), bias=AO_DEFAULT_BIAS):
+        """Ambient occlusion of N cameras' frames in one launch (mirt_view_ao_batch): seeds (int32 per ray of the batch, read and not written)
+        and ao_out (uint32 {open, cast} per pixel) hold the frames back to back, frame f's as view_ao leaves them with the basis cameras[f].
+        An _AoDesc may be given in place of `samples`."""
+        ao = samples if isinstance(samples, _AoDesc) else _AoDesc(C.sizeof(_AoDesc), int(samples), float(radius), float(bias))
+        ptr, n, keep = self._cameras(cameras)
+        self._chk(lib().mirt_view_ao_batch(self.h, C.byref(scene_desc) if scene_desc is not None else None, C.byref(view) if view is not None else None,
+                                           ptr, n, C.byref(ao) if ao is not None else None, seeds.h if seeds else None, ao_out.h if ao_out else None))
 
     def filter_atrous(self, width, height, tone, radiance, normal_hits, albedo_depth, filtered=None, pixel=None, iterations=None,
                       normal_power_log2=None, sigma_depth=None, sigma_colour=None, demodulate=None, structure=None):

@@ -3,7 +3,9 @@ mirt_trace_occluded, mirt_trace_radiance; the definitions are include/mirt.h's) 
 panoramic, fisheye or orthographic camera into cuda tensors (mirt_render_view), view_guides: its first-hit guides (mirt_view_guides),
 view_ao: its ambient occlusion (mirt_view_ao), and
 denoised_view: progressive frames, the guides from the first (mirt_render_view_guided), and the a-trous filter behind the last;
-render_views: the frames of N cameras in one launch (mirt_render_view_batch), and probe_sh: the order-2 spherical-harmonic coefficients of the
+render_views: the frames of N cameras in one launch (mirt_render_view_batch; with want_guides mirt_render_view_guided_batch),
+view_guides_batch and view_ao_batch: their guides and ambient occlusion (mirt_view_guides_batch, mirt_view_ao_batch), probe_depth: the mean
+distance to the first hit around N positions, and probe_sh: the order-2 spherical-harmonic coefficients of the
 radiance arriving at N positions, from N small equirect frames and one matmul against sh9_basis.
 
 The tensors are not copied: each is wrapped as a buffer of the context (Context.wrap) for the length of the call, and the launches are queued on
@@ -202,20 +204,73 @@ def denoised_view(ctx, dev_scene, view, seeds, passes=1, bounces=5, **filter_par
     return filtered, pixel
 
 
-def render_views(ctx, dev_scene, view, cameras, seeds, bounces=5, accumulate_into=None, want_pixel=False):
-    """-> radiance [N, height, width, 4] float32 cuda, or (radiance, pixel [N, height, width, 4] uint8) with want_pixel: the whole frames of N
-    cameras that share everything of `view` but the basis, in one launch (mirt_render_view_batch).  cameras: anything np.asarray(..., float32)
-    turns into [N, 12] -- eye, right, up, forward per frame; a cuda tensor is brought to the host (48 bytes a frame).  The call's ACCUMULATE flag
-    comes from accumulate_into (view.flags is neither read nor changed), a float32 cuda [N, height, width, 4] of sums to continue (written in place and returned).  seeds: int32 cuda
-    [N * height * width * k * k], frame after frame, advanced in place."""
-    from . import mirt
+def _batch_cameras(view, cameras, who):
+    """-> cameras as a contiguous float32 numpy [N, 12]; a cuda tensor is brought to the host (48 bytes a frame).  Whole frames only."""
     if isinstance(cameras, torch.Tensor):
         cameras = cameras.detach().cpu().numpy()
     cam = np.ascontiguousarray(np.asarray(cameras, np.float32))
     if cam.ndim != 2 or cam.shape[1] != 12:
         raise ValueError(f"cameras: expected [N, 12] floats (eye, right, up, forward per frame), got {cam.shape}")
     if view.row0 or (view.nrows and view.nrows != view.height):
-        raise ValueError("render_views renders whole frames: view.row0 and view.nrows must be 0")
+        raise ValueError(f"{who} renders whole frames: view.row0 and view.nrows must be 0")
+    return cam
+
+
+def view_guides_batch(ctx, dev_scene, view, cameras):
+    """-> (normal_hits, albedo_depth), float32 cuda [N, height, width, 4] each on the context's device: the first-hit guides of the whole frames
+    of N cameras that share everything of `view` but the basis, in one launch (mirt_view_guides_batch).  cameras: as for render_views."""
+    cam = _batch_cameras(view, cameras, "view_guides_batch")
+    nf = cam.shape[0]
+    npix = nf * view.height * view.width
+    device = torch.device("cuda", ctx.device)
+    nh = torch.empty((nf, view.height, view.width, 4), dtype=torch.float32, device=device)
+    ad = torch.empty((nf, view.height, view.width, 4), dtype=torch.float32, device=device)
+    if nf:
+        with _OnTorchStream(ctx, device):
+            wrapped = [ctx.wrap(nh.data_ptr(), npix * 16), ctx.wrap(ad.data_ptr(), npix * 16)]
+            try:
+                ctx.view_guides_batch(dev_scene.pass_desc(None, None), view, cam, wrapped[0], wrapped[1])
+            finally:
+                for b in wrapped:
+                    b.release()
+    return nh, ad
+
+
+def view_ao_batch(ctx, dev_scene, view, cameras, seeds, samples=None, radius=float("inf"), bias=None):
+    """-> ao, int32 cuda [N, height, width, 2] on the context's device: {open, cast} per pixel of the whole frames of N cameras, in one launch
+    (mirt_view_ao_batch).  seeds: int32 cuda [N * height * width * k * k], frame after frame, read and not written.  samples / bias left None
+    are MIRT_AO_DEFAULT_*."""
+    from . import mirt
+    cam = _batch_cameras(view, cameras, "view_ao_batch")
+    nf = cam.shape[0]
+    npix = nf * view.height * view.width
+    n = npix * view.k * view.k
+    if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.shape == (n,) and seeds.is_contiguous()):
+        raise ValueError(f"seeds: a contiguous int32 cuda tensor [{n}]")
+    if seeds.device.index != ctx.device:
+        raise ValueError(f"seeds live on cuda:{seeds.device.index}, the context on device {ctx.device}")
+    ao = torch.empty((nf, view.height, view.width, 2), dtype=torch.int32, device=seeds.device)
+    if nf:
+        with _OnTorchStream(ctx, seeds.device):
+            wrapped = [ctx.wrap(seeds.data_ptr(), n * 4), ctx.wrap(ao.data_ptr(), npix * 8)]
+            try:
+                ctx.view_ao_batch(dev_scene.pass_desc(None, None), view, cam, wrapped[0], wrapped[1], samples=mirt.AO_DEFAULT_SAMPLES if samples is None else samples,
+                                  radius=radius, bias=mirt.AO_DEFAULT_BIAS if bias is None else bias)
+            finally:
+                for b in wrapped:
+                    b.release()
+    return ao
+
+
+def render_views(ctx, dev_scene, view, cameras, seeds, bounces=5, accumulate_into=None, want_pixel=False, want_guides=False):
+    """-> radiance [N, height, width, 4] float32 cuda, or (radiance, pixel [N, height, width, 4] uint8) with want_pixel: the whole frames of N
+    cameras that share everything of `view` but the basis, in one launch (mirt_render_view_batch).  want_guides: the frames' first-hit guides
+    too (mirt_render_view_guided_batch) -- the result ends with normal_hits and albedo_depth, float32 [N, height, width, 4] each.  cameras: anything np.asarray(..., float32)
+    turns into [N, 12] -- eye, right, up, forward per frame; a cuda tensor is brought to the host (48 bytes a frame).  The call's ACCUMULATE flag
+    comes from accumulate_into (view.flags is neither read nor changed), a float32 cuda [N, height, width, 4] of sums to continue (written in place and returned).  seeds: int32 cuda
+    [N * height * width * k * k], frame after frame, advanced in place."""
+    from . import mirt
+    cam = _batch_cameras(view, cameras, "render_views")
     nf = cam.shape[0]
     npix = nf * view.height * view.width
     n = npix * view.k * view.k
@@ -230,17 +285,24 @@ def render_views(ctx, dev_scene, view, cameras, seeds, bounces=5, accumulate_int
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == shape and out.is_contiguous() and out.device == seeds.device):
         raise ValueError("accumulate_into: a contiguous float32 cuda tensor [N, height, width, 4] on the seeds' device")
     pixel = torch.empty(shape, dtype=torch.uint8, device=seeds.device) if want_pixel else None
+    guides = [torch.empty(shape, dtype=torch.float32, device=seeds.device) for _ in range(2)] if want_guides else []
     view = type(view).from_buffer_copy(view)   # the caller's descriptor keeps its flags
     view.flags = mirt.VIEW_ACCUMULATE if accumulate_into is not None else 0
     if nf:
         with _OnTorchStream(ctx, seeds.device):
             wrapped = [ctx.wrap(seeds.data_ptr(), n * 4), ctx.wrap(out.data_ptr(), npix * 16)] + ([ctx.wrap(pixel.data_ptr(), npix * 4)] if want_pixel else [])
+            gw = [ctx.wrap(g.data_ptr(), npix * 16) for g in guides]
             try:
-                ctx.render_view_batch(dev_scene.pass_desc(None, None, bounces=bounces), view, cam, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None)
+                desc = dev_scene.pass_desc(None, None, bounces=bounces)
+                if want_guides:
+                    ctx.render_view_guided_batch(desc, view, cam, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None, gw[0], gw[1])
+                else:
+                    ctx.render_view_batch(desc, view, cam, wrapped[0], wrapped[1], wrapped[2] if want_pixel else None)
             finally:
-                for b in wrapped:
+                for b in wrapped + gw:
                     b.release()
-    return (out, pixel) if want_pixel else out
+    result = (out,) + ((pixel,) if want_pixel else ()) + tuple(guides)
+    return result if len(result) > 1 else out
 
 
 def sh9_directions(width, height):
@@ -302,3 +364,22 @@ def probe_sh(ctx, dev_scene, positions, width=32, height=16, k=2, passes=1, boun
     m = (sh9_basis(width, height) * sh9_weights(width, height)[:, None] / (k * k * passes)).T   # [9, P], the pixel's scale folded in
     m = torch.from_numpy(np.ascontiguousarray(m.astype(np.float32))).to(device)
     return torch.matmul(m, sums.reshape(nf, height * width, 4)[:, :, :3])
+
+
+def probe_depth(ctx, dev_scene, positions, width=32, height=16, k=1):
+    """-> (mean_distance [N, height, width], hit_fraction [N, height, width]) float32 cuda: around each of the N positions ([N, 3]) the mean
+    distance to the first hit of a pixel's k * k samples -- the visibility term of an irradiance volume -- and the fraction of the samples that
+    hit.  N width x height EQUIRECT frames with probe_sh's unit basis (right = +x, up = +y, forward = -z), so depth is distance, in one launch
+    (view_guides_batch); mean_distance = depth_sum / hits where hits > 0 and +inf elsewhere, hit_fraction = hits / (k * k)."""
+    from . import mirt
+    if isinstance(positions, torch.Tensor):
+        positions = positions.detach().cpu().numpy()
+    pos = np.asarray(positions, np.float32).reshape(-1, 3)
+    cam = np.zeros((pos.shape[0], 12), np.float32)
+    cam[:, 0:3] = pos
+    cam[:, 3], cam[:, 7], cam[:, 11] = 1.0, 1.0, -1.0
+    view = mirt.view_desc(mirt.VIEW_EQUIRECT, width, height, k=k)
+    nh, ad = view_guides_batch(ctx, dev_scene, view, cam)
+    hits, depth = nh[..., 3], ad[..., 3]
+    mean = torch.where(hits > 0, depth / hits, torch.full_like(depth, float("inf")))
+    return mean, hits / float(k * k)

@@ -462,8 +462,8 @@ MIRT_API int mirt_view_deferred(mirt_ctx* ctx, uint64_t* rays);
  * KERNELS: k_viewRaysBatch and k_viewPassBatch (csrc/pt_kernels_view_batch.hip: the text of k_viewRays and k_viewPass, csrc/pt_view_kernels.inc,
  * with the compile-time flag BATCH set, in a translation unit of their own) -- the stacked frames are one image of n_frames * height
  * rows to them; a lane takes its frame from its row and loads that camera from the table (csrc/pt_view.hpp).  The single calls keep their code.
- * NOT BUILT: batched guides and ambient occlusion (view_ray is shared with k_viewGuides and k_viewAo, so they can follow); row tiles of a batch;
- * frames that differ in model, size or k; cameras in device memory; graph capture.
+ * The batch's guides and ambient occlusion: mirt_view_guides_batch, mirt_render_view_guided_batch, mirt_view_ao_batch, below.
+ * NOT BUILT: row tiles of a batch; frames that differ in model, size or k; cameras in device memory; graph capture.
  * MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
 typedef struct mirt_view_camera { float eye[3], right[3], up[3], forward[3]; } mirt_view_camera;   /* 48 bytes */
 MIRT_API int mirt_view_rays_batch(mirt_ctx* ctx, const mirt_view_desc* view, const mirt_view_camera* cameras, uint32_t n_frames, mirt_buf* rays);
@@ -573,6 +573,37 @@ MIRT_API int mirt_ao_deferred(mirt_ctx* ctx, uint64_t* pixels);
  * launch, graph capture.  MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
 MIRT_API int mirt_view_ao(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, const mirt_ao_desc* ao, mirt_buf* seeds, mirt_buf* ao_out);
 MIRT_API int mirt_view_ao_deferred(mirt_ctx* ctx, uint64_t* pixels);
+/* GUIDES AND AMBIENT OCCLUSION OF THE BATCHED VIEW CAMERAS: what an irradiance volume needs beside radiance per probe -- the distance to the
+ * first hit (the visibility term), normals and albedo, ambient occlusion -- for n_frames cameras in ONE call and one launch (pair).
+ * DEFINITION, by composition, exactly as for mirt_render_view_batch.  R = width * height * k * k, P = width * height.  The buffers are n_frames
+ * frames back to back: frame f owns seeds [f * R, (f + 1) * R) and radiance, pixel, normal_hits, albedo_depth and ao_out [f * P, (f + 1) * P).
+ * Frame f ends, bit for bit in every buffer the caller passes, as after the single call -- mirt_view_guides, mirt_render_view_guided,
+ * mirt_view_ao -- on buffers holding just that slice, with a descriptor equal to *view but eye / right / up / forward = cameras[f].  Both
+ * libraries give this against their own single calls.  view->eye / right / up / forward are neither read nor checked.  AO seeds are read and
+ * never written.  In the guided call MIRT_VIEW_ACCUMULATE, tone and the dead FISHEYE samples behave as in the single call.
+ * CHECKS, all before anything is queued; nothing is written when one fails, and the context works afterwards.  First the batch's, in
+ * mirt_render_view_batch's order: whole frames only, n_frames * R <= 2^32 - 256, cameras NULL with n_frames > 0, a non-finite camera component
+ * (the message names the frame).  Then the single call's own, in its order: both guides NULL; the AO descriptor's rules, NULL seeds, NULL
+ * ao_out; for the guided call the frame's rules and then both guides NULL.  The overlap rules are the single calls', on the whole batch
+ * buffers.  MIRT_E_RANGE: a buffer shorter than n_frames frames.  MIRT_E_DATA, MIRT_E_HANDLE and a call while capturing as in the single calls.
+ * n_frames == 0 is MIRT_OK and queues nothing.
+ * COUNTERS.  mirt_view_ao_deferred reports the last mirt_view_ao_batch as it reports mirt_view_ao (pixels); mirt_view_deferred the guided batch
+ * as the plain batch; mirt_ctx_guided_views counts a guided batch call that took the one-launch route once.
+ * KERNELS (csrc/pt_kernels_view_batch.hip): k_viewGuidesBatch and k_viewAoBatch, the text of k_viewGuides and k_viewAo
+ * (csrc/pt_view_aov_kernels.inc) with the camera from the table -- one lane and one mask bit per pixel of the image of n_frames * height rows,
+ * the optimistic / exact pair PER PIXEL.  The guided call's ROUTE is mirt_render_view_guided's: k_viewPassBatch writes the guides itself at
+ * k = 1, 2, 4 or 8; at k = 16 and under MIRT_GUIDED_VIEW=0 the call queues the plain batch's launches and then the guide batch's.  The outputs
+ * are final in stream order, as documented there.
+ * NOT BUILT: row tiles of a batch; frames that differ in model, size or k; cameras in device memory; a one-launch guided route at k = 16; AO
+ * folded into the frame's launch; filtering a batch (the a-trous filter would have to stop at frame borders); graph capture.
+ * MIRT_ABI_VERSION is unchanged: a host detects the entry points by their symbols. */
+MIRT_API int mirt_view_guides_batch(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, const mirt_view_camera* cameras,
+                                    uint32_t n_frames, mirt_buf* normal_hits, mirt_buf* albedo_depth);
+MIRT_API int mirt_render_view_guided_batch(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, const mirt_view_camera* cameras,
+                                           uint32_t n_frames, mirt_buf* seeds, mirt_buf* radiance, mirt_buf* pixel, mirt_buf* normal_hits,
+                                           mirt_buf* albedo_depth);
+MIRT_API int mirt_view_ao_batch(mirt_ctx* ctx, const mirt_pass_desc* scene, const mirt_view_desc* view, const mirt_view_camera* cameras,
+                                uint32_t n_frames, const mirt_ao_desc* ao, mirt_buf* seeds, mirt_buf* ao_out);
 /* Edge-avoiding A-TROUS FILTER of a few-rays-per-pixel frame, guided by the first-hit guide buffers: `radiance` as a pass writes it (un-scaled
  * sums), `normal_hits` and `albedo_depth` as mirt_render_guides writes them, all float4 per pixel of a width x height image -- a whole frame, or a
  * gathered one.  Everything stays on the device; the working images live in the context's scratch buffer.
